@@ -384,6 +384,22 @@ def measured_traffic(which, n_reads, kernel):
                                                         "breakdown_bytes", "memory_side_requests_per_read", "count_pass_us_per_launch_rocprofv3")}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """What the timed path's last step left on the device, as DIR/<name><suffix>.npy in float64 (every counter and histogram bin is an
+    integer below 2**53: exact).  Copied to the host outside the timed region."""
+    host = {name: t.detach().cpu().numpy().astype(np.float64) for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+    log(f"[bench] outputs of the last timed step -> {dirname}: " + ", ".join(f"{n}{suffix}.npy {a.shape}" for n, a in host.items()))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script, one per GPU, BEFORE anything in
     this process touches the GPU (the parent never does), and leave with the worst exit code."""
@@ -437,6 +453,9 @@ def main():
     ap.add_argument("--c4-samples", type=int, default=8)
     ap.add_argument("--c4-pairs", type=int, default=12_000_000, help="read pairs per sample (SURVEY 8: 30x of 60 Mb = 12 M pairs)")
     ap.add_argument("--c4-threads", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed (per-k-mer counters, per-node counters, "
+                         "coverage histogram) as DIR/<name>.npy (float64) -- for comparing two builds output for output")
     ap.add_argument("--budget-s", type=float, default=480.0,
                     help="wall clock for the whole command: a leg whose estimate does not fit what is left is skipped ({'skipped': 'budget'}), the headline never")
     args = ap.parse_args()
@@ -580,7 +599,7 @@ def main():
         """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.  A timed
         region shorter than `min_seconds` (the caller's --steps of a 5 ms step) is never the whole measurement: the K-step
         region is then repeated and the reported time is the mean over the repeats -- still K steps' worth, each repeat
-        bracketed the same way."""
+        bracketed the same way.  min_seconds=0: one K-step region, no repeats."""
         c = on_ctx or ctx
         for _ in range(warmup):
             step()
@@ -694,8 +713,11 @@ def main():
             vdist.allreduce_counts(ctx, dist, comm_dev, ctx_device=ctx_dev)
         ctx.counts_finish_device(d_cov, d_cov_node, d_hist)
 
-    elapsed, kernel_ms = timed(step, args.steps, args.warmup)
+    # the headline: exactly --steps timed steps (one region, never repeated), so that ms_per_step is what one step of that region took
+    elapsed, kernel_ms = timed(step, args.steps, args.warmup, min_seconds=0.0)
     c2_repeats = timed.repeats
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cov": d_cov, "cov_node": d_cov_node, "hist": d_hist}, "" if rank == 0 else f"_rank{rank}")
     kernel_ms_ranks = per_rank(kernel_ms)
     cov_sum = int(d_cov.to(torch.int64).sum().item())
     hist = d_hist.cpu().numpy()
@@ -746,8 +768,8 @@ def main():
             "value": value, "unit": "reads/s", "n_gpus": world, "world_size": dist.get_world_size() if dist else 1,
             "steps": args.steps, "warmup": args.warmup,
             "timed_region": {"repeats_of_the_k_step_region": c2_repeats, "seconds_in_all": elapsed * c2_repeats,
-                             "note": "a K-step region shorter than 1 s is repeated (each repeat bracketed by barrier + "
-                                     "synchronize) and ms_per_step is the mean over the repeats"},
+                             "note": "exactly --steps timed steps in one region bracketed by barrier + synchronize; "
+                                     "ms_per_step is that region's time over --steps"},
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if shard else "weak",
             "vs_baseline": None, "dtype": "u64", "data": "synthetic",
             "config": {"workload": "C2: 1 Mb ref + 1 k SNP graph (15 haplotypes, 53 734 k-mers), "

@@ -99,3 +99,21 @@ def test_committed_traffic_files_follow_from_the_committed_rocprofv3_summaries(w
     assert abs(want["count_pass_us_per_launch_rocprofv3"] / 1e3 - live_ms) / live_ms < 0.2, (want["count_pass_us_per_launch_rocprofv3"], live_ms)
     traffic = {"c2": line["roofline"]["traffic"], "c3": line["c3"]["roofline"]["traffic"], "c5": line["c5"]["roofline"]["traffic"], "bloom": line["bloom"]["roofline"]["traffic"]}[which]
     assert traffic == want["bytes_per_launch"]
+
+
+def test_dump_outputs_writes_exact_float64_arrays_within_the_limit(bench, tmp_path, monkeypatch):
+    """--dump-outputs: every array the timed path hands back, as <name>.npy in float64, values unchanged; more than the limit is refused."""
+    import torch
+    cov = torch.tensor([0, 1, 255, 7], dtype=torch.uint8)
+    hist = torch.tensor([3, 0, 2 ** 40], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "out"), {"cov": cov, "hist": hist})
+    assert sorted(os.listdir(tmp_path / "out")) == ["cov.npy", "hist.npy"]
+    got = np.load(tmp_path / "out" / "cov.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, cov.numpy().astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "out" / "hist.npy"), hist.numpy().astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "out"), {"cov": cov}, "_rank1")
+    assert (tmp_path / "out" / "cov_rank1.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 4 - 1)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "big"), {"cov": cov})
+    assert not (tmp_path / "big").exists()
