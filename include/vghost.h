@@ -77,6 +77,10 @@ int64_t vgh_fastx_read_all(const char *path, char **block_out, size_t *n_bytes_o
  * "gzip" or "bgzf": how the bytes were decoded (csrc/host/byte_source.hpp) */
 int64_t vgh_fastx_read_all_mt(const char *path, uint32_t decode_threads, char **block_out, size_t *n_bytes_out,
                               uint64_t *read_base, char source_kind[8]);
+/* A BAM / unaligned BAM file through the host decoder (csrc/host/bam_reader.hpp): the same block of its reads (flag & 0x900 == 0,
+ * l_seq > 0; SEQ decoded as stored).  Returns the number of reads, or <0 (vgh_last_error: "'<path>': not a valid BAM record at
+ * decompressed byte N (<what>)", or a file that is not BAM).  *read_base gets sum(l_seq). */
+int64_t vgh_bam_read_all(const char *path, uint32_t decode_threads, char **block_out, size_t *n_bytes_out, uint64_t *read_base);
 void vgh_free(void *p);
 /* CRC-32 (gzip polynomial) of the ingest decoder, csrc/host/fast_inflate.hpp (for tests) */
 uint32_t vgh_crc32(uint32_t crc, const void *data, size_t n);

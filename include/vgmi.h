@@ -198,6 +198,14 @@ int vgmi_fastq_bgzf_want(vgmi_fastq *fq, size_t *comp_bytes);
  *   not_bgzf  the bytes at `taken` are not a block-gzip member (plain gzip member, damage): the device path ends there
  * replaces: gzread's inflate under kseq (include/kseq.h:59-72, src/fastq_kmer.cpp:74-78). */
 int vgmi_fastq_commit_bgzf(vgmi_fastq *fq, size_t n_bytes, size_t *taken, size_t *n_text, int *not_bgzf);
+/* A BAM (or unaligned BAM) stream: block-gzip input as above, whose text is the BAM format instead of FASTQ (vgmi_bam.hip).
+ * header_bytes = bytes of the decompressed stream the header takes (magic, l_text, text, n_ref, the references), n_ref = its
+ * number of references; the host reads both (csrc/host/bam_reader.cpp).  Then acquire / commit_bgzf / bgzf_want / bgzf_status /
+ * close as for FASTQ; commit and commit_gzip are refused.  The reads are the records with flag & 0x900 == 0 and l_seq > 0, their
+ * 4-bit SEQ decoded as stored.  close: n_records / n_bases = those reads and their bases; consumed_bytes = a record boundary in the
+ * decompressed stream (header included); stopped != 0: the record there is not a valid BAM record, or is longer than the 1 MiB
+ * carry -- the host decoder takes the stream over at consumed_bytes. */
+int vgmi_fastq_open_bam(vgmi_ctx *ctx, uint64_t header_bytes, int32_t n_ref, vgmi_fastq **out);
 /* An ORDINARY gzip member (one DEFLATE stream: what `gzip` writes) inflated on the device, host memory to host memory: block starts are
  * guessed every 32 KiB of compressed bytes, the stretches between them decoded side by side with placeholders for the window each
  * cannot know, checked by having to end exactly where the next one starts, then resolved (vgmi_gunzip.hip; replaces zlib's inflate

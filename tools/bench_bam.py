@@ -1,0 +1,154 @@
+"""bench_bam.py -- a sample's reads through vgh_sample_count as unaligned BAM and as block-gzip FASTQ of the same reads, with the same
+member size (0xff00 bytes of text), in one process: reads/s of each, alternating, median of --reps.  Prints one JSON line.
+
+    python tools/bench_bam.py [--reads 20000000] [--reps 3] [--dir DIR] [--only bam|fastq]
+
+The reads are 150 bp drawn from the C1 cohort's haplotypes (tests/golden/c1) by the seeded generator; the BAM records are unmapped
+(flag 4, refID -1), named, with a quality string and no aux fields -- what a sequencer's uBAM holds."""
+import argparse
+import json
+import os
+import statistics
+import struct
+import sys
+import tempfile
+import time
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from varigraph_amd import host, synth, vgmi  # noqa: E402
+
+L = 150
+MEMBER = 0xff00
+PIECE = 1_000_000     # reads generated, laid out and compressed at a time
+NT16 = np.frombuffer(b"=ACMGRSVTWYHKDBN", dtype=np.uint8)
+EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def _member(d, level):
+    c = zlib.compressobj(level, zlib.DEFLATED, -15)
+    cd = c.compress(d) + c.flush()
+    return b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(cd) + 25) + cd + struct.pack("<II", zlib.crc32(d), len(d))
+
+
+class BgzfWriter:
+    """members of exactly MEMBER bytes of a continuous stream (records straddle them), compressed by threads (zlib drops the GIL)"""
+
+    def __init__(self, path, level, pool):
+        self.f, self.level, self.pool, self.carry = open(path, "wb"), level, pool, b""
+
+    def write(self, data):
+        data = self.carry + data
+        n = len(data) // MEMBER * MEMBER
+        self.carry = data[n:]
+        for m in self.pool.map(lambda o: _member(data[o:o + MEMBER], self.level), range(0, n, MEMBER)):
+            self.f.write(m)
+
+    def close(self):
+        if self.carry:
+            self.f.write(_member(self.carry, self.level))
+        self.f.write(EOF_BLOCK)
+        self.f.close()
+
+
+def _records(rows, first):
+    """fixed-layout uBAM records of the reads `rows` (n x 150 ASCII): name 'r%09d', no CIGAR, SEQ, QUAL 30, no aux"""
+    n = rows.shape[0]
+    name = 11
+    size = 4 + 32 + name + L // 2 + L
+    rec = np.zeros((n, size), dtype=np.uint8)
+    fixed = struct.pack("<iiiBBHHHiiii", size - 4, -1, -1, name, 0, 4680, 0, 4, L, -1, -1, 0)
+    rec[:, :36] = np.frombuffer(fixed, dtype=np.uint8)
+    idx = np.arange(first, first + n, dtype=np.int64)
+    rec[:, 36] = ord("r")
+    for d in range(9):
+        rec[:, 37 + d] = (idx // 10 ** (8 - d)) % 10 + ord("0")
+    code = np.zeros(256, dtype=np.uint8)
+    code[NT16] = np.arange(16, dtype=np.uint8)
+    c = code[rows]
+    rec[:, 36 + name:36 + name + L // 2] = c[:, 0::2] << 4 | c[:, 1::2]
+    rec[:, 36 + name + L // 2:] = 30
+    return rec
+
+
+def _fastq(rows, first):
+    n = rows.shape[0]
+    m = np.empty((n, 12 + L + 3 + L + 1), dtype=np.uint8)
+    idx = np.arange(first, first + n, dtype=np.int64)
+    m[:, 0], m[:, 1] = ord("@"), ord("r")
+    for d in range(9):
+        m[:, 2 + d] = (idx // 10 ** (8 - d)) % 10 + ord("0")
+    m[:, 11] = 10
+    m[:, 12:12 + L] = rows
+    m[:, 12 + L], m[:, 13 + L], m[:, 14 + L] = 10, ord("+"), 10
+    m[:, 15 + L:15 + 2 * L] = ord("?")
+    m[:, 15 + 2 * L] = 10
+    return m
+
+
+def make_files(d, n_reads, haps, level):
+    bam, fq = os.path.join(d, "reads.bam"), os.path.join(d, "reads.fq.gz")
+    with ThreadPoolExecutor(16) as pool:
+        wb, wf = BgzfWriter(bam, level, pool), BgzfWriter(fq, level, pool)
+        text = b"@HD\tVN:1.6\tSO:unknown\n@RG\tID:bench\tSM:sample0\n"
+        wb.write(b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", 0))
+        for first in range(0, n_reads, PIECE):
+            n = min(PIECE, n_reads - first)
+            rows = vgmi.synth_reads_host(4242, first, n, L, haps).reshape(n, L + 1)[:, :L]
+            wb.write(_records(rows, first).tobytes())
+            wf.write(_fastq(rows, first).tobytes())
+        wb.close()
+        wf.close()
+    return bam, fq
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=20_000_000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--level", type=int, default=1)
+    ap.add_argument("--dir", default=None)
+    ap.add_argument("--only", choices=["bam", "fastq"], default=None)
+    a = ap.parse_args()
+    gdir = os.path.join(ROOT, "tests", "golden", "c1")
+    meta = json.load(open(os.path.join(gdir, "meta.json")))
+    ref = synth.make_reference(meta["ref_len"], seed=meta["ref_seed"])
+    variants, gts = synth.make_cohort(ref, meta["n_var"], n_samples=meta["n_samples"], ploidy=meta["ploidy"], seed=meta["cohort_seed"])
+    haps = synth.sample_haplotypes(ref, variants, gts, 0, meta["ploidy"])
+    tmp = tempfile.TemporaryDirectory(dir=a.dir)
+    t0 = time.perf_counter()
+    bam, fq = make_files(tmp.name, a.reads, haps, a.level)
+    t_make = time.perf_counter() - t0
+    g = host.Graph(os.path.join(gdir, "graph.bin.gz"))
+    ctx = vgmi.Context(0)
+    g.upload(ctx)
+    legs = {"bam": bam, "fastq": fq} if a.only is None else {a.only: bam if a.only == "bam" else fq}
+    rates, stats = {k: [] for k in legs}, {}
+    g.sample_count(ctx, [bam], threads=16, require_depth=False)      # warm-up: code objects, pinned buffers
+    for _ in range(a.reps):
+        for k, p in legs.items():
+            t = time.perf_counter()
+            cov, _, hist, st = g.sample_count(ctx, [p], threads=16, require_depth=False)
+            dt = time.perf_counter() - t
+            rates[k].append(st["n_reads"] / dt)
+            stats[k] = (st["n_reads"], st["read_base"], hist.tobytes())
+    if len(stats) == 2:
+        assert stats["bam"] == stats["fastq"], "BAM and FASTQ legs count differently"
+    out = {"tool": "bench_bam", "reads": a.reads, "read_len": L, "member_text_bytes": MEMBER, "level": a.level,
+           "bytes": {k: os.path.getsize(p) for k, p in (("bam", bam), ("fastq", fq))}, "make_s": round(t_make, 1),
+           "reads_per_s": {k: float("%.4g" % statistics.median(v)) for k, v in rates.items()},
+           "runs": {k: ["%.4g" % x for x in v] for k, v in rates.items()}}
+    if len(stats) == 2:
+        out["bam_over_fastq"] = round(out["reads_per_s"]["bam"] / out["reads_per_s"]["fastq"], 3)
+    print(json.dumps(out))
+    ctx.close()
+    g.close()
+    tmp.cleanup()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,137 @@
+#include "bam_reader.hpp"
+
+#include <cstring>
+#include <stdexcept>
+
+namespace vgh {
+
+namespace {
+uint32_t le32(const unsigned char* p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// bytes already taken from a source, then the rest of it
+class PrefixSource final : public ByteSource {
+public:
+    PrefixSource(std::vector<unsigned char> head, std::unique_ptr<ByteSource> rest) : head_(std::move(head)), rest_(std::move(rest)) {}
+    bool next_chunk(const unsigned char*& p, size_t& n) override
+    {
+        if (!head_done_) {
+            head_done_ = true;
+            if (!head_.empty()) {
+                p = head_.data();
+                n = head_.size();
+                return true;
+            }
+        }
+        return rest_->next_chunk(p, n);
+    }
+    const char* kind() const override { return rest_->kind(); }
+
+private:
+    std::vector<unsigned char> head_;
+    bool head_done_ = false;
+    std::unique_ptr<ByteSource> rest_;
+};
+}  // namespace
+
+std::unique_ptr<ByteSource> open_sniffed(const std::string& path, unsigned decode_threads, bool& is_bam)
+{
+    is_bam = false;
+    std::unique_ptr<ByteSource> src = ByteSource::open(path, decode_threads);
+    if (strcmp(src->kind(), "bgzf") != 0) return src;
+    std::vector<unsigned char> head;
+    const unsigned char* p = nullptr;
+    size_t n = 0;
+    while (head.size() < 4 && src->next_chunk(p, n)) head.insert(head.end(), p, p + n);
+    is_bam = head.size() >= 4 && memcmp(head.data(), "BAM\1", 4) == 0;
+    return std::make_unique<PrefixSource>(std::move(head), std::move(src));
+}
+
+void BamReader::bad(uint64_t at, const char* what) const
+{
+    throw std::runtime_error("'" + path_ + "': not a valid BAM record at decompressed byte " + std::to_string(at) + " (" + what + ")");
+}
+
+bool BamReader::fill(size_t n)
+{
+    while (buf_.size() - pos_ < n) {
+        if (pos_ && pos_ >= buf_.size() / 2) {
+            buf_.erase(buf_.begin(), buf_.begin() + (long)pos_);
+            pos_ = 0;
+        }
+        const unsigned char* p = nullptr;
+        size_t m = 0;
+        if (!src_->next_chunk(p, m)) return false;
+        buf_.insert(buf_.end(), p, p + m);
+    }
+    return true;
+}
+
+BamReader::BamReader(std::unique_ptr<ByteSource> src, const std::string& path) : src_(std::move(src)), path_(path)
+{
+    // magic, l_text, text, n_ref, then per reference l_name, name, l_ref
+    uint64_t need = 8;
+    if (!fill(need)) bad(buf_.size(), "truncated header");
+    if (memcmp(buf_.data(), "BAM\1", 4) != 0) bad(0, "no BAM magic");
+    const int32_t l_text = (int32_t)le32(buf_.data() + 4);
+    if (l_text < 0) bad(4, "negative l_text");
+    need += (uint64_t)l_text + 4;
+    if (!fill(need)) bad(buf_.size(), "truncated header");
+    n_ref_ = (int32_t)le32(buf_.data() + need - 4);
+    if (n_ref_ < 0) bad(need - 4, "negative n_ref");
+    // the references are read a piece at a time: the header may be large, the buffer only holds what is needed
+    off_ = need;
+    pos_ = need;
+    for (int32_t r = 0; r < n_ref_; ++r) {
+        if (!fill(4)) bad(off_ + (buf_.size() - pos_), "truncated header");
+        const int32_t l_name = (int32_t)le32(buf_.data() + pos_);
+        if (l_name < 0) bad(off_, "negative l_name");
+        if (!fill(8 + (size_t)l_name)) bad(off_ + (buf_.size() - pos_), "truncated header");
+        pos_ += 8 + (size_t)l_name;
+        off_ += 8 + (uint64_t)l_name;
+    }
+    header_bytes_ = off_;
+}
+
+void BamReader::skip_to(uint64_t offset)
+{
+    while (off_ < offset) {
+        if (pos_ == buf_.size()) {
+            buf_.clear();
+            pos_ = 0;
+            if (!fill(1)) return;
+        }
+        const size_t d = (size_t)std::min<uint64_t>(offset - off_, buf_.size() - pos_);
+        pos_ += d;
+        off_ += d;
+    }
+}
+
+long BamReader::next()
+{
+    static const char nt16[] = "=ACMGRSVTWYHKDBN";
+    for (;;) {
+        if (!fill(1)) return -1;
+        const uint64_t at = off_;
+        if (!fill(4)) bad(at, "block_size runs past the end of the data");
+        const uint32_t bs = le32(buf_.data() + pos_);
+        if (!fill(4 + (size_t)bs)) bad(at, "block_size runs past the end of the data");
+        const unsigned char* r = buf_.data() + pos_;
+        if (bs < 32) bad(at, "fixed fields longer than block_size");
+        const int32_t ref = (int32_t)le32(r + 4), next_ref = (int32_t)le32(r + 24);
+        if (ref < -1 || ref >= n_ref_) bad(at, "refID out of range");
+        if (next_ref < -1 || next_ref >= n_ref_) bad(at, "next_refID out of range");
+        const uint32_t l_rn = r[12], n_cig = r[16] | (uint32_t)r[17] << 8, flag = r[18] | (uint32_t)r[19] << 8, l_seq = le32(r + 20);
+        if (l_rn == 0) bad(at, "l_read_name is 0");
+        if (32ull + l_rn + 4ull * n_cig + (l_seq + 1ull) / 2 + l_seq > bs) bad(at, "fields longer than block_size");
+        if (r[36 + l_rn - 1] != 0) bad(at, "read name not NUL-terminated");
+        pos_ += 4 + (size_t)bs;
+        off_ += 4 + (uint64_t)bs;
+        if ((flag & 0x900u) || l_seq == 0) continue;
+        const unsigned char* s = r + 36 + l_rn + 4 * (size_t)n_cig;
+        seq_.resize(l_seq);
+        for (uint32_t i = 0; i < l_seq; ++i) seq_[i] = nt16[(s[i >> 1] >> ((~i & 1) << 2)) & 15];
+        return (long)l_seq;
+    }
+}
+
+}  // namespace vgh

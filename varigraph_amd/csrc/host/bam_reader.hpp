@@ -1,0 +1,48 @@
+// bam_reader.hpp -- the reads of a BAM / unaligned BAM file (SAM spec 4.2) over a ByteSource: the host decoder of the BAM stream
+// (vgmi_fastq_open_bam).  It takes the stream where the device cannot (a record it stops at, a damaged member, a pipe), it is the
+// reader of the host-parse path (even k), and it is the yardstick of the device kernels (vgmi_bam.hip).
+//   reads     records with flag & 0x900 == 0 (no secondary, no supplementary alignment) and l_seq > 0 -- what `samtools fastq`
+//             writes by default; QC-fail, duplicate and unmapped records are reads too
+//   sequence  the 4-bit SEQ field through "=ACMGRSVTWYHKDBN", as stored (no reverse complement: the k-mers are canonical)
+// A record that is not valid throws "'<path>': not a valid BAM record at decompressed byte N (<what>)", N = its first byte.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "byte_source.hpp"
+
+namespace vgh {
+
+class BamReader {
+public:
+    // reads and checks the header
+    BamReader(std::unique_ptr<ByteSource> src, const std::string& path);
+    uint64_t header_bytes() const { return header_bytes_; }   // magic .. the last reference, in decompressed bytes
+    int32_t n_ref() const { return n_ref_; }
+    // passes over the stream up to decompressed byte `offset` (a record boundary at or behind the current position)
+    void skip_to(uint64_t offset);
+
+    // >= 0: sequence length (seq() holds it); -1: end of the data
+    long next();
+    const std::string& seq() const { return seq_; }
+
+private:
+    bool fill(size_t n);   // at least n bytes buffered; false if the data ends first
+    [[noreturn]] void bad(uint64_t at, const char* what) const;
+
+    std::unique_ptr<ByteSource> src_;
+    std::string path_;
+    std::vector<unsigned char> buf_;
+    size_t pos_ = 0;        // buf_[pos_] is decompressed byte off_
+    uint64_t off_ = 0;
+    uint64_t header_bytes_ = 0;
+    int32_t n_ref_ = 0;
+    std::string seq_;
+};
+
+// the bytes of `path` as ByteSource::open delivers them; is_bam: block gzip whose text starts with "BAM\1" (decided from content)
+std::unique_ptr<ByteSource> open_sniffed(const std::string& path, unsigned decode_threads, bool& is_bam);
+
+}  // namespace vgh

@@ -16,6 +16,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "bam_reader.hpp"
 #include "fast_inflate.hpp"
 #include "fastx_reader.hpp"
 #include "vgmi.h"
@@ -56,8 +57,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         ch.full.push_back(std::move(b));
         ch.cv_full.notify_one();
     };
-    try {
-        FastxReader rd(path, decode_threads);
+    auto run = [&](auto& rd) {
         std::unique_ptr<Block> cur = grab();
         while (rd.next() >= 0) {  // stops at EOF (-1) and at the first truncated record (-2)
             const std::string& s = rd.seq();
@@ -79,6 +79,17 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
             std::lock_guard<std::mutex> lk(ch.mu);
             ch.free_list.push_back(std::move(cur));
         }
+    };
+    try {
+        bool is_bam = false;
+        std::unique_ptr<ByteSource> src = open_sniffed(path, decode_threads, is_bam);
+        if (is_bam) {
+            BamReader rd(std::move(src), path);
+            run(rd);
+        } else {
+            FastxReader rd(std::move(src));
+            run(rd);
+        }
     } catch (const std::exception& e) {
         std::lock_guard<std::mutex> lk(ch.mu);
         if (ch.error.empty()) ch.error = e.what();
@@ -90,9 +101,10 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
 
 // ---- device-side parsing (vgmi_fastq_*): the host moves file text, the device finds the records ----------------------
 
-// records of `rd` (from a record boundary on) through the host reader into read blocks and vgmi_reads_submit; the
-// context's host-block path is single-threaded, hence the mutex shared by the files of one sample
-void host_leg(vgmi_ctx* ctx, FastxReader& rd, const std::string& path, size_t block_bytes, std::mutex& submit_mu, uint64_t& n_reads,
+// records of `rd` (from a record boundary on; FastxReader or BamReader) through the host reader into read blocks and vgmi_reads_submit;
+// the context's host-block path is single-threaded, hence the mutex shared by the files of one sample
+template <class Reader>
+void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_bytes, std::mutex& submit_mu, uint64_t& n_reads,
               uint64_t& read_base)
 {
     std::vector<char> block;
@@ -188,8 +200,15 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     if (!S_ISREG(sb.st_mode)) {
         ::close(guard.fd);
         guard.fd = -1;
-        FastxReader rd(ByteSource::open(path, threads));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        bool is_bam = false;
+        std::unique_ptr<ByteSource> src = open_sniffed(path, threads, is_bam);   // (a BAM pipe: recognised from its first decoded bytes)
+        if (is_bam) {
+            BamReader rd(std::move(src), path);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        } else {
+            FastxReader rd(std::move(src));
+            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        }
         return res;
     }
 
@@ -198,8 +217,27 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     if (!plain) {
         unsigned char h[18] = {0};
         if (::pread(fd, h, 18, 0) == 18 && h[2] == 8 && h[3] == 4 && (h[10] | h[11] << 8) >= 6 && h[12] == 'B' && h[13] == 'C') bgzf = true;
-        const char* off = std::getenv("VGH_HOST_INFLATE");   // A/B: block gzip through the host's inflate workers
-        if (off && off[0] == '1') bgzf = false;
+    }
+    // block gzip whose text starts with "BAM\1": BAM records, found and decoded on the device; the host reads the header (its
+    // length and number of references) and decodes wherever the device stops
+    bool bam = false;
+    uint64_t bam_header = 0;
+    int32_t bam_n_ref = 0;
+    if (bgzf) {
+        std::unique_ptr<ByteSource> src = open_sniffed(path, 1, bam);
+        if (bam) {
+            BamReader hdr(std::move(src), path);
+            bam_header = hdr.header_bytes();
+            bam_n_ref = hdr.n_ref();
+        }
+    }
+    if (const char* off = std::getenv("VGH_HOST_INFLATE"); off && off[0] == '1' && bgzf) {   // A/B: block gzip through the host's inflate workers
+        bgzf = false;
+        if (bam) {
+            BamReader rd(ByteSource::open(path, threads), path);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+            return res;
+        }
     }
 
     // ordinary gzip: inflated on the device too (vgmi_gunzip.hip; VGH_DEVICE_GUNZIP=0: by the host's inflate threads, the A/B and
@@ -210,7 +248,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     bool gz_gave_up = false;
 
     vgmi_fastq* fq = nullptr;
-    if (vgmi_fastq_open(ctx, &fq) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+    if ((bam ? vgmi_fastq_open_bam(ctx, bam_header, bam_n_ref, &fq) : vgmi_fastq_open(ctx, &fq)) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
     uint64_t n_rec = 0, n_bases = 0, consumed = 0;
     int stopped = 0;
     std::vector<char> tail(1u << 20);
@@ -336,7 +374,15 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     // what the device did not take: the text after the last complete record (an unterminated last line, or nothing), or
     // -- once it met a record that is not a regular four-line one -- the rest of the stream from that record on; for
     // block gzip also the file from the first member the device did not take or could not vouch for
-    if (stopped || gz_gave_up) {       // (the host decodes the file from its start and passes over the text the device has counted)
+    if (bam) {
+        // the host decoder from the record the device stopped at, or the first it did not take (behind a damaged or missing member, or
+        // the front of a record the data ends inside): from the file's start, passing over the header and what the device counted
+        if (stopped || inflate_failed || comp_taken < file_size || tail_len) {
+            BamReader rd(ByteSource::open(path, threads), path);
+            rd.skip_to(consumed);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        }
+    } else if (stopped || gz_gave_up) {       // (the host decodes the file from its start and passes over the text the device has counted)
         FastxReader rd(ByteSource::skip(ByteSource::open(path, threads), consumed));
         host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
     } else if (bgzf && (inflate_failed ? comp_good : comp_taken) < file_size) {

@@ -60,6 +60,7 @@ void usage(const char* argv0)
               << "Perform genotyping based on k-mer counting (MI355X build).\n\n"
               << "    --load-graph    FILE   Genome Graph index written by `varigraph construct` [graph.bin]\n"
               << "    -s, --sample    FILE   samples configuration: sample read1.fq.gz [read2.fq.gz ...] per line\n"
+              << "                           (FASTQ / FASTA, plain, gzip or block gzip, or BAM / unaligned BAM)\n"
               << "    -g, --genotype  STR    sample genome status, hom/het [het]\n"
               << "    --sample-ploidy INT    sample ploidy, 2-8 [2]\n"
               << "    -n, --number    INT    haploids used for genotyping [15]\n"

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <string>
 
+#include "bam_reader.hpp"
 #include "fastq_kmer_hip.hpp"
 #include "fast_inflate.hpp"
 #include "fastx_reader.hpp"
@@ -129,6 +130,36 @@ int64_t vgh_fastx_read_all_mt(const char* path, uint32_t decode_threads, char** 
             block.append(s.data(), strnlen(s.data(), s.size()));
             block.push_back('\n');
             rb += s.size();
+            ++n;
+        }
+        char* p = static_cast<char*>(malloc(block.size() ? block.size() : 1));
+        if (!p) return VGMI_E_NOMEM;
+        memcpy(p, block.data(), block.size());
+        *block_out = p;
+        *n_bytes_out = block.size();
+        if (read_base) *read_base = rb;
+        return n;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return VGMI_E_INVALID;
+    }
+}
+
+int64_t vgh_bam_read_all(const char* path, uint32_t decode_threads, char** block_out, size_t* n_bytes_out, uint64_t* read_base)
+{
+    if (!path || !block_out || !n_bytes_out) return VGMI_E_INVALID;
+    try {
+        bool is_bam = false;
+        std::unique_ptr<vgh::ByteSource> src = vgh::open_sniffed(path, decode_threads ? decode_threads : 1, is_bam);
+        if (!is_bam) throw std::runtime_error(std::string("'") + path + "': not a BAM file (block gzip starting with BAM\\1)");
+        vgh::BamReader rd(std::move(src), path);
+        std::string block;
+        int64_t n = 0;
+        uint64_t rb = 0;
+        while (rd.next() >= 0) {
+            block += rd.seq();
+            block.push_back('\n');
+            rb += rd.seq().size();
             ++n;
         }
         char* p = static_cast<char*>(malloc(block.size() ? block.size() : 1));

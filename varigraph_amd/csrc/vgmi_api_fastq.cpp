@@ -42,6 +42,11 @@ struct vgmi_fastq {
     uint64_t gz_text = 0;                            // text bytes the device produced
     std::vector<uint32_t> batch_members;             // members per committed batch
     std::vector<uint64_t> member_size;               // compressed size of every member committed, in stream order
+    // BAM records instead of FASTQ text (vgmi_fastq_open_bam; vgmi_bam.hip): its candidate arrays live in d_nlpos
+    bool bam = false;
+    int32_t n_ref = 0;
+    BamState* d_bam = nullptr;
+    uint8_t* d_mark = nullptr;
 };
 
 namespace {
@@ -58,7 +63,8 @@ extern "C++" void vgapi::fastq_free(vgmi_fastq* f)
         if (f->d_raw[i]) (void)hipFree(f->d_raw[i]);
     }
     for (void* p : {(void*)f->d_packed, (void*)f->d_tile, (void*)f->d_nlpos, (void*)f->d_rec, (void*)f->d_off, (void*)f->d_bsum,
-                    (void*)f->d_state, (void*)f->d_comp, (void*)f->d_members, (void*)f->d_status, (void*)f->d_crc, (void*)f->d_verdict})
+                    (void*)f->d_state, (void*)f->d_comp, (void*)f->d_members, (void*)f->d_status, (void*)f->d_crc, (void*)f->d_verdict,
+                    (void*)f->d_bam, (void*)f->d_mark})
         if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         if (f->h_members[i]) (void)hipHostFree(f->h_members[i]);
@@ -104,6 +110,7 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->gz_in_member = false;
             r->gz_bit = r->gz_avail = r->gz_skip = r->gz_reason = 0;
             r->gz_text = 0;
+            r->bam = false;
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -155,6 +162,28 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
     return VGMI_OK;
 }
 
+int vgmi_fastq_open_bam(vgmi_ctx* c, uint64_t header_bytes, int32_t n_ref, vgmi_fastq** out)
+{
+    if (!c || !out || n_ref < 0) return VGMI_E_INVALID;
+    int rc = vgmi_fastq_open(c, out);
+    if (rc) return rc;
+    vgmi_fastq* f = *out;
+    f->bam = true;
+    f->n_ref = n_ref;
+    hipError_t e = hipSuccess;
+    if (!f->d_bam) {
+        e = hipMalloc(reinterpret_cast<void**>(&f->d_bam), sizeof(BamState));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&f->d_mark), (size_t)f->cap_lines / 4 + 1);
+    }
+    if (e == hipSuccess) e = launch_bam_init(f->d_bam, header_bytes, f->stream);
+    if (e != hipSuccess) {
+        (void)vgmi_fastq_close(f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        *out = nullptr;
+        HIPCHK(c, e);
+    }
+    return VGMI_OK;
+}
+
 int vgmi_fastq_acquire(vgmi_fastq* f, char** host_buf, size_t* capacity)
 {
     if (!f || !host_buf || !capacity) return VGMI_E_INVALID;
@@ -197,6 +226,7 @@ int vgmi_fastq_commit(vgmi_fastq* f, size_t n_bytes)
     vgmi_ctx* c = f->c;
     if (f->acquired < 0) return fail(c, VGMI_E_STATE, "no buffer acquired");
     if (n_bytes > f->cap) return fail(c, VGMI_E_INVALID, "more bytes than the buffer holds");
+    if (f->bam) return fail(c, VGMI_E_STATE, "a BAM stream takes block gzip (vgmi_fastq_commit_bgzf)");
     const int i = f->acquired;
     f->acquired = -1;
     if (n_bytes == 0) return VGMI_OK;
@@ -362,7 +392,30 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
     b.state = f->d_state;
     b.cap_lines = f->cap_lines;
     b.tail_max = f->tail_max;
-    if (text) {
+    if (text && f->bam) {
+        BamBuffers bb{};
+        bb.raw = b.raw;
+        bb.raw_next = b.raw_next;
+        bb.packed = b.packed;
+        bb.tile = b.tile;
+        bb.cap_cand = f->cap_lines / 4;          // d_rec / d_off hold cap_lines / 4 + 1; d_nlpos holds the four arrays below
+        bb.cand = f->d_nlpos;
+        bb.j0 = bb.cand + bb.cap_cand;
+        bb.ja = bb.j0 + bb.cap_cand + 1;
+        bb.jb = bb.ja + bb.cap_cand + 1;
+        bb.mark = f->d_mark;
+        bb.rec_bytes = b.rec_bytes;
+        bb.out_off = b.out_off;
+        bb.block_sum = b.block_sum;
+        bb.state = b.state;
+        bb.bam = f->d_bam;
+        bb.tail_max = b.tail_max;
+        bb.n_ref = f->n_ref;
+        HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
+        int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + (size_t)text, nullptr, 0, f->stream,
+                              &f->d_state->packed_bytes);
+        if (rc) return rc;
+    } else if (text) {
         HIPCHK(c, launch_fastq_chunk(b, text, f->stream, &f->d_verdict->good_bytes));
         int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + (size_t)text, nullptr, 0, f->stream,
                               &f->d_state->packed_bytes);
@@ -640,6 +693,7 @@ int vgmi_fastq_commit_gzip(vgmi_fastq* f, size_t n_bytes, int at_eof, size_t* ta
     if (n_text) *n_text = 0;
     if (f->acquired < 0) return fail(c, VGMI_E_STATE, "no buffer acquired");
     if (n_bytes > f->cap) return fail(c, VGMI_E_INVALID, "more bytes than the buffer holds");
+    if (f->bam) return fail(c, VGMI_E_STATE, "a BAM stream takes block gzip (vgmi_fastq_commit_bgzf)");
     const int i = f->acquired;
     f->acquired = -1;
     HIPCHK(c, hipSetDevice(c->device));

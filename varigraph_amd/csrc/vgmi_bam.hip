@@ -1,0 +1,380 @@
+// vgmi_bam.hip -- BAM records on the device (gfx950): the reads of a BAM / unaligned BAM file, taken from the text the block-gzip
+// inflate kernel (vgmi_inflate.hip) has just written, into the same '\n'-joined read block the FASTQ parser writes.
+//
+// Which records are reads, and what a read is (the records `samtools fastq` writes by default; SAM spec 4.2):
+//   kept      flag & 0x900 == 0 (no secondary, no supplementary alignment) and l_seq > 0 (SEQ '*' has no bases: the
+//             reference aborts on an empty read, kmer.cpp:124)
+//   sequence  the l_seq bases of the 4-bit SEQ field, high nibble first, through "=ACMGRSVTWYHKDBN", as stored (a
+//             reverse-strand record adds the same canonical k-mers as its reverse complement)
+// A record is valid when its block_size stays inside the data, l_read_name >= 1 and the name's last byte is NUL,
+// 32 + l_read_name + 4 n_cigar_op + ceil(l_seq / 2) + l_seq <= block_size, and refID, next_refID lie in [-1, n_ref).
+// The first record that is not valid -- or is longer than the 1 MiB carry between chunks, wherever it lies -- stops the device for good, and the
+// host decoder (csrc/host/bam_reader.cpp, which names the fault) takes the stream over at that record's first byte.
+//
+// Records are a chain of length prefixes (next = off + 4 + block_size) that need not line up with anything else, and a serial
+// walk is one dependent load per record.  So, per chunk, all on one HIP stream:
+//   B0 the header bytes still to pass over ->
+//   B1 candidate test at every byte offset (all the checks above: they are local to the record) -> B2 scan of the per-tile
+//   counts -> B3 candidate offsets, in order ->
+//   B4 successor of every candidate (the candidate at off + 4 + block_size, or the terminal) ->
+//   B5 the chain from the chunk's first byte (a record boundary: the carried record, or the first byte behind the header):
+//   rounds of pointer doubling, round r marks the successors at distance 2^r of everything marked and squares the jump ->
+//   B6 l_seq + 1 of every kept record of the chain, B7 scan -> B8 4-bit decode, a wavefront per record ->
+//   B9 bookkeeping (records, bases, consumed bytes, tail; where the chain ends) -> B10 tail carried into the other raw buffer.
+// Offsets are absolute in the raw buffer (tail_max bytes of carry area, then the chunk), so they fit 32 bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vgmi_block_scan.h"
+#include "vgmi_kernels.h"
+
+namespace vgk {
+
+#define BAM_PIECES 4u                      // 16-byte pieces per thread in the byte-parallel kernels, 4 KiB apart (as vgmi_fastq.hip)
+#define BAM_TILE (4096u * BAM_PIECES)
+#define BAM_NONE 0xFFFFFFFFu
+#define BAM_GRID 2048u                     // workgroups of the candidate-parallel kernels (grid-stride)
+
+__device__ __forceinline__ uint32_t bam_end(uint32_t tail_max, uint32_t n_new, const uint32_t* n_new_dev)
+{
+    if (n_new_dev) {
+        const uint32_t d = *n_new_dev;
+        n_new = d < n_new ? d : n_new;
+    }
+    return tail_max + n_new;
+}
+
+// the little-endian dword at byte o of raw: two aligned loads (the raw buffer has slack behind the data) and a funnel shift
+__device__ __forceinline__ uint32_t bam_ld32(const uint8_t* raw, uint32_t o)
+{
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(raw + (o & ~3u));
+    return __builtin_amdgcn_alignbyte(w[1], w[0], o & 3u);
+}
+
+// the checks of the header comment on the fixed part of a record at o: 0 whole and valid so far (the name's NUL is the caller's),
+// 1 the data ends inside the record or its block_size, 2 whole but not a valid record
+__device__ __forceinline__ int bam_fixed(uint32_t o, uint32_t end, uint32_t bs, uint32_t ref, uint32_t l_rn, uint32_t n_cig, uint32_t l_seq,
+                                         uint32_t next_ref, int32_t n_ref)
+{
+    if (end - o < 4u || (unsigned long long)o + 4u + bs > end) return 1;
+    const bool ok = bs >= 32u && (int32_t)ref >= -1 && (int32_t)ref < n_ref && (int32_t)next_ref >= -1 && (int32_t)next_ref < n_ref &&
+                    l_rn >= 1u && 32ull + l_rn + 4ull * n_cig + (l_seq + 1ull) / 2u + l_seq <= bs;
+    return ok ? 0 : 2;
+}
+
+// the same from global memory (one thread): o < end
+__device__ int bam_check(const uint8_t* raw, uint32_t o, uint32_t end, int32_t n_ref, uint32_t* block_size)
+{
+    if (end - o < 4u) return 1;
+    const uint32_t bs = bam_ld32(raw, o);
+    *block_size = bs;
+    if ((unsigned long long)o + 4u + bs > end) return 1;
+    if (bs < 32u) return 2;
+    const uint32_t w16 = bam_ld32(raw, o + 16);
+    const uint32_t l_rn = raw[o + 12];
+    const int r = bam_fixed(o, end, bs, bam_ld32(raw, o + 4), l_rn, w16 & 0xFFFFu, bam_ld32(raw, o + 20), bam_ld32(raw, o + 24), n_ref);
+    if (r) return r;
+    return raw[o + 36 + l_rn - 1] == 0 ? 0 : 2;
+}
+
+// bit jj of the result: a whole, valid record no longer than the carry starts at off + jj (off 16-aligned, lo <= off + jj < end)
+__device__ __forceinline__ uint32_t bam_cand_mask(const uint8_t* raw, uint32_t off, uint32_t lo, uint32_t end, int32_t n_ref, uint32_t tail_max)
+{
+    uint32_t w[17];   // bytes off .. off + 63 (zeros behind the data) and a pad dword for the funnel shift
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+        const uint4 v = off + 16u * q < end ? *reinterpret_cast<const uint4*>(raw + off + 16u * q) : make_uint4(0u, 0u, 0u, 0u);
+        w[4 * q] = v.x;
+        w[4 * q + 1] = v.y;
+        w[4 * q + 2] = v.z;
+        w[4 * q + 3] = v.w;
+    }
+    w[16] = 0;
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t jj = 0; jj < 16; ++jj) {
+        const uint32_t o = off + jj;
+#define BAM_W(b) __builtin_amdgcn_alignbyte(w[((b) >> 2) + 1], w[(b) >> 2], (b) & 3u)
+        const uint32_t bs = BAM_W(jj), ref = BAM_W(jj + 4), w12 = BAM_W(jj + 12), w16 = BAM_W(jj + 16), l_seq = BAM_W(jj + 20),
+                       next_ref = BAM_W(jj + 24);
+#undef BAM_W
+        if (o >= lo && o < end && bs <= tail_max - 4u && bam_fixed(o, end, bs, ref, w12 & 0xFFu, w16 & 0xFFFFu, l_seq, next_ref, n_ref) == 0 &&
+            raw[o + 36 + (w12 & 0xFFu) - 1] == 0)
+            m |= 1u << jj;
+    }
+    return m;
+}
+
+// B0: the header (magic .. the last reference) is passed over, however many chunks it spans
+__global__ void bam_begin_kernel(FqState* st, BamState* bs, uint32_t tail_max, uint32_t n_new, const uint32_t* n_new_dev)
+{
+    if (threadIdx.x || blockIdx.x || st->stopped || !bs->hdr_left) return;
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    const unsigned long long avail = end - st->start;
+    const uint32_t skip = (uint32_t)(bs->hdr_left < avail ? bs->hdr_left : avail);
+    st->start += skip;
+    st->consumed += skip;
+    bs->hdr_left -= skip;
+}
+
+// B1: candidates per tile
+__global__ __launch_bounds__(256) void bam_count_kernel(const uint8_t* raw, const FqState* st, uint32_t tail_max, uint32_t n_new,
+                                                        const uint32_t* n_new_dev, int32_t n_ref, uint32_t* tile_cnt)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    const uint32_t start = st->start, off0 = blockIdx.x * BAM_TILE + threadIdx.x * 16u;
+    uint32_t n = 0;
+    if (!st->stopped) {
+#pragma unroll
+        for (uint32_t j = 0; j < BAM_PIECES; ++j) {
+            const uint32_t off = off0 + j * 4096u;
+            if (off < end && off + 16 > start) n += __popc(bam_cand_mask(raw, off, start, end, n_ref, tail_max));
+        }
+    }
+    const uint32_t t = block_reduce_add(n, sh);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = t;
+}
+
+// B3: candidate offsets in order (tile_base: B2's scan of B1's counts; its total is bs->n_cand)
+__global__ __launch_bounds__(256) void bam_cand_kernel(const uint8_t* raw, const FqState* st, const BamState* bs, uint32_t tail_max, uint32_t n_new,
+                                                       const uint32_t* n_new_dev, int32_t n_ref, const uint32_t* tile_base, uint32_t* cand,
+                                                       uint32_t cap)
+{
+    __shared__ uint32_t sh[4];
+    if (st->stopped || bs->n_cand > cap) return;   // (uniform) too many: nothing of this chunk is taken
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    const uint32_t start = st->start, off0 = blockIdx.x * BAM_TILE + threadIdx.x * 16u;
+    uint32_t base = tile_base[blockIdx.x];
+#pragma unroll
+    for (uint32_t j = 0; j < BAM_PIECES; ++j) {
+        const uint32_t off = off0 + j * 4096u;
+        uint32_t m = off < end && off + 16 > start ? bam_cand_mask(raw, off, start, end, n_ref, tail_max) : 0u;
+        uint32_t tot;
+        uint32_t pos = base + block_scan_excl(__popc(m), sh, &tot);
+        base += tot;
+        while (m) {
+            const uint32_t q = __builtin_ctz(m);
+            m &= m - 1;
+            cand[pos++] = off + q;
+        }
+    }
+}
+
+// B4: successor of every candidate; the terminal (index n) stands for "no candidate there" and leads to itself
+__global__ __launch_bounds__(256) void bam_link_kernel(const uint8_t* raw, const FqState* st, const BamState* bs, const uint32_t* cand,
+                                                       uint32_t* j0, uint8_t* mark, uint32_t cap)
+{
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) {
+        if (i == n) {
+            j0[n] = n;
+            mark[n] = 0;
+            continue;
+        }
+        const uint32_t o = cand[i];
+        const uint32_t nx = o + 4u + bam_ld32(raw, o);
+        // mostly the next candidate or one of the few behind it (a false candidate is rare); else a binary search
+        uint32_t lo = i + 1, hi = n, j = n;
+        for (uint32_t t = 0; t < 4 && lo < hi; ++t, ++lo) {
+            const uint32_t c = cand[lo];
+            if (c >= nx) {
+                hi = lo;
+                if (c == nx) j = lo;
+                break;
+            }
+        }
+        while (j == n && lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2, c = cand[mid];
+            if (c == nx) j = mid;
+            else if (c < nx) lo = mid + 1;
+            else hi = mid;
+        }
+        j0[i] = j;
+        mark[i] = i == 0 && o == st->start;
+    }
+}
+
+// B5 round r: everything marked marks its successor at distance 2^r (J = src), and dst = J o J.  After round r the nodes at
+// distance 0 .. 2^(r+1) - 1 from the start are marked; a node marked early in the same round only marks further chain nodes.
+__global__ __launch_bounds__(256) void bam_jump_kernel(const BamState* bs, const uint32_t* src, uint32_t* dst, uint8_t* mark, uint32_t r,
+                                                       uint32_t cap)
+{
+    const uint32_t n = bs->n_cand;
+    if (n > cap || (1ull << r) >= n) return;   // (uniform) the chain is at most n long
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) {
+        const uint32_t t = src[i];
+        dst[i] = src[t];
+        if (mark[i]) mark[t] = 1;
+    }
+}
+
+// B6: packed bytes of every kept record of the chain; the chain's last record (successor: the terminal)
+__global__ __launch_bounds__(256) void bam_keep_kernel(const uint8_t* raw, BamState* bs, const uint32_t* cand, const uint32_t* j0, const uint8_t* mark,
+                                                       uint32_t* rec_bytes, uint32_t cap)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    uint32_t kept = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint32_t b = 0;
+        if (mark[i]) {
+            const uint32_t o = cand[i];
+            const uint32_t flag = bam_ld32(raw, o + 16) >> 16, l_seq = bam_ld32(raw, o + 20);
+            if (!(flag & 0x900u) && l_seq) {
+                b = l_seq + 1;
+                ++kept;
+            }
+            if (j0[i] == n) bs->last = i;
+        }
+        rec_bytes[i] = b;
+    }
+    const uint32_t t = block_reduce_add(kept, sh);
+    if (threadIdx.x == 0 && t) atomicAdd(&bs->n_kept, t);
+}
+
+// B7: scan of rec_bytes: block sums (phase 0), then (after launch_scan_small over the sums) the offsets (phase 1)
+__global__ __launch_bounds__(1024) void bam_scan_blocks_kernel(const uint32_t* v, const BamState* bs, uint32_t* block_sum, uint32_t* out, int phase,
+                                                              uint32_t cap)
+{
+    __shared__ uint32_t sh[16];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    if (blockIdx.x * 1024u >= n) {      // (uniform) the launch is sized for the capacity
+        if (phase == 0 && threadIdx.x == 0) block_sum[blockIdx.x] = 0;
+        return;
+    }
+    const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+    uint32_t tot;
+    const uint32_t ex = block_scan_excl(i < n ? v[i] : 0u, sh, &tot);
+    if (phase == 0) {
+        if (threadIdx.x == 0) block_sum[blockIdx.x] = tot;
+    } else if (i < n) {
+        out[i] = block_sum[blockIdx.x] + ex;
+    }
+}
+
+// B8: 4-bit SEQ -> ASCII, a wavefront per kept record, two bases per lane and byte
+__global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* raw, const BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                                         const uint32_t* out_off, uint8_t* packed, uint32_t cap)
+{
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    const char* nt16 = "=ACMGRSVTWYHKDBN";
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t i = wave; i < n; i += n_waves) {
+        const uint32_t nb = rec_bytes[i];
+        if (!nb) continue;
+        const uint32_t o = cand[i], l_seq = nb - 1;
+        const uint32_t s = o + 36u + raw[o + 12] + 4u * (bam_ld32(raw, o + 16) & 0xFFFFu);
+        uint8_t* dst = packed + out_off[i];
+        for (uint32_t k = lane; 2 * k < l_seq; k += 64) {
+            const uint32_t b = raw[s + k];
+            dst[2 * k] = nt16[b >> 4];
+            if (2 * k + 1 < l_seq) dst[2 * k + 1] = nt16[b & 15u];
+        }
+        if (lane == 0) dst[l_seq] = '\n';
+    }
+}
+
+// B9: chunk bookkeeping (one thread)
+__global__ void bam_finish_kernel(const uint8_t* raw, FqState* st, const BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                  const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max, int32_t n_ref)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    uint32_t kept = 0, packed = 0, chain_end = st->start, tail = 0;
+    if (!st->stopped) {
+        const uint32_t n = bs->n_cand;
+        if (n > cap) {
+            st->stopped = 1;     // more candidates than the arrays hold: nothing of this chunk is taken, the host resumes at its first byte
+        } else {
+            if (bs->last != BAM_NONE) {
+                const uint32_t o = cand[bs->last];
+                chain_end = o + 4u + bam_ld32(raw, o);
+                kept = bs->n_kept;
+                packed = out_off[n - 1] + rec_bytes[n - 1];
+            }
+            if (chain_end < end) {
+                // what follows the chain: the front of a record the next chunk completes, or something the host must judge
+                uint32_t block_size = 0;
+                const int r = bam_check(raw, chain_end, end, n_ref, &block_size);
+                if (r == 1 && (end - chain_end < 4u || block_size <= tail_max - 4u)) tail = end - chain_end;
+                else st->stopped = 1;     // not a valid record, or one longer than the carry (whole or not: never a candidate)
+            }
+        }
+    }
+    st->n_good = kept;
+    st->packed_bytes = packed;
+    st->n_records += kept;
+    st->n_bases += packed - kept;
+    st->consumed += chain_end - st->start;
+    st->consumed_end = chain_end;
+    st->tail_len = tail;
+}
+
+// B10: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
+__global__ __launch_bounds__(256) void bam_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, BamState* bs, uint32_t tail_max)
+{
+    const uint32_t tail = st->tail_len, from = st->consumed_end;
+    for (uint32_t i = threadIdx.x; i < tail; i += blockDim.x) raw_next[tail_max - tail + i] = raw[from + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        st->start = tail_max - tail;
+        bs->n_cand = 0;
+        bs->last = BAM_NONE;
+        bs->n_kept = 0;
+    }
+}
+
+__global__ void bam_init_kernel(BamState* bs, unsigned long long header_bytes)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    *bs = BamState{};
+    bs->hdr_left = header_bytes;
+    bs->last = BAM_NONE;
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------
+hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(bam_init_kernel, dim3(1), dim3(1), 0, s, bs, header_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev)
+{
+    const uint32_t end = b.tail_max + n_new;
+    const uint32_t n_tiles = (end + BAM_TILE - 1) / BAM_TILE;
+    const uint32_t n_rblk = b.cap_cand / 1024u + 1;
+    const uint32_t grid = (b.cap_cand + 256u) / 256u < BAM_GRID ? (b.cap_cand + 256u) / 256u : BAM_GRID;
+    hipLaunchKernelGGL(bam_begin_kernel, dim3(1), dim3(1), 0, s, b.state, b.bam, b.tail_max, n_new, n_new_dev);
+    hipLaunchKernelGGL(bam_count_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.n_ref, b.tile);
+    hipError_t e = launch_scan_small(b.tile, n_tiles, &b.bam->n_cand, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bam_cand_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.bam, b.tail_max, n_new, n_new_dev, b.n_ref, b.tile, b.cand,
+                       b.cap_cand);
+    hipLaunchKernelGGL(bam_link_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.j0, b.mark, b.cap_cand);
+    // rounds while 2^r < n: ceil(log2(cap + 1)) launched, those beyond the chunk's candidates return at once
+    const uint32_t* src = b.j0;
+    for (uint32_t r = 0; (1ull << r) <= b.cap_cand; ++r) {
+        uint32_t* dst = src == b.ja ? b.jb : b.ja;
+        hipLaunchKernelGGL(bam_jump_kernel, dim3(grid), dim3(256), 0, s, b.bam, src, dst, b.mark, r, b.cap_cand);
+        src = dst;
+    }
+    hipLaunchKernelGGL(bam_keep_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
+    hipLaunchKernelGGL(bam_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.bam, b.block_sum, b.out_off, 0, b.cap_cand);
+    e = launch_scan_small(b.block_sum, n_rblk, nullptr, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bam_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.bam, b.block_sum, b.out_off, 1, b.cap_cand);
+    hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
+    hipLaunchKernelGGL(bam_finish_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_cand,
+                       b.tail_max, b.n_ref);
+    hipLaunchKernelGGL(bam_carry_kernel, dim3(1), dim3(256), 0, s, b.raw, b.raw_next, b.state, b.bam, b.tail_max);
+    return hipGetLastError();
+}
+
+}  // namespace vgk

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
 
 namespace vgk {
@@ -61,38 +62,6 @@ __device__ __forceinline__ uint32_t fq_valid_mask(uint32_t off, uint32_t lo, uin
     if (off < lo) m &= lo - off >= 16 ? 0u : (0xFFFFu << (lo - off));
     if (off + 16 > hi) m &= hi <= off ? 0u : (0xFFFFu >> (off + 16 - hi));
     return m & 0xFFFFu;
-}
-
-__device__ __forceinline__ uint32_t block_reduce_add(uint32_t v, uint32_t* sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (uint32_t i = 0; i < (blockDim.x >> 6); ++i) t += sh[i];
-    __syncthreads();
-    return t;
-}
-
-// exclusive prefix of v over the block's threads (blockDim.x <= 1024); *total = block sum
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* sh, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t n = __shfl_up(inc, o);
-        if (lane >= (uint32_t)o) inc += n;
-    }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (uint32_t i = 0; i < (blockDim.x >> 6); ++i) {
-        if (i < wave) base += sh[i];
-        tot += sh[i];
-    }
-    __syncthreads();
-    if (total) *total = tot;
-    return base + inc - v;
 }
 
 // K1: newlines per tile; '\r' / NUL bytes anywhere in the chunk make it dirty
@@ -310,6 +279,12 @@ __global__ void fq_init_kernel(FqState* st, uint32_t tail_max)
 hipError_t launch_fastq_init(FqState* st, uint32_t tail_max, hipStream_t s)
 {
     hipLaunchKernelGGL(fq_init_kernel, dim3(1), dim3(1), 0, s, st, tail_max);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_small(uint32_t* v, uint32_t n, uint32_t* total, hipStream_t s)
+{
+    hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, v, n, total);
     return hipGetLastError();
 }
 

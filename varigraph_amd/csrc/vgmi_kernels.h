@@ -131,6 +131,35 @@ hipError_t launch_fastq_init(FqState* st, uint32_t tail_max, hipStream_t s);
 // n_new_dev (may be null): the chunk is cut to min(n_new, *n_new_dev) bytes on the device (text in front of a block-gzip
 // member that did not inflate)
 hipError_t launch_fastq_chunk(const FqBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);
+// one workgroup's exclusive scan of v[0, n) in place (vgmi_fastq.hip); the sum goes to *total (may be null)
+hipError_t launch_scan_small(uint32_t* v, uint32_t n, uint32_t* total, hipStream_t s);
+
+// BAM records on the device (vgmi_bam.hip): the same FqState bookkeeping and packed block as the FASTQ parser
+struct BamState {                      // device-resident, one per open BAM stream
+    unsigned long long hdr_left;       // header bytes of the decompressed stream not yet passed over
+    uint32_t n_cand;                   // per chunk: offsets where a whole, valid record could start
+    uint32_t last;                     // per chunk: the last record of the chain from the chunk's start (BAM_NONE: none)
+    uint32_t n_kept;                   // per chunk: records of the chain that are read (flag & 0x900 == 0, l_seq > 0)
+    uint32_t pad;
+};
+struct BamBuffers {
+    const uint8_t* raw;                // tail_max bytes of carry area + the chunk
+    uint8_t* raw_next;                 // the other raw buffer (receives the tail)
+    uint8_t* packed;                   // '\n'-joined sequences
+    uint32_t* tile;                    // candidates per tile, then their base
+    uint32_t* cand;                    // cap_cand offsets, ascending
+    uint32_t *j0, *ja, *jb;            // cap_cand + 1 entries each: successor of every candidate, and two for its powers
+    uint8_t* mark;                     // cap_cand + 1: on the chain from the chunk's start
+    uint32_t* rec_bytes;               // cap_cand: l_seq + 1 of a kept record, 0 otherwise
+    uint32_t* out_off;                 // cap_cand: offset in the packed block
+    uint32_t* block_sum;               // scan scratch: cap_cand / 1024 + 2
+    FqState* state;
+    BamState* bam;
+    uint32_t cap_cand, tail_max;
+    int32_t n_ref;
+};
+hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s);
+hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);
 
 // block-gzip members inflated on the device (vgmi_inflate.hip)
 struct BgzfMember {

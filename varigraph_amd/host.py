@@ -54,6 +54,8 @@ def lib():
     l.vgh_fastx_read_all_mt.restype = C.c_int64
     l.vgh_fastx_read_all_mt.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                         C.c_char_p]
+    l.vgh_bam_read_all.restype = C.c_int64
+    l.vgh_bam_read_all.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
     l.vgh_free.restype = None; l.vgh_free.argtypes = [vp]
     l.vgh_sample_count.restype = C.c_int
     l.vgh_sample_count.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp,
@@ -253,6 +255,21 @@ def fastx_read_all(path, decode_threads=1, with_kind=False):
         l.vgh_free(p)
     if with_kind:
         return block, int(cnt), rb.value, kind.value.decode()
+    return block, int(cnt), rb.value
+
+
+def bam_read_all(path, decode_threads=1):
+    """The reads of a BAM / unaligned BAM file through the host decoder (csrc/host/bam_reader.hpp) as a '\\n'-joined block:
+    (block, n_reads, read_base).  A malformed record raises RuntimeError naming its decompressed byte."""
+    l = lib()
+    p, n, rb = C.c_void_p(), C.c_size_t(), C.c_uint64()
+    cnt = l.vgh_bam_read_all(os.fsencode(path), decode_threads, C.byref(p), C.byref(n), C.byref(rb))
+    if cnt < 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    try:
+        block = _arr(p.value, n.value, np.uint8)
+    finally:
+        l.vgh_free(p)
     return block, int(cnt), rb.value
 
 

@@ -65,6 +65,7 @@ def load_library():
         "vgmi_counts_export_device": (i32, [vp, vp]),
         "vgmi_counts_import_device": (i32, [vp, vp]),
         "vgmi_fastq_open": (i32, [vp, C.POINTER(vp)]),
+        "vgmi_fastq_open_bam": (i32, [vp, C.c_uint64, i32, C.POINTER(vp)]),
         "vgmi_fastq_acquire": (i32, [vp, C.POINTER(vp), C.POINTER(sz)]),
         "vgmi_fastq_text_capacity": (i32, [vp, C.POINTER(sz)]),
         "vgmi_fastq_commit": (i32, [vp, sz]),
@@ -324,6 +325,17 @@ class Context:
         good_compressed_bytes, taken (compressed bytes handed over as whole members)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        return self._bgzf_stream(fq, comp, piece)
+
+    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None):
+        """A BAM file's block-gzip bytes through the device inflate + BAM record kernels (vgmi_fastq_open_bam): header_bytes = the
+        header's length in the decompressed stream (magic to the last reference), n_ref its number of references.  Returns the dict of fastq_bgzf; consumed
+        counts decompressed bytes, header included."""
+        fq = C.c_void_p()
+        self._chk(self._l.vgmi_fastq_open_bam(self._h, header_bytes, n_ref, C.byref(fq)))
+        return self._bgzf_stream(fq, comp, piece)
+
+    def _bgzf_stream(self, fq, comp, piece):
         comp = bytes(comp)
         pos, carry, total_taken, n_call = 0, b"", 0, 0
         failed, good, reason = C.c_int(), C.c_uint64(), C.c_uint32()
