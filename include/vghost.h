@@ -81,6 +81,10 @@ int64_t vgh_fastx_read_all_mt(const char *path, uint32_t decode_threads, char **
  * l_seq > 0; SEQ decoded as stored).  Returns the number of reads, or <0 (vgh_last_error: "'<path>': not a valid BAM record at
  * decompressed byte N (<what>)", or a file that is not BAM).  *read_base gets sum(l_seq). */
 int64_t vgh_bam_read_all(const char *path, uint32_t decode_threads, char **block_out, size_t *n_bytes_out, uint64_t *read_base);
+/* What the device path of vgh_sample_count makes of an input file, from its first bytes (no device involved): kind = "plain" |
+ * "gzip" | "bgzf"; first_byte = the first byte of its text (-1: it has none); bam = block gzip whose text starts with "BAM\1";
+ * fasta = the text starts with '>' and goes to the device's FASTA parser (VGH_DEVICE_FASTA=0: never).  Any pointer may be NULL. */
+int vgh_sniff_input(const char *path, char kind[8], int *first_byte, int *bam, int *fasta);
 void vgh_free(void *p);
 /* CRC-32 (gzip polynomial) of the ingest decoder, csrc/host/fast_inflate.hpp (for tests) */
 uint32_t vgh_crc32(uint32_t crc, const void *data, size_t n);

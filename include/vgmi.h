@@ -206,6 +206,16 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq *fq, size_t n_bytes, size_t *taken, size_t
  * decompressed stream (header included); stopped != 0: the record there is not a valid BAM record, or is longer than the 1 MiB
  * carry -- the host decoder takes the stream over at consumed_bytes. */
 int vgmi_fastq_open_bam(vgmi_ctx *ctx, uint64_t header_bytes, int32_t n_ref, vgmi_fastq **out);
+/* A FASTA stream (vgmi_fasta.hip): text whose first byte is '>', single-line or wrapped.  acquire / commit / commit_bgzf /
+ * commit_gzip / the status calls / close as for FASTQ.  Line by line, as kseq_read does (include/kseq.h:208-215): a line that
+ * starts with '>' or '@' is a header line and starts a record, an empty line is skipped, any other line that does not start with
+ * '+' is a sequence line; a record's read is its sequence lines joined.  A record is complete when the next header line has been
+ * seen, so the LAST record of the text is never taken by the device: close returns it (from its header line on) as the unconsumed
+ * tail with stopped == 0, for the host reader.  close: n_records / n_bases = the records taken and their bases; stopped != 0:
+ * record number n_records has a line starting with '+' (FASTQ), has no sequence, or is longer than the 1 MiB carry (a contig, not
+ * a read), or its chunk holds a '\r' or NUL byte or does not start with a header line -- the host reader takes the stream over
+ * at consumed_bytes, the first byte of that record's header line.  Odd k, as vgmi_fastq_open. */
+int vgmi_fastq_open_fasta(vgmi_ctx *ctx, vgmi_fastq **out);
 /* An ORDINARY gzip member (one DEFLATE stream: what `gzip` writes) inflated on the device, host memory to host memory: block starts are
  * guessed every 32 KiB of compressed bytes, the stretches between them decoded side by side with placeholders for the window each
  * cannot know, checked by having to end exactly where the next one starts, then resolved (vgmi_gunzip.hip; replaces zlib's inflate

@@ -178,6 +178,36 @@ GunzipEnd host_gunzip_verdict(const std::string& path, uint64_t& n_text)
     return end;
 }
 
+}  // namespace
+
+InputSniff sniff_input(const std::string& path)
+{
+    InputSniff r;
+    const int fd = ::open(path.c_str(), O_RDONLY);
+    if (fd < 0) throw std::runtime_error("'" + path + "': No such file or directory.");
+    // plain or compressed?  (gzopen's transparent mode: anything that does not start with the gzip magic is plain)
+    unsigned char h[18] = {0};
+    const ssize_t got = ::pread(fd, h, 18, 0);
+    ::close(fd);
+    r.plain = !(got >= 2 && h[0] == 0x1f && h[1] == 0x8b);
+    // block gzip?  (the first member carries the 'BC' extra subfield: bgzip, htslib)
+    r.bgzf = !r.plain && got == 18 && h[2] == 8 && h[3] == 4 && (h[10] | h[11] << 8) >= 6 && h[12] == 'B' && h[13] == 'C';
+    if (r.plain) {
+        if (got >= 1) r.first_byte = h[0];
+    } else {
+        std::unique_ptr<ByteSource> src = open_sniffed(path, 1, r.bam);
+        const unsigned char* p = nullptr;
+        size_t n = 0;
+        while (src->next_chunk(p, n))
+            if (n) { r.first_byte = p[0]; break; }
+    }
+    const char* off = std::getenv("VGH_DEVICE_FASTA");
+    r.fasta = !r.bam && r.first_byte == '>' && !(off && off[0] == '0');
+    return r;
+}
+
+namespace {
+
 struct DeviceFileResult {
     uint64_t n_reads = 0, read_base = 0;
 };
@@ -185,12 +215,8 @@ struct DeviceFileResult {
 DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t block_bytes, unsigned threads, std::mutex& submit_mu)
 {
     DeviceFileResult res;
-    // plain or compressed?  (gzopen's transparent mode: anything that does not start with the gzip magic is plain)
     int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) throw std::runtime_error("'" + path + "': No such file or directory.");
-    unsigned char magic[2] = {0, 0};
-    const ssize_t got = ::pread(fd, magic, 2, 0);
-    const bool plain = !(got == 2 && magic[0] == 0x1f && magic[1] == 0x8b);
     struct stat sb;
     if (fstat(fd, &sb) != 0) { ::close(fd); throw std::runtime_error("'" + path + "': cannot stat"); }
     const uint64_t file_size = (uint64_t)sb.st_size;
@@ -212,24 +238,19 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         return res;
     }
 
-    // block gzip?  (the first member carries the 'BC' extra subfield: bgzip, htslib)
-    bool bgzf = false;
-    if (!plain) {
-        unsigned char h[18] = {0};
-        if (::pread(fd, h, 18, 0) == 18 && h[2] == 8 && h[3] == 4 && (h[10] | h[11] << 8) >= 6 && h[12] == 'B' && h[13] == 'C') bgzf = true;
-    }
+    // plain, gzip or block gzip; BAM, FASTA or FASTQ text: by the first bytes
+    const InputSniff sniff = sniff_input(path);
+    const bool plain = sniff.plain, bam = sniff.bam, fasta = sniff.fasta;
+    bool bgzf = sniff.bgzf;
     // block gzip whose text starts with "BAM\1": BAM records, found and decoded on the device; the host reads the header (its
     // length and number of references) and decodes wherever the device stops
-    bool bam = false;
     uint64_t bam_header = 0;
     int32_t bam_n_ref = 0;
-    if (bgzf) {
-        std::unique_ptr<ByteSource> src = open_sniffed(path, 1, bam);
-        if (bam) {
-            BamReader hdr(std::move(src), path);
-            bam_header = hdr.header_bytes();
-            bam_n_ref = hdr.n_ref();
-        }
+    if (bam) {
+        bool is_bam = false;
+        BamReader hdr(open_sniffed(path, 1, is_bam), path);
+        bam_header = hdr.header_bytes();
+        bam_n_ref = hdr.n_ref();
     }
     if (const char* off = std::getenv("VGH_HOST_INFLATE"); off && off[0] == '1' && bgzf) {   // A/B: block gzip through the host's inflate workers
         bgzf = false;
@@ -248,7 +269,9 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     bool gz_gave_up = false;
 
     vgmi_fastq* fq = nullptr;
-    if ((bam ? vgmi_fastq_open_bam(ctx, bam_header, bam_n_ref, &fq) : vgmi_fastq_open(ctx, &fq)) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+    // text whose first byte is '>': FASTA records, single-line or wrapped, joined on the device (vgmi_fasta.hip); the hand-over is the
+    // FASTQ stream's -- the last record, which only the end of the data completes, comes back as the tail
+    if ((bam ? vgmi_fastq_open_bam(ctx, bam_header, bam_n_ref, &fq) : fasta ? vgmi_fastq_open_fasta(ctx, &fq) : vgmi_fastq_open(ctx, &fq)) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
     uint64_t n_rec = 0, n_bases = 0, consumed = 0;
     int stopped = 0;
     std::vector<char> tail(1u << 20);

@@ -48,6 +48,16 @@ private:
     double kernel_s_ = 0;
 };
 
+// What the device path makes of an input file, decided from its first bytes alone (no device involved): the container by the
+// gzip magic and the 'BC' extra subfield of the first member, BAM by "BAM\1" at the start of a block-gzip file's text, FASTA by a
+// text whose first byte is '>' (vgmi_fastq_open_fasta; VGH_DEVICE_FASTA=0: the FASTQ-mode parser, which hands a FASTA stream to
+// the host reader at record 0).  first_byte: the text's first byte, -1 when it has none.  Throws like ByteSource::open.
+struct InputSniff {
+    bool plain = true, bgzf = false, bam = false, fasta = false;
+    int first_byte = -1;
+};
+InputSniff sniff_input(const std::string& path);
+
 // Coverage statistics that turn the counters into hapKmerCoverage_ (src/varigraph.cpp:198,220-243,
 // 308-362).  Returns false where the reference exits with "Failed to retrieve depth information".
 struct CoverageStats {

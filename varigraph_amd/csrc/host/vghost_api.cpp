@@ -175,6 +175,25 @@ int64_t vgh_bam_read_all(const char* path, uint32_t decode_threads, char** block
     }
 }
 
+int vgh_sniff_input(const char* path, char kind[8], int* first_byte, int* bam, int* fasta)
+{
+    if (!path) return VGMI_E_INVALID;
+    try {
+        const vgh::InputSniff r = vgh::sniff_input(path);
+        if (kind) {
+            memset(kind, 0, 8);
+            strncpy(kind, r.plain ? "plain" : r.bgzf ? "bgzf" : "gzip", 7);
+        }
+        if (first_byte) *first_byte = r.first_byte;
+        if (bam) *bam = r.bam;
+        if (fasta) *fasta = r.fasta;
+        return VGMI_OK;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return VGMI_E_INVALID;
+    }
+}
+
 int64_t vgh_fastx_read_all(const char* path, char** block_out, size_t* n_bytes_out, uint64_t* read_base)
 {
     return vgh_fastx_read_all_mt(path, 1, block_out, n_bytes_out, read_base, nullptr);

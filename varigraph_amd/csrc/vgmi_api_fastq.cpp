@@ -47,6 +47,9 @@ struct vgmi_fastq {
     int32_t n_ref = 0;
     BamState* d_bam = nullptr;
     uint8_t* d_mark = nullptr;
+    // FASTA text instead of FASTQ text (vgmi_fastq_open_fasta; vgmi_fasta.hip): its per-line and per-record arrays
+    bool fasta = false;
+    uint8_t* d_fa = nullptr;
 };
 
 namespace {
@@ -64,7 +67,7 @@ extern "C++" void vgapi::fastq_free(vgmi_fastq* f)
     }
     for (void* p : {(void*)f->d_packed, (void*)f->d_tile, (void*)f->d_nlpos, (void*)f->d_rec, (void*)f->d_off, (void*)f->d_bsum,
                     (void*)f->d_state, (void*)f->d_comp, (void*)f->d_members, (void*)f->d_status, (void*)f->d_crc, (void*)f->d_verdict,
-                    (void*)f->d_bam, (void*)f->d_mark})
+                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa})
         if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         if (f->h_members[i]) (void)hipHostFree(f->h_members[i]);
@@ -111,6 +114,7 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->gz_bit = r->gz_avail = r->gz_skip = r->gz_reason = 0;
             r->gz_text = 0;
             r->bam = false;
+            r->fasta = false;
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -184,6 +188,58 @@ int vgmi_fastq_open_bam(vgmi_ctx* c, uint64_t header_bytes, int32_t n_ref, vgmi_
     return VGMI_OK;
 }
 
+int vgmi_fastq_open_fasta(vgmi_ctx* c, vgmi_fastq** out)
+{
+    if (!c || !out) return VGMI_E_INVALID;
+    int rc = vgmi_fastq_open(c, out);
+    if (rc) return rc;
+    vgmi_fastq* f = *out;
+    f->fasta = true;
+    if (!f->d_fa) {
+        // total (16 bytes), the per-1024-line sums, the per-line offsets, the two per-record arrays (FaBuffers)
+        const size_t bytes = 16 + ((size_t)f->cap_lines / 1024 + 2) * 8 + ((size_t)f->cap_lines + 2) * 4 + (size_t)fasta_cap_rec(f->cap_lines) * 8;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_fa), bytes);
+        if (e != hipSuccess) {
+            (void)vgmi_fastq_close(f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+            *out = nullptr;
+            HIPCHK(c, e);
+        }
+    }
+    return VGMI_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the record parser of the stream's kind over the chunk in d_raw[i]: n_new bytes behind the carry area (cut to *n_new_dev if given)
+hipError_t parse_chunk(vgmi_fastq* f, int i, uint32_t n_new, const uint32_t* n_new_dev)
+{
+    FqBuffers b{};
+    b.raw = f->d_raw[i];
+    b.raw_next = f->d_raw[i ^ 1];
+    b.packed = f->d_packed;
+    b.tile = f->d_tile;
+    b.nlpos = f->d_nlpos;
+    b.rec_bytes = f->d_rec;
+    b.out_off = f->d_off;
+    b.block_sum = f->d_bsum;
+    b.state = f->d_state;
+    b.cap_lines = f->cap_lines;
+    b.tail_max = f->tail_max;
+    if (!f->fasta) return launch_fastq_chunk(b, n_new, f->stream, n_new_dev);
+    FaBuffers a{};
+    a.q = b;
+    a.total = reinterpret_cast<unsigned long long*>(f->d_fa);
+    a.bsum = a.total + 2;
+    a.dest = reinterpret_cast<uint32_t*>(a.bsum + ((size_t)f->cap_lines / 1024 + 2));
+    a.rec_d = a.dest + ((size_t)f->cap_lines + 2);
+    a.rec_pos = a.rec_d + fasta_cap_rec(f->cap_lines);
+    return launch_fasta_chunk(a, n_new, f->stream, n_new_dev);
+}
+}  // namespace
+
+extern "C" {
+
 int vgmi_fastq_acquire(vgmi_fastq* f, char** host_buf, size_t* capacity)
 {
     if (!f || !host_buf || !capacity) return VGMI_E_INVALID;
@@ -234,19 +290,7 @@ int vgmi_fastq_commit(vgmi_fastq* f, size_t n_bytes)
     HIPCHK(c, hipMemcpyAsync(f->d_raw[i] + f->tail_max, f->h_stage[i], n_bytes, hipMemcpyHostToDevice, f->stream));
     HIPCHK(c, hipEventRecord(f->h_done[i], f->stream));
     f->h_busy[i] = true;
-    FqBuffers b{};
-    b.raw = f->d_raw[i];
-    b.raw_next = f->d_raw[i ^ 1];
-    b.packed = f->d_packed;
-    b.tile = f->d_tile;
-    b.nlpos = f->d_nlpos;
-    b.rec_bytes = f->d_rec;
-    b.out_off = f->d_off;
-    b.block_sum = f->d_bsum;
-    b.state = f->d_state;
-    b.cap_lines = f->cap_lines;
-    b.tail_max = f->tail_max;
-    HIPCHK(c, launch_fastq_chunk(b, (uint32_t)n_bytes, f->stream));
+    HIPCHK(c, parse_chunk(f, i, (uint32_t)n_bytes, nullptr));
     // the read block's length is on the device: the count kernels fetch it (upper bound here: tail + chunk)
     int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + n_bytes, nullptr, 0, f->stream,
                           &f->d_state->packed_bytes);
@@ -416,7 +460,7 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
                               &f->d_state->packed_bytes);
         if (rc) return rc;
     } else if (text) {
-        HIPCHK(c, launch_fastq_chunk(b, text, f->stream, &f->d_verdict->good_bytes));
+        HIPCHK(c, parse_chunk(f, i, text, &f->d_verdict->good_bytes));
         int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + (size_t)text, nullptr, 0, f->stream,
                               &f->d_state->packed_bytes);
         if (rc) return rc;
@@ -795,19 +839,7 @@ int vgmi_fastq_commit_gzip(vgmi_fastq* f, size_t n_bytes, int at_eof, size_t* ta
     }
     if (n_text) *n_text = text_total;
     if (text_total) {
-        FqBuffers b{};
-        b.raw = f->d_raw[i];
-        b.raw_next = f->d_raw[i ^ 1];
-        b.packed = f->d_packed;
-        b.tile = f->d_tile;
-        b.nlpos = f->d_nlpos;
-        b.rec_bytes = f->d_rec;
-        b.out_off = f->d_off;
-        b.block_sum = f->d_bsum;
-        b.state = f->d_state;
-        b.cap_lines = f->cap_lines;
-        b.tail_max = f->tail_max;
-        HIPCHK(c, launch_fastq_chunk(b, (uint32_t)text_total, f->stream));
+        HIPCHK(c, parse_chunk(f, i, (uint32_t)text_total, nullptr));
         const int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + text_total, nullptr, 0, f->stream, &f->d_state->packed_bytes);
         if (rc) return rc;
         f->next = i ^ 1;

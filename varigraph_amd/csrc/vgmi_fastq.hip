@@ -288,6 +288,17 @@ hipError_t launch_scan_small(uint32_t* v, uint32_t n, uint32_t* total, hipStream
     return hipGetLastError();
 }
 
+// K1-K3 alone: st->n_lines, st->dirty and the newline positions of a chunk (the FASTA parser, vgmi_fasta.hip, starts from them)
+hipError_t launch_fastq_lines(const FqBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev)
+{
+    const uint32_t end = b.tail_max + n_new;
+    const uint32_t n_tiles = (end + FQ_TILE - 1) / FQ_TILE;
+    hipLaunchKernelGGL(fq_count_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.tile);
+    hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, b.tile, n_tiles, &b.state->n_lines);
+    hipLaunchKernelGGL(fq_nlpos_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.tile, b.nlpos, b.cap_lines);
+    return hipGetLastError();
+}
+
 hipError_t launch_fastq_chunk(const FqBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev)
 {
     const uint32_t end = b.tail_max + n_new;

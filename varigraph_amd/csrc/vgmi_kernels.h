@@ -134,6 +134,24 @@ hipError_t launch_fastq_chunk(const FqBuffers& b, uint32_t n_new, hipStream_t s,
 // one workgroup's exclusive scan of v[0, n) in place (vgmi_fastq.hip); the sum goes to *total (may be null)
 hipError_t launch_scan_small(uint32_t* v, uint32_t n, uint32_t* total, hipStream_t s);
 
+// K1-K3 of the FASTQ parser alone: newline count (FqState::n_lines, ::dirty) and positions
+hipError_t launch_fastq_lines(const FqBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);
+
+// FASTA records on the device (vgmi_fasta.hip): the same FqState bookkeeping and packed block as the FASTQ parser
+struct FaBuffers {
+    FqBuffers q;                       // rec_bytes, out_off and block_sum are not used
+    unsigned long long* total;         // (header lines << 32 | packed bytes) of the chunk
+    unsigned long long* bsum;          // the same per 1024 lines (scan scratch): cap_lines / 1024 + 2
+    uint32_t* dest;                    // per line: offset in the packed block (cap_lines + 2)
+    uint32_t* rec_d;                   // per record: offset of its sequence in the packed block (fasta_cap_rec entries)
+    uint32_t* rec_pos;                 // per record: where its header line starts in the raw buffer (fasta_cap_rec entries)
+};
+// Entries of the per-record arrays.  A record in front of the first one without a sequence byte takes two lines or more, so that
+// one's number and its successor's lie below (cap_lines + 1) / 2 + 1 however many header lines a chunk holds: header lines beyond
+// the arrays are not recorded, and the bookkeeping never looks beyond the first bad record.
+__host__ __device__ inline uint32_t fasta_cap_rec(uint32_t cap_lines) { return cap_lines / 2u + 4u; }
+hipError_t launch_fasta_chunk(const FaBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);
+
 // BAM records on the device (vgmi_bam.hip): the same FqState bookkeeping and packed block as the FASTQ parser
 struct BamState {                      // device-resident, one per open BAM stream
     unsigned long long hdr_left;       // header bytes of the decompressed stream not yet passed over

@@ -54,6 +54,8 @@ def lib():
     l.vgh_fastx_read_all_mt.restype = C.c_int64
     l.vgh_fastx_read_all_mt.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                         C.c_char_p]
+    l.vgh_sniff_input.restype = C.c_int
+    l.vgh_sniff_input.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     l.vgh_bam_read_all.restype = C.c_int64
     l.vgh_bam_read_all.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
     l.vgh_free.restype = None; l.vgh_free.argtypes = [vp]
@@ -256,6 +258,17 @@ def fastx_read_all(path, decode_threads=1, with_kind=False):
     if with_kind:
         return block, int(cnt), rb.value, kind.value.decode()
     return block, int(cnt), rb.value
+
+
+def sniff_input(path):
+    """What the device path makes of an input file, from its first bytes (vgh_sniff_input; no device involved):
+    dict(kind, first_byte, bam, fasta)."""
+    l = lib()
+    kind = C.create_string_buffer(8)
+    first, bam, fasta = C.c_int(), C.c_int(), C.c_int()
+    if l.vgh_sniff_input(os.fsencode(path), kind, C.byref(first), C.byref(bam), C.byref(fasta)) != 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    return {"kind": kind.value.decode(), "first_byte": first.value, "bam": bool(bam.value), "fasta": bool(fasta.value)}
 
 
 def bam_read_all(path, decode_threads=1):

@@ -66,6 +66,7 @@ def load_library():
         "vgmi_counts_import_device": (i32, [vp, vp]),
         "vgmi_fastq_open": (i32, [vp, C.POINTER(vp)]),
         "vgmi_fastq_open_bam": (i32, [vp, C.c_uint64, i32, C.POINTER(vp)]),
+        "vgmi_fastq_open_fasta": (i32, [vp, C.POINTER(vp)]),
         "vgmi_fastq_acquire": (i32, [vp, C.POINTER(vp), C.POINTER(sz)]),
         "vgmi_fastq_text_capacity": (i32, [vp, C.POINTER(sz)]),
         "vgmi_fastq_commit": (i32, [vp, sz]),
@@ -300,6 +301,16 @@ class Context:
         whole staging buffers).  Returns dict(n_records, n_bases, consumed, stopped, tail)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        return self._text_stream(fq, text, piece)
+
+    def fasta_text(self, text, piece=None):
+        """Device-side FASTA parser (vgmi_fastq_open_fasta) over one stream of file text, as fastq_text.  The last record of the text
+        is never taken by the device: it comes back as `tail`, from its header line on."""
+        fq = C.c_void_p()
+        self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
+        return self._text_stream(fq, text, piece)
+
+    def _text_stream(self, fq, text, piece):
         mv = memoryview(text)
         pos = 0
         try:
@@ -325,6 +336,12 @@ class Context:
         good_compressed_bytes, taken (compressed bytes handed over as whole members)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        return self._bgzf_stream(fq, comp, piece)
+
+    def fasta_bgzf(self, comp, piece=None):
+        """Block-gzip FASTA through the device inflate + FASTA parser.  Returns the dict of fastq_bgzf."""
+        fq = C.c_void_p()
+        self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
         return self._bgzf_stream(fq, comp, piece)
 
     def bam_bgzf(self, comp, header_bytes, n_ref, piece=None):
@@ -374,6 +391,15 @@ class Context:
         (1 data over, 2 the device gave up), device_text_bytes, reason, taken (compressed bytes used up)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        return self._gzip_stream(fq, comp, piece)
+
+    def fasta_gzip(self, comp, piece=None):
+        """Ordinary gzip FASTA through the device inflate + FASTA parser.  Returns the dict of fastq_gzip."""
+        fq = C.c_void_p()
+        self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
+        return self._gzip_stream(fq, comp, piece)
+
+    def _gzip_stream(self, fq, comp, piece):
         comp = bytes(comp)
         pos, carry, total_taken, stop, n_call = 0, b"", 0, 0, 0
         dtext, reason = C.c_uint64(), C.c_uint32()
