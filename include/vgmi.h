@@ -116,6 +116,13 @@ int vgmi_xtable_info(vgmi_ctx *ctx, size_t *n_lines, size_t *overflow_pairs);
  * bases; VGMI_CTABLE_K=0 keeps them on the generic / literal kernels).  Diagnostic only; no reference counterpart. */
 int vgmi_ctable_info(vgmi_ctx *ctx, size_t *n_buckets, size_t *n_entries, size_t *n_unitigs, size_t *moved_entries,
                      size_t *overflow_kmers);
+/* Since round 6 a count launch over the context table hands its counter updates to two kernels behind it when the block is
+ * large enough and the table small enough, and falls back to atomics in the row loop otherwise.  How many count
+ * launches of this context over the context table deferred their updates and how many did not, since the context was made, and
+ * the geometry of the last one that deferred: counter regions, counters a region, records a workgroup's room of a region
+ * holds, records the buffer holds (all 0 before the first).  Diagnostic only; no reference counterpart. */
+int vgmi_ctable_defer_info(vgmi_ctx *ctx, uint64_t *deferred_launches, uint64_t *plain_launches, uint32_t *n_bins,
+                           uint32_t *region, uint32_t *room, uint32_t *cap);
 
 /* Per-node k-mer lists in CSR form.
  * replaces: nodeSrt::GraphKmerHashHapStrMapIterVec built by ConstructIndex::graph2node

@@ -32,6 +32,29 @@ def chr20():
     ctx.close()
 
 
+PRE = 2_000_000
+CT_DEFER_KNOBS = ("VGMI_CT_DEFER", "VGMI_CT_DEFER_MIN", "VGMI_CT_DEFER_CAP", "VGMI_CT_DEFER_ROOM")
+
+
+def _prefix_want(chr20):
+    """The oracle's counters of the 2 M-read prefix, computed once for the tests that compare with them."""
+    if "want_prefix" not in chr20:
+        t = o.Table(chr20["keys"])
+        t.count_block(chr20["block"][: PRE * (L + 1)].cpu().numpy(), 27)
+        chr20["want_prefix"] = t.counts()
+    return chr20["want_prefix"]
+
+
+def _launch(ctx, d_block, n_reads):
+    """One count launch over the first n_reads of the block -> (counters, deferred launches it made, plain launches it made)"""
+    before = ctx.ctable_defer_info()
+    ctx.counts_reset()
+    ctx.reads_submit_device(d_block, n_reads * (L + 1), n_reads)
+    cov, _, _ = ctx.counts_finish()
+    after = ctx.ctable_defer_info()
+    return cov, after["deferred_launches"] - before["deferred_launches"], after["plain_launches"] - before["plain_launches"]
+
+
 def test_c3_full_size_prefix_equals_oracle_and_properties(chr20):
     ctx, keys, d_block, n_reads = chr20["ctx"], chr20["keys"], chr20["block"], chr20["n_reads"]
     assert keys.size > 2.5e7
@@ -51,15 +74,50 @@ def test_c3_full_size_prefix_equals_oracle_and_properties(chr20):
     ctx.counts_reset()
     ctx.reads_submit_device(d_block, pre * (L + 1), pre)
     part, _, _ = ctx.counts_finish()
-    t = o.Table(keys)
-    t.count_block(d_block[: pre * (L + 1)].cpu().numpy(), 27)
-    want = t.counts()
+    want = _prefix_want(chr20)
     assert np.array_equal(part, want)
     assert want.sum() > 10 * pre          # the dense graph: ~20 hits per read
     # (3) monotone in the input, (4) 30x coverage touches nearly every k-mer of the sequenced haplotypes
     assert (full >= part).all()
     assert (full != 0).mean() > 0.85      # (keys that pair an allele with a neighbouring site's other allele are not on the sample)
     assert int(full.max()) < 255 or (full == 255).sum() < 100
+
+
+def test_c3_deferred_prefix_equals_oracle(chr20, monkeypatch):
+    """The 2 M-read prefix (302 MB: below the size that defers by itself) with deferral forced, counter by counter against the oracle: the
+    chr20-class table has more counter regions than the accumulate kernel has workgroups (1 024 regions of about 25 000 at 256 CUs: four a
+    workgroup), which no smaller graph of the suite reaches through the count kernel."""
+    import torch
+    ctx, d_block = chr20["ctx"], chr20["block"]
+    monkeypatch.setenv("VGMI_CT_DEFER", "1")
+    monkeypatch.setenv("VGMI_CT_DEFER_MIN", "0")
+    part, deferred, plain = _launch(ctx, d_block, PRE)
+    assert (deferred, plain) == (1, 0)
+    assert np.array_equal(part, _prefix_want(chr20))
+    di = ctx.ctable_defer_info()
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    n_keys = chr20["keys"].size
+    if n_cu == 256:      # (2.56e7 counters: regions of 25 034)
+        assert di["n_bins"] == 1024 and -(-n_keys // 1024) <= di["region"] < 25_100, di
+    assert di["n_bins"] > n_cu and di["n_bins"] * di["region"] >= n_keys, di
+
+
+def test_c3_dispatch_rule_of_the_product(chr20, monkeypatch):
+    """No knob set: the 3.6 GB launch defers its counter updates, the 302 MB prefix keeps them in the row loop.  The full launch gives the
+    same counters either way -- a cross-check between two kernels that are each compared with the oracle above, not a substitute for that."""
+    ctx, d_block, n_reads = chr20["ctx"], chr20["block"], chr20["n_reads"]
+    for name in CT_DEFER_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    full, deferred, plain = _launch(ctx, d_block, n_reads)
+    assert (deferred, plain) == (1, 0)
+    part, deferred, plain = _launch(ctx, d_block, PRE)
+    assert (deferred, plain) == (0, 1)
+    assert np.array_equal(part, _prefix_want(chr20))
+    monkeypatch.setenv("VGMI_CT_DEFER", "0")
+    full_rows, deferred, plain = _launch(ctx, d_block, n_reads)
+    assert (deferred, plain) == (0, 1)
+    assert np.array_equal(full_rows, full)
+    assert (full >= part).all() and int(full.astype(np.int64).sum()) > 10 * n_reads
 
 
 def test_reset_is_ordered_before_host_staged_blocks(chr20):

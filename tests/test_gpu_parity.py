@@ -552,6 +552,40 @@ def test_saturation_flags_do_not_travel_with_the_table_image(ctx):
 
 
 # ----------------------------------------------------------------------------- large graphs (global grid bitmap)
+_LARGE_GRAPH_CASES = {}
+
+
+def _large_graph(k):
+    """The 4 Mb / 66 000-SNP graph of the large-graph matrix: (keys, reference, the other haplotype, SNP positions)."""
+    from varigraph_amd import synth
+    G, V = 4_000_000, 66_000
+    ref = synth.make_reference(G, seed=4242)
+    rng = np.random.default_rng(17)
+    pos = np.sort(rng.choice(np.arange(100, G - 100), size=V, replace=False))
+    alts = synth._ACGT[(synth._CODE[ref[pos]] + rng.integers(1, 4, size=V)) % 4]
+    keys = synth.snp_kmer_keys(ref, pos, alts, k=k)
+    assert keys.size > 200_000
+    hap1 = ref.copy()
+    hap1[pos] = alts
+    return keys, ref, hap1, pos
+
+
+def _large_graph_case(k):
+    """Keys, read block and the oracle's counters of the large-graph matrix: they depend on k only, so every variant of a k shares them."""
+    if k not in _LARGE_GRAPH_CASES:
+        keys, ref, hap1, _ = _large_graph(k)
+        n_reads = 300_000
+        block = vgmi.synth_reads_host(5, 0, n_reads, 150, [ref, hap1])
+        # sprinkle ragged reads so the stream is not 151-periodic and ends in a partial row
+        extra = block_from_seqs([hap1[i:i + L].tobytes() for i, L in ((1000, 31), (5000, 27), (9000, 200), (77, 26), (123456, 64))])
+        block = np.concatenate([block, extra])
+        n_reads += 5
+        t = o.Table(keys)
+        t.count_block(block, k)
+        _LARGE_GRAPH_CASES[k] = (keys, block, n_reads, t.counts())
+    return _LARGE_GRAPH_CASES[k]
+
+
 @pytest.mark.parametrize("k,placement", [(27, None), (25, None), (23, None), (21, None), (19, None), (24, None), (22, None), (20, None), (26, None), (28, None), (28, {"VGMI_CTABLE_LOAD": "90"}), (28, {"VGMI_CT_DEFER": "0"}), (25, {"VGMI_CTABLE_K": "0"}),
                                          (21, {"VGMI_CTABLE_LOAD": "90"}), (23, {"VGMI_CTABLE_LOAD": "10"}), (27, {"VGMI_XTABLE": "0"}), (27, {"VGMI_XTABLE": "0", "VGMI_LOCALITY": "0"}),
                                          (27, {"VGMI_XTABLE": "0", "VGMI_LOCALITY": "3"}),
@@ -565,12 +599,22 @@ def test_saturation_flags_do_not_travel_with_the_table_image(ctx):
                                          (22, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}), (19, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}),
                                          (27, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0", "VGMI_CT_DEFER_CAP": "40000"}),
                                          (27, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0", "VGMI_CT_DEFER_ROOM": "500"}),
-                                         (27, {"VGMI_CT_DEFER": "0"})],
+                                         (27, {"VGMI_CT_DEFER": "0"}),
+                                         (28, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}), (26, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}),
+                                         (24, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}), (23, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}),
+                                         (21, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}), (20, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0"}),
+                                         (28, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0", "VGMI_CT_DEFER_CAP": "40000"}),
+                                         (24, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0", "VGMI_CT_DEFER_CAP": "40000"}),
+                                         (28, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0", "VGMI_CT_DEFER_ROOM": "500"}),
+                                         (21, {"VGMI_CT_DEFER": "1", "VGMI_CT_DEFER_MIN": "0", "VGMI_CT_DEFER_ROOM": "500"})],
                          ids=["k27", "k25", "k23", "k21", "k19", "k24", "k22", "k20", "k26", "k28", "k28-context-table-crowded", "k28-counts-in-the-row-loop", "k25-generic-kernel", "k21-context-table-crowded", "k23-context-table-sparse", "k27-minimiser-buckets", "k27-random-homes", "k27-buckets-of-8", "k27-16-byte-slots",
                               "k27-16-byte-slots-dense-counters", "k27-16-byte-slots-random-homes", "k27-slots-by-minimiser-offset",
                               "k27-grid-table", "k27-grid-table-ids-by-key-index", "k27-grid-table-crowded", "k27-context-table-crowded",
                               "k27-context-table-sparse", "k27-deferred-counts", "k25-deferred-counts", "k22-deferred-counts", "k19-deferred-counts",
-                              "k27-deferred-counts-buffer-fills-up", "k27-deferred-counts-rooms-fill-up", "k27-counts-in-the-row-loop"])
+                              "k27-deferred-counts-buffer-fills-up", "k27-deferred-counts-rooms-fill-up", "k27-counts-in-the-row-loop",
+                              "k28-deferred-counts", "k26-deferred-counts", "k24-deferred-counts", "k23-deferred-counts", "k21-deferred-counts", "k20-deferred-counts",
+                              "k28-deferred-counts-buffer-fills-up", "k24-deferred-counts-buffer-fills-up", "k28-deferred-counts-rooms-fill-up",
+                              "k21-deferred-counts-rooms-fill-up"])
 def test_large_graph_grid_variant_matches_oracle(k, placement, monkeypatch):
     """> 65 536 keys: k = 27 takes count27c_kernel over the context table (default since round 4; path-ordered counter ids), with
     VGMI_CTABLE=0 count27x_kernel over round 2's grid-16-mer table, with
@@ -580,26 +624,15 @@ def test_large_graph_grid_variant_matches_oracle(k, placement, monkeypatch):
     hit rate: exercises ring pressure, re-queued collision probes and unsaturated counters.  The k = 27 table has
     8-byte slots in minimiser buckets with per-slot counters by default; the other formats and placements stay covered.
     Round 6: VGMI_CT_DEFER=1 -- the context-table kernels write their runs of hits out and two kernels behind them count them by counter
-    region in LDS (vgmi_ctdefer.hip); also with a record buffer and with rooms far too small (the rest is counted by plain atomics)."""
+    region in LDS (vgmi_ctdefer.hip); also with a record buffer and with rooms far too small (the rest is counted by plain atomics).
+    Every countkc_defer_kernel<K> (k = 19 .. 28) is in the matrix, k = 28, 24 and 21 also with a buffer / rooms that fill up; the cases that
+    set VGMI_CT_DEFER check through vgmi_ctable_defer_info that every launch took the path they are about."""
     import torch
     for name, val in (placement or {}).items():
         monkeypatch.setenv(name, val)
-    from varigraph_amd import synth
-    G, V = 4_000_000, 66_000
-    ref = synth.make_reference(G, seed=4242)
-    rng = np.random.default_rng(17)
-    pos = np.sort(rng.choice(np.arange(100, G - 100), size=V, replace=False))
-    alts = synth._ACGT[(synth._CODE[ref[pos]] + rng.integers(1, 4, size=V)) % 4]
-    keys = synth.snp_kmer_keys(ref, pos, alts, k=k)
-    assert keys.size > 200_000
-    hap1 = ref.copy()
-    hap1[pos] = alts
-    n_reads = 300_000
-    block = vgmi.synth_reads_host(5, 0, n_reads, 150, [ref, hap1])
-    # sprinkle ragged reads so the stream is not 151-periodic and ends in a partial row
-    extra = block_from_seqs([hap1[i:i + L].tobytes() for i, L in ((1000, 31), (5000, 27), (9000, 200), (77, 26), (123456, 64))])
-    block = np.concatenate([block, extra])
-    n_reads += 5
+    keys, block, n_reads, want = _large_graph_case(k)
+    deferred = bool(placement) and placement.get("VGMI_CT_DEFER") == "1"
+    in_row_loop = bool(placement) and placement.get("VGMI_CT_DEFER") == "0"
     c = vgmi.Context(0, buffer_mib=16)
     try:
         c.table_upload(keys, k)
@@ -614,11 +647,20 @@ def test_large_graph_grid_variant_matches_oracle(k, placement, monkeypatch):
         c.counts_reset()
         c.reads_submit(block, n_reads)               # chunked through the 16 MiB staging buffers
         cov, _, _ = c.counts_finish()
-        t = o.Table(keys)
-        t.count_block(block, k)
-        want = t.counts()
         assert np.array_equal(cov, want)
         assert want.sum() > 5_000_000 and want.max() > 8
+        # which kernels counted: a deferral that fell back to the row loop (or the reverse) would be green and check nothing
+        launches, di = c.count_kernel_ms()[1], c.ctable_defer_info()
+        assert launches >= 2
+        if deferred:
+            assert (di["deferred_launches"], di["plain_launches"]) == (launches, 0), di
+            assert di["n_bins"] * di["region"] >= keys.size and di["n_bins"] >= 2, di
+            if "VGMI_CT_DEFER_CAP" in placement:
+                assert di["cap"] == 40448, di
+            if "VGMI_CT_DEFER_ROOM" in placement:
+                assert di["room"] == 501, di
+        elif in_row_loop:
+            assert (di["deferred_launches"], di["plain_launches"]) == (0, launches), di
         # device-resident single launch gives the same
         c.counts_reset()
         d = torch.from_numpy(block).cuda()
@@ -629,6 +671,11 @@ def test_large_graph_grid_variant_matches_oracle(k, placement, monkeypatch):
         c.reads_submit_device(d, block.size, n_reads, d_off)
         cov2, _, _ = c.counts_finish()
         assert np.array_equal(cov2, want)
+        dj = c.ctable_defer_info()
+        if deferred:
+            assert (dj["deferred_launches"], dj["plain_launches"]) == (di["deferred_launches"] + 1, 0), dj
+        elif in_row_loop:
+            assert (dj["deferred_launches"], dj["plain_launches"]) == (0, di["plain_launches"] + 1), dj
     finally:
         c.close()
 

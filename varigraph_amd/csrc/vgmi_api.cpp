@@ -174,6 +174,14 @@ int launch_ctable_count(vgmi_ctx* c, const RowParams& p, size_t n_bytes, hipStre
     CtDefer d;
     int rc = ctd_prepare(c, n_bytes, st, &d);
     if (rc) return rc;
+    {      // which path this launch takes (vgmi_ctable_defer_info: a fall-back to the plain kernel is silent otherwise)
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (d.rec) {
+            ++c->ctd_deferred;
+            c->ctd_last[0] = d.n_bins, c->ctd_last[1] = d.region, c->ctd_last[2] = d.room, c->ctd_last[3] = d.cap;
+        } else
+            ++c->ctd_plain;
+    }
     HIPCHK(c, launch_count27c(p, c->tv.xt, (uint32_t)c->n_cu, st, &d));
     if (d.rec) HIPCHK(c, launch_ctd_apply(c->tv.xt, d, (uint32_t)c->n_cu, st));
     return VGMI_OK;

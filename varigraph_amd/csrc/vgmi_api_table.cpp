@@ -829,6 +829,20 @@ int vgmi_ctable_info(vgmi_ctx* c, size_t* n_buckets, size_t* n_entries, size_t* 
     return VGMI_OK;
 }
 
+int vgmi_ctable_defer_info(vgmi_ctx* c, uint64_t* deferred_launches, uint64_t* plain_launches, uint32_t* n_bins, uint32_t* region, uint32_t* room,
+                           uint32_t* cap)
+{
+    if (!c) return VGMI_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (deferred_launches) *deferred_launches = c->ctd_deferred;
+    if (plain_launches) *plain_launches = c->ctd_plain;
+    if (n_bins) *n_bins = c->ctd_last[0];
+    if (region) *region = c->ctd_last[1];
+    if (room) *room = c->ctd_last[2];
+    if (cap) *cap = c->ctd_last[3];
+    return VGMI_OK;
+}
+
 int vgmi_table_info(vgmi_ctx* c, size_t* n_keys, uint32_t* k, size_t* n_slots, size_t* filter_bits)
 {
     if (!c) return VGMI_E_INVALID;

@@ -206,14 +206,22 @@ size_t ctd_scratch_bytes(uint64_t n_bytes, uint64_t n_counts, uint32_t n_cu, CtD
     if (region < 256) region = 256;      // (tables of a few thousand counters: fewer regions than CUs)
     n_bins = (n_counts + region - 1) / region;
     const uint32_t n_wg = n_cu & ~1u;      // workgroups of the scatter kernel (even: the accumulate kernel takes rooms in pairs)
+    if (n_wg < 2) return 0;                // (a device of one CU: the plain kernel)
     // a read of 150 bases makes ~3.4 runs at chr20 class: room for one run per 16 bytes of text (9.4 a read) + a chunk per wavefront of the largest grid
     uint64_t cap = n_bytes / 16 + 8192ull * CTD_CHUNK;
     cap = (cap + CTD_CHUNK - 1) / CTD_CHUNK * CTD_CHUNK;
     if (cap > 0xC0000000ull) cap = 0xC0000000ull;      // the cursor is 32 bits (the runs beyond leave as atomics)
-    if (const char* e = getenv("VGMI_CT_DEFER_CAP")) cap = ((uint64_t)atoll(e) + CTD_CHUNK - 1) / CTD_CHUNK * CTD_CHUNK + CTD_CHUNK;      // tests: a buffer that fills up
+    if (const char* e = getenv("VGMI_CT_DEFER_CAP")) {      // tests: a buffer that fills up (whatever the value says, CTD_CHUNK <= cap <= 0xC0000000)
+        const long long v = atoll(e);
+        cap = v < 0 ? CTD_CHUNK : v > 0xC0000000ll ? 0xC0000000ull : ((uint64_t)v + CTD_CHUNK - 1) / CTD_CHUNK * CTD_CHUNK + CTD_CHUNK;
+        if (cap > 0xC0000000ull) cap = 0xC0000000ull;
+    }
     // a workgroup's room in a bin: its share of a FULL record buffer (2.7 x the mean at chr20 class) + slack for the spread of small means
     uint64_t room = cap / (n_bins * n_wg) + 64;
-    if (const char* e = getenv("VGMI_CT_DEFER_ROOM")) room = (uint64_t)atoll(e) + 1;                                                     // tests: rooms that fill up
+    if (const char* e = getenv("VGMI_CT_DEFER_ROOM")) {      // tests: rooms that fill up (1 <= room <= cap)
+        const long long v = atoll(e);
+        room = v < 0 ? 1 : (uint64_t)v >= cap ? cap : (uint64_t)v + 1;
+    }
     d->cap = (uint32_t)cap;
     d->n_bins = (uint32_t)n_bins;
     d->room = (uint32_t)room;

@@ -120,6 +120,8 @@ struct vgmi_ctx {
     unsigned long long* d_hist = nullptr;
     uint32_t* d_status = nullptr;
     std::map<hipStream_t, std::pair<uint8_t*, size_t>> ctd_scratch;      // deferred counter updates (vgmi_ctdefer.hip): per stream that counts, records + rooms
+    uint64_t ctd_deferred = 0, ctd_plain = 0;      // context-table count launches of this context that deferred their counter updates / that did not (under mu)
+    uint32_t ctd_last[4] = {0, 0, 0, 0};           // n_bins, region, room, cap of the last one that deferred
     std::map<hipStream_t, unsigned long long*> debit_lists;      // even k on the fast path: per stream that counts, VG_DEBIT_LIST positions + a counter
 
     // per-sample state

@@ -52,6 +52,7 @@ def load_library():
         "vgmi_table_info": (i32, [vp, C.POINTER(sz), C.POINTER(u32), C.POINTER(sz), C.POINTER(sz)]),
         "vgmi_xtable_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
         "vgmi_ctable_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "vgmi_ctable_defer_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "vgmi_table_lookup": (i32, [vp, vp, sz, vp]),
         "vgmi_nodes_upload": (i32, [vp, vp, vp, sz]),
         "vgmi_flags_upload": (i32, [vp, vp]),
@@ -245,6 +246,13 @@ class Context:
         v = [C.c_size_t() for _ in range(5)]
         self._chk(self._l.vgmi_ctable_info(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("n_buckets", "n_entries", "n_unitigs", "moved_entries", "overflow_kmers"), (x.value for x in v)))
+
+    def ctable_defer_info(self):
+        """Count launches over the context table that deferred their counter updates / that kept them in the row loop, and the
+        geometry of the last deferred one."""
+        v = [C.c_uint64(), C.c_uint64()] + [C.c_uint32() for _ in range(4)]
+        self._chk(self._l.vgmi_ctable_defer_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("deferred_launches", "plain_launches", "n_bins", "region", "room", "cap"), (x.value for x in v)))
 
     def nodes_upload(self, node_off, key_index):
         node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
