@@ -317,7 +317,7 @@ int vgmi_hmm_calls_part(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, const uin
 /* ---- emission scores of the HMM's nodes on the device ---------------------------------------------------------------------
  * replaces: GenotypeNameSpace::hidden_states + observable_states (src/genotype.cpp:640-830, 960-1000, most_likely_depth :1118-1145)
  * for a DIPLOID sample whose windows all use the same genotype list -- every haplotype of the graph is selected (-n >= haplotypes),
- * so no k-mer list is pruned and nothing is drawn per window.  Everything is in NODE ORDER (entry j = place j of the graph2node
+ * so no k-mer list is pruned and nothing is drawn per window (-n below the haplotypes: vgmi_hmm_emissions_select further down).  Everything is in NODE ORDER (entry j = place j of the graph2node
  * lists, the order of vgmi_counts_finish's cov_node):
  *   entries_upload   once per graph: per entry  multiplicity << 8 | haplotype bits << 16  (f and BitVec of its k-mer)
  *   sample_upload    per sample: the coverage of every entry (cov_node) 
@@ -374,6 +374,40 @@ int vgmi_hmm_part_calls_plan(vgmi_hmm_part *part, const vgmi_hmm_plan *plan, voi
 void vgmi_hmm_plan_free(vgmi_hmm_plan *plan);
 int vgmi_hmm_tallies(vgmi_ctx *ctx, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *winner,
                      uint32_t n_gt, const uint8_t *hap_ab, uint32_t n_hap, uint64_t sel_mask, uint32_t *out, uint8_t *unique_out);
+/* ---- haplotypes selected per window: -n below the number of haplotypes of the graph, a diploid sample ------------------------------
+ * replaces, per sample: the support sums of haplotype_selection (src/genotype.cpp:500-560), hidden_states with filter = true and
+ * observable_states (:640-830 -- with the prune of :673-686 and :815-818 -- and :960-1000), and the tallies posterior() reads for a
+ * call (:1387-1414), all on the PRUNED node lists.  As soon as -n selects, the reference draws haplotypes per window, drops from a
+ * node's list every k-mer no selected haplotype carries -- for good: the next sample of the run starts from the shortened lists -- and
+ * scores what is left.  For a diploid sample the genotype list keeps its shape from window to window (pairs over n_used = -n places);
+ * what changes is which haplotype stands at each place.  So:
+ *   alive_upload / alive_fetch   one byte per entry next to entries_upload's words: the entry is still in its node's list (all ones after
+ *                    entries_upload).  Upload the host's lists when the host pruned on its own; fetch for tests and diagnostics.
+ *   support          per window w the sums the draw is weighted by: support_out[w * n_hap + hap] = sum of coverage c over the alive
+ *                    entries, with c > 1 and multiplicity <= 1 and bit `hap` set, of the rows with row_win[r] == w (32-bit sums: exact
+ *                    in any order).  The gamma draws (std::mt19937, libm) stay on the host.
+ *   emissions_select vgmi_hmm_emissions with row r in window row_win[r]: genotype g is (win_used[n_used w + pos_a[g]],
+ *                    win_used[n_used w + pos_b[g]]), the mask of the window's haplotypes is win_top_mask[w], gt0 is over the window's
+ *                    places.  A row is the RANGE [entry_begin, +entry_count) that spans what is left of its node's list; dead entries
+ *                    are passed over, an alive entry no haplotype of the window carries is marked dead (the prune -- not flag bit 1)
+ *                    and passed over.  n_kept_out counts the entries that took part; flag bit 0 and vgmi_hmm_part_fix_rows work as
+ *                    above, fix_j being places in the row's range.  Haplotype ids go up to 8 * bit_len - 2 (46).
+ *   tallies_select   vgmi_hmm_tallies with the called genotype's haplotypes taken from the row's window; only alive entries count,
+ *                    for unique_out too.
+ * Recursion and posterior run on the part as before (vgmi_hmm_part_calls; gid / order are per sample here).  Calls that write the
+ * alive bytes of the same rows must not run side by side. */
+int vgmi_hmm_alive_upload(vgmi_ctx *ctx, const uint8_t *host_alive, size_t n_entries);
+int vgmi_hmm_alive_fetch(vgmi_ctx *ctx, uint8_t *host_alive_out, size_t n_entries);
+int vgmi_hmm_support(vgmi_ctx *ctx, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t *entry_begin,
+                     const uint32_t *entry_count, const uint32_t *row_win, uint32_t *support_out /* n_windows x n_hap */);
+int vgmi_hmm_emissions_select(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used, const uint8_t *pos_a, const uint8_t *pos_b, uint32_t n_windows,
+                              const uint8_t *win_used /* n_windows x n_used */, const uint64_t *win_top_mask, uint32_t bit_len, float ave,
+                              double lower, double upper, const void *tables, uint64_t n_rows, const uint64_t *entry_begin,
+                              const uint32_t *entry_count, const uint32_t *row_win, const uint16_t *gt0, uint32_t *n_kept_out,
+                              uint8_t *flags_out, vgmi_hmm_part **out);
+int vgmi_hmm_tallies_select(vgmi_ctx *ctx, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win,
+                            const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b, uint32_t n_used,
+                            uint32_t n_windows, const uint8_t *win_used, uint32_t *out, uint8_t *unique_out);
 /* the part's emission rows back on the host (n_rows x n_gt long doubles): tests and diagnostics */
 int vgmi_hmm_part_fetch(vgmi_hmm_part *part, void *obs_out);
 void vgmi_hmm_part_free(vgmi_hmm_part *part);

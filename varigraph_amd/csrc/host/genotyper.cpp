@@ -614,7 +614,10 @@ Genotyper::NodeStates Genotyper::hidden_states(Chrom& chr, uint32_t node_i, cons
         }
     }
     if (filter) {
-        if (kept.size() != node.kmers.size()) lists_whole_.store(false, std::memory_order_relaxed);     // the device's emission path needs whole lists
+        if (kept.size() != node.kmers.size()) {
+            lists_whole_.store(false, std::memory_order_relaxed);     // the device's whole-list emission path needs whole lists
+            alive_stale_.store(true, std::memory_order_relaxed);      // ... and the per-window one the lists as they are now
+        }
         node.kmers.keep(kept);
     }
     return ns;
@@ -1555,7 +1558,7 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
                             cfg.transition == "rec" && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;
     std::vector<WindowWork> works(use_device ? tasks.size() : 0);
     size_t dev_n_gt = 0, total_room = 0;
-    bool dev_emit = false;
+    bool dev_emit = false, dev_select = false;
     const uint32_t dev_stride = cfg.sample_ploidy + 1;
     struct Raw {
         void* p = nullptr;
@@ -1593,7 +1596,16 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
         // (round 5: polyploid samples too -- their genotypes are blocks of `ploidy` consecutive haplotypes, :846-873, a handful per window)
         dev_emit = device_ok && !emit_device_off_ && r.packed != nullptr && cfg.sample_ploidy >= 2 && cfg.sample_ploidy <= 4 && n_hap_ <= r.haploid_num && n_hap_ <= 16 &&
                    dev_n_gt <= 128 && lists_whole_.load() && [] { const char* e = getenv("VGH_HMM_EMIT_DEVICE"); return !(e && e[0] == '0'); }();
-        if (device_ok && !dev_emit) {
+        // ... and when -n selects fewer haplotypes than the graph has, for a diploid sample (below: every window draws its own haplotypes,
+        // the genotype list keeps its shape, the k-mer lists are pruned on the device and here alike).  VGH_HMM_SELECT_DEVICE=0: the host
+        // prepares such a sample as before.
+        bool plain_ids = true;      // haplotype h is bit h of an entry's word
+        for (size_t i = 0; i < hap_ids_.size(); ++i) plain_ids = plain_ids && hap_ids_[i] == i;
+        dev_select = device_ok && !dev_emit && r.packed != nullptr && cfg.sample_ploidy == 2 && n_hap_ > r.haploid_num && r.haploid_num >= 1 &&
+                     r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen &&
+                     [] { const char* e = getenv("VGH_HMM_EMIT_DEVICE"); return !(e && e[0] == '0'); }() &&
+                     [] { const char* e = getenv("VGH_HMM_SELECT_DEVICE"); return !(e && e[0] == '0'); }();
+        if (device_ok && !dev_emit && !dev_select) {
             raw_obs.p = std::malloc(total_room * dev_n_gt * sizeof(long double));
             raw_pw.p = std::malloc(2 * total_room * 2 * dev_stride * sizeof(long double));
             raw_row.p = std::calloc(2 * total_room, sizeof(uint32_t));
@@ -2406,6 +2418,452 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
             }
             emitted_on_device = true;
             if (g_phase_on) std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s\n", n_parts_e, since_begin() * 1e-9 - tb0);
+        }
+    }
+    // ---- ... and with the haplotypes selected PER WINDOW (-n below the graph's haplotypes, a diploid sample: DESIGN_INGEST_HMM.md 4.13).
+    // The reference draws every window's haplotypes from their k-mer support, drops from a node's list every k-mer no drawn haplotype
+    // carries -- for good -- and scores what is left (src/genotype.cpp:500-610, 673-686, 815-818).  haplotype_combinations over the sorted
+    // draw yields pairs over -n places whatever was drawn: positions, keep matrix and the shape of every step are the sample's, the
+    // haplotype at each place is the window's.  Support sums, emissions (with the prune), recursion, posterior and tallies run on the
+    // device; the draws (std::mt19937, libm), the sequence checks (strings), the step tables (libm) and the genotype strings stay here.
+    // A row is the range [front, back] of what is left of its node's list plus the device's alive bytes; node.kmers is pruned by the same
+    // rule right after the emission launch, so that the host's lists and the device's bytes agree after every sample.
+    if (dev_select) {
+        const double tb0 = since_begin() * 1e-9;
+        const float ave = r.hap_cov;
+        double lower = 256.0f, upper = -0.1f;
+        poisson_interval(ave, lower, upper);
+        const uint32_t n_used = r.haploid_num;
+        std::vector<uint16_t> places(n_used);
+        std::iota(places.begin(), places.end(), (uint16_t)0);
+        const std::vector<std::vector<uint16_t>> shape = haplotype_combinations(places, cfg.sample_type, 2, (uint16_t)(n_hap_ - 1));
+        const size_t n_gt = shape.size();
+        bool pairs = n_gt >= 1 && n_gt <= 128;
+        for (const auto& gtv : shape) pairs = pairs && gtv.size() == 2;
+        if (pairs) {
+            std::vector<uint8_t> pos_a(n_gt), pos_b(n_gt), keep_mat(n_gt * n_gt);
+            for (size_t gi = 0; gi < n_gt; ++gi) {
+                pos_a[gi] = (uint8_t)shape[gi][0];
+                pos_b[gi] = (uint8_t)shape[gi][1];
+            }
+            for (size_t i = 0; i < n_gt; ++i)
+                for (size_t j = 0; j < n_gt; ++j) {      // std::set_intersection of two sorted pairs (places keep the haplotypes' order)
+                    uint8_t n2 = 0;
+                    for (size_t x = 0, y = 0; x < 2 && y < 2;) {
+                        if (shape[i][x] < shape[j][y]) ++x;
+                        else if (shape[j][y] < shape[i][x]) ++y;
+                        else { ++n2; ++x; ++y; }
+                    }
+                    keep_mat[i * n_gt + j] = n2;
+                }
+            std::vector<long double> tab(3 * 256);
+            for (int c2 = 0; c2 < 256; ++c2) {
+                tab[c2] = geometric(error_param(ave), (uint8_t)c2);
+                for (uint8_t h = 1; h <= 2; ++h) tab[(size_t)h * 256 + c2] = poisson_pmf(ave * h, (uint8_t)c2);
+            }
+            auto dev_check = [&](int rc, const char* what) {
+                if (rc != VGMI_OK) throw std::runtime_error(std::string(what) + vgmi_last_error(dev_));
+            };
+            if (!entries_uploaded_) {
+                dev_check(vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
+                entries_uploaded_ = true;
+                if (!lists_whole_.load()) alive_stale_.store(true);
+            }
+            dev_check(vgmi_hmm_sample_upload(dev_, cov_node, n_entries), "device HMM emissions: ");
+            if (alive_stale_.load()) {      // a sample of this run took a host path: the lists as the host left them
+                std::vector<uint8_t> alive(n_entries, 0);
+                for (const auto& c : chroms_)
+                    for (const auto& n : c.nodes)
+                        for (uint32_t pos : n.kmers) alive[pos] = 1;
+                dev_check(vgmi_hmm_alive_upload(dev_, alive.data(), n_entries), "device HMM emissions: ");
+                alive_stale_.store(false);
+            }
+            const size_t nw = tasks.size();
+            // rows, window after window.  Support reads every node with more than one allele; the HMM works on those --sv leaves.
+            std::vector<uint64_t> sup_begin, e_begin_sv;
+            std::vector<uint32_t> sup_count, sup_win, sup_node, e_count_sv, e_win_sv, e_node_sv;
+            std::vector<size_t> win_row0(nw + 1, 0);
+            {
+                CpuBudget::Hold cpu;
+                PhaseTimer t_list(g_phase.list);
+                for (size_t t = 0; t < nw; ++t) {
+                    Chrom& chr = *tasks[t].chr;
+                    auto vcf_chr = g_.vcf_info.find(chr.name);
+                    if (vcf_chr == g_.vcf_info.end()) throw std::runtime_error("'" + chr.name + "' does not exist in the VCF file.");
+                    for (uint32_t i = tasks[t].first; i < tasks[t].last; ++i) {
+                        const Node& n = chr.nodes[i];
+                        if (n.gn->hap_gt.size() <= 1) continue;
+                        const uint64_t b = n.kmers.empty() ? 0 : n.kmers.front();
+                        const uint32_t cnt = n.kmers.empty() ? 0 : n.kmers.back() - n.kmers.front() + 1;
+                        sup_begin.push_back(b);
+                        sup_count.push_back(cnt);
+                        sup_win.push_back((uint32_t)t);
+                        sup_node.push_back(i);
+                        if (cfg.sv_only) {
+                            auto site = vcf_chr->second.find(n.start);
+                            if (site == vcf_chr->second.end())
+                                throw std::runtime_error("'" + chr.name + ":" + std::to_string(n.start) + "' does not exist in the VCF file.");
+                            if (site->second[3].size() < 50 && site->second[4].size() < 50) continue;
+                            e_begin_sv.push_back(b);
+                            e_count_sv.push_back(cnt);
+                            e_win_sv.push_back((uint32_t)t);
+                            e_node_sv.push_back(i);
+                        }
+                    }
+                    win_row0[t + 1] = cfg.sv_only ? e_begin_sv.size() : sup_begin.size();
+                }
+            }
+            const std::vector<uint64_t>& e_begin = cfg.sv_only ? e_begin_sv : sup_begin;
+            const std::vector<uint32_t>&e_count = cfg.sv_only ? e_count_sv : sup_count, &row_win = cfg.sv_only ? e_win_sv : sup_win,
+                                       &row_node = cfg.sv_only ? e_node_sv : sup_node;
+            const size_t n_rows = e_begin.size();
+            const int64_t ta = since_begin();
+            // 1. the support the draw is weighted by, on the device
+            std::vector<uint32_t> support(nw * n_hap_, 0);
+            dev_check(vgmi_hmm_support(dev_, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
+                      "device HMM support: ");
+            const int64_t t_sup = since_begin();
+            // the windows on the run's threads
+            auto over_windows = [&](std::atomic<long long>& spent, const std::function<void(size_t)>& fn) {
+                std::atomic<size_t> nextw{0};
+                std::string herr;
+                std::mutex hmu;
+                auto body = [&]() {
+                    for (;;) {
+                        const size_t wi = nextw.fetch_add(1);
+                        if (wi >= nw) return;
+                        try {
+                            CpuBudget::Hold cpu;
+                            PhaseTimer tt(spent);
+                            fn(wi);
+                        } catch (const std::exception& e) {
+                            std::lock_guard<std::mutex> lock(hmu);
+                            if (herr.empty()) herr = e.what();
+                        }
+                    }
+                };
+                std::vector<std::thread> hs;
+                for (size_t h2 = 1; h2 < n_threads; ++h2) hs.emplace_back(body);
+                body();
+                for (auto& th : hs) th.join();
+                if (!herr.empty()) throw std::runtime_error(herr);
+            };
+            // 2. the draws; 3. what follows from them: the window's haplotypes and mask, its genotypes, the rows' reference-allele masks
+            std::vector<std::vector<uint16_t>> win_top(nw);
+            std::vector<std::vector<std::vector<uint16_t>>> win_gts(nw);
+            std::vector<uint8_t> win_used8(nw * n_used, 0);
+            std::vector<uint64_t> win_mask(nw, 0);
+            std::vector<uint16_t> gt0(n_rows ? n_rows : 1, 0);
+            over_windows(g_phase.select, [&](size_t wi) {
+                HaplotypeSampler sampler(std::vector<uint32_t>(support.begin() + wi * n_hap_, support.begin() + (wi + 1) * n_hap_), (int)r.haploid_num);
+                std::vector<uint16_t>& top = win_top[wi];
+                top = sampler.top;
+                std::sort(top.begin(), top.end());
+                if (top.size() != n_used) throw std::runtime_error("internal: a window drew another number of haplotypes");
+                for (size_t p2 = 0; p2 < n_used; ++p2) {
+                    win_used8[wi * n_used + p2] = (uint8_t)top[p2];
+                    win_mask[wi] |= 1ULL << top[p2];
+                }
+                win_gts[wi].resize(n_gt);
+                for (size_t gi = 0; gi < n_gt; ++gi) win_gts[wi][gi] = {top[pos_a[gi]], top[pos_b[gi]]};
+                const Chrom& chr = *tasks[wi].chr;
+                for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+                    const auto& hap_gt = chr.nodes[row_node[rr]].gn->hap_gt;
+                    uint16_t m = 0;
+                    for (size_t p2 = 0; p2 < n_used; ++p2) m |= (uint16_t)((hap_gt[top[p2]] == 0) << p2);
+                    gt0[rr] = m;
+                }
+            });
+            const int64_t t_draw = since_begin();
+            size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0;
+            int64_t t_emit = t_draw, t_a = t_draw, t_rows = t_draw, t_b = t_draw, t_calls = t_draw;
+            std::vector<long double> prob(n_rows ? n_rows : 1);
+            std::vector<uint32_t> winner(n_rows ? n_rows : 1, 0xFFFFFFFFu);
+            std::vector<std::vector<uint32_t>> win_rows(nw);      // per window: the rows that have a score
+            size_t n_steps = 0;
+            if (n_rows) {
+                // 4. emission scores on the device, the prune included
+                std::vector<uint32_t> n_kept(n_rows);
+                std::vector<uint8_t> flags(n_rows);
+                struct PartHandle {
+                    vgmi_hmm_part* p = nullptr;
+                    ~PartHandle() { vgmi_hmm_part_free(p); }
+                } ph;
+                dev_check(vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, n_used, pos_a.data(), pos_b.data(), (uint32_t)nw, win_used8.data(), win_mask.data(),
+                                                    (uint32_t)g_.bitlen, ave, lower, upper, tab.data(), n_rows, e_begin.data(), e_count.data(), row_win.data(),
+                                                    gt0.data(), n_kept.data(), flags.data(), &ph.p),
+                          "device HMM emissions: ");
+                t_emit = since_begin();
+                // 5. the same prune on the host's lists, for exactly the nodes that lost k-mers; 6. the sequence checks of flagged rows
+                static const bool fix_on_device = !(getenv("VGH_HMM_FIX_DEVICE") && getenv("VGH_HMM_FIX_DEVICE")[0] == '0');
+                std::vector<std::vector<uint64_t>> host_rows(nw), fix_rows(nw);
+                std::vector<std::vector<long double>> host_obs(nw);
+                std::vector<std::vector<uint32_t>> fix_cnt(nw), fix_j(nw);
+                std::vector<std::vector<uint16_t>> fix_mask(nw);
+                std::atomic<size_t> pruned_nodes{0};
+                over_windows(g_phase.pass_a, [&](size_t wi) {
+                    Chrom& chr = *tasks[wi].chr;
+                    const std::vector<uint16_t>& top = win_top[wi];
+                    std::vector<uint32_t> kept;
+                    ScoreCtx sctx;
+                    sctx.ave = ave;
+                    sctx.score_up = upper;
+                    NodeStates st;
+                    GenotypeList glist;
+                    for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+                        Node& node = chr.nodes[row_node[rr]];
+                        if (n_kept[rr] != node.kmers.size()) {
+                            kept.clear();
+                            for (uint32_t pos : node.kmers)
+                                if ((r.packed[pos] >> 16) & win_mask[wi]) kept.push_back(pos);
+                            if (kept.size() != n_kept[rr]) throw std::runtime_error("internal: the device's k-mer lists differ from the host's");
+                            node.kmers.keep(kept);
+                            ++pruned_nodes;
+                        }
+                        if (!(flags[rr] & 1u)) continue;
+                        if (fix_on_device) {
+                            PhaseTimer tt(g_phase.states);
+                            const size_t before = fix_j[wi].size();
+                            sequence_fixes(chr, row_node[rr], top, gt0[rr], lower, upper, r, fix_j[wi], fix_mask[wi]);
+                            // (sequence_fixes counts along the list; the device along the row's range)
+                            for (size_t q = before; q < fix_j[wi].size(); ++q) fix_j[wi][q] = node.kmers[fix_j[wi][q]] - (uint32_t)e_begin[rr];
+                            if (fix_j[wi].size() != before) {
+                                fix_rows[wi].push_back(rr);
+                                fix_cnt[wi].push_back((uint32_t)(fix_j[wi].size() - before));
+                            }
+                        } else {
+                            if (glist.off.empty()) {
+                                glist.off.assign(n_gt + 1, 0);
+                                for (size_t gi = 0; gi < n_gt; ++gi) {
+                                    glist.flat.insert(glist.flat.end(), win_gts[wi][gi].begin(), win_gts[wi][gi].end());
+                                    glist.off[gi + 1] = (uint32_t)glist.flat.size();
+                                }
+                                glist.pos_a = pos_a;
+                                glist.pos_b = pos_b;
+                            }
+                            {
+                                PhaseTimer tt(g_phase.states);
+                                st = hidden_states(chr, row_node[rr], top, win_gts[wi], top, glist, lower, upper, true, r, std::move(st), nullptr);
+                            }
+                            PhaseTimer tt(g_phase.emit);
+                            const std::vector<long double> obs = score_states(st, sctx);
+                            if (!obs.empty()) {
+                                host_rows[wi].push_back(rr);
+                                host_obs[wi].insert(host_obs[wi].end(), obs.begin(), obs.end());
+                            }
+                        }
+                    }
+                });
+                n_pruned = pruned_nodes.load();
+                if (n_pruned) lists_whole_.store(false, std::memory_order_relaxed);
+                alive_stale_.store(false);      // (hidden_states above walked lists that were pruned already: nothing left them)
+                t_a = since_begin();
+                {
+                    std::vector<uint64_t> all_rows, f_rows;
+                    std::vector<long double> all_obs;
+                    std::vector<uint32_t> f_off(1, 0), f_j;
+                    std::vector<uint16_t> f_m;
+                    for (size_t wi = 0; wi < nw; ++wi) {
+                        all_rows.insert(all_rows.end(), host_rows[wi].begin(), host_rows[wi].end());
+                        all_obs.insert(all_obs.end(), host_obs[wi].begin(), host_obs[wi].end());
+                        f_rows.insert(f_rows.end(), fix_rows[wi].begin(), fix_rows[wi].end());
+                        for (uint32_t cnt2 : fix_cnt[wi]) f_off.push_back(f_off.back() + cnt2);
+                        f_j.insert(f_j.end(), fix_j[wi].begin(), fix_j[wi].end());
+                        f_m.insert(f_m.end(), fix_mask[wi].begin(), fix_mask[wi].end());
+                    }
+                    n_host_rows = all_rows.size();
+                    n_fixed_rows = f_rows.size();
+                    if (!all_rows.empty()) dev_check(vgmi_hmm_part_set_rows(ph.p, all_rows.size(), all_rows.data(), all_obs.data()), "device HMM emissions: ");
+                    if (!f_rows.empty())
+                        dev_check(vgmi_hmm_part_fix_rows(ph.p, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
+                }
+                t_rows = since_begin();
+                // 7. the recursion's inputs: genotype strings (the window's haplotypes decide them), step tables (libm), chains
+                const uint32_t stride = 3;
+                struct Seen { uint32_t start, end; int64_t row; };
+                std::vector<std::vector<Seen>> seen(nw);
+                std::vector<uint8_t> gid(n_rows * n_gt, 0), order(n_rows * n_gt, 0);
+                over_windows(g_phase.pass_a, [&](size_t wi) {
+                    Chrom& chr = *tasks[wi].chr;
+                    std::unordered_map<uint32_t, uint32_t> gs_memo;      // reference-allele mask of a two-allele node -> a row that holds the pattern
+                    for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+                        Node& n = chr.nodes[row_node[rr]];
+                        const uint32_t n_start = n.start, n_end = (uint32_t)(n_start + n.gn->seqs[0].size() - 1);
+                        if (n_kept[rr] == 0) {
+                            seen[wi].push_back(Seen{n_start, n_end, -1});
+                            continue;
+                        }
+                        seen[wi].push_back(Seen{n_start, n_end, (int64_t)rr});
+                        bool biallelic = true;
+                        for (uint16_t hap : win_top[wi]) biallelic = biallelic && n.gn->hap_gt[hap] <= 1;
+                        auto it = biallelic ? gs_memo.find(gt0[rr]) : gs_memo.end();
+                        if (it != gs_memo.end()) {
+                            std::memcpy(gid.data() + rr * n_gt, gid.data() + (size_t)it->second * n_gt, n_gt);
+                            std::memcpy(order.data() + rr * n_gt, order.data() + (size_t)it->second * n_gt, n_gt);
+                        } else {
+                            (void)genotype_strings(n, win_gts[wi], gid.data() + rr * n_gt, order.data() + rr * n_gt);     // <= 128 strings: always fits
+                            if (biallelic) gs_memo.emplace(gt0[rr], (uint32_t)rr);
+                        }
+                        win_rows[wi].push_back((uint32_t)rr);
+                    }
+                });
+                std::vector<size_t> win_step0(nw + 1, 0);
+                for (size_t wi = 0; wi < nw; ++wi) win_step0[wi + 1] = win_step0[wi] + 2 * win_rows[wi].size();
+                n_steps = win_step0[nw];
+                if (n_steps) {
+                    std::vector<long double> pw(n_steps * 2 * stride);
+                    std::vector<uint32_t> row(n_steps, 0);
+                    std::vector<uint8_t> restart(n_steps, 0);
+                    std::vector<uint64_t> fwd(n_rows, 0), bwd(n_rows, 0);
+                    std::vector<vgmi_hmm_chain> chains;
+                    for (size_t wi = 0; wi < nw; ++wi) {
+                        const size_t m = win_rows[wi].size();
+                        if (!m) continue;
+                        chains.push_back(vgmi_hmm_chain{win_step0[wi], m, 0, 0});
+                        chains.push_back(vgmi_hmm_chain{win_step0[wi] + m, m, 0, 0});
+                    }
+                    over_windows(g_phase.pass_b, [&](size_t wi) {
+                        const size_t m = win_rows[wi].size();
+                        if (!m) return;
+                        const size_t step0 = win_step0[wi];
+                        constexpr uint32_t kMemo = 4096;      // the tables of powers are a function of the distance alone
+                        std::vector<long double> memo((size_t)kMemo * 2 * stride);
+                        std::vector<uint8_t> memo_have(kMemo, 0);
+                        auto powers = [&](long double* dst, uint32_t distance) {
+                            if (distance < kMemo && memo_have[distance]) {
+                                std::memcpy(dst, &memo[(size_t)distance * 2 * stride], 2 * stride * sizeof(long double));
+                                return;
+                            }
+                            long double recomb, no_recomb;
+                            std::tie(recomb, no_recomb) = transition_probabilities(distance, (uint16_t)n_hap_);
+                            for (uint32_t k = 0; k < stride; ++k) {
+                                dst[k] = std::pow(no_recomb, (int32_t)k);
+                                dst[stride + k] = std::pow(recomb, (int32_t)k);
+                            }
+                            if (distance < kMemo) {
+                                std::memcpy(&memo[(size_t)distance * 2 * stride], dst, 2 * stride * sizeof(long double));
+                                memo_have[distance] = 1;
+                            }
+                        };
+                        const std::vector<Seen>& sn = seen[wi];
+                        size_t j = 0;
+                        for (size_t q = 0; q < sn.size(); ++q) {
+                            if (sn[q].row < 0) continue;
+                            const size_t fs = step0 + j, bs = step0 + m + (m - 1 - j);
+                            powers(pw.data() + fs * 2 * stride, sn[q].start - (q ? sn[q - 1].end : 0u));
+                            restart[fs] = (q == 0 || sn[q - 1].row < 0) ? 1 : 0;
+                            row[fs] = (uint32_t)sn[q].row;
+                            powers(pw.data() + bs * 2 * stride, (q + 1 < sn.size() ? sn[q + 1].start : 0u) - sn[q].end);
+                            restart[bs] = (q + 1 == sn.size() || sn[q + 1].row < 0) ? 1 : 0;
+                            row[bs] = (uint32_t)sn[q].row;
+                            fwd[sn[q].row] = fs;
+                            bwd[sn[q].row] = bs;
+                            ++j;
+                        }
+                    });
+                    t_b = since_begin();
+                    const long double uniform = 1.0L / (long double)n_gt;
+                    dev_check(vgmi_hmm_part_calls(ph.p, 2, keep_mat.data(), 1, row.data(), restart.data(), pw.data(), n_steps, &uniform, chains.data(),
+                                                  (uint32_t)chains.size(), gid.data(), order.data(), fwd.data(), bwd.data(), prob.data(), winner.data()),
+                              "device HMM recursion: ");
+                } else {
+                    t_b = since_begin();
+                }
+                t_calls = since_begin();
+            }
+            for (int64_t v = dev_first.load(); ta < v && !dev_first.compare_exchange_weak(v, ta);) {}
+            for (int64_t v = dev_last.load(); t_calls > v && !dev_last.compare_exchange_weak(v, t_calls);) {}
+            // 8. the calls' tallies on the device (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists)
+            std::vector<uint32_t> tally;
+            std::vector<uint8_t> tally_uniq;
+            static const bool device_tallies = !(getenv("VGH_DEVICE_TALLIES") && getenv("VGH_DEVICE_TALLIES")[0] == '0');
+            if (device_tallies && n_steps) {
+                tally.resize(4 * n_rows);
+                tally_uniq.resize(n_rows);
+                dev_check(vgmi_hmm_tallies_select(dev_, n_rows, e_begin.data(), e_count.data(), row_win.data(), winner.data(), (uint32_t)n_gt, pos_a.data(),
+                                                  pos_b.data(), n_used, (uint32_t)nw, win_used8.data(), tally.data(), tally_uniq.data()),
+                          "device tallies: ");
+            }
+            // 9. the lines
+            over_windows(g_phase.pass_c, [&](size_t wi) {
+                emit_windows_done += !win_rows[wi].empty();
+                const Chrom& chr = *tasks[wi].chr;
+                if (tally.empty()) {
+                    WindowWork w;
+                    w.chr = tasks[wi].chr;
+                    w.n_gt = n_gt;
+                    w.genotypes = win_gts[wi];
+                    w.top = win_top[wi];
+                    std::vector<long double> pr(win_rows[wi].size());
+                    std::vector<uint32_t> wn(win_rows[wi].size());
+                    for (size_t q = 0; q < win_rows[wi].size(); ++q) {
+                        w.nodes.push_back(row_node[win_rows[wi][q]]);
+                        pr[q] = prob[win_rows[wi][q]];
+                        wn[q] = winner[win_rows[wi][q]];
+                    }
+                    window_finish(w, pr.data(), wn.data(), r);
+                    make_piece(wi);
+                    return;
+                }
+                // written straight from what came back: the called pair, the posterior, the tallies (make_piece's lines)
+                piece_done[wi] = 1;
+                auto vc = g_.vcf_info.find(chr.name);
+                if (vc == g_.vcf_info.end()) return;
+                const auto& sites = vc->second;
+                auto site = win_rows[wi].empty() ? sites.end() : sites.lower_bound(chr.nodes[row_node[win_rows[wi][0]]].start);
+                std::string out;
+                for (const uint32_t rw : win_rows[wi]) {
+                    const Node& node = chr.nodes[row_node[rw]];
+                    while (site != sites.end() && site->first < node.start) ++site;
+                    if (winner[rw] >= n_gt) continue;            // no entry with a positive posterior: no call
+                    if (site == sites.end() || site->first != node.start) continue;
+                    const uint64_t ga = node.gn->hap_gt[win_top[wi][pos_a[winner[rw]]]], gb = node.gn->hap_gt[win_top[wi][pos_b[winner[rw]]]];
+                    if (ga == 0 && gb == 0) continue;
+                    const auto& fields = site->second;
+                    for (size_t i = 0; i < 9; i++) {
+                        if (i == 0) out += fields[i];
+                        else if (i == 6) out += "\tPASS";
+                        else if (i < 8) { out += '\t'; out += fields[i]; }
+                        else out += "\tGT:GQ:GPP:NAK:CAK:UK";
+                    }
+                    out += '\t';
+                    const long double pr = prob[rw];
+                    const float gq = phred_scaled(pr);
+                    if (gq < cfg.min_gq) out += "./.";
+                    else {
+                        append_uint(out, ga);
+                        out += '/';
+                        append_uint(out, gb);
+                    }
+                    out += ':';
+                    append_fixed1(out, gq);
+                    out += ':';
+                    append_fixed1(out, pr);
+                    out += ':';
+                    const uint32_t* tl = &tally[4 * rw];
+                    append_uint(out, tl[0]);
+                    out += ',';
+                    append_uint(out, tl[2]);
+                    out += ':';
+                    append_fixed1(out, tl[0] ? static_cast<float>((uint64_t)tl[1]) / (float)(uint64_t)tl[0] : 0.0f);
+                    out += ',';
+                    append_fixed1(out, tl[2] ? static_cast<float>((uint64_t)tl[3]) / (float)(uint64_t)tl[2] : 0.0f);
+                    out += ':';
+                    append_uint(out, tally_uniq[rw]);
+                    out += '\n';
+                }
+                pieces[wi] = std::move(out);
+            });
+            emitted_on_device = true;
+            if (g_phase_on) {
+                std::fprintf(stderr, "[varigraph-mi] HMM with haplotypes selected per window (%zu windows, %zu rows, %zu nodes pruned, %zu nodes scored by the host, %zu scored "
+                             "again on the device): support %.3f, draws (host) %.3f, emission kernel %.3f, prune + sequence checks (host) %.3f, rows fixed on the device %.3f, "
+                             "strings + step tables (host) %.3f, recursion + posterior %.3f\n",
+                             nw, n_rows, n_pruned, n_host_rows, n_fixed_rows, (t_sup - ta) * 1e-9, (t_draw - t_sup) * 1e-9, (t_emit - t_draw) * 1e-9, (t_a - t_emit) * 1e-9,
+                             (t_rows - t_a) * 1e-9, (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
+                std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: 1 parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
+                             since_begin() * 1e-9 - tb0, nw, tasks.size());
+            }
         }
     }
     if (!emitted_on_device) {

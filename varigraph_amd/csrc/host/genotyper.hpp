@@ -199,6 +199,9 @@ private:
     std::vector<uint16_t> hap_ids_;   // the keys of g_.hap_names in their order
     std::atomic<bool> lists_whole_{true};   // no node's k-mer list has been pruned (the device's emission path needs whole, contiguous lists)
     bool entries_uploaded_ = false;         // the graph's per-entry multiplicity and haplotype bits are on dev_
+    // the host pruned a k-mer list on its own since the device last had the lists' state (vgmi_hmm_alive_upload): a sample whose
+    // haplotypes are selected per window on the device uploads the lists first
+    std::atomic<bool> alive_stale_{false};
     bool emit_device_off_ = false;          // the device's emission path turned out not to apply to this graph
     std::vector<uint64_t> packed_;    // per node-list entry: coverage (this sample) | multiplicity << 8 | haplotype bits << 16
 };

@@ -528,6 +528,7 @@ void vgmi_destroy(vgmi_ctx* c)
     for (auto& b : c->hmm_blocks) (void)hipFree(b.first);
     if (c->d_hmm_entries) (void)hipFree(c->d_hmm_entries);
     if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
+    if (c->d_hmm_alive) (void)hipFree(c->d_hmm_alive);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

@@ -221,13 +221,88 @@ int vgmi_hmm_entries_upload(vgmi_ctx* c, const uint64_t* entries, size_t n)
     HIPCHK(c, hipSetDevice(c->device));
     if (c->d_hmm_entries) (void)hipFree(c->d_hmm_entries);
     if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
+    if (c->d_hmm_alive) (void)hipFree(c->d_hmm_alive);
     c->d_hmm_entries = nullptr;
     c->d_hmm_cov = nullptr;
+    c->d_hmm_alive = nullptr;
     c->hmm_n_entries = n;
     if (hipMalloc(reinterpret_cast<void**>(&c->d_hmm_entries), (n ? n : 1) * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_hmm_cov), n ? n : 1) != hipSuccess)
+        hipMalloc(reinterpret_cast<void**>(&c->d_hmm_cov), n ? n : 1) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->d_hmm_alive), n ? n : 1) != hipSuccess)
         return fail(c, VGMI_E_NOMEM, "HMM emissions: not enough device memory for the node-list entries");
     if (n) HIPCHK(c, hipMemcpy(c->d_hmm_entries, entries, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->d_hmm_alive, 1, n ? n : 1));      // a fresh graph: every entry is in its node's list
+    return VGMI_OK;
+}
+
+// ---- which entries are still in their node's list (src/genotype.cpp:815-818: the forward pass shortens a node's list to the k-mers a
+// selected haplotype carries, and ConstructIndex::reset does not restore it).  One byte per entry, next to the entries; all ones after
+// vgmi_hmm_entries_upload.  vgmi_hmm_emissions_select clears bytes; the host's lists are uploaded when the host pruned on its own.
+int vgmi_hmm_alive_upload(vgmi_ctx* c, const uint8_t* alive, size_t n)
+{
+    if (!c || (n && !alive)) return VGMI_E_INVALID;
+    if (!c->d_hmm_alive || n != c->hmm_n_entries) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n) HIPCHK(c, hipMemcpy(c->d_hmm_alive, alive, n, hipMemcpyHostToDevice));
+    return VGMI_OK;
+}
+
+int vgmi_hmm_alive_fetch(vgmi_ctx* c, uint8_t* alive_out, size_t n)
+{
+    if (!c || (n && !alive_out)) return VGMI_E_INVALID;
+    if (!c->d_hmm_alive || n != c->hmm_n_entries) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n) HIPCHK(c, hipMemcpy(alive_out, c->d_hmm_alive, n, hipMemcpyDeviceToHost));
+    return VGMI_OK;
+}
+
+namespace {
+// rows of a per-window call: inside the uploaded entries, each in a window that exists
+int hmm_check_rows(vgmi_ctx* c, const char* what, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                   uint32_t n_windows)
+{
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (entry_begin[r] > c->hmm_n_entries || entry_count[r] > c->hmm_n_entries - entry_begin[r] || row_win[r] >= n_windows)
+            return fail(c, VGMI_E_INVALID, what);
+    return VGMI_OK;
+}
+}  // namespace
+
+// ---- selection support (src/genotype.cpp:500-560, haplotype_selection's sums): support_out[w * n_hap + hap] = sum of c over the alive
+// entries of window w's rows with c > 1 and multiplicity <= 1 that haplotype `hap` carries.  The gamma draws stay on the host.
+int vgmi_hmm_support(vgmi_ctx* c, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
+                     const uint32_t* row_win, uint32_t* support_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win)) || (n_windows && !support_out)) return VGMI_E_INVALID;
+    if (n_hap < 1 || n_hap > 48) return fail(c, VGMI_E_INVALID, "HMM support: 1..48 haplotypes");
+    if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM support: upload the entries and the sample's coverage first");
+    if (int rc = hmm_check_rows(c, "HMM support: a row outside the entries or the windows", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_windows == 0) return VGMI_OK;
+    const size_t b_sup = (size_t)n_windows * n_hap * 4;
+    if (n_rows == 0) {
+        memset(support_out, 0, b_sup);
+        return VGMI_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_cnt = up(n_rows * 8), o_win = up(o_cnt + n_rows * 4), o_sup = up(o_win + n_rows * 4), total = up(o_sup + b_sup);
+    size_t d_bytes = 0;
+    uint8_t* d = hmm_block_take(c, total, d_bytes);
+    if (!d) return fail(c, VGMI_E_NOMEM, "HMM support: not enough device memory");
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, entry_begin, n_rows * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_cnt, entry_count, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_win, row_win, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d + o_sup, 0, b_sup, st);
+    if (e == hipSuccess)
+        e = launch_hmm_support(c->d_hmm_entries, c->d_hmm_cov, c->d_hmm_alive, reinterpret_cast<const uint64_t*>(d), reinterpret_cast<const uint32_t*>(d + o_cnt),
+                               reinterpret_cast<const uint32_t*>(d + o_win), n_rows, n_hap, reinterpret_cast<uint32_t*>(d + o_sup), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(support_out, d + o_sup, b_sup, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (st) (void)hipStreamDestroy(st);
+    hmm_block_give(c, d, d_bytes);
+    HIPCHK(c, e);
     return VGMI_OK;
 }
 
@@ -257,9 +332,58 @@ int vgmi_hmm_emissions(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const uint8_
 
 // ... for genotypes of `ploidy` haplotypes (2 .. 4): pos[g * ploidy + q] = the place in `used` of genotype g's q-th haplotype; tables holds
 // (ploidy + 1) x 256 terms (geometric for h = 0, Poisson(ave * h) for h = 1 .. ploidy)
+namespace {
+struct HmmSelect {      // haplotypes selected per window (vgmi_hmm_emissions_select)
+    uint32_t n_windows;
+    const uint8_t* win_used;          // n_windows x n_used
+    const uint64_t* win_top_mask;     // n_windows
+    const uint32_t* row_win;          // n_rows
+};
+int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t* used, const uint8_t* pos, uint64_t top_mask,
+                       uint32_t bit_len, float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin,
+                       const uint32_t* entry_count, const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out, const HmmSelect* sel);
+}  // namespace
+
 int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t* used, const uint8_t* pos, uint64_t top_mask,
                               uint32_t bit_len, float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin,
                               const uint32_t* entry_count, const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    return hmm_emissions_impl(c, n_gt, ploidy, n_used, used, pos, top_mask, bit_len, ave, lower, upper, tables, n_rows, entry_begin, entry_count, gt0, n_kept_out,
+                              flags_out, out, nullptr);
+}
+
+// ---- emission scores with the haplotypes selected per window (-n below the panel's haplotypes, a diploid sample) ----------------------
+// replaces: hidden_states(..., filter = true) + observable_states (src/genotype.cpp:640-830 with the prune of :673-686 and :815-818,
+// :960-1000).  The genotype list has the same shape in every window -- genotype g is the pair (used_w[pos_a[g]], used_w[pos_b[g]]) --
+// and row r takes the haplotypes win_used[n_used * row_win[r] ..] and the mask win_top_mask[row_win[r]] of its window.  A row is the
+// RANGE [entry_begin, +entry_count) of what remains of its node's list plus the alive bytes; entries a selection does not carry die.
+int vgmi_hmm_emissions_select(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_windows,
+                              const uint8_t* win_used, const uint64_t* win_top_mask, uint32_t bit_len, float ave, double lower, double upper,
+                              const void* tables, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                              const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    if (!c || !pos_a || !pos_b || !out || n_gt < 1 || n_gt > 128) return VGMI_E_INVALID;
+    if (n_windows < 1 || !win_used || !win_top_mask || (n_rows && !row_win)) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their selections");
+    if (n_used < 1 || n_used > 16 || bit_len < 1 || bit_len > 6) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes over 1..16 haplotypes, 1..6 bytes of haplotype bits");
+    if (!c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
+    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
+        if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a selected haplotype outside the haplotype bits");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (row_win[r] >= n_windows) return fail(c, VGMI_E_INVALID, "HMM emissions: a row of a window that does not exist");
+    std::vector<uint8_t> pos(2 * (size_t)n_gt);
+    for (uint32_t g = 0; g < n_gt; ++g) {
+        pos[2 * g] = pos_a[g];
+        pos[2 * g + 1] = pos_b[g];
+    }
+    const HmmSelect sel{n_windows, win_used, win_top_mask, row_win};
+    return hmm_emissions_impl(c, n_gt, 2, n_used, win_used, pos.data(), 0, bit_len, ave, lower, upper, tables, n_rows, entry_begin, entry_count, gt0, n_kept_out,
+                              flags_out, out, &sel);
+}
+
+namespace {
+int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t* used, const uint8_t* pos, uint64_t top_mask,
+                       uint32_t bit_len, float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin,
+                       const uint32_t* entry_count, const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out, const HmmSelect* sel)
 {
     if (!c || !used || !pos || !tables || !out) return VGMI_E_INVALID;
     if (ploidy < 2 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM emissions: genotypes of 2..4 haplotypes");
@@ -287,10 +411,14 @@ int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint3
     part->n_rows = n_rows;
     part->n_gt = n_gt;
     const size_t b_obs = (size_t)(n_rows ? n_rows : 1) * n_gt * 16;
-    uint8_t* d_small = nullptr;     // entry_begin | entry_count | gt0 | tables | n_kept | flags
+    uint8_t* d_small = nullptr;     // entry_begin | entry_count | gt0 | tables | n_kept | flags | (per-window selection: row_win | win_used | win_top_mask)
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t n_win = sel ? sel->n_windows : 0;
     const size_t o_eb = 0, o_ec = up(o_eb + n_rows * 8), o_g0 = up(o_ec + n_rows * 4), o_tab = up(o_g0 + n_rows * 2), o_nk = up(o_tab + n_tab * 16),
-                 o_fl = up(o_nk + n_rows * 4), total = up(o_fl + n_rows) + 256;
+                 o_fl = up(o_nk + n_rows * 4), o_rw = up(o_fl + n_rows), o_wu = up(o_rw + (sel ? n_rows * 4 : 0)), o_wm = up(o_wu + n_win * 16),
+                 total = up(o_wm + n_win * 8) + 256;
+    std::vector<uint8_t> wu16(n_win * 16, 0);      // a window's haplotypes in 16 bytes, whatever n_used
+    for (size_t w = 0; w < n_win; ++w) memcpy(&wu16[w * 16], sel->win_used + w * n_used, n_used);
     hipStream_t st = nullptr;
     size_t small_bytes = 0;
     part->d_obs = hmm_block_take(c, b_obs, part->obs_bytes);
@@ -307,6 +435,9 @@ int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint3
     if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_ec, entry_count, n_rows * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_g0, gt0, n_rows * 2, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_tab, tables, n_tab * 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && sel && n_rows) e = hipMemcpyAsync(d_small + o_rw, sel->row_win, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && sel) e = hipMemcpyAsync(d_small + o_wu, wu16.data(), n_win * 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && sel) e = hipMemcpyAsync(d_small + o_wm, sel->win_top_mask, n_win * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         HmmEmitParams P{};
         P.packed = c->d_hmm_entries;
@@ -331,6 +462,12 @@ int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint3
         P.obs = part->d_obs;
         P.n_kept = reinterpret_cast<uint32_t*>(d_small + o_nk);
         P.flags = d_small + o_fl;
+        if (sel) {
+            P.row_win = reinterpret_cast<const uint32_t*>(d_small + o_rw);
+            P.win_used = d_small + o_wu;
+            P.win_top_mask = reinterpret_cast<const unsigned long long*>(d_small + o_wm);
+            P.alive = c->d_hmm_alive;
+        }
         e = launch_hmm_emissions(P, n_rows, st);
         part->emit = P;
     }
@@ -350,6 +487,7 @@ int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint3
     *out = part;
     return VGMI_OK;
 }
+}  // namespace
 
 // Rows the emission launch flagged (bit 0: an under-covered multi-copy k-mer that a haplotype of the window carries -- the reference
 // then consults the haplotype's sequence, src/genotype.cpp:760-800), scored again with what the host found there: entry fix_j[i] of
@@ -592,6 +730,57 @@ int vgmi_hmm_tallies(vgmi_ctx* c, uint64_t n_rows, const uint64_t* entry_begin, 
         e = launch_hmm_tally(reinterpret_cast<const unsigned long long*>(c->d_hmm_entries), c->d_hmm_cov, reinterpret_cast<const uint64_t*>(d),
                              reinterpret_cast<const uint32_t*>(d + o_cnt), reinterpret_cast<const uint32_t*>(d + o_win), d + o_hap, n_gt, n_hap, sel_mask, n_rows,
                              reinterpret_cast<uint32_t*>(d + o_out), d + o_uni, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + o_out, n_rows * 16, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(unique_out, d + o_uni, n_rows, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (st) (void)hipStreamDestroy(st);
+    hmm_block_give(c, d, d_bytes);
+    HIPCHK(c, e);
+    return VGMI_OK;
+}
+
+// ---- the calls' tallies with the haplotypes selected per window (src/genotype.cpp:1387-1414 on the pruned lists): the called genotype
+// winner[i] of a row of window w is the pair (win_used[n_used w + pos_a[g]], win_used[n_used w + pos_b[g]]); only alive entries count,
+// for the haplotypes' k-mers and for the count of single-copy k-mers alike.
+int vgmi_hmm_tallies_select(vgmi_ctx* c, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                            const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used, uint32_t n_windows,
+                            const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win || !winner || !out || !unique_out)) || !pos_a || !pos_b || !win_used) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16 || n_windows < 1) return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes over 1..16 haplotypes");
+    if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM tallies: upload the entries and the sample's coverage first");
+    for (uint32_t g = 0; g < n_gt; ++g)
+        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM tallies: a genotype names a haplotype outside the list");
+    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
+        if (win_used[i] >= 48) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
+    if (int rc = hmm_check_rows(c, "HMM tallies: a row outside the entries or the windows", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_rows == 0) return VGMI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint8_t> wu16((size_t)n_windows * 16, 0), pos_ab(2 * (size_t)n_gt);
+    for (size_t w = 0; w < n_windows; ++w) memcpy(&wu16[w * 16], win_used + w * n_used, n_used);
+    for (uint32_t g = 0; g < n_gt; ++g) {
+        pos_ab[2 * g] = pos_a[g];
+        pos_ab[2 * g + 1] = pos_b[g];
+    }
+    // one block: entry_begin | entry_count | row_win | winner | out | unique | pos_ab | win_used
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_cnt = n_rows * 8, o_rw = o_cnt + n_rows * 4, o_win = o_rw + n_rows * 4, o_out = o_win + n_rows * 4, o_uni = o_out + n_rows * 16,
+                 o_pos = up(o_uni + n_rows), o_wu = up(o_pos + pos_ab.size()), total = up(o_wu + wu16.size());
+    size_t d_bytes = 0;
+    uint8_t* d = hmm_block_take(c, total, d_bytes);
+    if (!d) return fail(c, VGMI_E_NOMEM, "HMM tallies: not enough device memory");
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, entry_begin, n_rows * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_cnt, entry_count, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_rw, row_win, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_win, winner, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pos, pos_ab.data(), pos_ab.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_wu, wu16.data(), wu16.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_hmm_tally_select(c->d_hmm_entries, c->d_hmm_cov, c->d_hmm_alive, reinterpret_cast<const uint64_t*>(d), reinterpret_cast<const uint32_t*>(d + o_cnt),
+                                    reinterpret_cast<const uint32_t*>(d + o_rw), reinterpret_cast<const uint32_t*>(d + o_win), d + o_pos, d + o_wu, n_gt, n_rows,
+                                    reinterpret_cast<uint32_t*>(d + o_out), d + o_uni, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + o_out, n_rows * 16, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(unique_out, d + o_uni, n_rows, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -70,6 +70,7 @@ struct vgmi_ctx {
     // finished would wait for the parts still running (vgmi_hmm_calls_part); a sample reuses the last sample's blocks
     unsigned long long* d_hmm_entries = nullptr;     // vgmi_hmm_entries_upload: per node-list entry f << 8 | haplotype bits << 16
     uint8_t* d_hmm_cov = nullptr;                    // vgmi_hmm_sample_upload: this sample's coverage per entry
+    uint8_t* d_hmm_alive = nullptr;                  // per entry: still in its node's list (vgmi_hmm_alive_upload; pruned by vgmi_hmm_emissions_select)
     size_t hmm_n_entries = 0;
     std::mutex hmm_mu;
     std::vector<std::pair<uint8_t*, size_t>> hmm_blocks;   // not in use

@@ -450,7 +450,8 @@ __global__ __launch_bounds__(256) void hmm_posterior_big_kernel(HmmPostParams P)
 // h = 0, Poisson(ave * h) otherwise, libm values tabulated by the host per sample -- and the lane multiplies it onto its product
 // in the reference's long double (vg_x80.h).  A k-mer that is under-covered, multi-copy and carried makes the reference check
 // the haplotype's SEQUENCE (:760-800): such a node is flagged and scored by the host.  Every k-mer list must be whole (no
-// selected-haplotype pruning: all haplotypes are selected), which the caller guarantees and bit 1 of the flags verifies.
+// selected-haplotype pruning: all haplotypes are selected), which the caller guarantees and bit 1 of the flags verifies -- unless the
+// haplotypes are selected per window (SELECT below): then the kernel prunes, as the reference's forward pass does.
 __device__ __forceinline__ uint32_t hmm_most_likely_depth(uint32_t h, uint32_t c, uint32_t f, float ave, double upper)
 {
     if (f == 1u) return c;
@@ -460,6 +461,11 @@ __device__ __forceinline__ uint32_t hmm_most_likely_depth(uint32_t h, uint32_t c
     return c;
 }
 
+// SELECT (vgmi_hmm_emissions_select): -n picks fewer haplotypes than the panel has, so every window has drawn its own.  The row names its
+// window, the window supplies `used` and the mask (ids up to 46: every shift of the bits is 64 bits wide); an entry that is no longer in
+// its node's list is passed over, and an entry no selected haplotype carries LEAVES the list here, for good (src/genotype.cpp:673-686,
+// 815-818: the next window, the next sample score what is left).  Every lane takes the same decisions; lane 0 writes them down.
+template <bool SELECT>
 __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
 {
     __shared__ uint64_t s_tm[1280];      // (ploidy + 1) x 256 terms: up to four haplotypes per genotype
@@ -477,6 +483,13 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     const uint64_t e0 = P.entry_begin[rowi];
     const uint32_t cnt = P.entry_count[rowi], gt0 = P.gt0[rowi];
     const bool active = g < P.n_gt;
+    unsigned long long top_mask = P.top_mask;
+    const uint8_t* wused = nullptr;
+    if (SELECT) {
+        const uint32_t w = P.row_win[rowi];
+        top_mask = P.win_top_mask[w];
+        wused = P.win_used + (size_t)w * 16u;
+    }
     const uint32_t pa = P.pos_a[active ? g : 0u], pb = P.pos_b[active ? g : 0u];
     const uint32_t pc = P.ploidy > 2u ? P.pos_more[0][active ? g : 0u] : 0u, pd = P.ploidy > 3u ? P.pos_more[1][active ? g : 0u] : 0u;
     VgN80 prod;
@@ -484,19 +497,25 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     prod.e = VG_X80_BIAS;
     uint32_t kept = 0, flag = 0;
     for (uint32_t j = 0; j < cnt; ++j) {
+        if (SELECT && P.alive[e0 + j] == 0) continue;      // pruned by an earlier window's or sample's selection
         const unsigned long long w = P.packed[e0 + j];
         const uint32_t c = P.cov[e0 + j], f = (uint32_t)(w >> 8) & 0xFFu;
         const unsigned long long bits = w >> 16;
         const uint32_t lb = (uint32_t)(bits >> (P.bl8 - 1u)) & 1u;
-        if ((bits & P.top_mask) == 0) {      // the host would drop it from the list: this path does not prune
-            flag |= 2u;
+        if ((bits & top_mask) == 0) {
+            if (SELECT) {
+                if (g == 0 && !P.fix_rows) P.alive[e0 + j] = 0;      // the prune
+            } else {
+                flag |= 2u;      // the host would drop it from the list: this path does not prune
+            }
             continue;
         }
         ++kept;
         const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
         uint32_t om = 0;
         for (uint32_t p = 0; p < P.n_used; ++p) {
-            const uint32_t one = (in_interval && ((gt0 >> p) & 1u)) ? 1u : (uint32_t)(bits >> P.used[p]) & 1u;
+            const uint32_t hap = SELECT ? (uint32_t)wused[p] : (uint32_t)P.used[p];
+            const uint32_t one = (in_interval && ((gt0 >> p) & 1u)) ? 1u : (uint32_t)((bits >> hap) & 1ull);
             om |= one << p;
         }
         if ((double)c < P.lower && f >= 2u && om != 0) flag |= 1u;
@@ -565,6 +584,87 @@ __global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long
     uniq[r] = (uint8_t)u;
 }
 
+// ... with haplotypes selected per window (vgmi_hmm_tallies_select): the called genotype's haplotypes are the row's window's, and only
+// the entries still in the node's list count -- the unique-k-mer count as well (posterior() walks the pruned list)
+__global__ __launch_bounds__(256) void hmm_tally_select_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
+                                                               const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
+                                                               const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win,
+                                                               const uint32_t* __restrict__ winner, const uint8_t* __restrict__ pos_ab,
+                                                               const uint8_t* __restrict__ win_used, uint32_t n_gt, uint64_t n_rows,
+                                                               uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_rows) return;
+    uint32_t num_a = 0, sum_a = 0, num_b = 0, sum_b = 0, u = 0;
+    const uint32_t g = winner[r];
+    if (g < n_gt) {
+        const uint8_t* used = win_used + (size_t)row_win[r] * 16u;
+        const uint32_t ha = used[pos_ab[2u * g]], hb = used[pos_ab[2u * g + 1u]];
+        const uint64_t e0 = entry_begin[r];
+        const uint32_t cnt = entry_count[r];
+        for (uint32_t j = 0; j < cnt; ++j) {
+            if (alive[e0 + j] == 0) continue;
+            const unsigned long long w = packed[e0 + j];
+            const uint32_t c = cov[e0 + j];
+            const unsigned long long bits = w >> 16;
+            if (((uint32_t)(w >> 8) & 0xFFu) <= 1u && u < 255u) ++u;
+            if ((bits >> ha) & 1ull) { ++num_a; sum_a += c; }
+            if ((bits >> hb) & 1ull) { ++num_b; sum_b += c; }
+        }
+    }
+    out[4 * r] = num_a;
+    out[4 * r + 1] = sum_a;
+    out[4 * r + 2] = num_b;
+    out[4 * r + 3] = sum_b;
+    uniq[r] = (uint8_t)u;
+}
+
+// ---- selection support of the windows (src/genotype.cpp:500-560: what haplotype_selection sums before the gamma draws) ---------------
+// support[w][hap] = sum of c over the alive entries of window w's rows with c > 1 and multiplicity <= 1 that haplotype `hap` carries.
+// 32-bit integer sums: any order of additions gives the host's number.  A workgroup takes kSupportRows consecutive rows, a wavefront a
+// row at a time, a lane an entry; the sums of a workgroup are gathered in LDS and leave it as one atomic per haplotype and window (rows
+// come window after window, so a workgroup nearly always sees one window).
+constexpr uint32_t kSupportRows = 64;
+__global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
+                                                          const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
+                                                          const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win, uint64_t n_rows,
+                                                          uint32_t n_hap, uint32_t* __restrict__ support)
+{
+    __shared__ uint32_t s_sup[48];
+    const uint64_t r0 = (uint64_t)blockIdx.x * kSupportRows;
+    const uint64_t r1 = r0 + kSupportRows < n_rows ? r0 + kSupportRows : n_rows;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const unsigned long long hap_mask = (1ull << n_hap) - 1ull;      // n_hap <= 48
+    uint64_t ra = r0;
+    while (ra < r1) {      // the rows [ra, rb) of one window
+        const uint32_t w = row_win[ra];
+        uint64_t rb = ra + 1;
+        while (rb < r1 && row_win[rb] == w) ++rb;
+        if (threadIdx.x < 48u) s_sup[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint64_t r = ra + wave; r < rb; r += 4) {
+            const uint64_t e0 = entry_begin[r];
+            const uint32_t cnt = entry_count[r];
+            for (uint32_t j = lane; j < cnt; j += 64u) {
+                if (alive[e0 + j] == 0) continue;
+                const unsigned long long word = packed[e0 + j];
+                const uint32_t c = cov[e0 + j];
+                if (c <= 1u || ((uint32_t)(word >> 8) & 0xFFu) > 1u) continue;
+                unsigned long long bits = (word >> 16) & hap_mask;
+                while (bits) {
+                    const uint32_t hap = (uint32_t)__ffsll((long long)bits) - 1u;
+                    bits &= bits - 1ull;
+                    atomicAdd(&s_sup[hap], c);
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
+        __syncthreads();
+        ra = rb;
+    }
+}
+
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,
                             const uint8_t* hap_ab, uint32_t n_gt, uint32_t n_hap, unsigned long long sel_mask, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
                             hipStream_t st)
@@ -585,7 +685,32 @@ hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uin
 hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(hmm_emissions_kernel, dim3((uint32_t)n_rows), dim3(128), 0, st, P);
+    if (P.row_win) {
+        if (!P.win_used || !P.win_top_mask || !P.alive) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(hmm_emissions_kernel<true>, dim3((uint32_t)n_rows), dim3(128), 0, st, P);
+    } else {
+        hipLaunchKernelGGL(hmm_emissions_kernel<false>, dim3((uint32_t)n_rows), dim3(128), 0, st, P);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_hmm_support(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
+                              const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    if (n_hap < 1 || n_hap > 48) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hmm_support_kernel, dim3((uint32_t)((n_rows + kSupportRows - 1) / kSupportRows)), dim3(256), 0, st, packed, cov, alive, entry_begin,
+                       entry_count, row_win, n_rows, n_hap, support);
+    return hipGetLastError();
+}
+
+hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
+                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab,
+                                   const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(hmm_tally_select_kernel, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, alive, entry_begin, entry_count, row_win,
+                       winner, pos_ab, win_used, n_gt, n_rows, out, uniq);
     return hipGetLastError();
 }
 

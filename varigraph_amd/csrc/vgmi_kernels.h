@@ -284,8 +284,25 @@ struct HmmEmitParams {
     const uint32_t* fix_off;            // per fixed row: its stretch of (fix_j, fix_mask), ascending in fix_j
     const uint32_t* fix_j;              // 32 bits like entry_count and the kernel's j
     const uint16_t* fix_mask;
+    // haplotypes selected per window (-n below the panel's haplotypes, a diploid sample: vgmi_hmm_emissions_select).  Null row_win: the
+    // one selection above serves every row.  Else row r belongs to window row_win[r], whose haplotypes are win_used[16 w ..] (n_used of
+    // them, ids up to 46) with the mask win_top_mask[w]; `alive` says which entries are still in their node's list, and an alive entry
+    // no selected haplotype carries is marked dead there -- the forward pass's prune (src/genotype.cpp:673-686, 815-818)
+    const uint32_t* row_win;
+    const uint8_t* win_used;
+    const unsigned long long* win_top_mask;
+    uint8_t* alive;
 };
 hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStream_t st);
+// selection support of every window (src/genotype.cpp:500-560): support[w * n_hap + hap] += c over the alive entries of the window's rows
+// with c > 1 and multiplicity <= 1 whose bit `hap` is set; `support` is zeroed by the caller
+hipError_t launch_hmm_support(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
+                              const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st);
+// the calls' tallies with per-window selection: genotype g of a row of window w is (win_used[16 w + pos_a[g]], win_used[16 w + pos_b[g]]);
+// only alive entries count
+hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
+                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab,
+                                   const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
 hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uint8_t* src, uint32_t n_gt, uint64_t n, hipStream_t st);
 size_t hmm_lds_bytes(uint32_t n_gt, uint32_t ploidy);
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,
