@@ -316,14 +316,18 @@ def test_command_line_with_selection_on_the_device_equals_the_reference(extra, s
     """`varigraph-mi genotype -n 5 --use-depth` over a 13-haplotype graph, three samples in one run: every VCF is the deterministic
     reference build's byte for byte, the VGH_TIMING log shows the emissions on the device with haplotypes selected per window for every
     window of all three samples, and VGH_HMM_SELECT_DEVICE=0 (the host's preparation) writes the same bytes.  The reference's VCFs hold
-    at least 200 lines each ("a few hundred": an empty result must not pass)."""
+    at least 200 lines each ("a few hundred": an empty result must not pass).  VGH_HMM_FIX_DEVICE=0 (flagged nodes scored by the host: 50 to
+    58 per sample of this cohort, 1 to 3 under --sv; none of them is scored again on the device in a default run) and VGH_DEVICE_TALLIES=0
+    (the calls' tallies walked by the host) keep the selection on the device and write the same bytes."""
     from test_gpu_configs import CLI, ENV, REF, _run, _vcf
     work, graph, cfg = select_cohort
     opts = ["-n", "5", "--use-depth", "--granularity", "0.05"] + extra      # 50 kb windows: four of them
     tag = "_".join(extra).replace("-", "") or "het"
     outs, logs = {}, {}
     for name, exe, more, env in (("cpu", REF, [], ENV), ("native", CLI, ["--gpu", "0"], dict(ENV, VGH_TIMING="1")),
-                                 ("host", CLI, ["--gpu", "0"], dict(ENV, VGH_TIMING="1", VGH_HMM_SELECT_DEVICE="0"))):
+                                 ("host", CLI, ["--gpu", "0"], dict(ENV, VGH_TIMING="1", VGH_HMM_SELECT_DEVICE="0")),
+                                 ("host_fixes", CLI, ["--gpu", "0"], dict(ENV, VGH_TIMING="1", VGH_HMM_FIX_DEVICE="0")),
+                                 ("host_tallies", CLI, ["--gpu", "0"], dict(ENV, VGH_TIMING="1", VGH_DEVICE_TALLIES="0"))):
         d = os.path.join(work, f"{name}_{tag}")
         os.makedirs(d, exist_ok=True)
         open(os.path.join(d, "samples.cfg"), "w").write(cfg)
@@ -339,6 +343,13 @@ def test_command_line_with_selection_on_the_device_equals_the_reference(extra, s
     for i in range(3):
         assert outs["native"][i] == outs["cpu"][i], (extra, i)
         assert outs["host"][i] == outs["cpu"][i], (extra, i, "VGH_HMM_SELECT_DEVICE=0")
-    seen = re.findall(r"HMM emissions on the device: .*haplotypes selected per window for (\d+) of (\d+) windows", logs["native"])
-    assert len(seen) == 3 and all(a == b and int(b) >= 4 for a, b in seen), seen
+        # the flagged nodes scored by the host instead of a second launch; the calls' tallies walked by the host
+        assert outs["host_fixes"][i] == outs["cpu"][i], (extra, i, "VGH_HMM_FIX_DEVICE=0")
+        assert outs["host_tallies"][i] == outs["cpu"][i], (extra, i, "VGH_DEVICE_TALLIES=0")
+    for name in ("native", "host_fixes", "host_tallies"):
+        seen = re.findall(r"HMM emissions on the device: .*haplotypes selected per window for (\d+) of (\d+) windows", logs[name])
+        assert len(seen) == 3 and all(a == b and int(b) >= 4 for a, b in seen), (name, seen)
+    scored = {name: [tuple(map(int, m)) for m in re.findall(r"(\d+) nodes scored by the host, (\d+) scored again on the device", logs[name])]
+              for name in ("native", "host_fixes")}
+    print(f"-n 5 {' '.join(extra)}: nodes scored by the host / again on the device, per sample: {scored}")
     assert "haplotypes selected per window" not in logs["host"]

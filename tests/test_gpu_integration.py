@@ -11,6 +11,7 @@ itself prints GQ 99.0 vs 192.7 at a few sites on the GPU box's EPYC vs the build
 container) are therefore compared field-wise without GQ."""
 import gzip
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -678,7 +679,8 @@ def test_native_cli_block_gzip_and_plain_inputs(tmp_path):
 def test_native_cli_hmm_on_the_device_in_parts_equals_the_host_hmm(tmp_path):
     """The same sample with the HMM's recursion and posterior on the device (the default: the windows go to the device in
     parts as they are prepared -- twenty windows of 5 kb here, four parts) and on the host (VGH_HMM_DEVICE=0): identical VCF bytes, and
-    the log shows which one ran."""
+    the log shows which one ran.  So do VGH_HMM_FIX_DEVICE=0 and VGH_DEVICE_TALLIES=0 with the emissions on the device (no node of this
+    cohort is flagged: bytes only)."""
     if not os.path.exists(CLI):
         _missing("varigraph-mi not built")
     d = os.path.join(GOLDEN, "cohort_sv")
@@ -687,7 +689,8 @@ def test_native_cli_hmm_on_the_device_in_parts_equals_the_host_hmm(tmp_path):
     fq = [os.path.join(d, f"reads_{i}.fq.gz") for i in (1, 2)]
     out = {}
     for name, knob in (("device", {}), ("host", {"VGH_HMM_DEVICE": "0"}), ("bound", {"VGH_HMM_DEVICE_GIB": "0"}),
-                       ("nomem", {"VGH_HMM_FAKE_NOMEM": "1", "VGH_HMM_EMIT_DEVICE": "0"}), ("host_emissions", {"VGH_HMM_EMIT_DEVICE": "0"})):
+                       ("nomem", {"VGH_HMM_FAKE_NOMEM": "1", "VGH_HMM_EMIT_DEVICE": "0"}), ("host_emissions", {"VGH_HMM_EMIT_DEVICE": "0"}),
+                       ("host_fixes", {"VGH_HMM_FIX_DEVICE": "0"}), ("host_tallies", {"VGH_DEVICE_TALLIES": "0"})):
         w = tmp_path / name
         w.mkdir()
         (w / "samples.cfg").write_text("sample0 " + " ".join(fq) + "\n")
@@ -706,5 +709,11 @@ def test_native_cli_hmm_on_the_device_in_parts_equals_the_host_hmm(tmp_path):
     # emission scores prepared by the host (round 2's path) and on the device (the default for this panel: all 15 haplotypes selected)
     assert out["host_emissions"][0] == out["host"][0] and "emissions on the device" not in out["host_emissions"][1]
     assert "emissions on the device" in out["device"][1]
+    # ... with the flagged nodes scored by the host instead of a second launch, and with the calls' tallies walked by the host
+    for name in ("host_fixes", "host_tallies"):
+        assert out[name][0] == out["host"][0] and "emissions on the device" in out[name][1], name
+    scored = {name: [tuple(map(int, m)) for m in re.findall(r"\((\d+) of \d+ nodes scored by the host, (\d+) scored again on the device\)", out[name][1])]
+              for name in ("device", "host_fixes")}
+    print(f"nodes scored by the host / again on the device, per part: {scored}")
     # a sample whose scores exceed the bound stays on the host
     assert out["bound"][0] == out["host"][0] and "HMM part" not in out["bound"][1]

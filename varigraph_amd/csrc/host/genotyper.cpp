@@ -977,12 +977,275 @@ std::vector<long double> Genotyper::score_states(const NodeStates& ns, ScoreCtx&
     return obs;
 }
 
+// ---------------------------------------------------------------- what the three paths through the HMM share
+namespace {
+// every switch of the device paths is on unless its variable starts with '0'
+bool knob_off(const char* name)
+{
+    const char* e = getenv(name);
+    return e && e[0] == '0';
+}
+
+void device_check(vgmi_ctx* dev, int rc, const char* what)
+{
+    if (rc != VGMI_OK) throw std::runtime_error(std::string(what) + vgmi_last_error(dev));
+}
+
+struct PartHandle {
+    vgmi_hmm_part* p = nullptr;
+    ~PartHandle() { vgmi_hmm_part_free(p); }
+};
+
+// fn(0) .. fn(n - 1) on `threads` threads, the caller's among them: a thread token and `spent` per item; the first error is thrown
+// once every thread has ended
+void over_windows(size_t n, size_t threads, std::atomic<long long>& spent, const std::function<void(size_t)>& fn)
+{
+    std::atomic<size_t> next{0};
+    std::string err;
+    std::mutex mu;
+    auto body = [&]() {
+        for (;;) {
+            const size_t i = next.fetch_add(1);
+            if (i >= n) return;
+            try {
+                CpuBudget::Hold cpu;
+                PhaseTimer tt(spent);
+                fn(i);
+            } catch (const std::exception& e) {
+                std::lock_guard<std::mutex> lock(mu);
+                if (err.empty()) err = e.what();
+            }
+        }
+    };
+    std::vector<std::thread> helpers;
+    for (size_t h = 1; h < threads; ++h) helpers.emplace_back(body);
+    body();
+    for (auto& th : helpers) th.join();
+    if (!err.empty()) throw std::runtime_error(err);
+}
+
+// how many haplotypes two sorted genotypes share (the size of their std::set_intersection)
+int32_t shared_haplotypes(const std::vector<uint16_t>& a, const std::vector<uint16_t>& b)
+{
+    int32_t n = 0;
+    for (size_t x = 0, y = 0; x < a.size() && y < b.size();) {
+        if (a[x] < b[y]) ++x;
+        else if (b[y] < a[x]) ++y;
+        else { ++n; ++x; ++y; }
+    }
+    return n;
+}
+
+std::vector<uint8_t> keep_matrix(const std::vector<std::vector<uint16_t>>& genotypes)
+{
+    const size_t n_gt = genotypes.size();
+    std::vector<uint8_t> keep_mat(n_gt * n_gt);
+    for (size_t i = 0; i < n_gt; ++i)
+        for (size_t j = 0; j < n_gt; ++j) keep_mat[i * n_gt + j] = (uint8_t)shared_haplotypes(genotypes[i], genotypes[j]);
+    return keep_mat;
+}
+
+// the sample's libm values for the emission kernel: geometric(error_param(ave), c) for h = 0, poisson(ave * h, c) for h = 1 .. ploidy
+std::vector<long double> emission_table(float ave, uint32_t ploidy)
+{
+    std::vector<long double> tab((size_t)(ploidy + 1) * 256);
+    for (int c = 0; c < 256; ++c) {
+        tab[c] = geometric(error_param(ave), (uint8_t)c);
+        for (uint8_t h = 1; h <= ploidy; ++h) tab[(size_t)h * 256 + c] = poisson_pmf(ave * h, (uint8_t)c);
+    }
+    return tab;
+}
+
+// ---- a site's VCF line (src/genotype.cpp:1628-1690)
+using SiteMap = std::map<uint32_t, std::vector<std::string>>;
+
+// CHROM .. INFO with FILTER forced PASS, FORMAT and the tab behind it; false (nothing appended): the VCF has no such site
+bool append_site_head(std::string& out, const std::vector<std::string>* fields)
+{
+    if (!fields) return false;
+    for (size_t i = 0; i < 9; i++) {
+        if (i == 0) out += (*fields)[i];
+        else if (i == 6) out += "\tPASS";
+        else if (i < 8) { out += '\t'; out += (*fields)[i]; }
+        else out += "\tGT:GQ:GPP:NAK:CAK:UK";
+    }
+    out += '\t';
+    return true;
+}
+
+void append_sample_field(std::string& out, const uint64_t* gt, size_t n_alleles, bool no_call, float gq, long double probability, const uint64_t* kmer_num,
+                         const float* kmer_ave_cov, size_t n_counts, uint8_t unique_kmers)
+{
+    for (size_t i = 0; i < n_alleles; ++i) {
+        if (i) out += '/';
+        if (no_call) out += '.';
+        else append_uint(out, gt[i]);
+    }
+    out += ':';
+    append_fixed1(out, gq);
+    out += ':';
+    append_fixed1(out, probability);
+    out += ':';
+    for (size_t i = 0; i < n_counts; ++i) {
+        if (i) out += ',';
+        append_uint(out, kmer_num[i]);
+    }
+    out += ':';
+    for (size_t i = 0; i < n_counts; i++) {
+        if (i) out += ',';
+        append_fixed1(out, kmer_ave_cov[i]);
+    }
+    out += ':';
+    append_uint(out, unique_kmers);
+    out += '\n';
+}
+
+// A diploid call's line straight from what the device sent back -- the called pair's alleles, the posterior, the tallies (k-mers,
+// coverage sum per called haplotype) -- without the detour through the node's call record (window_finish writes it, write_piece reads it
+// back: two walks over half a million scattered nodes per sample).  head(out) as append_site_head.
+template <class Head>
+void append_tally_line(std::string& out, uint64_t ga, uint64_t gb, long double probability, const uint32_t* tl, uint8_t unique_kmers, float min_gq, Head&& head)
+{
+    if ((ga == 0 && gb == 0) || !head(out)) return;
+    const float gq = phred_scaled(probability);
+    const uint64_t gt[2] = {ga, gb}, num[2] = {tl[0], tl[2]};
+    const float cov[2] = {tl[0] ? static_cast<float>((uint64_t)tl[1]) / (float)(uint64_t)tl[0] : 0.0f,
+                          tl[2] ? static_cast<float>((uint64_t)tl[3]) / (float)(uint64_t)tl[2] : 0.0f};
+    append_sample_field(out, gt, 2, gq < min_gq, gq, probability, num, cov, 2, unique_kmers);
+}
+
+// A window's nodes come in the order of their start, as the sites of the map do: one walk along the map instead of a search from its
+// root per node (0.4 thread-seconds per chr20-scale sample were these searches)
+struct SiteWalk {
+    const SiteMap& sites;
+    SiteMap::const_iterator site;
+    uint32_t prev_start = UINT32_MAX;      // (the first node is searched for; a node in front of the last one, too -- never, with node lists as graph.bin holds them)
+    explicit SiteWalk(const SiteMap& s) : sites(s), site(s.end()) {}
+    const std::vector<std::string>* at(uint32_t start)      // nullptr: no site at `start`
+    {
+        if (start < prev_start) site = sites.lower_bound(start);
+        prev_start = start;
+        while (site != sites.end() && site->first < start) ++site;
+        return site == sites.end() || site->first != start ? nullptr : &site->second;
+    }
+};
+}  // namespace
+
+// the line of a node's call, if it has one with a non-reference allele; gt: scratch; head(out) as append_site_head
+template <class Head>
+void Genotyper::append_call_line(std::string& out, const Node& node, float min_gq, std::vector<uint64_t>& gt, Head&& head)
+{
+    const SiteCall& call = node.call;
+    if (call.haps.empty()) return;
+    gt.clear();
+    bool all_ref = true;
+    for (uint16_t hap : call.haps) {
+        gt.push_back((uint64_t)node.gn->hap_gt[hap]);
+        all_ref = all_ref && gt.back() == 0;
+    }
+    if (all_ref || !head(out)) return;
+    const float gq = phred_scaled(call.probability);
+    append_sample_field(out, gt.data(), gt.size(), gq < min_gq, gq, call.probability, call.kmer_num.data(), call.kmer_ave_cov.data(), call.kmer_num.size(),
+                        call.unique_kmers);
+}
+
+const Genotyper::SiteMap& Genotyper::vcf_sites(const Chrom& chr) const
+{
+    auto vcf_chr = g_.vcf_info.find(chr.name);
+    if (vcf_chr == g_.vcf_info.end()) throw std::runtime_error("'" + chr.name + "' does not exist in the VCF file.");
+    return vcf_chr->second;
+}
+
+// which nodes the HMM passes over: those with one allele and, under --sv, those whose alleles are all shorter than 50 bases
+bool Genotyper::skipped(const Chrom& chr, const SiteMap& sites, const Node& n, bool sv_only)
+{
+    if (n.gn->hap_gt.size() <= 1) return true;
+    if (sv_only) {
+        auto site = sites.find(n.start);
+        if (site == sites.end()) throw std::runtime_error("'" + chr.name + ":" + std::to_string(n.start) + "' does not exist in the VCF file.");
+        if (site->second[3].size() < 50 && site->second[4].size() < 50) return true;
+    }
+    return false;
+}
+
+// used: the haplotypes occurring in `genotypes`, ascending
+Genotyper::GenotypeList Genotyper::genotype_list(const std::vector<std::vector<uint16_t>>& genotypes, const std::vector<uint16_t>& used)
+{
+    const size_t n_gt = genotypes.size();
+    GenotypeList glist;
+    glist.off.assign(n_gt + 1, 0);
+    for (size_t gi = 0; gi < n_gt; ++gi) {
+        glist.flat.insert(glist.flat.end(), genotypes[gi].begin(), genotypes[gi].end());
+        glist.off[gi + 1] = (uint32_t)glist.flat.size();
+        glist.pairs = glist.pairs && genotypes[gi].size() == 2;
+    }
+    if (glist.pairs && used.size() <= 16) {
+        std::unordered_map<uint16_t, uint8_t> where;
+        for (size_t p = 0; p < used.size(); ++p) where[used[p]] = (uint8_t)p;
+        glist.pos_a.resize(n_gt);
+        glist.pos_b.resize(n_gt);
+        for (size_t gi = 0; gi < n_gt; ++gi) {
+            glist.pos_a[gi] = where[glist.flat[2 * gi]];
+            glist.pos_b[gi] = where[glist.flat[2 * gi + 1]];
+        }
+    }
+    return glist;
+}
+
+// The step tables of a window's two chains, forward (the nodes in order) and backward (from the last): per step the powers
+// no_recomb^0..ploidy, recomb^0..ploidy of the gap to the node before it in the chain, whether the chain restarts there, and its row;
+// per scored node the steps that hold its alpha and its beta.  pw / row / restart point at the window's first step, which is step
+// `step0` of the arrays the device gets; a node's row is row_base + at, fwd / bwd are indexed by `at`.
+void Genotyper::step_tables(const std::vector<Seen>& seen, uint32_t stride, uint16_t population, size_t step0, size_t row_base, long double* pw,
+                            uint32_t* row, uint8_t* restart, uint64_t* fwd, uint64_t* bwd)
+{
+    size_t m = 0;
+    for (const Seen& sn : seen) m += sn.at >= 0;
+    if (!m) return;
+    // the tables of powers are a function of the distance alone: neighbouring nodes are tens to hundreds of bases apart, so a window's
+    // few thousand steps share a few hundred distinct tables (same libm calls, each made once)
+    constexpr uint32_t kMemo = 4096;
+    std::vector<long double> memo((size_t)kMemo * 2 * stride);
+    std::vector<uint8_t> memo_have(kMemo, 0);
+    auto powers = [&](long double* dst, uint32_t distance) {
+        if (distance < kMemo && memo_have[distance]) {
+            std::memcpy(dst, &memo[(size_t)distance * 2 * stride], 2 * stride * sizeof(long double));
+            return;
+        }
+        long double recomb, no_recomb;
+        std::tie(recomb, no_recomb) = transition_probabilities(distance, population);
+        for (uint32_t k = 0; k < stride; ++k) {
+            dst[k] = std::pow(no_recomb, (int32_t)k);
+            dst[stride + k] = std::pow(recomb, (int32_t)k);
+        }
+        if (distance < kMemo) {
+            std::memcpy(&memo[(size_t)distance * 2 * stride], dst, 2 * stride * sizeof(long double));
+            memo_have[distance] = 1;
+        }
+    };
+    size_t j = 0;
+    for (size_t q = 0; q < seen.size(); ++q) {
+        if (seen[q].at < 0) continue;
+        const size_t fs = j, bs = m + (m - 1 - j);     // its forward and its backward step
+        // forward: the node in front (prev_end = 0 in front of the first); the chain restarts behind a node without scores
+        powers(pw + fs * 2 * stride, seen[q].start - (q ? seen[q - 1].end : 0u));
+        restart[fs] = (q == 0 || seen[q - 1].at < 0) ? 1 : 0;
+        row[fs] = (uint32_t)(row_base + seen[q].at);
+        // backward: the node behind (prev_start = 0 behind the last)
+        powers(pw + bs * 2 * stride, (q + 1 < seen.size() ? seen[q + 1].start : 0u) - seen[q].end);
+        restart[bs] = (q + 1 == seen.size() || seen[q + 1].at < 0) ? 1 : 0;
+        row[bs] = (uint32_t)(row_base + seen[q].at);
+        fwd[seen[q].at] = step0 + fs;
+        bwd[seen[q].at] = step0 + bs;
+        ++j;
+    }
+}
+
 // ---------------------------------------------------------------- one window: selection, forward, backward, posterior
 void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, WindowWork* work, const std::vector<uint16_t>* forced_top)
 {
     const GenotypeConfig& cfg = *r.cfg;
-    auto vcf_chr = g_.vcf_info.find(chr.name);
-    if (vcf_chr == g_.vcf_info.end()) throw std::runtime_error("'" + chr.name + "' does not exist in the VCF file.");
+    const SiteMap& sites = vcf_sites(chr);
     if (first >= chr.nodes.size()) return;
 
     // ---- haplotype selection (src/genotype.cpp:500-610)
@@ -1030,16 +1293,7 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
     double lower = 256.0f, upper = -0.1f;
     poisson_interval(r.hap_cov, lower, upper);
 
-    auto skipped = [&](const Node& n) -> bool {
-        if (n.gn->hap_gt.size() <= 1) return true;
-        if (cfg.sv_only) {
-            auto site = vcf_chr->second.find(n.start);
-            if (site == vcf_chr->second.end())
-                throw std::runtime_error("'" + chr.name + ":" + std::to_string(n.start) + "' does not exist in the VCF file.");
-            if (site->second[3].size() < 50 && site->second[4].size() < 50) return true;
-        }
-        return false;
-    };
+    auto skipped = [&](const Node& n) { return Genotyper::skipped(chr, sites, n, cfg.sv_only); };
     // emission score of every genotype of a node (observable_states, :960-1000).  poisson(ave * h, c) and
     // geometric(p, c) are pure functions of (h, c) within a sample: evaluated once each (the values, and therefore
     // the products, are the reference's bit for bit)
@@ -1055,37 +1309,10 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
     for (const auto& gtv : genotypes) used.insert(used.end(), gtv.begin(), gtv.end());
     std::sort(used.begin(), used.end());
     used.erase(std::unique(used.begin(), used.end()), used.end());
-    auto shared = [](const std::vector<uint16_t>& a, const std::vector<uint16_t>& b) -> int32_t {
-        int32_t n = 0;
-        for (size_t x = 0, y = 0; x < a.size() && y < b.size();) {
-            if (a[x] < b[y]) ++x;
-            else if (b[y] < a[x]) ++y;
-            else { ++n; ++x; ++y; }
-        }
-        return n;
-    };
-    GenotypeList glist;
-    glist.off.assign(n_gt + 1, 0);
-    for (size_t gi = 0; gi < n_gt; ++gi) {
-        glist.flat.insert(glist.flat.end(), genotypes[gi].begin(), genotypes[gi].end());
-        glist.off[gi + 1] = (uint32_t)glist.flat.size();
-        glist.pairs = glist.pairs && genotypes[gi].size() == 2;
-    }
-    if (glist.pairs && used.size() <= 16) {
-        std::unordered_map<uint16_t, uint8_t> where;
-        for (size_t p = 0; p < used.size(); ++p) where[used[p]] = (uint8_t)p;
-        glist.pos_a.resize(n_gt);
-        glist.pos_b.resize(n_gt);
-        for (size_t gi = 0; gi < n_gt; ++gi) {
-            glist.pos_a[gi] = where[glist.flat[2 * gi]];
-            glist.pos_b[gi] = where[glist.flat[2 * gi + 1]];
-        }
-    }
+    const GenotypeList glist = genotype_list(genotypes, used);
     bool all_full = true;   // every genotype has `ploidy` haplotypes
     for (const auto& gtv : genotypes) all_full = all_full && gtv.size() == (size_t)cfg.sample_ploidy;
-    std::vector<uint8_t> keep_mat(n_gt * n_gt);
-    for (size_t i = 0; i < n_gt; ++i)
-        for (size_t j = 0; j < n_gt; ++j) keep_mat[i * n_gt + j] = (uint8_t)shared(genotypes[i], genotypes[j]);
+    const std::vector<uint8_t> keep_mat = keep_matrix(genotypes);
 
     // emission score of every genotype of a node; empty when the node has no k-mer left (every genotype is skipped).
     // Every genotype's score is the product of its k-mers' terms in k-mer order (observable_states); walking the
@@ -1175,7 +1402,7 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
                         }
                         res += t;
                     } else {
-                        const int32_t keep = aligned ? (int32_t)keep_mat[gi * n_gt + pi] : shared(haps, *p.haps);
+                        const int32_t keep = aligned ? (int32_t)keep_mat[gi * n_gt + pi] : shared_haplotypes(haps, *p.haps);
                         const int32_t change = hap_num - keep;
                         const long double pk = keep <= max_n ? pow_keep[keep] : std::pow(no_recomb, keep);
                         const long double pc = (change >= 0 && change <= max_n) ? pow_change[change] : std::pow(recomb, change);
@@ -1203,9 +1430,7 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
     const bool to_device = work != nullptr && work->obs != nullptr && n_gt == work->n_gt && cfg.transition == "rec" && all_full && n_gt <= 2048 &&
                            cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;    // 2048: VGMI_HMM_MAX_GT (csrc/vgmi_kernels.h)
     if (to_device) {
-        const uint32_t stride = cfg.sample_ploidy + 1;
-        struct Seen { uint32_t start, end; int32_t at; };   // every node the HMM works on; at: its place in work->nodes or -1
-        std::vector<Seen> seen;
+        std::vector<Seen> seen;      // at: the node's place in work->nodes
         NodeStates st;
         for (uint32_t i = first; i < last; ++i) {
             Node& n = chr.nodes[i];
@@ -1227,7 +1452,7 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
                 seen.push_back(Seen{n_start, n_end, -1});
                 continue;
             }
-            seen.push_back(Seen{n_start, n_end, (int32_t)work->nodes.size()});
+            seen.push_back(Seen{n_start, n_end, (int64_t)work->nodes.size()});
             if (work->nodes.size() >= work->room || obs.size() != n_gt) throw std::runtime_error("internal: device HMM window larger than announced");
             std::memcpy(work->obs + work->nodes.size() * n_gt, obs.data(), n_gt * sizeof(long double));
             if (!genotype_strings(n, genotypes, work->gid + work->nodes.size() * n_gt, work->order + work->nodes.size() * n_gt)) {
@@ -1240,29 +1465,7 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
             }
             work->nodes.push_back(i);
         }
-        const size_t m = work->nodes.size();
-        auto powers = [&](long double* dst, uint32_t distance) {
-            long double recomb, no_recomb;
-            std::tie(recomb, no_recomb) = transition_probabilities(distance, (uint16_t)n_hap_);
-            for (uint32_t k = 0; k < stride; ++k) {
-                dst[k] = std::pow(no_recomb, (int32_t)k);
-                dst[stride + k] = std::pow(recomb, (int32_t)k);
-            }
-        };
-        for (size_t q = 0; q < seen.size(); ++q) {
-            if (seen[q].at < 0) continue;
-            const size_t j = (size_t)seen[q].at, fs = j, bs = m + (m - 1 - j);     // its forward and its backward step
-            // forward: the node in front (prev_end = 0 in front of the first); the chain restarts behind a node without scores
-            powers(work->pw + fs * 2 * stride, seen[q].start - (q ? seen[q - 1].end : 0u));
-            work->restart[fs] = (q == 0 || seen[q - 1].at < 0) ? 1 : 0;
-            work->row[fs] = (uint32_t)(work->row0 + j);
-            // backward: the node behind (prev_start = 0 behind the last)
-            powers(work->pw + bs * 2 * stride, (q + 1 < seen.size() ? seen[q + 1].start : 0u) - seen[q].end);
-            work->restart[bs] = (q + 1 == seen.size() || seen[q + 1].at < 0) ? 1 : 0;
-            work->row[bs] = (uint32_t)(work->row0 + j);
-            work->fwd_step[j] = work->step0 + fs;
-            work->bwd_step[j] = work->step0 + bs;
-        }
+        step_tables(seen, cfg.sample_ploidy + 1, (uint16_t)n_hap_, work->step0, work->row0, work->pw, work->row, work->restart, work->fwd_step, work->bwd_step);
         work->chr = &chr;
         work->on_device = true;
         work->n_gt = n_gt;
@@ -1467,56 +1670,126 @@ void Genotyper::window_finish(WindowWork& w, const long double* prob, const uint
 }
 
 // ---------------------------------------------------------------- driver + VCF text
-std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const std::string& sample_name,
-                           const GenotypeConfig& cfg, const uint8_t* cov_node)
-{
-    const auto t_begin = std::chrono::steady_clock::now();
-    const size_t n_entries = g_.node_key_index.size();
-    std::vector<uint8_t> gathered;
-    if (!cov_node) {      // a caller with per-key counters only (tests, the C API): the per-node gather on the host
-        gathered.resize(n_entries);
-        for (size_t j = 0; j < n_entries; ++j) gathered[j] = cov[g_.node_key_index[j]];
-        cov_node = gathered.data();
-    }
-    Run r;
-    r.cov = cov_node;
-    r.hap_cov = hap_kmer_coverage;
-    r.cfg = &cfg;
-    r.haploid_num = std::min(cfg.haploid_num, n_hap_);
-    if (g_.bitlen <= 6) {
-        // one word per entry of the node lists: multiplicity and haplotype bits are the graph's (filled once, a gather over the
-        // key arrays), the low byte is this sample's coverage -- a sequential pass over the device's cov_node
-        const size_t bl = g_.bitlen;
-        const bool first = packed_.size() != n_entries;
-        if (first) {
-            packed_.reserve(n_entries);
-            advise_huge_pages(packed_.data(), n_entries * sizeof(uint64_t));
-            packed_.resize(n_entries);
-        }
-        const uint32_t nt = std::max(1u, cfg.threads);
-        std::vector<std::thread> fill;
-        auto part = [&](size_t a, size_t b) {
-            CpuBudget::Hold cpu;
-            PhaseTimer tt(g_phase.fill);
-            if (first && g_.entry_words.size() == n_entries) {      // the graph's half was gathered once for every Genotyper
-                for (size_t j = a; j < b; ++j) packed_[j] = g_.entry_words[j] | cov_node[j];
-            } else if (first) {
-                for (size_t j = a; j < b; ++j) {
-                    const size_t key = g_.node_key_index[j];
-                    uint64_t bits = 0;
-                    std::memcpy(&bits, &g_.bitvec[key * bl], bl);
-                    packed_[j] = (uint64_t)cov_node[j] | (uint64_t)(uint8_t)g_.f[key] << 8 | bits << 16;
-                }
-            } else {
-                for (size_t j = a; j < b; ++j) packed_[j] = (packed_[j] & ~(uint64_t)0xFF) | cov_node[j];
-            }
-        };
-        for (uint32_t t = 1; t < nt; ++t) fill.emplace_back(part, n_entries * t / nt, n_entries * (t + 1) / nt);
-        part(0, n_entries / nt);
-        for (auto& th : fill) th.join();
-        r.packed = packed_.data();
-    }
+struct Genotyper::RunShared {
+    const Run& r;
+    std::chrono::steady_clock::time_point t_begin;
+    std::vector<Task> tasks;
+    uint32_t n_threads = 1;
+    // A window's VCF lines are written as soon as its calls are known -- for most windows while the last chains are still on the
+    // device -- and joined in task order at the end
+    std::vector<std::string> pieces;
+    std::vector<uint8_t> piece_done;
+    std::atomic<int64_t> dev_first{INT64_MAX}, dev_last{0};      // from the first device call's start to the last one's end
+    std::atomic<size_t> emit_windows_done{0};                    // windows with rows whose emissions the device scored
 
+    explicit RunShared(const Run& run) : r(run) {}
+    int64_t since_begin() const { return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count(); }
+    void note_device_span(int64_t ta, int64_t tb)
+    {
+        for (int64_t v = dev_first.load(); ta < v && !dev_first.compare_exchange_weak(v, ta);) {}
+        for (int64_t v = dev_last.load(); tb > v && !dev_last.compare_exchange_weak(v, tb);) {}
+    }
+};
+
+struct Genotyper::DevicePaths {
+    bool pool_device = false;      // windows on the pool, their recursion and posterior on the device
+    bool emit = false;             // emissions on the device, whole panel
+    bool select = false;           // emissions on the device, haplotypes selected per window
+    size_t n_gt = 0, total_room = 0;
+};
+
+// The windows on the pool write their emission scores and step tables straight into the run's arrays: room for every node with more
+// than one allele is set aside per window (a node without k-mers leaves its row unused).
+struct Genotyper::WindowBuffers {
+    long double *obs = nullptr, *pw = nullptr, *prob = nullptr;
+    uint32_t *row = nullptr, *win = nullptr;
+    uint8_t *restart = nullptr, *gid = nullptr, *order = nullptr;
+    uint64_t *fs = nullptr, *bs = nullptr;
+    size_t n_gt = 0;
+    uint32_t stride = 0;
+
+    WindowBuffers() = default;
+    WindowBuffers(const WindowBuffers&) = delete;
+    WindowBuffers& operator=(const WindowBuffers&) = delete;
+    ~WindowBuffers()
+    {
+        for (void* p : {(void*)obs, (void*)pw, (void*)prob, (void*)row, (void*)win, (void*)restart, (void*)gid, (void*)order, (void*)fs, (void*)bs}) std::free(p);
+    }
+    bool ready() const { return obs != nullptr; }
+    void allocate(size_t total_room, size_t n_genotypes, uint32_t ploidy)
+    {
+        n_gt = n_genotypes;
+        stride = ploidy + 1;
+        obs = static_cast<long double*>(std::malloc(total_room * n_gt * sizeof(long double)));
+        pw = static_cast<long double*>(std::malloc(2 * total_room * 2 * stride * sizeof(long double)));
+        row = static_cast<uint32_t*>(std::calloc(2 * total_room, sizeof(uint32_t)));
+        restart = static_cast<uint8_t*>(std::calloc(2 * total_room, 1));
+        gid = static_cast<uint8_t*>(std::calloc(total_room * n_gt, 1));
+        order = static_cast<uint8_t*>(std::calloc(total_room * n_gt, 1));
+        fs = static_cast<uint64_t*>(std::calloc(total_room, sizeof(uint64_t)));
+        bs = static_cast<uint64_t*>(std::calloc(total_room, sizeof(uint64_t)));
+        prob = static_cast<long double*>(std::malloc(total_room * sizeof(long double)));
+        win = static_cast<uint32_t*>(std::malloc(total_room * sizeof(uint32_t)));
+        if (!obs || !pw || !row || !restart || !gid || !order || !fs || !bs || !prob || !win) throw std::runtime_error("out of memory (HMM tables)");
+        advise_huge_pages(obs, total_room * n_gt * sizeof(long double));       // gigabytes, first touched here and by the copies
+    }
+    void bind(WindowWork& w) const
+    {
+        w.n_gt = n_gt;      // a window whose genotype list has another length takes the host path
+        w.obs = obs + w.row0 * n_gt;
+        w.pw = pw + w.step0 * 2 * stride;
+        w.row = row + w.step0;
+        w.restart = restart + w.step0;
+        w.gid = gid + w.row0 * n_gt;
+        w.order = order + w.row0 * n_gt;
+        w.fwd_step = fs + w.row0;
+        w.bwd_step = bs + w.row0;
+        // rows and steps a window leaves unused (nodes without k-mers) still point into its own part of the arrays
+        std::fill(w.row, w.row + 2 * w.room, (uint32_t)w.row0);
+        std::fill(w.fwd_step, w.fwd_step + w.room, (uint64_t)w.step0);
+        std::fill(w.bwd_step, w.bwd_step + w.room, (uint64_t)w.step0);
+    }
+};
+
+// One word per entry of the node lists: multiplicity and haplotype bits are the graph's (filled once, a gather over the key arrays),
+// the low byte is this sample's coverage -- a sequential pass over the device's cov_node
+void Genotyper::fill_packed(Run& r, uint32_t threads)
+{
+    const size_t n_entries = g_.node_key_index.size();
+    const uint8_t* const cov_node = r.cov;
+    const size_t bl = g_.bitlen;
+    const bool first = packed_.size() != n_entries;
+    if (first) {
+        packed_.reserve(n_entries);
+        advise_huge_pages(packed_.data(), n_entries * sizeof(uint64_t));
+        packed_.resize(n_entries);
+    }
+    const uint32_t nt = std::max(1u, threads);
+    std::vector<std::thread> fill;
+    auto part = [&](size_t a, size_t b) {
+        CpuBudget::Hold cpu;
+        PhaseTimer tt(g_phase.fill);
+        if (first && g_.entry_words.size() == n_entries) {      // the graph's half was gathered once for every Genotyper
+            for (size_t j = a; j < b; ++j) packed_[j] = g_.entry_words[j] | cov_node[j];
+        } else if (first) {
+            for (size_t j = a; j < b; ++j) {
+                const size_t key = g_.node_key_index[j];
+                uint64_t bits = 0;
+                std::memcpy(&bits, &g_.bitvec[key * bl], bl);
+                packed_[j] = (uint64_t)cov_node[j] | (uint64_t)(uint8_t)g_.f[key] << 8 | bits << 16;
+            }
+        } else {
+            for (size_t j = a; j < b; ++j) packed_[j] = (packed_[j] & ~(uint64_t)0xFF) | cov_node[j];
+        }
+    };
+    for (uint32_t t = 1; t < nt; ++t) fill.emplace_back(part, n_entries * t / nt, n_entries * (t + 1) / nt);
+    part(0, n_entries / nt);
+    for (auto& th : fill) th.join();
+    r.packed = packed_.data();
+}
+
+void Genotyper::reset_calls()
+{
     for (auto& c : chroms_)
         for (auto& n : c.nodes) {
             if (n.hmm.capacity()) std::vector<HmmScore>().swap(n.hmm);
@@ -1527,9 +1800,11 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
             n.call.kmer_ave_cov.clear();
             n.call.unique_kmers = 0;
         }
+}
 
-    // windows of `chr_len_thread` bp over the node list of every chromosome (src/genotype.cpp:76-140)
-    struct Task { Chrom* chr; uint32_t first, last; };
+// windows of `chr_len_thread` bp over the node list of every chromosome (src/genotype.cpp:76-140)
+std::vector<Genotyper::Task> Genotyper::windows(const GenotypeConfig& cfg)
+{
     std::vector<Task> tasks;
     for (auto& chr : chroms_) {
         const uint64_t n_nodes = chr.nodes.size();
@@ -1550,172 +1825,100 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
             tasks.push_back({&chr, first, end});
         }
     }
-    // With a device context (set_device; VGH_HMM_DEVICE=0 keeps the host): recursion and posterior of the eligible windows on the
-    // device (window(), window_finish()).
-    // The windows write their emission scores and step tables straight into the run's arrays: room for every node with more
-    // than one allele is set aside per window (a node without k-mers leaves its row unused).
-    const bool use_device = dev_ != nullptr && [] { const char* e = getenv("VGH_HMM_DEVICE"); return !(e && e[0] == '0'); }() &&
-                            cfg.transition == "rec" && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;
-    std::vector<WindowWork> works(use_device ? tasks.size() : 0);
-    size_t dev_n_gt = 0, total_room = 0;
-    bool dev_emit = false, dev_select = false;
-    const uint32_t dev_stride = cfg.sample_ploidy + 1;
-    struct Raw {
-        void* p = nullptr;
-        ~Raw() { std::free(p); }
-    } raw_obs, raw_pw, raw_row, raw_restart, raw_gid, raw_order, raw_fs, raw_bs, raw_prob, raw_win;
-    if (use_device) {
-        std::vector<uint16_t> some(std::min<size_t>(r.haploid_num, n_hap_));
-        for (size_t i = 0; i < some.size(); ++i) some[i] = (uint16_t)i;
-        dev_n_gt = haplotype_combinations(some, cfg.sample_type, cfg.sample_ploidy, (uint16_t)(n_hap_ - 1)).size();
-        for (size_t t = 0; t < tasks.size(); ++t) {
-            size_t room = 0;
-            for (uint32_t i = tasks[t].first; i < tasks[t].last; ++i) room += tasks[t].chr->nodes[i].gn->hap_gt.size() > 1;
-            works[t].room = room;
-            works[t].row0 = total_room;
-            works[t].step0 = 2 * total_room;
-            total_room += room;
-        }
-        // (the emission scores of all windows are held at once, on the host and -- with alpha and beta, three times that -- on
-        // the device: beyond 16 GiB, a genome's worth of sites at 120 genotypes, the host runs the recursion as before;
-        // VGH_HMM_DEVICE_GIB moves the bound)
-        size_t score_gib = 16;
-        if (const char* e = getenv("VGH_HMM_DEVICE_GIB")) score_gib = (size_t)std::max(0L, atol(e));
-        // ... and what the device has free right now: a part holds its scores, alpha and beta (3 x its scores) until its calls are
-        // back, all parts of a sample may be in flight at once, and 4 / dev_parts_ samples share the device (set_device)
-        bool fits_device = true;
-        {
-            size_t free_b = 0, total_b = 0;
-            const size_t need = 3 * total_room * dev_n_gt * sizeof(long double) * ((4 + dev_parts_ - 1) / dev_parts_) + (size_t(1) << 30);
-            if (vgmi_device_memory(dev_, &free_b, &total_b) == VGMI_OK) fits_device = need <= free_b - free_b / 10;
-            if (!fits_device && g_phase_on)
-                std::fprintf(stderr, "[varigraph-mi] HMM on the host: %.1f GiB of device memory wanted, %.1f free\n", need / 1073741824.0, free_b / 1073741824.0);
-        }
-        const bool device_ok = fits_device && dev_n_gt >= 1 && dev_n_gt <= 2048 && total_room && total_room * dev_n_gt * sizeof(long double) <= (score_gib << 30);
-        // the emission scores can be computed on the device as well (below): a diploid sample, every haplotype selected, whole lists
-        // (round 5: polyploid samples too -- their genotypes are blocks of `ploidy` consecutive haplotypes, :846-873, a handful per window)
-        dev_emit = device_ok && !emit_device_off_ && r.packed != nullptr && cfg.sample_ploidy >= 2 && cfg.sample_ploidy <= 4 && n_hap_ <= r.haploid_num && n_hap_ <= 16 &&
-                   dev_n_gt <= 128 && lists_whole_.load() && [] { const char* e = getenv("VGH_HMM_EMIT_DEVICE"); return !(e && e[0] == '0'); }();
-        // ... and when -n selects fewer haplotypes than the graph has, for a diploid sample (below: every window draws its own haplotypes,
-        // the genotype list keeps its shape, the k-mer lists are pruned on the device and here alike).  VGH_HMM_SELECT_DEVICE=0: the host
-        // prepares such a sample as before.
-        bool plain_ids = true;      // haplotype h is bit h of an entry's word
-        for (size_t i = 0; i < hap_ids_.size(); ++i) plain_ids = plain_ids && hap_ids_[i] == i;
-        dev_select = device_ok && !dev_emit && r.packed != nullptr && cfg.sample_ploidy == 2 && n_hap_ > r.haploid_num && r.haploid_num >= 1 &&
-                     r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen &&
-                     [] { const char* e = getenv("VGH_HMM_EMIT_DEVICE"); return !(e && e[0] == '0'); }() &&
-                     [] { const char* e = getenv("VGH_HMM_SELECT_DEVICE"); return !(e && e[0] == '0'); }();
-        if (device_ok && !dev_emit && !dev_select) {
-            raw_obs.p = std::malloc(total_room * dev_n_gt * sizeof(long double));
-            raw_pw.p = std::malloc(2 * total_room * 2 * dev_stride * sizeof(long double));
-            raw_row.p = std::calloc(2 * total_room, sizeof(uint32_t));
-            raw_restart.p = std::calloc(2 * total_room, 1);
-            raw_gid.p = std::calloc(total_room * dev_n_gt, 1);
-            raw_order.p = std::calloc(total_room * dev_n_gt, 1);
-            raw_fs.p = std::calloc(total_room, sizeof(uint64_t));
-            raw_bs.p = std::calloc(total_room, sizeof(uint64_t));
-            raw_prob.p = std::malloc(total_room * sizeof(long double));
-            raw_win.p = std::malloc(total_room * sizeof(uint32_t));
-            if (!raw_obs.p || !raw_pw.p || !raw_row.p || !raw_restart.p || !raw_gid.p || !raw_order.p || !raw_fs.p || !raw_bs.p || !raw_prob.p || !raw_win.p)
-                throw std::runtime_error("out of memory (HMM tables)");
-            advise_huge_pages(raw_obs.p, total_room * dev_n_gt * sizeof(long double));       // gigabytes, first touched here and by the copies
-            for (size_t t = 0; t < tasks.size(); ++t) {
-                works[t].n_gt = dev_n_gt;      // a window whose genotype list has another length takes the host path
-                works[t].obs = static_cast<long double*>(raw_obs.p) + works[t].row0 * dev_n_gt;
-                works[t].pw = static_cast<long double*>(raw_pw.p) + works[t].step0 * 2 * dev_stride;
-                works[t].row = static_cast<uint32_t*>(raw_row.p) + works[t].step0;
-                works[t].restart = static_cast<uint8_t*>(raw_restart.p) + works[t].step0;
-                works[t].gid = static_cast<uint8_t*>(raw_gid.p) + works[t].row0 * dev_n_gt;
-                works[t].order = static_cast<uint8_t*>(raw_order.p) + works[t].row0 * dev_n_gt;
-                works[t].fwd_step = static_cast<uint64_t*>(raw_fs.p) + works[t].row0;
-                works[t].bwd_step = static_cast<uint64_t*>(raw_bs.p) + works[t].row0;
-                // rows and steps a window leaves unused (nodes without k-mers) still point into its own part of the arrays
-                std::fill(works[t].row, works[t].row + 2 * works[t].room, (uint32_t)works[t].row0);
-                std::fill(works[t].fwd_step, works[t].fwd_step + works[t].room, (uint64_t)works[t].step0);
-                std::fill(works[t].bwd_step, works[t].bwd_step + works[t].room, (uint64_t)works[t].step0);
-            }
-        }
+    return tasks;
+}
+
+// Which path a sample takes.  With a device context (set_device; VGH_HMM_DEVICE=0 keeps the host): recursion and posterior of the
+// eligible windows on the device (window(), window_finish()); `works` gets a window's room in the run's arrays.
+Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works) const
+{
+    const GenotypeConfig& cfg = *r.cfg;
+    DevicePaths dp;
+    const bool use_device = dev_ != nullptr && !knob_off("VGH_HMM_DEVICE") && cfg.transition == "rec" && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;
+    if (!use_device) return dp;
+    works.resize(tasks.size());
+    std::vector<uint16_t> some(std::min<size_t>(r.haploid_num, n_hap_));
+    for (size_t i = 0; i < some.size(); ++i) some[i] = (uint16_t)i;
+    dp.n_gt = haplotype_combinations(some, cfg.sample_type, cfg.sample_ploidy, (uint16_t)(n_hap_ - 1)).size();
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        size_t room = 0;
+        for (uint32_t i = tasks[t].first; i < tasks[t].last; ++i) room += tasks[t].chr->nodes[i].gn->hap_gt.size() > 1;
+        works[t].room = room;
+        works[t].row0 = dp.total_room;
+        works[t].step0 = 2 * dp.total_room;
+        dp.total_room += room;
     }
-    const bool device_ready = raw_obs.p != nullptr;
-    const uint32_t n_threads = std::max(1u, std::min<uint32_t>(cfg.threads, (uint32_t)tasks.size()));
-    // ---- VCF (src/genotype.cpp:1579-1696): sites in vcf_info order, only those with a non-reference call.  The
-    // reference walks mVcfInfoMap (chromosome, then position) and looks every site up in the graph; the windows are the
-    // same nodes in the same order, so every task writes the lines of its own nodes and the pieces are joined in task
-    // order (chromosomes of the graph that the VCF lacks have thrown in window() already).  A window's lines are written
-    // as soon as its calls are known -- for most windows while the last chains are still on the device.
-    std::vector<std::string> pieces(tasks.size());
-    std::vector<uint8_t> piece_done(tasks.size(), 0);
-    auto make_piece = [&](size_t t) {
-        piece_done[t] = 1;
-        const Chrom& chr = *tasks[t].chr;
-        auto vc = g_.vcf_info.find(chr.name);
-        if (vc == g_.vcf_info.end()) return;
-        const auto& sites = vc->second;
-        std::string out;
-        std::vector<uint64_t> gt;
-        // the window's nodes come in the order of their start, as the sites of the map do: one walk along the map instead of a
-        // search from its root per node (0.4 thread-seconds per chr20-scale sample were these searches)
-        auto site = tasks[t].first < tasks[t].last ? sites.lower_bound(chr.nodes[tasks[t].first].start) : sites.end();
-        uint32_t prev_start = 0;
-        for (uint32_t ni = tasks[t].first; ni < tasks[t].last; ++ni) {
-            const Node& node = chr.nodes[ni];
-            const SiteCall& call = node.call;
-            if (node.start < prev_start) site = sites.lower_bound(node.start);      // (never, with node lists as graph.bin holds them)
-            prev_start = node.start;
-            while (site != sites.end() && site->first < node.start) ++site;
-            if (call.haps.empty()) continue;
-            if (site == sites.end() || site->first != node.start) continue;
-            const auto& fields = site->second;
-            gt.clear();
-            bool all_ref = true;
-            for (uint16_t hap : call.haps) {
-                gt.push_back((uint64_t)node.gn->hap_gt[hap]);
-                all_ref = all_ref && gt.back() == 0;
-            }
-            if (all_ref) continue;
-            for (size_t i = 0; i < 9; i++) {
-                if (i == 0) out += fields[i];
-                else if (i == 6) out += "\tPASS";
-                else if (i < 8) { out += '\t'; out += fields[i]; }
-                else out += "\tGT:GQ:GPP:NAK:CAK:UK";
-            }
-            const float gq = phred_scaled(call.probability);
-            const bool no_call = gq < cfg.min_gq;
-            out += '\t';
-            for (size_t i = 0; i < gt.size(); ++i) {
-                if (i) out += '/';
-                if (no_call) out += '.';
-                else append_uint(out, gt[i]);
-            }
-            out += ':';
-            append_fixed1(out, gq);
-            out += ':';
-            append_fixed1(out, call.probability);
-            out += ':';
-            for (size_t i = 0; i < call.kmer_num.size(); ++i) {
-                if (i) out += ',';
-                append_uint(out, call.kmer_num[i]);
-            }
-            out += ':';
-            for (size_t i = 0; i < call.kmer_ave_cov.size(); i++) {
-                if (i) out += ',';
-                append_fixed1(out, call.kmer_ave_cov[i]);
-            }
-            out += ':';
-            append_uint(out, call.unique_kmers);
-            out += '\n';
-        }
-        pieces[t] = std::move(out);
-    };
-    // ---- three kinds of work on one pool: a window is prepared (window()), the recursion and posterior of a PART of the
-    // windows run on the device (one call per part, on a thread of its own that mostly waits), the calls of a part's windows
-    // are written back (window_finish()).  A chain is serial from its first node to its last, so the device takes as long
-    // for ten windows as for all of them: the parts go to the device as soon as their windows are prepared, side by side
-    // (vgmi_hmm_calls_part: own stream and buffers per call), while the pool prepares the next and finishes the last.
-    // At most four parts, over all the samples genotyped at the same time (set_device): a process has four hardware queues by
-    // default and a stream beyond them shares one, waiting behind the other stream's kernel for its whole length.
+    const size_t dev_n_gt = dp.n_gt, total_room = dp.total_room;
+    // (the emission scores of all windows are held at once, on the host and -- with alpha and beta, three times that -- on
+    // the device: beyond 16 GiB, a genome's worth of sites at 120 genotypes, the host runs the recursion as before;
+    // VGH_HMM_DEVICE_GIB moves the bound)
+    size_t score_gib = 16;
+    if (const char* e = getenv("VGH_HMM_DEVICE_GIB")) score_gib = (size_t)std::max(0L, atol(e));
+    // ... and what the device has free right now: a part holds its scores, alpha and beta (3 x its scores) until its calls are
+    // back, all parts of a sample may be in flight at once, and 4 / dev_parts_ samples share the device (set_device)
+    bool fits_device = true;
+    {
+        size_t free_b = 0, total_b = 0;
+        const size_t need = 3 * total_room * dev_n_gt * sizeof(long double) * ((4 + dev_parts_ - 1) / dev_parts_) + (size_t(1) << 30);
+        if (vgmi_device_memory(dev_, &free_b, &total_b) == VGMI_OK) fits_device = need <= free_b - free_b / 10;
+        if (!fits_device && g_phase_on)
+            std::fprintf(stderr, "[varigraph-mi] HMM on the host: %.1f GiB of device memory wanted, %.1f free\n", need / 1073741824.0, free_b / 1073741824.0);
+    }
+    const bool device_ok = fits_device && dev_n_gt >= 1 && dev_n_gt <= 2048 && total_room && total_room * dev_n_gt * sizeof(long double) <= (score_gib << 30);
+    // the emission scores can be computed on the device as well (hmm_whole_panel): a diploid sample, every haplotype selected, whole lists
+    // (polyploid samples too -- their genotypes are blocks of `ploidy` consecutive haplotypes, :846-873, a handful per window).
+    // VGH_HMM_EMIT_DEVICE=0: the host prepares the scores as before.
+    dp.emit = device_ok && !emit_device_off_ && r.packed != nullptr && cfg.sample_ploidy >= 2 && cfg.sample_ploidy <= 4 && n_hap_ <= r.haploid_num && n_hap_ <= 16 &&
+              dev_n_gt <= 128 && lists_whole_.load() && !knob_off("VGH_HMM_EMIT_DEVICE");
+    // ... and when -n selects fewer haplotypes than the graph has, for a diploid sample (hmm_selected: every window draws its own haplotypes,
+    // the genotype list keeps its shape, the k-mer lists are pruned on the device and here alike).  VGH_HMM_SELECT_DEVICE=0: the host
+    // prepares such a sample as before.
+    bool plain_ids = true;      // haplotype h is bit h of an entry's word
+    for (size_t i = 0; i < hap_ids_.size(); ++i) plain_ids = plain_ids && hap_ids_[i] == i;
+    dp.select = device_ok && !dp.emit && r.packed != nullptr && cfg.sample_ploidy == 2 && n_hap_ > r.haploid_num && r.haploid_num >= 1 &&
+                r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen && !knob_off("VGH_HMM_EMIT_DEVICE") &&
+                !knob_off("VGH_HMM_SELECT_DEVICE");
+    dp.pool_device = device_ok && !dp.emit && !dp.select;
+    return dp;
+}
+
+// ---- VCF (src/genotype.cpp:1579-1696): sites in vcf_info order, only those with a non-reference call.  The
+// reference walks mVcfInfoMap (chromosome, then position) and looks every site up in the graph; the windows are the
+// same nodes in the same order, so every task writes the lines of its own nodes and the pieces are joined in task
+// order (chromosomes of the graph that the VCF lacks have thrown in window() already).
+void Genotyper::write_piece(RunShared& s, size_t t)
+{
+    s.piece_done[t] = 1;
+    const Task& task = s.tasks[t];
+    const Chrom& chr = *task.chr;
+    auto vc = g_.vcf_info.find(chr.name);
+    if (vc == g_.vcf_info.end()) return;
+    SiteWalk walk(vc->second);
+    std::string out;
+    std::vector<uint64_t> gt;
+    for (uint32_t ni = task.first; ni < task.last; ++ni) {
+        const Node& node = chr.nodes[ni];
+        const std::vector<std::string>* fields = walk.at(node.start);
+        append_call_line(out, node, s.r.cfg->min_gq, gt, [&](std::string& o) { return append_site_head(o, fields); });
+    }
+    s.pieces[t] = std::move(out);
+}
+
+// ---- Windows on the pool.  Three kinds of work on one pool: a window is prepared (window()), the recursion and posterior of a PART of the
+// windows run on the device (one call per part, on a thread of its own that mostly waits), the calls of a part's windows
+// are written back (window_finish()).  A chain is serial from its first node to its last, so the device takes as long
+// for ten windows as for all of them: the parts go to the device as soon as their windows are prepared, side by side
+// (vgmi_hmm_calls_part: own stream and buffers per call), while the pool prepares the next and finishes the last.
+// At most four parts, over all the samples genotyped at the same time (set_device): a process has four hardware queues by
+// default and a stream beyond them shares one, waiting behind the other stream's kernel for its whole length.
+void Genotyper::hmm_on_pool(RunShared& s, std::vector<WindowWork>& works, const WindowBuffers& bufs, size_t n_gt)
+{
+    const Run& r = s.r;
+    const GenotypeConfig& cfg = *r.cfg;
+    const std::vector<Task>& tasks = s.tasks;
+    const bool device_ready = bufs.ready();
     const size_t max_parts = std::min<size_t>(4, dev_parts_);
-    const size_t part_windows = std::max<size_t>(n_threads, (tasks.size() + max_parts - 1) / max_parts);
+    const size_t part_windows = std::max<size_t>(s.n_threads, (tasks.size() + max_parts - 1) / max_parts);
     const size_t n_parts = device_ready ? (tasks.size() + part_windows - 1) / part_windows : 0;
     std::vector<std::atomic<size_t>> part_done(n_parts);
     for (auto& d : part_done) d.store(0);
@@ -1727,13 +1930,11 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
     std::atomic<size_t> next{0};
     std::string error;
     std::atomic<bool> failed{false};
-    std::atomic<int64_t> dev_first{INT64_MAX}, dev_last{0};
     auto fail_with = [&](const char* what) {
         if (!failed.exchange(true)) error = what;
         std::lock_guard<std::mutex> lock(q_mu);
         q_cv.notify_all();
     };
-    auto since_begin = [&]() { return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count(); };
     auto run_part = [&](size_t part) {
         try {
             const size_t t0 = part * part_windows, t1 = std::min(tasks.size(), t0 + part_windows);
@@ -1741,7 +1942,7 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
             for (size_t t = t0; t < t1; ++t)
                 if (works[t].on_device && !works[t].nodes.empty()) dw.push_back(t);
             if (!dw.empty() && !failed.load()) {
-                const size_t n = dev_n_gt;
+                const size_t n = n_gt;
                 std::vector<uint8_t> keep(dw.size() * n * n);
                 std::vector<vgmi_hmm_chain> chains;
                 for (size_t wi = 0; wi < dw.size(); ++wi) {
@@ -1754,12 +1955,10 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
                 }
                 const uint64_t row_lo = works[t0].row0, row_hi = works[t1 - 1].row0 + works[t1 - 1].room;
                 const long double uniform = 1.0L / (long double)n;
-                const int64_t ta = since_begin();
-                const int rc = vgmi_hmm_calls_part(dev_, (uint32_t)n, cfg.sample_ploidy, keep.data(), (uint32_t)dw.size(), raw_obs.p, row_lo, row_hi,
-                                        static_cast<const uint32_t*>(raw_row.p), static_cast<const uint8_t*>(raw_restart.p), raw_pw.p, 2 * row_lo,
-                                        2 * row_hi, &uniform, chains.data(), (uint32_t)chains.size(), static_cast<const uint8_t*>(raw_gid.p),
-                                        static_cast<const uint8_t*>(raw_order.p), static_cast<const uint64_t*>(raw_fs.p),
-                                        static_cast<const uint64_t*>(raw_bs.p), raw_prob.p, static_cast<uint32_t*>(raw_win.p));
+                const int64_t ta = s.since_begin();
+                const int rc = vgmi_hmm_calls_part(dev_, (uint32_t)n, cfg.sample_ploidy, keep.data(), (uint32_t)dw.size(), bufs.obs, row_lo, row_hi, bufs.row,
+                                                   bufs.restart, bufs.pw, 2 * row_lo, 2 * row_hi, &uniform, chains.data(), (uint32_t)chains.size(), bufs.gid,
+                                                   bufs.order, bufs.fs, bufs.bs, bufs.prob, bufs.win);
                 if (rc == VGMI_E_NOMEM || (rc == VGMI_OK && getenv("VGH_HMM_FAKE_NOMEM") && part % 2 == 1)) {
                     // the device had no room for this part after all (other samples' parts, the table, the read buffers): the
                     // host runs these windows' recursion instead, with the haplotypes the first pass drew -- the sample is
@@ -1774,11 +1973,10 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
                     dw.clear();
                 } else if (rc != VGMI_OK)
                     throw std::runtime_error(std::string("device HMM recursion: ") + vgmi_last_error(dev_));
-                const int64_t tb = since_begin();
+                const int64_t tb = s.since_begin();
                 if (g_phase_on)
                     std::fprintf(stderr, "[varigraph-mi] HMM part %zu (windows %zu-%zu): on the device from %.3f to %.3f s\n", part, t0, t1 - 1, ta * 1e-9, tb * 1e-9);
-                for (int64_t v = dev_first.load(); ta < v && !dev_first.compare_exchange_weak(v, ta);) {}
-                for (int64_t v = dev_last.load(); tb > v && !dev_last.compare_exchange_weak(v, tb);) {}
+                s.note_device_span(ta, tb);
             }
             std::lock_guard<std::mutex> lock(q_mu);
             for (size_t t : dw) finish_q.push_back(t);
@@ -1819,1072 +2017,771 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
             try {
                 CpuBudget::Hold cpu;
                 WindowWork& w = works[t];
-                window_finish(w, static_cast<const long double*>(raw_prob.p) + w.row0, static_cast<const uint32_t*>(raw_win.p) + w.row0, r);
-                make_piece(t);
+                window_finish(w, bufs.prob + w.row0, bufs.win + w.row0, r);
+                write_piece(s, t);
             } catch (const std::exception& e) {
                 fail_with(e.what());
                 return;
             }
         }
     };
-    // ---- emission scores on the device too (vgmi_hmm_emissions): a diploid sample over a graph all of whose haplotypes are selected
-    // (-n >= haplotypes: one genotype list for every window, no k-mer list is ever pruned).  Per part of the windows: the host lists
-    // the nodes' entry ranges, the device scores them from the node-ordered coverage it was handed, the host scores the few nodes
-    // whose haplotype sequences must be consulted, builds the step tables (libm) and the genotype strings, the device runs recursion
-    // and posterior on the scores where they lie.  VGH_HMM_EMIT_DEVICE=0: the host prepares the scores as before.
-    bool emitted_on_device = false;
-    std::atomic<size_t> emit_windows_done{0};
-    if (dev_emit) {
-        const double tb0 = since_begin() * 1e-9;
-        const float ave = r.hap_cov;
-        double lower = 256.0f, upper = -0.1f;
-        poisson_interval(ave, lower, upper);
-        // one genotype list for the whole sample
-        std::vector<uint16_t> top;
-        for (const auto& kv : g_.hap_names) top.push_back(kv.first);
-        std::sort(top.begin(), top.end());
-        const std::vector<std::vector<uint16_t>> genotypes = haplotype_combinations(top, cfg.sample_type, cfg.sample_ploidy, (uint16_t)(n_hap_ - 1));
-        const size_t n_gt = genotypes.size();
-        std::vector<uint16_t> used;
-        for (const auto& gtv : genotypes) used.insert(used.end(), gtv.begin(), gtv.end());
-        std::sort(used.begin(), used.end());
-        used.erase(std::unique(used.begin(), used.end()), used.end());
-        bool pairs = true;      // (every genotype holds `ploidy` haplotypes: pairs for a diploid sample)
-        for (const auto& gtv : genotypes) pairs = pairs && gtv.size() == cfg.sample_ploidy;
-        if (pairs && n_gt >= 1 && n_gt <= 128 && used.size() <= 16) {
-            GenotypeList glist;
-            glist.off.assign(n_gt + 1, 0);
-            std::vector<uint8_t> where(n_hap_ + 1, 0), used8(used.size());
-            for (size_t p2 = 0; p2 < used.size(); ++p2) {
-                where[used[p2]] = (uint8_t)p2;
-                used8[p2] = (uint8_t)used[p2];
-            }
-            glist.pos_a.resize(n_gt);
-            glist.pos_b.resize(n_gt);
-            glist.pairs = cfg.sample_ploidy == 2;
-            std::vector<uint8_t> pos_all(n_gt * cfg.sample_ploidy);      // per genotype its haplotypes' places in `used`
-            for (size_t gi = 0; gi < n_gt; ++gi) {
-                glist.flat.insert(glist.flat.end(), genotypes[gi].begin(), genotypes[gi].end());
-                glist.off[gi + 1] = (uint32_t)glist.flat.size();
-                glist.pos_a[gi] = where[genotypes[gi][0]];
-                glist.pos_b[gi] = where[genotypes[gi][1]];
-                for (uint32_t q = 0; q < cfg.sample_ploidy; ++q) pos_all[gi * cfg.sample_ploidy + q] = where[genotypes[gi][q]];
-            }
-            if (cfg.sample_ploidy != 2) {      // (hidden_states' pair shuffle is for pairs; the host-scored path of VGH_HMM_FIX_DEVICE=0 takes the general loop)
-                glist.pos_a.clear();
-                glist.pos_b.clear();
-            }
-            auto shared2 = [](const std::vector<uint16_t>& a, const std::vector<uint16_t>& b) -> uint8_t {
-                uint8_t n2 = 0;
-                for (size_t x = 0, y = 0; x < a.size() && y < b.size();) {
-                    if (a[x] < b[y]) ++x;
-                    else if (b[y] < a[x]) ++y;
-                    else { ++n2; ++x; ++y; }
-                }
-                return n2;
-            };
-            std::vector<uint8_t> keep_mat(n_gt * n_gt);
-            for (size_t i = 0; i < n_gt; ++i)
-                for (size_t j = 0; j < n_gt; ++j) keep_mat[i * n_gt + j] = shared2(genotypes[i], genotypes[j]);
-            uint64_t top_mask = 0;
-            for (uint16_t hap : top) top_mask |= 1ULL << hap;
-            // the sample's libm values: geometric(error_param(ave), c) for h = 0, poisson(ave * h, c) for h = 1 .. ploidy
-            std::vector<long double> tab((size_t)(cfg.sample_ploidy + 1) * 256);
-            for (int c2 = 0; c2 < 256; ++c2) {
-                tab[c2] = geometric(error_param(ave), (uint8_t)c2);
-                for (uint8_t h = 1; h <= cfg.sample_ploidy; ++h) tab[(size_t)h * 256 + c2] = poisson_pmf(ave * h, (uint8_t)c2);
-            }
-            if (!entries_uploaded_) {
-                if (vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()) != VGMI_OK) throw std::runtime_error(std::string("device HMM emissions: ") + vgmi_last_error(dev_));
-                entries_uploaded_ = true;
-            }
-            if (vgmi_hmm_sample_upload(dev_, cov_node, n_entries) != VGMI_OK) throw std::runtime_error(std::string("device HMM emissions: ") + vgmi_last_error(dev_));
-            const uint32_t stride = cfg.sample_ploidy + 1;
-            const size_t max_parts_e = std::min<size_t>(4, dev_parts_);
-            const size_t per_part = std::max<size_t>(1, (tasks.size() + max_parts_e - 1) / max_parts_e);
-            const size_t n_parts_e = (tasks.size() + per_part - 1) / per_part;
-            std::atomic<bool> broken{false};
-            std::mutex err_mu;
-            std::string err_text;
-            const std::string cache_key = std::to_string(tasks.size()) + "/" + std::to_string(per_part) + "/" + std::to_string(cfg.sv_only) + "/" +
-                                          std::to_string(cfg.sample_ploidy) + "/" + cfg.sample_type + "/" + std::to_string(n_gt) + "/" +
-                                          std::to_string(r.haploid_num) + "/" + std::to_string(cfg.chr_len_thread);
-            // What a part's device calls need beyond a sample's coverage is a function of the graph and the options: the rows (entry
-            // ranges, reference-allele masks), and the PLAN -- genotype strings, which rows have a score, the step tables (libm), chains,
-            // all of it resident on the device (vgmi_hmm_plan).  Made by the first sample that gets there, kept with the graph, shared
-            // by every Genotyper of the run (eight consumers of one device built eight of everything in round 4).
-            int dev_id = 0;
-            (void)vgmi_device_of(dev_, &dev_id);
-            if (emit_cache_.size() != n_parts_e) {
-                emit_cache_.clear();
-                emit_cache_.resize(n_parts_e);
-            }
-            for (size_t part = 0; part < n_parts_e; ++part) {
-                const std::string slot = "emit/" + std::to_string(dev_id) + "/" + std::to_string(n_parts_e) + "/" + std::to_string(part) + "/" + cache_key;
-                std::lock_guard<std::mutex> lock(g_.shared_mu);
-                auto it = g_.shared_slots.find(slot);
-                if (it == g_.shared_slots.end()) it = g_.shared_slots.emplace(slot, std::static_pointer_cast<void>(std::make_shared<EmitPartCache>())).first;
-                emit_cache_[part] = std::static_pointer_cast<EmitPartCache>(it->second);
-            }
-            auto part_fn = [&](size_t part) {
-                try {
-                    const size_t t0 = part * per_part, t1 = std::min(tasks.size(), t0 + per_part);
-                    EmitPartCache& pc = *emit_cache_[part];
-                    // rows: every node the HMM works on, window after window (the same for every sample and every Genotyper: listed once)
-                    {
-                        std::lock_guard<std::mutex> lock(pc.mu);
-                        if (pc.key != cache_key) {
-                            CpuBudget::Hold cpu;
-                            PhaseTimer t_list(g_phase.list);
-                            pc.e_begin.clear(); pc.e_count.clear(); pc.row_node.clear(); pc.gt0.clear();
-                            pc.plan.reset();
-                            pc.win_row0.assign(t1 - t0 + 1, 0);
-                            for (size_t t = t0; t < t1; ++t) {
-                                Chrom& chr = *tasks[t].chr;
-                                auto vcf_chr = g_.vcf_info.find(chr.name);
-                                if (vcf_chr == g_.vcf_info.end()) throw std::runtime_error("'" + chr.name + "' does not exist in the VCF file.");
-                                for (uint32_t i = tasks[t].first; i < tasks[t].last; ++i) {
-                                    const Node& n = chr.nodes[i];
-                                    if (n.gn->hap_gt.size() <= 1) continue;
-                                    if (cfg.sv_only) {
-                                        auto site = vcf_chr->second.find(n.start);
-                                        if (site == vcf_chr->second.end())
-                                            throw std::runtime_error("'" + chr.name + ":" + std::to_string(n.start) + "' does not exist in the VCF file.");
-                                        if (site->second[3].size() < 50 && site->second[4].size() < 50) continue;
-                                    }
-                                    if (!n.kmers.empty() && (size_t)(n.kmers.back() - n.kmers.front()) + 1 != n.kmers.size()) {
-                                        broken = true;      // a pruned list after all: the host path
-                                        return;
-                                    }
-                                    pc.e_begin.push_back(n.kmers.empty() ? 0 : n.kmers.front());
-                                    pc.e_count.push_back((uint32_t)n.kmers.size());
-                                    uint16_t m = 0;
-                                    for (size_t p2 = 0; p2 < used.size(); ++p2) m |= (uint16_t)((n.gn->hap_gt[used[p2]] == 0) << p2);
-                                    pc.gt0.push_back(m);
-                                    pc.row_node.push_back(i);
-                                }
-                                pc.win_row0[t - t0 + 1] = pc.e_begin.size();
-                            }
-                            pc.key = cache_key;
-                        }
-                    }
-                    const std::vector<uint64_t>& e_begin = pc.e_begin;
-                    const std::vector<uint32_t>&e_count = pc.e_count, &row_node = pc.row_node;
-                    const std::vector<uint16_t>& gt0 = pc.gt0;
-                    const std::vector<size_t>& win_row0 = pc.win_row0;
-                    const size_t n_rows = e_begin.size();
-                    if (n_rows == 0) return;      // no node of this part is the HMM's business (--sv over a part without long alleles): no calls, no lines
-                    std::vector<uint32_t> n_kept(n_rows ? n_rows : 1);
-                    std::vector<uint8_t> flags(n_rows ? n_rows : 1);
-                    struct PartHandle {
-                        vgmi_hmm_part* p = nullptr;
-                        ~PartHandle() { vgmi_hmm_part_free(p); }
-                    } ph;
-                    const int64_t ta = since_begin();
-                    int64_t t_emit = 0, t_a = 0, t_rows = 0, t_b = 0, t_calls = 0;
-                    size_t n_fixed_rows = 0;
-                    if (vgmi_hmm_emissions_ploidy(dev_, (uint32_t)n_gt, cfg.sample_ploidy, (uint32_t)used.size(), used8.data(), pos_all.data(), top_mask,
-                                                  (uint32_t)g_.bitlen, ave, lower, upper, tab.data(), n_rows, e_begin.data(), e_count.data(), gt0.data(), n_kept.data(),
-                                                  flags.data(), &ph.p) != VGMI_OK)
-                        throw std::runtime_error(std::string("device HMM emissions: ") + vgmi_last_error(dev_));
-                    t_emit = since_begin();
-                    for (size_t rr = 0; rr < n_rows; ++rr)
-                        if (flags[rr] & 2u) {
-                            broken = true;          // a k-mer no haplotype carries: the host path prunes it
-                            return;
-                        }
-                    // The part's windows on `helpers` threads.  A: the nodes whose haplotype sequences must be consulted -- which entries
-                    // lose which haplotypes, for the device to score those rows again.  (Once per graph, under the part's lock: the
-                    // genotype strings, which nodes have a score at all, B: the step tables (libm) -- the plan.)  Then recursion and
-                    // posterior on the device.  C: the calls and the VCF lines.
-                    const size_t nw = t1 - t0;
-                    const size_t helpers = std::max<size_t>(1, std::min<size_t>(nw, n_threads / n_parts_e));
-                    auto over_windows = [&](std::atomic<long long>& spent, const std::function<void(size_t)>& fn) {
-                        std::atomic<size_t> nextw{0};
-                        std::string herr;
-                        std::mutex hmu;
-                        auto body = [&]() {
-                            for (;;) {
-                                const size_t wi = nextw.fetch_add(1);
-                                if (wi >= nw) return;
-                                try {
-                                    CpuBudget::Hold cpu;
-                                    PhaseTimer tt(spent);
-                                    fn(wi);
-                                } catch (const std::exception& e) {
-                                    std::lock_guard<std::mutex> lock(hmu);
-                                    if (herr.empty()) herr = e.what();
-                                }
-                            }
-                        };
-                        std::vector<std::thread> hs;
-                        for (size_t h2 = 1; h2 < helpers; ++h2) hs.emplace_back(body);
-                        body();
-                        for (auto& th : hs) th.join();
-                        if (!herr.empty()) throw std::runtime_error(herr);
-                    };
-                    std::vector<std::vector<uint64_t>> host_rows(nw);
-                    std::vector<std::vector<long double>> host_obs(nw);
-                    static const bool fix_on_device = !(getenv("VGH_HMM_FIX_DEVICE") && getenv("VGH_HMM_FIX_DEVICE")[0] == '0');
-                    std::vector<std::vector<uint64_t>> fix_rows(nw);
-                    std::vector<std::vector<uint32_t>> fix_cnt(nw);
-                    std::vector<std::vector<uint32_t>> fix_j(nw);
-                    std::vector<std::vector<uint16_t>> fix_mask(nw);
-                    over_windows(g_phase.pass_a, [&](size_t wi) {
-                        Chrom& chr = *tasks[t0 + wi].chr;
-                        ScoreCtx sctx;
-                        sctx.ave = ave;
-                        sctx.score_up = upper;
-                        NodeStates st;
-                        for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
-                            if (!(flags[rr] & 1u)) continue;
-                            if (fix_on_device) {
-                                // a multi-copy, under-covered, carried k-mer: the reference consults the haplotype's sequence (:760-800).
-                                // The strings are the host's; the row's products stay on the device, scored again below with the
-                                // haplotypes the sequences rule out taken off the entries concerned
-                                PhaseTimer tt(g_phase.states);
-                                const size_t before = fix_j[wi].size();
-                                sequence_fixes(chr, row_node[rr], used, gt0[rr], lower, upper, r, fix_j[wi], fix_mask[wi]);
-                                if (fix_j[wi].size() != before) {
-                                    fix_rows[wi].push_back(rr);
-                                    fix_cnt[wi].push_back((uint32_t)(fix_j[wi].size() - before));
-                                }
-                            } else {
-                                // ... VGH_HMM_FIX_DEVICE=0: scored by the host (hidden states, products in x87 arithmetic), handed in as rows
-                                {
-                                    PhaseTimer tt(g_phase.states);
-                                    st = hidden_states(chr, row_node[rr], top, genotypes, used, glist, lower, upper, true, r, std::move(st), nullptr);
-                                }
-                                PhaseTimer tt(g_phase.emit);
-                                const std::vector<long double> obs = score_states(st, sctx);
-                                n_kept[rr] = (uint32_t)(obs.empty() ? 0 : st.c.size());
-                                if (!obs.empty()) {
-                                    host_rows[wi].push_back(rr);
-                                    host_obs[wi].insert(host_obs[wi].end(), obs.begin(), obs.end());
-                                }
-                            }
-                        }
-                    });
-                    t_a = since_begin();
-                    {
-                        std::vector<uint64_t> all_rows;
-                        std::vector<long double> all_obs;
-                        for (size_t wi = 0; wi < nw; ++wi) {
-                            all_rows.insert(all_rows.end(), host_rows[wi].begin(), host_rows[wi].end());
-                            all_obs.insert(all_obs.end(), host_obs[wi].begin(), host_obs[wi].end());
-                            std::vector<long double>().swap(host_obs[wi]);
-                        }
-                        if (!all_rows.empty() && vgmi_hmm_part_set_rows(ph.p, all_rows.size(), all_rows.data(), all_obs.data()) != VGMI_OK)
-                            throw std::runtime_error(std::string("device HMM emissions: ") + vgmi_last_error(dev_));
-                        std::vector<uint64_t> f_rows;
-                        std::vector<uint32_t> f_off(1, 0);
-                        std::vector<uint32_t> f_j;
-                        std::vector<uint16_t> f_m;
-                        for (size_t wi = 0; wi < nw; ++wi) {
-                            f_rows.insert(f_rows.end(), fix_rows[wi].begin(), fix_rows[wi].end());
-                            for (uint32_t cnt2 : fix_cnt[wi]) f_off.push_back(f_off.back() + cnt2);
-                            f_j.insert(f_j.end(), fix_j[wi].begin(), fix_j[wi].end());
-                            f_m.insert(f_m.end(), fix_mask[wi].begin(), fix_mask[wi].end());
-                        }
-                        n_fixed_rows = f_rows.size();
-                        if (!f_rows.empty() && vgmi_hmm_part_fix_rows(ph.p, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()) != VGMI_OK)
-                            throw std::runtime_error(std::string("device HMM emissions: ") + vgmi_last_error(dev_));
-                    }
-                    t_rows = since_begin();
-                    // ---- the plan: for the rows that have a score -- the same for every sample of this path (a row's kept k-mers are
-                    // those some haplotype carries, and every haplotype is selected); held against the pattern all the same
-                    std::vector<uint8_t> scored(n_rows);
-                    for (size_t rr = 0; rr < n_rows; ++rr) scored[rr] = n_kept[rr] != 0;
-                    std::shared_ptr<EmitPartPlan> plan;
-                    {
-                        std::lock_guard<std::mutex> lock(pc.mu);
-                        if (!pc.plan || pc.plan->scored != scored) {
-                            auto np = std::make_shared<EmitPartPlan>();
-                            np->scored = scored;
-                            np->win_nodes.resize(nw);
-                            np->win_rows.resize(nw);
-                            struct Seen { uint32_t start, end; int64_t row; };
-                            std::vector<std::vector<Seen>> seen(nw);
-                            std::vector<uint8_t> gid(n_rows * n_gt, 0), order(n_rows * n_gt, 0);
-                            over_windows(g_phase.pass_a, [&](size_t wi) {
-                                Chrom& chr = *tasks[t0 + wi].chr;
-                                // the genotype strings of a node with two alleles depend on which haplotypes carry the reference allele only:
-                                // one evaluation per distinct mask (the strings themselves as genotype_strings builds them)
-                                std::unordered_map<uint32_t, uint32_t> gs_memo;      // mask -> a row that holds the pattern
-                                for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
-                                    Node& n = chr.nodes[row_node[rr]];
-                                    const uint32_t n_start = n.start, n_end = (uint32_t)(n_start + n.gn->seqs[0].size() - 1);
-                                    if (!scored[rr]) {
-                                        seen[wi].push_back(Seen{n_start, n_end, -1});
-                                        continue;
-                                    }
-                                    seen[wi].push_back(Seen{n_start, n_end, (int64_t)rr});
-                                    bool biallelic = true;
-                                    for (uint16_t hap : used) biallelic = biallelic && n.gn->hap_gt[hap] <= 1;
-                                    auto it = biallelic ? gs_memo.find(gt0[rr]) : gs_memo.end();
-                                    if (it != gs_memo.end()) {
-                                        std::memcpy(gid.data() + rr * n_gt, gid.data() + (size_t)it->second * n_gt, n_gt);
-                                        std::memcpy(order.data() + rr * n_gt, order.data() + (size_t)it->second * n_gt, n_gt);
-                                    } else {
-                                        (void)genotype_strings(n, genotypes, gid.data() + rr * n_gt, order.data() + rr * n_gt);     // <= 128 strings: always fits
-                                        if (biallelic) gs_memo.emplace(gt0[rr], (uint32_t)rr);
-                                    }
-                                    np->win_nodes[wi].push_back(row_node[rr]);
-                                    np->win_rows[wi].push_back((uint32_t)rr);
-                                }
-                            });
-                            {   // the lines' shared heads, window by window (one walk along the chromosome's site map per window)
-                                std::vector<std::string> heads(nw);
-                                std::vector<std::vector<uint32_t>> head_len(nw);
-                                over_windows(g_phase.pass_a, [&](size_t wi) {
-                                    const Chrom& chr = *tasks[t0 + wi].chr;
-                                    auto vc = g_.vcf_info.find(chr.name);
-                                    std::string& out = heads[wi];
-                                    head_len[wi].assign(win_row0[wi + 1] - win_row0[wi], 0);
-                                    if (vc == g_.vcf_info.end()) return;
-                                    const auto& sites = vc->second;
-                                    auto site = win_row0[wi] < win_row0[wi + 1] ? sites.lower_bound(chr.nodes[row_node[win_row0[wi]]].start) : sites.end();
-                                    uint32_t prev_start = 0;
-                                    for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
-                                        const Node& node = chr.nodes[row_node[rr]];
-                                        if (node.start < prev_start) site = sites.lower_bound(node.start);
-                                        prev_start = node.start;
-                                        while (site != sites.end() && site->first < node.start) ++site;
-                                        if (site == sites.end() || site->first != node.start) continue;
-                                        const auto& fields = site->second;
-                                        const size_t before = out.size();
-                                        for (size_t i = 0; i < 9; i++) {
-                                            if (i == 0) out += fields[i];
-                                            else if (i == 6) out += "\tPASS";
-                                            else if (i < 8) { out += '\t'; out += fields[i]; }
-                                            else out += "\tGT:GQ:GPP:NAK:CAK:UK";
-                                        }
-                                        out += '\t';
-                                        head_len[wi][rr - win_row0[wi]] = (uint32_t)(out.size() - before);
-                                    }
-                                });
-                                np->line_head_off.assign(n_rows + 1, 0);
-                                size_t total = 0;
-                                for (size_t wi = 0; wi < nw; ++wi) total += heads[wi].size();
-                                np->line_head.reserve(total);
-                                for (size_t wi = 0; wi < nw; ++wi) {
-                                    for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr)
-                                        np->line_head_off[rr + 1] = np->line_head_off[rr] + head_len[wi][rr - win_row0[wi]];
-                                    np->line_head += heads[wi];
-                                    std::string().swap(heads[wi]);
-                                }
-                            }
-                            std::vector<size_t> win_step0(nw + 1, 0);
-                            for (size_t wi = 0; wi < nw; ++wi) win_step0[wi + 1] = win_step0[wi] + 2 * np->win_rows[wi].size();
-                            const size_t n_steps = win_step0[nw];
-                            np->n_steps = n_steps;
-                            if (n_steps) {
-                                std::vector<long double> pw(n_steps * 2 * stride);
-                                std::vector<uint32_t> row(n_steps, 0);
-                                std::vector<uint8_t> restart(n_steps, 0);
-                                std::vector<uint64_t> fwd(n_rows, 0), bwd(n_rows, 0);
-                                std::vector<vgmi_hmm_chain> chains;
-                                for (size_t wi = 0; wi < nw; ++wi) {
-                                    const size_t m = np->win_rows[wi].size();
-                                    if (!m) continue;
-                                    chains.push_back(vgmi_hmm_chain{win_step0[wi], m, 0, 0});
-                                    chains.push_back(vgmi_hmm_chain{win_step0[wi] + m, m, 0, 0});
-                                }
-                                over_windows(g_phase.pass_b, [&](size_t wi) {
-                                    const size_t m = np->win_rows[wi].size();
-                                    if (!m) return;
-                                    const size_t step0 = win_step0[wi];
-                                    // the tables of powers are a function of the distance alone: neighbouring nodes are tens to hundreds of bases
-                                    // apart, so a window's few thousand steps share a few hundred distinct tables (same libm calls, each made once)
-                                    constexpr uint32_t kMemo = 4096;
-                                    std::vector<long double> memo((size_t)kMemo * 2 * stride);
-                                    std::vector<uint8_t> memo_have(kMemo, 0);
-                                    auto powers = [&](long double* dst, uint32_t distance) {
-                                        if (distance < kMemo && memo_have[distance]) {
-                                            std::memcpy(dst, &memo[(size_t)distance * 2 * stride], 2 * stride * sizeof(long double));
-                                            return;
-                                        }
-                                        long double recomb, no_recomb;
-                                        std::tie(recomb, no_recomb) = transition_probabilities(distance, (uint16_t)n_hap_);
-                                        for (uint32_t k = 0; k < stride; ++k) {
-                                            dst[k] = std::pow(no_recomb, (int32_t)k);
-                                            dst[stride + k] = std::pow(recomb, (int32_t)k);
-                                        }
-                                        if (distance < kMemo) {
-                                            std::memcpy(&memo[(size_t)distance * 2 * stride], dst, 2 * stride * sizeof(long double));
-                                            memo_have[distance] = 1;
-                                        }
-                                    };
-                                    const std::vector<Seen>& sn = seen[wi];
-                                    size_t j = 0;
-                                    for (size_t q = 0; q < sn.size(); ++q) {
-                                        if (sn[q].row < 0) continue;
-                                        const size_t fs = step0 + j, bs = step0 + m + (m - 1 - j);
-                                        powers(pw.data() + fs * 2 * stride, sn[q].start - (q ? sn[q - 1].end : 0u));
-                                        restart[fs] = (q == 0 || sn[q - 1].row < 0) ? 1 : 0;
-                                        row[fs] = (uint32_t)sn[q].row;
-                                        powers(pw.data() + bs * 2 * stride, (q + 1 < sn.size() ? sn[q + 1].start : 0u) - sn[q].end);
-                                        restart[bs] = (q + 1 == sn.size() || sn[q + 1].row < 0) ? 1 : 0;
-                                        row[bs] = (uint32_t)sn[q].row;
-                                        fwd[sn[q].row] = fs;
-                                        bwd[sn[q].row] = bs;
-                                        ++j;
-                                    }
-                                });
-                                const long double uniform = 1.0L / (long double)n_gt;
-                                if (vgmi_hmm_plan_create(dev_, (uint32_t)n_gt, cfg.sample_ploidy, keep_mat.data(), 1, n_rows, row.data(), restart.data(), pw.data(), n_steps,
-                                                         &uniform, chains.data(), (uint32_t)chains.size(), gid.data(), order.data(), fwd.data(), bwd.data(), &np->plan) != VGMI_OK)
-                                    throw std::runtime_error(std::string("device HMM plan: ") + vgmi_last_error(dev_));
-                            }
-                            pc.plan = np;
-                        }
-                        plan = pc.plan;
-                    }
-                    const std::vector<std::vector<uint32_t>>&win_nodes = plan->win_nodes, &win_rows = plan->win_rows;
-                    const size_t n_steps = plan->n_steps;
-                    t_b = since_begin();
-                    std::vector<long double> prob(n_rows ? n_rows : 1);
-                    std::vector<uint32_t> winner(n_rows ? n_rows : 1, 0xFFFFFFFFu);
-                    if (n_steps && vgmi_hmm_part_calls_plan(ph.p, plan->plan, prob.data(), winner.data()) != VGMI_OK)
-                        throw std::runtime_error(std::string("device HMM recursion: ") + vgmi_last_error(dev_));
-                    const int64_t tbb = since_begin();
-                    t_calls = tbb;
-                    if (g_phase_on)
-                        std::fprintf(stderr, "[varigraph-mi] HMM part %zu (windows %zu-%zu): emissions, recursion and posterior on the device from %.3f to %.3f s (%zu of %zu nodes scored by the host, %zu scored again on the device): "
-                                     "emission kernel %.3f, sequence checks (host) %.3f, rows fixed on the device %.3f, plan (strings + step tables: once per graph) %.3f, recursion + posterior %.3f\n",
-                                     part, t0, t1 - 1, ta * 1e-9, tbb * 1e-9, [&] { size_t c2 = 0; for (auto& v : host_rows) c2 += v.size(); return c2; }(), n_rows, n_fixed_rows,
-                                     (t_emit - ta) * 1e-9, (t_a - t_emit) * 1e-9, (t_rows - t_a) * 1e-9, (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
-                    for (int64_t v = dev_first.load(); ta < v && !dev_first.compare_exchange_weak(v, ta);) {}
-                    for (int64_t v = dev_last.load(); tbb > v && !dev_last.compare_exchange_weak(v, tbb);) {}
-                    // the calls' k-mer tallies on the device too (the node lists and the sample's coverage are there for the emissions):
-                    // per sample, the walk over every called node's k-mer list was 0.8 of 1.7 host thread-seconds (VGH_DEVICE_TALLIES=0: the walk)
-                    std::vector<uint32_t> tally;
-                    std::vector<uint8_t> tally_uniq;
-                    static const bool device_tallies = !(getenv("VGH_DEVICE_TALLIES") && getenv("VGH_DEVICE_TALLIES")[0] == '0');
-                    if (device_tallies && n_steps && cfg.sample_ploidy == 2 && n_hap_ <= 64 && n_gt <= 128) {
-                        std::vector<uint8_t> hap_ab(2 * n_gt, 0xFF);
-                        bool pairs = true;
-                        for (size_t g2 = 0; g2 < n_gt; ++g2) {
-                            if (genotypes[g2].size() != 2 || genotypes[g2][0] > 254 || genotypes[g2][1] > 254) { pairs = false; break; }
-                            hap_ab[2 * g2] = (uint8_t)genotypes[g2][0];
-                            hap_ab[2 * g2 + 1] = (uint8_t)genotypes[g2][1];
-                        }
-                        uint64_t sel = 0;
-                        for (uint16_t hap : top)
-                            if (hap < n_hap_ && hap < 64) sel |= 1ull << hap;
-                        if (pairs) {
-                            tally.resize(4 * n_rows);
-                            tally_uniq.resize(n_rows);
-                            if (vgmi_hmm_tallies(dev_, n_rows, e_begin.data(), e_count.data(), winner.data(), (uint32_t)n_gt, hap_ab.data(), n_hap_, sel, tally.data(),
-                                                 tally_uniq.data()) != VGMI_OK)
-                                throw std::runtime_error(std::string("device tallies: ") + vgmi_last_error(dev_));
-                        }
-                    }
-                    over_windows(g_phase.pass_c, [&](size_t wi) {
-                        if (!tally.empty()) {
-                            // a diploid sample with the calls' tallies from the device: the line is written straight from what came back
-                            // -- the called genotype's two haplotypes, their k-mer counts and coverage sums, the posterior -- without the
-                            // detour through the nodes' call records (window_finish writes them, make_piece reads them back: two walks over
-                            // half a million scattered nodes per sample)
-                            piece_done[t0 + wi] = 1;
-                            const Chrom& chr = *tasks[t0 + wi].chr;
-                            const std::vector<uint32_t>&nodes_w = win_nodes[wi], &rows_w = win_rows[wi];
-                            std::string out;
-                            size_t room = 0;
-                            for (size_t q = 0; q < rows_w.size(); ++q) room += (size_t)(plan->line_head_off[rows_w[q] + 1] - plan->line_head_off[rows_w[q]]) + 48;
-                            out.reserve(room);
-                            for (size_t q = 0; q < rows_w.size(); ++q) {
-                                const size_t rw = rows_w[q];
-                                if (winner[rw] >= n_gt) continue;            // no entry with a positive posterior: no call
-                                const uint64_t h0 = plan->line_head_off[rw], h1 = plan->line_head_off[rw + 1];
-                                if (h0 == h1) continue;                      // no such site in the VCF
-                                const Node& node = chr.nodes[nodes_w[q]];
-                                const std::vector<uint16_t>& called = genotypes[winner[rw]];
-                                const uint64_t ga = node.gn->hap_gt[called[0]], gb = node.gn->hap_gt[called[1]];
-                                if (ga == 0 && gb == 0) continue;
-                                out.append(plan->line_head, h0, h1 - h0);
-                                const long double pr = prob[rw];
-                                const float gq = phred_scaled(pr);
-                                if (gq < cfg.min_gq) out += "./.";
-                                else {
-                                    append_uint(out, ga);
-                                    out += '/';
-                                    append_uint(out, gb);
-                                }
-                                out += ':';
-                                append_fixed1(out, gq);
-                                out += ':';
-                                append_fixed1(out, pr);
-                                out += ':';
-                                const uint32_t* tl = &tally[4 * rw];
-                                append_uint(out, tl[0]);
-                                out += ',';
-                                append_uint(out, tl[2]);
-                                out += ':';
-                                append_fixed1(out, tl[0] ? static_cast<float>((uint64_t)tl[1]) / (float)(uint64_t)tl[0] : 0.0f);
-                                out += ',';
-                                append_fixed1(out, tl[2] ? static_cast<float>((uint64_t)tl[3]) / (float)(uint64_t)tl[2] : 0.0f);
-                                out += ':';
-                                append_uint(out, tally_uniq[rw]);
-                                out += '\n';
-                            }
-                            pieces[t0 + wi] = std::move(out);
-                            emit_windows_done += !nodes_w.empty();
-                            return;
-                        }
-                        WindowWork w;
-                        w.chr = tasks[t0 + wi].chr;
-                        w.n_gt = n_gt;
-                        w.genotypes = genotypes;
-                        w.top = top;
-                        w.nodes = win_nodes[wi];
-                        std::vector<long double> pr(w.nodes.size());
-                        std::vector<uint32_t> wn(w.nodes.size());
-                        std::vector<uint32_t> tl(tally.empty() ? 0 : 4 * w.nodes.size());
-                        std::vector<uint8_t> tu(tally.empty() ? 0 : w.nodes.size());
-                        for (size_t q = 0; q < w.nodes.size(); ++q) {
-                            const size_t rw = win_rows[wi][q];
-                            pr[q] = prob[rw];
-                            wn[q] = winner[rw];
-                            if (!tally.empty()) {
-                                std::memcpy(&tl[4 * q], &tally[4 * rw], 16);
-                                tu[q] = tally_uniq[rw];
-                            }
-                        }
-                        window_finish(w, pr.data(), wn.data(), r, tally.empty() ? nullptr : tl.data(), tally.empty() ? nullptr : tu.data());
-                        // the window's lines (make_piece's, for the scored nodes -- no other node has a call -- with the head of every
-                        // line taken from the plan instead of the site map)
-                        {
-                            piece_done[t0 + wi] = 1;
-                            const Chrom& chr = *tasks[t0 + wi].chr;
-                            std::string out;
-                            size_t room = 0;
-                            for (size_t q = 0; q < w.nodes.size(); ++q) room += (size_t)(plan->line_head_off[win_rows[wi][q] + 1] - plan->line_head_off[win_rows[wi][q]]) + 48;
-                            out.reserve(room);
-                            for (size_t q = 0; q < w.nodes.size(); ++q) {
-                                const Node& node = chr.nodes[w.nodes[q]];
-                                const SiteCall& call = node.call;
-                                if (call.haps.empty()) continue;
-                                const size_t rw = win_rows[wi][q];
-                                const uint64_t h0 = plan->line_head_off[rw], h1 = plan->line_head_off[rw + 1];
-                                if (h0 == h1) continue;      // no such site in the VCF
-                                bool all_ref = true;
-                                for (uint16_t hap : call.haps) all_ref = all_ref && node.gn->hap_gt[hap] == 0;
-                                if (all_ref) continue;
-                                out.append(plan->line_head, h0, h1 - h0);
-                                const float gq = phred_scaled(call.probability);
-                                const bool no_call = gq < cfg.min_gq;
-                                for (size_t i = 0; i < call.haps.size(); ++i) {
-                                    if (i) out += '/';
-                                    if (no_call) out += '.';
-                                    else append_uint(out, (uint64_t)node.gn->hap_gt[call.haps[i]]);
-                                }
-                                out += ':';
-                                append_fixed1(out, gq);
-                                out += ':';
-                                append_fixed1(out, call.probability);
-                                out += ':';
-                                for (size_t i = 0; i < call.kmer_num.size(); ++i) {
-                                    if (i) out += ',';
-                                    append_uint(out, call.kmer_num[i]);
-                                }
-                                out += ':';
-                                for (size_t i = 0; i < call.kmer_ave_cov.size(); i++) {
-                                    if (i) out += ',';
-                                    append_fixed1(out, call.kmer_ave_cov[i]);
-                                }
-                                out += ':';
-                                append_uint(out, call.unique_kmers);
-                                out += '\n';
-                            }
-                            pieces[t0 + wi] = std::move(out);
-                        }
-                        emit_windows_done += !w.nodes.empty();
-                    });
-                } catch (const std::exception& e) {
-                    std::lock_guard<std::mutex> lock(err_mu);
-                    if (err_text.empty()) err_text = e.what();
-                }
-            };
-            std::vector<std::thread> pthreads;
-            for (size_t p2 = 1; p2 < n_parts_e; ++p2) pthreads.emplace_back(part_fn, p2);
-            if (n_parts_e) part_fn(0);
-            for (auto& th : pthreads) th.join();
-            if (!err_text.empty()) throw std::runtime_error(err_text);
-            if (broken.load()) {
-                // a list was pruned after all (or would be): this graph takes the host's preparation from now on
-                emit_device_off_ = true;
-                return run(cov, hap_kmer_coverage, sample_name, cfg, cov_node);
-            }
-            emitted_on_device = true;
-            if (g_phase_on) std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s\n", n_parts_e, since_begin() * 1e-9 - tb0);
-        }
-    }
-    // ---- ... and with the haplotypes selected PER WINDOW (-n below the graph's haplotypes, a diploid sample: DESIGN_INGEST_HMM.md 4.13).
-    // The reference draws every window's haplotypes from their k-mer support, drops from a node's list every k-mer no drawn haplotype
-    // carries -- for good -- and scores what is left (src/genotype.cpp:500-610, 673-686, 815-818).  haplotype_combinations over the sorted
-    // draw yields pairs over -n places whatever was drawn: positions, keep matrix and the shape of every step are the sample's, the
-    // haplotype at each place is the window's.  Support sums, emissions (with the prune), recursion, posterior and tallies run on the
-    // device; the draws (std::mt19937, libm), the sequence checks (strings), the step tables (libm) and the genotype strings stay here.
-    // A row is the range [front, back] of what is left of its node's list plus the device's alive bytes; node.kmers is pruned by the same
-    // rule right after the emission launch, so that the host's lists and the device's bytes agree after every sample.
-    if (dev_select) {
-        const double tb0 = since_begin() * 1e-9;
-        const float ave = r.hap_cov;
-        double lower = 256.0f, upper = -0.1f;
-        poisson_interval(ave, lower, upper);
-        const uint32_t n_used = r.haploid_num;
-        std::vector<uint16_t> places(n_used);
-        std::iota(places.begin(), places.end(), (uint16_t)0);
-        const std::vector<std::vector<uint16_t>> shape = haplotype_combinations(places, cfg.sample_type, 2, (uint16_t)(n_hap_ - 1));
-        const size_t n_gt = shape.size();
-        bool pairs = n_gt >= 1 && n_gt <= 128;
-        for (const auto& gtv : shape) pairs = pairs && gtv.size() == 2;
-        if (pairs) {
-            std::vector<uint8_t> pos_a(n_gt), pos_b(n_gt), keep_mat(n_gt * n_gt);
-            for (size_t gi = 0; gi < n_gt; ++gi) {
-                pos_a[gi] = (uint8_t)shape[gi][0];
-                pos_b[gi] = (uint8_t)shape[gi][1];
-            }
-            for (size_t i = 0; i < n_gt; ++i)
-                for (size_t j = 0; j < n_gt; ++j) {      // std::set_intersection of two sorted pairs (places keep the haplotypes' order)
-                    uint8_t n2 = 0;
-                    for (size_t x = 0, y = 0; x < 2 && y < 2;) {
-                        if (shape[i][x] < shape[j][y]) ++x;
-                        else if (shape[j][y] < shape[i][x]) ++y;
-                        else { ++n2; ++x; ++y; }
-                    }
-                    keep_mat[i * n_gt + j] = n2;
-                }
-            std::vector<long double> tab(3 * 256);
-            for (int c2 = 0; c2 < 256; ++c2) {
-                tab[c2] = geometric(error_param(ave), (uint8_t)c2);
-                for (uint8_t h = 1; h <= 2; ++h) tab[(size_t)h * 256 + c2] = poisson_pmf(ave * h, (uint8_t)c2);
-            }
-            auto dev_check = [&](int rc, const char* what) {
-                if (rc != VGMI_OK) throw std::runtime_error(std::string(what) + vgmi_last_error(dev_));
-            };
-            if (!entries_uploaded_) {
-                dev_check(vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
-                entries_uploaded_ = true;
-                if (!lists_whole_.load()) alive_stale_.store(true);
-            }
-            dev_check(vgmi_hmm_sample_upload(dev_, cov_node, n_entries), "device HMM emissions: ");
-            if (alive_stale_.load()) {      // a sample of this run took a host path: the lists as the host left them
-                std::vector<uint8_t> alive(n_entries, 0);
-                for (const auto& c : chroms_)
-                    for (const auto& n : c.nodes)
-                        for (uint32_t pos : n.kmers) alive[pos] = 1;
-                dev_check(vgmi_hmm_alive_upload(dev_, alive.data(), n_entries), "device HMM emissions: ");
-                alive_stale_.store(false);
-            }
-            const size_t nw = tasks.size();
-            // rows, window after window.  Support reads every node with more than one allele; the HMM works on those --sv leaves.
-            std::vector<uint64_t> sup_begin, e_begin_sv;
-            std::vector<uint32_t> sup_count, sup_win, sup_node, e_count_sv, e_win_sv, e_node_sv;
-            std::vector<size_t> win_row0(nw + 1, 0);
-            {
-                CpuBudget::Hold cpu;
-                PhaseTimer t_list(g_phase.list);
-                for (size_t t = 0; t < nw; ++t) {
-                    Chrom& chr = *tasks[t].chr;
-                    auto vcf_chr = g_.vcf_info.find(chr.name);
-                    if (vcf_chr == g_.vcf_info.end()) throw std::runtime_error("'" + chr.name + "' does not exist in the VCF file.");
-                    for (uint32_t i = tasks[t].first; i < tasks[t].last; ++i) {
-                        const Node& n = chr.nodes[i];
-                        if (n.gn->hap_gt.size() <= 1) continue;
-                        const uint64_t b = n.kmers.empty() ? 0 : n.kmers.front();
-                        const uint32_t cnt = n.kmers.empty() ? 0 : n.kmers.back() - n.kmers.front() + 1;
-                        sup_begin.push_back(b);
-                        sup_count.push_back(cnt);
-                        sup_win.push_back((uint32_t)t);
-                        sup_node.push_back(i);
-                        if (cfg.sv_only) {
-                            auto site = vcf_chr->second.find(n.start);
-                            if (site == vcf_chr->second.end())
-                                throw std::runtime_error("'" + chr.name + ":" + std::to_string(n.start) + "' does not exist in the VCF file.");
-                            if (site->second[3].size() < 50 && site->second[4].size() < 50) continue;
-                            e_begin_sv.push_back(b);
-                            e_count_sv.push_back(cnt);
-                            e_win_sv.push_back((uint32_t)t);
-                            e_node_sv.push_back(i);
-                        }
-                    }
-                    win_row0[t + 1] = cfg.sv_only ? e_begin_sv.size() : sup_begin.size();
-                }
-            }
-            const std::vector<uint64_t>& e_begin = cfg.sv_only ? e_begin_sv : sup_begin;
-            const std::vector<uint32_t>&e_count = cfg.sv_only ? e_count_sv : sup_count, &row_win = cfg.sv_only ? e_win_sv : sup_win,
-                                       &row_node = cfg.sv_only ? e_node_sv : sup_node;
-            const size_t n_rows = e_begin.size();
-            const int64_t ta = since_begin();
-            // 1. the support the draw is weighted by, on the device
-            std::vector<uint32_t> support(nw * n_hap_, 0);
-            dev_check(vgmi_hmm_support(dev_, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
-                      "device HMM support: ");
-            const int64_t t_sup = since_begin();
-            // the windows on the run's threads
-            auto over_windows = [&](std::atomic<long long>& spent, const std::function<void(size_t)>& fn) {
-                std::atomic<size_t> nextw{0};
-                std::string herr;
-                std::mutex hmu;
-                auto body = [&]() {
-                    for (;;) {
-                        const size_t wi = nextw.fetch_add(1);
-                        if (wi >= nw) return;
-                        try {
-                            CpuBudget::Hold cpu;
-                            PhaseTimer tt(spent);
-                            fn(wi);
-                        } catch (const std::exception& e) {
-                            std::lock_guard<std::mutex> lock(hmu);
-                            if (herr.empty()) herr = e.what();
-                        }
-                    }
-                };
-                std::vector<std::thread> hs;
-                for (size_t h2 = 1; h2 < n_threads; ++h2) hs.emplace_back(body);
-                body();
-                for (auto& th : hs) th.join();
-                if (!herr.empty()) throw std::runtime_error(herr);
-            };
-            // 2. the draws; 3. what follows from them: the window's haplotypes and mask, its genotypes, the rows' reference-allele masks
-            std::vector<std::vector<uint16_t>> win_top(nw);
-            std::vector<std::vector<std::vector<uint16_t>>> win_gts(nw);
-            std::vector<uint8_t> win_used8(nw * n_used, 0);
-            std::vector<uint64_t> win_mask(nw, 0);
-            std::vector<uint16_t> gt0(n_rows ? n_rows : 1, 0);
-            over_windows(g_phase.select, [&](size_t wi) {
-                HaplotypeSampler sampler(std::vector<uint32_t>(support.begin() + wi * n_hap_, support.begin() + (wi + 1) * n_hap_), (int)r.haploid_num);
-                std::vector<uint16_t>& top = win_top[wi];
-                top = sampler.top;
-                std::sort(top.begin(), top.end());
-                if (top.size() != n_used) throw std::runtime_error("internal: a window drew another number of haplotypes");
-                for (size_t p2 = 0; p2 < n_used; ++p2) {
-                    win_used8[wi * n_used + p2] = (uint8_t)top[p2];
-                    win_mask[wi] |= 1ULL << top[p2];
-                }
-                win_gts[wi].resize(n_gt);
-                for (size_t gi = 0; gi < n_gt; ++gi) win_gts[wi][gi] = {top[pos_a[gi]], top[pos_b[gi]]};
-                const Chrom& chr = *tasks[wi].chr;
-                for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
-                    const auto& hap_gt = chr.nodes[row_node[rr]].gn->hap_gt;
-                    uint16_t m = 0;
-                    for (size_t p2 = 0; p2 < n_used; ++p2) m |= (uint16_t)((hap_gt[top[p2]] == 0) << p2);
-                    gt0[rr] = m;
-                }
-            });
-            const int64_t t_draw = since_begin();
-            size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0;
-            int64_t t_emit = t_draw, t_a = t_draw, t_rows = t_draw, t_b = t_draw, t_calls = t_draw;
-            std::vector<long double> prob(n_rows ? n_rows : 1);
-            std::vector<uint32_t> winner(n_rows ? n_rows : 1, 0xFFFFFFFFu);
-            std::vector<std::vector<uint32_t>> win_rows(nw);      // per window: the rows that have a score
-            size_t n_steps = 0;
-            if (n_rows) {
-                // 4. emission scores on the device, the prune included
-                std::vector<uint32_t> n_kept(n_rows);
-                std::vector<uint8_t> flags(n_rows);
-                struct PartHandle {
-                    vgmi_hmm_part* p = nullptr;
-                    ~PartHandle() { vgmi_hmm_part_free(p); }
-                } ph;
-                dev_check(vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, n_used, pos_a.data(), pos_b.data(), (uint32_t)nw, win_used8.data(), win_mask.data(),
-                                                    (uint32_t)g_.bitlen, ave, lower, upper, tab.data(), n_rows, e_begin.data(), e_count.data(), row_win.data(),
-                                                    gt0.data(), n_kept.data(), flags.data(), &ph.p),
-                          "device HMM emissions: ");
-                t_emit = since_begin();
-                // 5. the same prune on the host's lists, for exactly the nodes that lost k-mers; 6. the sequence checks of flagged rows
-                static const bool fix_on_device = !(getenv("VGH_HMM_FIX_DEVICE") && getenv("VGH_HMM_FIX_DEVICE")[0] == '0');
-                std::vector<std::vector<uint64_t>> host_rows(nw), fix_rows(nw);
-                std::vector<std::vector<long double>> host_obs(nw);
-                std::vector<std::vector<uint32_t>> fix_cnt(nw), fix_j(nw);
-                std::vector<std::vector<uint16_t>> fix_mask(nw);
-                std::atomic<size_t> pruned_nodes{0};
-                over_windows(g_phase.pass_a, [&](size_t wi) {
-                    Chrom& chr = *tasks[wi].chr;
-                    const std::vector<uint16_t>& top = win_top[wi];
-                    std::vector<uint32_t> kept;
-                    ScoreCtx sctx;
-                    sctx.ave = ave;
-                    sctx.score_up = upper;
-                    NodeStates st;
-                    GenotypeList glist;
-                    for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
-                        Node& node = chr.nodes[row_node[rr]];
-                        if (n_kept[rr] != node.kmers.size()) {
-                            kept.clear();
-                            for (uint32_t pos : node.kmers)
-                                if ((r.packed[pos] >> 16) & win_mask[wi]) kept.push_back(pos);
-                            if (kept.size() != n_kept[rr]) throw std::runtime_error("internal: the device's k-mer lists differ from the host's");
-                            node.kmers.keep(kept);
-                            ++pruned_nodes;
-                        }
-                        if (!(flags[rr] & 1u)) continue;
-                        if (fix_on_device) {
-                            PhaseTimer tt(g_phase.states);
-                            const size_t before = fix_j[wi].size();
-                            sequence_fixes(chr, row_node[rr], top, gt0[rr], lower, upper, r, fix_j[wi], fix_mask[wi]);
-                            // (sequence_fixes counts along the list; the device along the row's range)
-                            for (size_t q = before; q < fix_j[wi].size(); ++q) fix_j[wi][q] = node.kmers[fix_j[wi][q]] - (uint32_t)e_begin[rr];
-                            if (fix_j[wi].size() != before) {
-                                fix_rows[wi].push_back(rr);
-                                fix_cnt[wi].push_back((uint32_t)(fix_j[wi].size() - before));
-                            }
-                        } else {
-                            if (glist.off.empty()) {
-                                glist.off.assign(n_gt + 1, 0);
-                                for (size_t gi = 0; gi < n_gt; ++gi) {
-                                    glist.flat.insert(glist.flat.end(), win_gts[wi][gi].begin(), win_gts[wi][gi].end());
-                                    glist.off[gi + 1] = (uint32_t)glist.flat.size();
-                                }
-                                glist.pos_a = pos_a;
-                                glist.pos_b = pos_b;
-                            }
-                            {
-                                PhaseTimer tt(g_phase.states);
-                                st = hidden_states(chr, row_node[rr], top, win_gts[wi], top, glist, lower, upper, true, r, std::move(st), nullptr);
-                            }
-                            PhaseTimer tt(g_phase.emit);
-                            const std::vector<long double> obs = score_states(st, sctx);
-                            if (!obs.empty()) {
-                                host_rows[wi].push_back(rr);
-                                host_obs[wi].insert(host_obs[wi].end(), obs.begin(), obs.end());
-                            }
-                        }
-                    }
-                });
-                n_pruned = pruned_nodes.load();
-                if (n_pruned) lists_whole_.store(false, std::memory_order_relaxed);
-                alive_stale_.store(false);      // (hidden_states above walked lists that were pruned already: nothing left them)
-                t_a = since_begin();
-                {
-                    std::vector<uint64_t> all_rows, f_rows;
-                    std::vector<long double> all_obs;
-                    std::vector<uint32_t> f_off(1, 0), f_j;
-                    std::vector<uint16_t> f_m;
-                    for (size_t wi = 0; wi < nw; ++wi) {
-                        all_rows.insert(all_rows.end(), host_rows[wi].begin(), host_rows[wi].end());
-                        all_obs.insert(all_obs.end(), host_obs[wi].begin(), host_obs[wi].end());
-                        f_rows.insert(f_rows.end(), fix_rows[wi].begin(), fix_rows[wi].end());
-                        for (uint32_t cnt2 : fix_cnt[wi]) f_off.push_back(f_off.back() + cnt2);
-                        f_j.insert(f_j.end(), fix_j[wi].begin(), fix_j[wi].end());
-                        f_m.insert(f_m.end(), fix_mask[wi].begin(), fix_mask[wi].end());
-                    }
-                    n_host_rows = all_rows.size();
-                    n_fixed_rows = f_rows.size();
-                    if (!all_rows.empty()) dev_check(vgmi_hmm_part_set_rows(ph.p, all_rows.size(), all_rows.data(), all_obs.data()), "device HMM emissions: ");
-                    if (!f_rows.empty())
-                        dev_check(vgmi_hmm_part_fix_rows(ph.p, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
-                }
-                t_rows = since_begin();
-                // 7. the recursion's inputs: genotype strings (the window's haplotypes decide them), step tables (libm), chains
-                const uint32_t stride = 3;
-                struct Seen { uint32_t start, end; int64_t row; };
-                std::vector<std::vector<Seen>> seen(nw);
-                std::vector<uint8_t> gid(n_rows * n_gt, 0), order(n_rows * n_gt, 0);
-                over_windows(g_phase.pass_a, [&](size_t wi) {
-                    Chrom& chr = *tasks[wi].chr;
-                    std::unordered_map<uint32_t, uint32_t> gs_memo;      // reference-allele mask of a two-allele node -> a row that holds the pattern
-                    for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
-                        Node& n = chr.nodes[row_node[rr]];
-                        const uint32_t n_start = n.start, n_end = (uint32_t)(n_start + n.gn->seqs[0].size() - 1);
-                        if (n_kept[rr] == 0) {
-                            seen[wi].push_back(Seen{n_start, n_end, -1});
-                            continue;
-                        }
-                        seen[wi].push_back(Seen{n_start, n_end, (int64_t)rr});
-                        bool biallelic = true;
-                        for (uint16_t hap : win_top[wi]) biallelic = biallelic && n.gn->hap_gt[hap] <= 1;
-                        auto it = biallelic ? gs_memo.find(gt0[rr]) : gs_memo.end();
-                        if (it != gs_memo.end()) {
-                            std::memcpy(gid.data() + rr * n_gt, gid.data() + (size_t)it->second * n_gt, n_gt);
-                            std::memcpy(order.data() + rr * n_gt, order.data() + (size_t)it->second * n_gt, n_gt);
-                        } else {
-                            (void)genotype_strings(n, win_gts[wi], gid.data() + rr * n_gt, order.data() + rr * n_gt);     // <= 128 strings: always fits
-                            if (biallelic) gs_memo.emplace(gt0[rr], (uint32_t)rr);
-                        }
-                        win_rows[wi].push_back((uint32_t)rr);
-                    }
-                });
-                std::vector<size_t> win_step0(nw + 1, 0);
-                for (size_t wi = 0; wi < nw; ++wi) win_step0[wi + 1] = win_step0[wi] + 2 * win_rows[wi].size();
-                n_steps = win_step0[nw];
-                if (n_steps) {
-                    std::vector<long double> pw(n_steps * 2 * stride);
-                    std::vector<uint32_t> row(n_steps, 0);
-                    std::vector<uint8_t> restart(n_steps, 0);
-                    std::vector<uint64_t> fwd(n_rows, 0), bwd(n_rows, 0);
-                    std::vector<vgmi_hmm_chain> chains;
-                    for (size_t wi = 0; wi < nw; ++wi) {
-                        const size_t m = win_rows[wi].size();
-                        if (!m) continue;
-                        chains.push_back(vgmi_hmm_chain{win_step0[wi], m, 0, 0});
-                        chains.push_back(vgmi_hmm_chain{win_step0[wi] + m, m, 0, 0});
-                    }
-                    over_windows(g_phase.pass_b, [&](size_t wi) {
-                        const size_t m = win_rows[wi].size();
-                        if (!m) return;
-                        const size_t step0 = win_step0[wi];
-                        constexpr uint32_t kMemo = 4096;      // the tables of powers are a function of the distance alone
-                        std::vector<long double> memo((size_t)kMemo * 2 * stride);
-                        std::vector<uint8_t> memo_have(kMemo, 0);
-                        auto powers = [&](long double* dst, uint32_t distance) {
-                            if (distance < kMemo && memo_have[distance]) {
-                                std::memcpy(dst, &memo[(size_t)distance * 2 * stride], 2 * stride * sizeof(long double));
-                                return;
-                            }
-                            long double recomb, no_recomb;
-                            std::tie(recomb, no_recomb) = transition_probabilities(distance, (uint16_t)n_hap_);
-                            for (uint32_t k = 0; k < stride; ++k) {
-                                dst[k] = std::pow(no_recomb, (int32_t)k);
-                                dst[stride + k] = std::pow(recomb, (int32_t)k);
-                            }
-                            if (distance < kMemo) {
-                                std::memcpy(&memo[(size_t)distance * 2 * stride], dst, 2 * stride * sizeof(long double));
-                                memo_have[distance] = 1;
-                            }
-                        };
-                        const std::vector<Seen>& sn = seen[wi];
-                        size_t j = 0;
-                        for (size_t q = 0; q < sn.size(); ++q) {
-                            if (sn[q].row < 0) continue;
-                            const size_t fs = step0 + j, bs = step0 + m + (m - 1 - j);
-                            powers(pw.data() + fs * 2 * stride, sn[q].start - (q ? sn[q - 1].end : 0u));
-                            restart[fs] = (q == 0 || sn[q - 1].row < 0) ? 1 : 0;
-                            row[fs] = (uint32_t)sn[q].row;
-                            powers(pw.data() + bs * 2 * stride, (q + 1 < sn.size() ? sn[q + 1].start : 0u) - sn[q].end);
-                            restart[bs] = (q + 1 == sn.size() || sn[q + 1].row < 0) ? 1 : 0;
-                            row[bs] = (uint32_t)sn[q].row;
-                            fwd[sn[q].row] = fs;
-                            bwd[sn[q].row] = bs;
-                            ++j;
-                        }
-                    });
-                    t_b = since_begin();
-                    const long double uniform = 1.0L / (long double)n_gt;
-                    dev_check(vgmi_hmm_part_calls(ph.p, 2, keep_mat.data(), 1, row.data(), restart.data(), pw.data(), n_steps, &uniform, chains.data(),
-                                                  (uint32_t)chains.size(), gid.data(), order.data(), fwd.data(), bwd.data(), prob.data(), winner.data()),
-                              "device HMM recursion: ");
-                } else {
-                    t_b = since_begin();
-                }
-                t_calls = since_begin();
-            }
-            for (int64_t v = dev_first.load(); ta < v && !dev_first.compare_exchange_weak(v, ta);) {}
-            for (int64_t v = dev_last.load(); t_calls > v && !dev_last.compare_exchange_weak(v, t_calls);) {}
-            // 8. the calls' tallies on the device (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists)
-            std::vector<uint32_t> tally;
-            std::vector<uint8_t> tally_uniq;
-            static const bool device_tallies = !(getenv("VGH_DEVICE_TALLIES") && getenv("VGH_DEVICE_TALLIES")[0] == '0');
-            if (device_tallies && n_steps) {
-                tally.resize(4 * n_rows);
-                tally_uniq.resize(n_rows);
-                dev_check(vgmi_hmm_tallies_select(dev_, n_rows, e_begin.data(), e_count.data(), row_win.data(), winner.data(), (uint32_t)n_gt, pos_a.data(),
-                                                  pos_b.data(), n_used, (uint32_t)nw, win_used8.data(), tally.data(), tally_uniq.data()),
-                          "device tallies: ");
-            }
-            // 9. the lines
-            over_windows(g_phase.pass_c, [&](size_t wi) {
-                emit_windows_done += !win_rows[wi].empty();
-                const Chrom& chr = *tasks[wi].chr;
-                if (tally.empty()) {
-                    WindowWork w;
-                    w.chr = tasks[wi].chr;
-                    w.n_gt = n_gt;
-                    w.genotypes = win_gts[wi];
-                    w.top = win_top[wi];
-                    std::vector<long double> pr(win_rows[wi].size());
-                    std::vector<uint32_t> wn(win_rows[wi].size());
-                    for (size_t q = 0; q < win_rows[wi].size(); ++q) {
-                        w.nodes.push_back(row_node[win_rows[wi][q]]);
-                        pr[q] = prob[win_rows[wi][q]];
-                        wn[q] = winner[win_rows[wi][q]];
-                    }
-                    window_finish(w, pr.data(), wn.data(), r);
-                    make_piece(wi);
-                    return;
-                }
-                // written straight from what came back: the called pair, the posterior, the tallies (make_piece's lines)
-                piece_done[wi] = 1;
-                auto vc = g_.vcf_info.find(chr.name);
-                if (vc == g_.vcf_info.end()) return;
-                const auto& sites = vc->second;
-                auto site = win_rows[wi].empty() ? sites.end() : sites.lower_bound(chr.nodes[row_node[win_rows[wi][0]]].start);
-                std::string out;
-                for (const uint32_t rw : win_rows[wi]) {
-                    const Node& node = chr.nodes[row_node[rw]];
-                    while (site != sites.end() && site->first < node.start) ++site;
-                    if (winner[rw] >= n_gt) continue;            // no entry with a positive posterior: no call
-                    if (site == sites.end() || site->first != node.start) continue;
-                    const uint64_t ga = node.gn->hap_gt[win_top[wi][pos_a[winner[rw]]]], gb = node.gn->hap_gt[win_top[wi][pos_b[winner[rw]]]];
-                    if (ga == 0 && gb == 0) continue;
-                    const auto& fields = site->second;
-                    for (size_t i = 0; i < 9; i++) {
-                        if (i == 0) out += fields[i];
-                        else if (i == 6) out += "\tPASS";
-                        else if (i < 8) { out += '\t'; out += fields[i]; }
-                        else out += "\tGT:GQ:GPP:NAK:CAK:UK";
-                    }
-                    out += '\t';
-                    const long double pr = prob[rw];
-                    const float gq = phred_scaled(pr);
-                    if (gq < cfg.min_gq) out += "./.";
-                    else {
-                        append_uint(out, ga);
-                        out += '/';
-                        append_uint(out, gb);
-                    }
-                    out += ':';
-                    append_fixed1(out, gq);
-                    out += ':';
-                    append_fixed1(out, pr);
-                    out += ':';
-                    const uint32_t* tl = &tally[4 * rw];
-                    append_uint(out, tl[0]);
-                    out += ',';
-                    append_uint(out, tl[2]);
-                    out += ':';
-                    append_fixed1(out, tl[0] ? static_cast<float>((uint64_t)tl[1]) / (float)(uint64_t)tl[0] : 0.0f);
-                    out += ',';
-                    append_fixed1(out, tl[2] ? static_cast<float>((uint64_t)tl[3]) / (float)(uint64_t)tl[2] : 0.0f);
-                    out += ':';
-                    append_uint(out, tally_uniq[rw]);
-                    out += '\n';
-                }
-                pieces[wi] = std::move(out);
-            });
-            emitted_on_device = true;
-            if (g_phase_on) {
-                std::fprintf(stderr, "[varigraph-mi] HMM with haplotypes selected per window (%zu windows, %zu rows, %zu nodes pruned, %zu nodes scored by the host, %zu scored "
-                             "again on the device): support %.3f, draws (host) %.3f, emission kernel %.3f, prune + sequence checks (host) %.3f, rows fixed on the device %.3f, "
-                             "strings + step tables (host) %.3f, recursion + posterior %.3f\n",
-                             nw, n_rows, n_pruned, n_host_rows, n_fixed_rows, (t_sup - ta) * 1e-9, (t_draw - t_sup) * 1e-9, (t_emit - t_draw) * 1e-9, (t_a - t_emit) * 1e-9,
-                             (t_rows - t_a) * 1e-9, (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
-                std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: 1 parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
-                             since_begin() * 1e-9 - tb0, nw, tasks.size());
-            }
-        }
-    }
-    if (!emitted_on_device) {
     std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back(worker);
+    for (uint32_t t = 1; t < s.n_threads; ++t) pool.emplace_back(worker);
     worker();
     for (auto& th : pool) th.join();
     for (auto& th : part_threads)
         if (th.joinable()) th.join();
     if (failed.load()) throw std::runtime_error(error);
+}
+
+// ---------------------------------------------------------------- emissions on the device: what both paths do per row and per window
+struct Genotyper::WindowHaps {
+    const std::vector<uint16_t>& top;       // the selected haplotypes, ascending
+    const std::vector<uint16_t>& used;      // those occurring in the genotypes, ascending
+    const std::vector<std::vector<uint16_t>>& genotypes;
+    const GenotypeList& glist;
+};
+
+// Rows the emission kernel flagged hold a multi-copy, under-covered, carried k-mer: the reference consults the haplotype's sequence
+// (:760-800).  The strings are the host's; the row's products stay on the device, scored again (vgmi_hmm_part_fix_rows) with the
+// haplotypes the sequences rule out taken off the entries concerned.  VGH_HMM_FIX_DEVICE=0: such a row is scored by the host (hidden
+// states, products in x87 arithmetic) and handed in (vgmi_hmm_part_set_rows).  Collected per window, by the window's thread.
+struct Genotyper::FlaggedRows {
+    std::vector<std::vector<uint64_t>> host_rows, fix_rows;
+    std::vector<std::vector<long double>> host_obs;
+    std::vector<std::vector<uint32_t>> fix_cnt, fix_j;      // fix_j: the entries, counted along the node's list
+    std::vector<std::vector<uint16_t>> fix_mask;
+    size_t n_host = 0, n_fixed = 0;      // rows handed over by upload_flagged
+    explicit FlaggedRows(size_t nw) : host_rows(nw), fix_rows(nw), host_obs(nw), fix_cnt(nw), fix_j(nw), fix_mask(nw) {}
+};
+
+struct Genotyper::FlaggedScratch {      // of one window's thread
+    ScoreCtx sctx;
+    NodeStates st;
+    double lower, upper;
+    FlaggedScratch(float ave, double lo, double up) : lower(lo), upper(up)
+    {
+        sctx.ave = ave;
+        sctx.score_up = up;
     }
-    last_device_seconds = dev_last.load() > 0 ? (double)(dev_last.load() - dev_first.load()) * 1e-9 : 0;
-    last_windows = tasks.size();
-    last_device_windows = emitted_on_device ? emit_windows_done.load() : 0;
+};
+
+void Genotyper::flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint16_t gt0, const Run& r,
+                            FlaggedScratch& sc, uint32_t& n_kept)
+{
+    static const bool fix_on_device = !knob_off("VGH_HMM_FIX_DEVICE");
+    if (fix_on_device) {
+        PhaseTimer tt(g_phase.states);
+        const size_t before = fl.fix_j[wi].size();
+        sequence_fixes(chr, node_i, h.used, gt0, sc.lower, sc.upper, r, fl.fix_j[wi], fl.fix_mask[wi]);
+        if (fl.fix_j[wi].size() != before) {
+            fl.fix_rows[wi].push_back(rr);
+            fl.fix_cnt[wi].push_back((uint32_t)(fl.fix_j[wi].size() - before));
+        }
+        return;
+    }
+    {
+        PhaseTimer tt(g_phase.states);
+        sc.st = hidden_states(chr, node_i, h.top, h.genotypes, h.used, h.glist, sc.lower, sc.upper, true, r, std::move(sc.st), nullptr);
+    }
+    PhaseTimer tt(g_phase.emit);
+    const std::vector<long double> obs = score_states(sc.st, sc.sctx);
+    n_kept = (uint32_t)(obs.empty() ? 0 : sc.st.c.size());
+    if (!obs.empty()) {
+        fl.host_rows[wi].push_back(rr);
+        fl.host_obs[wi].insert(fl.host_obs[wi].end(), obs.begin(), obs.end());
+    }
+}
+
+void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part)
+{
+    std::vector<uint64_t> all_rows, f_rows;
+    std::vector<long double> all_obs;
+    std::vector<uint32_t> f_off(1, 0), f_j;
+    std::vector<uint16_t> f_m;
+    for (size_t wi = 0; wi < fl.host_rows.size(); ++wi) {
+        all_rows.insert(all_rows.end(), fl.host_rows[wi].begin(), fl.host_rows[wi].end());
+        all_obs.insert(all_obs.end(), fl.host_obs[wi].begin(), fl.host_obs[wi].end());
+        std::vector<long double>().swap(fl.host_obs[wi]);
+        f_rows.insert(f_rows.end(), fl.fix_rows[wi].begin(), fl.fix_rows[wi].end());
+        for (uint32_t cnt : fl.fix_cnt[wi]) f_off.push_back(f_off.back() + cnt);
+        f_j.insert(f_j.end(), fl.fix_j[wi].begin(), fl.fix_j[wi].end());
+        f_m.insert(f_m.end(), fl.fix_mask[wi].begin(), fl.fix_mask[wi].end());
+    }
+    fl.n_host = all_rows.size();
+    fl.n_fixed = f_rows.size();
+    if (!all_rows.empty()) device_check(dev_, vgmi_hmm_part_set_rows(part, all_rows.size(), all_rows.data(), all_obs.data()), "device HMM emissions: ");
+    if (!f_rows.empty()) device_check(dev_, vgmi_hmm_part_fix_rows(part, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
+}
+
+// The rows [row_lo, row_hi) of a window: every node as the chains see it (`seen`), and for the rows that have a score (n_kept) the
+// genotype strings of their entries (gid / order: n_gt bytes per row).  The genotype strings of a node with two alleles depend on which
+// haplotypes carry the reference allele only: one evaluation per distinct mask (the strings themselves as genotype_strings builds them).
+void Genotyper::row_strings(const Chrom& chr, size_t row_lo, size_t row_hi, const uint32_t* row_node, const uint16_t* gt0, const uint32_t* n_kept,
+                            const WindowHaps& h, uint8_t* gid, uint8_t* order, std::vector<Seen>& seen, std::vector<uint32_t>& scored_rows) const
+{
+    const size_t n_gt = h.genotypes.size();
+    std::unordered_map<uint32_t, uint32_t> gs_memo;      // mask -> a row that holds the pattern
+    for (size_t rr = row_lo; rr < row_hi; ++rr) {
+        const Node& n = chr.nodes[row_node[rr]];
+        const uint32_t n_start = n.start, n_end = (uint32_t)(n_start + n.gn->seqs[0].size() - 1);
+        if (n_kept[rr] == 0) {
+            seen.push_back(Seen{n_start, n_end, -1});
+            continue;
+        }
+        seen.push_back(Seen{n_start, n_end, (int64_t)rr});
+        bool biallelic = true;
+        for (uint16_t hap : h.used) biallelic = biallelic && n.gn->hap_gt[hap] <= 1;
+        auto it = biallelic ? gs_memo.find(gt0[rr]) : gs_memo.end();
+        if (it != gs_memo.end()) {
+            std::memcpy(gid + rr * n_gt, gid + (size_t)it->second * n_gt, n_gt);
+            std::memcpy(order + rr * n_gt, order + (size_t)it->second * n_gt, n_gt);
+        } else {
+            (void)genotype_strings(n, h.genotypes, gid + rr * n_gt, order + rr * n_gt);     // <= 128 strings: always fits
+            if (biallelic) gs_memo.emplace(gt0[rr], (uint32_t)rr);
+        }
+        scored_rows.push_back((uint32_t)rr);
+    }
+}
+
+// The step tables of a part's windows end to end (two chains per window with a scored row), as the device call takes them
+struct Genotyper::StepArrays {
+    std::vector<size_t> win_step0;
+    size_t n_steps = 0;
+    uint32_t stride;
+    std::vector<long double> pw;
+    std::vector<uint32_t> row;
+    std::vector<uint8_t> restart;
+    std::vector<uint64_t> fwd, bwd;
+    std::vector<vgmi_hmm_chain> chains;
+
+    StepArrays(const std::vector<std::vector<uint32_t>>& win_rows, size_t n_rows, uint32_t ploidy) : win_step0(win_rows.size() + 1, 0), stride(ploidy + 1)
+    {
+        for (size_t wi = 0; wi < win_rows.size(); ++wi) win_step0[wi + 1] = win_step0[wi] + 2 * win_rows[wi].size();
+        n_steps = win_step0.back();
+        if (!n_steps) return;
+        pw.resize(n_steps * 2 * stride);
+        row.assign(n_steps, 0);
+        restart.assign(n_steps, 0);
+        fwd.assign(n_rows, 0);
+        bwd.assign(n_rows, 0);
+        for (size_t wi = 0; wi < win_rows.size(); ++wi) {
+            const size_t m = win_rows[wi].size();
+            if (!m) continue;
+            chains.push_back(vgmi_hmm_chain{win_step0[wi], m, 0, 0});
+            chains.push_back(vgmi_hmm_chain{win_step0[wi] + m, m, 0, 0});
+        }
+    }
+    void fill(size_t wi, const std::vector<Seen>& seen, uint16_t population)      // (libm: a window per thread)
+    {
+        const size_t s0 = win_step0[wi];
+        step_tables(seen, stride, population, s0, 0, pw.data() + s0 * 2 * stride, row.data() + s0, restart.data() + s0, fwd.data(), bwd.data());
+    }
+};
+
+// the calls of a window's scored rows into its nodes' records, for the lines that are written from those (no tallies from the device)
+void Genotyper::finish_rows(Chrom* chr, const std::vector<uint32_t>& rows, const uint32_t* row_node, const WindowHaps& h, const long double* prob,
+                            const uint32_t* winner, const Run& r)
+{
+    WindowWork w;
+    w.chr = chr;
+    w.n_gt = h.genotypes.size();
+    w.genotypes = h.genotypes;
+    w.top = h.top;
+    std::vector<long double> pr(rows.size());
+    std::vector<uint32_t> wn(rows.size());
+    for (size_t q = 0; q < rows.size(); ++q) {
+        w.nodes.push_back(row_node[rows[q]]);
+        pr[q] = prob[rows[q]];
+        wn[q] = winner[rows[q]];
+    }
+    window_finish(w, pr.data(), wn.data(), r);
+}
+
+// ---------------------------------------------------------------- emissions on the device, whole panel
+// Emission scores on the device too (vgmi_hmm_emissions): a sample over a graph all of whose haplotypes are selected (-n >= haplotypes:
+// one genotype list for every window, no k-mer list is ever pruned).  Per part of the windows: the host lists the nodes' entry ranges,
+// the device scores them from the node-ordered coverage it was handed, the host sees to the few nodes whose haplotype sequences must
+// be consulted, builds the step tables (libm) and the genotype strings, the device runs recursion and posterior on the scores where
+// they lie.
+struct Genotyper::PanelSample {
+    float ave = 0;
+    double lower = 256.0f, upper = -0.1f;
+    std::vector<uint16_t> top, used;      // one genotype list for the whole sample
+    std::vector<std::vector<uint16_t>> genotypes;
+    GenotypeList glist;
+    std::vector<uint8_t> used8, pos_all;      // pos_all: per genotype its haplotypes' places in `used`
+    std::vector<uint8_t> keep_mat;
+    uint64_t top_mask = 0;
+    std::vector<long double> tab;
+    size_t per_part = 1, n_parts = 0;
+    std::string cache_key;
+    std::atomic<bool> broken{false};      // a pruned list after all: the host path
+    WindowHaps haps() const { return WindowHaps{top, used, genotypes, glist}; }
+};
+
+Genotyper::Emitted Genotyper::hmm_whole_panel(RunShared& s)
+{
+    const Run& r = s.r;
+    const GenotypeConfig& cfg = *r.cfg;
+    const double tb0 = s.since_begin() * 1e-9;
+    PanelSample ps;
+    ps.ave = r.hap_cov;
+    poisson_interval(ps.ave, ps.lower, ps.upper);
+    for (const auto& kv : g_.hap_names) ps.top.push_back(kv.first);
+    std::sort(ps.top.begin(), ps.top.end());
+    ps.genotypes = haplotype_combinations(ps.top, cfg.sample_type, cfg.sample_ploidy, (uint16_t)(n_hap_ - 1));
+    const size_t n_gt = ps.genotypes.size();
+    for (const auto& gtv : ps.genotypes) ps.used.insert(ps.used.end(), gtv.begin(), gtv.end());
+    std::sort(ps.used.begin(), ps.used.end());
+    ps.used.erase(std::unique(ps.used.begin(), ps.used.end()), ps.used.end());
+    bool full = true;      // (every genotype holds `ploidy` haplotypes: pairs for a diploid sample)
+    for (const auto& gtv : ps.genotypes) full = full && gtv.size() == cfg.sample_ploidy;
+    if (!(full && n_gt >= 1 && n_gt <= 128 && ps.used.size() <= 16)) return Emitted::no;
+    ps.glist = genotype_list(ps.genotypes, ps.used);
+    std::vector<uint8_t> where(n_hap_ + 1, 0);
+    ps.used8.resize(ps.used.size());
+    for (size_t p = 0; p < ps.used.size(); ++p) {
+        where[ps.used[p]] = (uint8_t)p;
+        ps.used8[p] = (uint8_t)ps.used[p];
+    }
+    ps.pos_all.resize(n_gt * cfg.sample_ploidy);
+    for (size_t gi = 0; gi < n_gt; ++gi)
+        for (uint32_t q = 0; q < cfg.sample_ploidy; ++q) ps.pos_all[gi * cfg.sample_ploidy + q] = where[ps.genotypes[gi][q]];
+    ps.keep_mat = keep_matrix(ps.genotypes);
+    for (uint16_t hap : ps.top) ps.top_mask |= 1ULL << hap;
+    ps.tab = emission_table(ps.ave, cfg.sample_ploidy);
+    if (!entries_uploaded_) {
+        device_check(dev_, vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
+        entries_uploaded_ = true;
+    }
+    device_check(dev_, vgmi_hmm_sample_upload(dev_, r.cov, g_.node_key_index.size()), "device HMM emissions: ");
+    const size_t max_parts = std::min<size_t>(4, dev_parts_);
+    ps.per_part = std::max<size_t>(1, (s.tasks.size() + max_parts - 1) / max_parts);
+    ps.n_parts = (s.tasks.size() + ps.per_part - 1) / ps.per_part;
+    ps.cache_key = std::to_string(s.tasks.size()) + "/" + std::to_string(ps.per_part) + "/" + std::to_string(cfg.sv_only) + "/" +
+                   std::to_string(cfg.sample_ploidy) + "/" + cfg.sample_type + "/" + std::to_string(n_gt) + "/" + std::to_string(r.haploid_num) + "/" +
+                   std::to_string(cfg.chr_len_thread);
+    // What a part's device calls need beyond a sample's coverage is a function of the graph and the options: the rows (entry
+    // ranges, reference-allele masks), and the PLAN -- genotype strings, which rows have a score, the step tables (libm), chains,
+    // all of it resident on the device (vgmi_hmm_plan).  Made by the first sample that gets there, kept with the graph, shared
+    // by every Genotyper of the run (eight consumers of one device would otherwise build eight of everything).
+    int dev_id = 0;
+    (void)vgmi_device_of(dev_, &dev_id);
+    if (emit_cache_.size() != ps.n_parts) {
+        emit_cache_.clear();
+        emit_cache_.resize(ps.n_parts);
+    }
+    for (size_t part = 0; part < ps.n_parts; ++part) {
+        const std::string slot = "emit/" + std::to_string(dev_id) + "/" + std::to_string(ps.n_parts) + "/" + std::to_string(part) + "/" + ps.cache_key;
+        std::lock_guard<std::mutex> lock(g_.shared_mu);
+        auto it = g_.shared_slots.find(slot);
+        if (it == g_.shared_slots.end()) it = g_.shared_slots.emplace(slot, std::static_pointer_cast<void>(std::make_shared<EmitPartCache>())).first;
+        emit_cache_[part] = std::static_pointer_cast<EmitPartCache>(it->second);
+    }
+    std::mutex err_mu;
+    std::string err_text;
+    auto part_fn = [&](size_t part) {
+        try {
+            panel_part(s, ps, part);
+        } catch (const std::exception& e) {
+            std::lock_guard<std::mutex> lock(err_mu);
+            if (err_text.empty()) err_text = e.what();
+        }
+    };
+    std::vector<std::thread> pthreads;
+    for (size_t p = 1; p < ps.n_parts; ++p) pthreads.emplace_back(part_fn, p);
+    if (ps.n_parts) part_fn(0);
+    for (auto& th : pthreads) th.join();
+    if (!err_text.empty()) throw std::runtime_error(err_text);
+    if (ps.broken.load()) return Emitted::lists_pruned;
+    if (g_phase_on) std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s\n", ps.n_parts, s.since_begin() * 1e-9 - tb0);
+    return Emitted::yes;
+}
+
+// the rows of a part: every node the HMM works on, window after window (the same for every sample and every Genotyper: listed once).
+// false: a node's list is not whole
+bool Genotyper::panel_rows(RunShared& s, const PanelSample& ps, EmitPartCache& pc, size_t t0, size_t t1)
+{
+    std::lock_guard<std::mutex> lock(pc.mu);
+    if (pc.key == ps.cache_key) return true;
+    CpuBudget::Hold cpu;
+    PhaseTimer t_list(g_phase.list);
+    pc.e_begin.clear(); pc.e_count.clear(); pc.row_node.clear(); pc.gt0.clear();
+    pc.plan.reset();
+    pc.win_row0.assign(t1 - t0 + 1, 0);
+    for (size_t t = t0; t < t1; ++t) {
+        const Chrom& chr = *s.tasks[t].chr;
+        const SiteMap& sites = vcf_sites(chr);
+        for (uint32_t i = s.tasks[t].first; i < s.tasks[t].last; ++i) {
+            const Node& n = chr.nodes[i];
+            if (skipped(chr, sites, n, s.r.cfg->sv_only)) continue;
+            if (!n.kmers.empty() && (size_t)(n.kmers.back() - n.kmers.front()) + 1 != n.kmers.size()) return false;
+            pc.e_begin.push_back(n.kmers.empty() ? 0 : n.kmers.front());
+            pc.e_count.push_back((uint32_t)n.kmers.size());
+            uint16_t m = 0;
+            for (size_t p = 0; p < ps.used.size(); ++p) m |= (uint16_t)((n.gn->hap_gt[ps.used[p]] == 0) << p);
+            pc.gt0.push_back(m);
+            pc.row_node.push_back(i);
+        }
+        pc.win_row0[t - t0 + 1] = pc.e_begin.size();
+    }
+    pc.key = ps.cache_key;
+    return true;
+}
+
+// The plan of a part, for the rows that have a score -- the same for every sample of this path (a row's kept k-mers are those some
+// haplotype carries, and every haplotype is selected); held against the pattern all the same.  Made under the part's lock.
+std::shared_ptr<Genotyper::EmitPartPlan> Genotyper::panel_plan(RunShared& s, const PanelSample& ps, EmitPartCache& pc, size_t t0, size_t nw, size_t helpers,
+                                                               const std::vector<uint32_t>& n_kept)
+{
+    const size_t n_rows = pc.e_begin.size(), n_gt = ps.genotypes.size();
+    const std::vector<size_t>& win_row0 = pc.win_row0;
+    std::vector<uint8_t> scored(n_rows);
+    for (size_t rr = 0; rr < n_rows; ++rr) scored[rr] = n_kept[rr] != 0;
+    std::lock_guard<std::mutex> lock(pc.mu);
+    if (pc.plan && pc.plan->scored == scored) return pc.plan;
+    auto np = std::make_shared<EmitPartPlan>();
+    np->scored = scored;
+    np->win_rows.resize(nw);
+    std::vector<std::vector<Seen>> seen(nw);
+    std::vector<uint8_t> gid(n_rows * n_gt, 0), order(n_rows * n_gt, 0);
+    const WindowHaps haps = ps.haps();
+    over_windows(nw, helpers, g_phase.pass_a, [&](size_t wi) {
+        row_strings(*s.tasks[t0 + wi].chr, win_row0[wi], win_row0[wi + 1], pc.row_node.data(), pc.gt0.data(), n_kept.data(), haps, gid.data(), order.data(), seen[wi],
+                    np->win_rows[wi]);
+    });
+    // the lines' shared heads, window by window
+    std::vector<std::string> heads(nw);
+    std::vector<std::vector<uint32_t>> head_len(nw);
+    over_windows(nw, helpers, g_phase.pass_a, [&](size_t wi) {
+        const Chrom& chr = *s.tasks[t0 + wi].chr;
+        auto vc = g_.vcf_info.find(chr.name);
+        head_len[wi].assign(win_row0[wi + 1] - win_row0[wi], 0);
+        if (vc == g_.vcf_info.end()) return;
+        SiteWalk walk(vc->second);
+        for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+            const size_t before = heads[wi].size();
+            if (append_site_head(heads[wi], walk.at(chr.nodes[pc.row_node[rr]].start))) head_len[wi][rr - win_row0[wi]] = (uint32_t)(heads[wi].size() - before);
+        }
+    });
+    np->line_head_off.assign(n_rows + 1, 0);
+    size_t total = 0;
+    for (size_t wi = 0; wi < nw; ++wi) total += heads[wi].size();
+    np->line_head.reserve(total);
+    for (size_t wi = 0; wi < nw; ++wi) {
+        for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) np->line_head_off[rr + 1] = np->line_head_off[rr] + head_len[wi][rr - win_row0[wi]];
+        np->line_head += heads[wi];
+        std::string().swap(heads[wi]);
+    }
+    StepArrays steps(np->win_rows, n_rows, s.r.cfg->sample_ploidy);
+    np->n_steps = steps.n_steps;
+    if (steps.n_steps) {
+        over_windows(nw, helpers, g_phase.pass_b, [&](size_t wi) { steps.fill(wi, seen[wi], (uint16_t)n_hap_); });
+        const long double uniform = 1.0L / (long double)n_gt;
+        device_check(dev_, vgmi_hmm_plan_create(dev_, (uint32_t)n_gt, s.r.cfg->sample_ploidy, ps.keep_mat.data(), 1, n_rows, steps.row.data(), steps.restart.data(),
+                                                steps.pw.data(), steps.n_steps, &uniform, steps.chains.data(), (uint32_t)steps.chains.size(), gid.data(),
+                                                order.data(), steps.fwd.data(), steps.bwd.data(), &np->plan),
+                     "device HMM plan: ");
+    }
+    pc.plan = np;
+    return np;
+}
+
+void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
+{
+    const Run& r = s.r;
+    const GenotypeConfig& cfg = *r.cfg;
+    const size_t t0 = part * ps.per_part, t1 = std::min(s.tasks.size(), t0 + ps.per_part), nw = t1 - t0;
+    const size_t n_gt = ps.genotypes.size();
+    EmitPartCache& pc = *emit_cache_[part];
+    if (!panel_rows(s, ps, pc, t0, t1)) {
+        ps.broken = true;
+        return;
+    }
+    const std::vector<size_t>& win_row0 = pc.win_row0;
+    const size_t n_rows = pc.e_begin.size();
+    if (n_rows == 0) return;      // no node of this part is the HMM's business (--sv over a part without long alleles): no calls, no lines
+    std::vector<uint32_t> n_kept(n_rows);
+    std::vector<uint8_t> flags(n_rows);
+    PartHandle ph;
+    const int64_t ta = s.since_begin();
+    device_check(dev_, vgmi_hmm_emissions_ploidy(dev_, (uint32_t)n_gt, cfg.sample_ploidy, (uint32_t)ps.used.size(), ps.used8.data(), ps.pos_all.data(), ps.top_mask,
+                                                 (uint32_t)g_.bitlen, ps.ave, ps.lower, ps.upper, ps.tab.data(), n_rows, pc.e_begin.data(), pc.e_count.data(),
+                                                 pc.gt0.data(), n_kept.data(), flags.data(), &ph.p),
+                 "device HMM emissions: ");
+    const int64_t t_emit = s.since_begin();
+    for (size_t rr = 0; rr < n_rows; ++rr)
+        if (flags[rr] & 2u) {
+            ps.broken = true;          // a k-mer no haplotype carries: the host path prunes it
+            return;
+        }
+    // The part's windows on `helpers` threads.  A: the flagged rows.  (Once per graph, under the part's lock: the plan.)  Then recursion
+    // and posterior on the device.  C: the calls and the VCF lines.
+    const size_t helpers = std::max<size_t>(1, std::min<size_t>(nw, s.n_threads / ps.n_parts));
+    const WindowHaps haps = ps.haps();
+    FlaggedRows fl(nw);
+    over_windows(nw, helpers, g_phase.pass_a, [&](size_t wi) {
+        FlaggedScratch sc(ps.ave, ps.lower, ps.upper);
+        for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr)
+            if (flags[rr] & 1u) flagged_row(fl, wi, rr, *s.tasks[t0 + wi].chr, pc.row_node[rr], haps, pc.gt0[rr], r, sc, n_kept[rr]);
+    });
+    const int64_t t_a = s.since_begin();
+    upload_flagged(fl, ph.p);
+    const int64_t t_rows = s.since_begin();
+    const std::shared_ptr<EmitPartPlan> plan = panel_plan(s, ps, pc, t0, nw, helpers, n_kept);
+    const int64_t t_b = s.since_begin();
+    std::vector<long double> prob(n_rows);
+    std::vector<uint32_t> winner(n_rows, 0xFFFFFFFFu);
+    if (plan->n_steps) device_check(dev_, vgmi_hmm_part_calls_plan(ph.p, plan->plan, prob.data(), winner.data()), "device HMM recursion: ");
+    const int64_t t_calls = s.since_begin();
+    if (g_phase_on)
+        std::fprintf(stderr, "[varigraph-mi] HMM part %zu (windows %zu-%zu): emissions, recursion and posterior on the device from %.3f to %.3f s (%zu of %zu nodes scored by the host, %zu scored again on the device): "
+                     "emission kernel %.3f, sequence checks (host) %.3f, rows fixed on the device %.3f, plan (strings + step tables: once per graph) %.3f, recursion + posterior %.3f\n",
+                     part, t0, t1 - 1, ta * 1e-9, t_calls * 1e-9, fl.n_host, n_rows, fl.n_fixed, (t_emit - ta) * 1e-9, (t_a - t_emit) * 1e-9, (t_rows - t_a) * 1e-9,
+                     (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
+    s.note_device_span(ta, t_calls);
+    // the calls' k-mer tallies on the device too (the node lists and the sample's coverage are there for the emissions):
+    // per sample, the walk over every called node's k-mer list was 0.8 of 1.7 host thread-seconds (VGH_DEVICE_TALLIES=0: the walk)
+    std::vector<uint32_t> tally;
+    std::vector<uint8_t> tally_uniq;
+    static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
+    if (device_tallies && plan->n_steps && cfg.sample_ploidy == 2 && n_hap_ <= 64 && n_gt <= 128) {
+        std::vector<uint8_t> hap_ab(2 * n_gt, 0xFF);
+        bool pairs = true;
+        for (size_t g2 = 0; g2 < n_gt; ++g2) {
+            if (ps.genotypes[g2].size() != 2 || ps.genotypes[g2][0] > 254 || ps.genotypes[g2][1] > 254) { pairs = false; break; }
+            hap_ab[2 * g2] = (uint8_t)ps.genotypes[g2][0];
+            hap_ab[2 * g2 + 1] = (uint8_t)ps.genotypes[g2][1];
+        }
+        uint64_t sel = 0;
+        for (uint16_t hap : ps.top)
+            if (hap < n_hap_ && hap < 64) sel |= 1ull << hap;
+        if (pairs) {
+            tally.resize(4 * n_rows);
+            tally_uniq.resize(n_rows);
+            device_check(dev_, vgmi_hmm_tallies(dev_, n_rows, pc.e_begin.data(), pc.e_count.data(), winner.data(), (uint32_t)n_gt, hap_ab.data(), n_hap_, sel,
+                                                tally.data(), tally_uniq.data()),
+                         "device tallies: ");
+        }
+    }
+    over_windows(nw, helpers, g_phase.pass_c, [&](size_t wi) {
+        const size_t t = t0 + wi;
+        const Chrom& chr = *s.tasks[t].chr;
+        const std::vector<uint32_t>& rows_w = plan->win_rows[wi];
+        if (tally.empty()) finish_rows(s.tasks[t].chr, rows_w, pc.row_node.data(), haps, prob.data(), winner.data(), r);
+        // the lines of the scored rows -- no other node has a call -- with the head of every line taken from the plan instead of the site map
+        s.piece_done[t] = 1;
+        std::string out;
+        size_t room = 0;
+        for (const uint32_t rw : rows_w) room += (size_t)(plan->line_head_off[rw + 1] - plan->line_head_off[rw]) + 48;
+        out.reserve(room);
+        std::vector<uint64_t> gt;
+        for (const uint32_t rw : rows_w) {
+            auto head = [&](std::string& o) {
+                const uint64_t h0 = plan->line_head_off[rw], h1 = plan->line_head_off[rw + 1];
+                if (h0 != h1) o.append(plan->line_head, h0, h1 - h0);
+                return h0 != h1;      // false: no such site in the VCF
+            };
+            const Node& node = chr.nodes[pc.row_node[rw]];
+            if (tally.empty()) append_call_line(out, node, cfg.min_gq, gt, head);
+            else if (winner[rw] < n_gt) {      // (else no entry with a positive posterior: no call)
+                const std::vector<uint16_t>& called = ps.genotypes[winner[rw]];
+                append_tally_line(out, node.gn->hap_gt[called[0]], node.gn->hap_gt[called[1]], prob[rw], &tally[4 * rw], tally_uniq[rw], cfg.min_gq, head);
+            }
+        }
+        s.pieces[t] = std::move(out);
+        s.emit_windows_done += !rows_w.empty();
+    });
+}
+
+// ---------------------------------------------------------------- emissions on the device, haplotypes selected per window
+// -n below the graph's haplotypes, a diploid sample: DESIGN_INGEST_HMM.md 4.13.
+// The reference draws every window's haplotypes from their k-mer support, drops from a node's list every k-mer no drawn haplotype
+// carries -- for good -- and scores what is left (src/genotype.cpp:500-610, 673-686, 815-818).  haplotype_combinations over the sorted
+// draw yields pairs over -n places whatever was drawn: positions, keep matrix and the shape of every step are the sample's, the
+// haplotype at each place is the window's.  Support sums, emissions (with the prune), recursion, posterior and tallies run on the
+// device; the draws (std::mt19937, libm), the sequence checks (strings), the step tables (libm) and the genotype strings stay here.
+// A row is the range [front, back] of what is left of its node's list plus the device's alive bytes; node.kmers is pruned by the same
+// rule right after the emission launch, so that the host's lists and the device's bytes agree after every sample.
+Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
+{
+    const Run& r = s.r;
+    const GenotypeConfig& cfg = *r.cfg;
+    const std::vector<Task>& tasks = s.tasks;
+    const size_t n_entries = g_.node_key_index.size();
+    const double tb0 = s.since_begin() * 1e-9;
+    const float ave = r.hap_cov;
+    double lower = 256.0f, upper = -0.1f;
+    poisson_interval(ave, lower, upper);
+    const uint32_t n_used = r.haploid_num;
+    std::vector<uint16_t> places(n_used);
+    std::iota(places.begin(), places.end(), (uint16_t)0);
+    const std::vector<std::vector<uint16_t>> shape = haplotype_combinations(places, cfg.sample_type, 2, (uint16_t)(n_hap_ - 1));
+    const size_t n_gt = shape.size();
+    bool pairs = n_gt >= 1 && n_gt <= 128;
+    for (const auto& gtv : shape) pairs = pairs && gtv.size() == 2;
+    if (!pairs) return Emitted::no;
+    std::vector<uint8_t> pos_a(n_gt), pos_b(n_gt);
+    for (size_t gi = 0; gi < n_gt; ++gi) {
+        pos_a[gi] = (uint8_t)shape[gi][0];
+        pos_b[gi] = (uint8_t)shape[gi][1];
+    }
+    const std::vector<uint8_t> keep_mat = keep_matrix(shape);      // (places keep the haplotypes' order)
+    const std::vector<long double> tab = emission_table(ave, 2);
+    if (!entries_uploaded_) {
+        device_check(dev_, vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
+        entries_uploaded_ = true;
+        if (!lists_whole_.load()) alive_stale_.store(true);
+    }
+    device_check(dev_, vgmi_hmm_sample_upload(dev_, r.cov, n_entries), "device HMM emissions: ");
+    if (alive_stale_.load()) {      // a sample of this run took a host path: the lists as the host left them
+        std::vector<uint8_t> alive(n_entries, 0);
+        for (const auto& c : chroms_)
+            for (const auto& n : c.nodes)
+                for (uint32_t pos : n.kmers) alive[pos] = 1;
+        device_check(dev_, vgmi_hmm_alive_upload(dev_, alive.data(), n_entries), "device HMM emissions: ");
+        alive_stale_.store(false);
+    }
+    const size_t nw = tasks.size();
+    // rows, window after window.  Support reads every node with more than one allele; the HMM works on those --sv leaves.
+    std::vector<uint64_t> sup_begin, e_begin_sv;
+    std::vector<uint32_t> sup_count, sup_win, sup_node, e_count_sv, e_win_sv, e_node_sv;
+    std::vector<size_t> win_row0(nw + 1, 0);
+    {
+        CpuBudget::Hold cpu;
+        PhaseTimer t_list(g_phase.list);
+        for (size_t t = 0; t < nw; ++t) {
+            const Chrom& chr = *tasks[t].chr;
+            const SiteMap& sites = vcf_sites(chr);
+            for (uint32_t i = tasks[t].first; i < tasks[t].last; ++i) {
+                const Node& n = chr.nodes[i];
+                if (n.gn->hap_gt.size() <= 1) continue;
+                const uint64_t b = n.kmers.empty() ? 0 : n.kmers.front();
+                const uint32_t cnt = n.kmers.empty() ? 0 : n.kmers.back() - n.kmers.front() + 1;
+                sup_begin.push_back(b);
+                sup_count.push_back(cnt);
+                sup_win.push_back((uint32_t)t);
+                sup_node.push_back(i);
+                if (cfg.sv_only && !skipped(chr, sites, n, true)) {
+                    e_begin_sv.push_back(b);
+                    e_count_sv.push_back(cnt);
+                    e_win_sv.push_back((uint32_t)t);
+                    e_node_sv.push_back(i);
+                }
+            }
+            win_row0[t + 1] = cfg.sv_only ? e_begin_sv.size() : sup_begin.size();
+        }
+    }
+    const std::vector<uint64_t>& e_begin = cfg.sv_only ? e_begin_sv : sup_begin;
+    const std::vector<uint32_t>&e_count = cfg.sv_only ? e_count_sv : sup_count, &row_win = cfg.sv_only ? e_win_sv : sup_win,
+                               &row_node = cfg.sv_only ? e_node_sv : sup_node;
+    const size_t n_rows = e_begin.size();
+    const int64_t ta = s.since_begin();
+    // 1. the support the draw is weighted by, on the device
+    std::vector<uint32_t> support(nw * n_hap_, 0);
+    device_check(dev_, vgmi_hmm_support(dev_, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
+                 "device HMM support: ");
+    const int64_t t_sup = s.since_begin();
+    // 2. the draws; 3. what follows from them: the window's haplotypes and mask, its genotypes, the rows' reference-allele masks
+    std::vector<std::vector<uint16_t>> win_top(nw);
+    std::vector<std::vector<std::vector<uint16_t>>> win_gts(nw);
+    std::vector<GenotypeList> win_glist(nw);
+    std::vector<uint8_t> win_used8(nw * n_used, 0);
+    std::vector<uint64_t> win_mask(nw, 0);
+    std::vector<uint16_t> gt0(n_rows ? n_rows : 1, 0);
+    over_windows(nw, s.n_threads, g_phase.select, [&](size_t wi) {
+        HaplotypeSampler sampler(std::vector<uint32_t>(support.begin() + wi * n_hap_, support.begin() + (wi + 1) * n_hap_), (int)r.haploid_num);
+        std::vector<uint16_t>& top = win_top[wi];
+        top = sampler.top;
+        std::sort(top.begin(), top.end());
+        if (top.size() != n_used) throw std::runtime_error("internal: a window drew another number of haplotypes");
+        for (size_t p = 0; p < n_used; ++p) {
+            win_used8[wi * n_used + p] = (uint8_t)top[p];
+            win_mask[wi] |= 1ULL << top[p];
+        }
+        win_gts[wi].resize(n_gt);
+        for (size_t gi = 0; gi < n_gt; ++gi) win_gts[wi][gi] = {top[pos_a[gi]], top[pos_b[gi]]};
+        win_glist[wi] = genotype_list(win_gts[wi], top);
+        const Chrom& chr = *tasks[wi].chr;
+        for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+            const auto& hap_gt = chr.nodes[row_node[rr]].gn->hap_gt;
+            uint16_t m = 0;
+            for (size_t p = 0; p < n_used; ++p) m |= (uint16_t)((hap_gt[top[p]] == 0) << p);
+            gt0[rr] = m;
+        }
+    });
+    auto haps_of = [&](size_t wi) { return WindowHaps{win_top[wi], win_top[wi], win_gts[wi], win_glist[wi]}; };
+    const int64_t t_draw = s.since_begin();
+    size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0;
+    int64_t t_emit = t_draw, t_a = t_draw, t_rows = t_draw, t_b = t_draw, t_calls = t_draw;
+    std::vector<long double> prob(n_rows ? n_rows : 1);
+    std::vector<uint32_t> winner(n_rows ? n_rows : 1, 0xFFFFFFFFu);
+    std::vector<std::vector<uint32_t>> win_rows(nw);      // per window: the rows that have a score
+    size_t n_steps = 0;
+    if (n_rows) {
+        // 4. emission scores on the device, the prune included
+        std::vector<uint32_t> n_kept(n_rows);
+        std::vector<uint8_t> flags(n_rows);
+        PartHandle ph;
+        device_check(dev_, vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, n_used, pos_a.data(), pos_b.data(), (uint32_t)nw, win_used8.data(), win_mask.data(),
+                                                     (uint32_t)g_.bitlen, ave, lower, upper, tab.data(), n_rows, e_begin.data(), e_count.data(), row_win.data(),
+                                                     gt0.data(), n_kept.data(), flags.data(), &ph.p),
+                     "device HMM emissions: ");
+        t_emit = s.since_begin();
+        // 5. the same prune on the host's lists, for exactly the nodes that lost k-mers; 6. the flagged rows
+        FlaggedRows fl(nw);
+        std::atomic<size_t> pruned_nodes{0};
+        over_windows(nw, s.n_threads, g_phase.pass_a, [&](size_t wi) {
+            Chrom& chr = *tasks[wi].chr;
+            const WindowHaps haps = haps_of(wi);
+            std::vector<uint32_t> kept;
+            FlaggedScratch sc(ave, lower, upper);
+            for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+                Node& node = chr.nodes[row_node[rr]];
+                if (n_kept[rr] != node.kmers.size()) {
+                    kept.clear();
+                    for (uint32_t pos : node.kmers)
+                        if ((r.packed[pos] >> 16) & win_mask[wi]) kept.push_back(pos);
+                    if (kept.size() != n_kept[rr]) throw std::runtime_error("internal: the device's k-mer lists differ from the host's");
+                    node.kmers.keep(kept);
+                    ++pruned_nodes;
+                }
+                if (!(flags[rr] & 1u)) continue;
+                const size_t before = fl.fix_j[wi].size();
+                flagged_row(fl, wi, rr, chr, row_node[rr], haps, gt0[rr], r, sc, n_kept[rr]);
+                // (sequence_fixes counts along the list; the device along the row's range)
+                for (size_t q = before; q < fl.fix_j[wi].size(); ++q) fl.fix_j[wi][q] = node.kmers[fl.fix_j[wi][q]] - (uint32_t)e_begin[rr];
+            }
+        });
+        n_pruned = pruned_nodes.load();
+        if (n_pruned) lists_whole_.store(false, std::memory_order_relaxed);
+        alive_stale_.store(false);      // (hidden_states above walked lists that were pruned already: nothing left them)
+        t_a = s.since_begin();
+        upload_flagged(fl, ph.p);
+        n_host_rows = fl.n_host;
+        n_fixed_rows = fl.n_fixed;
+        t_rows = s.since_begin();
+        // 7. the recursion's inputs: genotype strings (the window's haplotypes decide them), step tables (libm), chains
+        std::vector<std::vector<Seen>> seen(nw);
+        std::vector<uint8_t> gid(n_rows * n_gt, 0), order(n_rows * n_gt, 0);
+        over_windows(nw, s.n_threads, g_phase.pass_a, [&](size_t wi) {
+            row_strings(*tasks[wi].chr, win_row0[wi], win_row0[wi + 1], row_node.data(), gt0.data(), n_kept.data(), haps_of(wi), gid.data(), order.data(), seen[wi],
+                        win_rows[wi]);
+        });
+        StepArrays steps(win_rows, n_rows, 2);
+        n_steps = steps.n_steps;
+        if (n_steps) over_windows(nw, s.n_threads, g_phase.pass_b, [&](size_t wi) { steps.fill(wi, seen[wi], (uint16_t)n_hap_); });
+        t_b = s.since_begin();
+        if (n_steps) {
+            const long double uniform = 1.0L / (long double)n_gt;
+            device_check(dev_, vgmi_hmm_part_calls(ph.p, 2, keep_mat.data(), 1, steps.row.data(), steps.restart.data(), steps.pw.data(), n_steps, &uniform,
+                                                   steps.chains.data(), (uint32_t)steps.chains.size(), gid.data(), order.data(), steps.fwd.data(), steps.bwd.data(),
+                                                   prob.data(), winner.data()),
+                         "device HMM recursion: ");
+        }
+        t_calls = s.since_begin();
+    }
+    s.note_device_span(ta, t_calls);
+    // 8. the calls' tallies on the device (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists)
+    std::vector<uint32_t> tally;
+    std::vector<uint8_t> tally_uniq;
+    static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
+    if (device_tallies && n_steps) {
+        tally.resize(4 * n_rows);
+        tally_uniq.resize(n_rows);
+        device_check(dev_, vgmi_hmm_tallies_select(dev_, n_rows, e_begin.data(), e_count.data(), row_win.data(), winner.data(), (uint32_t)n_gt, pos_a.data(),
+                                                   pos_b.data(), n_used, (uint32_t)nw, win_used8.data(), tally.data(), tally_uniq.data()),
+                     "device tallies: ");
+    }
+    // 9. the lines
+    over_windows(nw, s.n_threads, g_phase.pass_c, [&](size_t wi) {
+        s.emit_windows_done += !win_rows[wi].empty();
+        const Chrom& chr = *tasks[wi].chr;
+        if (tally.empty()) {
+            finish_rows(tasks[wi].chr, win_rows[wi], row_node.data(), haps_of(wi), prob.data(), winner.data(), r);
+            write_piece(s, wi);
+            return;
+        }
+        s.piece_done[wi] = 1;
+        auto vc = g_.vcf_info.find(chr.name);
+        if (vc == g_.vcf_info.end()) return;
+        SiteWalk walk(vc->second);
+        std::string out;
+        for (const uint32_t rw : win_rows[wi]) {
+            const Node& node = chr.nodes[row_node[rw]];
+            const std::vector<std::string>* fields = walk.at(node.start);
+            if (winner[rw] >= n_gt) continue;            // no entry with a positive posterior: no call
+            const std::vector<uint16_t>& called = win_gts[wi][winner[rw]];
+            append_tally_line(out, node.gn->hap_gt[called[0]], node.gn->hap_gt[called[1]], prob[rw], &tally[4 * rw], tally_uniq[rw], cfg.min_gq,
+                              [&](std::string& o) { return append_site_head(o, fields); });
+        }
+        s.pieces[wi] = std::move(out);
+    });
+    if (g_phase_on) {
+        std::fprintf(stderr, "[varigraph-mi] HMM with haplotypes selected per window (%zu windows, %zu rows, %zu nodes pruned, %zu nodes scored by the host, %zu scored "
+                     "again on the device): support %.3f, draws (host) %.3f, emission kernel %.3f, prune + sequence checks (host) %.3f, rows fixed on the device %.3f, "
+                     "strings + step tables (host) %.3f, recursion + posterior %.3f\n",
+                     nw, n_rows, n_pruned, n_host_rows, n_fixed_rows, (t_sup - ta) * 1e-9, (t_draw - t_sup) * 1e-9, (t_emit - t_draw) * 1e-9, (t_a - t_emit) * 1e-9,
+                     (t_rows - t_a) * 1e-9, (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
+        std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: 1 parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
+                     s.since_begin() * 1e-9 - tb0, nw, tasks.size());
+    }
+    return Emitted::yes;
+}
+
+std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const std::string& sample_name,
+                           const GenotypeConfig& cfg, const uint8_t* cov_node)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    std::vector<uint8_t> gathered;
+    if (!cov_node) {      // a caller with per-key counters only (tests, the C API): the per-node gather on the host
+        const size_t n_entries = g_.node_key_index.size();
+        gathered.resize(n_entries);
+        for (size_t j = 0; j < n_entries; ++j) gathered[j] = cov[g_.node_key_index[j]];
+        cov_node = gathered.data();
+    }
+    Run r;
+    r.cov = cov_node;
+    r.hap_cov = hap_kmer_coverage;
+    r.cfg = &cfg;
+    r.haploid_num = std::min(cfg.haploid_num, n_hap_);
+    if (g_.bitlen <= 6) fill_packed(r, cfg.threads);
+    reset_calls();
+
+    RunShared s(r);
+    s.t_begin = t_begin;
+    s.tasks = windows(cfg);
+    s.n_threads = std::max(1u, std::min<uint32_t>(cfg.threads, (uint32_t)s.tasks.size()));
+    s.pieces.resize(s.tasks.size());
+    s.piece_done.assign(s.tasks.size(), 0);
+
+    std::vector<WindowWork> works;
+    const DevicePaths paths = device_paths(r, s.tasks, works);
+    WindowBuffers bufs;
+    if (paths.pool_device) {
+        bufs.allocate(paths.total_room, paths.n_gt, cfg.sample_ploidy);
+        for (WindowWork& w : works) bufs.bind(w);
+    }
+    const Emitted emitted = paths.emit ? hmm_whole_panel(s) : paths.select ? hmm_selected(s) : Emitted::no;
+    if (emitted == Emitted::lists_pruned) {
+        // a list was pruned after all (or would be): this graph takes the host's preparation from now on
+        emit_device_off_ = true;
+        return run(cov, hap_kmer_coverage, sample_name, cfg, cov_node);
+    }
+    if (emitted == Emitted::no) hmm_on_pool(s, works, bufs, paths.n_gt);
+
+    const bool emitted_on_device = emitted == Emitted::yes;
+    last_device_seconds = s.dev_last.load() > 0 ? (double)(s.dev_last.load() - s.dev_first.load()) * 1e-9 : 0;
+    last_windows = s.tasks.size();
+    last_device_windows = emitted_on_device ? s.emit_windows_done.load() : 0;
     for (const auto& w : works) last_device_windows += w.on_device && !w.nodes.empty();
     const auto t_hmm = std::chrono::steady_clock::now();
     last_hmm_seconds = std::chrono::duration<double>(t_hmm - t_begin).count();
     if (g_phase_on) {
         std::fprintf(stderr, "[varigraph-mi] HMM thread-seconds: selection %.2f, hidden states %.2f, emissions %.2f, forward %.2f, backward %.2f, posterior %.2f (wall %.2f on %u threads)\n",
                      g_phase.select.exchange(0) * 1e-9, g_phase.states.exchange(0) * 1e-9, g_phase.emit.exchange(0) * 1e-9, g_phase.fwd.exchange(0) * 1e-9,
-                     g_phase.bwd.exchange(0) * 1e-9, g_phase.post.exchange(0) * 1e-9, last_hmm_seconds, n_threads);
+                     g_phase.bwd.exchange(0) * 1e-9, g_phase.post.exchange(0) * 1e-9, last_hmm_seconds, s.n_threads);
         if (last_device_seconds > 0) std::fprintf(stderr, "[varigraph-mi] HMM recursion on the device: %.2f s\n", last_device_seconds);
         if (emitted_on_device)
             std::fprintf(stderr, "[varigraph-mi] host thread-seconds around the device (all samples in flight since the last line of this kind): node lists %.2f, "
@@ -2899,15 +2796,15 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
         auto text_worker = [&]() {
             for (;;) {
                 const size_t t = next_text.fetch_add(1);
-                if (t >= tasks.size()) return;
-                if (!piece_done[t]) {
+                if (t >= s.tasks.size()) return;
+                if (!s.piece_done[t]) {
                     CpuBudget::Hold cpu;
-                    make_piece(t);
+                    write_piece(s, t);
                 }
             }
         };
         std::vector<std::thread> tpool;
-        for (uint32_t t = 1; t < n_threads; ++t) tpool.emplace_back(text_worker);
+        for (uint32_t t = 1; t < s.n_threads; ++t) tpool.emplace_back(text_worker);
         text_worker();
         for (auto& th : tpool) th.join();
     }
@@ -2916,7 +2813,7 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
     PhaseTimer t_text(g_phase.text);
     std::ostringstream oss;
     oss << g_.vcf_head + "\t" + sample_name + "\n";
-    for (const auto& piece : pieces) oss << piece;
+    for (const auto& piece : s.pieces) oss << piece;
     // SAVE::save strips the newlines around each 10 MB chunk and adds one back (src/save.cpp:16-24); on the whole
     // text that is: no leading newline, exactly one trailing
     std::string text = strip_newlines(oss.str());

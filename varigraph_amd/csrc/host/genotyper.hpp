@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -144,6 +145,54 @@ private:
 
     struct WindowWork;   // what a window hands to the device recursion and gets back (genotyper.cpp)
     struct ScoreCtx;     // per-thread scratch and memoised libm values of score_states
+    using SiteMap = std::map<uint32_t, std::vector<std::string>>;      // a chromosome of GraphIndex::vcf_info
+    struct Task { Chrom* chr; uint32_t first, last; };      // a window: nodes [first, last) of a chromosome
+    struct RunShared;        // what the paths of one run() share: windows, pieces of text, the device's time span
+    struct DevicePaths;      // which path a sample takes
+    struct WindowBuffers;    // the run's arrays the windows on the pool write into
+    struct PanelSample;      // whole-panel emissions: the sample's one genotype list and what follows from it
+    struct WindowHaps;       // a window's haplotypes, the genotypes over them and their flat list
+    struct FlaggedRows;      // what the host found out about the rows the emission kernel flagged
+    struct FlaggedScratch;
+    enum class Emitted { no, yes, lists_pruned };
+
+    // ---- run(), step by step
+    void fill_packed(Run& r, uint32_t threads);
+    void reset_calls();
+    std::vector<Task> windows(const GenotypeConfig& cfg);
+    DevicePaths device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works) const;
+    // the three ways through the HMM.  On the pool: window() prepares every window on the host, recursion and posterior go to the device
+    // in parts or stay here.  The other two score the emissions on the device as well: with every haplotype of the panel selected (one
+    // genotype list per sample, per-part cache and plan), or with the haplotypes drawn per window (-n below the panel, diploid)
+    void hmm_on_pool(RunShared& s, std::vector<WindowWork>& works, const WindowBuffers& bufs, size_t n_gt);
+    Emitted hmm_whole_panel(RunShared& s);
+    Emitted hmm_selected(RunShared& s);
+    void write_piece(RunShared& s, size_t t);      // the VCF lines of a window from its nodes' calls
+    // whole-panel emissions, per part of the windows
+    struct EmitPartCache;
+    struct EmitPartPlan;
+    void panel_part(RunShared& s, PanelSample& ps, size_t part);
+    bool panel_rows(RunShared& s, const PanelSample& ps, EmitPartCache& pc, size_t t0, size_t t1);
+    std::shared_ptr<EmitPartPlan> panel_plan(RunShared& s, const PanelSample& ps, EmitPartCache& pc, size_t t0, size_t nw, size_t helpers,
+                                             const std::vector<uint32_t>& n_kept);
+    // ---- what the paths share
+    const SiteMap& vcf_sites(const Chrom& chr) const;      // throws for a chromosome the VCF lacks
+    static bool skipped(const Chrom& chr, const SiteMap& sites, const Node& n, bool sv_only);      // not the HMM's business
+    static GenotypeList genotype_list(const std::vector<std::vector<uint16_t>>& genotypes, const std::vector<uint16_t>& used);
+    void flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint16_t gt0, const Run& r,
+                     FlaggedScratch& sc, uint32_t& n_kept);
+    void upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part);
+    // a node the HMM works on, in window order; at: where its scores are (a place in the window or a row of the part), -1: it has none
+    struct Seen { uint32_t start, end; int64_t at; };
+    struct StepArrays;
+    static void step_tables(const std::vector<Seen>& seen, uint32_t stride, uint16_t population, size_t step0, size_t row_base, long double* pw,
+                            uint32_t* row, uint8_t* restart, uint64_t* fwd, uint64_t* bwd);
+    void row_strings(const Chrom& chr, size_t row_lo, size_t row_hi, const uint32_t* row_node, const uint16_t* gt0, const uint32_t* n_kept, const WindowHaps& h,
+                     uint8_t* gid, uint8_t* order, std::vector<Seen>& seen, std::vector<uint32_t>& scored_rows) const;
+    void finish_rows(Chrom* chr, const std::vector<uint32_t>& rows, const uint32_t* row_node, const WindowHaps& h, const long double* prob,
+                     const uint32_t* winner, const Run& r);
+    template <class Head>
+    static void append_call_line(std::string& out, const Node& node, float min_gq, std::vector<uint64_t>& gt, Head&& head);
     std::vector<long double> score_states(const NodeStates& ns, ScoreCtx& sc) const;
     // forced_top: the window's selected haplotypes as an earlier pass over the same window drew them (the host takes a window
     // back from the device path: same haplotypes, same pruned k-mer lists, nothing is drawn again)
@@ -173,7 +222,7 @@ private:
     // sample, kept for the next (one list per part; `key` names the options it was made under).
     struct EmitPartPlan {      // made for one pattern of scored rows; immutable once made; the device block goes with the last holder
         std::vector<uint8_t> scored;
-        std::vector<std::vector<uint32_t>> win_nodes, win_rows;      // per window: the scored nodes and their rows
+        std::vector<std::vector<uint32_t>> win_rows;                 // per window: the rows that have a score
         // the part of a site's VCF line that every sample shares (CHROM .. INFO with FILTER forced PASS, FORMAT and the tab behind it:
         // src/genotype.cpp:1628-1640), per row of the part, end to end; a row without a site in the VCF has none
         std::string line_head;
