@@ -408,6 +408,28 @@ int vgmi_hmm_emissions_select(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used, con
 int vgmi_hmm_tallies_select(vgmi_ctx *ctx, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win,
                             const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b, uint32_t n_used,
                             uint32_t n_windows, const uint8_t *win_used, uint32_t *out, uint8_t *unique_out);
+/* ---- ... and a POLYPLOID sample (3 or 4 haplotypes per genotype) under -n: a genotype list per window ---------------------------------
+ * The genotypes of a polyploid sample are blocks of `ploidy` consecutive haplotypes (src/genotype.cpp:846-873): every drawn haplotype
+ * h > 0 gives the block that holds it (ids above the last haplotype read 0), a drawn 0 the all-zero block, and the list is the sorted
+ * set of distinct blocks -- 1 .. -n genotypes, another number in every window, over haplotypes that were not all drawn.  So the lists
+ * are handed over per window, by haplotype id, and every mask is 64 bits over haplotype ids (up to 8 * bit_len - 2):
+ *   emissions_select_ploidy  window w has win_n_gt[w] genotypes (1 .. n_gt, n_gt <= 64); genotype g of it is the `ploidy` ids
+ *                    win_haps[(w * n_gt + g) * ploidy ..], an id that stands several times counting each time.  The PRUNE is by
+ *                    win_top_mask[w], the drawn haplotypes: an alive entry none of them carries is marked dead and passed over.  The
+ *                    SCORE is over the genotypes' haplotypes, drawn or not.  gt0[r]: the haplotypes that carry the reference allele at
+ *                    row r's node.  The part's rows are n_gt scores wide; a row's scores beyond its window's count are zero.  n_kept_out
+ *                    and flag bit 0 as above.
+ *   part_fix_rows_wide  vgmi_hmm_part_fix_rows for such a part: fix_mask[i] holds the haplotype ids entry fix_j[i] loses.
+ * vgmi_hmm_part_set_rows, _part_calls (one n_gt per part: a caller with lists of several lengths makes a part per length, keep
+ * matrices per window through the chains' keep_index) and _part_fetch work on the part as before; the tallies of a polyploid call are
+ * the host's. */
+int vgmi_hmm_emissions_select_ploidy(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, uint32_t n_windows, const uint32_t *win_n_gt,
+                                     const uint8_t *win_haps /* n_windows x n_gt x ploidy */, const uint64_t *win_top_mask, uint32_t bit_len,
+                                     float ave, double lower, double upper, const void *tables, uint64_t n_rows, const uint64_t *entry_begin,
+                                     const uint32_t *entry_count, const uint32_t *row_win, const uint64_t *gt0, uint32_t *n_kept_out,
+                                     uint8_t *flags_out, vgmi_hmm_part **out);
+int vgmi_hmm_part_fix_rows_wide(vgmi_hmm_part *part, uint64_t n, const uint64_t *rows, const uint32_t *fix_off, const uint32_t *fix_j,
+                                const uint64_t *fix_mask);
 /* the part's emission rows back on the host (n_rows x n_gt long doubles): tests and diagnostics */
 int vgmi_hmm_part_fetch(vgmi_hmm_part *part, void *obs_out);
 void vgmi_hmm_part_free(vgmi_hmm_part *part);

@@ -628,33 +628,34 @@ Genotyper::EmitPartPlan::~EmitPartPlan() { vgmi_hmm_plan_free(plan); }
 // The sequence check of hidden_states() on its own (same conditions, same sets, same strings), for a node whose products stay on the
 // device: which entries of the node's list lose which haplotypes.  The fast path's reading of an entry (one 64-bit word: coverage,
 // multiplicity, haplotype bits) -- the device's emission kernel reads the same word the same way.
-void Genotyper::sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vector<uint16_t>& used, uint16_t gt0_mask, double lower, double upper,
-                               const Run& r, std::vector<uint32_t>& fix_j, std::vector<uint16_t>& fix_mask) const
+void Genotyper::sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vector<uint16_t>& used, uint64_t gt0_mask, double lower, double upper,
+                               const Run& r, std::vector<uint32_t>& fix_j, std::vector<uint64_t>& fix_mask) const
 {
     const Node& node = chr.nodes[node_i];
     const std::vector<uint16_t>& hap_gt = node.gn->hap_gt;
     const uint64_t bl = g_.bitlen;
     const uint32_t* const key_of = g_.node_key_index.data();
-    auto carried = [&](uint64_t w, uint32_t& low_multi) -> uint32_t {      // bits over `used`: the haplotypes that count as carrying the k-mer
+    // (masks over the places of `used`: 16 for a diploid sample's pairs, up to -n x ploidy <= 64 for a polyploid sample's blocks)
+    auto carried = [&](uint64_t w, uint32_t& low_multi) -> uint64_t {      // bits over `used`: the haplotypes that count as carrying the k-mer
         const uint8_t c = (uint8_t)w, f = (uint8_t)(w >> 8);
         const uint64_t bits = w >> 16;
         const int lb = (int)((bits >> (8 * bl - 1)) & 1u);
         const bool in_interval = lb == 1 && c >= lower && c <= upper;
-        uint32_t om = 0;
-        for (size_t p = 0; p < used.size(); ++p) om |= (uint32_t)((in_interval && ((gt0_mask >> p) & 1u)) ? 1u : (uint32_t)((bits >> used[p]) & 1u)) << p;
+        uint64_t om = 0;
+        for (size_t p = 0; p < used.size(); ++p) om |= (uint64_t)((in_interval && ((gt0_mask >> p) & 1u)) ? 1u : (uint32_t)((bits >> used[p]) & 1u)) << p;
         low_multi = (c < lower && f >= 2) ? 2u : (!(c > lower || f <= 1)) ? 1u : 0u;      // 2: asks for the sequences; 1: is checked once they are there
         return om;
     };
-    uint32_t need = 0;
+    uint64_t need = 0;
     for (uint32_t pos : node.kmers) {
         uint32_t lm;
-        const uint32_t om = carried(r.packed[pos], lm);
+        const uint64_t om = carried(r.packed[pos], lm);
         if (lm == 2u) need |= om;
     }
     if (!need) return;
     // the needed haplotypes' sequences; haplotypes with the same allele and the same flanks share one (two sequences at most nodes)
     std::vector<std::pair<std::string, std::unordered_set<uint64_t>>> seqs;
-    uint8_t which[16] = {0};
+    uint8_t which[64] = {0};
     for (size_t p = 0; p < used.size(); ++p) {
         if (!((need >> p) & 1u)) continue;
         const uint16_t hap = used[p], gt = hap_gt[hap];
@@ -675,15 +676,15 @@ void Genotyper::sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vec
     uint32_t j = 0;      // (an entry's index: 32 bits end to end, like entry_count -- graph2node keeps 128 k-mers a node, src/construct_index.cpp:1592-1596, but nothing here relies on it)
     for (uint32_t pos : node.kmers) {
         uint32_t lm;
-        const uint32_t om = carried(r.packed[pos], lm) & need;
+        const uint64_t om = carried(r.packed[pos], lm) & need;
         if (lm != 0u && om != 0u) {
             const uint64_t key_hash = g_.keys[key_of[pos]];
-            uint32_t drop = 0;
+            uint64_t drop = 0;
             for (size_t p = 0; p < used.size(); ++p)
-                if (((om >> p) & 1u) && seqs[which[p]].second.find(key_hash) == seqs[which[p]].second.end()) drop |= 1u << p;
+                if (((om >> p) & 1u) && seqs[which[p]].second.find(key_hash) == seqs[which[p]].second.end()) drop |= 1ull << p;
             if (drop) {
                 fix_j.push_back(j);
-                fix_mask.push_back((uint16_t)drop);
+                fix_mask.push_back(drop);
             }
         }
         ++j;
@@ -1830,7 +1831,7 @@ std::vector<Genotyper::Task> Genotyper::windows(const GenotypeConfig& cfg)
 
 // Which path a sample takes.  With a device context (set_device; VGH_HMM_DEVICE=0 keeps the host): recursion and posterior of the
 // eligible windows on the device (window(), window_finish()); `works` gets a window's room in the run's arrays.
-Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works) const
+Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works, bool refuse_select) const
 {
     const GenotypeConfig& cfg = *r.cfg;
     DevicePaths dp;
@@ -1875,8 +1876,17 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
     // prepares such a sample as before.
     bool plain_ids = true;      // haplotype h is bit h of an entry's word
     for (size_t i = 0; i < hap_ids_.size(); ++i) plain_ids = plain_ids && hap_ids_[i] == i;
-    dp.select = device_ok && !dp.emit && r.packed != nullptr && cfg.sample_ploidy == 2 && n_hap_ > r.haploid_num && r.haploid_num >= 1 &&
-                r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen && !knob_off("VGH_HMM_EMIT_DEVICE") &&
+    // A polyploid sample (3 or 4 haplotypes per genotype) takes that path too: its windows have lists of 1 .. -n blocks of haplotypes, so the
+    // room on the device is reckoned for -n genotypes, not for the handful dp.n_gt counts over the first -n haplotypes.
+    const bool blocks = cfg.sample_ploidy == 3 || cfg.sample_ploidy == 4;
+    const size_t sel_n_gt = blocks ? std::max<size_t>(dev_n_gt, r.haploid_num) : dev_n_gt;
+    const bool select_fits = !blocks || (total_room * sel_n_gt * sizeof(long double) <= (score_gib << 30) && [&] {
+        size_t free_b = 0, total_b = 0;
+        const size_t need = 3 * total_room * sel_n_gt * sizeof(long double) * ((4 + dev_parts_ - 1) / dev_parts_) + (size_t(1) << 30);
+        return vgmi_device_memory(dev_, &free_b, &total_b) != VGMI_OK || need <= free_b - free_b / 10;
+    }());
+    dp.select = device_ok && select_fits && !refuse_select && !dp.emit && r.packed != nullptr && (cfg.sample_ploidy == 2 || blocks) && n_hap_ > r.haploid_num &&
+                r.haploid_num >= 1 && r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen && !knob_off("VGH_HMM_EMIT_DEVICE") &&
                 !knob_off("VGH_HMM_SELECT_DEVICE");
     dp.pool_device = device_ok && !dp.emit && !dp.select;
     return dp;
@@ -2050,7 +2060,7 @@ struct Genotyper::FlaggedRows {
     std::vector<std::vector<uint64_t>> host_rows, fix_rows;
     std::vector<std::vector<long double>> host_obs;
     std::vector<std::vector<uint32_t>> fix_cnt, fix_j;      // fix_j: the entries, counted along the node's list
-    std::vector<std::vector<uint16_t>> fix_mask;
+    std::vector<std::vector<uint64_t>> fix_mask;            // over the places of `used`, until the caller says otherwise
     size_t n_host = 0, n_fixed = 0;      // rows handed over by upload_flagged
     explicit FlaggedRows(size_t nw) : host_rows(nw), fix_rows(nw), host_obs(nw), fix_cnt(nw), fix_j(nw), fix_mask(nw) {}
 };
@@ -2066,7 +2076,7 @@ struct Genotyper::FlaggedScratch {      // of one window's thread
     }
 };
 
-void Genotyper::flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint16_t gt0, const Run& r,
+void Genotyper::flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint64_t gt0, const Run& r,
                             FlaggedScratch& sc, uint32_t& n_kept)
 {
     static const bool fix_on_device = !knob_off("VGH_HMM_FIX_DEVICE");
@@ -2093,12 +2103,12 @@ void Genotyper::flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, u
     }
 }
 
-void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part)
+void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap_id)
 {
     std::vector<uint64_t> all_rows, f_rows;
     std::vector<long double> all_obs;
     std::vector<uint32_t> f_off(1, 0), f_j;
-    std::vector<uint16_t> f_m;
+    std::vector<uint64_t> f_m;
     for (size_t wi = 0; wi < fl.host_rows.size(); ++wi) {
         all_rows.insert(all_rows.end(), fl.host_rows[wi].begin(), fl.host_rows[wi].end());
         all_obs.insert(all_obs.end(), fl.host_obs[wi].begin(), fl.host_obs[wi].end());
@@ -2111,17 +2121,24 @@ void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part)
     fl.n_host = all_rows.size();
     fl.n_fixed = f_rows.size();
     if (!all_rows.empty()) device_check(dev_, vgmi_hmm_part_set_rows(part, all_rows.size(), all_rows.data(), all_obs.data()), "device HMM emissions: ");
-    if (!f_rows.empty()) device_check(dev_, vgmi_hmm_part_fix_rows(part, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
+    if (f_rows.empty()) return;
+    if (by_hap_id) {      // a part with a genotype list per window: the masks are over haplotype ids already
+        device_check(dev_, vgmi_hmm_part_fix_rows_wide(part, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
+        return;
+    }
+    const std::vector<uint16_t> f_m16(f_m.begin(), f_m.end());      // (<= 16 places)
+    device_check(dev_, vgmi_hmm_part_fix_rows(part, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m16.data()), "device HMM emissions: ");
 }
 
 // The rows [row_lo, row_hi) of a window: every node as the chains see it (`seen`), and for the rows that have a score (n_kept) the
 // genotype strings of their entries (gid / order: n_gt bytes per row).  The genotype strings of a node with two alleles depend on which
 // haplotypes carry the reference allele only: one evaluation per distinct mask (the strings themselves as genotype_strings builds them).
-void Genotyper::row_strings(const Chrom& chr, size_t row_lo, size_t row_hi, const uint32_t* row_node, const uint16_t* gt0, const uint32_t* n_kept,
+template <class Mask>
+void Genotyper::row_strings(const Chrom& chr, size_t row_lo, size_t row_hi, const uint32_t* row_node, const Mask* gt0, const uint32_t* n_kept,
                             const WindowHaps& h, uint8_t* gid, uint8_t* order, std::vector<Seen>& seen, std::vector<uint32_t>& scored_rows) const
 {
     const size_t n_gt = h.genotypes.size();
-    std::unordered_map<uint32_t, uint32_t> gs_memo;      // mask -> a row that holds the pattern
+    std::unordered_map<uint64_t, uint32_t> gs_memo;      // mask -> a row that holds the pattern
     for (size_t rr = row_lo; rr < row_hi; ++rr) {
         const Node& n = chr.nodes[row_node[rr]];
         const uint32_t n_start = n.start, n_end = (uint32_t)(n_start + n.gn->seqs[0].size() - 1);
@@ -2155,7 +2172,9 @@ struct Genotyper::StepArrays {
     std::vector<uint64_t> fwd, bwd;
     std::vector<vgmi_hmm_chain> chains;
 
-    StepArrays(const std::vector<std::vector<uint32_t>>& win_rows, size_t n_rows, uint32_t ploidy) : win_step0(win_rows.size() + 1, 0), stride(ploidy + 1)
+    // keep_per_window: window wi's chains use keep matrix wi (a genotype list per window); else one matrix serves all
+    StepArrays(const std::vector<std::vector<uint32_t>>& win_rows, size_t n_rows, uint32_t ploidy, bool keep_per_window = false)
+        : win_step0(win_rows.size() + 1, 0), stride(ploidy + 1)
     {
         for (size_t wi = 0; wi < win_rows.size(); ++wi) win_step0[wi + 1] = win_step0[wi] + 2 * win_rows[wi].size();
         n_steps = win_step0.back();
@@ -2168,8 +2187,9 @@ struct Genotyper::StepArrays {
         for (size_t wi = 0; wi < win_rows.size(); ++wi) {
             const size_t m = win_rows[wi].size();
             if (!m) continue;
-            chains.push_back(vgmi_hmm_chain{win_step0[wi], m, 0, 0});
-            chains.push_back(vgmi_hmm_chain{win_step0[wi] + m, m, 0, 0});
+            const uint32_t keep_index = keep_per_window ? (uint32_t)wi : 0u;
+            chains.push_back(vgmi_hmm_chain{win_step0[wi], m, keep_index, 0});
+            chains.push_back(vgmi_hmm_chain{win_step0[wi] + m, m, keep_index, 0});
         }
     }
     void fill(size_t wi, const std::vector<Seen>& seen, uint16_t population)      // (libm: a window per thread)
@@ -2504,6 +2524,41 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
 // device; the draws (std::mt19937, libm), the sequence checks (strings), the step tables (libm) and the genotype strings stay here.
 // A row is the range [front, back] of what is left of its node's list plus the device's alive bytes; node.kmers is pruned by the same
 // rule right after the emission launch, so that the host's lists and the device's bytes agree after every sample.
+// A polyploid sample (ploidy 3, 4) takes the same steps with another genotype list: haplotype_combinations turns every drawn haplotype into
+// the block of `ploidy` consecutive haplotypes that holds it (:846-873), so a window has 1 .. -n genotypes over up to -n x ploidy
+// haplotypes -- `used`, which the scores, the sequence checks and the strings go by -- while the prune still goes by the drawn ones.  The
+// device's recursion takes one list length per part: the windows are dealt into parts by the length of their lists (SelectedPart), each
+// with its own emission launch, keep matrix per window and 1 / n_gt.  The tallies of a polyploid call are the host's (finish_rows).
+struct Genotyper::SelectedSample {
+    float ave = 0;
+    double lower = 256.0f, upper = -0.1f;
+    uint32_t ploidy = 2, n_drawn = 0;
+    bool blocks = false;                     // polyploid: a genotype list per window
+    std::vector<long double> tab;
+    std::vector<uint8_t> pos_a, pos_b, keep_mat;      // diploid: the one shape of every window's list
+    // per window of the run
+    std::vector<std::vector<uint16_t>> win_top, win_used;      // drawn, ascending / occurring in the genotypes, ascending (diploid: the drawn ones)
+    std::vector<std::vector<std::vector<uint16_t>>> win_gts;
+    std::vector<GenotypeList> win_glist;
+    std::vector<uint8_t> win_used8;          // diploid: the drawn haplotypes as the device takes them
+    std::vector<uint64_t> win_mask;          // the drawn haplotypes
+    // what the VGH_TIMING line sums over the parts
+    size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0, n_parts = 0;
+    int64_t ns_emit = 0, ns_a = 0, ns_rows = 0, ns_b = 0, ns_calls = 0, t_last = 0;
+    const std::vector<uint16_t>& used(size_t wi) const { return blocks ? win_used[wi] : win_top[wi]; }
+    WindowHaps haps(size_t wi) const { return WindowHaps{win_top[wi], used(wi), win_gts[wi], win_glist[wi]}; }
+};
+
+// The windows of a sample whose genotype lists have `n_gt` entries, and their rows end to end (a diploid sample: every window)
+struct Genotyper::SelectedPart {
+    size_t n_gt = 0;
+    std::vector<uint32_t> wins;              // the run's windows, ascending
+    std::vector<size_t> win_row0;            // wins.size() + 1
+    std::vector<uint64_t> e_begin;
+    std::vector<uint32_t> e_count, row_win, row_node;      // row_win: a place in `wins`
+    std::vector<uint64_t> gt0;               // per row: the places of the window's `used` whose haplotype carries the reference allele
+};
+
 Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
 {
     const Run& r = s.r;
@@ -2511,24 +2566,31 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     const std::vector<Task>& tasks = s.tasks;
     const size_t n_entries = g_.node_key_index.size();
     const double tb0 = s.since_begin() * 1e-9;
-    const float ave = r.hap_cov;
-    double lower = 256.0f, upper = -0.1f;
-    poisson_interval(ave, lower, upper);
-    const uint32_t n_used = r.haploid_num;
-    std::vector<uint16_t> places(n_used);
-    std::iota(places.begin(), places.end(), (uint16_t)0);
-    const std::vector<std::vector<uint16_t>> shape = haplotype_combinations(places, cfg.sample_type, 2, (uint16_t)(n_hap_ - 1));
-    const size_t n_gt = shape.size();
-    bool pairs = n_gt >= 1 && n_gt <= 128;
-    for (const auto& gtv : shape) pairs = pairs && gtv.size() == 2;
-    if (!pairs) return Emitted::no;
-    std::vector<uint8_t> pos_a(n_gt), pos_b(n_gt);
-    for (size_t gi = 0; gi < n_gt; ++gi) {
-        pos_a[gi] = (uint8_t)shape[gi][0];
-        pos_b[gi] = (uint8_t)shape[gi][1];
+    SelectedSample ss;
+    ss.ave = r.hap_cov;
+    poisson_interval(ss.ave, ss.lower, ss.upper);
+    ss.ploidy = cfg.sample_ploidy;
+    ss.blocks = cfg.sample_ploidy > 2;
+    ss.n_drawn = r.haploid_num;
+    const uint32_t n_used = ss.n_drawn;
+    size_t n_gt = 0;      // diploid: of every window
+    if (!ss.blocks) {
+        std::vector<uint16_t> places(n_used);
+        std::iota(places.begin(), places.end(), (uint16_t)0);
+        const std::vector<std::vector<uint16_t>> shape = haplotype_combinations(places, cfg.sample_type, 2, (uint16_t)(n_hap_ - 1));
+        n_gt = shape.size();
+        bool pairs = n_gt >= 1 && n_gt <= 128;
+        for (const auto& gtv : shape) pairs = pairs && gtv.size() == 2;
+        if (!pairs) return Emitted::no;
+        ss.pos_a.resize(n_gt);
+        ss.pos_b.resize(n_gt);
+        for (size_t gi = 0; gi < n_gt; ++gi) {
+            ss.pos_a[gi] = (uint8_t)shape[gi][0];
+            ss.pos_b[gi] = (uint8_t)shape[gi][1];
+        }
+        ss.keep_mat = keep_matrix(shape);      // (places keep the haplotypes' order)
     }
-    const std::vector<uint8_t> keep_mat = keep_matrix(shape);      // (places keep the haplotypes' order)
-    const std::vector<long double> tab = emission_table(ave, 2);
+    ss.tab = emission_table(ss.ave, ss.ploidy);
     if (!entries_uploaded_) {
         device_check(dev_, vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
         entries_uploaded_ = true;
@@ -2574,8 +2636,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
         }
     }
     const std::vector<uint64_t>& e_begin = cfg.sv_only ? e_begin_sv : sup_begin;
-    const std::vector<uint32_t>&e_count = cfg.sv_only ? e_count_sv : sup_count, &row_win = cfg.sv_only ? e_win_sv : sup_win,
-                               &row_node = cfg.sv_only ? e_node_sv : sup_node;
+    const std::vector<uint32_t>&e_count = cfg.sv_only ? e_count_sv : sup_count, &row_node = cfg.sv_only ? e_node_sv : sup_node;
     const size_t n_rows = e_begin.size();
     const int64_t ta = s.since_begin();
     // 1. the support the draw is weighted by, on the device
@@ -2584,122 +2645,228 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
                  "device HMM support: ");
     const int64_t t_sup = s.since_begin();
     // 2. the draws; 3. what follows from them: the window's haplotypes and mask, its genotypes, the rows' reference-allele masks
-    std::vector<std::vector<uint16_t>> win_top(nw);
-    std::vector<std::vector<std::vector<uint16_t>>> win_gts(nw);
-    std::vector<GenotypeList> win_glist(nw);
-    std::vector<uint8_t> win_used8(nw * n_used, 0);
-    std::vector<uint64_t> win_mask(nw, 0);
-    std::vector<uint16_t> gt0(n_rows ? n_rows : 1, 0);
+    ss.win_top.resize(nw);
+    ss.win_used.resize(ss.blocks ? nw : 0);
+    ss.win_gts.resize(nw);
+    ss.win_glist.resize(nw);
+    ss.win_used8.assign(ss.blocks ? 0 : nw * n_used, 0);
+    ss.win_mask.assign(nw, 0);
+    std::vector<uint64_t> gt0(n_rows ? n_rows : 1, 0);
     over_windows(nw, s.n_threads, g_phase.select, [&](size_t wi) {
         HaplotypeSampler sampler(std::vector<uint32_t>(support.begin() + wi * n_hap_, support.begin() + (wi + 1) * n_hap_), (int)r.haploid_num);
-        std::vector<uint16_t>& top = win_top[wi];
+        std::vector<uint16_t>& top = ss.win_top[wi];
         top = sampler.top;
         std::sort(top.begin(), top.end());
         if (top.size() != n_used) throw std::runtime_error("internal: a window drew another number of haplotypes");
-        for (size_t p = 0; p < n_used; ++p) {
-            win_used8[wi * n_used + p] = (uint8_t)top[p];
-            win_mask[wi] |= 1ULL << top[p];
+        for (size_t p = 0; p < n_used; ++p) ss.win_mask[wi] |= 1ULL << top[p];
+        if (ss.blocks) {
+            ss.win_gts[wi] = haplotype_combinations(top, cfg.sample_type, ss.ploidy, (uint16_t)(n_hap_ - 1));
+            std::vector<uint16_t>& used = ss.win_used[wi];
+            for (const auto& gtv : ss.win_gts[wi]) used.insert(used.end(), gtv.begin(), gtv.end());
+            std::sort(used.begin(), used.end());
+            used.erase(std::unique(used.begin(), used.end()), used.end());
+        } else {
+            for (size_t p = 0; p < n_used; ++p) ss.win_used8[wi * n_used + p] = (uint8_t)top[p];
+            ss.win_gts[wi].resize(n_gt);
+            for (size_t gi = 0; gi < n_gt; ++gi) ss.win_gts[wi][gi] = {top[ss.pos_a[gi]], top[ss.pos_b[gi]]};
         }
-        win_gts[wi].resize(n_gt);
-        for (size_t gi = 0; gi < n_gt; ++gi) win_gts[wi][gi] = {top[pos_a[gi]], top[pos_b[gi]]};
-        win_glist[wi] = genotype_list(win_gts[wi], top);
+        const std::vector<uint16_t>& used = ss.used(wi);
+        ss.win_glist[wi] = genotype_list(ss.win_gts[wi], used);
         const Chrom& chr = *tasks[wi].chr;
         for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
             const auto& hap_gt = chr.nodes[row_node[rr]].gn->hap_gt;
-            uint16_t m = 0;
-            for (size_t p = 0; p < n_used; ++p) m |= (uint16_t)((hap_gt[top[p]] == 0) << p);
+            uint64_t m = 0;
+            for (size_t p = 0; p < used.size(); ++p) m |= (uint64_t)(hap_gt[used[p]] == 0) << p;
             gt0[rr] = m;
         }
     });
-    auto haps_of = [&](size_t wi) { return WindowHaps{win_top[wi], win_top[wi], win_gts[wi], win_glist[wi]}; };
     const int64_t t_draw = s.since_begin();
-    size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0;
-    int64_t t_emit = t_draw, t_a = t_draw, t_rows = t_draw, t_b = t_draw, t_calls = t_draw;
+    ss.t_last = t_draw;
+    // the parts: the windows by the length of their genotype lists (a diploid sample: one part)
+    std::vector<SelectedPart> parts;
+    {
+        CpuBudget::Hold cpu;
+        PhaseTimer t_list(g_phase.list);
+        std::map<size_t, size_t> part_of;      // list length -> part
+        for (size_t wi = 0; wi < nw; ++wi) {
+            const size_t len = ss.win_gts[wi].size();
+            if (len < 1 || (ss.blocks && (len > 64 || ss.used(wi).size() > 64))) throw std::runtime_error("internal: a window's genotype list the device cannot take");
+            auto it = part_of.find(len);
+            if (it == part_of.end()) {
+                it = part_of.emplace(len, parts.size()).first;
+                parts.emplace_back();
+                parts.back().n_gt = len;
+                parts.back().win_row0.push_back(0);
+            }
+            SelectedPart& pt = parts[it->second];
+            const uint32_t place = (uint32_t)pt.wins.size();
+            pt.wins.push_back((uint32_t)wi);
+            const size_t lo = win_row0[wi], hi = win_row0[wi + 1];
+            pt.e_begin.insert(pt.e_begin.end(), e_begin.begin() + lo, e_begin.begin() + hi);
+            pt.e_count.insert(pt.e_count.end(), e_count.begin() + lo, e_count.begin() + hi);
+            pt.row_node.insert(pt.row_node.end(), row_node.begin() + lo, row_node.begin() + hi);
+            pt.gt0.insert(pt.gt0.end(), gt0.begin() + lo, gt0.begin() + hi);
+            pt.row_win.insert(pt.row_win.end(), hi - lo, place);
+            pt.win_row0.push_back(pt.e_begin.size());
+        }
+    }
+    size_t n_steps = 0;
+    for (const SelectedPart& pt : parts) n_steps += selected_part(s, ss, pt);
+    s.note_device_span(ta, ss.t_last);
+    (void)n_steps;
+    if (g_phase_on) {
+        std::fprintf(stderr, "[varigraph-mi] HMM with haplotypes selected per window (%zu windows, %zu rows, %zu nodes pruned, %zu nodes scored by the host, %zu scored "
+                     "again on the device): support %.3f, draws (host) %.3f, emission kernel %.3f, prune + sequence checks (host) %.3f, rows fixed on the device %.3f, "
+                     "strings + step tables (host) %.3f, recursion + posterior %.3f\n",
+                     nw, n_rows, ss.n_pruned, ss.n_host_rows, ss.n_fixed_rows, (t_sup - ta) * 1e-9, (t_draw - t_sup) * 1e-9, ss.ns_emit * 1e-9, ss.ns_a * 1e-9,
+                     ss.ns_rows * 1e-9, ss.ns_b * 1e-9, ss.ns_calls * 1e-9);
+        std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
+                     std::max<size_t>(1, parts.size()), s.since_begin() * 1e-9 - tb0, nw, tasks.size());
+    }
+    return Emitted::yes;
+}
+
+// Steps 4 to 9 for one part; returns its steps
+size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const SelectedPart& pt)
+{
+    const Run& r = s.r;
+    const GenotypeConfig& cfg = *r.cfg;
+    const std::vector<Task>& tasks = s.tasks;
+    const size_t n_gt = pt.n_gt, nwp = pt.wins.size(), n_rows = pt.e_begin.size();
+    const float ave = ss.ave;
+    const double lower = ss.lower, upper = ss.upper;
+    const std::vector<size_t>& win_row0 = pt.win_row0;
+    const std::vector<uint32_t>& row_node = pt.row_node;
+    const int64_t t_begin = s.since_begin();
+    int64_t t_emit = t_begin, t_a = t_begin, t_rows = t_begin, t_b = t_begin, t_calls = t_begin;
     std::vector<long double> prob(n_rows ? n_rows : 1);
     std::vector<uint32_t> winner(n_rows ? n_rows : 1, 0xFFFFFFFFu);
-    std::vector<std::vector<uint32_t>> win_rows(nw);      // per window: the rows that have a score
+    std::vector<std::vector<uint32_t>> win_rows(nwp);      // per window: the rows that have a score
     size_t n_steps = 0;
     if (n_rows) {
         // 4. emission scores on the device, the prune included
         std::vector<uint32_t> n_kept(n_rows);
         std::vector<uint8_t> flags(n_rows);
         PartHandle ph;
-        device_check(dev_, vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, n_used, pos_a.data(), pos_b.data(), (uint32_t)nw, win_used8.data(), win_mask.data(),
-                                                     (uint32_t)g_.bitlen, ave, lower, upper, tab.data(), n_rows, e_begin.data(), e_count.data(), row_win.data(),
-                                                     gt0.data(), n_kept.data(), flags.data(), &ph.p),
-                     "device HMM emissions: ");
+        if (ss.blocks) {
+            // the lists by haplotype id, the rows' reference-allele masks over haplotype ids
+            std::vector<uint32_t> w_n(nwp, (uint32_t)n_gt);
+            std::vector<uint8_t> w_haps(nwp * n_gt * ss.ploidy);
+            std::vector<uint64_t> w_mask(nwp), gt0_ids(n_rows, 0);
+            for (size_t lw = 0; lw < nwp; ++lw) {
+                const size_t wi = pt.wins[lw];
+                w_mask[lw] = ss.win_mask[wi];
+                for (size_t gi = 0; gi < n_gt; ++gi)
+                    for (uint32_t q = 0; q < ss.ploidy; ++q) w_haps[(lw * n_gt + gi) * ss.ploidy + q] = (uint8_t)ss.win_gts[wi][gi][q];
+                const std::vector<uint16_t>& used = ss.win_used[wi];
+                for (size_t rr = win_row0[lw]; rr < win_row0[lw + 1]; ++rr)
+                    for (size_t p = 0; p < used.size(); ++p) gt0_ids[rr] |= ((pt.gt0[rr] >> p) & 1ull) << used[p];
+            }
+            device_check(dev_, vgmi_hmm_emissions_select_ploidy(dev_, (uint32_t)n_gt, ss.ploidy, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(),
+                                                                (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(), pt.e_count.data(),
+                                                                pt.row_win.data(), gt0_ids.data(), n_kept.data(), flags.data(), &ph.p),
+                         "device HMM emissions: ");
+        } else {
+            const std::vector<uint16_t> gt0_16(pt.gt0.begin(), pt.gt0.end());      // (<= 16 places)
+            device_check(dev_, vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, ss.n_drawn, ss.pos_a.data(), ss.pos_b.data(), (uint32_t)nwp, ss.win_used8.data(),
+                                                         ss.win_mask.data(), (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
+                                                         pt.e_count.data(), pt.row_win.data(), gt0_16.data(), n_kept.data(), flags.data(), &ph.p),
+                         "device HMM emissions: ");
+        }
         t_emit = s.since_begin();
         // 5. the same prune on the host's lists, for exactly the nodes that lost k-mers; 6. the flagged rows
-        FlaggedRows fl(nw);
+        FlaggedRows fl(nwp);
         std::atomic<size_t> pruned_nodes{0};
-        over_windows(nw, s.n_threads, g_phase.pass_a, [&](size_t wi) {
+        over_windows(nwp, s.n_threads, g_phase.pass_a, [&](size_t lw) {
+            const size_t wi = pt.wins[lw];
             Chrom& chr = *tasks[wi].chr;
-            const WindowHaps haps = haps_of(wi);
+            const WindowHaps haps = ss.haps(wi);
             std::vector<uint32_t> kept;
             FlaggedScratch sc(ave, lower, upper);
-            for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
+            for (size_t rr = win_row0[lw]; rr < win_row0[lw + 1]; ++rr) {
                 Node& node = chr.nodes[row_node[rr]];
                 if (n_kept[rr] != node.kmers.size()) {
                     kept.clear();
                     for (uint32_t pos : node.kmers)
-                        if ((r.packed[pos] >> 16) & win_mask[wi]) kept.push_back(pos);
+                        if ((r.packed[pos] >> 16) & ss.win_mask[wi]) kept.push_back(pos);
                     if (kept.size() != n_kept[rr]) throw std::runtime_error("internal: the device's k-mer lists differ from the host's");
                     node.kmers.keep(kept);
                     ++pruned_nodes;
                 }
                 if (!(flags[rr] & 1u)) continue;
-                const size_t before = fl.fix_j[wi].size();
-                flagged_row(fl, wi, rr, chr, row_node[rr], haps, gt0[rr], r, sc, n_kept[rr]);
-                // (sequence_fixes counts along the list; the device along the row's range)
-                for (size_t q = before; q < fl.fix_j[wi].size(); ++q) fl.fix_j[wi][q] = node.kmers[fl.fix_j[wi][q]] - (uint32_t)e_begin[rr];
+                const size_t before = fl.fix_j[lw].size();
+                flagged_row(fl, lw, rr, chr, row_node[rr], haps, pt.gt0[rr], r, sc, n_kept[rr]);
+                // (sequence_fixes counts along the list and over the places of `used`; the device along the row's range -- and, with a list
+                // per window, over haplotype ids)
+                for (size_t q = before; q < fl.fix_j[lw].size(); ++q) {
+                    fl.fix_j[lw][q] = node.kmers[fl.fix_j[lw][q]] - (uint32_t)pt.e_begin[rr];
+                    if (!ss.blocks) continue;
+                    uint64_t ids = 0;
+                    for (size_t p = 0; p < haps.used.size(); ++p) ids |= ((fl.fix_mask[lw][q] >> p) & 1ull) << haps.used[p];
+                    fl.fix_mask[lw][q] = ids;
+                }
             }
         });
-        n_pruned = pruned_nodes.load();
-        if (n_pruned) lists_whole_.store(false, std::memory_order_relaxed);
+        ss.n_pruned += pruned_nodes.load();
+        if (pruned_nodes.load()) lists_whole_.store(false, std::memory_order_relaxed);
         alive_stale_.store(false);      // (hidden_states above walked lists that were pruned already: nothing left them)
         t_a = s.since_begin();
-        upload_flagged(fl, ph.p);
-        n_host_rows = fl.n_host;
-        n_fixed_rows = fl.n_fixed;
+        upload_flagged(fl, ph.p, ss.blocks);
+        ss.n_host_rows += fl.n_host;
+        ss.n_fixed_rows += fl.n_fixed;
         t_rows = s.since_begin();
         // 7. the recursion's inputs: genotype strings (the window's haplotypes decide them), step tables (libm), chains
-        std::vector<std::vector<Seen>> seen(nw);
+        std::vector<std::vector<Seen>> seen(nwp);
         std::vector<uint8_t> gid(n_rows * n_gt, 0), order(n_rows * n_gt, 0);
-        over_windows(nw, s.n_threads, g_phase.pass_a, [&](size_t wi) {
-            row_strings(*tasks[wi].chr, win_row0[wi], win_row0[wi + 1], row_node.data(), gt0.data(), n_kept.data(), haps_of(wi), gid.data(), order.data(), seen[wi],
-                        win_rows[wi]);
+        over_windows(nwp, s.n_threads, g_phase.pass_a, [&](size_t lw) {
+            row_strings(*tasks[pt.wins[lw]].chr, win_row0[lw], win_row0[lw + 1], row_node.data(), pt.gt0.data(), n_kept.data(), ss.haps(pt.wins[lw]), gid.data(),
+                        order.data(), seen[lw], win_rows[lw]);
         });
-        StepArrays steps(win_rows, n_rows, 2);
+        StepArrays steps(win_rows, n_rows, ss.ploidy, ss.blocks);
         n_steps = steps.n_steps;
-        if (n_steps) over_windows(nw, s.n_threads, g_phase.pass_b, [&](size_t wi) { steps.fill(wi, seen[wi], (uint16_t)n_hap_); });
+        if (n_steps) over_windows(nwp, s.n_threads, g_phase.pass_b, [&](size_t lw) { steps.fill(lw, seen[lw], (uint16_t)n_hap_); });
         t_b = s.since_begin();
         if (n_steps) {
             const long double uniform = 1.0L / (long double)n_gt;
-            device_check(dev_, vgmi_hmm_part_calls(ph.p, 2, keep_mat.data(), 1, steps.row.data(), steps.restart.data(), steps.pw.data(), n_steps, &uniform,
-                                                   steps.chains.data(), (uint32_t)steps.chains.size(), gid.data(), order.data(), steps.fwd.data(), steps.bwd.data(),
-                                                   prob.data(), winner.data()),
+            std::vector<uint8_t> keep_all;      // a list per window: a keep matrix per window
+            if (ss.blocks) {
+                keep_all.reserve(nwp * n_gt * n_gt);
+                for (size_t lw = 0; lw < nwp; ++lw) {
+                    const std::vector<uint8_t> km = keep_matrix(ss.win_gts[pt.wins[lw]]);
+                    keep_all.insert(keep_all.end(), km.begin(), km.end());
+                }
+            }
+            device_check(dev_, vgmi_hmm_part_calls(ph.p, ss.ploidy, ss.blocks ? keep_all.data() : ss.keep_mat.data(), ss.blocks ? (uint32_t)nwp : 1u, steps.row.data(),
+                                                   steps.restart.data(), steps.pw.data(), n_steps, &uniform, steps.chains.data(), (uint32_t)steps.chains.size(),
+                                                   gid.data(), order.data(), steps.fwd.data(), steps.bwd.data(), prob.data(), winner.data()),
                          "device HMM recursion: ");
         }
         t_calls = s.since_begin();
     }
-    s.note_device_span(ta, t_calls);
-    // 8. the calls' tallies on the device (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists)
+    ss.ns_emit += t_emit - t_begin;
+    ss.ns_a += t_a - t_emit;
+    ss.ns_rows += t_rows - t_a;
+    ss.ns_b += t_b - t_rows;
+    ss.ns_calls += t_calls - t_b;
+    ss.t_last = t_calls;
+    // 8. the calls' tallies on the device, a diploid sample's (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists)
     std::vector<uint32_t> tally;
     std::vector<uint8_t> tally_uniq;
     static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
-    if (device_tallies && n_steps) {
+    if (device_tallies && n_steps && !ss.blocks) {
         tally.resize(4 * n_rows);
         tally_uniq.resize(n_rows);
-        device_check(dev_, vgmi_hmm_tallies_select(dev_, n_rows, e_begin.data(), e_count.data(), row_win.data(), winner.data(), (uint32_t)n_gt, pos_a.data(),
-                                                   pos_b.data(), n_used, (uint32_t)nw, win_used8.data(), tally.data(), tally_uniq.data()),
+        device_check(dev_, vgmi_hmm_tallies_select(dev_, n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(), (uint32_t)n_gt, ss.pos_a.data(),
+                                                   ss.pos_b.data(), ss.n_drawn, (uint32_t)nwp, ss.win_used8.data(), tally.data(), tally_uniq.data()),
                      "device tallies: ");
     }
     // 9. the lines
-    over_windows(nw, s.n_threads, g_phase.pass_c, [&](size_t wi) {
-        s.emit_windows_done += !win_rows[wi].empty();
+    over_windows(nwp, s.n_threads, g_phase.pass_c, [&](size_t lw) {
+        const size_t wi = pt.wins[lw];
+        s.emit_windows_done += !win_rows[lw].empty();
         const Chrom& chr = *tasks[wi].chr;
         if (tally.empty()) {
-            finish_rows(tasks[wi].chr, win_rows[wi], row_node.data(), haps_of(wi), prob.data(), winner.data(), r);
+            finish_rows(tasks[wi].chr, win_rows[lw], row_node.data(), ss.haps(wi), prob.data(), winner.data(), r);
             write_piece(s, wi);
             return;
         }
@@ -2708,26 +2875,17 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
         if (vc == g_.vcf_info.end()) return;
         SiteWalk walk(vc->second);
         std::string out;
-        for (const uint32_t rw : win_rows[wi]) {
+        for (const uint32_t rw : win_rows[lw]) {
             const Node& node = chr.nodes[row_node[rw]];
             const std::vector<std::string>* fields = walk.at(node.start);
             if (winner[rw] >= n_gt) continue;            // no entry with a positive posterior: no call
-            const std::vector<uint16_t>& called = win_gts[wi][winner[rw]];
+            const std::vector<uint16_t>& called = ss.win_gts[wi][winner[rw]];
             append_tally_line(out, node.gn->hap_gt[called[0]], node.gn->hap_gt[called[1]], prob[rw], &tally[4 * rw], tally_uniq[rw], cfg.min_gq,
                               [&](std::string& o) { return append_site_head(o, fields); });
         }
         s.pieces[wi] = std::move(out);
     });
-    if (g_phase_on) {
-        std::fprintf(stderr, "[varigraph-mi] HMM with haplotypes selected per window (%zu windows, %zu rows, %zu nodes pruned, %zu nodes scored by the host, %zu scored "
-                     "again on the device): support %.3f, draws (host) %.3f, emission kernel %.3f, prune + sequence checks (host) %.3f, rows fixed on the device %.3f, "
-                     "strings + step tables (host) %.3f, recursion + posterior %.3f\n",
-                     nw, n_rows, n_pruned, n_host_rows, n_fixed_rows, (t_sup - ta) * 1e-9, (t_draw - t_sup) * 1e-9, (t_emit - t_draw) * 1e-9, (t_a - t_emit) * 1e-9,
-                     (t_rows - t_a) * 1e-9, (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
-        std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: 1 parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
-                     s.since_begin() * 1e-9 - tb0, nw, tasks.size());
-    }
-    return Emitted::yes;
+    return n_steps;
 }
 
 std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const std::string& sample_name,
@@ -2757,7 +2915,11 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
     s.piece_done.assign(s.tasks.size(), 0);
 
     std::vector<WindowWork> works;
-    const DevicePaths paths = device_paths(r, s.tasks, works);
+    // (VGH_HMM_FAKE_NOMEM: as if the device had no room for the first sample of a run whose haplotypes are selected per window -- it takes
+    // the pool, the host prunes its lists, and the next sample has to start from those)
+    const bool refuse_select = getenv("VGH_HMM_FAKE_NOMEM") != nullptr && samples_run_ == 0;
+    ++samples_run_;
+    const DevicePaths paths = device_paths(r, s.tasks, works, refuse_select);
     WindowBuffers bufs;
     if (paths.pool_device) {
         bufs.allocate(paths.total_room, paths.n_gt, cfg.sample_ploidy);

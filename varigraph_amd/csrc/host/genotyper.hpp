@@ -160,13 +160,16 @@ private:
     void fill_packed(Run& r, uint32_t threads);
     void reset_calls();
     std::vector<Task> windows(const GenotypeConfig& cfg);
-    DevicePaths device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works) const;
+    DevicePaths device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works, bool refuse_select) const;
     // the three ways through the HMM.  On the pool: window() prepares every window on the host, recursion and posterior go to the device
     // in parts or stay here.  The other two score the emissions on the device as well: with every haplotype of the panel selected (one
-    // genotype list per sample, per-part cache and plan), or with the haplotypes drawn per window (-n below the panel, diploid)
+    // genotype list per sample, per-part cache and plan), or with the haplotypes drawn per window (-n below the panel, ploidy 2 .. 4)
     void hmm_on_pool(RunShared& s, std::vector<WindowWork>& works, const WindowBuffers& bufs, size_t n_gt);
     Emitted hmm_whole_panel(RunShared& s);
     Emitted hmm_selected(RunShared& s);
+    struct SelectedSample;   // haplotypes drawn per window: the sample's constants, every window's haplotypes and genotype list
+    struct SelectedPart;     // ... and the windows whose lists have one length, with their rows
+    size_t selected_part(RunShared& s, SelectedSample& ss, const SelectedPart& pt);
     void write_piece(RunShared& s, size_t t);      // the VCF lines of a window from its nodes' calls
     // whole-panel emissions, per part of the windows
     struct EmitPartCache;
@@ -179,15 +182,17 @@ private:
     const SiteMap& vcf_sites(const Chrom& chr) const;      // throws for a chromosome the VCF lacks
     static bool skipped(const Chrom& chr, const SiteMap& sites, const Node& n, bool sv_only);      // not the HMM's business
     static GenotypeList genotype_list(const std::vector<std::vector<uint16_t>>& genotypes, const std::vector<uint16_t>& used);
-    void flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint16_t gt0, const Run& r,
+    void flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint64_t gt0, const Run& r,
                      FlaggedScratch& sc, uint32_t& n_kept);
-    void upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part);
+    // by_hap_id: the part has a genotype list per window and fl's masks are over haplotype ids (vgmi_hmm_part_fix_rows_wide)
+    void upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap_id = false);
     // a node the HMM works on, in window order; at: where its scores are (a place in the window or a row of the part), -1: it has none
     struct Seen { uint32_t start, end; int64_t at; };
     struct StepArrays;
     static void step_tables(const std::vector<Seen>& seen, uint32_t stride, uint16_t population, size_t step0, size_t row_base, long double* pw,
                             uint32_t* row, uint8_t* restart, uint64_t* fwd, uint64_t* bwd);
-    void row_strings(const Chrom& chr, size_t row_lo, size_t row_hi, const uint32_t* row_node, const uint16_t* gt0, const uint32_t* n_kept, const WindowHaps& h,
+    template <class Mask>
+    void row_strings(const Chrom& chr, size_t row_lo, size_t row_hi, const uint32_t* row_node, const Mask* gt0, const uint32_t* n_kept, const WindowHaps& h,
                      uint8_t* gid, uint8_t* order, std::vector<Seen>& seen, std::vector<uint32_t>& scored_rows) const;
     void finish_rows(Chrom* chr, const std::vector<uint32_t>& rows, const uint32_t* row_node, const WindowHaps& h, const long double* prob,
                      const uint32_t* winner, const Run& r);
@@ -208,8 +213,8 @@ private:
                              const Node* ahead);
     // what the haplotypes' sequences say about a node's under-covered multi-copy k-mers (src/genotype.cpp:760-800), as the entries
     // of the node's list that lose haplotypes (bits over `used`): for the device's second emission launch (vgmi_hmm_part_fix_rows)
-    void sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vector<uint16_t>& used, uint16_t gt0_mask, double lower, double upper,
-                        const Run& r, std::vector<uint32_t>& fix_j, std::vector<uint16_t>& fix_mask) const;
+    void sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vector<uint16_t>& used, uint64_t gt0_mask, double lower, double upper,
+                        const Run& r, std::vector<uint32_t>& fix_j, std::vector<uint64_t>& fix_mask) const;
     std::pair<std::string, std::string> flanks(const Chrom& chr, uint32_t node_i, uint16_t hap, uint16_t alt_gt,
                                                std::string& alt_seq, uint32_t want) const;
     void posterior(Node& n, const std::vector<uint16_t>& top, const Run& r) const;
@@ -251,6 +256,7 @@ private:
     // the host pruned a k-mer list on its own since the device last had the lists' state (vgmi_hmm_alive_upload): a sample whose
     // haplotypes are selected per window on the device uploads the lists first
     std::atomic<bool> alive_stale_{false};
+    size_t samples_run_ = 0;
     bool emit_device_off_ = false;          // the device's emission path turned out not to apply to this graph
     std::vector<uint64_t> packed_;    // per node-list entry: coverage (this sample) | multiplicity << 8 | haplotype bits << 16
 };

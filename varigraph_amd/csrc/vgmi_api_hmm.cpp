@@ -213,6 +213,9 @@ struct vgmi_hmm_part {
     uint8_t* d_small = nullptr;
     size_t small_bytes = 0;
     std::vector<uint32_t> entry_count;      // (host copy: fix_j is checked against it)
+    // a part of vgmi_hmm_emissions_select_ploidy (a genotype list per window): its launch, for vgmi_hmm_part_fix_rows_wide
+    bool per_window_lists = false;
+    HmmEmitWinParams emit_win{};
 };
 
 int vgmi_hmm_entries_upload(vgmi_ctx* c, const uint64_t* entries, size_t n)
@@ -498,6 +501,7 @@ int vgmi_hmm_part_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows
     if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
     vgmi_ctx* c = part->c;
     if (n == 0) return VGMI_OK;
+    if (part->per_window_lists) return fail(c, VGMI_E_INVALID, "HMM emissions: this part's fixes are masks over haplotype ids (vgmi_hmm_part_fix_rows_wide)");
     const uint32_t n_fix = fix_off[n];
     if (n_fix && (!fix_j || !fix_mask)) return VGMI_E_INVALID;
     for (uint64_t r = 0; r < n; ++r) {
@@ -525,6 +529,154 @@ int vgmi_hmm_part_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows
         P.fix_j = reinterpret_cast<const uint32_t*>(d + o_j);
         P.fix_mask = reinterpret_cast<const uint16_t*>(d + o_m);
         e = launch_hmm_emissions(P, n, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (st) (void)hipStreamDestroy(st);
+    hmm_block_give(c, d, d_bytes);
+    HIPCHK(c, e);
+    return VGMI_OK;
+}
+
+// ---- emission scores with a genotype LIST per window (-n below the panel's haplotypes, a polyploid sample) -----------------------------
+// replaces what vgmi_hmm_emissions_select replaces, for the genotype lists of src/genotype.cpp:846-873: per drawn haplotype the block of
+// `ploidy` consecutive haplotypes that holds it, so 1 .. -n genotypes, another number in every window, over haplotypes that were not all
+// drawn.  Window w has win_n_gt[w] <= n_gt genotypes, genotype g of it the haplotype ids win_haps[(w * n_gt + g) * ploidy ..]; the prune is
+// by win_top_mask[w] (the drawn haplotypes), the scores are over the genotypes' haplotypes; gt0 and the fixes are masks over haplotype ids.
+int vgmi_hmm_emissions_select_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_windows, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                     const uint64_t* win_top_mask, uint32_t bit_len, float ave, double lower, double upper, const void* tables,
+                                     uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint64_t* gt0,
+                                     uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    if (!c || !tables || !out) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 4 || bit_len < 1 || bit_len > 6)
+        return fail(c, VGMI_E_INVALID, "HMM emissions: 1..64 genotypes of 2..4 haplotypes per window, 1..6 bytes of haplotype bits");
+    if (n_windows < 1 || !win_n_gt || !win_haps || !win_top_mask) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their genotype lists");
+    if (n_rows && (!entry_begin || !entry_count || !row_win || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
+    if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
+    const uint64_t hap_bits = (1ull << (8 * bit_len - 1)) - 1ull;      // the last bit is no haplotype
+    std::vector<uint64_t> used_mask(n_windows, 0);
+    for (uint32_t w = 0; w < n_windows; ++w) {
+        if (win_n_gt[w] < 1 || win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM emissions: a window's genotype count outside 1..n_gt");
+        for (size_t i = 0; i < (size_t)win_n_gt[w] * ploidy; ++i) {
+            const uint8_t hap = win_haps[(size_t)w * n_gt * ploidy + i];
+            if (hap >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype's haplotype outside the haplotype bits");
+            used_mask[w] |= 1ull << hap;
+        }
+        if (win_top_mask[w] & ~hap_bits) return fail(c, VGMI_E_INVALID, "HMM emissions: a drawn haplotype outside the haplotype bits");
+    }
+    if (int rc = hmm_check_rows(c, "HMM emissions: a row outside the entries or the windows", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    *out = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto* part = new vgmi_hmm_part;
+    part->c = c;
+    part->n_rows = n_rows;
+    part->n_gt = n_gt;
+    part->per_window_lists = true;
+    const size_t b_obs = (size_t)(n_rows ? n_rows : 1) * n_gt * 16, n_tab = (size_t)(ploidy + 1) * 256, b_haps = (size_t)n_windows * n_gt * ploidy;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // entry_begin | entry_count | gt0 | tables | n_kept | flags | row_win | win_n_gt | win_haps | win_top_mask | win_used_mask
+    const size_t o_eb = 0, o_ec = up(o_eb + n_rows * 8), o_g0 = up(o_ec + n_rows * 4), o_tab = up(o_g0 + n_rows * 8), o_nk = up(o_tab + n_tab * 16),
+                 o_fl = up(o_nk + n_rows * 4), o_rw = up(o_fl + n_rows), o_wn = up(o_rw + n_rows * 4), o_wh = up(o_wn + (size_t)n_windows * 4),
+                 o_wm = up(o_wh + b_haps), o_wu = up(o_wm + (size_t)n_windows * 8), total = up(o_wu + (size_t)n_windows * 8) + 256;
+    size_t small_bytes = 0;
+    part->d_obs = hmm_block_take(c, b_obs, part->obs_bytes);
+    uint8_t* d_small = hmm_block_take(c, total, small_bytes);
+    if (!part->d_obs || !d_small) {
+        hmm_block_give(c, part->d_obs, part->obs_bytes);
+        hmm_block_give(c, d_small, small_bytes);
+        delete part;
+        return fail(c, VGMI_E_NOMEM, "HMM emissions: not enough device memory");
+    }
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(d_small + o_eb, entry_begin, n_rows * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(d_small + o_ec, entry_count, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(d_small + o_g0, gt0, n_rows * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_tab, tables, n_tab * 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(d_small + o_rw, row_win, n_rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_wn, win_n_gt, (size_t)n_windows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_wh, win_haps, b_haps, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_wm, win_top_mask, (size_t)n_windows * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_small + o_wu, used_mask.data(), (size_t)n_windows * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        HmmEmitWinParams P{};
+        P.packed = c->d_hmm_entries;
+        P.cov = c->d_hmm_cov;
+        P.alive = c->d_hmm_alive;
+        P.entry_begin = reinterpret_cast<const uint64_t*>(d_small + o_eb);
+        P.entry_count = reinterpret_cast<const uint32_t*>(d_small + o_ec);
+        P.row_win = reinterpret_cast<const uint32_t*>(d_small + o_rw);
+        P.gt0 = reinterpret_cast<const unsigned long long*>(d_small + o_g0);
+        P.n_gt = n_gt;
+        P.ploidy = ploidy;
+        P.bl8 = 8 * bit_len;
+        P.ave = ave;
+        P.lower = lower;
+        P.upper = upper;
+        P.tables = d_small + o_tab;
+        P.win_n_gt = reinterpret_cast<const uint32_t*>(d_small + o_wn);
+        P.win_haps = d_small + o_wh;
+        P.win_top_mask = reinterpret_cast<const unsigned long long*>(d_small + o_wm);
+        P.win_used_mask = reinterpret_cast<const unsigned long long*>(d_small + o_wu);
+        P.obs = part->d_obs;
+        P.n_kept = reinterpret_cast<uint32_t*>(d_small + o_nk);
+        P.flags = d_small + o_fl;
+        P.n_items = n_rows;
+        e = launch_hmm_emissions_win(P, st);
+        part->emit_win = P;
+    }
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(n_kept_out, d_small + o_nk, n_rows * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(flags_out, d_small + o_fl, n_rows, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (st) (void)hipStreamDestroy(st);
+    if (e != hipSuccess) {
+        hmm_block_give(c, d_small, small_bytes);
+        hmm_block_give(c, part->d_obs, part->obs_bytes);
+        delete part;
+        HIPCHK(c, e);
+    }
+    part->d_small = d_small;
+    part->small_bytes = small_bytes;
+    part->entry_count.assign(entry_count, entry_count + n_rows);
+    *out = part;
+    return VGMI_OK;
+}
+
+// vgmi_hmm_part_fix_rows for such a part: fix_mask[i] holds the haplotype IDS entry fix_j[i] loses
+int vgmi_hmm_part_fix_rows_wide(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const uint32_t* fix_off, const uint32_t* fix_j, const uint64_t* fix_mask)
+{
+    if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
+    vgmi_ctx* c = part->c;
+    if (n == 0) return VGMI_OK;
+    if (!part->per_window_lists) return fail(c, VGMI_E_INVALID, "HMM emissions: this part's fixes are masks over the `used` list (vgmi_hmm_part_fix_rows)");
+    const uint32_t n_fix = fix_off[n];
+    if (n_fix && (!fix_j || !fix_mask)) return VGMI_E_INVALID;
+    for (uint64_t r = 0; r < n; ++r) {
+        if (rows[r] >= part->n_rows || fix_off[r] > fix_off[r + 1]) return fail(c, VGMI_E_INVALID, "HMM emissions: a fixed row outside the part");
+        for (uint32_t i = fix_off[r]; i < fix_off[r + 1]; ++i)
+            if (fix_j[i] >= part->entry_count[rows[r]] || (i > fix_off[r] && fix_j[i] <= fix_j[i - 1]))
+                return fail(c, VGMI_E_INVALID, "HMM emissions: a row's fixes must name its entries in ascending order");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_off = up(n * 8), o_j = up(o_off + (n + 1) * 4), o_m = up(o_j + (size_t)n_fix * 4), total = up(o_m + (size_t)n_fix * 8) + 256;
+    size_t d_bytes = 0;
+    uint8_t* d = hmm_block_take(c, total, d_bytes);
+    if (!d) return fail(c, VGMI_E_NOMEM, "HMM emissions: not enough device memory");
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, rows, n * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, fix_off, (n + 1) * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_fix) e = hipMemcpyAsync(d + o_j, fix_j, (size_t)n_fix * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_fix) e = hipMemcpyAsync(d + o_m, fix_mask, (size_t)n_fix * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        HmmEmitWinParams P = part->emit_win;
+        P.n_items = n;
+        P.fix_rows = reinterpret_cast<const uint64_t*>(d);
+        P.fix_off = reinterpret_cast<const uint32_t*>(d + o_off);
+        P.fix_j = reinterpret_cast<const uint32_t*>(d + o_j);
+        P.fix_mask = reinterpret_cast<const unsigned long long*>(d + o_m);
+        e = launch_hmm_emissions_win(P, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (st) (void)hipStreamDestroy(st);

@@ -541,6 +541,91 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     }
 }
 
+// ---- ... with a genotype LIST per window (vgmi_hmm_emissions_select_ploidy): a polyploid sample under -n ----------------------------
+// The genotypes of a window are the blocks of `ploidy` consecutive haplotypes that hold a drawn haplotype (src/genotype.cpp:846-873): 1 ..
+// -n of them, another number in every window, over up to -n x ploidy haplotypes of which only the drawn ones decide the prune.  So
+// nothing is a place in a 16-entry `used` list here: genotype g of window w names its haplotypes by id (win_haps), and every mask -- the
+// drawn haplotypes (the prune), the blocks' haplotypes (who counts as carrying), the row's reference-allele bits, a fix -- is 64 bits over
+// haplotype ids.  Which haplotypes carry an entry is then two mask operations for the whole wavefront instead of a loop over places, and
+// a lane's copy number is the sum over its `ploidy` ids with repeats (haplotype 0 stands several times in a truncated or all-zero block
+// and counts each time, as the host's flat list does).
+// A wavefront takes a row: the lists are 1 .. 16 genotypes long, a second wavefront per row would idle entirely; lanes beyond the window's
+// count idle through the entry loop (and write a zero score: the part's rows are n_gt wide).  Every decision about an entry -- dead,
+// pruned, flagged, fixed -- is the same for the whole wavefront: the row is made wavefront-uniform (readfirstlane), so the entry's word,
+// coverage and alive byte are scalar loads and the branches are uniform.  The term tables, (ploidy + 1) x 256 entries of 12 bytes, are
+// staged in LDS once per workgroup of four wavefronts, which takes kWinRows rows: a workgroup per row (the kernel above) would spend more
+// on staging 15 KB than on a list of some fifty entries.
+constexpr uint32_t kWinRows = 16;
+__global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams P)
+{
+    __shared__ uint64_t s_tm[1280];
+    __shared__ int32_t s_te[1280];
+    for (uint32_t i = threadIdx.x; i < (P.ploidy + 1u) * 256u; i += 256u) {
+        const VgN80 t = n80_from(x80_load(P.tables + (size_t)i * 16));
+        s_tm[i] = t.m;
+        s_te[i] = t.e;
+    }
+    __syncthreads();      // (the only one: from here on the wavefronts go their own ways)
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = threadIdx.x & 63u;
+    for (uint32_t k = wave; k < kWinRows; k += 4u) {
+        const uint64_t item = (uint64_t)blockIdx.x * kWinRows + k;
+        if (item >= P.n_items) break;
+        const uint64_t rowi = P.fix_rows ? P.fix_rows[item] : item;
+        uint32_t fp = P.fix_rows ? P.fix_off[item] : 0u;
+        const uint32_t fe = P.fix_rows ? P.fix_off[item + 1] : 0u;
+        const uint64_t e0 = P.entry_begin[rowi];
+        const uint32_t cnt = P.entry_count[rowi];
+        const unsigned long long gt0 = P.gt0[rowi];
+        const uint32_t w = P.row_win[rowi];
+        const unsigned long long top_mask = P.win_top_mask[w], used_mask = P.win_used_mask[w];
+        const uint32_t n_here = P.win_n_gt[w];
+        const bool active = g < n_here;
+        uint32_t hap[4] = {0, 0, 0, 0};
+        if (active)
+            for (uint32_t q = 0; q < P.ploidy; ++q) hap[q] = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
+        VgN80 prod;
+        prod.m = 1ULL << 63;      // 1.0L
+        prod.e = VG_X80_BIAS;
+        uint32_t kept = 0, flag = 0;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            if (P.alive[e0 + j] == 0) continue;      // pruned by an earlier window's or sample's selection
+            const unsigned long long word = P.packed[e0 + j];
+            const uint32_t c = P.cov[e0 + j], f = (uint32_t)(word >> 8) & 0xFFu;
+            const unsigned long long bits = word >> 16;
+            const uint32_t lb = (uint32_t)(bits >> (P.bl8 - 1u)) & 1u;
+            if ((bits & top_mask) == 0) {
+                if (g == 0 && !P.fix_rows) P.alive[e0 + j] = 0;      // the prune: by the DRAWN haplotypes
+                continue;
+            }
+            ++kept;
+            const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
+            unsigned long long om = (bits | (in_interval ? gt0 : 0ull)) & used_mask;      // the score: over the BLOCKS' haplotypes
+            if ((double)c < P.lower && f >= 2u && om != 0) flag |= 1u;
+            if (fp < fe && P.fix_j[fp] == j) {      // (the second launch: haplotypes whose sequence does not hold this k-mer do not carry it)
+                om &= ~P.fix_mask[fp];
+                ++fp;
+            }
+            if (!active) continue;
+            const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
+            uint32_t h = (uint32_t)((om >> hap[0]) & 1ull) + (uint32_t)((om >> hap[1]) & 1ull);
+            if (P.ploidy > 2u) h += (uint32_t)((om >> hap[2]) & 1ull);
+            if (P.ploidy > 3u) h += (uint32_t)((om >> hap[3]) & 1ull);
+            const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
+            const uint32_t ti = h * 256u + cc;
+            VgN80 t;
+            t.m = s_tm[ti];
+            t.e = s_te[ti];
+            prod = n80_mul(prod, t);
+        }
+        if (active) x80_store(P.obs + (rowi * P.n_gt + g) * 16, n80_to(prod));
+        else if (g < P.n_gt) *reinterpret_cast<uint4*>(P.obs + (rowi * P.n_gt + g) * 16) = make_uint4(0, 0, 0, 0);
+        if (g == 0 && !P.fix_rows) {
+            P.n_kept[rowi] = kept;
+            P.flags[rowi] = (uint8_t)flag;
+        }
+    }
+}
+
 // rows the host scored itself, handed in as one block: row[i] of the part <- src[i]
 __global__ __launch_bounds__(128) void hmm_scatter_rows_kernel(uint8_t* obs, const uint64_t* rows, const uint8_t* src, uint32_t n_gt)
 {
@@ -691,6 +776,15 @@ hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStre
     } else {
         hipLaunchKernelGGL(hmm_emissions_kernel<false>, dim3((uint32_t)n_rows), dim3(128), 0, st, P);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_hmm_emissions_win(const HmmEmitWinParams& P, hipStream_t st)
+{
+    if (P.n_items == 0) return hipSuccess;
+    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 4 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hmm_emissions_win_kernel, dim3((uint32_t)((P.n_items + kWinRows - 1) / kWinRows)), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 

@@ -294,6 +294,36 @@ struct HmmEmitParams {
     uint8_t* alive;
 };
 hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStream_t st);
+// ... with a genotype list per window (a polyploid sample under -n: vgmi_hmm_emissions_select_ploidy).  Window w has win_n_gt[w] <= n_gt
+// genotypes; genotype g of it is the `ploidy` haplotype IDS win_haps[(w * n_gt + g) * ploidy ..] (repeats count each time).  Every mask is
+// 64 bits over haplotype ids (up to 8 * bitlen - 2): win_top_mask the drawn haplotypes (the prune), win_used_mask the genotypes'
+// haplotypes (who counts as carrying an entry), gt0 the row's haplotypes with the reference allele, fix_mask what an entry loses.
+struct HmmEmitWinParams {
+    const unsigned long long* packed;
+    const uint8_t* cov;
+    uint8_t* alive;
+    const uint64_t* entry_begin;        // per row
+    const uint32_t* entry_count;
+    const uint32_t* row_win;
+    const unsigned long long* gt0;
+    uint32_t n_gt, ploidy, bl8;         // the width of a row of scores (<= 64), haplotypes per genotype (2 .. 4), 8 * bitlen
+    float ave;
+    double lower, upper;
+    const uint8_t* tables;              // (ploidy + 1) x 256 16-byte long doubles
+    const uint32_t* win_n_gt;           // per window
+    const uint8_t* win_haps;
+    const unsigned long long* win_top_mask;
+    const unsigned long long* win_used_mask;
+    uint8_t* obs;                       // out, per row: n_gt scores (zero beyond the window's count)
+    uint32_t* n_kept;
+    uint8_t* flags;                     // out, per row: bit 0 as in HmmEmitParams
+    uint64_t n_items;                   // rows of this launch: all of them, or the fix_rows
+    const uint64_t* fix_rows;           // the second launch (null in the first): item i scores row fix_rows[i] again
+    const uint32_t* fix_off;
+    const uint32_t* fix_j;
+    const unsigned long long* fix_mask;
+};
+hipError_t launch_hmm_emissions_win(const HmmEmitWinParams& P, hipStream_t st);
 // selection support of every window (src/genotype.cpp:500-560): support[w * n_hap + hap] += c over the alive entries of the window's rows
 // with c > 1 and multiplicity <= 1 whose bit `hap` is set; `support` is zeroed by the caller
 hipError_t launch_hmm_support(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,

@@ -97,6 +97,9 @@ def load_library():
         "vgmi_hmm_support": (i32, [vp, u32, u32, C.c_uint64, vp, vp, vp, vp]),
         "vgmi_hmm_emissions_select": (i32, [vp, u32, u32, vp, vp, u32, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
                                             vp, vp, C.POINTER(vp)]),
+        "vgmi_hmm_emissions_select_ploidy": (i32, [vp, u32, u32, u32, vp, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
+                                                   vp, vp, C.POINTER(vp)]),
+        "vgmi_hmm_part_fix_rows_wide": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
         "vgmi_hmm_tallies_select": (i32, [vp, C.c_uint64, vp, vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
         "vgmi_hmm_part_set_rows": (i32, [vp, C.c_uint64, vp, vp]),
         "vgmi_hmm_part_fix_rows": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
@@ -656,6 +659,38 @@ class Context:
             if fixes is not None:
                 f_rows, f_off, f_j, f_m = (np.ascontiguousarray(a, dtype=t) for a, t in zip(fixes, (np.uint64, np.uint32, np.uint32, np.uint16)))
                 self._chk(self._l.vgmi_hmm_part_fix_rows(part, f_rows.size, _ptr(f_rows), _ptr(f_off), _ptr(f_j), _ptr(f_m)))
+            obs = np.zeros((n_rows, n_gt), dtype=np.longdouble)
+            self._chk(self._l.vgmi_hmm_part_fetch(part, _ptr(obs)))
+        finally:
+            self._l.vgmi_hmm_part_free(part)
+        return obs, n_kept[:n_rows], flags[:n_rows]
+
+    def hmm_emissions_select_ploidy(self, ploidy, win_n_gt, win_haps, win_top_mask, bit_len, ave, lower, upper, tables, entry_begin, entry_count, row_win,
+                                    gt0, fixes=None):
+        """vgmi_hmm_emissions_select_ploidy (+ _part_fix_rows_wide) + _part_fetch: a genotype list per window.  win_haps: (n_windows, n_gt,
+        ploidy) haplotype ids, win_n_gt how many genotypes of each window count; gt0 and the fixes' masks are 64 bits over haplotype ids.
+        Returns (obs (rows, n_gt) longdouble, n_kept, flags)."""
+        win_n_gt = np.ascontiguousarray(win_n_gt, dtype=np.uint32)
+        win_haps = np.ascontiguousarray(win_haps, dtype=np.uint8)
+        win_top_mask = np.ascontiguousarray(win_top_mask, dtype=np.uint64)
+        tables = np.ascontiguousarray(tables, dtype=np.longdouble)
+        entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
+        entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
+        row_win = np.ascontiguousarray(row_win, dtype=np.uint32)
+        gt0 = np.ascontiguousarray(gt0, dtype=np.uint64)
+        assert win_haps.ndim == 3 and win_haps.shape[2] == ploidy and tables.size == 256 * (ploidy + 1)
+        assert win_n_gt.size == win_haps.shape[0] == win_top_mask.size
+        n_rows, n_gt = entry_begin.size, win_haps.shape[1]
+        n_kept = np.zeros(max(n_rows, 1), dtype=np.uint32)
+        flags = np.zeros(max(n_rows, 1), dtype=np.uint8)
+        part = C.c_void_p()
+        self._chk(self._l.vgmi_hmm_emissions_select_ploidy(self._h, n_gt, ploidy, win_haps.shape[0], _ptr(win_n_gt), _ptr(win_haps), _ptr(win_top_mask), bit_len,
+                                                            float(ave), float(lower), float(upper), _ptr(tables), n_rows, _ptr(entry_begin), _ptr(entry_count),
+                                                            _ptr(row_win), _ptr(gt0), _ptr(n_kept), _ptr(flags), C.byref(part)))
+        try:
+            if fixes is not None:
+                f_rows, f_off, f_j, f_m = (np.ascontiguousarray(a, dtype=t) for a, t in zip(fixes, (np.uint64, np.uint32, np.uint32, np.uint64)))
+                self._chk(self._l.vgmi_hmm_part_fix_rows_wide(part, f_rows.size, _ptr(f_rows), _ptr(f_off), _ptr(f_j), _ptr(f_m)))
             obs = np.zeros((n_rows, n_gt), dtype=np.longdouble)
             self._chk(self._l.vgmi_hmm_part_fetch(part, _ptr(obs)))
         finally:
