@@ -2,12 +2,16 @@
 `long double` arithmetic on the host (numpy.longdouble: the C type, element by element, in the reference's order of
 operations, src/genotype.cpp:1170-1380).  Emission scores down to 1e-4900 (gradual underflow), chains that restart, zero
 totals, one to four haplotypes per genotype."""
+import functools
 import itertools
+import types
 
 import numpy as np
 import pytest
 
 from varigraph_amd import vgmi
+from test_gpu_hmm_select import AVE, LOWER, UPPER, _model_emissions
+from test_gpu_hmm_select_ploidy import _model as _model_lists
 
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
@@ -640,3 +644,166 @@ def test_emission_scores_of_polyploid_genotypes_on_the_device(ploidy):
         assert n_kept[r] == counts[r], r
         assert np.array_equal(obs[r], prod), (r, int(np.argmax(obs[r] != prod)))
     assert seen_h == set(range(ploidy + 1))
+
+
+# ---- what a call leaves behind when it has nothing to do or refuses its input: the block pool, the streams, a part half made -------------
+@functools.lru_cache(maxsize=None)
+def _few_rows():
+    """Three rows of 4, 3 and 5 entries over nine haplotypes (two bytes of bits), one window: five of the haplotypes selected (15 pairs) for the
+    diploid calls, three blocks of three for the call with a genotype list per window.  Every entry is carried by a selected haplotype."""
+    rng = np.random.default_rng(31)
+    S = types.SimpleNamespace(bit_len=2, n_hap=9, ploidy=3)
+    S.counts = np.array([4, 3, 5], dtype=np.uint32)
+    S.entry_begin = np.array([0, 4, 7], dtype=np.uint64)
+    S.n_entries = 12
+    S.f = rng.choice([1, 1, 2, 3], size=S.n_entries).astype(np.uint64)
+    S.bits = rng.integers(0, 1 << S.n_hap, size=S.n_entries).astype(np.uint64) | np.uint64(1 << 4)
+    S.bits |= rng.integers(0, 2, size=S.n_entries).astype(np.uint64) << np.uint64(8 * S.bit_len - 1)
+    S.cov = rng.choice([1, 5, 14, 20, 23, 30, 60], size=S.n_entries).astype(np.uint8)
+    S.entries = (S.f << np.uint64(8)) | (S.bits << np.uint64(16))
+    S.alive = np.ones(S.n_entries, dtype=np.uint8)
+    S.alive[5] = 0
+    S.win_used = np.array([[0, 2, 4, 6, 8]], dtype=np.uint8)
+    S.mask = np.array([sum(1 << int(h) for h in S.win_used[0])], dtype=np.uint64)
+    S.pairs = list(itertools.combinations_with_replacement(range(5), 2))
+    S.pos_a, S.pos_b = [a for a, _ in S.pairs], [b for _, b in S.pairs]
+    S.gt0 = rng.integers(0, 1 << 5, size=3).astype(np.uint16)
+    S.tables = (rng.random(768).astype(LD) + LD(0.05)) * np.power(LD(10), rng.integers(-40, 1, size=768).astype(LD))
+    S.win_n = np.array([3], dtype=np.uint32)
+    S.win_haps = np.array([[[1, 2, 3], [4, 5, 6], [7, 8, 0]]], dtype=np.uint8)
+    S.win_top = np.array([(1 << 2) | (1 << 4) | (1 << 8)], dtype=np.uint64)
+    S.gt0_ids = rng.integers(0, 1 << S.n_hap, size=3, dtype=np.uint64)
+    S.tables4 = (rng.random(1024).astype(LD) + LD(0.05)) * np.power(LD(10), rng.integers(-40, 1, size=1024).astype(LD))
+    S.winner = np.array([3, 0xFFFFFFFF, 14], dtype=np.uint32)
+    return S
+
+
+def _row_call(kind, ctx, eb, ec, fixes=None):
+    """One of the five calls that take rows, through its wrapper, on rows (eb, ec) of _few_rows(): a tuple of arrays."""
+    S, n = _few_rows(), len(eb)
+    win = np.zeros(n, dtype=np.uint32)
+    if kind == "emissions":      # (uploads the entries and the coverage itself: every entry alive)
+        return ctx.hmm_emissions(S.entries, S.cov, S.win_used[0], S.pos_a, S.pos_b, int(S.mask[0]), S.bit_len, AVE, LOWER, UPPER, S.tables, eb, ec, S.gt0[:n])
+    if kind == "emissions_select":
+        return ctx.hmm_emissions_select(S.pos_a, S.pos_b, S.win_used, S.mask, S.bit_len, AVE, LOWER, UPPER, S.tables, eb, ec, win, S.gt0[:n], fixes=fixes)
+    if kind == "emissions_select_ploidy":
+        return ctx.hmm_emissions_select_ploidy(S.ploidy, S.win_n, S.win_haps, S.win_top, S.bit_len, AVE, LOWER, UPPER, S.tables4, eb, ec, win, S.gt0_ids[:n],
+                                               fixes=fixes)
+    if kind == "support":
+        return (ctx.hmm_support(S.n_hap, 1, eb, ec, win),)
+    assert kind == "tallies_select"
+    return ctx.hmm_tallies_select(eb, ec, win, S.winner[:n], S.pos_a, S.pos_b, S.win_used)
+
+
+def _row_model(kind, alive, eb, ec, fixes=None):
+    """What _row_call returns, spelled out on the host; `alive` is pruned in place where the call prunes."""
+    S, n = _few_rows(), len(eb)
+    win = np.zeros(n, dtype=np.uint32)
+    if kind == "emissions":
+        return _model_emissions(S.f, S.bits, S.cov, np.ones(S.n_entries, dtype=np.uint8), S.bit_len, S.pairs, S.win_used, S.tables, eb, ec, win, S.gt0[:n],
+                                prune=False)
+    if kind == "emissions_select":
+        return _model_emissions(S.f, S.bits, S.cov, alive, S.bit_len, S.pairs, S.win_used, S.tables, eb, ec, win, S.gt0[:n], fixes=fixes)
+    if kind == "emissions_select_ploidy":
+        return _model_lists(S.f, S.bits, S.cov, alive, S.bit_len, S.win_n, S.win_haps, S.win_top, S.tables4, eb, ec, win, S.gt0_ids[:n], fixes=fixes)
+    rows = [range(int(b), int(b) + int(c)) for b, c in zip(eb, ec)]
+    if kind == "support":
+        want = np.zeros((1, S.n_hap), dtype=np.uint32)
+        for r in rows:
+            for j in r:
+                if alive[j] and S.cov[j] > 1 and S.f[j] <= 1:
+                    want[0] += ((int(S.bits[j]) >> np.arange(S.n_hap)) & 1).astype(np.uint32) * np.uint32(S.cov[j])
+        return (want,)
+    out, uniq = np.zeros((n, 4), dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+    for i, r in enumerate(rows):
+        if S.winner[i] >= len(S.pairs):
+            continue
+        ha, hb = (int(S.win_used[0][p]) for p in S.pairs[S.winner[i]])
+        for j in r:
+            if not alive[j]:
+                continue
+            uniq[i] += S.f[j] <= 1
+            out[i] += np.array([(int(S.bits[j]) >> ha) & 1, ((int(S.bits[j]) >> ha) & 1) * int(S.cov[j]),
+                                (int(S.bits[j]) >> hb) & 1, ((int(S.bits[j]) >> hb) & 1) * int(S.cov[j])], dtype=np.uint32)
+    return out, uniq
+
+
+def _same(got, want):
+    return len(got) == len(want) and all(g.shape == w.shape and np.array_equal(g, w) for g, w in zip(got, want))
+
+
+ROW_CALLS = ["emissions", "emissions_select", "emissions_select_ploidy", "support", "tallies_select"]
+
+
+@pytest.mark.parametrize("kind", ROW_CALLS)
+def test_a_call_without_rows_returns_nothing_and_leaves_the_context_whole(kind):
+    """n_rows = 0 through each of the five calls that take rows: empty results (the support sums: all zero) and no error; a call with one
+    row on the same context afterwards gives the host arithmetic's value -- the blocks went back to the pool intact."""
+    assert np.finfo(LD).nmant == 63, "numpy.longdouble is not the x87 format here"
+    S = _few_rows()
+    ctx = vgmi.Context(0, buffer_mib=16)
+    try:
+        ctx.hmm_entries_upload(S.entries, S.cov, S.alive)
+        none = _row_call(kind, ctx, S.entry_begin[:0], S.counts[:0])
+        again = _row_call(kind, ctx, S.entry_begin[:0], S.counts[:0])
+        one = _row_call(kind, ctx, S.entry_begin[:1], S.counts[:1])
+    finally:
+        ctx.close()
+    for got in (none, again):
+        if kind == "support":
+            assert got[0].shape == (1, S.n_hap) and not got[0].any()
+        else:
+            assert all(a.size == 0 for a in got) and got[0].ndim == 2
+    want = _row_model(kind, S.alive.copy(), S.entry_begin[:1], S.counts[:1])
+    assert _same(one, want), (one, want)
+    assert any(a.any() for a in want)
+
+
+@pytest.mark.parametrize("kind", ROW_CALLS)
+def test_a_row_outside_the_entries_is_refused_on_the_host_and_the_context_serves_on(kind):
+    """A row that ends one entry behind the uploaded ones, and a row whose entry_begin + entry_count wraps 64 bits (2**64 - 1, 2), as the
+    last of two rows: each of the five calls refuses both before anything is launched (VgmiError, invalid argument), and the same
+    context then serves the valid rows with the host arithmetic's value."""
+    assert np.finfo(LD).nmant == 63, "numpy.longdouble is not the x87 format here"
+    S = _few_rows()
+    ctx = vgmi.Context(0, buffer_mib=16)
+    try:
+        ctx.hmm_entries_upload(S.entries, S.cov, S.alive)
+        for begin, count in ((S.n_entries - 2, 3), (2**64 - 1, 2)):
+            eb = np.array([0, begin], dtype=np.uint64)
+            ec = np.array([4, count], dtype=np.uint32)
+            with pytest.raises(vgmi.VgmiError) as e:
+                _row_call(kind, ctx, eb, ec)
+            assert e.value.code == vgmi.E_INVALID
+        got = _row_call(kind, ctx, S.entry_begin[:2], S.counts[:2])
+    finally:
+        ctx.close()
+    want = _row_model(kind, S.alive.copy(), S.entry_begin[:2], S.counts[:2])
+    assert _same(got, want), (got, want)
+    assert any(a.any() for a in want)
+
+
+@pytest.mark.parametrize("kind", ["emissions_select", "emissions_select_ploidy"])
+def test_a_refused_fix_leaves_the_context_whole_for_a_good_one(kind):
+    """Fixes that do not name a row's entries in ascending order are refused for a diploid part (masks over the places of the `used` list)
+    and for a part with a genotype list per window (masks over haplotype ids); the part made for them is taken apart.  A fresh part of
+    the same context then takes a correct fix: the scores are the host arithmetic's, bit for bit."""
+    assert np.finfo(LD).nmant == 63, "numpy.longdouble is not the x87 format here"
+    S = _few_rows()
+    masks = [0b00100, 0b10001] if kind == "emissions_select" else [1 << 4, (1 << 2) | (1 << 8)]
+    ctx = vgmi.Context(0, buffer_mib=16)
+    try:
+        ctx.hmm_entries_upload(S.entries, S.cov, S.alive)
+        plain = _row_call(kind, ctx, S.entry_begin, S.counts)
+        for js in ([2, 1], [1, 1]):
+            with pytest.raises(vgmi.VgmiError) as e:
+                _row_call(kind, ctx, S.entry_begin, S.counts, fixes=([0], [0, 2], js, masks))
+            assert e.value.code == vgmi.E_INVALID
+        fixed = _row_call(kind, ctx, S.entry_begin, S.counts, fixes=([0], [0, 2], [1, 2], masks))
+    finally:
+        ctx.close()
+    alive = S.alive.copy()
+    want_plain = _row_model(kind, alive, S.entry_begin, S.counts)
+    want_fixed = _row_model(kind, alive, S.entry_begin, S.counts, fixes={(0, 1): masks[0], (0, 2): masks[1]})
+    assert _same(plain, want_plain) and _same(fixed, want_fixed)
+    assert not np.array_equal(fixed[0][0], plain[0][0]) and np.array_equal(fixed[0][1:], plain[0][1:])

@@ -165,6 +165,39 @@ __global__ __launch_bounds__(64 * WAVES) void hmm_recursion_kernel(HmmParams P)
 //   with the largest post.  A zero denominator makes every post NaN on the host, which no comparison accepts: no call.
 __device__ __forceinline__ bool x80_gt(VgX80 a, VgX80 b) { return a.e > b.e || (a.e == b.e && a.m > b.m); }
 
+// what one lane does last, on the posts (s_m, s_e), the strings' sums (s_sum_m, s_sum_e) and the entries' strings (s_gid) in LDS: the
+// first maximum in string order (ord) is the call's probability, the first entry of that string with the largest post its genotype
+__device__ __forceinline__ void hmm_posterior_pick(const HmmPostParams& P, uint64_t rowi, const uint64_t* s_m, const uint32_t* s_e, const uint64_t* s_sum_m,
+                                                   const uint32_t* s_sum_e, const uint8_t* s_gid, const uint8_t* ord)
+{
+    const uint32_t n = P.n_gt;
+    VgX80 best = {0, 0};
+    uint32_t best_id = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < n && ord[k] != 0xFF; ++k) {
+        VgX80 sk;
+        sk.m = s_sum_m[ord[k]];
+        sk.e = s_sum_e[ord[k]];
+        if (best_id == 0xFFFFFFFFu || x80_gt(sk, best)) {     // the host starts from -1: the first string always enters
+            best = sk;
+            best_id = ord[k];
+        }
+    }
+    VgX80 max_post = {0, 0};
+    uint32_t win = 0xFFFFFFFFu;
+    for (uint32_t q = 0; q < n; ++q) {
+        if (s_gid[q] != best_id) continue;
+        VgX80 t;
+        t.m = s_m[q];
+        t.e = s_e[q];
+        if (x80_gt(t, max_post)) {
+            max_post = t;
+            win = q;
+        }
+    }
+    x80_store(P.prob + rowi * 16, best);
+    P.winner[rowi] = best_id == 0xFFFFFFFFu ? 0xFFFFFFFEu : win;   // 0xFFFFFFFE: no string at all
+}
+
 __global__ __launch_bounds__(128) void hmm_posterior_kernel(HmmPostParams P)
 {
     __shared__ uint64_t s_m[128];
@@ -212,34 +245,7 @@ __global__ __launch_bounds__(128) void hmm_posterior_kernel(HmmPostParams P)
     s_sum_m[g] = sum.m;
     s_sum_e[g] = sum.e;
     __syncthreads();
-    if (g == 0) {
-        const uint8_t* ord = P.order + rowi * n;
-        VgX80 best = {0, 0};
-        uint32_t best_id = 0xFFFFFFFFu;
-        for (uint32_t k = 0; k < n && ord[k] != 0xFF; ++k) {
-            VgX80 sk;
-            sk.m = s_sum_m[ord[k]];
-            sk.e = s_sum_e[ord[k]];
-            if (best_id == 0xFFFFFFFFu || x80_gt(sk, best)) {     // the host starts from -1: the first string always enters
-                best = sk;
-                best_id = ord[k];
-            }
-        }
-        VgX80 max_post = {0, 0};
-        uint32_t win = 0xFFFFFFFFu;
-        for (uint32_t q = 0; q < n; ++q) {
-            if (s_gid[q] != best_id) continue;
-            VgX80 t;
-            t.m = s_m[q];
-            t.e = s_e[q];
-            if (x80_gt(t, max_post)) {
-                max_post = t;
-                win = q;
-            }
-        }
-        x80_store(P.prob + rowi * 16, best);
-        P.winner[rowi] = best_id == 0xFFFFFFFFu ? 0xFFFFFFFEu : win;   // 0xFFFFFFFE: no string at all
-    }
+    if (g == 0) hmm_posterior_pick(P, rowi, s_m, s_e, s_sum_m, s_sum_e, s_gid, P.order + rowi * n);
 }
 
 // ---- more than 128 genotypes per window (`-n` > 15 on a diploid sample: n (n + 1) / 2 pairs; any list the C ABI is given) -------
@@ -411,34 +417,7 @@ __global__ __launch_bounds__(256) void hmm_posterior_big_kernel(HmmPostParams P)
     s_sum_m[tid] = sum.m;
     s_sum_e[tid] = sum.e;
     __syncthreads();
-    if (tid == 0) {
-        const uint8_t* ord = P.order + rowi * n;
-        VgX80 best = {0, 0};
-        uint32_t best_id = 0xFFFFFFFFu;
-        for (uint32_t k = 0; k < n && ord[k] != 0xFF; ++k) {
-            VgX80 sk;
-            sk.m = s_sum_m[ord[k]];
-            sk.e = s_sum_e[ord[k]];
-            if (best_id == 0xFFFFFFFFu || x80_gt(sk, best)) {
-                best = sk;
-                best_id = ord[k];
-            }
-        }
-        VgX80 max_post = {0, 0};
-        uint32_t win = 0xFFFFFFFFu;
-        for (uint32_t q = 0; q < n; ++q) {
-            if (s_gid[q] != best_id) continue;
-            VgX80 t;
-            t.m = s_m[q];
-            t.e = s_e[q];
-            if (x80_gt(t, max_post)) {
-                max_post = t;
-                win = q;
-            }
-        }
-        x80_store(P.prob + rowi * 16, best);
-        P.winner[rowi] = best_id == 0xFFFFFFFFu ? 0xFFFFFFFEu : win;
-    }
+    if (tid == 0) hmm_posterior_pick(P, rowi, s_m, s_e, s_sum_m, s_sum_e, s_gid, P.order + rowi * n);
 }
 
 // ---- emission scores of a node: hidden states (src/genotype.cpp:640-830) and observable states (:960-1000) --------------------
@@ -461,6 +440,18 @@ __device__ __forceinline__ uint32_t hmm_most_likely_depth(uint32_t h, uint32_t c
     return c;
 }
 
+// the sample's term tables, (ploidy + 1) x 256 long doubles, into LDS as 12-byte terms, by a workgroup of BLOCK lanes
+template <uint32_t BLOCK>
+__device__ __forceinline__ void hmm_stage_tables(const uint8_t* tables, uint32_t ploidy, uint64_t* s_tm, int32_t* s_te)
+{
+    for (uint32_t i = threadIdx.x; i < (ploidy + 1u) * 256u; i += BLOCK) {
+        const VgN80 t = n80_from(x80_load(tables + (size_t)i * 16));
+        s_tm[i] = t.m;
+        s_te[i] = t.e;
+    }
+    __syncthreads();
+}
+
 // SELECT (vgmi_hmm_emissions_select): -n picks fewer haplotypes than the panel has, so every window has drawn its own.  The row names its
 // window, the window supplies `used` and the mask (ids up to 46: every shift of the bits is 64 bits wide); an entry that is no longer in
 // its node's list is passed over, and an entry no selected haplotype carries LEAVES the list here, for good (src/genotype.cpp:673-686,
@@ -471,12 +462,7 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     __shared__ uint64_t s_tm[1280];      // (ploidy + 1) x 256 terms: up to four haplotypes per genotype
     __shared__ int32_t s_te[1280];
     const uint32_t g = threadIdx.x;
-    for (uint32_t i = g; i < (P.ploidy + 1u) * 256u; i += 128u) {
-        const VgN80 t = n80_from(x80_load(P.tables + (size_t)i * 16));
-        s_tm[i] = t.m;
-        s_te[i] = t.e;
-    }
-    __syncthreads();
+    hmm_stage_tables<128>(P.tables, P.ploidy, s_tm, s_te);
     const uint64_t rowi = P.fix_rows ? P.fix_rows[blockIdx.x] : P.row_lo + blockIdx.x;
     uint32_t fp = P.fix_rows ? P.fix_off[blockIdx.x] : 0u;
     const uint32_t fe = P.fix_rows ? P.fix_off[blockIdx.x + 1] : 0u;
@@ -560,12 +546,7 @@ __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams
 {
     __shared__ uint64_t s_tm[1280];
     __shared__ int32_t s_te[1280];
-    for (uint32_t i = threadIdx.x; i < (P.ploidy + 1u) * 256u; i += 256u) {
-        const VgN80 t = n80_from(x80_load(P.tables + (size_t)i * 16));
-        s_tm[i] = t.m;
-        s_te[i] = t.e;
-    }
-    __syncthreads();      // (the only one: from here on the wavefronts go their own ways)
+    hmm_stage_tables<256>(P.tables, P.ploidy, s_tm, s_te);      // (its barrier is the only one: from here on the wavefronts go their own ways)
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = threadIdx.x & 63u;
     for (uint32_t k = wave; k < kWinRows; k += 4u) {
         const uint64_t item = (uint64_t)blockIdx.x * kWinRows + k;
@@ -639,62 +620,41 @@ __global__ __launch_bounds__(128) void hmm_scatter_rows_kernel(uint8_t* obs, con
 // carries and the sum of their coverages (the caller divides), and how many k-mers have multiplicity <= 1 (clamped at 255).  A
 // haplotype outside the panel or the selection reads as (0, 0), as on the host.  One lane per row: the entries of a node are ~50
 // consecutive words.
+// SELECT (vgmi_hmm_tallies_select), haplotypes selected per window: hap_ab holds places in the row's window's list (win_used), and only
+// the entries still in the node's list count -- the unique-k-mer count as well (posterior() walks the pruned list)
+template <bool SELECT>
 __global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
-                                                        const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
-                                                        const uint32_t* __restrict__ winner, const uint8_t* __restrict__ hap_ab, uint32_t n_gt, uint32_t n_hap,
-                                                        unsigned long long sel_mask, uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
+                                                        const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
+                                                        const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win,
+                                                        const uint32_t* __restrict__ winner, const uint8_t* __restrict__ hap_ab,
+                                                        const uint8_t* __restrict__ win_used, uint32_t n_gt, uint32_t n_hap, unsigned long long sel_mask,
+                                                        uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
 {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r >= n_rows) return;
     uint32_t num_a = 0, sum_a = 0, num_b = 0, sum_b = 0, u = 0;
     const uint32_t g = winner[r];
     if (g < n_gt) {
-        const uint32_t ha = hap_ab[2u * g], hb = hap_ab[2u * g + 1u];
-        const bool ok_a = ha < n_hap && ((sel_mask >> ha) & 1ull), ok_b = hb < n_hap && ((sel_mask >> hb) & 1ull);
+        uint32_t ha = hap_ab[2u * g], hb = hap_ab[2u * g + 1u];
+        bool ok_a = true, ok_b = true;
+        if (SELECT) {
+            const uint8_t* used = win_used + (size_t)row_win[r] * 16u;
+            ha = used[ha];
+            hb = used[hb];
+        } else {
+            ok_a = ha < n_hap && ((sel_mask >> ha) & 1ull);
+            ok_b = hb < n_hap && ((sel_mask >> hb) & 1ull);
+        }
         const uint64_t e0 = entry_begin[r];
         const uint32_t cnt = entry_count[r];
         for (uint32_t j = 0; j < cnt; ++j) {
+            if (SELECT && alive[e0 + j] == 0) continue;
             const unsigned long long w = packed[e0 + j];
             const uint32_t c = cov[e0 + j];
             const unsigned long long bits = w >> 16;
             if (((uint32_t)(w >> 8) & 0xFFu) <= 1u && u < 255u) ++u;
             if (ok_a && ((bits >> ha) & 1ull)) { ++num_a; sum_a += c; }
             if (ok_b && ((bits >> hb) & 1ull)) { ++num_b; sum_b += c; }
-        }
-    }
-    out[4 * r] = num_a;
-    out[4 * r + 1] = sum_a;
-    out[4 * r + 2] = num_b;
-    out[4 * r + 3] = sum_b;
-    uniq[r] = (uint8_t)u;
-}
-
-// ... with haplotypes selected per window (vgmi_hmm_tallies_select): the called genotype's haplotypes are the row's window's, and only
-// the entries still in the node's list count -- the unique-k-mer count as well (posterior() walks the pruned list)
-__global__ __launch_bounds__(256) void hmm_tally_select_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
-                                                               const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
-                                                               const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win,
-                                                               const uint32_t* __restrict__ winner, const uint8_t* __restrict__ pos_ab,
-                                                               const uint8_t* __restrict__ win_used, uint32_t n_gt, uint64_t n_rows,
-                                                               uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
-{
-    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_rows) return;
-    uint32_t num_a = 0, sum_a = 0, num_b = 0, sum_b = 0, u = 0;
-    const uint32_t g = winner[r];
-    if (g < n_gt) {
-        const uint8_t* used = win_used + (size_t)row_win[r] * 16u;
-        const uint32_t ha = used[pos_ab[2u * g]], hb = used[pos_ab[2u * g + 1u]];
-        const uint64_t e0 = entry_begin[r];
-        const uint32_t cnt = entry_count[r];
-        for (uint32_t j = 0; j < cnt; ++j) {
-            if (alive[e0 + j] == 0) continue;
-            const unsigned long long w = packed[e0 + j];
-            const uint32_t c = cov[e0 + j];
-            const unsigned long long bits = w >> 16;
-            if (((uint32_t)(w >> 8) & 0xFFu) <= 1u && u < 255u) ++u;
-            if ((bits >> ha) & 1ull) { ++num_a; sum_a += c; }
-            if ((bits >> hb) & 1ull) { ++num_b; sum_b += c; }
         }
     }
     out[4 * r] = num_a;
@@ -755,8 +715,8 @@ hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov
                             hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(hmm_tally_kernel, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, entry_begin, entry_count, winner, hap_ab, n_gt, n_hap,
-                       sel_mask, n_rows, out, uniq);
+    hipLaunchKernelGGL(hmm_tally_kernel<false>, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, nullptr, entry_begin, entry_count, nullptr,
+                       winner, hap_ab, nullptr, n_gt, n_hap, sel_mask, n_rows, out, uniq);
     return hipGetLastError();
 }
 
@@ -803,8 +763,8 @@ hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8
                                    const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(hmm_tally_select_kernel, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, alive, entry_begin, entry_count, row_win,
-                       winner, pos_ab, win_used, n_gt, n_rows, out, uniq);
+    hipLaunchKernelGGL(hmm_tally_kernel<true>, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, alive, entry_begin, entry_count, row_win,
+                       winner, pos_ab, win_used, n_gt, 0u, 0ull, n_rows, out, uniq);
     return hipGetLastError();
 }
 
