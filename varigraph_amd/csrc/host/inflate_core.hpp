@@ -53,8 +53,11 @@ inline uint32_t bit_reverse(uint32_t code, uint32_t len)
 }
 
 // canonical Huffman code (RFC 1951 3.2.2) -> lookup table indexed by the next main_bits stream bits, second-level
-// tables for longer codes.  false: over-subscribed code or table space exhausted.
-inline bool build_table(const uint8_t* lens, uint32_t n, const uint32_t* sym_entry, uint32_t main_bits, uint32_t* table, size_t table_cap)
+// tables for longer codes.  false: over-subscribed code, table space exhausted, or an incomplete code that zlib refuses too
+// (inflate_table: legal only as a single code of one bit, and never for the code-length code -- `codes`; no code at all is left
+// to the decoding, where every look-up fails).
+inline bool build_table(const uint8_t* lens, uint32_t n, const uint32_t* sym_entry, uint32_t main_bits, uint32_t* table, size_t table_cap,
+                        bool codes = false)
 {
     uint32_t count[16] = {0};
     for (uint32_t i = 0; i < n; ++i) count[lens[i]]++;
@@ -65,6 +68,9 @@ inline bool build_table(const uint8_t* lens, uint32_t n, const uint32_t* sym_ent
         left -= (int)count[len];
         if (left < 0) return false;
     }
+    uint32_t max_len = 15;
+    while (max_len && !count[max_len]) --max_len;
+    if (left > 0 && max_len != 0 && (codes || max_len != 1)) return false;
     uint32_t offs[17];
     offs[1] = 0;
     for (uint32_t len = 1; len <= 15; ++len) offs[len + 1] = offs[len] + count[len];

@@ -190,7 +190,7 @@ Step read_dynamic_header(const Mapped& m, Bits& b, Tables& tb, bool strict)
     }
     if (strict && !code_complete(pre_lens, 19, nullptr)) return Step::Bad;
     uint32_t pre[1u << kPreBits];
-    if (!build_table(pre_lens, 19, kSym.pre, kPreBits, pre, 1u << kPreBits)) return Step::Bad;
+    if (!build_table(pre_lens, 19, kSym.pre, kPreBits, pre, 1u << kPreBits, true)) return Step::Bad;
     uint8_t lens[286 + 30 + 140];
     uint32_t i = 0;
     const uint32_t total = hlit + hdist;

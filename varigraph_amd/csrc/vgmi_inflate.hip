@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64 * INF_WAVES, WIDE ? 3 : 4) void bgzf_inflate_ker
             for (uint32_t s = lane; s < 288; s += 64) t.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
             if (lane < 32) t.len[288 + lane] = 5;
             inf_sync();
-            if (!inf_build(t, 0, 0, 288, lane) || !inf_build(t, 1, 288, 30, lane)) { err = 1; break; }
+            if (!inf_build(t, 0, 0, 288, lane) || !inf_build(t, 1, 288, 30, lane, INF_INC_ANY)) { err = 1; break; }
         } else {                    // dynamic codes: the code lengths are themselves Huffman coded
             const uint32_t hlit = take(5) + 257, hdist = take(5) + 1, hclen = take(4) + 4;
             if (hlit > 286 || hdist > 30) { err = 1; break; }
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(64 * INF_WAVES, WIDE ? 3 : 4) void bgzf_inflate_ker
                 if (lane == 0) t.len[288 + uni(inf_clen_order[i])] = (uint8_t)v;
             }
             inf_sync();
-            if (!inf_build(t, 1, 288, 19, lane)) { err = 1; break; }
+            if (!inf_build(t, 1, 288, 19, lane, INF_INC_NONE)) { err = 1; break; }
             // the hlit + hdist lengths, written to a staging area first (the code-length code occupies len[288..306])
             uint32_t idx = 0, prev = 0;
             uint8_t* const stage = reinterpret_cast<uint8_t*>(t.lit);        // rebuilt below

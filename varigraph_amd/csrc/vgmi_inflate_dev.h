@@ -48,14 +48,20 @@ __device__ __forceinline__ void inf_sync()
 }
 
 // Canonical Huffman tables of one alphabet from its code lengths (RFC 1951 3.2.2).  which: 0 literal/length, 1 distance.
-// Returns false for an over-subscribed set of lengths (incomplete sets are legal only in the one-code cases zlib accepts;
-// a code that is never assigned simply never matches and ends in the error path).
+// Returns false for an over-subscribed set of lengths, and for an incomplete one where zlib's inflate_table refuses it (what the
+// device decodes must be a prefix of what zlib decodes): `incomplete` says which are let through -- INF_INC_ONE a single code of
+// one bit (literal/length and distance codes of a dynamic block), INF_INC_NONE none (the code-length code), INF_INC_ANY all (the
+// fixed distance code: 30 of 32).  No code at all always passes: the first look-up fails.  Checked once per table, on the counts
+// the loop below has anyway.
 // All lanes at once: lane i holds symbols i, i + 64, ...; per code length, a ballot counts the symbols and ranks each among
 // those of its length in symbol order -- its canonical code is the first code of the length + the rank.  (One lane walking the
 // symbols through LDS, as rounds 2-3 had it, took ~0.1 ms a table: a tenth of a block-gzip member's time, and most of what a
 // candidate block header cost the start search of vgmi_gunzip.hip.)
+#define INF_INC_ONE 0u
+#define INF_INC_NONE 1u
+#define INF_INC_ANY 2u
 template <class T>
-__device__ bool inf_build(T& t, uint32_t which, uint32_t first, uint32_t n, uint32_t lane)
+__device__ bool inf_build(T& t, uint32_t which, uint32_t first, uint32_t n, uint32_t lane, uint32_t incomplete = INF_INC_ONE)
 {
     uint32_t* const tab = which ? t.dist : t.lit;
     const uint32_t bits = which ? INF_DIST_BITS : INF_LIT_BITS;
@@ -67,7 +73,7 @@ __device__ bool inf_build(T& t, uint32_t which, uint32_t first, uint32_t n, uint
         myl[k] = s < n ? t.len[first + s] : 0u;
         code[k] = pos[k] = 0;
     }
-    uint32_t fc = 0, o = 0;
+    uint32_t fc = 0, o = 0, max_len = 0;
     int32_t left = 1;
     bool ok = true;
 #pragma unroll
@@ -86,6 +92,7 @@ __device__ bool inf_build(T& t, uint32_t which, uint32_t first, uint32_t n, uint
         }
         left = (left << 1) - (int32_t)running;
         if (left < 0) ok = false;
+        if (running) max_len = l;
         if (lane == 0) {
             t.count[which][l] = (uint16_t)running;
             t.offs[which][l] = (uint16_t)o;
@@ -95,6 +102,7 @@ __device__ bool inf_build(T& t, uint32_t which, uint32_t first, uint32_t n, uint
     }
     if (lane == 0) t.count[which][0] = 0;
     inf_sync();
+    if (left > 0 && max_len != 0 && incomplete != INF_INC_ANY && (incomplete == INF_INC_NONE || max_len != 1)) ok = false;
     if (!ok) return false;
     // symbols in canonical order; the fast table: every code of at most `bits` bits, replicated over the unused high index bits
 #pragma unroll
