@@ -421,8 +421,18 @@ int vgmi_hmm_tallies_select(vgmi_ctx *ctx, uint64_t n_rows, const uint64_t *entr
  *                    and flag bit 0 as above.
  *   part_fix_rows_wide  vgmi_hmm_part_fix_rows for such a part: fix_mask[i] holds the haplotype ids entry fix_j[i] loses.
  * vgmi_hmm_part_set_rows, _part_calls (one n_gt per part: a caller with lists of several lengths makes a part per length, keep
- * matrices per window through the chains' keep_index) and _part_fetch work on the part as before; the tallies of a polyploid call are
- * the host's. */
+ * matrices per window through the chains' keep_index) and _part_fetch work on the part as before.
+ *   tallies_ploidy   the tallies of a call of `ploidy` (2 .. 4) haplotypes (src/genotype.cpp:1387-1414).  Row r lies in window
+ *                    w = row_win[r] (row_win NULL: window 0, one list for the whole sample) and its called genotype is g = winner[r].
+ *                    g >= win_n_gt[w] (win_n_gt NULL: n_gt in every window; n_gt 1 .. 128, win_n_gt[w] <= n_gt): the row reads zeros.
+ *                    Otherwise the called ids are win_haps[(w * n_gt + g) * ploidy + q], q = 0 .. ploidy - 1, and over the entries
+ *                    [entry_begin[r], + entry_count[r]) -- with use_alive only those whose alive byte is not 0 --
+ *                    out[r * 2 * ploidy + 2 q] = the entries whose bit id_q is set, out[.. + 2 q + 1] = the sum of their coverages,
+ *                    unique_out[r] = the entries of multiplicity <= 1, at most 255.  A place q counts only if id_q < 64 and bit id_q of
+ *                    win_sel_mask[w] (the drawn haplotypes, or the whole panel) is set, and reads (0, 0) otherwise; an id that stands
+ *                    several times in a genotype (the all-zero block, a truncated block) is tallied at every place it stands.
+ *                    VGMI_E_INVALID: a ploidy outside 2 .. 4, n_gt outside 1 .. 128, n_windows == 0, a win_n_gt[w] > n_gt, a row outside
+ *                    the entries or the windows.  VGMI_E_STATE: no entries or coverage uploaded, or no alive bytes with use_alive. */
 int vgmi_hmm_emissions_select_ploidy(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, uint32_t n_windows, const uint32_t *win_n_gt,
                                      const uint8_t *win_haps /* n_windows x n_gt x ploidy */, const uint64_t *win_top_mask, uint32_t bit_len,
                                      float ave, double lower, double upper, const void *tables, uint64_t n_rows, const uint64_t *entry_begin,
@@ -430,6 +440,10 @@ int vgmi_hmm_emissions_select_ploidy(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploi
                                      uint8_t *flags_out, vgmi_hmm_part **out);
 int vgmi_hmm_part_fix_rows_wide(vgmi_hmm_part *part, uint64_t n, const uint64_t *rows, const uint32_t *fix_off, const uint32_t *fix_j,
                                 const uint64_t *fix_mask);
+int vgmi_hmm_tallies_ploidy(vgmi_ctx *ctx, uint32_t ploidy, uint32_t n_gt, uint32_t n_windows, const uint32_t *win_n_gt /* NULL: n_gt in every window */,
+                            const uint8_t *win_haps /* n_windows x n_gt x ploidy ids */, const uint64_t *win_sel_mask /* n_windows */,
+                            uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win /* NULL: all rows in window 0 */,
+                            const uint32_t *winner, int use_alive, uint32_t *out /* n_rows x 2 x ploidy */, uint8_t *unique_out);
 /* the part's emission rows back on the host (n_rows x n_gt long doubles): tests and diagnostics */
 int vgmi_hmm_part_fetch(vgmi_hmm_part *part, void *obs_out);
 void vgmi_hmm_part_free(vgmi_hmm_part *part);

@@ -1101,18 +1101,26 @@ void append_sample_field(std::string& out, const uint64_t* gt, size_t n_alleles,
     out += '\n';
 }
 
-// A diploid call's line straight from what the device sent back -- the called pair's alleles, the posterior, the tallies (k-mers,
-// coverage sum per called haplotype) -- without the detour through the node's call record (window_finish writes it, write_piece reads it
-// back: two walks over half a million scattered nodes per sample).  head(out) as append_site_head.
-template <class Head>
-void append_tally_line(std::string& out, uint64_t ga, uint64_t gb, long double probability, const uint32_t* tl, uint8_t unique_kmers, float min_gq, Head&& head)
+// A call's line straight from what the device sent back -- the alleles of the `ploidy` (2 .. 4) called haplotypes, the posterior, the
+// tallies (k-mers, coverage sum per called haplotype: tl[2 q], tl[2 q + 1]) -- without the detour through the node's call record
+// (window_finish writes it, write_piece reads it back: two walks over half a million scattered nodes per sample).  An all-reference call
+// has no line.  head(out) as append_site_head.
+template <class HapGt, class Head>
+void append_tally_line(std::string& out, const HapGt& hap_gt, const uint16_t* called, uint32_t ploidy, long double probability, const uint32_t* tl,
+                       uint8_t unique_kmers, float min_gq, Head&& head)
 {
-    if ((ga == 0 && gb == 0) || !head(out)) return;
+    uint64_t gt[4], num[4];
+    float cov[4];
+    bool all_ref = true;
+    for (uint32_t q = 0; q < ploidy; ++q) {
+        gt[q] = (uint64_t)hap_gt[called[q]];
+        all_ref = all_ref && gt[q] == 0;
+        num[q] = tl[2 * q];
+        cov[q] = tl[2 * q] ? static_cast<float>((uint64_t)tl[2 * q + 1]) / (float)(uint64_t)tl[2 * q] : 0.0f;
+    }
+    if (all_ref || !head(out)) return;
     const float gq = phred_scaled(probability);
-    const uint64_t gt[2] = {ga, gb}, num[2] = {tl[0], tl[2]};
-    const float cov[2] = {tl[0] ? static_cast<float>((uint64_t)tl[1]) / (float)(uint64_t)tl[0] : 0.0f,
-                          tl[2] ? static_cast<float>((uint64_t)tl[3]) / (float)(uint64_t)tl[2] : 0.0f};
-    append_sample_field(out, gt, 2, gq < min_gq, gq, probability, num, cov, 2, unique_kmers);
+    append_sample_field(out, gt, ploidy, gq < min_gq, gq, probability, num, cov, ploidy, unique_kmers);
 }
 
 // A window's nodes come in the order of their start, as the sites of the map do: one walk along the map instead of a search from its
@@ -2237,6 +2245,7 @@ struct Genotyper::PanelSample {
     size_t per_part = 1, n_parts = 0;
     std::string cache_key;
     std::atomic<bool> broken{false};      // a pruned list after all: the host path
+    std::atomic<size_t> ploidy_tally_rows{0};      // rows of a polyploid sample whose calls the device tallied, over the parts
     WindowHaps haps() const { return WindowHaps{top, used, genotypes, glist}; }
 };
 
@@ -2316,6 +2325,8 @@ Genotyper::Emitted Genotyper::hmm_whole_panel(RunShared& s)
     if (!err_text.empty()) throw std::runtime_error(err_text);
     if (ps.broken.load()) return Emitted::lists_pruned;
     if (g_phase_on) std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s\n", ps.n_parts, s.since_begin() * 1e-9 - tb0);
+    if (g_phase_on && ps.ploidy_tally_rows.load())
+        std::fprintf(stderr, "[varigraph-mi] HMM tallies on the device: %zu rows, ploidy %u\n", ps.ploidy_tally_rows.load(), cfg.sample_ploidy);
     return Emitted::yes;
 }
 
@@ -2462,10 +2473,32 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
                      (t_b - t_rows) * 1e-9, (t_calls - t_b) * 1e-9);
     s.note_device_span(ta, t_calls);
     // the calls' k-mer tallies on the device too (the node lists and the sample's coverage are there for the emissions):
-    // per sample, the walk over every called node's k-mer list was 0.8 of 1.7 host thread-seconds (VGH_DEVICE_TALLIES=0: the walk)
-    std::vector<uint32_t> tally;
+    // per sample, the walk over every called node's k-mer list was 0.8 of 1.7 host thread-seconds (VGH_DEVICE_TALLIES=0: the walk).
+    // A tri- or tetraploid sample's through vgmi_hmm_tallies_ploidy: one window, the sample's one list by haplotype id, whole lists.
+    const uint32_t ploidy = cfg.sample_ploidy;
+    std::vector<uint32_t> tally;      // per row 2 x ploidy numbers
     std::vector<uint8_t> tally_uniq;
     static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
+    if (device_tallies && plan->n_steps && (ploidy == 3 || ploidy == 4) && n_hap_ <= 64 && n_gt <= 128) {
+        std::vector<uint8_t> haps_all(n_gt * ploidy);
+        bool ids = true;
+        for (size_t g2 = 0; g2 < n_gt && ids; ++g2)
+            for (uint32_t q = 0; q < ploidy; ++q) {
+                if (ps.genotypes[g2][q] > 254) { ids = false; break; }
+                haps_all[g2 * ploidy + q] = (uint8_t)ps.genotypes[g2][q];
+            }
+        uint64_t sel = 0;
+        for (uint16_t hap : ps.top)
+            if (hap < n_hap_ && hap < 64) sel |= 1ull << hap;
+        if (ids) {
+            tally.resize(2 * (size_t)ploidy * n_rows);
+            tally_uniq.resize(n_rows);
+            device_check(dev_, vgmi_hmm_tallies_ploidy(dev_, ploidy, (uint32_t)n_gt, 1, nullptr, haps_all.data(), &sel, n_rows, pc.e_begin.data(), pc.e_count.data(),
+                                                       nullptr, winner.data(), 0, tally.data(), tally_uniq.data()),
+                         "device tallies: ");
+            ps.ploidy_tally_rows += n_rows;
+        }
+    }
     if (device_tallies && plan->n_steps && cfg.sample_ploidy == 2 && n_hap_ <= 64 && n_gt <= 128) {
         std::vector<uint8_t> hap_ab(2 * n_gt, 0xFF);
         bool pairs = true;
@@ -2507,7 +2540,7 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
             if (tally.empty()) append_call_line(out, node, cfg.min_gq, gt, head);
             else if (winner[rw] < n_gt) {      // (else no entry with a positive posterior: no call)
                 const std::vector<uint16_t>& called = ps.genotypes[winner[rw]];
-                append_tally_line(out, node.gn->hap_gt[called[0]], node.gn->hap_gt[called[1]], prob[rw], &tally[4 * rw], tally_uniq[rw], cfg.min_gq, head);
+                append_tally_line(out, node.gn->hap_gt, called.data(), ploidy, prob[rw], &tally[2 * (size_t)ploidy * rw], tally_uniq[rw], cfg.min_gq, head);
             }
         }
         s.pieces[t] = std::move(out);
@@ -2528,7 +2561,8 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
 // the block of `ploidy` consecutive haplotypes that holds it (:846-873), so a window has 1 .. -n genotypes over up to -n x ploidy
 // haplotypes -- `used`, which the scores, the sequence checks and the strings go by -- while the prune still goes by the drawn ones.  The
 // device's recursion takes one list length per part: the windows are dealt into parts by the length of their lists (SelectedPart), each
-// with its own emission launch, keep matrix per window and 1 / n_gt.  The tallies of a polyploid call are the host's (finish_rows).
+// with its own emission launch, keep matrix per window and 1 / n_gt, and its own tally launch (vgmi_hmm_tallies_ploidy) over the same lists:
+// the lines of a polyploid sample are written from the device's numbers as a diploid sample's are.
 struct Genotyper::SelectedSample {
     float ave = 0;
     double lower = 256.0f, upper = -0.1f;
@@ -2543,7 +2577,7 @@ struct Genotyper::SelectedSample {
     std::vector<uint8_t> win_used8;          // diploid: the drawn haplotypes as the device takes them
     std::vector<uint64_t> win_mask;          // the drawn haplotypes
     // what the VGH_TIMING line sums over the parts
-    size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0, n_parts = 0;
+    size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0, n_parts = 0, n_ploidy_tally_rows = 0;
     int64_t ns_emit = 0, ns_a = 0, ns_rows = 0, ns_b = 0, ns_calls = 0, t_last = 0;
     const std::vector<uint16_t>& used(size_t wi) const { return blocks ? win_used[wi] : win_top[wi]; }
     WindowHaps haps(size_t wi) const { return WindowHaps{win_top[wi], used(wi), win_gts[wi], win_glist[wi]}; }
@@ -2722,6 +2756,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
                      ss.ns_rows * 1e-9, ss.ns_b * 1e-9, ss.ns_calls * 1e-9);
         std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
                      std::max<size_t>(1, parts.size()), s.since_begin() * 1e-9 - tb0, nw, tasks.size());
+        if (ss.n_ploidy_tally_rows) std::fprintf(stderr, "[varigraph-mi] HMM tallies on the device: %zu rows, ploidy %u\n", ss.n_ploidy_tally_rows, ss.ploidy);
     }
     return Emitted::yes;
 }
@@ -2743,16 +2778,21 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
     std::vector<uint32_t> winner(n_rows ? n_rows : 1, 0xFFFFFFFFu);
     std::vector<std::vector<uint32_t>> win_rows(nwp);      // per window: the rows that have a score
     size_t n_steps = 0;
+    // a list per window: the lists by haplotype id and the drawn haplotypes, for the emission launch and the tallies
+    std::vector<uint32_t> w_n;
+    std::vector<uint8_t> w_haps;
+    std::vector<uint64_t> w_mask;
     if (n_rows) {
         // 4. emission scores on the device, the prune included
         std::vector<uint32_t> n_kept(n_rows);
         std::vector<uint8_t> flags(n_rows);
         PartHandle ph;
         if (ss.blocks) {
-            // the lists by haplotype id, the rows' reference-allele masks over haplotype ids
-            std::vector<uint32_t> w_n(nwp, (uint32_t)n_gt);
-            std::vector<uint8_t> w_haps(nwp * n_gt * ss.ploidy);
-            std::vector<uint64_t> w_mask(nwp), gt0_ids(n_rows, 0);
+            // ... and the rows' reference-allele masks over haplotype ids
+            w_n.assign(nwp, (uint32_t)n_gt);
+            w_haps.resize(nwp * n_gt * ss.ploidy);
+            w_mask.resize(nwp);
+            std::vector<uint64_t> gt0_ids(n_rows, 0);
             for (size_t lw = 0; lw < nwp; ++lw) {
                 const size_t wi = pt.wins[lw];
                 w_mask[lw] = ss.win_mask[wi];
@@ -2849,10 +2889,19 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
     ss.ns_b += t_b - t_rows;
     ss.ns_calls += t_calls - t_b;
     ss.t_last = t_calls;
-    // 8. the calls' tallies on the device, a diploid sample's (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists)
-    std::vector<uint32_t> tally;
+    // 8. the calls' tallies on the device (VGH_DEVICE_TALLIES=0: the walk over the called nodes' lists); a polyploid sample's over the lists
+    // of the emission launch, the drawn haplotypes being the ones that count
+    std::vector<uint32_t> tally;      // per row 2 x ploidy numbers
     std::vector<uint8_t> tally_uniq;
     static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
+    if (device_tallies && n_steps && ss.blocks && ss.ploidy <= 4) {
+        tally.resize(2 * (size_t)ss.ploidy * n_rows);
+        tally_uniq.resize(n_rows);
+        device_check(dev_, vgmi_hmm_tallies_ploidy(dev_, ss.ploidy, (uint32_t)n_gt, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(), n_rows, pt.e_begin.data(),
+                                                   pt.e_count.data(), pt.row_win.data(), winner.data(), 1, tally.data(), tally_uniq.data()),
+                     "device tallies: ");
+        ss.n_ploidy_tally_rows += n_rows;
+    }
     if (device_tallies && n_steps && !ss.blocks) {
         tally.resize(4 * n_rows);
         tally_uniq.resize(n_rows);
@@ -2880,7 +2929,7 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
             const std::vector<std::string>* fields = walk.at(node.start);
             if (winner[rw] >= n_gt) continue;            // no entry with a positive posterior: no call
             const std::vector<uint16_t>& called = ss.win_gts[wi][winner[rw]];
-            append_tally_line(out, node.gn->hap_gt[called[0]], node.gn->hap_gt[called[1]], prob[rw], &tally[4 * rw], tally_uniq[rw], cfg.min_gq,
+            append_tally_line(out, node.gn->hap_gt, called.data(), ss.ploidy, prob[rw], &tally[2 * (size_t)ss.ploidy * rw], tally_uniq[rw], cfg.min_gq,
                               [&](std::string& o) { return append_site_head(o, fields); });
         }
         s.pieces[wi] = std::move(out);

@@ -897,6 +897,71 @@ int vgmi_hmm_tallies_select(vgmi_ctx* c, uint64_t n_rows, const uint64_t* entry_
 }
 
 
+// ---- the tallies of a POLYPLOID call (ploidy 3, 4; pairs are taken too): the called genotype winner[i] of a row of window w is the `ploidy`
+// ids win_haps[(w * n_gt + g) * ploidy ..] -- the lists the emission launches of such a sample take, the whole panel's being one window
+// (row_win == NULL) without alive bytes (use_alive == 0: no list was ever pruned).
+int vgmi_hmm_tallies_ploidy(vgmi_ctx* c, uint32_t ploidy, uint32_t n_gt, uint32_t n_windows, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                            const uint64_t* win_sel_mask, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                            const uint32_t* winner, int use_alive, uint32_t* out, uint8_t* unique_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !winner || !out || !unique_out)) || !win_haps || !win_sel_mask) return VGMI_E_INVALID;
+    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || n_gt > 128 || n_windows < 1)
+        return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes of 2..4 haplotypes in at least one window");
+    if (!c->d_hmm_entries || !c->d_hmm_cov || (use_alive && !c->d_hmm_alive))
+        return fail(c, VGMI_E_STATE, "HMM tallies: upload the entries and the sample's coverage first");
+    if (win_n_gt)
+        for (uint32_t w = 0; w < n_windows; ++w)
+            if (win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM tallies: a window with more genotypes than the lists are wide");
+    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_rows == 0) return VGMI_OK;
+    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_out = n_rows * 8 * ploidy;
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(row_win ? n_rows * 4 : 0), o_win = call.add(n_rows * 4),
+                 o_out = call.add(b_out), o_uni = call.add(n_rows), o_ng = call.add(win_n_gt ? (size_t)n_windows * 4 : 0), o_haps = call.add(b_haps),
+                 o_mask = call.add((size_t)n_windows * 8);
+    if (int rc = call.begin("HMM tallies")) return rc;
+    // VGMI_HMM_TIMING=1: upload / kernel / download, milliseconds on stderr (diagnostics)
+    const bool timing = getenv("VGMI_HMM_TIMING") != nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (timing)
+        for (auto& x : ev) (void)hipEventCreate(&x);
+    if (timing) (void)hipEventRecord(ev[0], call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    if (row_win) call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_win, winner, n_rows * 4);
+    if (win_n_gt) call.upload(o_ng, win_n_gt, (size_t)n_windows * 4);
+    call.upload(o_haps, win_haps, b_haps);
+    call.upload(o_mask, win_sel_mask, (size_t)n_windows * 8);
+    call.run([&] {
+        if (timing) (void)hipEventRecord(ev[1], call.stream());
+        const hipError_t e = launch_hmm_tally_ploidy(c->d_hmm_entries, c->d_hmm_cov, use_alive ? c->d_hmm_alive : nullptr, call.at<const uint64_t>(o_beg),
+                                       call.at<const uint32_t>(o_cnt), row_win ? call.at<const uint32_t>(o_rw) : nullptr, call.at<const uint32_t>(o_win),
+                                       win_n_gt ? call.at<const uint32_t>(o_ng) : nullptr, call.at(o_haps), call.at<const unsigned long long>(o_mask), n_gt, ploidy,
+                                       n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
+        if (timing) (void)hipEventRecord(ev[2], call.stream());
+        return e;
+    });
+    call.download(out, o_out, b_out);
+    call.download(unique_out, o_uni, n_rows);
+    if (timing) {
+        (void)hipEventRecord(ev[3], call.stream());
+        call.sync();
+        float up = 0, kern = 0, down = 0;
+        if (call.ok()) {
+            (void)hipEventElapsedTime(&up, ev[0], ev[1]);
+            (void)hipEventElapsedTime(&kern, ev[1], ev[2]);
+            (void)hipEventElapsedTime(&down, ev[2], ev[3]);
+        }
+        fprintf(stderr, "[vgmi] HMM tally call: %llu rows of %u haplotypes, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", (unsigned long long)n_rows,
+                ploidy, up, kern, down);
+        for (auto& x : ev) (void)hipEventDestroy(x);
+    }
+    HIPCHK(c, call.finish());
+    return VGMI_OK;
+}
+
+
 int vgmi_hmm_part_fetch(vgmi_hmm_part* part, void* obs_out)
 {
     if (!part || !obs_out) return VGMI_E_INVALID;

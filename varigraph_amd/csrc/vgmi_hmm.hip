@@ -664,6 +664,74 @@ __global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long
     uniq[r] = (uint8_t)u;
 }
 
+// ---- ... of a POLYPLOID call (vgmi_hmm_tallies_ploidy): the called genotype is `ploidy` haplotype ids of the row's window's list ---------
+// win_haps as the emission launch of such a sample takes them; an id that stands several times (haplotype 0 in a truncated or all-zero
+// block) is tallied at every place it stands, an id outside win_sel_mask[w] -- not drawn, not in the panel -- or beyond 63 reads (0, 0), a
+// winner at or beyond the window's count is no call: zeros.  alive == nullptr: the lists are whole, every entry counts.
+// A wavefront takes a row and a lane an entry, 64 entries a turn, so the loads of a turn are consecutive words / bytes; the row is made
+// wavefront-uniform (readfirstlane), the turns are the same for every lane, and what is counted is a ballot's population: the k-mers a
+// called haplotype carries and the single-copy k-mers never leave the scalar side.  The coverage sums are kept per lane and added up
+// across the wavefront once per row; lane 0 writes the row.  32-bit integer sums: any order of additions gives the host's numbers.
+constexpr uint32_t kTallyRows = 16;
+__global__ __launch_bounds__(256) void hmm_tally_ploidy_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
+                                                               const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
+                                                               const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win,
+                                                               const uint32_t* __restrict__ winner, const uint32_t* __restrict__ win_n_gt,
+                                                               const uint8_t* __restrict__ win_haps, const unsigned long long* __restrict__ win_sel_mask,
+                                                               uint32_t n_gt, uint32_t ploidy, uint64_t n_rows, uint32_t* __restrict__ out,
+                                                               uint8_t* __restrict__ uniq)
+{
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    for (uint32_t k = wave; k < kTallyRows; k += 4u) {
+        const uint64_t r = (uint64_t)blockIdx.x * kTallyRows + k;
+        if (r >= n_rows) break;
+        const uint32_t w = row_win ? row_win[r] : 0u;
+        const uint32_t g = winner[r];
+        uint32_t num[4] = {0, 0, 0, 0}, sum[4] = {0, 0, 0, 0}, u = 0;
+        if (g < (win_n_gt ? win_n_gt[w] : n_gt)) {
+            const unsigned long long sel = win_sel_mask[w];
+            uint32_t id[4] = {0, 0, 0, 0};
+            bool ok[4] = {false, false, false, false};
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)      // (unrolled with the places beyond `ploidy` left out: the arrays stay in registers)
+                if (q < ploidy) {
+                    const uint32_t h = win_haps[((size_t)w * n_gt + g) * ploidy + q];
+                    ok[q] = h < 64u && ((sel >> (h & 63u)) & 1ull);
+                    id[q] = ok[q] ? h : 0u;
+                }
+            const uint64_t e0 = entry_begin[r];
+            const uint32_t cnt = entry_count[r];
+            for (uint32_t base = 0; base < cnt; base += 64u) {      // (every lane takes every turn: the ballots are the wavefront's)
+                const uint32_t j = base + lane;
+                const bool in = j < cnt && (!alive || alive[e0 + j] != 0);
+                const unsigned long long word = in ? packed[e0 + j] : 0ull;
+                const uint32_t c = in ? cov[e0 + j] : 0u;
+                u += (uint32_t)__popcll(__ballot(in && ((uint32_t)(word >> 8) & 0xFFu) <= 1u));
+                const unsigned long long bits = word >> 16;
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) {
+                    const bool hit = in && ok[q] && ((bits >> id[q]) & 1ull);
+                    num[q] += (uint32_t)__popcll(__ballot(hit));
+                    sum[q] += hit ? c : 0u;
+                }
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)
+                for (uint32_t d = 32; d; d >>= 1) sum[q] += (uint32_t)__shfl_xor((int)sum[q], (int)d);
+            if (u > 255u) u = 255u;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)
+                if (q < ploidy) {
+                    out[(r * ploidy + q) * 2] = num[q];
+                    out[(r * ploidy + q) * 2 + 1] = sum[q];
+                }
+            uniq[r] = (uint8_t)u;
+        }
+    }
+}
+
 // ---- selection support of the windows (src/genotype.cpp:500-560: what haplotype_selection sums before the gamma draws) ---------------
 // support[w][hap] = sum of c over the alive entries of window w's rows with c > 1 and multiplicity <= 1 that haplotype `hap` carries.
 // 32-bit integer sums: any order of additions gives the host's number.  A workgroup takes kSupportRows consecutive rows, a wavefront a
@@ -765,6 +833,18 @@ hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8
     if (n_rows == 0) return hipSuccess;
     hipLaunchKernelGGL(hmm_tally_kernel<true>, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, alive, entry_begin, entry_count, row_win,
                        winner, pos_ab, win_used, n_gt, 0u, 0ull, n_rows, out, uniq);
+    return hipGetLastError();
+}
+
+hipError_t launch_hmm_tally_ploidy(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
+                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                   const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
+                                   hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || !win_haps || !win_sel_mask) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hmm_tally_ploidy_kernel, dim3((uint32_t)((n_rows + kTallyRows - 1) / kTallyRows)), dim3(256), 0, st, packed, cov, alive, entry_begin,
+                       entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, n_rows, out, uniq);
     return hipGetLastError();
 }
 

@@ -333,6 +333,13 @@ hipError_t launch_hmm_support(const unsigned long long* packed, const uint8_t* c
 hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
                                    const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab,
                                    const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
+// the tallies of a polyploid call: genotype g of a row of window w (row_win == nullptr: window 0) is the `ploidy` ids
+// win_haps[(w * n_gt + g) * ploidy ..], each tallied where it stands if win_sel_mask[w] holds it; a winner >= win_n_gt[w] (nullptr: n_gt)
+// reads zeros; alive == nullptr: every entry counts.  out: n_rows x ploidy x (k-mers, coverage sum)
+hipError_t launch_hmm_tally_ploidy(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
+                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                   const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
+                                   hipStream_t st);
 hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uint8_t* src, uint32_t n_gt, uint64_t n, hipStream_t st);
 size_t hmm_lds_bytes(uint32_t n_gt, uint32_t ploidy);
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,

@@ -101,6 +101,7 @@ def load_library():
                                                    vp, vp, C.POINTER(vp)]),
         "vgmi_hmm_part_fix_rows_wide": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
         "vgmi_hmm_tallies_select": (i32, [vp, C.c_uint64, vp, vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+        "vgmi_hmm_tallies_ploidy": (i32, [vp, u32, u32, u32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_int, vp, vp]),
         "vgmi_hmm_part_set_rows": (i32, [vp, C.c_uint64, vp, vp]),
         "vgmi_hmm_part_fix_rows": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
         "vgmi_hmm_plan_create": (i32, [vp, u32, u32, vp, u32, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, u32, vp, vp, vp, vp, C.POINTER(vp)]),
@@ -711,6 +712,27 @@ class Context:
         uniq = np.full(max(n_rows, 1), 0xEE, dtype=np.uint8)
         self._chk(self._l.vgmi_hmm_tallies_select(self._h, n_rows, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(winner), pos_a.size, _ptr(pos_a),
                                                    _ptr(pos_b), win_used.shape[1], win_used.shape[0], _ptr(win_used), _ptr(out), _ptr(uniq)))
+        return out[:n_rows], uniq[:n_rows]
+
+    def hmm_tallies_ploidy(self, ploidy, win_haps, win_sel_mask, entry_begin, entry_count, winner, row_win=None, win_n_gt=None, use_alive=True):
+        """vgmi_hmm_tallies_ploidy: win_haps (n_windows, n_gt, ploidy) haplotype ids, win_sel_mask (n_windows,) the haplotypes that count;
+        row_win None: every row in window 0, win_n_gt None: n_gt genotypes in every window.  Returns (out (rows, 2 * ploidy) uint32 --
+        k-mers and coverage sum per place of the called genotype -- and unique (rows,) uint8)."""
+        win_haps = np.ascontiguousarray(win_haps, dtype=np.uint8)
+        win_sel_mask = np.ascontiguousarray(win_sel_mask, dtype=np.uint64)
+        entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
+        entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
+        winner = np.ascontiguousarray(winner, dtype=np.uint32)
+        row_win = None if row_win is None else np.ascontiguousarray(row_win, dtype=np.uint32)
+        win_n_gt = None if win_n_gt is None else np.ascontiguousarray(win_n_gt, dtype=np.uint32)
+        assert win_haps.ndim == 3 and win_haps.shape[2] == ploidy and win_sel_mask.size == win_haps.shape[0] and entry_count.size == winner.size == entry_begin.size
+        assert (row_win is None or row_win.size == entry_begin.size) and (win_n_gt is None or win_n_gt.size == win_haps.shape[0])
+        n_rows, width = entry_begin.size, 2 * max(int(ploidy), 1)
+        out = np.full((max(n_rows, 1), width), 0xDEADBEEF, dtype=np.uint32)
+        uniq = np.full(max(n_rows, 1), 0xEE, dtype=np.uint8)
+        self._chk(self._l.vgmi_hmm_tallies_ploidy(self._h, ploidy, win_haps.shape[1], win_haps.shape[0], _ptr(win_n_gt),
+                                                   _ptr(win_haps), _ptr(win_sel_mask), n_rows, _ptr(entry_begin), _ptr(entry_count),
+                                                   _ptr(row_win), _ptr(winner), int(bool(use_alive)), _ptr(out), _ptr(uniq)))
         return out[:n_rows], uniq[:n_rows]
 
     def hmm_calls_part(self, keep, obs, row, restart, pow_tables, uniform, chains, ploidy, gid, order, fwd_step, bwd_step, rows, steps,
