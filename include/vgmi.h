@@ -292,6 +292,17 @@ typedef struct vgmi_hmm_chain {
 int vgmi_hmm_recursion(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, const uint8_t *keep, uint32_t n_windows,
                        const void *obs, uint64_t n_rows, const uint32_t *row, const uint8_t *restart, const void *pow,
                        uint64_t n_steps, const void *uniform, const vgmi_hmm_chain *chains, uint32_t n_chains, void *out);
+/* The recursion under `-m fre`, transitions by haplotype frequency (src/genotype.cpp:1196-1215, 1297-1316): both transition
+ * probabilities are zero there and, for a node that is not a chain's first,
+ *     r_g = sum over the previous entries p, in their order, of  ((prev_p * obs_g) * f[g][0]) * ... * f[g][ploidy - 1]
+ * with f[g][q] the window's score (the normalised gamma draw, hapIdxScoreMap) of genotype g's q-th haplotype; total, divide, the
+ * uniform fallback and a chain's first node (r_g = obs_g) as above.  There is no keep matrix and there are no powers:
+ * freq[(t * n_gt + g) * ploidy + q] is genotype g's q-th factor in table t, a 16-byte long double (the host widens the double, which
+ * is exact), and a chain's keep_index names its table.  ploidy 2 .. 4, 1 .. 128 genotypes, n_tables >= 1: anything else, a NULL freq
+ * or a chain whose index is >= n_tables is VGMI_E_INVALID, as is a step or row outside its arrays, and leaves the context usable. */
+int vgmi_hmm_recursion_fre(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, const void *freq, uint32_t n_tables, const void *obs,
+                           uint64_t n_rows, const uint32_t *row, const uint8_t *restart, uint64_t n_steps, const void *uniform,
+                           const vgmi_hmm_chain *chains, uint32_t n_chains, void *out);
 /* The same recursion followed by the posterior of every node (src/genotype.cpp:1387-1522) while alpha and beta are still
  * on the device: per row (node) the host gives the genotype STRING of every entry (gid: the reference keys a std::map by
  * the alleles as decimal strings, sorted as strings) and the strings in string order (order, 0xFF behind the last), and the
@@ -356,6 +367,12 @@ int vgmi_hmm_part_calls(vgmi_hmm_part *part, uint32_t ploidy, const uint8_t *kee
                         const uint8_t *restart, const void *pow, uint64_t n_steps, const void *uniform, const vgmi_hmm_chain *chains,
                         uint32_t n_chains, const uint8_t *gid, const uint8_t *order, const uint64_t *fwd_step, const uint64_t *bwd_step,
                         void *prob, uint32_t *winner);
+/* vgmi_hmm_part_calls under `-m fre`: the part's tables of factors (vgmi_hmm_recursion_fre: n_tables x n_gt x ploidy long doubles, n_gt
+ * the part's) in place of keep / pow, the same refusals; the posterior is the same. */
+int vgmi_hmm_part_calls_fre(vgmi_hmm_part *part, uint32_t ploidy, const void *freq, uint32_t n_tables, const uint32_t *row,
+                            const uint8_t *restart, uint64_t n_steps, const void *uniform, const vgmi_hmm_chain *chains, uint32_t n_chains,
+                            const uint8_t *gid, const uint8_t *order, const uint64_t *fwd_step, const uint64_t *bwd_step, void *prob,
+                            uint32_t *winner);
 /* The calls' k-mer tallies (src/genotype.cpp:1387-1414, read for the CALLED haplotypes): per row with winner[i] < n_gt, genotype
  * winner[i] = the haplotypes (hap_ab[2 g], hap_ab[2 g + 1]); out[4 i ..] = k-mers of the node haplotype a carries, the sum of
  * their coverages, the same for b (a haplotype >= n_hap or outside sel_mask: 0, 0); unique_out[i] = k-mers of multiplicity <= 1,

@@ -1047,6 +1047,21 @@ std::vector<uint8_t> keep_matrix(const std::vector<std::vector<uint16_t>>& genot
 }
 
 // the sample's libm values for the emission kernel: geometric(error_param(ave), c) for h = 0, poisson(ave * h, c) for h = 1 .. ploidy
+// `-m fre`: a window's table of factors for the device recursion (vgmi_hmm_recursion_fre) -- per genotype its haplotypes' scores, the
+// window's normalised gamma draws (HaplotypeSampler::score: hapIdxScoreMap), in the genotype's order, widened (exact).  A haplotype the
+// window did not draw has no score: where the host's recursion would have stopped (src/genotype.cpp:1203-1207), this stops.
+std::vector<long double> frequency_table(const std::vector<std::vector<uint16_t>>& genotypes, const std::unordered_map<uint16_t, double>& score)
+{
+    std::vector<long double> table;
+    for (const auto& haps : genotypes)
+        for (uint16_t hap : haps) {
+            auto it = score.find(hap);
+            if (it == score.end()) throw std::runtime_error("'" + std::to_string(hap) + "' does not exist in 'hapIdxScoreMap'.");
+            table.push_back((long double)it->second);
+        }
+    return table;
+}
+
 std::vector<long double> emission_table(float ave, uint32_t ploidy)
 {
     std::vector<long double> tab((size_t)(ploidy + 1) * 256);
@@ -1214,9 +1229,10 @@ void Genotyper::step_tables(const std::vector<Seen>& seen, uint32_t stride, uint
     // the tables of powers are a function of the distance alone: neighbouring nodes are tens to hundreds of bases apart, so a window's
     // few thousand steps share a few hundred distinct tables (same libm calls, each made once)
     constexpr uint32_t kMemo = 4096;
-    std::vector<long double> memo((size_t)kMemo * 2 * stride);
+    std::vector<long double> memo(pw ? (size_t)kMemo * 2 * stride : 0);
     std::vector<uint8_t> memo_have(kMemo, 0);
     auto powers = [&](long double* dst, uint32_t distance) {
+        if (!pw) return;      // transitions by haplotype frequency: no powers
         if (distance < kMemo && memo_have[distance]) {
             std::memcpy(dst, &memo[(size_t)distance * 2 * stride], 2 * stride * sizeof(long double));
             return;
@@ -1237,11 +1253,11 @@ void Genotyper::step_tables(const std::vector<Seen>& seen, uint32_t stride, uint
         if (seen[q].at < 0) continue;
         const size_t fs = j, bs = m + (m - 1 - j);     // its forward and its backward step
         // forward: the node in front (prev_end = 0 in front of the first); the chain restarts behind a node without scores
-        powers(pw + fs * 2 * stride, seen[q].start - (q ? seen[q - 1].end : 0u));
+        powers(pw ? pw + fs * 2 * stride : nullptr, seen[q].start - (q ? seen[q - 1].end : 0u));
         restart[fs] = (q == 0 || seen[q - 1].at < 0) ? 1 : 0;
         row[fs] = (uint32_t)(row_base + seen[q].at);
         // backward: the node behind (prev_start = 0 behind the last)
-        powers(pw + bs * 2 * stride, (q + 1 < seen.size() ? seen[q + 1].start : 0u) - seen[q].end);
+        powers(pw ? pw + bs * 2 * stride : nullptr, (q + 1 < seen.size() ? seen[q + 1].start : 0u) - seen[q].end);
         restart[bs] = (q + 1 == seen.size() || seen[q + 1].at < 0) ? 1 : 0;
         row[bs] = (uint32_t)(row_base + seen[q].at);
         fwd[seen[q].at] = step0 + fs;
@@ -1843,7 +1859,11 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
 {
     const GenotypeConfig& cfg = *r.cfg;
     DevicePaths dp;
-    const bool use_device = dev_ != nullptr && !knob_off("VGH_HMM_DEVICE") && cfg.transition == "rec" && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;
+    // `-m fre` (transitions by haplotype frequency) has a recursion kernel of its own, fed by the two paths that score the emissions on the
+    // device: 2 .. 4 haplotypes per genotype, at most 128 genotypes, never the pool.  VGH_HMM_FRE_DEVICE=0: such a sample stays on the host.
+    const bool fre = cfg.transition == "fre";
+    const bool transition_ok = cfg.transition == "rec" || (fre && cfg.sample_ploidy >= 2 && !knob_off("VGH_HMM_FRE_DEVICE"));
+    const bool use_device = dev_ != nullptr && !knob_off("VGH_HMM_DEVICE") && transition_ok && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;
     if (!use_device) return dp;
     works.resize(tasks.size());
     std::vector<uint16_t> some(std::min<size_t>(r.haploid_num, n_hap_));
@@ -1896,7 +1916,14 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
     dp.select = device_ok && select_fits && !refuse_select && !dp.emit && r.packed != nullptr && (cfg.sample_ploidy == 2 || blocks) && n_hap_ > r.haploid_num &&
                 r.haploid_num >= 1 && r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen && !knob_off("VGH_HMM_EMIT_DEVICE") &&
                 !knob_off("VGH_HMM_SELECT_DEVICE");
-    dp.pool_device = device_ok && !dp.emit && !dp.select;
+    if (fre) {
+        // the whole panel's windows draw too under `-m fre` (their scores are the factors): the support sums come from the device, which
+        // reads haplotype h as bit h.  With selection only a diploid sample: a polyploid one's blocks name haplotypes that were not drawn
+        // and have no score -- the reference stops there ("does not exist in 'hapIdxScoreMap'"), and so does the host path
+        dp.emit = dp.emit && plain_ids;
+        dp.select = dp.select && cfg.sample_ploidy == 2;
+    }
+    dp.pool_device = device_ok && !dp.emit && !dp.select && !fre;
     return dp;
 }
 
@@ -2174,20 +2201,22 @@ struct Genotyper::StepArrays {
     std::vector<size_t> win_step0;
     size_t n_steps = 0;
     uint32_t stride;
+    bool has_pow;
     std::vector<long double> pw;
     std::vector<uint32_t> row;
     std::vector<uint8_t> restart;
     std::vector<uint64_t> fwd, bwd;
     std::vector<vgmi_hmm_chain> chains;
 
-    // keep_per_window: window wi's chains use keep matrix wi (a genotype list per window); else one matrix serves all
-    StepArrays(const std::vector<std::vector<uint32_t>>& win_rows, size_t n_rows, uint32_t ploidy, bool keep_per_window = false)
-        : win_step0(win_rows.size() + 1, 0), stride(ploidy + 1)
+    // keep_per_window: window wi's chains use keep matrix wi (a genotype list per window) or table wi (`-m fre`); else one matrix serves
+    // all.  with_pow false (`-m fre`): no tables of powers are made
+    StepArrays(const std::vector<std::vector<uint32_t>>& win_rows, size_t n_rows, uint32_t ploidy, bool keep_per_window = false, bool with_pow = true)
+        : win_step0(win_rows.size() + 1, 0), stride(ploidy + 1), has_pow(with_pow)
     {
         for (size_t wi = 0; wi < win_rows.size(); ++wi) win_step0[wi + 1] = win_step0[wi] + 2 * win_rows[wi].size();
         n_steps = win_step0.back();
         if (!n_steps) return;
-        pw.resize(n_steps * 2 * stride);
+        if (has_pow) pw.resize(n_steps * 2 * stride);
         row.assign(n_steps, 0);
         restart.assign(n_steps, 0);
         fwd.assign(n_rows, 0);
@@ -2203,7 +2232,7 @@ struct Genotyper::StepArrays {
     void fill(size_t wi, const std::vector<Seen>& seen, uint16_t population)      // (libm: a window per thread)
     {
         const size_t s0 = win_step0[wi];
-        step_tables(seen, stride, population, s0, 0, pw.data() + s0 * 2 * stride, row.data() + s0, restart.data() + s0, fwd.data(), bwd.data());
+        step_tables(seen, stride, population, s0, 0, has_pow ? pw.data() + s0 * 2 * stride : nullptr, row.data() + s0, restart.data() + s0, fwd.data(), bwd.data());
     }
 };
 
@@ -2246,6 +2275,10 @@ struct Genotyper::PanelSample {
     std::string cache_key;
     std::atomic<bool> broken{false};      // a pruned list after all: the host path
     std::atomic<size_t> ploidy_tally_rows{0};      // rows of a polyploid sample whose calls the device tallied, over the parts
+    // `-m fre`: the scores of every window's draw are the recursion's factors -- per window of the run the table of the genotypes' haplotypes'
+    // scores; the recursion's other inputs go up per sample (vgmi_hmm_part_calls_fre) instead of lying in a plan
+    bool by_freq = false;
+    std::vector<std::vector<long double>> win_freq;
     WindowHaps haps() const { return WindowHaps{top, used, genotypes, glist}; }
 };
 
@@ -2277,7 +2310,8 @@ Genotyper::Emitted Genotyper::hmm_whole_panel(RunShared& s)
     ps.pos_all.resize(n_gt * cfg.sample_ploidy);
     for (size_t gi = 0; gi < n_gt; ++gi)
         for (uint32_t q = 0; q < cfg.sample_ploidy; ++q) ps.pos_all[gi * cfg.sample_ploidy + q] = where[ps.genotypes[gi][q]];
-    ps.keep_mat = keep_matrix(ps.genotypes);
+    ps.by_freq = cfg.transition == "fre";
+    if (!ps.by_freq) ps.keep_mat = keep_matrix(ps.genotypes);
     for (uint16_t hap : ps.top) ps.top_mask |= 1ULL << hap;
     ps.tab = emission_table(ps.ave, cfg.sample_ploidy);
     if (!entries_uploaded_) {
@@ -2285,12 +2319,13 @@ Genotyper::Emitted Genotyper::hmm_whole_panel(RunShared& s)
         entries_uploaded_ = true;
     }
     device_check(dev_, vgmi_hmm_sample_upload(dev_, r.cov, g_.node_key_index.size()), "device HMM emissions: ");
+    if (ps.by_freq && !panel_draws(s, ps)) return Emitted::lists_pruned;
     const size_t max_parts = std::min<size_t>(4, dev_parts_);
     ps.per_part = std::max<size_t>(1, (s.tasks.size() + max_parts - 1) / max_parts);
     ps.n_parts = (s.tasks.size() + ps.per_part - 1) / ps.per_part;
     ps.cache_key = std::to_string(s.tasks.size()) + "/" + std::to_string(ps.per_part) + "/" + std::to_string(cfg.sv_only) + "/" +
                    std::to_string(cfg.sample_ploidy) + "/" + cfg.sample_type + "/" + std::to_string(n_gt) + "/" + std::to_string(r.haploid_num) + "/" +
-                   std::to_string(cfg.chr_len_thread);
+                   std::to_string(cfg.chr_len_thread) + "/" + cfg.transition;
     // What a part's device calls need beyond a sample's coverage is a function of the graph and the options: the rows (entry
     // ranges, reference-allele masks), and the PLAN -- genotype strings, which rows have a score, the step tables (libm), chains,
     // all of it resident on the device (vgmi_hmm_plan).  Made by the first sample that gets there, kept with the graph, shared
@@ -2327,7 +2362,44 @@ Genotyper::Emitted Genotyper::hmm_whole_panel(RunShared& s)
     if (g_phase_on) std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s\n", ps.n_parts, s.since_begin() * 1e-9 - tb0);
     if (g_phase_on && ps.ploidy_tally_rows.load())
         std::fprintf(stderr, "[varigraph-mi] HMM tallies on the device: %zu rows, ploidy %u\n", ps.ploidy_tally_rows.load(), cfg.sample_ploidy);
+    if (g_phase_on && ps.by_freq)
+        std::fprintf(stderr, "[varigraph-mi] HMM transitions by haplotype frequency on the device: %zu windows\n", s.emit_windows_done.load());
     return Emitted::yes;
+}
+
+// `-m fre` with the whole panel: the windows draw all the same, because the scores of the draw are the recursion's factors.  The support
+// sums over every node with more than one allele come from the device (vgmi_hmm_support; the lists are whole, so a node's list is a
+// range), the draws are made here as hmm_selected makes them, and every window gets its table.  false: a node's list is not whole
+bool Genotyper::panel_draws(RunShared& s, PanelSample& ps)
+{
+    const Run& r = s.r;
+    const size_t nw = s.tasks.size();
+    std::vector<uint64_t> sup_begin;
+    std::vector<uint32_t> sup_count, sup_win;
+    {
+        CpuBudget::Hold cpu;
+        PhaseTimer t_list(g_phase.list);
+        for (size_t t = 0; t < nw; ++t) {
+            const Chrom& chr = *s.tasks[t].chr;
+            for (uint32_t i = s.tasks[t].first; i < s.tasks[t].last; ++i) {
+                const Node& n = chr.nodes[i];
+                if (n.gn->hap_gt.size() <= 1) continue;
+                if (!n.kmers.empty() && (size_t)(n.kmers.back() - n.kmers.front()) + 1 != n.kmers.size()) return false;
+                sup_begin.push_back(n.kmers.empty() ? 0 : n.kmers.front());
+                sup_count.push_back((uint32_t)n.kmers.size());
+                sup_win.push_back((uint32_t)t);
+            }
+        }
+    }
+    std::vector<uint32_t> support(nw * n_hap_, 0);
+    device_check(dev_, vgmi_hmm_support(dev_, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
+                 "device HMM support: ");
+    ps.win_freq.resize(nw);
+    over_windows(nw, s.n_threads, g_phase.select, [&](size_t wi) {
+        HaplotypeSampler sampler(std::vector<uint32_t>(support.begin() + wi * n_hap_, support.begin() + (wi + 1) * n_hap_), (int)r.haploid_num);
+        ps.win_freq[wi] = frequency_table(ps.genotypes, sampler.score);
+    });
+    return true;
 }
 
 // the rows of a part: every node the HMM works on, window after window (the same for every sample and every Genotyper: listed once).
@@ -2405,9 +2477,20 @@ std::shared_ptr<Genotyper::EmitPartPlan> Genotyper::panel_plan(RunShared& s, con
         np->line_head += heads[wi];
         std::string().swap(heads[wi]);
     }
-    StepArrays steps(np->win_rows, n_rows, s.r.cfg->sample_ploidy);
+    StepArrays steps(np->win_rows, n_rows, s.r.cfg->sample_ploidy, ps.by_freq, !ps.by_freq);
     np->n_steps = steps.n_steps;
-    if (steps.n_steps) {
+    if (steps.n_steps && ps.by_freq) {
+        // no device plan: the tables of factors are the sample's.  What is the graph's -- rows, restarts, chains, strings -- is kept here and
+        // goes up with every sample's tables (vgmi_hmm_part_calls_fre)
+        over_windows(nw, helpers, g_phase.pass_b, [&](size_t wi) { steps.fill(wi, seen[wi], (uint16_t)n_hap_); });
+        np->gid = std::move(gid);
+        np->order = std::move(order);
+        np->row = std::move(steps.row);
+        np->restart = std::move(steps.restart);
+        np->fwd = std::move(steps.fwd);
+        np->bwd = std::move(steps.bwd);
+        np->chains = std::move(steps.chains);
+    } else if (steps.n_steps) {
         over_windows(nw, helpers, g_phase.pass_b, [&](size_t wi) { steps.fill(wi, seen[wi], (uint16_t)n_hap_); });
         const long double uniform = 1.0L / (long double)n_gt;
         device_check(dev_, vgmi_hmm_plan_create(dev_, (uint32_t)n_gt, s.r.cfg->sample_ploidy, ps.keep_mat.data(), 1, n_rows, steps.row.data(), steps.restart.data(),
@@ -2464,7 +2547,19 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
     const int64_t t_b = s.since_begin();
     std::vector<long double> prob(n_rows);
     std::vector<uint32_t> winner(n_rows, 0xFFFFFFFFu);
-    if (plan->n_steps) device_check(dev_, vgmi_hmm_part_calls_plan(ph.p, plan->plan, prob.data(), winner.data()), "device HMM recursion: ");
+    if (plan->n_steps && ps.by_freq) {
+        const uint32_t ploidy_f = cfg.sample_ploidy;
+        const long double uniform = 1.0L / (long double)n_gt;
+        std::vector<long double> freq_all;
+        freq_all.reserve(nw * n_gt * ploidy_f);
+        for (size_t wi = 0; wi < nw; ++wi) freq_all.insert(freq_all.end(), ps.win_freq[t0 + wi].begin(), ps.win_freq[t0 + wi].end());
+        if (freq_all.size() != nw * n_gt * ploidy_f) throw std::runtime_error("internal: a window's table of haplotype scores has another length");
+        device_check(dev_, vgmi_hmm_part_calls_fre(ph.p, ploidy_f, freq_all.data(), (uint32_t)nw, plan->row.data(), plan->restart.data(), plan->n_steps, &uniform,
+                                                   plan->chains.data(), (uint32_t)plan->chains.size(), plan->gid.data(), plan->order.data(), plan->fwd.data(),
+                                                   plan->bwd.data(), prob.data(), winner.data()),
+                     "device HMM recursion: ");
+    } else if (plan->n_steps)
+        device_check(dev_, vgmi_hmm_part_calls_plan(ph.p, plan->plan, prob.data(), winner.data()), "device HMM recursion: ");
     const int64_t t_calls = s.since_begin();
     if (g_phase_on)
         std::fprintf(stderr, "[varigraph-mi] HMM part %zu (windows %zu-%zu): emissions, recursion and posterior on the device from %.3f to %.3f s (%zu of %zu nodes scored by the host, %zu scored again on the device): "
@@ -2576,6 +2671,8 @@ struct Genotyper::SelectedSample {
     std::vector<GenotypeList> win_glist;
     std::vector<uint8_t> win_used8;          // diploid: the drawn haplotypes as the device takes them
     std::vector<uint64_t> win_mask;          // the drawn haplotypes
+    bool by_freq = false;                    // `-m fre`: no keep matrix, no powers; per window the table of its genotypes' haplotypes' scores
+    std::vector<std::vector<long double>> win_freq;
     // what the VGH_TIMING line sums over the parts
     size_t n_fixed_rows = 0, n_host_rows = 0, n_pruned = 0, n_parts = 0, n_ploidy_tally_rows = 0;
     int64_t ns_emit = 0, ns_a = 0, ns_rows = 0, ns_b = 0, ns_calls = 0, t_last = 0;
@@ -2606,6 +2703,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     ss.ploidy = cfg.sample_ploidy;
     ss.blocks = cfg.sample_ploidy > 2;
     ss.n_drawn = r.haploid_num;
+    ss.by_freq = cfg.transition == "fre";
     const uint32_t n_used = ss.n_drawn;
     size_t n_gt = 0;      // diploid: of every window
     if (!ss.blocks) {
@@ -2622,7 +2720,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
             ss.pos_a[gi] = (uint8_t)shape[gi][0];
             ss.pos_b[gi] = (uint8_t)shape[gi][1];
         }
-        ss.keep_mat = keep_matrix(shape);      // (places keep the haplotypes' order)
+        if (!ss.by_freq) ss.keep_mat = keep_matrix(shape);      // (places keep the haplotypes' order)
     }
     ss.tab = emission_table(ss.ave, ss.ploidy);
     if (!entries_uploaded_) {
@@ -2685,6 +2783,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     ss.win_glist.resize(nw);
     ss.win_used8.assign(ss.blocks ? 0 : nw * n_used, 0);
     ss.win_mask.assign(nw, 0);
+    ss.win_freq.resize(ss.by_freq ? nw : 0);
     std::vector<uint64_t> gt0(n_rows ? n_rows : 1, 0);
     over_windows(nw, s.n_threads, g_phase.select, [&](size_t wi) {
         HaplotypeSampler sampler(std::vector<uint32_t>(support.begin() + wi * n_hap_, support.begin() + (wi + 1) * n_hap_), (int)r.haploid_num);
@@ -2706,6 +2805,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
         }
         const std::vector<uint16_t>& used = ss.used(wi);
         ss.win_glist[wi] = genotype_list(ss.win_gts[wi], used);
+        if (ss.by_freq) ss.win_freq[wi] = frequency_table(ss.win_gts[wi], sampler.score);
         const Chrom& chr = *tasks[wi].chr;
         for (size_t rr = win_row0[wi]; rr < win_row0[wi + 1]; ++rr) {
             const auto& hap_gt = chr.nodes[row_node[rr]].gn->hap_gt;
@@ -2757,6 +2857,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
         std::fprintf(stderr, "[varigraph-mi] HMM emissions on the device: %zu parts, %.2f s; haplotypes selected per window for %zu of %zu windows\n",
                      std::max<size_t>(1, parts.size()), s.since_begin() * 1e-9 - tb0, nw, tasks.size());
         if (ss.n_ploidy_tally_rows) std::fprintf(stderr, "[varigraph-mi] HMM tallies on the device: %zu rows, ploidy %u\n", ss.n_ploidy_tally_rows, ss.ploidy);
+        if (ss.by_freq) std::fprintf(stderr, "[varigraph-mi] HMM transitions by haplotype frequency on the device: %zu windows\n", s.emit_windows_done.load());
     }
     return Emitted::yes;
 }
@@ -2862,11 +2963,21 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
             row_strings(*tasks[pt.wins[lw]].chr, win_row0[lw], win_row0[lw + 1], row_node.data(), pt.gt0.data(), n_kept.data(), ss.haps(pt.wins[lw]), gid.data(),
                         order.data(), seen[lw], win_rows[lw]);
         });
-        StepArrays steps(win_rows, n_rows, ss.ploidy, ss.blocks);
+        StepArrays steps(win_rows, n_rows, ss.ploidy, ss.blocks || ss.by_freq, !ss.by_freq);
         n_steps = steps.n_steps;
         if (n_steps) over_windows(nwp, s.n_threads, g_phase.pass_b, [&](size_t lw) { steps.fill(lw, seen[lw], (uint16_t)n_hap_); });
         t_b = s.since_begin();
-        if (n_steps) {
+        if (n_steps && ss.by_freq) {      // a table of factors per window in place of keep matrix and powers
+            const long double uniform = 1.0L / (long double)n_gt;
+            std::vector<long double> freq_all;
+            freq_all.reserve(nwp * n_gt * ss.ploidy);
+            for (size_t lw = 0; lw < nwp; ++lw) freq_all.insert(freq_all.end(), ss.win_freq[pt.wins[lw]].begin(), ss.win_freq[pt.wins[lw]].end());
+            if (freq_all.size() != nwp * n_gt * ss.ploidy) throw std::runtime_error("internal: a window's table of haplotype scores has another length");
+            device_check(dev_, vgmi_hmm_part_calls_fre(ph.p, ss.ploidy, freq_all.data(), (uint32_t)nwp, steps.row.data(), steps.restart.data(), n_steps, &uniform,
+                                                       steps.chains.data(), (uint32_t)steps.chains.size(), gid.data(), order.data(), steps.fwd.data(),
+                                                       steps.bwd.data(), prob.data(), winner.data()),
+                         "device HMM recursion: ");
+        } else if (n_steps) {
             const long double uniform = 1.0L / (long double)n_gt;
             std::vector<uint8_t> keep_all;      // a list per window: a keep matrix per window
             if (ss.blocks) {

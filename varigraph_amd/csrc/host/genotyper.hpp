@@ -71,7 +71,8 @@ public:
     size_t last_windows = 0, last_device_windows = 0;     // windows of the last run() / those whose recursion and posterior ran on the device
 
     // The forward / backward recursion of eligible windows (transition "rec", every genotype with `ploidy` haplotypes, at most
-    // 2048 genotypes) runs on this context's device (vgmi_hmm_recursion: the reference's arithmetic bit for bit); nullptr: host.
+    // 2048 genotypes; transition "fre" where the emissions are scored on the device, at most 128 genotypes of 2 .. 4 haplotypes)
+    // runs on this context's device (vgmi_hmm_recursion, vgmi_hmm_recursion_fre: the reference's arithmetic bit for bit); nullptr: host.
     // max_parts: into how many device calls side by side a sample's windows may go (the process's four hardware queues,
     // shared by the consumers that genotype at the same time)
     void set_device(vgmi_ctx* ctx, unsigned max_parts = 4) { dev_ = ctx; dev_parts_ = max_parts ? max_parts : 1; }
@@ -176,6 +177,7 @@ private:
     struct EmitPartPlan;
     void panel_part(RunShared& s, PanelSample& ps, size_t part);
     bool panel_rows(RunShared& s, const PanelSample& ps, EmitPartCache& pc, size_t t0, size_t t1);
+    bool panel_draws(RunShared& s, PanelSample& ps);      // `-m fre`: every window's draw and its table of haplotype scores
     std::shared_ptr<EmitPartPlan> panel_plan(RunShared& s, const PanelSample& ps, EmitPartCache& pc, size_t t0, size_t nw, size_t helpers,
                                              const std::vector<uint32_t>& n_kept);
     // ---- what the paths share
@@ -234,6 +236,11 @@ private:
         std::vector<uint64_t> line_head_off;                         // n_rows + 1
         vgmi_hmm_plan* plan = nullptr;
         size_t n_steps = 0;
+        // `-m fre`: no device plan (the tables of factors are the sample's); the graph's share of the call's arrays is kept here
+        std::vector<uint8_t> gid, order, restart;
+        std::vector<uint32_t> row;
+        std::vector<uint64_t> fwd, bwd;
+        std::vector<vgmi_hmm_chain> chains;
         ~EmitPartPlan();
     };
     struct EmitPartCache {     // shared by the Genotypers of a graph (GraphIndex::shared_slots); `mu` guards the listing and the plan's making

@@ -193,19 +193,30 @@ std::vector<uint8_t> hmm_used16(const uint8_t* win_used, size_t n_windows, uint3
 int hmm_run(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, uint32_t n_windows, const void* obs, uint64_t row_lo,
             uint64_t row_hi, const uint32_t* row, const uint8_t* restart, const void* pow, uint64_t step_lo, uint64_t step_hi,
             const void* uniform, const vgmi_hmm_chain* chains, uint32_t n_chains, void* out, const uint8_t* gid, const uint8_t* order,
-            const uint64_t* fwd_step, const uint64_t* bwd_step, void* prob, uint32_t* winner, const uint8_t* dev_obs = nullptr)
+            const uint64_t* fwd_step, const uint64_t* bwd_step, void* prob, uint32_t* winner, const uint8_t* dev_obs = nullptr, const void* freq = nullptr,
+            bool by_freq = false)
 {
     // dev_obs: the emission rows [row_lo, row_hi) are already on the device (vgmi_hmm_emissions); obs is then not read
-    if (!c || !keep || (!obs && !dev_obs) || !row || !restart || !pow || !uniform || !chains) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > VGMI_HMM_MAX_GT || ploidy < 1 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM recursion: 1..2048 genotypes of 1..4 haplotypes");
-    if (int rc = hmm_check_keep(c, "HMM recursion", keep, n_windows, n_gt)) return rc;
+    // by_freq: transitions by haplotype frequency (vgmi_hmm_recursion_fre) -- n_windows tables of n_gt x ploidy factors in `freq` take the
+    // place of the keep matrices and there are no powers; everything else of the call is the same
+    if (!c || (!obs && !dev_obs) || !row || !restart || !uniform || !chains) return VGMI_E_INVALID;
+    if (by_freq) {
+        if (ploidy < 2 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM recursion by haplotype frequency: genotypes of 2..4 haplotypes");
+        if (n_gt < 1 || n_gt > 128) return fail(c, VGMI_E_INVALID, "HMM recursion by haplotype frequency: 1..128 genotypes");
+        if (!freq || n_windows == 0) return fail(c, VGMI_E_INVALID, "HMM recursion by haplotype frequency: no table of factors");
+    } else {
+        if (!keep || !pow) return VGMI_E_INVALID;
+        if (n_gt < 1 || n_gt > VGMI_HMM_MAX_GT || ploidy < 1 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM recursion: 1..2048 genotypes of 1..4 haplotypes");
+        if (int rc = hmm_check_keep(c, "HMM recursion", keep, n_windows, n_gt)) return rc;
+    }
     if (row_lo > row_hi || step_lo > step_hi) return fail(c, VGMI_E_INVALID, "HMM recursion: an empty-handed range");
     const uint64_t n_rows = row_hi - row_lo, n_steps = step_hi - step_lo;
     if (int rc = hmm_check_ranges(c, "HMM recursion", chains, n_chains, n_windows, row, row_lo, row_hi, step_lo, step_hi, gid ? fwd_step : nullptr, bwd_step)) return rc;
     if (n_steps == 0 || n_chains == 0) return VGMI_OK;
     const uint32_t stride = ploidy + 1;
-    const size_t b_keep = (size_t)n_windows * n_gt * n_gt, w_obs = (size_t)n_gt * 16, b_obs = dev_obs ? 0 : (size_t)n_rows * w_obs, b_row = (size_t)n_steps * 4,
-                 w_pow = (size_t)2 * stride * 16, b_pow = (size_t)n_steps * w_pow, b_ch = (size_t)n_chains * sizeof(vgmi_hmm_chain),
+    // (b_keep: the keep matrices, or the tables of factors in their place)
+    const size_t b_keep = by_freq ? (size_t)n_windows * n_gt * ploidy * 16 : (size_t)n_windows * n_gt * n_gt, w_obs = (size_t)n_gt * 16,
+                 b_obs = dev_obs ? 0 : (size_t)n_rows * w_obs, b_row = (size_t)n_steps * 4, w_pow = by_freq ? 0 : (size_t)2 * stride * 16, b_pow = (size_t)n_steps * w_pow, b_ch = (size_t)n_chains * sizeof(vgmi_hmm_chain),
                  b_out = (size_t)n_steps * w_obs, b_gid = gid ? (size_t)n_rows * n_gt : 0, b_fs = gid ? (size_t)n_rows * 8 : 0,
                  b_prob = gid ? (size_t)n_rows * 16 : 0, b_win = gid ? (size_t)n_rows * 4 : 0;
     static_assert(sizeof(vgmi_hmm_chain) == sizeof(HmmChain), "chain layout");
@@ -223,11 +234,11 @@ int hmm_run(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, ui
     if (timing)
         for (auto& x : ev) (void)hipEventCreate(&x);
     if (timing) (void)hipEventRecord(ev[0], st);
-    call.upload(o_keep, keep, b_keep);
+    call.upload(o_keep, by_freq ? freq : keep, b_keep);
     if (!dev_obs) call.upload(o_obs, static_cast<const uint8_t*>(obs) + row_lo * w_obs, b_obs);
     call.upload(o_row, row + step_lo, b_row);
     call.upload(o_rs, restart + step_lo, n_steps);
-    call.upload(o_pow, static_cast<const uint8_t*>(pow) + step_lo * w_pow, b_pow);
+    if (!by_freq) call.upload(o_pow, static_cast<const uint8_t*>(pow) + step_lo * w_pow, b_pow);
     call.upload(o_uni, uniform, 16);
     call.upload(o_ch, chains, b_ch);
     if (gid) {
@@ -240,6 +251,22 @@ int hmm_run(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, ui
     // where global row / step 0 would lie (the kernels only touch the range)
     auto back = [](uint8_t* p, size_t bytes) { return reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(p) - bytes); };
     call.run([&] {
+        if (by_freq) {
+            HmmFreParams F{};
+            F.n_gt = n_gt;
+            F.ploidy = ploidy;
+            F.freq = call.at(o_keep);
+            F.obs = back(dev_obs ? const_cast<uint8_t*>(dev_obs) : call.at(o_obs), row_lo * w_obs);
+            F.row = reinterpret_cast<const uint32_t*>(back(call.at(o_row), step_lo * 4));
+            F.restart = back(call.at(o_rs), step_lo);
+            F.uniform = call.at(o_uni);
+            F.chains = call.at<const HmmChain>(o_ch);
+            F.out = back(call.at(o_out), step_lo * w_obs);
+            if (timing) (void)hipEventRecord(ev[1], st);
+            const hipError_t e = launch_hmm_recursion_fre(F, n_chains, st);
+            if (timing) (void)hipEventRecord(ev[2], st);
+            return e;
+        }
         HmmParams P{};
         P.n_gt = n_gt;
         P.ploidy = ploidy;
@@ -284,9 +311,9 @@ int hmm_run(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, ui
             (void)hipEventElapsedTime(&g, ev[2], ev[3]);
         }
         auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-        fprintf(stderr, "[vgmi] HMM on the device: %u chains, %llu steps, upload %.1f ms (%.0f MB), recursion %.1f ms, posterior + download %.1f ms; "
+        fprintf(stderr, "[vgmi] HMM on the device%s: %u chains, %llu steps, upload %.1f ms (%.0f MB), recursion %.1f ms, posterior + download %.1f ms; "
                         "host: memory %.1f ms, copies issued in %.1f ms, whole call %.1f ms\n",
-                n_chains, (unsigned long long)n_steps, a, (double)(b_keep + b_obs + b_row + b_pow + 2 * b_gid + 2 * b_fs) / 1e6, b, g, ms(h0, h1),
+                by_freq ? " (by haplotype frequency)" : "", n_chains, (unsigned long long)n_steps, a, (double)(b_keep + b_obs + b_row + b_pow + 2 * b_gid + 2 * b_fs) / 1e6, b, g, ms(h0, h1),
                 ms(h1, h2), ms(h0, std::chrono::steady_clock::now()));
         for (auto& x : ev) (void)hipEventDestroy(x);
     }
@@ -707,6 +734,16 @@ int vgmi_hmm_part_calls(vgmi_hmm_part* part, uint32_t ploidy, const uint8_t* kee
                    nullptr, gid, order, fwd_step, bwd_step, prob, winner, part->d_obs);
 }
 
+// ... under `-m fre`: n_tables tables of the part's n_gt x ploidy factors in place of keep / pow (vgmi_hmm_recursion_fre); the posterior is the same
+int vgmi_hmm_part_calls_fre(vgmi_hmm_part* part, uint32_t ploidy, const void* freq, uint32_t n_tables, const uint32_t* row, const uint8_t* restart,
+                            uint64_t n_steps, const void* uniform, const vgmi_hmm_chain* chains, uint32_t n_chains, const uint8_t* gid, const uint8_t* order,
+                            const uint64_t* fwd_step, const uint64_t* bwd_step, void* prob, uint32_t* winner)
+{
+    if (!part || !gid || !order || !fwd_step || !bwd_step || !prob || !winner) return VGMI_E_INVALID;
+    return hmm_run(part->c, part->n_gt, ploidy, nullptr, n_tables, nullptr, 0, part->n_rows, row, restart, nullptr, 0, n_steps, uniform, chains, n_chains, nullptr,
+                   gid, order, fwd_step, bwd_step, prob, winner, part->d_obs, freq, true);
+}
+
 // ---- a part's recursion inputs kept on the device (round 5).  Everything hmm_run uploads but the emission scores -- keep matrix, step
 // tables (pow), rows, restarts, chains, genotype strings' ids and order, the rows' steps: 230 MB per chr20-scale sample -- is a
 // function of the graph and the options, not of the sample: a plan holds it on the device, made once, used by every sample (and every
@@ -986,6 +1023,17 @@ int vgmi_hmm_recursion(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_
     if (!out) return VGMI_E_INVALID;
     return hmm_run(c, n_gt, ploidy, keep, n_windows, obs, 0, n_rows, row, restart, pow, 0, n_steps, uniform, chains, n_chains, out, nullptr,
                    nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---- the recursion under `-m fre` (src/genotype.cpp:1196-1215, 1297-1316): r_g = sum over p of ((prev_p * obs_g) * f_g0) * f_g1 ..., the
+// factors of genotype g from table chains[i].keep_index: freq[(t * n_gt + g) * ploidy + q], long doubles (the sampler's doubles, widened)
+int vgmi_hmm_recursion_fre(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const void* freq, uint32_t n_tables, const void* obs, uint64_t n_rows,
+                           const uint32_t* row, const uint8_t* restart, uint64_t n_steps, const void* uniform, const vgmi_hmm_chain* chains,
+                           uint32_t n_chains, void* out)
+{
+    if (!out) return VGMI_E_INVALID;
+    return hmm_run(c, n_gt, ploidy, nullptr, n_tables, obs, 0, n_rows, row, restart, nullptr, 0, n_steps, uniform, chains, n_chains, out, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, nullptr, freq, true);
 }
 
 int vgmi_hmm_calls(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, uint32_t n_windows, const void* obs, uint64_t n_rows,

@@ -158,6 +158,131 @@ __global__ __launch_bounds__(64 * WAVES) void hmm_recursion_kernel(HmmParams P)
     }
 }
 
+// ---- the recursion under `-m fre`: transitions by haplotype frequency (src/genotype.cpp:1196-1215, 1297-1316) ---------------------
+// Both transition probabilities are zero there and a term is  (prev_p * obs_g) * score[hap_g[0]] * ... * score[hap_g[ploidy - 1]],
+// the window's normalised gamma draws (doubles, widened exactly) multiplied on in the genotype's haplotype order.  obs_g comes first, so
+// a term depends on p and g before any factor that is the lane's alone: no step table, 1 + PLOIDY products per term.  What does not
+// change is the layout (a workgroup per chain, a lane per genotype, WAVES wavefronts), the sum over the previous entries in their order,
+// the total, the divide and the uniform fallback.  A chain's keep_index names its table of factors: n_gt x PLOIDY long doubles.
+// The previous row is published to LDS after the divide, one value per entry; every lane walks it in entry order.  Only  r + t  is a
+// dependency from term to term: term p + 1 is multiplied out before term p is added, so its products overlap the addition.
+template <uint32_t PLOIDY, uint32_t WAVES>
+__global__ __launch_bounds__(64 * WAVES) void hmm_recursion_fre_kernel(HmmFreParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t hmm_smem[];
+    const uint32_t n = P.n_gt, per_wave = (n + WAVES - 1) / WAVES, lane = threadIdx.x & 63u;
+    const bool active = lane < per_wave && (threadIdx.x >> 6) * per_wave + lane < n;
+    const uint32_t g = active ? (threadIdx.x >> 6) * per_wave + lane : 0u;      // an idle lane reads genotype 0's inputs and writes nothing
+    uint64_t* const s_r_m = reinterpret_cast<uint64_t*>(hmm_smem);             // this node's sums, for the total
+    uint64_t* const s_p_m = s_r_m + 128;                                        // the previous node's row
+    int32_t* const s_r_e = reinterpret_cast<int32_t*>(s_p_m + 128);
+    int32_t* const s_p_e = s_r_e + 128;
+
+    const HmmChain ch = P.chains[blockIdx.x];
+    const VgX80 uniform = x80_load(P.uniform);
+    if (ch.n_steps == 0) return;
+    // the lane's factors: the window's, the same at every step.  ef: what they add to the bound on a term's exponent
+    VgN80 f[PLOIDY];
+    bool dead = false;
+    int32_t ef = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < PLOIDY; ++q) {
+        f[q] = n80_from(x80_load(P.freq + (((size_t)ch.keep_index * n + g) * PLOIDY + q) * 16));
+        dead = dead || f[q].m == 0;
+        ef += f[q].e - VG_X80_BIAS + 1;
+    }
+
+    if (active) {      // a chain that does not begin with a restart begins from zeros, as the other kernel's does
+        s_p_m[g] = 0;
+        s_p_e[g] = 0;
+    }
+    __syncthreads();
+
+    uint32_t lane_zero = 0;      // (see hmm_recursion_kernel: the per-step loads stay on the vector memory path)
+    asm volatile("" : "+v"(lane_zero));
+    const uint64_t s_end = ch.first_step + ch.n_steps;
+    VgX80 obs_cur = x80_load(P.obs + ((size_t)P.row[ch.first_step] * n + g) * 16);
+    uint32_t restart_cur = P.restart[ch.first_step + lane_zero];
+    uint32_t row_next = ch.n_steps > 1 ? P.row[ch.first_step + 1] : 0u;
+
+    for (uint64_t s = ch.first_step; s < s_end; ++s) {
+        VgX80 obs_nx = obs_cur;
+        uint32_t restart_nx = 0, row_after = 0;
+        if (s + 1 < s_end) {      // the next step's inputs, fetched a step ahead
+            obs_nx = x80_load(P.obs + ((size_t)row_next * n + g) * 16);
+            restart_nx = P.restart[s + 1 + lane_zero];
+        }
+        if (s + 2 < s_end) row_after = P.row[s + 2 + lane_zero];
+
+        const bool restart = __builtin_amdgcn_readfirstlane(restart_cur) != 0;
+        VgN80 o = {0, 0};
+        if (active) o = n80_from(obs_cur);
+        VgN80 r = {0, 0};
+        if (active) {
+            if (restart) {
+                r = o;
+            } else {
+                // a term's exponent is at most its operands' summed, plus one per multiply (and one to spare, as the other kernel has it)
+                const bool lane_dead = dead || o.m == 0;
+                const int32_t eo = o.e - VG_X80_BIAS + 1 + ef + 1;
+                auto term = [&](uint32_t p, const VgN80& sum) {
+                    VgN80 pv;
+                    pv.m = s_p_m[p + lane_zero];
+                    pv.e = s_p_e[p + lane_zero];
+                    // nothing to add: a zero operand, or a term more than 64 binades below the sum so far (which only grows, so the sum
+                    // of a term earlier decides no differently than the exact one would allow).  Skipped when the wavefront agrees.
+                    const bool nothing = pv.m == 0 || lane_dead || (sum.m != 0 && sum.e - (pv.e + eo) > 64);
+                    VgN80 t = {0, 0};
+                    if (__builtin_amdgcn_ballot_w64(!nothing) != 0) {
+                        t = n80_mul(pv, o);
+#pragma unroll
+                        for (uint32_t q = 0; q < PLOIDY; ++q) t = n80_mul(t, f[q]);
+                    }
+                    return t;
+                };
+                VgN80 t = term(0, r);
+                for (uint32_t p = 0; p < n; ++p) {
+                    VgN80 tn = {0, 0};
+                    if (p + 1 < n) tn = term(p + 1, r);
+                    if (__builtin_amdgcn_ballot_w64(t.m != 0) != 0) r = n80_sum(r, t);
+                    t = tn;
+                }
+            }
+            s_r_m[g] = r.m;
+            s_r_e[g] = r.e;
+        }
+        __syncthreads();
+        VgN80 total = {0, 0};
+        VgN80 tn;
+        tn.m = s_r_m[lane_zero];
+        tn.e = s_r_e[lane_zero];
+        for (uint32_t p = 0; p < n; ++p) {      // every lane adds the same values in the same order (hmm_recursion_kernel)
+            const VgN80 t = tn;
+            if (p + 1 < n) {
+                tn.m = s_r_m[p + 1 + lane_zero];
+                tn.e = s_r_e[p + 1 + lane_zero];
+            }
+            if (t.m == 0 || (total.m != 0 && total.e - t.e > 64)) continue;
+            total = n80_sum(total, t);
+        }
+        VgX80 out = uniform;
+        VgN80 prev = n80_from(uniform);
+        if (total.m != 0) {
+            prev = n80_div(r, total);
+            out = n80_to(prev);
+        }
+        if (active) {
+            x80_store(P.out + (s * n + g) * 16, out);
+            s_p_m[g] = prev.m;
+            s_p_e[g] = prev.e;
+        }
+        __syncthreads();
+        obs_cur = obs_nx;
+        restart_cur = restart_nx;
+        row_next = row_after;
+    }
+}
+
 // ---- posterior of a node (src/genotype.cpp:1387-1522) from the alpha / beta rows the recursion left on the device --------
 //   denominator = sum of a_g * b_g in entry order;  post_g = (a_g * b_g) / denominator;  per genotype STRING (gid, made by the
 //   host: alleles as decimal strings, sorted as strings) the sum of its entries' posts in entry order;  the first maximum in
@@ -869,6 +994,23 @@ size_t hmm_lds_bytes(uint32_t n_gt, uint32_t ploidy)
 }
 
 namespace {
+// how many wavefronts a chain gets and how much LDS its workgroup asks for, for both recursion launchers
+uint32_t hmm_waves_and_lds(uint32_t n_chains, size_t plain_lds, size_t& lds)
+{
+    // A small launch asks for more than half a CU's LDS: its workgroups then have a CU each.  The parts of a sample are
+    // launches of a few dozen chains on streams of their own; the dispatcher starts each at the same CUs, and chains that
+    // share a SIMD wait for each other's instructions (measured: 450 instead of 400 ms for the later parts).
+    const size_t alone = 84 * 1024;
+    const bool spread = n_chains <= 64 && plain_lds < alone;
+    lds = spread ? alone : plain_lds;
+    uint32_t waves = spread ? 4u : 2u;
+    if (const char* w = getenv("VGMI_HMM_WAVES")) waves = atoi(w) == 4 ? 4u : 2u;     // A/B
+    // (Several callers on one device -- the samples of a run side by side -- need nothing special: a SIMD runs two of these
+    // wavefronts at little more than one's pace, a chain is latency; tools/gpu_hmm_pack.sh, 1 000 steps of 120 genotypes: 60 chains in
+    // one launch 33.5 ms, 480 chains 39.6 ms, 960 chains 39.5 ms in the dense layout -- and 78.7 ms packed two workgroups to a CU.)
+    return waves;
+}
+
 template <uint32_t STRIDE, uint32_t WAVES>
 hipError_t launch_recursion_as(const HmmParams& Q, uint32_t n_chains, size_t lds, size_t plain_lds, hipStream_t st)
 {
@@ -926,17 +1068,8 @@ hipError_t launch_hmm_recursion(const HmmParams& P, uint32_t n_chains, hipStream
         }
     }
     const size_t plain_lds = hmm_lds_bytes(P.n_gt, P.ploidy);
-    // A small launch asks for more than half a CU's LDS: its workgroups then have a CU each.  The parts of a sample are
-    // launches of a few dozen chains on streams of their own; the dispatcher starts each at the same CUs, and chains that
-    // share a SIMD wait for each other's instructions (measured: 450 instead of 400 ms for the later parts).
-    const size_t alone = 84 * 1024;
-    const bool spread = n_chains <= 64 && plain_lds < alone;
-    const size_t lds = spread ? alone : plain_lds;
-    uint32_t waves = spread ? 4u : 2u;
-    if (const char* w = getenv("VGMI_HMM_WAVES")) waves = atoi(w) == 4 ? 4u : 2u;     // A/B
-    // (Several callers on one device -- the samples of a run side by side -- need nothing special: a SIMD runs two of these
-    // wavefronts at little more than one's pace, a chain is latency; tools/gpu_hmm_pack.sh, 1 000 steps of 120 genotypes: 60 chains in
-    // one launch 33.5 ms, 480 chains 39.6 ms, 960 chains 39.5 ms in the dense layout -- and 78.7 ms packed two workgroups to a CU.)
+    size_t lds = 0;
+    const uint32_t waves = hmm_waves_and_lds(n_chains, plain_lds, lds);
     HmmParams Q = P;
     Q.dbg = vgmi_dbg_env();
     switch (P.ploidy) {
@@ -944,6 +1077,44 @@ hipError_t launch_hmm_recursion(const HmmParams& P, uint32_t n_chains, hipStream
         case 2: return launch_recursion_waves<3>(waves, Q, n_chains, lds, plain_lds, st);
         case 3: return launch_recursion_waves<4>(waves, Q, n_chains, lds, plain_lds, st);
         case 4: return launch_recursion_waves<5>(waves, Q, n_chains, lds, plain_lds, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+namespace {
+template <uint32_t PLOIDY, uint32_t WAVES>
+hipError_t launch_recursion_fre_as(const HmmFreParams& P, uint32_t n_chains, size_t lds, size_t plain_lds, hipStream_t st)
+{
+    if (lds > plain_lds &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(hmm_recursion_fre_kernel<PLOIDY, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess) {
+        (void)hipGetLastError();    // not granted: the plain launch
+        lds = plain_lds;
+    }
+    hipLaunchKernelGGL((hmm_recursion_fre_kernel<PLOIDY, WAVES>), dim3(n_chains), dim3(64 * WAVES), lds, st, P);
+    return hipGetLastError();
+}
+template <uint32_t PLOIDY>
+hipError_t launch_recursion_fre_waves(uint32_t waves, const HmmFreParams& P, uint32_t n_chains, size_t lds, size_t plain_lds, hipStream_t st)
+{
+    switch (waves) {
+        case 4: return launch_recursion_fre_as<PLOIDY, 4>(P, n_chains, lds, plain_lds, st);
+        default: return launch_recursion_fre_as<PLOIDY, 2>(P, n_chains, lds, plain_lds, st);
+    }
+}
+}  // namespace
+
+hipError_t launch_hmm_recursion_fre(const HmmFreParams& P, uint32_t n_chains, hipStream_t st)
+{
+    if (n_chains == 0) return hipSuccess;
+    if (P.n_gt < 1 || P.n_gt > 128 || !P.freq) return hipErrorInvalidValue;
+    const size_t plain_lds = (size_t)2 * 128 * 12 + 64;      // two rows of 128 values
+    size_t lds = 0;
+    const uint32_t waves = hmm_waves_and_lds(n_chains, plain_lds, lds);
+    switch (P.ploidy) {
+        case 2: return launch_recursion_fre_waves<2>(waves, P, n_chains, lds, plain_lds, st);
+        case 3: return launch_recursion_fre_waves<3>(waves, P, n_chains, lds, plain_lds, st);
+        case 4: return launch_recursion_fre_waves<4>(waves, P, n_chains, lds, plain_lds, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -245,6 +245,18 @@ struct HmmParams {
     uint32_t dbg;                   // VGMI_DBG ablations (wrong results): 1 no sum over entries, 2 no terms, 4 no division; 8 no skipped terms (right results)
 };
 hipError_t launch_hmm_recursion(const HmmParams& P, uint32_t n_chains, hipStream_t st);
+// ... under `-m fre` (transitions by haplotype frequency): no keep matrix and no powers, a table of factors per window instead
+struct HmmFreParams {
+    uint32_t n_gt, ploidy;          // genotypes per window (<= 128: one lane per genotype), haplotypes per genotype (2 .. 4)
+    const uint8_t* freq;            // per table: n_gt x ploidy factors, 16 bytes each -- genotype g's q-th haplotype's score at (g * ploidy + q)
+    const uint8_t* obs;             // as in HmmParams from here on; a chain's keep_index names its table
+    const uint32_t* row;
+    const uint8_t* restart;
+    const uint8_t* uniform;
+    const HmmChain* chains;
+    uint8_t* out;
+};
+hipError_t launch_hmm_recursion_fre(const HmmFreParams& P, uint32_t n_chains, hipStream_t st);
 struct HmmPostParams {
     uint32_t n_gt;
     uint64_t row0;                  // the launch's first row (workgroup b takes row0 + b)

@@ -83,6 +83,7 @@ def load_library():
         "vgmi_bloom_add_seq": (i32, [vp, vp, u64, u32]),
         "vgmi_bloom_add_seq_device": (i32, [vp, vp, u64, u32]),
         "vgmi_hmm_recursion": (i32, [vp, u32, u32, vp, u32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, u32, vp]),
+        "vgmi_hmm_recursion_fre": (i32, [vp, u32, u32, vp, u32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, u32, vp]),
         "vgmi_hmm_calls": (i32, [vp, u32, u32, vp, u32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "vgmi_hmm_calls_part": (i32, [vp, u32, u32, vp, u32, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, u32,
                                       vp, vp, vp, vp, vp, vp]),
@@ -108,6 +109,7 @@ def load_library():
         "vgmi_hmm_part_calls_plan": (i32, [vp, vp, vp, vp]),
         "vgmi_hmm_plan_free": (None, [vp]),
         "vgmi_hmm_part_calls": (i32, [vp, u32, vp, u32, vp, vp, vp, C.c_uint64, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
+        "vgmi_hmm_part_calls_fre": (i32, [vp, u32, vp, u32, vp, vp, C.c_uint64, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
         "vgmi_hmm_part_fetch": (i32, [vp, vp]),
         "vgmi_hmm_part_free": (None, [vp]),
         "vgmi_bloom_fetch": (i32, [vp, vp]),
@@ -502,6 +504,28 @@ class Context:
                                               _ptr(restart), _ptr(pow_tables), row.size, _ptr(uni), _ptr(ch), len(chains), _ptr(out)))
         return out
 
+    def hmm_recursion_fre(self, freq, obs, row, restart, uniform, chains, ploidy, n_tables=None):
+        """The recursion under `-m fre` (vgmi_hmm_recursion_fre).  freq: (tables, n_gt, ploidy) longdouble, genotype g's q-th haplotype's
+        score in table t (None: a NULL pointer); a chain's third item names its table; n_tables: what the call is told when not freq's
+        first dimension; the rest as hmm_recursion.  Returns (steps, n_gt) longdouble."""
+        if freq is not None:
+            freq = np.ascontiguousarray(freq, dtype=np.longdouble)
+        if n_tables is None:
+            n_tables = 0 if freq is None else freq.shape[0]
+        obs = np.ascontiguousarray(obs, dtype=np.longdouble)
+        row = np.ascontiguousarray(row, dtype=np.uint32)
+        restart = np.ascontiguousarray(restart, dtype=np.uint8)
+        uni = np.ascontiguousarray([uniform], dtype=np.longdouble)
+        n_gt = obs.shape[1]
+        ch = np.zeros((len(chains), 3), dtype=np.uint64)
+        for i, (f, n, k) in enumerate(chains):
+            ch[i] = (f, n, k)
+        out = np.zeros((row.size, n_gt), dtype=np.longdouble)
+        assert obs.itemsize == 16
+        self._chk(self._l.vgmi_hmm_recursion_fre(self._h, n_gt, ploidy, _ptr(freq), n_tables, _ptr(obs),
+                                                  obs.shape[0], _ptr(row), _ptr(restart), row.size, _ptr(uni), _ptr(ch), len(chains), _ptr(out)))
+        return out
+
     def hmm_calls(self, keep, obs, row, restart, pow_tables, uniform, chains, ploidy, gid, order, fwd_step, bwd_step):
         """hmm_recursion followed by the posterior on the device (vgmi_hmm_calls): returns (prob, winner, alpha_beta)."""
         keep = np.ascontiguousarray(keep, dtype=np.uint8)
@@ -531,7 +555,8 @@ class Context:
         """vgmi_hmm_entries_upload + _sample_upload + _emissions + _part_fetch: returns (obs (rows, n_gt) longdouble, n_kept, flags).
         fixes = (rows, off, j, mask): vgmi_hmm_part_fix_rows before the fetch.  calls = dict(ploidy, keep, row, restart, pow, uniform,
         chains, gid, order, fwd, bwd): the part's recursion and posterior both ways -- vgmi_hmm_part_calls with host arrays and
-        vgmi_hmm_plan_create + vgmi_hmm_part_calls_plan -- returned as a fourth item ((prob, winner), (prob, winner))."""
+        vgmi_hmm_plan_create + vgmi_hmm_part_calls_plan -- returned as a fourth item ((prob, winner), (prob, winner)).  calls with freq
+        ((tables, n_gt, ploidy) longdouble) in place of keep and pow: vgmi_hmm_part_calls_fre, the fourth item is ((prob, winner),)."""
         entries = np.ascontiguousarray(entries, dtype=np.uint64)
         cov_node = np.ascontiguousarray(cov_node, dtype=np.uint8)
         used = np.ascontiguousarray(used, dtype=np.uint8)
@@ -569,10 +594,14 @@ class Context:
             obs = np.zeros((n_rows, n_gt), dtype=np.longdouble)
             self._chk(self._l.vgmi_hmm_part_fetch(part, _ptr(obs)))
             if calls is not None:
-                keep = np.ascontiguousarray(calls["keep"], dtype=np.uint8)
+                by_freq = "freq" in calls
+                if by_freq:
+                    freq = np.ascontiguousarray(calls["freq"], dtype=np.longdouble)
+                else:
+                    keep = np.ascontiguousarray(calls["keep"], dtype=np.uint8)
+                    pw = np.ascontiguousarray(calls["pow"], dtype=np.longdouble)
                 row = np.ascontiguousarray(calls["row"], dtype=np.uint32)
                 restart = np.ascontiguousarray(calls["restart"], dtype=np.uint8)
-                pw = np.ascontiguousarray(calls["pow"], dtype=np.longdouble)
                 uni = np.ascontiguousarray([calls["uniform"]], dtype=np.longdouble)
                 ch = np.zeros((len(calls["chains"]), 3), dtype=np.uint64)
                 for i, (f, n, k) in enumerate(calls["chains"]):
@@ -583,6 +612,10 @@ class Context:
                 bwd = np.ascontiguousarray(calls["bwd"], dtype=np.uint64)
                 out = []
                 p1, w1 = np.zeros(n_rows, dtype=np.longdouble), np.zeros(n_rows, dtype=np.uint32)
+                if by_freq:
+                    self._chk(self._l.vgmi_hmm_part_calls_fre(part, calls["ploidy"], _ptr(freq), freq.shape[0], _ptr(row), _ptr(restart), row.size, _ptr(uni),
+                                                               _ptr(ch), len(calls["chains"]), _ptr(gid), _ptr(order), _ptr(fwd), _ptr(bwd), _ptr(p1), _ptr(w1)))
+                    return obs, n_kept[:n_rows], flags[:n_rows], ((p1, w1),)
                 self._chk(self._l.vgmi_hmm_part_calls(part, calls["ploidy"], _ptr(keep), 1, _ptr(row), _ptr(restart), _ptr(pw), row.size, _ptr(uni), _ptr(ch),
                                                        len(calls["chains"]), _ptr(gid), _ptr(order), _ptr(fwd), _ptr(bwd), _ptr(p1), _ptr(w1)))
                 plan = C.c_void_p()
