@@ -21,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 STREAM = ("short_literal_runs", "big_member", "distances_x_lengths")      # members of the stream-form run
 PIECES = (None, 150_000)
 LEAD = "short_literal_runs"                                               # the good member in front of every refused block-gzip member
+BGZF_DATA = 18                                                            # a block-gzip member's header: its DEFLATE bytes start here
 
 
 def _b64(b):
@@ -29,6 +30,35 @@ def _b64(b):
 
 def _keep(r):
     return {k: (_b64(v) if isinstance(v, bytes) else v) for k, v in r.items()}
+
+
+_RESIDUES = None
+
+
+def residue_members():
+    """Eight block-gzip members -- FASTQ records around the blocks of stored_alignments (stored, fixed, dynamic) and dynamic_headers in
+    turn -- whose DEFLATE bytes start at every residue mod 4 of the file offset: the device reads a member's input as aligned words
+    from wherever it lies.  A character more in a record's name is a byte more of DEFLATE data (a fixed code of eight bits), so every
+    member is given the name that makes its size 1 mod 4: each starts a residue behind the one before it.
+    -> (the members, their texts, the kinds of block in them)"""
+    global _RESIDUES
+    if _RESIDUES is None:
+        import deflate_builder as db
+        import test_deflate_shapes_cpu as shapes
+        members, texts, kinds = [], [], set()
+        for i in range(8):
+            inner = shapes._case_stored_alignments() if i % 2 == 0 else shapes._case_headers()
+            for pad in range(4):
+                blocks = shapes._record(inner, name=b"m%d" % i + b"x" * pad)
+                text = shapes._tokens_text(blocks)
+                m = db.bgzf_member(db.deflate(blocks), text)
+                if len(m) % 4 == 1:
+                    break
+            members.append(m)
+            texts.append(text)
+            kinds |= {type(b).__name__ for b in blocks}
+        _RESIDUES = members, texts, kinds
+    return _RESIDUES
 
 
 def run_all():
@@ -53,6 +83,10 @@ def run_all():
             r = c.fastq_bgzf(comp)
             cov, _, _ = c.counts_finish()
             res[key] = dict(_keep(r), cov=_b64(cov.tobytes()))
+        c.counts_reset()
+        r = c.fastq_bgzf(b"".join(residue_members()[0]) + db.BGZF_EOF)
+        cov, _, _ = c.counts_finish()
+        res["bgzf_residues"] = dict(_keep(r), cov=_b64(cov.tobytes()))
         lead = shapes.by_name(LEAD).bz()
         for k in cases:
             if not k.ok and k.bgzf:
@@ -143,6 +177,28 @@ def check_bgzf(res):
         assert r["consumed"] + len(base64.b64decode(r["tail"])) == len(lead.text) and r["n_records"] <= 1, k.name
 
 
+def check_residues(res):
+    import deflate_builder as db
+    import zlib
+    members, texts, kinds = residue_members()
+    # where every member's DEFLATE bytes start in the file, from the sizes written
+    starts = [sum(len(m) for m in members[:i]) + BGZF_DATA for i in range(len(members))]
+    assert len(members) >= 8 and {s % 4 for s in starts} == {0, 1, 2, 3}, starts
+    assert kinds == {"Stored", "Fixed", "Dynamic"}
+    for m, t in zip(members, texts):
+        assert zlib.decompressobj(-15).decompress(m[BGZF_DATA:-8]) == t
+    assert sum(len(t) for t in texts) < 16384
+    r = res["bgzf_residues"]
+    total = sum(len(m) for m in members) + len(db.BGZF_EOF)
+    if "residues" not in _WANT:
+        _WANT["residues"] = _counts(texts)
+    n_rec, want = _WANT["residues"]
+    assert not r["inflate_failed"] and not r["stopped"], (r["reason"], r["good_compressed_bytes"])
+    assert r["taken"] == r["good_compressed_bytes"] == total
+    assert r["consumed"] == sum(len(t) for t in texts) and r["n_records"] == n_rec == len(members) and base64.b64decode(r["tail"]) == b""
+    assert np.array_equal(np.frombuffer(base64.b64decode(r["cov"]), dtype=np.uint8), want) and want.any()
+
+
 def check_stream(res):
     import test_deflate_shapes_cpu as shapes
     n_rec, want = _want("stream", STREAM)
@@ -180,6 +236,10 @@ def test_block_gzip_wide(wide):
     check_bgzf(wide)
 
 
+def test_block_gzip_members_at_every_alignment_wide(wide):
+    check_residues(wide)
+
+
 def test_gzip_stream_wide(wide):
     check_stream(wide)
 
@@ -190,6 +250,10 @@ def test_ordinary_gzip_first_form(first_form):
 
 def test_block_gzip_first_form(first_form):
     check_bgzf(first_form)
+
+
+def test_block_gzip_members_at_every_alignment_first_form(first_form):
+    check_residues(first_form)
 
 
 def test_gzip_stream_first_form(first_form):

@@ -8,8 +8,8 @@
 //                          dynamic-code block can start: 64 bit positions per step against the cheap tests (BFINAL = 0, BTYPE = 2,
 //                          HLIT / HDIST in range, the code-length code's Kraft sum exact), survivors against the whole header
 //                          (literal/length and distance codes complete).
-//   2. gz_decode_kernel    a wavefront per stretch between two such starts decodes it the way vgmi_inflate.hip decodes a block-gzip
-//                          member (batches of 64 bit positions), but into 16-bit SYMBOLS: a back-reference that reaches in front
+//   2. gz_decode_kernel    a wavefront per stretch between two such starts decodes it with the block decoder vgmi_inflate.hip decodes a
+//                          block-gzip member with (inf_block of vgmi_inflate_dev.h; GzSink here), but into 16-bit SYMBOLS: a back-reference that reaches in front
 //                          of the stretch -- into the 32 KiB window it cannot know -- yields placeholders 256 + (offset into that
 //                          window), which later copies propagate like bytes.  A stretch must END exactly where the next one starts:
 //                          that is the check of the guessed start (by induction from the stream's true first bit every start in an
@@ -21,7 +21,6 @@
 // at a known compressed offset and the host decoder (csrc/host/fast_inflate.cpp) goes on from there with the window it is handed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -71,59 +70,22 @@ __global__ __launch_bounds__(64 * GZ_FIND_WAVES, 8) void gz_find_kernel(const ui
     if (to > end_bits - (end_bits < 2048u ? end_bits : 2048u)) to = end_bits - (end_bits < 2048u ? end_bits : 2048u);    // a header needs room
     uint32_t found = GZ_NONE;
 
-    // scalar bit reader (vgmi_inflate.hip's), restarted per candidate
-    uint64_t bitbuf = 0;
-    uint32_t bitcnt = 0, ip = 0;
-    const uint32_t* wq;
-    uint32_t wa, wb, wc;
-    auto reload = [&]() {
-        const uint32_t lead = ip & 3u;
-        wq = in4 + (ip >> 2);
-        wa = ld32u(wq);
-        wb = ld32u(wq + 1);
-        wc = ld32u(wq + 2);
-        bitbuf = (uint64_t)(wa >> (8u * lead));
-        bitcnt = 32u - 8u * lead;
-        ip += 4u - lead;
-        wa = wb;
-        wb = wc;
-        wc = ld32u(wq + 3);
-        ++wq;
-    };
-    auto refill = [&]() {
-        if (bitcnt <= 32u) {
-            bitbuf |= (uint64_t)wa << bitcnt;
-            bitcnt += 32u;
-            ip += 4u;
-            wa = wb;
-            wb = wc;
-            wc = ld32u(wq + 3);
-            ++wq;
-        }
-    };
-    auto take = [&](uint32_t n) -> uint32_t {
-        const uint32_t v = (uint32_t)bitbuf & ((1u << n) - 1u);
-        bitbuf >>= n;
-        bitcnt -= n;
-        return v;
-    };
+    InfBits r;      // restarted per candidate
     // the whole header at bit p: three complete codes (what every encoder writes)?
     auto header_ok = [&](uint32_t p) -> bool {
-        ip = p >> 3;
-        reload();
-        take(p & 7u);
-        refill();
-        take(3);
-        const uint32_t hlit = take(5) + 257, hdist = take(5) + 1, hclen = take(4) + 4;
+        r.start(comp, p);
+        r.refill();
+        r.take(3);
+        const uint32_t hlit = r.take(5) + 257, hdist = r.take(5) + 1, hclen = r.take(4) + 4;
         if (hlit > 286 || hdist > 30) return false;
         // The code-length code (19 symbols, lengths of 3 bits in the order of RFC 1951 3.2.7), built in registers: lane s holds symbol
         // s; counts per length by ballot, a symbol's canonical code = first code of its length + its rank among the symbols of that
         // length; every lane then fills two of the 128 entries of the 7-bit decoding table.  (The general table builder -- serial
         // loops of one lane over LDS -- cost 60 000 clock ticks a candidate, two thirds of this kernel: gpurun_out/r4w3.)
-        refill();
-        const uint32_t f_lo = take(30);
-        refill();
-        const uint64_t F = ((uint64_t)take(27) << 30 | f_lo) & ((1ull << (3u * hclen)) - 1ull);
+        r.refill();
+        const uint32_t f_lo = r.take(30);
+        r.refill();
+        const uint64_t F = ((uint64_t)r.take(27) << 30 | f_lo) & ((1ull << (3u * hclen)) - 1ull);
         const uint32_t my_i = lane < 19 ? (uint32_t)gz_clen_inv[lane] : 63u;
         const uint32_t my_l = my_i < 19 ? (uint32_t)(F >> (3u * my_i)) & 7u : 0u;
         uint32_t first[8], cnt[8], off[8], my_off = 0;
@@ -157,9 +119,7 @@ __global__ __launch_bounds__(64 * GZ_FIND_WAVES, 8) void gz_find_kernel(const ui
         }
         inf_sync();
         // the reader goes on behind the 3-bit lengths
-        ip = (p + 17u + 3u * hclen) >> 3;
-        reload();
-        take((p + 17u + 3u * hclen) & 7u);
+        r.start(comp, p + 17u + 3u * hclen);
         // the hlit + hdist code lengths, with the Kraft sums of the two codes kept as they come (32768 = complete): a candidate that
         // is no header over-subscribes one of them within a few dozen lengths and ends there (decoding all ~300 lengths of every
         // false candidate was two thirds of this kernel)
@@ -177,12 +137,12 @@ __global__ __launch_bounds__(64 * GZ_FIND_WAVES, 8) void gz_find_kernel(const ui
             }
         };
         while (idx < hlit + hdist) {
-            refill();
-            const uint32_t i7 = (uint32_t)bitbuf & 127u;
+            r.refill();
+            const uint32_t i7 = (uint32_t)r.bitbuf & 127u;
             const uint32_t e = (i7 & 64u) ? (uint32_t)__builtin_amdgcn_readlane((int)ent[1], (int)(i7 & 63u)) : (uint32_t)__builtin_amdgcn_readlane((int)ent[0], (int)i7);
             const uint32_t l = e & 15u, sym = e >> 4;
             if (!l) { bad = true; break; }
-            take(l);
+            r.take(l);
             if (sym < 16) {
                 put(idx++, sym);
                 prev = sym;
@@ -191,9 +151,9 @@ __global__ __launch_bounds__(64 * GZ_FIND_WAVES, 8) void gz_find_kernel(const ui
                 if (sym == 16) {
                     if (idx == 0) { bad = true; break; }
                     val = prev;
-                    rep = 3 + take(2);
-                } else if (sym == 17) rep = 3 + take(3);
-                else rep = 11 + take(7);
+                    rep = 3 + r.take(2);
+                } else if (sym == 17) rep = 3 + r.take(3);
+                else rep = 11 + r.take(7);
                 if (idx + rep > hlit + hdist) { bad = true; break; }
                 if (val) {      // a run of equal lengths, taken whole: what falls in front of hlit is literal/length code, the rest distance code
                     const uint32_t n_lit = idx < hlit ? (rep < hlit - idx ? rep : hlit - idx) : 0u, n_dist = rep - n_lit, c = 32768u >> val;
@@ -277,318 +237,111 @@ struct GzSegOut {
     uint32_t final_block;  // the last decoded block carried BFINAL: the member ends at end_bit
 };
 
+// What a stretch of an ordinary gzip stream gives the block decoder (vgmi_inflate_dev.h: inf_block).  The batch buffer is 256-byte
+// aligned and ends at n_bytes; the output is 16-bit symbols in the stretch's slice of the pool: bytes, and placeholders
+// 256 + GZ_WIN + q (q < 0) for the text in front of the stretch that a match reaches into.
 template <bool WIDE>
-__global__ __launch_bounds__(64 * (WIDE ? GZW_WAVES : GZ_WAVES), WIDE ? 2 : 4) void gz_decode_kernel(const uint8_t* __restrict__ comp, uint32_t n_bytes, const GzSeg* __restrict__ segs,
-                                                                            uint32_t n_seg, uint16_t* __restrict__ pool, GzSegOut* __restrict__ outs)
-{
-    typedef InfWideT<uint16_t, 4096> WideTables;      // (2 048 entries and batches of 704 symbols leave LDS for twelve wavefronts a CU
-                                                       // instead of eight, and cost 17.5 against 10.5 ms a piece: gpurun_out/r4w12)
-    typedef typename std::conditional<WIDE, WideTables, InfTablesT<uint16_t>>::type GzTables;
-    constexpr uint32_t RING = WIDE ? WideTables::kRing : INF_RING, NEAR = WIDE ? WideTables::kNear : INF_NEAR;
-    constexpr uint32_t WAVES = WIDE ? GZW_WAVES : GZ_WAVES;
-    __shared__ GzTables tabs[WAVES];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave_in_block = uni(threadIdx.x >> 6);
-    const uint32_t sg = blockIdx.x * WAVES + wave_in_block;
-    if (sg >= n_seg) return;
-    GzTables& t = tabs[wave_in_block];
-    const uint8_t* const in = comp;
-    const uint32_t* const in4 = reinterpret_cast<const uint32_t*>(comp);
-    const uint32_t end_bits = n_bytes * 8u;
-    const uint32_t stop_bit = uni(segs[sg].stop_bit);
-    uint16_t* const out = pool + uni(segs[sg].sym_off);
-    const uint32_t out_cap = uni(segs[sg].sym_cap);
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(out_cap * 2u), 0x00020000);
-    uint32_t* const ring32 = reinterpret_cast<uint32_t*>(t.ring);
-    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(comp), 0, (int)((n_bytes + 3u) & ~3u), 0x00020000);
+struct GzSink {
+    // The wide tables' size: 2 048 entries and batches of 704 symbols leave LDS for twelve wavefronts a CU instead of eight, and cost
+    // 17.5 against 10.5 ms a piece (measured in round 4)
+    typedef InfWideT<uint16_t, 4096> WideTables;
+    typedef typename std::conditional<WIDE, WideTables, InfTablesT<uint16_t>>::type Tables;
+    typedef uint16_t Ring;
+    static constexpr uint32_t kRing = WIDE ? WideTables::kRing : INF_RING, kNear = WIDE ? WideTables::kNear : INF_NEAR;
+    static constexpr uint32_t kStored = 128u;
+    static constexpr uint32_t lead_bits = 0u;
+    Tables& t;
+    const uint32_t lane;
+    const uint8_t* const in;
+    const uint32_t* const in4;
+    const uint32_t n_bytes, end_bits;
+    const __amdgpu_buffer_rsrc_t irsrc;
+    uint16_t* const out;
+    const uint32_t cap;                            // room in the symbol pool
+    const __amdgpu_buffer_rsrc_t orsrc;
+    uint32_t* const ring32;
+    const uint32_t back_ok;                        // text that exists in front of the stretch (GzSeg::win_avail)
+    uint32_t flushed = 0;
+    uint32_t block_end_bit;                        // end of the last block decoded whole
 
-    uint32_t bp = uni(segs[sg].start_bit);
-    const uint32_t win_avail = uni(segs[sg].win_avail);
-    uint32_t op = 0, flushed = 0, err = 0;
+    __device__ __forceinline__ GzSink(Tables& t_, uint32_t lane_, const uint8_t* comp, uint32_t n_bytes_, uint16_t* out_, uint32_t out_cap, uint32_t win_avail,
+                                      uint32_t start_bit)
+        : t(t_), lane(lane_), in(comp), in4(reinterpret_cast<const uint32_t*>(comp)), n_bytes(n_bytes_), end_bits(n_bytes_ * 8u),
+          irsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(comp), 0, (int)((n_bytes_ + 3u) & ~3u), 0x00020000)), out(out_), cap(out_cap),
+          orsrc(__builtin_amdgcn_make_buffer_rsrc(out_, 0, (int)(out_cap * 2u), 0x00020000)), ring32(reinterpret_cast<uint32_t*>(t_.ring)), back_ok(win_avail),
+          block_end_bit(start_bit)
+    {
+    }
 
+    __device__ __forceinline__ uint32_t stored_overrun(uint32_t src, uint32_t len, uint32_t op) const
+    {
+        if (src + len > n_bytes) return 9;
+        return op + len > cap ? 3u : 0u;
+    }
+    // full: the stretch outgrows its room; else the symbols may have run into the padding behind the data
+    __device__ __forceinline__ uint32_t overrun(bool full, uint32_t bp, uint32_t adv) const { return full ? 3u : bp + adv > end_bits ? 9u : 0u; }
+    __device__ __forceinline__ uint32_t slow_overrun(uint32_t bp) const { return bp > end_bits ? 9u : 0u; }
+    __device__ __forceinline__ void block_end(uint32_t bp, uint32_t err)
+    {
+        if (!err) block_end_bit = bp;
+    }
     // ring -> global memory: whole blocks of 128 symbols (the pool slice is word aligned); all of it at the end
-    auto flush = [&](bool all) {
+    __device__ __forceinline__ void flush(uint32_t op, bool all)
+    {
         while (op - flushed >= 128u) {
-            const uint32_t r = (flushed + 2u * lane) & (RING - 1u);
+            const uint32_t r = (flushed + 2u * lane) & (kRing - 1u);
             __builtin_amdgcn_raw_buffer_store_b32(ring32[r >> 1], orsrc, (flushed + 2u * lane) * 2u, 0, 0);
             flushed += 128u;
         }
         if (all)
             while (flushed < op) {
                 const uint32_t p = flushed + lane;
-                if (p < op) __builtin_amdgcn_raw_buffer_store_b16(t.ring[p & (RING - 1u)], orsrc, p * 2u, 0, 0);
+                if (p < op) __builtin_amdgcn_raw_buffer_store_b16(t.ring[p & (kRing - 1u)], orsrc, p * 2u, 0, 0);
                 flushed = flushed + 64u < op ? flushed + 64u : op;
             }
-    };
+    }
     // one LZ77 match at output position P: sources in front of the stretch are placeholders for the window it does not know
-    auto copy_match = [&](uint32_t P, uint32_t len, uint32_t dist) {
-        const bool far = dist > NEAR;
-        if (far) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // flushed symbols are read back (see vgmi_inflate.hip)
+    __device__ __forceinline__ void copy_match(uint32_t P, uint32_t len, uint32_t dist)
+    {
+        const bool far = dist > kNear;
+        if (far) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // flushed symbols are read back (see BgzfSink::copy_match)
         for (uint32_t i = lane; i < len; i += 64) {
             const int32_t q = (int32_t)(P - dist + (dist >= len ? i : i % dist));
             uint16_t v;
             if (q < 0) v = (uint16_t)(256 + (int32_t)GZ_WIN + q);
-            else v = far ? out[q] : t.ring[(uint32_t)q & (RING - 1u)];
-            t.ring[(P + i) & (RING - 1u)] = v;
+            else v = far ? out[q] : t.ring[(uint32_t)q & (kRing - 1u)];
+            t.ring[(P + i) & (kRing - 1u)] = v;
         }
         inf_sync();
-    };
-
-    uint64_t bitbuf = 0;
-    uint32_t bitcnt = 0, ip = 0;
-    const uint32_t* wq;
-    uint32_t wa, wb, wc;
-    auto reload = [&]() {
-        const uint32_t lead = ip & 3u;
-        wq = in4 + (ip >> 2);
-        wa = ld32u(wq);
-        wb = ld32u(wq + 1);
-        wc = ld32u(wq + 2);
-        bitbuf = (uint64_t)(wa >> (8u * lead));
-        bitcnt = 32u - 8u * lead;
-        ip += 4u - lead;
-        wa = wb;
-        wb = wc;
-        wc = ld32u(wq + 3);
-        ++wq;
-    };
-    auto refill = [&]() {
-        if (bitcnt <= 32u) {
-            bitbuf |= (uint64_t)wa << bitcnt;
-            bitcnt += 32u;
-            ip += 4u;
-            wa = wb;
-            wb = wc;
-            wc = ld32u(wq + 3);
-            ++wq;
-        }
-    };
-    auto need = [&](uint32_t n) { if (bitcnt < n) refill(); };
-    auto take = [&](uint32_t n) -> uint32_t {
-        const uint32_t v = (uint32_t)bitbuf & ((1u << n) - 1u);
-        bitbuf >>= n;
-        bitcnt -= n;
-        return v;
-    };
-    auto scalar_at_bp = [&]() {
-        ip = bp >> 3;
-        reload();
-        take(bp & 7u);
-    };
-    auto scalar_done = [&]() { bp = 8u * ip - bitcnt; };
-
-    bool last = false;
-    uint32_t block_end = bp;        // end of the last block decoded whole
-    while (!last && !err && bp < stop_bit) {
-        if (bp + 3u > end_bits) { err = 9; break; }
-        scalar_at_bp();
-        refill();
-        last = take(1) != 0;
-        const uint32_t type = take(2);
-        if (type == 0) {            // stored
-            take(bitcnt & 7u);
-            refill();
-            const uint32_t len = take(16), nlen = take(16);
-            if ((len ^ 0xFFFFu) != nlen) { err = 6; break; }
-            const uint32_t src = ip - (bitcnt >> 3);
-            if (src + len > n_bytes) { err = 9; break; }
-            if (op + len > out_cap) { err = 3; break; }
-            for (uint32_t done = 0; done < len;) {
-                const uint32_t n = len - done < 128u ? len - done : 128u;
-                for (uint32_t i = lane; i < n; i += 64) t.ring[(op + i) & (RING - 1u)] = in[src + done + i];
-                inf_sync();
-                op += n;
-                done += n;
-                flush(false);
-            }
-            bp = 8u * (src + len);
-            block_end = bp;
-            continue;
-        }
-        if (type == 3) { err = 7; break; }
-        if (type == 1) {
-            for (uint32_t s = lane; s < 288; s += 64) t.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-            if (lane < 32) t.len[288 + lane] = 5;
-            inf_sync();
-            if (!inf_build(t, 0, 0, 288, lane) || !inf_build(t, 1, 288, 30, lane, INF_INC_ANY)) { err = 1; break; }
-        } else {
-            const uint32_t hlit = take(5) + 257, hdist = take(5) + 1, hclen = take(4) + 4;
-            if (hlit > 286 || hdist > 30) { err = 1; break; }
-            refill();
-            if (lane < 19) t.len[288 + lane] = 0;
-            inf_sync();
-            for (uint32_t i = 0; i < hclen; ++i) {
-                if (bitcnt < 3) refill();
-                const uint32_t v = take(3);
-                if (lane == 0) t.len[288 + uni(inf_clen_order[i])] = (uint8_t)v;
-            }
-            inf_sync();
-            if (!inf_build(t, 1, 288, 19, lane, INF_INC_NONE)) { err = 1; break; }
-            uint32_t idx = 0, prev = 0;
-            uint8_t* const stage = reinterpret_cast<uint8_t*>(t.lit);
-            auto put = [&](uint32_t i, uint32_t v) { if (lane == 0) stage[i] = (uint8_t)v; };
-            while (idx < hlit + hdist && !err) {
-                refill();
-                const uint32_t e = uni(t.dist[(uint32_t)bitbuf & ((1u << INF_DIST_BITS) - 1u)]);
-                const uint32_t l = e & 15u, sym = e >> 4;
-                if (!l) { err = 1; break; }
-                take(l);
-                if (sym < 16) {
-                    put(idx++, sym);
-                    prev = sym;
-                } else {
-                    uint32_t rep, val = 0;
-                    if (sym == 16) {
-                        if (idx == 0) { err = 1; break; }
-                        val = prev;
-                        rep = 3 + take(2);
-                    } else if (sym == 17) rep = 3 + take(3);
-                    else rep = 11 + take(7);
-                    if (idx + rep > hlit + hdist) { err = 1; break; }
-                    for (uint32_t r = 0; r < rep; ++r) put(idx++, val);
-                    prev = val;
-                }
-            }
-            if (err) break;
-            inf_sync();
-            uint8_t mine[5];
-#pragma unroll
-            for (uint32_t q = 0; q < 5; ++q) {
-                const uint32_t s = lane + 64 * q;
-                uint32_t v = 0;
-                if (s < 288) {
-                    if (s < hlit) v = stage[s];
-                } else if (s - 288 < hdist) v = stage[hlit + (s - 288)];
-                mine[q] = (uint8_t)v;
-            }
-            inf_sync();
-#pragma unroll
-            for (uint32_t q = 0; q < 5; ++q) t.len[lane + 64 * q] = mine[q];
-            inf_sync();
-            if (uni(t.len[256]) == 0) { err = 1; break; }
-            if (!inf_build(t, 0, 0, 288, lane) || !inf_build(t, 1, 288, 30, lane)) { err = 1; break; }
-        }
-        if constexpr (WIDE) {
-            infw_limits(t, 0, lane);
-            infw_limits(t, 1, lane);
-            infw_pack_lit2(t, lane);
-        }
-        inf_pack_lit(t, lane);
-        inf_pack_dist(t, lane);
-        scalar_done();
-
-        bool eob = false;
-        if constexpr (WIDE) {
-            uint32_t nl = 40;      // sub-blocks a batch looks at: what the batches before it got through, and a few
-            while (!eob && !err) {
-                const uint32_t g = bp + 64u * lane;
-                const uint32_t wo = (g >> 5) * 4u, sh = g & 31u;
-                const uint32_t x0 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(irsrc, wo, 0, 0), x1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(irsrc, wo + 4u, 0, 0),
-                               x2 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(irsrc, wo + 8u, 0, 0), x3 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(irsrc, wo + 12u, 0, 0),
-                               x4 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(irsrc, wo + 16u, 0, 0);
-                const uint32_t room = out_cap - op < WideTables::kCap ? out_cap - op : WideTables::kCap;
-                const InfWideOut B = inf_wide<GzTables, uint16_t>(t, __builtin_amdgcn_alignbit(x1, x0, sh), __builtin_amdgcn_alignbit(x2, x1, sh),
-                                                                  __builtin_amdgcn_alignbit(x3, x2, sh), __builtin_amdgcn_alignbit(x4, x3, sh), op, room, nl, lane);
-                if (B.bad) { err = 2; break; }
-                if (!B.adv) { err = 3; break; }                        // the stretch outgrows its room
-                if (bp + B.adv > end_bits) { err = 9; break; }         // the symbols ran into the padding behind the data
-                if (!infw_matches<GzTables, uint16_t, true>(t, B.n_match, op, out, win_avail, lane)) { err = 2; break; }
-                op += B.out;
-                bp += B.adv;
-                eob = B.eob != 0;
-                if (!eob) nl = B.last + 2u >= nl ? (nl + 8u < 64u ? nl + 8u : 64u) : B.last + 4u;
-                flush(false);
-            }
-        } else
-        while (!eob && !err) {
-            const uint32_t b = bp + lane;
-            const uint32_t* const w = in4 + (b >> 5);
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-            const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, b & 31u), hi = __builtin_amdgcn_alignbit(w2, w1, b & 31u);
-            const InfBatch B = inf_batch(t, lo, hi, lane);
-            eob = B.eob;
-            const bool slow = B.slow;
-            const uint32_t off = B.out, pos = B.adv;
-            uint64_t matches = B.matches;
-            if (op + off > out_cap) { err = 3; break; }
-            if (bp + pos > end_bits) { err = 9; break; }       // the symbols ran into the padding behind the data
-            if ((B.lits >> lane) & 1ull) {
-                const uint32_t e = B.e, n = (e >> 6) & 3u, P = op + B.off;
-                if (((e >> 4) & 3u) == 0) {
-                    t.ring[P & (RING - 1u)] = (uint16_t)((e >> 8) & 255u);
-                    if (n > 1) t.ring[(P + 1u) & (RING - 1u)] = (uint16_t)((e >> 16) & 255u);
-                    if (n > 2) t.ring[(P + 2u) & (RING - 1u)] = (uint16_t)(e >> 24);
-                }
-            }
-            inf_sync();
-            while (matches) {
-                const uint32_t ml = (uint32_t)__builtin_ctzll(matches);
-                matches &= matches - 1ull;
-                const uint32_t P = op + (uint32_t)__builtin_amdgcn_readlane((int)B.off, (int)ml);
-                const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)B.mlen, (int)ml);
-                const uint32_t dist = (uint32_t)__builtin_amdgcn_readlane((int)B.mdist, (int)ml);
-                if (dist > P + win_avail) { err = 2; break; }
-                copy_match(P, len, dist);
-            }
-            if (err) break;
-            op += off;
-            bp += pos;
-            flush(false);
-            if (slow) {
-                scalar_at_bp();
-                need(32);
-                uint32_t l;
-                int32_t sym = inf_slow(t, 0, bitbuf, l);
-                sym = (int32_t)uni((uint32_t)sym);
-                l = uni(l);
-                if (sym < 0) { err = 2; break; }
-                take(l);
-                if (sym < 256) {
-                    if (op >= out_cap) { err = 3; break; }
-                    if (lane == 0) t.ring[op & (RING - 1u)] = (uint16_t)sym;
-                    inf_sync();
-                    ++op;
-                } else if (sym == 256) {
-                    eob = true;
-                } else {
-                    sym -= 257;
-                    if (sym >= 29) { err = 2; break; }
-                    uint32_t len;
-                    if (sym < 8) len = 3 + (uint32_t)sym;
-                    else if (sym == 28) len = 258;
-                    else {
-                        const uint32_t x = ((uint32_t)sym >> 2) - 1;
-                        len = ((4u + ((uint32_t)sym & 3u)) << x) + 3u + take(x);
-                    }
-                    need(32);
-                    uint32_t dl2;
-                    int32_t dsym = inf_slow(t, 1, bitbuf, dl2);
-                    dsym = (int32_t)uni((uint32_t)dsym);
-                    dl2 = uni(dl2);
-                    if (dsym < 0 || dsym >= 30) { err = 2; break; }
-                    take(dl2);
-                    uint32_t dist;
-                    if (dsym < 4) dist = 1 + (uint32_t)dsym;
-                    else {
-                        const uint32_t x = ((uint32_t)dsym >> 1) - 1;
-                        dist = ((2u + ((uint32_t)dsym & 1u)) << x) + 1u + take(x);
-                    }
-                    if (dist > op + win_avail) { err = 2; break; }
-                    if (op + len > out_cap) { err = 3; break; }
-                    copy_match(op, len, dist);
-                    op += len;
-                }
-                scalar_done();
-                if (bp > end_bits) { err = 9; break; }
-                flush(false);
-            }
-        }
-        if (!err) block_end = bp;
     }
+    __device__ __forceinline__ bool matches(uint32_t n_match, uint32_t op) { return infw_matches<Tables, uint16_t, true>(t, n_match, op, out, back_ok, lane); }
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(64 * (WIDE ? GZW_WAVES : GZ_WAVES), WIDE ? 2 : 4) void gz_decode_kernel(const uint8_t* __restrict__ comp, uint32_t n_bytes, const GzSeg* __restrict__ segs,
+                                                                            uint32_t n_seg, uint16_t* __restrict__ pool, GzSegOut* __restrict__ outs)
+{
+    typedef typename GzSink<WIDE>::Tables GzTables;
+    constexpr uint32_t WAVES = WIDE ? GZW_WAVES : GZ_WAVES;
+    __shared__ GzTables tabs[WAVES];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave_in_block = uni(threadIdx.x >> 6);
+    const uint32_t sg = blockIdx.x * WAVES + wave_in_block;
+    if (sg >= n_seg) return;
+    const uint32_t stop_bit = uni(segs[sg].stop_bit);
+    uint32_t bp = uni(segs[sg].start_bit);
+    GzSink<WIDE> sink(tabs[wave_in_block], lane, comp, n_bytes, pool + uni(segs[sg].sym_off), uni(segs[sg].sym_cap), uni(segs[sg].win_avail), bp);
+    uint32_t op = 0, err = 0;
+    bool last = false;
+    while (!last && !err && bp < stop_bit) {
+        if (bp + 3u > sink.end_bits) { err = 9; break; }
+        inf_block<WIDE>(sink, bp, op, err, last);
+    }
+    const uint32_t block_end = sink.block_end_bit;
     if (!err && !last && stop_bit != GZ_NONE && block_end != stop_bit) err = 8;
     if (!err && !last && stop_bit == GZ_NONE) err = 9;        // the data ended between two blocks: the stream goes on in the next piece
     // (a member that ends in front of stop_bit is no error of this stretch: the chain ends with it, final_block says so)
-    flush(true);
+    sink.flush(op, true);
     if (lane == 0) outs[sg] = GzSegOut{op, block_end, err, last ? 1u : 0u};
 }
 
@@ -805,7 +558,7 @@ hipError_t launch_gz_find(const uint8_t* comp, uint32_t n_bytes, uint32_t sub_by
 hipError_t launch_gz_decode(const uint8_t* comp, uint32_t n_bytes, const void* segs, uint32_t n_seg, uint16_t* pool, void* outs, hipStream_t st)
 {
     if (n_seg) {
-        static const bool wide = !(getenv("VGMI_INFLATE_WIDE") && getenv("VGMI_INFLATE_WIDE")[0] == '0');
+        const bool wide = inf_wide_form();
         const uint32_t waves = wide ? GZW_WAVES : GZ_WAVES;
         const dim3 grid((n_seg + waves - 1) / waves), block(64 * waves);
         if (wide) hipLaunchKernelGGL(gz_decode_kernel<true>, grid, block, 0, st, comp, n_bytes, static_cast<const GzSeg*>(segs), n_seg, pool, static_cast<GzSegOut*>(outs));

@@ -1,11 +1,17 @@
-// vgmi_inflate_dev.h -- what the two DEFLATE decoders of the device share: the per-wavefront tables in LDS, their construction from
-// code lengths (RFC 1951 3.2.2), the packed entries a batch of 64 bit positions is decoded from, the bit-by-bit path of long codes.
-// Used by vgmi_inflate.hip (block-gzip members: one wavefront per member, bytes out) and vgmi_gunzip.hip (ordinary gzip streams: one
-// wavefront per stretch between guessed block starts, symbols with back-reference placeholders out).
+// vgmi_inflate_dev.h -- the DEFLATE decoder of the device (RFC 1951), written once: the per-wavefront tables in LDS, their construction
+// from code lengths (3.2.2), the packed entries a batch of 64 bit positions is decoded from, the bit-by-bit path of long codes, the
+// scalar bit reader (InfBits), a block's tables from its header (inf_block_tables) and one whole block -- header, stored bytes or
+// symbols in either batch form (inf_block, at the end of the file).
+// Two kernels instantiate inf_block, each with a SINK of its own -- a small struct beside the kernel that holds what the decoder
+// does not decide: where the input lies and where it ends, the ring's element and where it is flushed to, how far back a match
+// may reach and how it is copied, which reason an overrun gets.  vgmi_inflate.hip (block-gzip members: one wavefront per member,
+// bytes out, ISIZE and CRC-32 checked) and vgmi_gunzip.hip (ordinary gzip streams: one wavefront per stretch between guessed block
+// starts, symbols with back-reference placeholders out); the start search of vgmi_gunzip.hip reads headers with InfBits too.
 #ifndef VGMI_INFLATE_DEV_H
 #define VGMI_INFLATE_DEV_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace vgk {
 
@@ -38,6 +44,53 @@ __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin
 // The block headers and the one-symbol path read the input with SCALAR loads (constant address space, wave-uniform address)
 typedef __attribute__((address_space(4))) const uint32_t inf_cu32;
 __device__ __forceinline__ uint32_t ld32u(const uint32_t* p) { return *reinterpret_cast<inf_cu32*>((uintptr_t)p); }
+
+// ---- the scalar bit reader of block headers, stored blocks and the one-symbol path ----
+struct InfBits {
+    uint64_t bitbuf;
+    uint32_t bitcnt, ip;           // bits in bitbuf; bytes of base[] that are in it or in front of it
+    const uint32_t* wq;
+    uint32_t wa, wb, wc;           // the words behind them, loaded ahead
+    // start at bit bp of base[], whatever its alignment: the input is read as aligned words
+    __device__ __forceinline__ void start(const uint8_t* base, uint32_t bp)
+    {
+        ip = bp >> 3;
+        const uint32_t lead = (uint32_t)((uint64_t)(base + ip) & 3u);
+        wq = reinterpret_cast<const uint32_t*>((uint64_t)(base + ip) & ~3ULL);
+        wa = ld32u(wq);
+        wb = ld32u(wq + 1);
+        wc = ld32u(wq + 2);
+        bitbuf = (uint64_t)(wa >> (8u * lead));
+        bitcnt = 32u - 8u * lead;
+        ip += 4u - lead;
+        wa = wb;
+        wb = wc;
+        wc = ld32u(wq + 3);
+        ++wq;
+        take(bp & 7u);
+    }
+    __device__ __forceinline__ void refill()           // leaves at least 33 bits
+    {
+        if (bitcnt <= 32u) {
+            bitbuf |= (uint64_t)wa << bitcnt;
+            bitcnt += 32u;
+            ip += 4u;
+            wa = wb;
+            wb = wc;
+            wc = ld32u(wq + 3);
+            ++wq;
+        }
+    }
+    __device__ __forceinline__ void need(uint32_t n) { if (bitcnt < n) refill(); }
+    __device__ __forceinline__ uint32_t take(uint32_t n)
+    {
+        const uint32_t v = (uint32_t)bitbuf & ((1u << n) - 1u);
+        bitbuf >>= n;
+        bitcnt -= n;
+        return v;
+    }
+    __device__ __forceinline__ uint32_t pos() const { return 8u * ip - bitcnt; }      // bits of base[] consumed
+};
 
 __device__ __forceinline__ uint32_t bitrev(uint32_t code, uint32_t len) { return __builtin_bitreverse32(code) >> (32 - len); }
 
@@ -678,6 +731,256 @@ __device__ __forceinline__ bool infw_matches(T& t, uint32_t n_match, uint32_t op
         }
     }
     return true;
+}
+
+// ---- a block's decoding tables from its header ----------------------------------------------------------------------------------
+// type: BTYPE 1 (fixed codes, RFC 1951 3.2.6) or 2 (dynamic codes, 3.2.7: r stands behind BTYPE).  Leaves lit[] / dist[] packed for the
+// batches (and the wide batches' side tables) and r behind the header.  Returns 0, or reason 1: code lengths zlib would refuse.
+template <bool WIDE, class T>
+__device__ __forceinline__ uint32_t inf_block_tables(T& t, uint32_t type, InfBits& r, uint32_t lane)
+{
+    if (type == 1) {
+        for (uint32_t s = lane; s < 288; s += 64) t.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
+        if (lane < 32) t.len[288 + lane] = 5;
+        inf_sync();
+        if (!inf_build(t, 0, 0, 288, lane) || !inf_build(t, 1, 288, 30, lane, INF_INC_ANY)) return 1;
+    } else {                    // the code lengths are themselves Huffman coded
+        const uint32_t hlit = r.take(5) + 257, hdist = r.take(5) + 1, hclen = r.take(4) + 4;
+        if (hlit > 286 || hdist > 30) return 1;
+        r.refill();
+        // code length alphabet: built in the distance slots (19 symbols), decoded through the distance table
+        if (lane < 19) t.len[288 + lane] = 0;
+        inf_sync();
+        for (uint32_t i = 0; i < hclen; ++i) {
+            if (r.bitcnt < 3) r.refill();
+            const uint32_t v = r.take(3);
+            if (lane == 0) t.len[288 + uni(inf_clen_order[i])] = (uint8_t)v;
+        }
+        inf_sync();
+        if (!inf_build(t, 1, 288, 19, lane, INF_INC_NONE)) return 1;
+        // the hlit + hdist lengths, written to a staging area first (the code-length code occupies len[288..306])
+        uint32_t idx = 0, prev = 0;
+        uint8_t* const stage = reinterpret_cast<uint8_t*>(t.lit);        // rebuilt below
+        auto put = [&](uint32_t i, uint32_t v) { if (lane == 0) stage[i] = (uint8_t)v; };
+        while (idx < hlit + hdist) {
+            r.refill();
+            const uint32_t e = uni(t.dist[(uint32_t)r.bitbuf & ((1u << INF_DIST_BITS) - 1u)]);
+            const uint32_t l = e & 15u, sym = e >> 4;
+            if (!l) return 1;               // code-length codes are at most 7 bits: always in the fast table
+            r.take(l);
+            if (sym < 16) {
+                put(idx++, sym);
+                prev = sym;
+            } else {
+                uint32_t rep, val = 0;
+                if (sym == 16) {
+                    if (idx == 0) return 1;
+                    val = prev;
+                    rep = 3 + r.take(2);
+                } else if (sym == 17) rep = 3 + r.take(3);
+                else rep = 11 + r.take(7);
+                if (idx + rep > hlit + hdist) return 1;
+                for (uint32_t k = 0; k < rep; ++k) put(idx++, val);
+                prev = val;
+            }
+        }
+        inf_sync();
+        // staging -> len[]: literal/length 0..hlit-1 (rest 0), distance 288..288+hdist-1 (rest 0)
+        uint8_t mine[5];
+#pragma unroll
+        for (uint32_t q = 0; q < 5; ++q) {
+            const uint32_t s = lane + 64 * q;      // 0..319
+            uint32_t v = 0;
+            if (s < 288) {
+                if (s < hlit) v = stage[s];
+            } else if (s - 288 < hdist) v = stage[hlit + (s - 288)];
+            mine[q] = (uint8_t)v;
+        }
+        inf_sync();
+#pragma unroll
+        for (uint32_t q = 0; q < 5; ++q) t.len[lane + 64 * q] = mine[q];
+        inf_sync();
+        if (uni(t.len[256]) == 0) return 1;     // no end-of-block code
+        if (!inf_build(t, 0, 0, 288, lane) || !inf_build(t, 1, 288, 30, lane)) return 1;
+    }
+    if constexpr (WIDE) {
+        infw_limits(t, 0, lane);
+        infw_limits(t, 1, lane);
+        infw_pack_lit2(t, lane);
+    }
+    inf_pack_lit(t, lane);
+    inf_pack_dist(t, lane);
+    return 0;
+}
+
+// ---- one block -------------------------------------------------------------------------------------------------------------------
+// The block that starts at bit bp of the sink's input: header, then a stored block's bytes or the symbols -- wide batches
+// (inf_wide / infw_matches) or batches of 64 bit positions (inf_batch) with the one-symbol path for codes longer than the tables'
+// index.  bp, op (output produced so far), err (0, or the reason decoding stopped) and last (BFINAL) are the caller's wave-uniform
+// state.  What a Sink (BgzfSink in vgmi_inflate.hip, GzSink in vgmi_gunzip.hip) provides:
+//   Ring, kRing, kNear, Tables        the ring's element and geometry, the tables' type; t, lane
+//   kStored                           elements a stored block moves between two flushes
+//   in, in4, lead_bits, irsrc         the input: bytes (bit 0 of in[0] is bit 0 of the data), the aligned words in4 + lead_bits bits,
+//                                     and a descriptor over them for the wide batches
+//   cap, back_ok                      output the block may fill up to; how far in front of the output a match may reach
+//   stored_overrun / overrun / slow_overrun    0 or the reason a stored block / a batch / the one-symbol path may not go on
+//   copy_match, matches, flush        one match copied by the wavefront, a wide batch's queue, ring -> global memory
+//   block_end                         called behind a block's last symbol (also where the symbol loops gave up: err says so)
+template <bool WIDE, class Sink>
+__device__ __forceinline__ void inf_block(Sink& s, uint32_t& bp, uint32_t& op, uint32_t& err, bool& last)
+{
+    typedef typename Sink::Ring Ring;
+    typedef typename Sink::Tables T;
+    constexpr uint32_t RM = Sink::kRing - 1u;
+    T& t = s.t;
+    const uint32_t lane = s.lane;
+    InfBits r;
+    r.start(s.in, bp);
+    r.refill();
+    last = r.take(1) != 0;
+    const uint32_t type = r.take(2);
+    if (type == 0) {            // stored
+        r.take(r.bitcnt & 7u);  // to the byte boundary
+        r.refill();
+        const uint32_t len = r.take(16), nlen = r.take(16);
+        if ((len ^ 0xFFFFu) != nlen) { err = 6; return; }
+        const uint32_t src = r.ip - (r.bitcnt >> 3);      // the bytes still in the bit buffer come first
+        if ((err = s.stored_overrun(src, len, op))) return;
+        for (uint32_t done = 0; done < len;) {
+            const uint32_t n = len - done < Sink::kStored ? len - done : Sink::kStored;
+            for (uint32_t i = lane; i < n; i += 64) t.ring[(op + i) & RM] = s.in[src + done + i];
+            inf_sync();
+            op += n;
+            done += n;
+            s.flush(op, false);
+        }
+        bp = 8u * (src + len);
+        s.block_end(bp, err);
+        return;
+    }
+    if (type == 3) { err = 7; return; }
+    if ((err = inf_block_tables<WIDE>(t, type, r, lane))) return;
+    bp = r.pos();
+
+    bool eob = false;
+    if constexpr (WIDE) {
+        uint32_t nl = 40;      // sub-blocks a batch looks at: what the batches before it got through, and a few
+        // ---- batches of 64 sub-blocks of 64 bits ----
+        while (!eob && !err) {
+            const uint32_t g = s.lead_bits + bp + 64u * lane;
+            const uint32_t wo = (g >> 5) * 4u, sh = g & 31u;
+            const uint32_t x0 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.irsrc, wo, 0, 0), x1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.irsrc, wo + 4u, 0, 0),
+                           x2 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.irsrc, wo + 8u, 0, 0), x3 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.irsrc, wo + 12u, 0, 0),
+                           x4 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.irsrc, wo + 16u, 0, 0);
+            const uint32_t room = s.cap - op < T::kCap ? s.cap - op : T::kCap;
+            const InfWideOut B = inf_wide<T, Ring>(t, __builtin_amdgcn_alignbit(x1, x0, sh), __builtin_amdgcn_alignbit(x2, x1, sh), __builtin_amdgcn_alignbit(x3, x2, sh),
+                                                   __builtin_amdgcn_alignbit(x4, x3, sh), op, room, nl, lane);
+            if (B.bad) { err = 2; break; }
+            if ((err = s.overrun(!B.adv, bp, B.adv))) break;       // (no symbol fits: the output is full)
+            if (!s.matches(B.n_match, op)) { err = 2; break; }
+            op += B.out;
+            bp += B.adv;
+            eob = B.eob != 0;
+            if (!eob) nl = B.last + 2u >= nl ? (nl + 8u < 64u ? nl + 8u : 64u) : B.last + 4u;
+            s.flush(op, false);
+        }
+    } else
+    // ---- batches of 64 bit positions ----
+    while (!eob && !err) {
+        // the 64 bits that start at bit bp + lane
+        const uint32_t b = s.lead_bits + bp + lane;
+        const uint32_t* const w = s.in4 + (b >> 5);
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+        const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, b & 31u), hi = __builtin_amdgcn_alignbit(w2, w1, b & 31u);
+        // what would start here
+        const InfBatch B = inf_batch(t, lo, hi, lane);
+        eob = B.eob;
+        const bool slow = B.slow;
+        const uint32_t off = B.out, pos = B.adv;
+        uint64_t matches = B.matches;
+        if ((err = s.overrun(op + off > s.cap, bp, pos))) break;
+        // literals: up to three per lane
+        if ((B.lits >> lane) & 1ull) {
+            const uint32_t e = B.e, n = (e >> 6) & 3u, P = op + B.off;
+            if (((e >> 4) & 3u) == 0) {
+                t.ring[P & RM] = (Ring)((e >> 8) & 255u);
+                if (n > 1) t.ring[(P + 1u) & RM] = (Ring)((e >> 16) & 255u);
+                if (n > 2) t.ring[(P + 2u) & RM] = (Ring)(e >> 24);
+            }
+        }
+        inf_sync();
+        // matches, in order
+        while (matches) {
+            const uint32_t ml = (uint32_t)__builtin_ctzll(matches);
+            matches &= matches - 1ull;
+            const uint32_t P = op + (uint32_t)__builtin_amdgcn_readlane((int)B.off, (int)ml);
+            const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)B.mlen, (int)ml);
+            const uint32_t dist = (uint32_t)__builtin_amdgcn_readlane((int)B.mdist, (int)ml);
+            if (dist > P + s.back_ok) { err = 2; break; }
+            s.copy_match(P, len, dist);
+        }
+        if (err) break;
+        op += off;
+        bp += pos;
+        s.flush(op, false);
+        if (slow) {
+            // one symbol the tables do not hold whole (a code longer than the index): the scalar way
+            r.start(s.in, bp);
+            r.need(32);
+            uint32_t l;
+            int32_t sym = inf_slow(t, 0, r.bitbuf, l);
+            sym = (int32_t)uni((uint32_t)sym);
+            l = uni(l);
+            if (sym < 0) { err = 2; break; }      // (a short code the packed table rejected -- a reserved length symbol -- decodes here too)
+            r.take(l);
+            if (sym < 256) {
+                if (op >= s.cap) { err = 3; break; }
+                if (lane == 0) t.ring[op & RM] = (Ring)sym;
+                inf_sync();
+                ++op;
+            } else if (sym == 256) {
+                eob = true;
+            } else {
+                sym -= 257;
+                if (sym >= 29) { err = 2; break; }
+                uint32_t len;
+                if (sym < 8) len = 3 + (uint32_t)sym;
+                else if (sym == 28) len = 258;
+                else {
+                    const uint32_t x = ((uint32_t)sym >> 2) - 1;
+                    len = ((4u + ((uint32_t)sym & 3u)) << x) + 3u + r.take(x);
+                }
+                r.need(32);     // a distance code (<= 15 bits) and its extra bits (<= 13)
+                uint32_t dl2;
+                int32_t dsym = inf_slow(t, 1, r.bitbuf, dl2);
+                dsym = (int32_t)uni((uint32_t)dsym);
+                dl2 = uni(dl2);
+                if (dsym < 0 || dsym >= 30) { err = 2; break; }
+                r.take(dl2);
+                uint32_t dist;
+                if (dsym < 4) dist = 1 + (uint32_t)dsym;
+                else {
+                    const uint32_t x = ((uint32_t)dsym >> 1) - 1;
+                    dist = ((2u + ((uint32_t)dsym & 1u)) << x) + 1u + r.take(x);
+                }
+                if (dist > op + s.back_ok) { err = 2; break; }
+                if (op + len > s.cap) { err = 3; break; }
+                s.copy_match(op, len, dist);
+                op += len;
+            }
+            bp = r.pos();
+            if ((err = s.slow_overrun(bp))) break;
+            s.flush(op, false);
+        }
+    }
+    s.block_end(bp, err);
+}
+
+// VGMI_INFLATE_WIDE=0 selects the first form of both decoders' inner loop (batches of 64 bit positions); read once per process
+inline bool inf_wide_form()
+{
+    static const bool wide = !(getenv("VGMI_INFLATE_WIDE") && getenv("VGMI_INFLATE_WIDE")[0] == '0');
+    return wide;
 }
 
 }  // namespace vgk
