@@ -282,7 +282,10 @@ int vgmi_bloom_query(vgmi_ctx *ctx, const uint64_t *host_keys, size_t n, uint8_t
  * all have `ploidy` haplotypes and whose transition is "rec".  A chain is one window walked in one direction; per step the
  * host supplies the node's row of emission scores, the two tables of powers (libm stays on the host: no_recomb^0..ploidy,
  * then recomb^0..ploidy) and whether the chain (re)starts there (the first node, or the node behind one without k-mers).
- * At most 2048 genotypes; beyond 128 the keep matrices must be symmetric (they are by construction: what two genotypes share).
+ * At most 2048 genotypes of 1 .. 8 haplotypes (a ploidy outside that: VGMI_E_INVALID, here and in every call below that takes keep
+ * matrices; vgmi_hmm_emissions_ploidy and _select_ploidy take 2 .. 8); beyond 128 genotypes
+ * 12 x n_gt x (ploidy + 2) bytes must fit the 160 KiB of a workgroup's local memory (2048 genotypes up to ploidy 4, 1364 at ploidy 8:
+ * VGMI_E_INVALID beyond), and beyond 128 the keep matrices must be symmetric (they are by construction: what two genotypes share).
  * Every value is an x86-64 `long double` in its 16-byte memory form; out[step * n_gt + g] is the normalised score the
  * reference stores in HMMScore::a (forward chains) or ::b (backward chains), bit for bit (csrc/vg_x80.h). All pointers host. */
 typedef struct vgmi_hmm_chain {
@@ -349,7 +352,7 @@ int vgmi_hmm_emissions(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used, const uint
                        uint64_t top_mask, uint32_t bit_len, float ave, double lower, double upper, const void *tables,
                        uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint16_t *gt0,
                        uint32_t *n_kept_out, uint8_t *flags_out, vgmi_hmm_part **out);
-/* ... the same for genotypes of `ploidy` haplotypes, 2 .. 4 (a polyploid sample's genotypes are blocks of consecutive haplotypes,
+/* ... the same for genotypes of `ploidy` haplotypes, 2 .. 8 (a polyploid sample's genotypes are blocks of consecutive haplotypes,
  * src/genotype.cpp:846-873): pos[g * ploidy + q] = the place in `used` of genotype g's q-th haplotype; tables holds (ploidy + 1) x 256
  * terms (geometric for h = 0, Poisson(ave * h) for h = 1 .. ploidy).  vgmi_hmm_emissions is this with ploidy 2. */
 int vgmi_hmm_emissions_ploidy(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t *used, const uint8_t *pos,
@@ -425,7 +428,7 @@ int vgmi_hmm_emissions_select(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used, con
 int vgmi_hmm_tallies_select(vgmi_ctx *ctx, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win,
                             const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b, uint32_t n_used,
                             uint32_t n_windows, const uint8_t *win_used, uint32_t *out, uint8_t *unique_out);
-/* ---- ... and a POLYPLOID sample (3 or 4 haplotypes per genotype) under -n: a genotype list per window ---------------------------------
+/* ---- ... and a POLYPLOID sample (3 .. 8 haplotypes per genotype; the tallies: 3 or 4) under -n: a genotype list per window ---------------------------------
  * The genotypes of a polyploid sample are blocks of `ploidy` consecutive haplotypes (src/genotype.cpp:846-873): every drawn haplotype
  * h > 0 gives the block that holds it (ids above the last haplotype read 0), a drawn 0 the all-zero block, and the list is the sorted
  * set of distinct blocks -- 1 .. -n genotypes, another number in every window, over haplotypes that were not all drawn.  So the lists

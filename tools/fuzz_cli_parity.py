@@ -2,7 +2,8 @@
 """Drawn end-to-end cases through both CLIs (the unmodified reference, oracle/_ref/varigraph_det, and varigraph-mi) on one GPU box:
 genome size, variant mix, cohort size and ploidy, k, construct mode, reads per sample and every genotype option are drawn from a seed;
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
-  fuzz_cli_parity.py <first seed> <cases>"""
+  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N]
+--max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from."""
 import gzip, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -55,6 +56,7 @@ def dress(path, rng):
     return path + ".gz"
 
 
+MAX_PLOIDY = 4      # --max-ploidy N: ploidy 5 .. N joins both draws (DESIGN_INGEST_HMM 4.15: the device's HMM for samples of ploidy 5 .. 8)
 FORCE = {}      # --k K / --genome G on the command line: the drawn value replaced (round 6: campaigns of k = 28 over graphs on either side of 65 536 k-mers)
 
 
@@ -62,7 +64,8 @@ def case(seed):
     rng = np.random.default_rng(seed)
     pick = lambda xs: xs[int(rng.integers(0, len(xs)))]
     genome = int(pick([40_000, 90_000, 200_000, 400_000, 1_500_000, 1_500_000]))      # (the last: more than 65 536 k-mers with dense variants -- the context table at any k)
-    vploidy = pick([2, 2, 2, 3, 4])
+    more_ploidy = list(range(5, MAX_PLOIDY + 1))
+    vploidy = pick([2, 2, 2, 3, 4] + more_ploidy)
     n_samples = pick([1, 2, 3, 5, 7]) if vploidy <= 2 else pick([1, 2, 3])
     k = pick([27, 27, 27, 21, 25, 22, 28, 15, 11, 19, 23, 20, 24, 26])
     k = FORCE.get("k", k)
@@ -71,7 +74,7 @@ def case(seed):
     copts = pick([[], [], ["--fast"], ["--use-unique-kmers"]])
     n_var = max(5, genome // pick([300, 600, 1500]))
     indel, sv = pick([0.0, 0.1, 0.3]), pick([0.0, 0.01, 0.05])
-    sploidy = pick([2, 2, 2, 3, 4])
+    sploidy = pick([2, 2, 2, 3, 4] + more_ploidy)
     gopts = ["-g", pick(["het", "het", "hom"]), "-m", pick(["rec", "fre"]), "--sample-ploidy", str(sploidy), "-n", str(pick([1, 2, 4, 7, 15, 15, 40]))]
     if rng.random() < 0.3: gopts += ["--sv"]
     if rng.random() < 0.4: gopts += ["--use-depth"]
@@ -134,6 +137,7 @@ if __name__ == "__main__":
     first, n = int(sys.argv[1]), int(sys.argv[2])
     for i, a in enumerate(sys.argv):
         if a in ("--k", "--genome"): FORCE[a[2:]] = int(sys.argv[i + 1])
+        if a == "--max-ploidy": MAX_PLOIDY = int(sys.argv[i + 1])
     bad = 0
     for s in range(first, first + n):
         t0 = time.time()

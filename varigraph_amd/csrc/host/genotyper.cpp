@@ -1116,16 +1116,21 @@ void append_sample_field(std::string& out, const uint64_t* gt, size_t n_alleles,
     out += '\n';
 }
 
-// A call's line straight from what the device sent back -- the alleles of the `ploidy` (2 .. 4) called haplotypes, the posterior, the
+// A call's line straight from what the device sent back -- the alleles of the `ploidy` (2 .. kTallyPloidyMax) called haplotypes, the posterior, the
 // tallies (k-mers, coverage sum per called haplotype: tl[2 q], tl[2 q + 1]) -- without the detour through the node's call record
 // (window_finish writes it, write_piece reads it back: two walks over half a million scattered nodes per sample).  An all-reference call
 // has no line.  head(out) as append_site_head.
+// (The device tallies calls of up to kTallyPloidyMax haplotypes, vgmi_hmm_tallies_ploidy; a call of more keeps the host's walk over the
+// called nodes' lists -- finish_rows, window_finish -- and never comes here: device_tally_ploidy() is what both callers ask.)
+constexpr uint32_t kTallyPloidyMax = 4;
+inline bool device_tally_ploidy(uint32_t ploidy) { return ploidy >= 3 && ploidy <= kTallyPloidyMax; }
 template <class HapGt, class Head>
 void append_tally_line(std::string& out, const HapGt& hap_gt, const uint16_t* called, uint32_t ploidy, long double probability, const uint32_t* tl,
                        uint8_t unique_kmers, float min_gq, Head&& head)
 {
-    uint64_t gt[4], num[4];
-    float cov[4];
+    if (ploidy > kTallyPloidyMax) throw std::runtime_error("internal: a tally line for a call of more haplotypes than the device tallies");
+    uint64_t gt[kTallyPloidyMax], num[kTallyPloidyMax];
+    float cov[kTallyPloidyMax];
     bool all_ref = true;
     for (uint32_t q = 0; q < ploidy; ++q) {
         gt[q] = (uint64_t)hap_gt[called[q]];
@@ -1453,7 +1458,7 @@ void Genotyper::window(Chrom& chr, uint32_t first, uint32_t last, const Run& r, 
     // itself and the posterior follow in window_finish() (the pruning of a node's k-mer list depends on the window's
     // haplotypes, not on alpha, so nothing here waits for the recursion)
     const bool to_device = work != nullptr && work->obs != nullptr && n_gt == work->n_gt && cfg.transition == "rec" && all_full && n_gt <= 2048 &&
-                           cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;    // 2048: VGMI_HMM_MAX_GT (csrc/vgmi_kernels.h)
+                           cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 8;    // 2048: VGMI_HMM_MAX_GT (csrc/vgmi_kernels.h)
     if (to_device) {
         std::vector<Seen> seen;      // at: the node's place in work->nodes
         NodeStates st;
@@ -1862,8 +1867,9 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
     // `-m fre` (transitions by haplotype frequency) has a recursion kernel of its own, fed by the two paths that score the emissions on the
     // device: 2 .. 4 haplotypes per genotype, at most 128 genotypes, never the pool.  VGH_HMM_FRE_DEVICE=0: such a sample stays on the host.
     const bool fre = cfg.transition == "fre";
-    const bool transition_ok = cfg.transition == "rec" || (fre && cfg.sample_ploidy >= 2 && !knob_off("VGH_HMM_FRE_DEVICE"));
-    const bool use_device = dev_ != nullptr && !knob_off("VGH_HMM_DEVICE") && transition_ok && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 4;
+    // (`-m rec` takes genotypes of up to 8 haplotypes; the `-m fre` kernel stops at 4: such a sample of ploidy 5 .. 8 stays on the host)
+    const bool transition_ok = cfg.transition == "rec" || (fre && cfg.sample_ploidy >= 2 && cfg.sample_ploidy <= 4 && !knob_off("VGH_HMM_FRE_DEVICE"));
+    const bool use_device = dev_ != nullptr && !knob_off("VGH_HMM_DEVICE") && transition_ok && cfg.sample_ploidy >= 1 && cfg.sample_ploidy <= 8;
     if (!use_device) return dp;
     works.resize(tasks.size());
     std::vector<uint16_t> some(std::min<size_t>(r.haploid_num, n_hap_));
@@ -1897,16 +1903,16 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
     // the emission scores can be computed on the device as well (hmm_whole_panel): a diploid sample, every haplotype selected, whole lists
     // (polyploid samples too -- their genotypes are blocks of `ploidy` consecutive haplotypes, :846-873, a handful per window).
     // VGH_HMM_EMIT_DEVICE=0: the host prepares the scores as before.
-    dp.emit = device_ok && !emit_device_off_ && r.packed != nullptr && cfg.sample_ploidy >= 2 && cfg.sample_ploidy <= 4 && n_hap_ <= r.haploid_num && n_hap_ <= 16 &&
+    dp.emit = device_ok && !emit_device_off_ && r.packed != nullptr && cfg.sample_ploidy >= 2 && cfg.sample_ploidy <= 8 && n_hap_ <= r.haploid_num && n_hap_ <= 16 &&
               dev_n_gt <= 128 && lists_whole_.load() && !knob_off("VGH_HMM_EMIT_DEVICE");
     // ... and when -n selects fewer haplotypes than the graph has, for a diploid sample (hmm_selected: every window draws its own haplotypes,
     // the genotype list keeps its shape, the k-mer lists are pruned on the device and here alike).  VGH_HMM_SELECT_DEVICE=0: the host
     // prepares such a sample as before.
     bool plain_ids = true;      // haplotype h is bit h of an entry's word
     for (size_t i = 0; i < hap_ids_.size(); ++i) plain_ids = plain_ids && hap_ids_[i] == i;
-    // A polyploid sample (3 or 4 haplotypes per genotype) takes that path too: its windows have lists of 1 .. -n blocks of haplotypes, so the
+    // A polyploid sample (3 .. 8 haplotypes per genotype: use_device bounds it) takes that path too: its windows have lists of 1 .. -n blocks of haplotypes, so the
     // room on the device is reckoned for -n genotypes, not for the handful dp.n_gt counts over the first -n haplotypes.
-    const bool blocks = cfg.sample_ploidy == 3 || cfg.sample_ploidy == 4;
+    const bool blocks = cfg.sample_ploidy >= 3;
     const size_t sel_n_gt = blocks ? std::max<size_t>(dev_n_gt, r.haploid_num) : dev_n_gt;
     const bool select_fits = !blocks || (total_room * sel_n_gt * sizeof(long double) <= (score_gib << 30) && [&] {
         size_t free_b = 0, total_b = 0;
@@ -2569,12 +2575,13 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
     s.note_device_span(ta, t_calls);
     // the calls' k-mer tallies on the device too (the node lists and the sample's coverage are there for the emissions):
     // per sample, the walk over every called node's k-mer list was 0.8 of 1.7 host thread-seconds (VGH_DEVICE_TALLIES=0: the walk).
-    // A tri- or tetraploid sample's through vgmi_hmm_tallies_ploidy: one window, the sample's one list by haplotype id, whole lists.
+    // A tri- or tetraploid sample's through vgmi_hmm_tallies_ploidy: one window, the sample's one list by haplotype id, whole lists
+    // (ploidy 5 .. 8: the walk, finish_rows).
     const uint32_t ploidy = cfg.sample_ploidy;
     std::vector<uint32_t> tally;      // per row 2 x ploidy numbers
     std::vector<uint8_t> tally_uniq;
     static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
-    if (device_tallies && plan->n_steps && (ploidy == 3 || ploidy == 4) && n_hap_ <= 64 && n_gt <= 128) {
+    if (device_tallies && plan->n_steps && device_tally_ploidy(ploidy) && n_hap_ <= 64 && n_gt <= 128) {
         std::vector<uint8_t> haps_all(n_gt * ploidy);
         bool ids = true;
         for (size_t g2 = 0; g2 < n_gt && ids; ++g2)
@@ -2652,7 +2659,7 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
 // device; the draws (std::mt19937, libm), the sequence checks (strings), the step tables (libm) and the genotype strings stay here.
 // A row is the range [front, back] of what is left of its node's list plus the device's alive bytes; node.kmers is pruned by the same
 // rule right after the emission launch, so that the host's lists and the device's bytes agree after every sample.
-// A polyploid sample (ploidy 3, 4) takes the same steps with another genotype list: haplotype_combinations turns every drawn haplotype into
+// A polyploid sample (ploidy 3 .. 8) takes the same steps with another genotype list: haplotype_combinations turns every drawn haplotype into
 // the block of `ploidy` consecutive haplotypes that holds it (:846-873), so a window has 1 .. -n genotypes over up to -n x ploidy
 // haplotypes -- `used`, which the scores, the sequence checks and the strings go by -- while the prune still goes by the drawn ones.  The
 // device's recursion takes one list length per part: the windows are dealt into parts by the length of their lists (SelectedPart), each
@@ -3005,7 +3012,7 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
     std::vector<uint32_t> tally;      // per row 2 x ploidy numbers
     std::vector<uint8_t> tally_uniq;
     static const bool device_tallies = !knob_off("VGH_DEVICE_TALLIES");
-    if (device_tallies && n_steps && ss.blocks && ss.ploidy <= 4) {
+    if (device_tallies && n_steps && ss.blocks && device_tally_ploidy(ss.ploidy)) {
         tally.resize(2 * (size_t)ss.ploidy * n_rows);
         tally_uniq.resize(n_rows);
         device_check(dev_, vgmi_hmm_tallies_ploidy(dev_, ss.ploidy, (uint32_t)n_gt, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(), n_rows, pt.e_begin.data(),

@@ -164,7 +164,7 @@ private:
     DevicePaths device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works, bool refuse_select) const;
     // the three ways through the HMM.  On the pool: window() prepares every window on the host, recursion and posterior go to the device
     // in parts or stay here.  The other two score the emissions on the device as well: with every haplotype of the panel selected (one
-    // genotype list per sample, per-part cache and plan), or with the haplotypes drawn per window (-n below the panel, ploidy 2 .. 4)
+    // genotype list per sample, per-part cache and plan), or with the haplotypes drawn per window (-n below the panel, ploidy 2 .. 8)
     void hmm_on_pool(RunShared& s, std::vector<WindowWork>& works, const WindowBuffers& bufs, size_t n_gt);
     Emitted hmm_whole_panel(RunShared& s);
     Emitted hmm_selected(RunShared& s);

@@ -150,6 +150,15 @@ int hmm_check_keep(vgmi_ctx* c, const char* who, const uint8_t* keep, uint32_t n
     return VGMI_OK;
 }
 
+// beyond 128 genotypes the step table of a whole node lives in LDS, 12 x n_gt x (ploidy + 2) bytes (hmm_recursion_big_kernel) of the 160 KiB a
+// workgroup can have: 2 048 genotypes up to ploidy 4, 1 364 at ploidy 8
+int hmm_check_lds(vgmi_ctx* c, const char* who, uint32_t n_gt, uint32_t ploidy)
+{
+    if (n_gt > 128 && (size_t)n_gt * (ploidy + 2) * 12 + 64 > (size_t)160 * 1024)
+        return fail(c, VGMI_E_INVALID, std::string(who) + ": more than 128 genotypes of this many haplotypes do not fit the device's local memory");
+    return VGMI_OK;
+}
+
 // chains, steps and (with fwd_step) rows point inside rows [row_lo, row_hi) and steps [step_lo, step_hi)
 int hmm_check_ranges(vgmi_ctx* c, const char* who, const vgmi_hmm_chain* chains, uint32_t n_chains, uint32_t n_windows, const uint32_t* row, uint64_t row_lo,
                      uint64_t row_hi, uint64_t step_lo, uint64_t step_hi, const uint64_t* fwd_step, const uint64_t* bwd_step)
@@ -206,7 +215,8 @@ int hmm_run(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, ui
         if (!freq || n_windows == 0) return fail(c, VGMI_E_INVALID, "HMM recursion by haplotype frequency: no table of factors");
     } else {
         if (!keep || !pow) return VGMI_E_INVALID;
-        if (n_gt < 1 || n_gt > VGMI_HMM_MAX_GT || ploidy < 1 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM recursion: 1..2048 genotypes of 1..4 haplotypes");
+        if (n_gt < 1 || n_gt > VGMI_HMM_MAX_GT || ploidy < 1 || ploidy > 8) return fail(c, VGMI_E_INVALID, "HMM recursion: 1..2048 genotypes of 1..8 haplotypes");
+        if (int rc = hmm_check_lds(c, "HMM recursion", n_gt, ploidy)) return rc;
         if (int rc = hmm_check_keep(c, "HMM recursion", keep, n_windows, n_gt)) return rc;
     }
     if (row_lo > row_hi || step_lo > step_hi) return fail(c, VGMI_E_INVALID, "HMM recursion: an empty-handed range");
@@ -383,7 +393,7 @@ int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_u
                        const uint32_t* entry_count, const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out, const HmmSelect* sel)
 {
     if (!c || !used || !pos || !tables || !out) return VGMI_E_INVALID;
-    if (ploidy < 2 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM emissions: genotypes of 2..4 haplotypes");
+    if (ploidy < 2 || ploidy > 8 || (sel && ploidy != 2)) return fail(c, VGMI_E_INVALID, "HMM emissions: genotypes of 2..8 haplotypes");
     if (n_gt < 1 || n_gt > 128) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes");
     HmmEmitParams P{};
     for (uint32_t g = 0; g < n_gt; ++g) {
@@ -584,7 +594,7 @@ int vgmi_hmm_emissions(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const uint8_
 }
 
 
-// ... for genotypes of `ploidy` haplotypes (2 .. 4): pos[g * ploidy + q] = the place in `used` of genotype g's q-th haplotype; tables holds
+// ... for genotypes of `ploidy` haplotypes (2 .. 8): pos[g * ploidy + q] = the place in `used` of genotype g's q-th haplotype; tables holds
 // (ploidy + 1) x 256 terms (geometric for h = 0, Poisson(ave * h) for h = 1 .. ploidy)
 int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t* used, const uint8_t* pos, uint64_t top_mask,
                               uint32_t bit_len, float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin,
@@ -640,8 +650,8 @@ int vgmi_hmm_emissions_select_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy
                                      uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
 {
     if (!c || !tables || !out) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 4 || bit_len < 1 || bit_len > 6)
-        return fail(c, VGMI_E_INVALID, "HMM emissions: 1..64 genotypes of 2..4 haplotypes per window, 1..6 bytes of haplotype bits");
+    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 8 || bit_len < 1 || bit_len > 6)
+        return fail(c, VGMI_E_INVALID, "HMM emissions: 1..64 genotypes of 2..8 haplotypes per window, 1..6 bytes of haplotype bits");
     if (n_windows < 1 || !win_n_gt || !win_haps || !win_top_mask) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their genotype lists");
     if (n_rows && (!entry_begin || !entry_count || !row_win || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
     if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
@@ -763,7 +773,8 @@ int vgmi_hmm_plan_create(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint
     if (!c || !out) return VGMI_E_INVALID;
     *out = nullptr;
     if (!keep || !row || !restart || !pow || !uniform || !chains || !gid || !order || !fwd_step || !bwd_step) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > VGMI_HMM_MAX_GT || ploidy < 1 || ploidy > 4) return fail(c, VGMI_E_INVALID, "HMM plan: 1..2048 genotypes of 1..4 haplotypes");
+    if (n_gt < 1 || n_gt > VGMI_HMM_MAX_GT || ploidy < 1 || ploidy > 8) return fail(c, VGMI_E_INVALID, "HMM plan: 1..2048 genotypes of 1..8 haplotypes");
+    if (int rc = hmm_check_lds(c, "HMM plan", n_gt, ploidy)) return rc;
     if (int rc = hmm_check_keep(c, "HMM plan", keep, n_windows, n_gt)) return rc;
     if (n_steps == 0 || n_chains == 0 || n_rows == 0) return fail(c, VGMI_E_INVALID, "HMM plan: nothing to plan");
     if (int rc = hmm_check_ranges(c, "HMM plan", chains, n_chains, n_windows, row, 0, n_rows, 0, n_steps, fwd_step, bwd_step)) return rc;

@@ -58,6 +58,7 @@ __global__ __launch_bounds__(64 * WAVES) void hmm_recursion_kernel(HmmParams P)
     asm volatile("" : "+v"(lane_zero));
     auto fetch = [&](uint64_t s, uint32_t row_s, HmmStepIn<STRIDE>& in) {
         const uint8_t* pw = P.pow + s * (size_t)(2 * stride) * 16 + lane_zero;
+#pragma unroll      // (the tables stay in registers at every stride: left to itself the compiler stops unrolling at stride 9 and indexes them in scratch)
         for (uint32_t k = 0; k < stride; ++k) {
             in.keep_pow[k] = x80_load(pw + (size_t)k * 16);
             in.change_pow[k] = x80_load(pw + (size_t)(stride + (stride - 1 - k)) * 16);
@@ -84,6 +85,7 @@ __global__ __launch_bounds__(64 * WAVES) void hmm_recursion_kernel(HmmParams P)
         if (active) o = n80_from(cur.obs);
         if (!restart) {
             // (prev * no_recomb^keep) * recomb^change for this lane's previous entry and every keep
+#pragma unroll
             for (uint32_t k = 0; k < stride; ++k) {
                 const VgN80 st = n80_mul(n80_mul(prev, n80_from(cur.keep_pow[k])), n80_from(cur.change_pow[k]));
                 if (active) {
@@ -581,11 +583,14 @@ __device__ __forceinline__ void hmm_stage_tables(const uint8_t* tables, uint32_t
 // window, the window supplies `used` and the mask (ids up to 46: every shift of the bits is 64 bits wide); an entry that is no longer in
 // its node's list is passed over, and an entry no selected haplotype carries LEAVES the list here, for good (src/genotype.cpp:673-686,
 // 815-818: the next window, the next sample score what is left).  Every lane takes the same decisions; lane 0 writes them down.
-template <bool SELECT>
+// MAXP: the most haplotypes a genotype may have.  The tables are sized by it -- 4: 1 280 terms, 15 360 bytes of LDS, what a diploid, tri- or
+// tetraploid launch has always asked for; 8: 2 304 terms, 27 648 bytes, for ploidy 5 .. 8 only (a workgroup per row: a larger table for
+// everyone would cost every diploid launch workgroups per CU).
+template <bool SELECT, uint32_t MAXP>
 __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
 {
-    __shared__ uint64_t s_tm[1280];      // (ploidy + 1) x 256 terms: up to four haplotypes per genotype
-    __shared__ int32_t s_te[1280];
+    __shared__ uint64_t s_tm[(MAXP + 1u) * 256u];      // (ploidy + 1) x 256 terms: up to MAXP haplotypes per genotype
+    __shared__ int32_t s_te[(MAXP + 1u) * 256u];
     const uint32_t g = threadIdx.x;
     hmm_stage_tables<128>(P.tables, P.ploidy, s_tm, s_te);
     const uint64_t rowi = P.fix_rows ? P.fix_rows[blockIdx.x] : P.row_lo + blockIdx.x;
@@ -603,6 +608,12 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     }
     const uint32_t pa = P.pos_a[active ? g : 0u], pb = P.pos_b[active ? g : 0u];
     const uint32_t pc = P.ploidy > 2u ? P.pos_more[0][active ? g : 0u] : 0u, pd = P.ploidy > 3u ? P.pos_more[1][active ? g : 0u] : 0u;
+    uint32_t pe[MAXP > 4u ? MAXP - 4u : 1u] = {0};      // the fifth to the eighth haplotype's places (unrolled: the array stays in registers)
+    if (MAXP > 4u) {
+#pragma unroll
+        for (uint32_t q = 4; q < MAXP; ++q)
+            if (q < P.ploidy) pe[q - 4u] = P.pos_more[q - 2u][active ? g : 0u];
+    }
     VgN80 prod;
     prod.m = 1ULL << 63;      // 1.0L
     prod.e = VG_X80_BIAS;
@@ -638,6 +649,11 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
         uint32_t h = ((om >> pa) & 1u) + ((om >> pb) & 1u);
         if (P.ploidy > 2u) h += (om >> pc) & 1u;
         if (P.ploidy > 3u) h += (om >> pd) & 1u;
+        if (MAXP > 4u) {
+#pragma unroll
+            for (uint32_t q = 4; q < MAXP; ++q)
+                if (q < P.ploidy) h += (om >> pe[q - 4u]) & 1u;
+        }
         const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
         const uint32_t ti = h * 256u + cc;
         VgN80 t;
@@ -666,11 +682,13 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
 // coverage and alive byte are scalar loads and the branches are uniform.  The term tables, (ploidy + 1) x 256 entries of 12 bytes, are
 // staged in LDS once per workgroup of four wavefronts, which takes kWinRows rows: a workgroup per row (the kernel above) would spend more
 // on staging 15 KB than on a list of some fifty entries.
+// MAXP as in hmm_emissions_kernel: 15 360 bytes of tables for ploidy 2 .. 4, 27 648 for ploidy 5 .. 8.
 constexpr uint32_t kWinRows = 16;
+template <uint32_t MAXP>
 __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams P)
 {
-    __shared__ uint64_t s_tm[1280];
-    __shared__ int32_t s_te[1280];
+    __shared__ uint64_t s_tm[(MAXP + 1u) * 256u];
+    __shared__ int32_t s_te[(MAXP + 1u) * 256u];
     hmm_stage_tables<256>(P.tables, P.ploidy, s_tm, s_te);      // (its barrier is the only one: from here on the wavefronts go their own ways)
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = threadIdx.x & 63u;
     for (uint32_t k = wave; k < kWinRows; k += 4u) {
@@ -686,9 +704,16 @@ __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams
         const unsigned long long top_mask = P.win_top_mask[w], used_mask = P.win_used_mask[w];
         const uint32_t n_here = P.win_n_gt[w];
         const bool active = g < n_here;
-        uint32_t hap[4] = {0, 0, 0, 0};
-        if (active)
-            for (uint32_t q = 0; q < P.ploidy; ++q) hap[q] = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
+        uint32_t hap[MAXP] = {0};
+        if (active) {
+            if (MAXP > 4u) {
+#pragma unroll
+                for (uint32_t q = 0; q < MAXP; ++q)      // (unrolled with the places beyond `ploidy` left out: the array stays in registers)
+                    if (q < P.ploidy) hap[q] = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
+            } else {
+                for (uint32_t q = 0; q < P.ploidy; ++q) hap[q] = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
+            }
+        }
         VgN80 prod;
         prod.m = 1ULL << 63;      // 1.0L
         prod.e = VG_X80_BIAS;
@@ -716,6 +741,11 @@ __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams
             uint32_t h = (uint32_t)((om >> hap[0]) & 1ull) + (uint32_t)((om >> hap[1]) & 1ull);
             if (P.ploidy > 2u) h += (uint32_t)((om >> hap[2]) & 1ull);
             if (P.ploidy > 3u) h += (uint32_t)((om >> hap[3]) & 1ull);
+            if (MAXP > 4u) {
+#pragma unroll
+                for (uint32_t q = 4; q < MAXP; ++q)      // (a repeated id counts at every place it stands)
+                    if (q < P.ploidy) h += (uint32_t)((om >> hap[q]) & 1ull);
+            }
             const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
             const uint32_t ti = h * 256u + cc;
             VgN80 t;
@@ -923,11 +953,15 @@ hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uin
 hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
+    if (P.ploidy < 2 || P.ploidy > 8) return hipErrorInvalidValue;
     if (P.row_win) {
         if (!P.win_used || !P.win_top_mask || !P.alive) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(hmm_emissions_kernel<true>, dim3((uint32_t)n_rows), dim3(128), 0, st, P);
+        if (P.ploidy > 4) return hipErrorInvalidValue;      // (selection per window by places: a diploid sample's)
+        hipLaunchKernelGGL((hmm_emissions_kernel<true, 4>), dim3((uint32_t)n_rows), dim3(128), 0, st, P);
+    } else if (P.ploidy > 4) {
+        hipLaunchKernelGGL((hmm_emissions_kernel<false, 8>), dim3((uint32_t)n_rows), dim3(128), 0, st, P);
     } else {
-        hipLaunchKernelGGL(hmm_emissions_kernel<false>, dim3((uint32_t)n_rows), dim3(128), 0, st, P);
+        hipLaunchKernelGGL((hmm_emissions_kernel<false, 4>), dim3((uint32_t)n_rows), dim3(128), 0, st, P);
     }
     return hipGetLastError();
 }
@@ -935,9 +969,11 @@ hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStre
 hipError_t launch_hmm_emissions_win(const HmmEmitWinParams& P, hipStream_t st)
 {
     if (P.n_items == 0) return hipSuccess;
-    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 4 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask)
+    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 8 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hmm_emissions_win_kernel, dim3((uint32_t)((P.n_items + kWinRows - 1) / kWinRows)), dim3(256), 0, st, P);
+    const dim3 grid((uint32_t)((P.n_items + kWinRows - 1) / kWinRows));
+    if (P.ploidy > 4) hipLaunchKernelGGL(hmm_emissions_win_kernel<8>, grid, dim3(256), 0, st, P);
+    else hipLaunchKernelGGL(hmm_emissions_win_kernel<4>, grid, dim3(256), 0, st, P);
     return hipGetLastError();
 }
 
@@ -1064,6 +1100,10 @@ hipError_t launch_hmm_recursion(const HmmParams& P, uint32_t n_chains, hipStream
             case 2: return launch_recursion_big<3>(Q, n_chains, st);
             case 3: return launch_recursion_big<4>(Q, n_chains, st);
             case 4: return launch_recursion_big<5>(Q, n_chains, st);
+            case 5: return launch_recursion_big<6>(Q, n_chains, st);
+            case 6: return launch_recursion_big<7>(Q, n_chains, st);
+            case 7: return launch_recursion_big<8>(Q, n_chains, st);
+            case 8: return launch_recursion_big<9>(Q, n_chains, st);
             default: return hipErrorInvalidValue;
         }
     }
@@ -1077,6 +1117,10 @@ hipError_t launch_hmm_recursion(const HmmParams& P, uint32_t n_chains, hipStream
         case 2: return launch_recursion_waves<3>(waves, Q, n_chains, lds, plain_lds, st);
         case 3: return launch_recursion_waves<4>(waves, Q, n_chains, lds, plain_lds, st);
         case 4: return launch_recursion_waves<5>(waves, Q, n_chains, lds, plain_lds, st);
+        case 5: return launch_recursion_waves<6>(waves, Q, n_chains, lds, plain_lds, st);
+        case 6: return launch_recursion_waves<7>(waves, Q, n_chains, lds, plain_lds, st);
+        case 7: return launch_recursion_waves<8>(waves, Q, n_chains, lds, plain_lds, st);
+        case 8: return launch_recursion_waves<9>(waves, Q, n_chains, lds, plain_lds, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -231,9 +231,9 @@ struct HmmChain {
     uint32_t keep_index;            // which keep matrix (one per window)
     uint32_t pad;
 };
-#define VGMI_HMM_MAX_GT 2048u        // genotypes per window the device takes (12 x n x (ploidy + 2) bytes of LDS: 147 KB at the bound)
+#define VGMI_HMM_MAX_GT 2048u        // genotypes per window the device takes (12 x n x (ploidy + 2) bytes of LDS: 147 KB at the bound with ploidy 4; the C ABI refuses what 160 KiB do not hold at ploidy 5 .. 8)
 struct HmmParams {
-    uint32_t n_gt, ploidy;          // genotypes per window (<= VGMI_HMM_MAX_GT; <= 128: one lane per genotype, keep matrix in LDS), haplotypes per genotype (<= 4)
+    uint32_t n_gt, ploidy;          // genotypes per window (<= VGMI_HMM_MAX_GT; <= 128: one lane per genotype, keep matrix in LDS), haplotypes per genotype (<= 8)
     const uint8_t* keep;            // per window: n_gt x n_gt, haplotypes shared by genotype g (row) and previous entry p
     const uint8_t* obs;             // per node: n_gt emission scores, 16 bytes each (x86-64 long double)
     const uint32_t* row;            // per step: the node's row in obs
@@ -280,8 +280,8 @@ struct HmmEmitParams {
     uint64_t row_lo;                    // the launch's first row (workgroup b takes row_lo + b)
     uint32_t n_gt, n_used, bl8;         // genotypes (<= 128), haplotypes in them (<= 16), bit length of a k-mer's haplotype bits (8 * bitlen)
     uint8_t used[16], pos_a[128], pos_b[128];
-    uint8_t pos_more[2][128];           // genotypes of three or four haplotypes (ploidy): the third and the fourth one's places in `used`
-    uint32_t ploidy;                    // 2 .. 4: haplotypes per genotype
+    uint8_t pos_more[6][128];           // genotypes of three to eight haplotypes (ploidy): the third to the eighth one's places in `used`
+    uint32_t ploidy;                    // 2 .. 8: haplotypes per genotype
     unsigned long long top_mask;
     float ave;
     double lower, upper;
@@ -318,7 +318,7 @@ struct HmmEmitWinParams {
     const uint32_t* entry_count;
     const uint32_t* row_win;
     const unsigned long long* gt0;
-    uint32_t n_gt, ploidy, bl8;         // the width of a row of scores (<= 64), haplotypes per genotype (2 .. 4), 8 * bitlen
+    uint32_t n_gt, ploidy, bl8;         // the width of a row of scores (<= 64), haplotypes per genotype (2 .. 8), 8 * bitlen
     float ave;
     double lower, upper;
     const uint8_t* tables;              // (ploidy + 1) x 256 16-byte long doubles

@@ -568,7 +568,7 @@ class Context:
         entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
         gt0 = np.ascontiguousarray(gt0, dtype=np.uint16)
         ploidy = 2
-        if pos is not None:      # genotypes of 2 .. 4 haplotypes: pos (n_gt, ploidy) -> vgmi_hmm_emissions_ploidy
+        if pos is not None:      # genotypes of 2 .. 8 haplotypes: pos (n_gt, ploidy) -> vgmi_hmm_emissions_ploidy
             pos = np.ascontiguousarray(pos, dtype=np.uint8)
             ploidy = pos.shape[1]
         assert tables.size == (ploidy + 1) * 256
