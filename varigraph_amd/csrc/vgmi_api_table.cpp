@@ -427,7 +427,8 @@ int build_xtable(vgmi_ctx* c)
 }
 
 // the path table of small graphs, derived from the compact image like the grid-16-mer table of large ones (after an upload,
-// an import and a clone alike); VGMI_PTABLE=0 keeps count27s_kernel on the hash table alone (A/B).  The device orders the
+// an import and a clone alike); VGMI_PTABLE=0 keeps count27s_kernel on the hash table alone (A/B).  SB and PC are per-sample state
+// and start at zero here, whatever the image's history.  The device orders the
 // k-mers along their unitigs (vgmi_ptable.hip); the layout of the sequence and the index is host work over <= 65 536 k-mers.
 int build_ptable(vgmi_ctx* c)
 {
@@ -570,12 +571,14 @@ int build_ptable(vgmi_ctx* c)
     he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_index), index.size() * 8);
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_S), S.size() * 4);
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_VB), VB.size() * 4);
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SB), VB.size() * 4);
+    // the saturation bits and, behind them, the position counters: one allocation, one memset per sample (vgmi_counts_reset)
+    const size_t pc_words = (size_t)Tp + 64;
+    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SB), (VB.size() + pc_words) * 4);
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SLOT), (size_t)(Tp + 64) * 4);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_index, index.data(), index.size() * 8, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_S, S.data(), S.size() * 4, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_VB, VB.data(), VB.size() * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemset(c->d_pt_SB, 0, VB.size() * 4);
+    if (he == hipSuccess) he = hipMemset(c->d_pt_SB, 0, (VB.size() + pc_words) * 4);
     if (he == hipSuccess) he = hipMemset(c->d_pt_SLOT, 0, (size_t)(Tp + 64) * 4);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_SLOT, slot.data(), (size_t)Tp * 4, hipMemcpyHostToDevice);
     {   // slot -> place: the slow paths -- the hash-table fallback of runs the index does not cover, the generic kernel on the
@@ -586,7 +589,7 @@ int build_ptable(vgmi_ctx* c)
         if (he == hipSuccess) he = hipMemcpy(c->d_pt_PLACE, place_of_slot.data(), h.cap * 4, hipMemcpyHostToDevice);
     }
     HIPCHK(c, he);
-    c->pt_sb_bytes = VB.size() * 4;
+    c->pt_sb_bytes = (VB.size() + pc_words) * 4;
     if (getenv("VGMI_VERBOSE"))
         fprintf(stderr, "[vgmi] path table: %llu k-mers in %llu chains, %llu bases, %llu 12-mers with a fifth place, %llu buckets with a third 12-mer\n",
                 (unsigned long long)n, (unsigned long long)chains, (unsigned long long)Tp, (unsigned long long)slow_cx, (unsigned long long)bucket_ovf);
@@ -596,6 +599,9 @@ int build_ptable(vgmi_ctx* c)
     c->tv.pt.SB = c->d_pt_SB;
     c->tv.pt.SLOT = c->d_pt_SLOT;
     c->tv.pt.PLACE = c->d_pt_PLACE;
+    // VGMI_PT_POSCOUNT=0 keeps the drain's increments on the hash table's counters (A/B)
+    const char* pcv = getenv("VGMI_PT_POSCOUNT");
+    c->tv.pt.PC = pcv && pcv[0] == '0' ? nullptr : c->d_pt_SB + VB.size();
     c->tv.pt.bucket_log2 = bucket_log2;
     c->tv.pt.Tp = (uint32_t)Tp;
     return VGMI_OK;

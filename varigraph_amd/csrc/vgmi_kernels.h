@@ -48,6 +48,8 @@ struct PathView {
     uint32_t* SB;                      // bit per base position: ... and its counter has reached the clamp (per sample)
     const uint32_t* SLOT;              // per base position: the hash-table slot of the k-mer that starts here
     const uint32_t* PLACE;             // per hash-table slot: the place (first half of S) where its k-mer starts, 0: none -- for the slow paths' saturation bits
+    uint32_t* PC;                      // per base position: what the path-table drain has counted of the k-mer that starts here or at the mirrored
+                                       // place (the cell of the smaller of the two); a k-mer's count is counts[slot] + PC[cell].  nullptr: not in use
     uint32_t bucket_log2;
     uint32_t Tp;                       // bases in S, pads included: S[Tp - 1 - j] is the complement of S[j]
 };

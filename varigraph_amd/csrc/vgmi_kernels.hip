@@ -139,6 +139,22 @@ __device__ __forceinline__ uint32_t* count_cell(const TableView& t, uint64_t s, 
     return t.counts ? &t.counts[key_index] : &t.slots[s].count;
 }
 
+// small graphs whose path-table drain counts by position (PathView::PC): the cell of the k-mer in slot s, or nullptr -- a k-mer's
+// count is the sum of both cells (mod 2^32: even k's debits stand in counts[s]), clamped at 255 where it is read out
+__device__ __forceinline__ uint32_t* pt_cell(const TableView& t, uint64_t s)
+{
+    if (!t.pt.PC) return nullptr;
+    const uint32_t pos = t.pt.PLACE[s];
+    if (pos == 0u) return nullptr;
+    const uint32_t mir = t.pt.Tp - t.k - pos;
+    return t.pt.PC + (pos < mir ? pos : mir);
+}
+__device__ __forceinline__ uint32_t pt_counted(const TableView& t, uint64_t s)
+{
+    const uint32_t* const pc = pt_cell(t, s);
+    return pc ? *pc : 0u;
+}
+
 // exact-table probe + saturating count of one canonical k-mer (generic kernels; either table format)
 __device__ __forceinline__ uint64_t table_home(const TableView& t, uint64_t canon)
 {
@@ -615,19 +631,37 @@ __device__ __forceinline__ uint4 vmp_bits_value()     // {start bits lo, hi, sat
     if (c == 3) VG_MOV4("v88", "v89", "v90", "v91");
     return v;
 }
-// rare path of the path-table drain: four independent dword loads / four returning atomic increments, one wait for all
-__device__ __forceinline__ void vm_load_dword4_sync(const uint32_t* p0, const uint32_t* p1, const uint32_t* p2, const uint32_t* p3, uint32_t (&v)[4])
+// rare path of the path-table drain: four independent dword loads / four returning atomic increments, one wait for all (the clobbers
+// only keep the compiler's operands below the hand-managed registers: tools/check_hot_vgprs.py)
+__device__ __forceinline__ void vm_load_dword4_sync(const uint32_t* base, const uint32_t (&idx)[4], uint32_t (&v)[4])      // base: wave-uniform
 {
-    asm volatile("global_load_dword %0, %4, off ; VGHOT\n\tglobal_load_dword %1, %5, off ; VGHOT\n\tglobal_load_dword %2, %6, off ; VGHOT\n\t"
-                 "global_load_dword %3, %7, off ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(p0), "v"(p1), "v"(p2), "v"(p3) : "memory");
+    const uint32_t o0 = idx[0] << 2, o1 = idx[1] << 2, o2 = idx[2] << 2, o3 = idx[3] << 2;
+    asm volatile("global_load_dword %0, %4, %8 ; VGHOT\n\tglobal_load_dword %1, %5, %8 ; VGHOT\n\tglobal_load_dword %2, %6, %8 ; VGHOT\n\t"
+                 "global_load_dword %3, %7, %8 ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "s"(base) : "memory", VG_HOT_CLOBBERS_P);
 }
-__device__ __forceinline__ void vm_atomic_add4_sync(uint32_t* p0, uint32_t* p1, uint32_t* p2, uint32_t* p3, const uint32_t (&add)[4], uint32_t (&old)[4])
+__device__ __forceinline__ void vm_atomic_add4_sync(uint32_t* base, const uint32_t (&idx)[4], const uint32_t (&add)[4], uint32_t (&old)[4])
 {
-    asm volatile("global_atomic_add %0, %4, %8, off sc0 ; VGHOT\n\tglobal_atomic_add %1, %5, %9, off sc0 ; VGHOT\n\t"
-                 "global_atomic_add %2, %6, %10, off sc0 ; VGHOT\n\tglobal_atomic_add %3, %7, %11, off sc0 ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT"
+    const uint32_t o0 = idx[0] << 2, o1 = idx[1] << 2, o2 = idx[2] << 2, o3 = idx[3] << 2;
+    asm volatile("global_atomic_add %0, %4, %8, %12 sc0 ; VGHOT\n\tglobal_atomic_add %1, %5, %9, %12 sc0 ; VGHOT\n\t"
+                 "global_atomic_add %2, %6, %10, %12 sc0 ; VGHOT\n\tglobal_atomic_add %3, %7, %11, %12 sc0 ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT"
                  : "=&v"(old[0]), "=&v"(old[1]), "=&v"(old[2]), "=&v"(old[3])
-                 : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(add[0]), "v"(add[1]), "v"(add[2]), "v"(add[3]) : "memory");
+                 : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "v"(add[0]), "v"(add[1]), "v"(add[2]), "v"(add[3]), "s"(base) : "memory", VG_HOT_CLOBBERS_P);
+}
+// position counters of the path-table drain: four returning increments of cells of one array (byte offsets from its base;
+// 0xFFFFFFFF: none -- the lane is masked out of that instruction, no request leaves for it and its `old` stays), one wait for all;
+// every compare runs under the full mask again: a VALU compare clears the bits of inactive lanes
+__device__ __forceinline__ void vm_atomic_inc4_masked_sync(uint32_t* base, const uint32_t (&off)[4], uint32_t one, uint32_t (&old)[4])
+{
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %[sv], exec ; VGHOT\n\t"
+                 "v_cmp_ne_u32_e32 vcc, -1, %[o0] ; VGHOT\n\ts_and_b64 exec, %[sv], vcc ; VGHOT\n\tglobal_atomic_add %[r0], %[o0], %[one], %[b] sc0 ; VGHOT\n\t"
+                 "s_mov_b64 exec, %[sv] ; VGHOT\n\tv_cmp_ne_u32_e32 vcc, -1, %[o1] ; VGHOT\n\ts_and_b64 exec, %[sv], vcc ; VGHOT\n\tglobal_atomic_add %[r1], %[o1], %[one], %[b] sc0 ; VGHOT\n\t"
+                 "s_mov_b64 exec, %[sv] ; VGHOT\n\tv_cmp_ne_u32_e32 vcc, -1, %[o2] ; VGHOT\n\ts_and_b64 exec, %[sv], vcc ; VGHOT\n\tglobal_atomic_add %[r2], %[o2], %[one], %[b] sc0 ; VGHOT\n\t"
+                 "s_mov_b64 exec, %[sv] ; VGHOT\n\tv_cmp_ne_u32_e32 vcc, -1, %[o3] ; VGHOT\n\ts_and_b64 exec, %[sv], vcc ; VGHOT\n\tglobal_atomic_add %[r3], %[o3], %[one], %[b] sc0 ; VGHOT\n\t"
+                 "s_mov_b64 exec, %[sv] ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT"
+                 : [sv] "=&s"(sv), [r0] "+v"(old[0]), [r1] "+v"(old[1]), [r2] "+v"(old[2]), [r3] "+v"(old[3])
+                 : [o0] "v"(off[0]), [o1] "v"(off[1]), [o2] "v"(off[2]), [o3] "v"(off[3]), [one] "v"(one), [b] "s"(base) : "vcc", "memory", VG_HOT_CLOBBERS_P);
 }
 __device__ __forceinline__ uint32_t vm_load_dword_sync(const uint32_t* ptr)
 {
@@ -1269,6 +1303,7 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
     const uint32_t* const ptVB = p.table.pt.VB;
     uint32_t* const ptSB = p.table.pt.SB;
     const uint32_t* const ptSLOT = p.table.pt.SLOT;
+    uint32_t* const ptPC = p.table.pt.PC;
     const uint32_t pt_Tp = p.table.pt.Tp, pt_bshift = 32u - p.table.pt.bucket_log2;
     const uint32_t l1_min = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.l1_min);
     uint32_t n_after_idx = 8, n_after_seq = 8;            // hot operations issued after the index load / after the last load of phase 2
@@ -1409,6 +1444,45 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
         return hits & ~sats;
     };
     auto bump_all = [&](uint32_t todo, uint32_t place) __attribute__((always_inline)) {
+        if (ptPC != nullptr) {
+            // position counters: the hits of a run are consecutive cells of PC, so the wave takes the runs apart -- lane j of each
+            // 16-lane group adds window j of the run that lane s of its group holds, s = the lanes with work in any group, four of
+            // them per round trip.  An instruction then touches the one or two lines of each of (up to) four runs, not 64 lines.
+            const uint64_t busy = __builtin_amdgcn_ballot_w64(todo != 0);
+            uint32_t left = ((uint32_t)busy | (uint32_t)(busy >> 16) | (uint32_t)(busy >> 32) | (uint32_t)(busy >> 48)) & 0xFFFFu;
+#pragma unroll 1
+            while (left != 0) {
+                uint32_t off[4], old[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const bool on = left != 0;
+                    const uint32_t src = ((lane & 48u) + (on ? (uint32_t)__builtin_ctz(left) : 0u)) << 2;
+                    left &= left - 1u;      // 0 stays 0
+                    const uint32_t t = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)todo);
+                    const uint32_t pos = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)place) + (lane & 15u);
+                    const uint32_t mir = pt_Tp - K - pos;
+                    off[q] = on && ((t >> (lane & 15u)) & 1u) ? (pos < mir ? pos : mir) << 2 : 0xFFFFFFFFu;
+                }
+                vm_atomic_inc4_masked_sync(ptPC, off, one, old);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (off[q] != 0xFFFFFFFFu && old[q] == 254u) {
+                        // this increment took the cell to the clamp: later hits skip their atomic (both places), and the k-mer is
+                        // flagged in the hash table as below.  Even k: not while debits stand in counts[slot] -- the sum of the two
+                        // cells is then below the clamp; such a k-mer is never flagged and its hits go on being counted
+                        const uint32_t pos = off[q] >> 2, mir = pt_Tp - K - pos;
+                        const uint32_t sl = vm_load_dword_sync(ptSLOT + pos);
+                        if (!(K & 1u) && (int32_t)vm_load_dword_sync(counts + sl) < 0) continue;
+                        vm_atomic_or_sync(reinterpret_cast<uint32_t*>(&slots8[sl]) + 1, (uint32_t)(VG_SLOT_SAT >> 32));
+                        vm_store_byte_sync(p.table.sat_dirty + (sl >> VG_SAT_REGION_LOG2), 1u);
+                        vm_atomic_or_sync(ptSB + (pos >> 5), 1u << (pos & 31u));
+                        vm_atomic_or_sync(ptSB + (mir >> 5), 1u << (mir & 31u));
+                    }
+                }
+            }
+            return;
+        }
+        // (VGMI_PT_POSCOUNT=0: the counters of the hash table's slots)
         // the unsaturated hits of this lane's run, up to four windows per round (every lane with a hit left takes part): their
         // slots in one round trip, their counters in a second.  A lane with fewer hits left pads the round by adding 0 to the
         // counter of its first window (its own address: a shared dummy would serialise every padded lane of the device).
@@ -1423,9 +1497,10 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
                     pos[q] = place + (live[q] ? (uint32_t)__builtin_ctz(todo) : 0u);
                     todo &= todo - 1u;      // 0 stays 0
                 }
-                vm_load_dword4_sync(ptSLOT + pos[0], ptSLOT + pos[1], ptSLOT + pos[2], ptSLOT + pos[3], sl);
+                vm_load_dword4_sync(ptSLOT, pos, sl);
                 const uint32_t add[4] = {1u, live[1] ? 1u : 0u, live[2] ? 1u : 0u, live[3] ? 1u : 0u};
-                vm_atomic_add4_sync(&counts[sl[0]], &counts[live[1] ? sl[1] : sl[0]], &counts[live[2] ? sl[2] : sl[0]], &counts[live[3] ? sl[3] : sl[0]], add, old);
+                const uint32_t at[4] = {sl[0], live[1] ? sl[1] : sl[0], live[2] ? sl[2] : sl[0], live[3] ? sl[3] : sl[0]};
+                vm_atomic_add4_sync(counts, at, add, old);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if (live[q] && old[q] == 254u) {
@@ -2273,7 +2348,7 @@ __global__ void cov_kernel(TableView t, const uint32_t* key_slot, uint64_t n, co
     __syncthreads();
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t c32 = *count_cell(t, key_slot[i], (uint32_t)i);
+        const uint32_t c32 = *count_cell(t, key_slot[i], (uint32_t)i) + pt_counted(t, key_slot[i]);
         uint32_t c = c32 < 255u ? c32 : 255u;
         // (even k on the fast path: the counter of a saturated k-mer may stand below the clamp -- a debit of seq_kernel<MODE_DEBIT> whose
         // increment the saturation flag then skipped; the flag says the sum reached it)
@@ -2293,9 +2368,16 @@ __global__ void counts_xfer_kernel(TableView t, const uint32_t* key_slot, uint32
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         uint32_t* cell = count_cell(t, key_slot[i], (uint32_t)i);
-        if (import) *cell = ext[i];
-        else {
+        uint32_t* const pc = pt_cell(t, key_slot[i]);
+        if (import) {
+            *cell = ext[i];
+            if (pc) *pc = 0u;
+        } else {
             uint32_t v = *cell;
+            if (pc) {
+                v += *pc;
+                v = v < 255u ? v : 255u;
+            }
             if (t.slots8 && !(t.k & 1u) && (t.slots8[key_slot[i]] & VG_SLOT_SAT) && v < 255u) v = 255u;      // (even k, fast path: see cov_kernel)
             ext[i] = v;
         }
