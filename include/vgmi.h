@@ -464,6 +464,38 @@ int vgmi_hmm_tallies_ploidy(vgmi_ctx *ctx, uint32_t ploidy, uint32_t n_gt, uint3
                             const uint8_t *win_haps /* n_windows x n_gt x ploidy ids */, const uint64_t *win_sel_mask /* n_windows */,
                             uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win /* NULL: all rows in window 0 */,
                             const uint32_t *winner, int use_alive, uint32_t *out /* n_rows x 2 x ploidy */, uint8_t *unique_out);
+/* ---- ... and a DIPLOID sample over a panel of 48 to 254 haplotypes: 7 to 32 bytes of haplotype bits per entry ------------------------
+ * vgmi_hmm_entries_upload packs six bytes of haplotype bits into a word.  Beyond that an entry is handed over as it stands in the graph:
+ *   entries_upload_wide   f[e] the entry's multiplicity, bits + e * bit_len its bit_len (1 .. 32) bytes of haplotype bits.  On the device
+ *                    they become W 64-bit words per entry, little-endian, zero-padded (W = 1 up to 8 bytes, 2 up to 16, 4 up to 32).
+ *                    Coverage and alive bytes are allocated as by entries_upload, every entry alive; vgmi_hmm_sample_upload,
+ *                    _alive_upload and _alive_fetch serve both forms.  It replaces whatever entries the context held, of either form.
+ *   entries_reserve_wide + entries_fill_wide   the same in pieces, for a caller that gathers the entries chunk by chunk: reserve makes room
+ *                    for n_entries (all alive, bits not yet defined), fill writes entries [first, first + n).
+ *   support_wide, emissions_select_wide, tallies_select_wide   the contracts of vgmi_hmm_support, _emissions_select and _tallies_select with
+ *                    n_hap up to 255 (and at most 8 * bit_len - 1), win_top_mask n_windows x W words (word i of window w at [w * W + i]:
+ *                    haplotypes 64 i .. 64 i + 63) and win_used ids up to 8 * bit_len - 2.  The last bit of the vector is the flag it is in
+ *                    the packed form, no haplotype.  gt0 and fix_mask stay masks over the at most 16 places of a window's list, so a part
+ *                    made by emissions_select_wide is scored again by vgmi_hmm_part_fix_rows -- the SAME function, not _fix_rows_wide
+ *                    (whose masks are over haplotype ids) -- and vgmi_hmm_part_set_rows, _part_calls, _part_calls_fre and _part_fetch work
+ *                    on it as on any part.  bit_len must be the upload's.
+ * VGMI_E_INVALID (the context serves on): bit_len outside 1 .. 32, n_hap outside 1 .. 8 * bit_len - 1, a win_used id at or beyond
+ * 8 * bit_len - 1, n_used outside 1 .. 16, n_gt outside 1 .. 128, a row outside the entries or the windows.  VGMI_E_STATE: a _wide call on
+ * a context whose entries were uploaded by vgmi_hmm_entries_upload (or not at all) or with another bit_len; vgmi_hmm_support,
+ * _emissions*, _tallies* on a context whose entries were uploaded by entries_upload_wide. */
+int vgmi_hmm_entries_upload_wide(vgmi_ctx *ctx, const uint8_t *f, const uint8_t *bits /* n_entries x bit_len */, size_t n_entries, uint32_t bit_len);
+int vgmi_hmm_entries_reserve_wide(vgmi_ctx *ctx, size_t n_entries, uint32_t bit_len);
+int vgmi_hmm_entries_fill_wide(vgmi_ctx *ctx, size_t first, size_t n, const uint8_t *f, const uint8_t *bits /* n x bit_len */);
+int vgmi_hmm_support_wide(vgmi_ctx *ctx, uint32_t bit_len, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t *entry_begin,
+                          const uint32_t *entry_count, const uint32_t *row_win, uint32_t *support_out /* n_windows x n_hap */);
+int vgmi_hmm_emissions_select_wide(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used, const uint8_t *pos_a, const uint8_t *pos_b, uint32_t n_windows,
+                                   const uint8_t *win_used /* n_windows x n_used */, const uint64_t *win_top_mask /* n_windows x W */,
+                                   uint32_t bit_len, float ave, double lower, double upper, const void *tables, uint64_t n_rows,
+                                   const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win, const uint16_t *gt0,
+                                   uint32_t *n_kept_out, uint8_t *flags_out, vgmi_hmm_part **out);
+int vgmi_hmm_tallies_select_wide(vgmi_ctx *ctx, uint32_t bit_len, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count,
+                                 const uint32_t *row_win, const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b,
+                                 uint32_t n_used, uint32_t n_windows, const uint8_t *win_used, uint32_t *out, uint8_t *unique_out);
 /* the part's emission rows back on the host (n_rows x n_gt long doubles): tests and diagnostics */
 int vgmi_hmm_part_fetch(vgmi_hmm_part *part, void *obs_out);
 void vgmi_hmm_part_free(vgmi_hmm_part *part);

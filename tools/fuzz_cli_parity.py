@@ -2,8 +2,10 @@
 """Drawn end-to-end cases through both CLIs (the unmodified reference, oracle/_ref/varigraph_det, and varigraph-mi) on one GPU box:
 genome size, variant mix, cohort size and ploidy, k, construct mode, reads per sample and every genotype option are drawn from a seed;
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
-  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N]
---max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from."""
+  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N]
+--max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from.
+--max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100 and 127 diploid VCF samples, as
+far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 255 haplotypes, 7 to 32 bytes of haplotype bits per k-mer."""
 import gzip, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -57,6 +59,7 @@ def dress(path, rng):
 
 
 MAX_PLOIDY = 4      # --max-ploidy N: ploidy 5 .. N joins both draws (DESIGN_INGEST_HMM 4.15: the device's HMM for samples of ploidy 5 .. 8)
+MAX_VCF_SAMPLES = 7      # --max-vcf-samples N: diploid cohorts of up to N samples (DESIGN_INGEST_HMM 4.16: the device's HMM over panels of 48 to 254 haplotypes)
 FORCE = {}      # --k K / --genome G on the command line: the drawn value replaced (round 6: campaigns of k = 28 over graphs on either side of 65 536 k-mers)
 
 
@@ -66,7 +69,8 @@ def case(seed):
     genome = int(pick([40_000, 90_000, 200_000, 400_000, 1_500_000, 1_500_000]))      # (the last: more than 65 536 k-mers with dense variants -- the context table at any k)
     more_ploidy = list(range(5, MAX_PLOIDY + 1))
     vploidy = pick([2, 2, 2, 3, 4] + more_ploidy)
-    n_samples = pick([1, 2, 3, 5, 7]) if vploidy <= 2 else pick([1, 2, 3])
+    more_samples = [n for n in (24, 33, 48, 64, 100, 127) if n <= MAX_VCF_SAMPLES]
+    n_samples = pick([1, 2, 3, 5, 7] + more_samples) if vploidy <= 2 else pick([1, 2, 3])
     k = pick([27, 27, 27, 21, 25, 22, 28, 15, 11, 19, 23, 20, 24, 26])
     k = FORCE.get("k", k)
     genome = FORCE.get("genome", genome)
@@ -138,6 +142,7 @@ if __name__ == "__main__":
     for i, a in enumerate(sys.argv):
         if a in ("--k", "--genome"): FORCE[a[2:]] = int(sys.argv[i + 1])
         if a == "--max-ploidy": MAX_PLOIDY = int(sys.argv[i + 1])
+        if a == "--max-vcf-samples": MAX_VCF_SAMPLES = int(sys.argv[i + 1])
     bad = 0
     for s in range(first, first + n):
         t0 = time.time()

@@ -31,6 +31,7 @@
 #include <unordered_set>
 
 #include "../vgmi_device.h"
+#include "entry_bits.hpp"
 #include "fixed1.hpp"
 #include "mem_advice.hpp"
 #include "node_flanks.hpp"
@@ -298,6 +299,9 @@ struct Genotyper::Run {
     const uint8_t* cov;      // cov_node
     // coverage | multiplicity << 8 | haplotype bits << 16 of every entry in one word, when the bits fit; else nullptr
     const uint64_t* packed = nullptr;
+    // ... and when they do not (7 to 32 bytes, a diploid sample): the entries are read from the graph's bit vectors, and the device holds them
+    // as bytes (hmm_selected; VGH_HMM_WIDE_DEVICE=0: no such path)
+    bool wide = false;
     float hap_cov;
     const GenotypeConfig* cfg;
     uint32_t haploid_num;   // min(-n, #haplotypes)
@@ -636,20 +640,18 @@ void Genotyper::sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vec
     const uint64_t bl = g_.bitlen;
     const uint32_t* const key_of = g_.node_key_index.data();
     // (masks over the places of `used`: 16 for a diploid sample's pairs, up to -n x ploidy <= 64 for a polyploid sample's blocks)
-    auto carried = [&](uint64_t w, uint32_t& low_multi) -> uint64_t {      // bits over `used`: the haplotypes that count as carrying the k-mer
-        const uint8_t c = (uint8_t)w, f = (uint8_t)(w >> 8);
-        const uint64_t bits = w >> 16;
-        const int lb = (int)((bits >> (8 * bl - 1)) & 1u);
-        const bool in_interval = lb == 1 && c >= lower && c <= upper;
-        uint64_t om = 0;
-        for (size_t p = 0; p < used.size(); ++p) om |= (uint64_t)((in_interval && ((gt0_mask >> p) & 1u)) ? 1u : (uint32_t)((bits >> used[p]) & 1u)) << p;
-        low_multi = (c < lower && f >= 2) ? 2u : (!(c > lower || f <= 1)) ? 1u : 0u;      // 2: asks for the sequences; 1: is checked once they are there
-        return om;
+    // bits over `used`: the haplotypes that count as carrying the k-mer (entry_bits.hpp: the packed word, or -- a graph of 7 to 32 bytes of
+    // haplotype bits -- the entry's bytes in the graph's bit vectors and the sample's coverage)
+    auto carried = [&](uint32_t pos, uint32_t& low_multi) -> uint64_t {
+        if (r.packed) return vgh::carried_packed(r.packed[pos], (uint32_t)bl, used.data(), used.size(), gt0_mask, lower, upper, low_multi);
+        const uint32_t key = key_of[pos];
+        return vgh::carried_bytes(r.cov[pos], (uint8_t)g_.f[key], reinterpret_cast<const uint8_t*>(&g_.bitvec[(size_t)key * bl]), (uint32_t)bl, used.data(),
+                                  used.size(), gt0_mask, lower, upper, low_multi);
     };
     uint64_t need = 0;
     for (uint32_t pos : node.kmers) {
         uint32_t lm;
-        const uint64_t om = carried(r.packed[pos], lm);
+        const uint64_t om = carried(pos, lm);
         if (lm == 2u) need |= om;
     }
     if (!need) return;
@@ -676,7 +678,7 @@ void Genotyper::sequence_fixes(const Chrom& chr, uint32_t node_i, const std::vec
     uint32_t j = 0;      // (an entry's index: 32 bits end to end, like entry_count -- graph2node keeps 128 k-mers a node, src/construct_index.cpp:1592-1596, but nothing here relies on it)
     for (uint32_t pos : node.kmers) {
         uint32_t lm;
-        const uint64_t om = carried(r.packed[pos], lm) & need;
+        const uint64_t om = carried(pos, lm) & need;
         if (lm != 0u && om != 0u) {
             const uint64_t key_hash = g_.keys[key_of[pos]];
             uint64_t drop = 0;
@@ -1818,6 +1820,40 @@ void Genotyper::fill_packed(Run& r, uint32_t threads)
     r.packed = packed_.data();
 }
 
+// The graph's half of every entry for a panel of 48 to 254 haplotypes -- multiplicity and the 7 to 32 bytes of haplotype bits -- to the
+// device, once per graph and context: gathered through node_key_index chunk by chunk into a staging buffer (threaded like fill_packed)
+// and handed over (vgmi_hmm_entries_fill_wide); no second copy of n_entries x bitlen bytes is kept on the host.
+void Genotyper::upload_entries_wide(uint32_t threads)
+{
+    const size_t n_entries = g_.node_key_index.size(), bl = g_.bitlen;
+    const auto t0 = std::chrono::steady_clock::now();
+    device_check(dev_, vgmi_hmm_entries_reserve_wide(dev_, n_entries, (uint32_t)bl), "device HMM emissions: ");
+    constexpr size_t kChunk = (size_t)1 << 22;      // entries per hand-over: at most 128 MiB of bits
+    const size_t chunk = std::min(kChunk, std::max<size_t>(n_entries, 1));
+    std::vector<uint8_t> f(chunk), bits(chunk * bl);
+    const uint32_t nt = std::max(1u, threads);
+    for (size_t lo = 0; lo < n_entries; lo += chunk) {
+        const size_t m = std::min(chunk, n_entries - lo);
+        auto part = [&](size_t a, size_t b) {
+            CpuBudget::Hold cpu;
+            PhaseTimer tt(g_phase.fill);
+            for (size_t j = a; j < b; ++j) {
+                const size_t key = g_.node_key_index[lo + j];
+                f[j] = (uint8_t)g_.f[key];
+                std::memcpy(&bits[j * bl], &g_.bitvec[key * bl], bl);
+            }
+        };
+        std::vector<std::thread> fill;
+        for (uint32_t t = 1; t < nt; ++t) fill.emplace_back(part, m * t / nt, m * (t + 1) / nt);
+        part(0, m / nt);
+        for (auto& th : fill) th.join();
+        device_check(dev_, vgmi_hmm_entries_fill_wide(dev_, lo, m, f.data(), bits.data()), "device HMM emissions: ");
+    }
+    if (g_phase_on)
+        std::fprintf(stderr, "[varigraph-mi] HMM haplotype bits on the device: %zu bytes per entry (%zu entries, %.3f s)\n", bl, n_entries,
+                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+}
+
 void Genotyper::reset_calls()
 {
     for (auto& c : chroms_)
@@ -1919,7 +1955,20 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
         const size_t need = 3 * total_room * sel_n_gt * sizeof(long double) * ((4 + dev_parts_ - 1) / dev_parts_) + (size_t(1) << 30);
         return vgmi_device_memory(dev_, &free_b, &total_b) != VGMI_OK || need <= free_b - free_b / 10;
     }());
-    dp.select = device_ok && select_fits && !refuse_select && !dp.emit && r.packed != nullptr && (cfg.sample_ploidy == 2 || blocks) && n_hap_ > r.haploid_num &&
+    // A graph of 7 to 32 bytes of haplotype bits (48 to 254 haplotypes) has no packed words: a diploid sample's entries go to the device as
+    // bytes (r.wide), once per graph and context -- W words and a multiplicity byte per entry that have to fit as well
+    bool wide_fits = true;
+    if (r.wide && !entries_uploaded_) {
+        size_t free_b = 0, total_b = 0;
+        const size_t n_entries = g_.node_key_index.size();
+        const size_t need = n_entries * (8 * (size_t)vgh::words_of((uint32_t)g_.bitlen) + 3) + 3 * total_room * sel_n_gt * sizeof(long double) * ((4 + dev_parts_ - 1) / dev_parts_) +
+                            (size_t(1) << 30);
+        if (vgmi_device_memory(dev_, &free_b, &total_b) == VGMI_OK) wide_fits = need <= free_b - free_b / 10;
+        if (!wide_fits && g_phase_on)
+            std::fprintf(stderr, "[varigraph-mi] HMM on the host: %.1f GiB of device memory wanted, %.1f free\n", need / 1073741824.0, free_b / 1073741824.0);
+    }
+    const bool entries_ok = r.packed != nullptr || (r.wide && wide_fits);
+    dp.select = device_ok && select_fits && !refuse_select && !dp.emit && entries_ok && (cfg.sample_ploidy == 2 || blocks) && n_hap_ > r.haploid_num &&
                 r.haploid_num >= 1 && r.haploid_num <= 16 && dev_n_gt <= 128 && plain_ids && n_hap_ < 8 * g_.bitlen && !knob_off("VGH_HMM_EMIT_DEVICE") &&
                 !knob_off("VGH_HMM_SELECT_DEVICE");
     if (fre) {
@@ -2677,7 +2726,9 @@ struct Genotyper::SelectedSample {
     std::vector<std::vector<std::vector<uint16_t>>> win_gts;
     std::vector<GenotypeList> win_glist;
     std::vector<uint8_t> win_used8;          // diploid: the drawn haplotypes as the device takes them
-    std::vector<uint64_t> win_mask;          // the drawn haplotypes
+    std::vector<uint64_t> win_mask;          // the drawn haplotypes: mask_words words per window (one unless the entries are bytes)
+    uint32_t mask_words = 1;
+    bool wide = false;                       // the entries are on the device as bytes (7 to 32 of them): the _wide calls
     bool by_freq = false;                    // `-m fre`: no keep matrix, no powers; per window the table of its genotypes' haplotypes' scores
     std::vector<std::vector<long double>> win_freq;
     // what the VGH_TIMING line sums over the parts
@@ -2730,8 +2781,13 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
         if (!ss.by_freq) ss.keep_mat = keep_matrix(shape);      // (places keep the haplotypes' order)
     }
     ss.tab = emission_table(ss.ave, ss.ploidy);
+    ss.wide = r.packed == nullptr;
+    if (ss.wide && (!r.wide || ss.blocks)) throw std::runtime_error("internal: a sample without packed entries on the selected path");
+    ss.mask_words = ss.wide ? vgh::words_of((uint32_t)g_.bitlen) : 1u;
+    const uint32_t bit_len = (uint32_t)g_.bitlen;
     if (!entries_uploaded_) {
-        device_check(dev_, vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
+        if (ss.wide) upload_entries_wide(s.n_threads);
+        else device_check(dev_, vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
         entries_uploaded_ = true;
         if (!lists_whole_.load()) alive_stale_.store(true);
     }
@@ -2780,8 +2836,12 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     const int64_t ta = s.since_begin();
     // 1. the support the draw is weighted by, on the device
     std::vector<uint32_t> support(nw * n_hap_, 0);
-    device_check(dev_, vgmi_hmm_support(dev_, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
-                 "device HMM support: ");
+    if (ss.wide)
+        device_check(dev_, vgmi_hmm_support_wide(dev_, bit_len, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
+                     "device HMM support: ");
+    else
+        device_check(dev_, vgmi_hmm_support(dev_, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
+                     "device HMM support: ");
     const int64_t t_sup = s.since_begin();
     // 2. the draws; 3. what follows from them: the window's haplotypes and mask, its genotypes, the rows' reference-allele masks
     ss.win_top.resize(nw);
@@ -2789,7 +2849,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     ss.win_gts.resize(nw);
     ss.win_glist.resize(nw);
     ss.win_used8.assign(ss.blocks ? 0 : nw * n_used, 0);
-    ss.win_mask.assign(nw, 0);
+    ss.win_mask.assign(nw * ss.mask_words, 0);
     ss.win_freq.resize(ss.by_freq ? nw : 0);
     std::vector<uint64_t> gt0(n_rows ? n_rows : 1, 0);
     over_windows(nw, s.n_threads, g_phase.select, [&](size_t wi) {
@@ -2798,7 +2858,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
         top = sampler.top;
         std::sort(top.begin(), top.end());
         if (top.size() != n_used) throw std::runtime_error("internal: a window drew another number of haplotypes");
-        for (size_t p = 0; p < n_used; ++p) ss.win_mask[wi] |= 1ULL << top[p];
+        for (size_t p = 0; p < n_used; ++p) ss.win_mask[wi * ss.mask_words + (top[p] >> 6)] |= 1ULL << (top[p] & 63u);      // (packed entries: ids below 47, one word)
         if (ss.blocks) {
             ss.win_gts[wi] = haplotype_combinations(top, cfg.sample_type, ss.ploidy, (uint16_t)(n_hap_ - 1));
             std::vector<uint16_t>& used = ss.win_used[wi];
@@ -2903,7 +2963,7 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
             std::vector<uint64_t> gt0_ids(n_rows, 0);
             for (size_t lw = 0; lw < nwp; ++lw) {
                 const size_t wi = pt.wins[lw];
-                w_mask[lw] = ss.win_mask[wi];
+                w_mask[lw] = ss.win_mask[wi];      // (a polyploid sample: packed entries, one word per window)
                 for (size_t gi = 0; gi < n_gt; ++gi)
                     for (uint32_t q = 0; q < ss.ploidy; ++q) w_haps[(lw * n_gt + gi) * ss.ploidy + q] = (uint8_t)ss.win_gts[wi][gi][q];
                 const std::vector<uint16_t>& used = ss.win_used[wi];
@@ -2916,10 +2976,16 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
                          "device HMM emissions: ");
         } else {
             const std::vector<uint16_t> gt0_16(pt.gt0.begin(), pt.gt0.end());      // (<= 16 places)
-            device_check(dev_, vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, ss.n_drawn, ss.pos_a.data(), ss.pos_b.data(), (uint32_t)nwp, ss.win_used8.data(),
-                                                         ss.win_mask.data(), (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
-                                                         pt.e_count.data(), pt.row_win.data(), gt0_16.data(), n_kept.data(), flags.data(), &ph.p),
-                         "device HMM emissions: ");
+            if (ss.wide)      // (a diploid sample has one part: its windows are the run's, in order, and so are the masks)
+                device_check(dev_, vgmi_hmm_emissions_select_wide(dev_, (uint32_t)n_gt, ss.n_drawn, ss.pos_a.data(), ss.pos_b.data(), (uint32_t)nwp, ss.win_used8.data(),
+                                                                  ss.win_mask.data(), (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
+                                                                  pt.e_count.data(), pt.row_win.data(), gt0_16.data(), n_kept.data(), flags.data(), &ph.p),
+                             "device HMM emissions: ");
+            else
+                device_check(dev_, vgmi_hmm_emissions_select(dev_, (uint32_t)n_gt, ss.n_drawn, ss.pos_a.data(), ss.pos_b.data(), (uint32_t)nwp, ss.win_used8.data(),
+                                                             ss.win_mask.data(), (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
+                                                             pt.e_count.data(), pt.row_win.data(), gt0_16.data(), n_kept.data(), flags.data(), &ph.p),
+                             "device HMM emissions: ");
         }
         t_emit = s.since_begin();
         // 5. the same prune on the host's lists, for exactly the nodes that lost k-mers; 6. the flagged rows
@@ -2935,8 +3001,15 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
                 Node& node = chr.nodes[row_node[rr]];
                 if (n_kept[rr] != node.kmers.size()) {
                     kept.clear();
-                    for (uint32_t pos : node.kmers)
-                        if ((r.packed[pos] >> 16) & ss.win_mask[wi]) kept.push_back(pos);
+                    if (ss.wide) {      // the entry's bytes in the graph's bit vectors against the window's words
+                        const size_t bl = g_.bitlen;
+                        const uint64_t* const mask = &ss.win_mask[wi * ss.mask_words];
+                        for (uint32_t pos : node.kmers)
+                            if (vgh::meets_bytes(reinterpret_cast<const uint8_t*>(&g_.bitvec[(size_t)g_.node_key_index[pos] * bl]), (uint32_t)bl, mask)) kept.push_back(pos);
+                    } else {
+                        for (uint32_t pos : node.kmers)
+                            if (vgh::meets_packed(r.packed[pos], ss.win_mask[wi])) kept.push_back(pos);
+                    }
                     if (kept.size() != n_kept[rr]) throw std::runtime_error("internal: the device's k-mer lists differ from the host's");
                     node.kmers.keep(kept);
                     ++pruned_nodes;
@@ -3023,9 +3096,15 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
     if (device_tallies && n_steps && !ss.blocks) {
         tally.resize(4 * n_rows);
         tally_uniq.resize(n_rows);
-        device_check(dev_, vgmi_hmm_tallies_select(dev_, n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(), (uint32_t)n_gt, ss.pos_a.data(),
-                                                   ss.pos_b.data(), ss.n_drawn, (uint32_t)nwp, ss.win_used8.data(), tally.data(), tally_uniq.data()),
-                     "device tallies: ");
+        if (ss.wide)
+            device_check(dev_, vgmi_hmm_tallies_select_wide(dev_, (uint32_t)g_.bitlen, n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(),
+                                                            (uint32_t)n_gt, ss.pos_a.data(), ss.pos_b.data(), ss.n_drawn, (uint32_t)nwp, ss.win_used8.data(), tally.data(),
+                                                            tally_uniq.data()),
+                         "device tallies: ");
+        else
+            device_check(dev_, vgmi_hmm_tallies_select(dev_, n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(), (uint32_t)n_gt, ss.pos_a.data(),
+                                                       ss.pos_b.data(), ss.n_drawn, (uint32_t)nwp, ss.win_used8.data(), tally.data(), tally_uniq.data()),
+                         "device tallies: ");
     }
     // 9. the lines
     over_windows(nwp, s.n_threads, g_phase.pass_c, [&](size_t lw) {
@@ -3072,6 +3151,7 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
     r.cfg = &cfg;
     r.haploid_num = std::min(cfg.haploid_num, n_hap_);
     if (g_.bitlen <= 6) fill_packed(r, cfg.threads);
+    else r.wide = g_.bitlen <= 32 && cfg.sample_ploidy == 2 && !knob_off("VGH_HMM_WIDE_DEVICE");
     reset_calls();
 
     RunShared s(r);

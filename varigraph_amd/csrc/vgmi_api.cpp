@@ -529,6 +529,8 @@ void vgmi_destroy(vgmi_ctx* c)
     if (c->d_hmm_entries) (void)hipFree(c->d_hmm_entries);
     if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
     if (c->d_hmm_alive) (void)hipFree(c->d_hmm_alive);
+    if (c->d_hmm_f) (void)hipFree(c->d_hmm_f);
+    if (c->d_hmm_bits) (void)hipFree(c->d_hmm_bits);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

@@ -15,6 +15,9 @@ struct vgmi_hmm_part {
     // a part of vgmi_hmm_emissions_select_ploidy (a genotype list per window): its launch, for vgmi_hmm_part_fix_rows_wide
     bool per_window_lists = false;
     HmmEmitWinParams emit_win{};
+    // a part of vgmi_hmm_emissions_select_wide (W words of haplotype bits per entry; 0: none of the above): its launch, for vgmi_hmm_part_fix_rows
+    uint32_t wide_words = 0;
+    HmmEmitWideParams emit_wide{};
 };
 
 namespace {
@@ -451,6 +454,14 @@ int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_u
 // a part's flagged rows scored again (vgmi_hmm_part_fix_rows, _wide): the part's own launch with the fixes attached
 hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t* rows, const uint32_t* off, const uint32_t* j, const uint16_t* mask, hipStream_t st)
 {
+    if (part.wide_words) {      // (the same masks over the places of a window's list; the entries' bits are W words)
+        HmmEmitWideParams Q = part.emit_wide;
+        Q.e.fix_rows = rows;
+        Q.e.fix_off = off;
+        Q.e.fix_j = j;
+        Q.e.fix_mask = mask;
+        return launch_hmm_emissions_wide(Q, part.wide_words, n, st);
+    }
     HmmEmitParams P = part.emit;
     P.fix_rows = rows;
     P.fix_off = off;
@@ -496,6 +507,57 @@ int hmm_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const ui
     HIPCHK(c, call.finish());
     return VGMI_OK;
 }
+
+// the entries of vgmi_hmm_entries_upload_wide leave the context (a replaced table, either form)
+void hmm_wide_free(vgmi_ctx* c)
+{
+    if (c->d_hmm_f) (void)hipFree(c->d_hmm_f);
+    if (c->d_hmm_bits) (void)hipFree(c->d_hmm_bits);
+    c->d_hmm_f = nullptr;
+    c->d_hmm_bits = nullptr;
+    c->hmm_bit_len = 0;
+    c->hmm_words = 0;
+}
+
+// a _wide call's width against the upload's: VGMI_E_INVALID for a width no upload can have, VGMI_E_STATE for another form or width
+int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len)
+{
+    if (bit_len < 1 || bit_len > 32) return fail(c, VGMI_E_INVALID, std::string(who) + ": 1..32 bytes of haplotype bits");
+    if (!c->d_hmm_bits || !c->d_hmm_f || !c->d_hmm_cov || !c->d_hmm_alive)
+        return fail(c, VGMI_E_STATE, std::string(who) + ": upload the entries with vgmi_hmm_entries_upload_wide first");
+    if (bit_len != c->hmm_bit_len) return fail(c, VGMI_E_STATE, std::string(who) + ": the entries were uploaded with another number of bytes of haplotype bits");
+    return VGMI_OK;
+}
+
+// VGMI_HMM_TIMING=1 for a staged call: upload / kernel / download, milliseconds on stderr (diagnostics)
+struct HmmCallTimes {
+    bool on = getenv("VGMI_HMM_TIMING") != nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    HmmCallTimes()
+    {
+        if (on)
+            for (auto& x : ev) (void)hipEventCreate(&x);
+    }
+    ~HmmCallTimes()
+    {
+        if (on)
+            for (auto& x : ev) (void)hipEventDestroy(x);
+    }
+    void mark(int i, hipStream_t st) { if (on) (void)hipEventRecord(ev[i], st); }
+    void report(HmmCall& call, const char* what, uint64_t n_rows, uint32_t bit_len)
+    {
+        if (!on) return;
+        call.sync();
+        float up = 0, kern = 0, down = 0;
+        if (call.ok()) {
+            (void)hipEventElapsedTime(&up, ev[0], ev[1]);
+            (void)hipEventElapsedTime(&kern, ev[1], ev[2]);
+            (void)hipEventElapsedTime(&down, ev[2], ev[3]);
+        }
+        fprintf(stderr, "[vgmi] HMM %s call, %u bytes of haplotype bits: %llu rows, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", what, bit_len,
+                (unsigned long long)n_rows, up, kern, down);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -507,6 +569,7 @@ int vgmi_hmm_entries_upload(vgmi_ctx* c, const uint64_t* entries, size_t n)
     if (c->d_hmm_entries) (void)hipFree(c->d_hmm_entries);
     if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
     if (c->d_hmm_alive) (void)hipFree(c->d_hmm_alive);
+    hmm_wide_free(c);
     c->d_hmm_entries = nullptr;
     c->d_hmm_cov = nullptr;
     c->d_hmm_alive = nullptr;
@@ -1009,6 +1072,212 @@ int vgmi_hmm_tallies_ploidy(vgmi_ctx* c, uint32_t ploidy, uint32_t n_gt, uint32_
     return VGMI_OK;
 }
 
+
+// ---- a diploid sample over a panel of 48 to 254 haplotypes (vgmi.h): the entries as a multiplicity byte and W words of haplotype bits ----
+int vgmi_hmm_entries_reserve_wide(vgmi_ctx* c, size_t n, uint32_t bit_len)
+{
+    if (!c) return VGMI_E_INVALID;
+    if (bit_len < 1 || bit_len > 32) return fail(c, VGMI_E_INVALID, "HMM entries: 1..32 bytes of haplotype bits");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->d_hmm_entries) (void)hipFree(c->d_hmm_entries);
+    if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
+    if (c->d_hmm_alive) (void)hipFree(c->d_hmm_alive);
+    hmm_wide_free(c);
+    c->d_hmm_entries = nullptr;
+    c->d_hmm_cov = nullptr;
+    c->d_hmm_alive = nullptr;
+    c->hmm_n_entries = n;
+    const uint32_t W = bit_len <= 8 ? 1u : bit_len <= 16 ? 2u : 4u;
+    if (hipMalloc(reinterpret_cast<void**>(&c->d_hmm_f), n ? n : 1) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->d_hmm_bits), (n ? n : 1) * 8 * W) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->d_hmm_cov), n ? n : 1) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->d_hmm_alive), n ? n : 1) != hipSuccess) {
+        (void)hipGetLastError();
+        if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
+        if (c->d_hmm_alive) (void)hipFree(c->d_hmm_alive);
+        c->d_hmm_cov = nullptr;
+        c->d_hmm_alive = nullptr;
+        hmm_wide_free(c);
+        c->hmm_n_entries = 0;
+        return fail(c, VGMI_E_NOMEM, "HMM emissions: not enough device memory for the node-list entries");
+    }
+    c->hmm_bit_len = bit_len;
+    c->hmm_words = W;
+    HIPCHK(c, hipMemset(c->d_hmm_bits, 0, (n ? n : 1) * 8 * W));
+    HIPCHK(c, hipMemset(c->d_hmm_f, 0, n ? n : 1));
+    HIPCHK(c, hipMemset(c->d_hmm_alive, 1, n ? n : 1));      // a fresh graph: every entry is in its node's list
+    return VGMI_OK;
+}
+
+int vgmi_hmm_entries_fill_wide(vgmi_ctx* c, size_t first, size_t n, const uint8_t* f, const uint8_t* bits)
+{
+    if (!c || (n && (!f || !bits))) return VGMI_E_INVALID;
+    if (!c->d_hmm_bits || !c->d_hmm_f) return fail(c, VGMI_E_STATE, "HMM entries: reserve the entries first");
+    if (first > c->hmm_n_entries || n > c->hmm_n_entries - first) return fail(c, VGMI_E_INVALID, "HMM entries: a range outside the reserved entries");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t W = c->hmm_words, bl = c->hmm_bit_len;
+    constexpr size_t kChunk = (size_t)1 << 20;      // entries per staged copy
+    std::vector<uint64_t> words;
+    for (size_t a = 0; a < n; a += kChunk) {
+        const size_t m = std::min(kChunk, n - a);
+        words.assign(m * W, 0);
+        for (size_t j = 0; j < m; ++j) memcpy(&words[j * W], bits + (a + j) * bl, bl);      // (little-endian host: byte i of the vector is byte i of the words)
+        HIPCHK(c, hipMemcpy(c->d_hmm_bits + (first + a) * W, words.data(), m * W * 8, hipMemcpyHostToDevice));
+    }
+    if (n) HIPCHK(c, hipMemcpy(c->d_hmm_f + first, f, n, hipMemcpyHostToDevice));
+    return VGMI_OK;
+}
+
+int vgmi_hmm_entries_upload_wide(vgmi_ctx* c, const uint8_t* f, const uint8_t* bits, size_t n, uint32_t bit_len)
+{
+    if (!c || (n && (!f || !bits))) return VGMI_E_INVALID;
+    if (int rc = vgmi_hmm_entries_reserve_wide(c, n, bit_len)) return rc;
+    return vgmi_hmm_entries_fill_wide(c, 0, n, f, bits);
+}
+
+int vgmi_hmm_support_wide(vgmi_ctx* c, uint32_t bit_len, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t* entry_begin,
+                          const uint32_t* entry_count, const uint32_t* row_win, uint32_t* support_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win)) || (n_windows && !support_out)) return VGMI_E_INVALID;
+    if (int rc = hmm_check_wide(c, "HMM support", bit_len)) return rc;
+    if (n_hap < 1 || n_hap > 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM support: more haplotypes than the haplotype bits hold");
+    if (int rc = hmm_check_rows(c, "HMM support", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_windows == 0) return VGMI_OK;
+    const size_t b_sup = (size_t)n_windows * n_hap * 4;
+    if (n_rows == 0) {
+        memset(support_out, 0, b_sup);
+        return VGMI_OK;
+    }
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_sup = call.add(b_sup);
+    if (int rc = call.begin("HMM support")) return rc;
+    HmmCallTimes tm;
+    tm.mark(0, call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    call.upload(o_win, row_win, n_rows * 4);
+    call.zero(o_sup, b_sup);
+    tm.mark(1, call.stream());
+    call.run([&] {
+        return launch_hmm_support_wide(c->hmm_words, c->d_hmm_f, c->d_hmm_bits, c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg),
+                                       call.at<const uint32_t>(o_cnt), call.at<const uint32_t>(o_win), n_rows, n_hap, call.at<uint32_t>(o_sup), call.stream());
+    });
+    tm.mark(2, call.stream());
+    call.download(support_out, o_sup, b_sup);
+    tm.mark(3, call.stream());
+    tm.report(call, "support", n_rows, bit_len);
+    HIPCHK(c, call.finish());
+    return VGMI_OK;
+}
+
+int vgmi_hmm_emissions_select_wide(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_windows,
+                                   const uint8_t* win_used, const uint64_t* win_top_mask, uint32_t bit_len, float ave, double lower, double upper,
+                                   const void* tables, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                                   const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    if (!c || !pos_a || !pos_b || !tables || !out) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes over 1..16 haplotypes");
+    if (n_windows < 1 || !win_used || !win_top_mask || (n_rows && !row_win)) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their selections");
+    if (n_rows && (!entry_begin || !entry_count || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
+    if (int rc = hmm_check_wide(c, "HMM emissions", bit_len)) return rc;
+    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
+        if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a selected haplotype outside the haplotype bits");
+    HmmEmitWideParams Q{};
+    HmmEmitParams& P = Q.e;
+    for (uint32_t g = 0; g < n_gt; ++g) {
+        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype names a haplotype outside the list");
+        P.pos_a[g] = pos_a[g];
+        P.pos_b[g] = pos_b[g];
+    }
+    if (int rc = hmm_check_rows(c, "HMM emissions", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    *out = nullptr;
+    const uint32_t W = c->hmm_words;
+    HmmEmitCall ec(c, n_rows, 2, 2);
+    HmmCall& call = ec.call;
+    const size_t o_rw = call.add(n_rows * 4), o_wu = call.add((size_t)n_windows * 16), o_wm = call.add((size_t)n_windows * 8 * W);
+    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used);
+    if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
+    HmmCallTimes tm;
+    tm.mark(0, call.stream());
+    call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_wu, wu16.data(), wu16.size());
+    call.upload(o_wm, win_top_mask, (size_t)n_windows * 8 * W);
+    Q.f = c->d_hmm_f;
+    Q.bits = c->d_hmm_bits;
+    P.cov = c->d_hmm_cov;
+    P.alive = c->d_hmm_alive;
+    P.entry_begin = call.at<const uint64_t>(ec.o_eb);
+    P.entry_count = call.at<const uint32_t>(ec.o_ec);
+    P.gt0 = call.at<const uint16_t>(ec.o_g0);
+    P.row_lo = 0;
+    P.n_gt = n_gt;
+    P.n_used = n_used;
+    P.bl8 = 8 * bit_len;
+    P.ploidy = 2;
+    P.ave = ave;
+    P.lower = lower;
+    P.upper = upper;
+    P.tables = call.at(ec.o_tab);
+    P.obs = ec.part->d_obs;
+    P.n_kept = call.at<uint32_t>(ec.o_nk);
+    P.flags = call.at(ec.o_fl);
+    P.row_win = call.at<const uint32_t>(o_rw);
+    P.win_used = call.at(o_wu);
+    P.win_top_mask = call.at<const unsigned long long>(o_wm);
+    tm.mark(1, call.stream());
+    call.run([&] { return launch_hmm_emissions_wide(Q, W, n_rows, call.stream()); });
+    tm.mark(2, call.stream());
+    ec.part->wide_words = W;
+    ec.part->emit_wide = Q;
+    if (tm.on) {      // (finish() fetches them again: the figure is the diagnostics')
+        call.download(n_kept_out, ec.o_nk, n_rows * 4);
+        call.download(flags_out, ec.o_fl, n_rows);
+        tm.mark(3, call.stream());
+        tm.report(call, "emission", n_rows, bit_len);
+    }
+    return ec.finish(entry_count, n_kept_out, flags_out, out);
+}
+
+int vgmi_hmm_tallies_select_wide(vgmi_ctx* c, uint32_t bit_len, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
+                                 const uint32_t* row_win, const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used,
+                                 uint32_t n_windows, const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win || !winner || !out || !unique_out)) || !pos_a || !pos_b || !win_used) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16 || n_windows < 1) return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes over 1..16 haplotypes");
+    if (int rc = hmm_check_wide(c, "HMM tallies", bit_len)) return rc;
+    for (uint32_t g = 0; g < n_gt; ++g)
+        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM tallies: a genotype names a haplotype outside the list");
+    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
+        if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
+    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_rows == 0) return VGMI_OK;
+    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used), pos_ab = hmm_pos_pairs(pos_a, pos_b, n_gt);
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_out = call.add(n_rows * 16),
+                 o_uni = call.add(n_rows), o_pos = call.add(pos_ab.size()), o_wu = call.add(wu16.size());
+    if (int rc = call.begin("HMM tallies")) return rc;
+    HmmCallTimes tm;
+    tm.mark(0, call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_win, winner, n_rows * 4);
+    call.upload(o_pos, pos_ab.data(), pos_ab.size());
+    call.upload(o_wu, wu16.data(), wu16.size());
+    tm.mark(1, call.stream());
+    call.run([&] {
+        return launch_hmm_tally_wide(c->hmm_words, c->d_hmm_f, c->d_hmm_bits, c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg),
+                                     call.at<const uint32_t>(o_cnt), call.at<const uint32_t>(o_rw), call.at<const uint32_t>(o_win), call.at(o_pos), call.at(o_wu),
+                                     n_gt, n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
+    });
+    tm.mark(2, call.stream());
+    call.download(out, o_out, n_rows * 16);
+    call.download(unique_out, o_uni, n_rows);
+    tm.mark(3, call.stream());
+    tm.report(call, "tally", n_rows, bit_len);
+    HIPCHK(c, call.finish());
+    return VGMI_OK;
+}
 
 int vgmi_hmm_part_fetch(vgmi_hmm_part* part, void* obs_out)
 {

@@ -933,6 +933,222 @@ __global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long lo
     }
 }
 
+// ---- panels of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry's haplotype bits are W = 1, 2 or 4 words ----------------------------
+// The packed word above holds six bytes of haplotype bits.  Here an entry is its multiplicity byte f[e] and its bit vector as it stands
+// in the graph, little-endian in W 64-bit words, zero-padded, entry-major: bits[e * W + i] -- one contiguous 8, 16 or 32-byte load.
+// The last bit of the vector (bit bl8 - 1) is the flag it is everywhere, never a haplotype.  The three kernels keep the layouts of their
+// namesakes: row, window and every haplotype id are wavefront-uniform where they were, so the words of an entry, the window's mask and
+// the choice of the word that holds a haplotype stay on the scalar side.  A register array of W words is only ever indexed by an
+// unrolled loop's counter; the word of haplotype `hap` is picked by a chain over W (hmm_pick_word) or loaded on its own (the tallies).
+template <uint32_t W>
+__device__ __forceinline__ unsigned long long hmm_pick_word(const unsigned long long (&b)[W], uint32_t wi)
+{
+    unsigned long long w = 0;      // (masks, not selects: a chain of selects over an array is what the compiler turns back into an index)
+#pragma unroll
+    for (uint32_t i = 0; i < W; ++i) w |= b[i] & (0ull - (unsigned long long)(wi == i));
+    return w;
+}
+
+// hmm_support_kernel for up to 255 haplotypes: a wavefront per row, a lane per entry, the set bits walked word by word
+template <uint32_t W>
+__global__ __launch_bounds__(256) void hmm_support_wide_kernel(const uint8_t* __restrict__ f, const unsigned long long* __restrict__ bits,
+                                                               const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
+                                                               const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
+                                                               const uint32_t* __restrict__ row_win, uint64_t n_rows, uint32_t n_hap,
+                                                               uint32_t* __restrict__ support)
+{
+    __shared__ uint32_t s_sup[256];
+    const uint64_t r0 = (uint64_t)blockIdx.x * kSupportRows;
+    const uint64_t r1 = r0 + kSupportRows < n_rows ? r0 + kSupportRows : n_rows;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    unsigned long long hap_mask[W];      // the first n_hap bits (n_hap <= 64 W - 1)
+#pragma unroll
+    for (uint32_t i = 0; i < W; ++i) hap_mask[i] = n_hap >= 64u * (i + 1u) ? ~0ull : n_hap <= 64u * i ? 0ull : (1ull << (n_hap - 64u * i)) - 1ull;
+    uint64_t ra = r0;
+    while (ra < r1) {      // the rows [ra, rb) of one window
+        const uint32_t w = row_win[ra];
+        uint64_t rb = ra + 1;
+        while (rb < r1 && row_win[rb] == w) ++rb;
+        s_sup[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint64_t r = ra + wave; r < rb; r += 4) {
+            const uint64_t e0 = entry_begin[r];
+            const uint32_t cnt = entry_count[r];
+            for (uint32_t j = lane; j < cnt; j += 64u) {
+                const uint64_t e = e0 + j;
+                if (alive[e] == 0) continue;
+                const uint32_t c = cov[e];
+                if (c <= 1u || (uint32_t)f[e] > 1u) continue;
+#pragma unroll
+                for (uint32_t i = 0; i < W; ++i) {
+                    unsigned long long word = bits[e * W + i] & hap_mask[i];
+                    while (word) {
+                        const uint32_t hap = 64u * i + (uint32_t)__ffsll((long long)word) - 1u;
+                        word &= word - 1ull;
+                        atomicAdd(&s_sup[hap], c);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
+        __syncthreads();
+        ra = rb;
+    }
+}
+
+// hmm_emissions_kernel<true, 4> for a diploid sample over such a panel: a workgroup per row, a lane per pair of places.  The prune asks
+// whether ANY word of the entry meets the window's mask; from `om` -- at most 16 bits over the places of the window's list -- on it is
+// that kernel: the same term tables in LDS (15 360 bytes), the same products.
+template <uint32_t W>
+__global__ __launch_bounds__(128) void hmm_emissions_wide_kernel(HmmEmitWideParams Q)
+{
+    __shared__ uint64_t s_tm[5u * 256u];
+    __shared__ int32_t s_te[5u * 256u];
+    const HmmEmitParams& P = Q.e;
+    const uint32_t g = threadIdx.x;
+    hmm_stage_tables<128>(P.tables, 2u, s_tm, s_te);
+    const uint64_t rowi = P.fix_rows ? P.fix_rows[blockIdx.x] : P.row_lo + blockIdx.x;
+    uint32_t fp = P.fix_rows ? P.fix_off[blockIdx.x] : 0u;
+    const uint32_t fe = P.fix_rows ? P.fix_off[blockIdx.x + 1] : 0u;
+    const uint64_t e0 = P.entry_begin[rowi];
+    const uint32_t cnt = P.entry_count[rowi], gt0 = P.gt0[rowi];
+    const bool active = g < P.n_gt;
+    const uint32_t w = P.row_win[rowi];
+    unsigned long long top_mask[W];
+#pragma unroll
+    for (uint32_t i = 0; i < W; ++i) top_mask[i] = P.win_top_mask[(size_t)w * W + i];
+    const uint8_t* const wused = P.win_used + (size_t)w * 16u;
+    const uint32_t pa = P.pos_a[active ? g : 0u], pb = P.pos_b[active ? g : 0u];
+    const uint32_t lb_word = (P.bl8 - 1u) >> 6, lb_bit = (P.bl8 - 1u) & 63u;
+    VgN80 prod;
+    prod.m = 1ULL << 63;      // 1.0L
+    prod.e = VG_X80_BIAS;
+    uint32_t kept = 0, flag = 0;
+    for (uint32_t j = 0; j < cnt; ++j) {
+        const uint64_t e = e0 + j;
+        if (P.alive[e] == 0) continue;      // pruned by an earlier window's or sample's selection
+        unsigned long long b[W], met = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < W; ++i) {
+            b[i] = Q.bits[e * W + i];
+            met |= b[i] & top_mask[i];
+        }
+        const uint32_t c = P.cov[e], f = Q.f[e];
+        if (met == 0) {
+            if (g == 0 && !P.fix_rows) P.alive[e] = 0;      // the prune
+            continue;
+        }
+        ++kept;
+        const uint32_t lb = (uint32_t)(hmm_pick_word<W>(b, lb_word) >> lb_bit) & 1u;
+        const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
+        uint32_t om = 0;
+        for (uint32_t p = 0; p < P.n_used; ++p) {
+            const uint32_t hap = (uint32_t)wused[p];
+            const uint32_t one = (in_interval && ((gt0 >> p) & 1u)) ? 1u : (uint32_t)((hmm_pick_word<W>(b, hap >> 6) >> (hap & 63u)) & 1ull);
+            om |= one << p;
+        }
+        if ((double)c < P.lower && f >= 2u && om != 0) flag |= 1u;
+        if (fp < fe && P.fix_j[fp] == j) {      // (the second launch: haplotypes whose sequence does not hold this k-mer do not carry it)
+            om &= ~(uint32_t)P.fix_mask[fp];
+            ++fp;
+        }
+        const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
+        const uint32_t h = ((om >> pa) & 1u) + ((om >> pb) & 1u);
+        const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
+        const uint32_t ti = h * 256u + cc;
+        VgN80 t;
+        t.m = s_tm[ti];
+        t.e = s_te[ti];
+        prod = n80_mul(prod, t);
+    }
+    if (active) x80_store(P.obs + (rowi * P.n_gt + g) * 16, n80_to(prod));
+    if (g == 0 && !P.fix_rows) {
+        P.n_kept[rowi] = kept;
+        P.flags[rowi] = (uint8_t)flag;
+    }
+}
+
+// hmm_tally_kernel<true> over such a panel: a lane per row, and per entry the two words that hold the called haplotypes
+template <uint32_t W>
+__global__ __launch_bounds__(256) void hmm_tally_wide_kernel(const uint8_t* __restrict__ f, const unsigned long long* __restrict__ bits,
+                                                             const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
+                                                             const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
+                                                             const uint32_t* __restrict__ row_win, const uint32_t* __restrict__ winner,
+                                                             const uint8_t* __restrict__ pos_ab, const uint8_t* __restrict__ win_used, uint32_t n_gt,
+                                                             uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_rows) return;
+    uint32_t num_a = 0, sum_a = 0, num_b = 0, sum_b = 0, u = 0;
+    const uint32_t g = winner[r];
+    if (g < n_gt) {
+        const uint8_t* used = win_used + (size_t)row_win[r] * 16u;
+        const uint32_t ha = used[pos_ab[2u * g]], hb = used[pos_ab[2u * g + 1u]];
+        const uint32_t wa = W > 1u ? ha >> 6 : 0u, wb = W > 1u ? hb >> 6 : 0u;
+        const uint64_t e0 = entry_begin[r];
+        const uint32_t cnt = entry_count[r];
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint64_t e = e0 + j;
+            if (alive[e] == 0) continue;
+            const uint32_t c = cov[e];
+            if ((uint32_t)f[e] <= 1u && u < 255u) ++u;
+            if ((bits[e * W + wa] >> (ha & 63u)) & 1ull) { ++num_a; sum_a += c; }
+            if ((bits[e * W + wb] >> (hb & 63u)) & 1ull) { ++num_b; sum_b += c; }
+        }
+    }
+    out[4 * r] = num_a;
+    out[4 * r + 1] = sum_a;
+    out[4 * r + 2] = num_b;
+    out[4 * r + 3] = sum_b;
+    uniq[r] = (uint8_t)u;
+}
+
+hipError_t launch_hmm_support_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
+                                   const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap,
+                                   uint32_t* support, hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    if (n_hap < 1 || n_hap > 64u * W - 1u || n_hap > 255u) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((n_rows + kSupportRows - 1) / kSupportRows));
+    switch (W) {
+        case 1: hipLaunchKernelGGL(hmm_support_wide_kernel<1>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, n_rows, n_hap, support); break;
+        case 2: hipLaunchKernelGGL(hmm_support_wide_kernel<2>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, n_rows, n_hap, support); break;
+        case 4: hipLaunchKernelGGL(hmm_support_wide_kernel<4>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, n_rows, n_hap, support); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_hmm_emissions_wide(const HmmEmitWideParams& Q, uint32_t W, uint64_t n_rows, hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    const HmmEmitParams& P = Q.e;
+    if (P.ploidy != 2 || !P.row_win || !P.win_used || !P.win_top_mask || !P.alive || !Q.f || !Q.bits || P.bl8 < 8 || P.bl8 > 64u * W) return hipErrorInvalidValue;
+    switch (W) {
+        case 1: hipLaunchKernelGGL(hmm_emissions_wide_kernel<1>, dim3((uint32_t)n_rows), dim3(128), 0, st, Q); break;
+        case 2: hipLaunchKernelGGL(hmm_emissions_wide_kernel<2>, dim3((uint32_t)n_rows), dim3(128), 0, st, Q); break;
+        case 4: hipLaunchKernelGGL(hmm_emissions_wide_kernel<4>, dim3((uint32_t)n_rows), dim3(128), 0, st, Q); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_hmm_tally_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
+                                 const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
+                                 const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    const dim3 grid((uint32_t)((n_rows + 255) / 256));
+    switch (W) {
+        case 1: hipLaunchKernelGGL(hmm_tally_wide_kernel<1>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, pos_ab, win_used, n_gt, n_rows, out, uniq); break;
+        case 2: hipLaunchKernelGGL(hmm_tally_wide_kernel<2>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, pos_ab, win_used, n_gt, n_rows, out, uniq); break;
+        case 4: hipLaunchKernelGGL(hmm_tally_wide_kernel<4>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, pos_ab, win_used, n_gt, n_rows, out, uniq); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,
                             const uint8_t* hap_ab, uint32_t n_gt, uint32_t n_hap, unsigned long long sel_mask, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
                             hipStream_t st)

@@ -354,6 +354,22 @@ hipError_t launch_hmm_tally_ploidy(const unsigned long long* packed, const uint8
                                    const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
                                    const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
                                    hipStream_t st);
+// ---- panels of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry is its multiplicity byte f[e] and its haplotype bits in W = 1, 2 or 4
+// 64-bit words, little-endian, zero-padded, entry-major (bits[e * W + i]).  The launches keep the contracts of their namesakes above.
+// Emissions, a diploid sample with haplotypes selected per window: `e` as vgmi_hmm_emissions_select fills it, except that `packed` is not
+// read, win_top_mask holds W words per window and win_used ids go up to bl8 - 2
+struct HmmEmitWideParams {
+    HmmEmitParams e;
+    const uint8_t* f;
+    const unsigned long long* bits;
+};
+hipError_t launch_hmm_emissions_wide(const HmmEmitWideParams& Q, uint32_t W, uint64_t n_rows, hipStream_t st);
+hipError_t launch_hmm_support_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
+                                   const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap,
+                                   uint32_t* support, hipStream_t st);
+hipError_t launch_hmm_tally_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
+                                 const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
+                                 const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
 hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uint8_t* src, uint32_t n_gt, uint64_t n, hipStream_t st);
 size_t hmm_lds_bytes(uint32_t n_gt, uint32_t ploidy);
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,
