@@ -1,15 +1,14 @@
 // csrc/vg_x80.h (extended precision in integer arithmetic, non-negative operands) against the x87 unit: products, sums and
 // quotients of random and edge operands -- normal numbers over the whole exponent range, results that underflow gradually,
 // denormal operands, zeros, significands of all ones / single bits / short patterns; the normalised-form variants (n80_*)
-// on the same operands and along the chains.  Prints "<n> cases, <k> mismatches".
+// on the same operands and along the chains.  The operands are X80Gen's (x80_cases.h).  Prints "<n> cases, <k> mismatches".
 // Test infrastructure (tests/test_x80_cpu.py).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
-
 #include "vg_x80.h"
+#include "x80_cases.h"
 
 static long double to_ld(VgX80 v)
 {
@@ -32,48 +31,11 @@ static bool same(VgX80 a, VgX80 b) { return a.m == b.m && a.e == b.e; }
 int main(int argc, char** argv)
 {
     const long n = argc > 1 ? atol(argv[1]) : 3000000;
-    std::mt19937_64 rng(12345);
-    auto significand = [&]() -> uint64_t {
-        switch (rng() % 8) {
-            case 0: return ~0ULL;
-            case 1: return 1ULL << 63;
-            case 2: return (1ULL << 63) | 1u;
-            case 3: return (1ULL << 63) | (rng() & 0xFFFF);
-            case 4: return ~(rng() & 0xFFFF);
-            case 5: return (1ULL << 63) | (1ULL << (rng() % 63));
-            default: return rng() | (1ULL << 63);
-        }
-    };
-    auto value = [&]() -> VgX80 {
-        VgX80 v;
-        const unsigned kind = (unsigned)(rng() % 16);
-        if (kind == 0) {
-            v.m = 0;
-            v.e = 0;
-        } else if (kind == 1) {                       // denormal
-            v.e = 0;
-            v.m = significand() >> (1 + rng() % 63);
-            if (v.m == 0) v.m = 1;
-        } else if (kind < 5) {                        // close to the underflow boundary
-            v.e = 1 + (uint32_t)(rng() % 140);
-            v.m = significand();
-        } else if (kind < 8) {                        // products of these land around the boundary
-            v.e = 8100 + (uint32_t)(rng() % 300);
-            v.m = significand();
-        } else if (kind < 12) {                       // probabilities
-            v.e = VG_X80_BIAS - (uint32_t)(rng() % 200);
-            v.m = significand();
-        } else {                                      // anything below 2^8
-            v.e = 1 + (uint32_t)(rng() % (VG_X80_BIAS + 8));
-            v.m = significand();
-        }
-        return v;
-    };
+    X80Gen gen(12345);
     long bad = 0, cases = 0;
     for (long i = 0; i < n; ++i) {
-        const VgX80 a = value();
-        VgX80 b = value();
-        if (rng() % 3 == 0 && a.e > 80 && b.e) b.e = a.e - 70 + (uint32_t)(rng() % 140);   // every alignment distance of a sum
+        VgX80 a, b;
+        gen.pair(a, b);
         volatile long double x = to_ld(a), y = to_ld(b);
         {
             volatile long double p = x * y;
@@ -100,14 +62,8 @@ int main(int argc, char** argv)
     }
     // the fused term  r + s * o  with r placed around the product (every alignment distance, both orders), and anywhere
     for (long i = 0; i < n; ++i) {
-        const VgX80 sv = value(), o = value();
-        if ((int)sv.e + (int)o.e > 2 * VG_X80_BIAS - 100) continue;
-        VgX80 r = value();
-        if (rng() % 4 && sv.m && o.m) {
-            const int pe = (int)(sv.e ? sv.e : 1) + (int)(o.e ? o.e : 1) - VG_X80_BIAS + (int)(rng() % 140) - 70;
-            r.e = pe < 1 ? 0 : (uint32_t)pe;
-            r.m = r.e ? significand() : significand() >> (1 + rng() % 63);
-        }
+        VgX80 r, sv, o;
+        if (!gen.triple(r, sv, o)) continue;
         volatile long double x = to_ld(r), y = to_ld(sv), z = to_ld(o);
         volatile long double p = y * z;
         volatile long double w = x + p;
@@ -124,10 +80,10 @@ int main(int argc, char** argv)
         VgX80 r = {0, 0};
         VgN80 rn = {0, 0}, rf = {0, 0};
         volatile long double rr = 0.0L;
-        const VgX80 o = value();
+        const VgX80 o = gen.value();
         volatile long double oo = to_ld(o);
         for (int t = 0; t < 120; ++t) {
-            const VgX80 s = value();
+            const VgX80 s = gen.value();
             volatile long double ss = to_ld(s);
             if ((int)s.e + (int)o.e > 2 * VG_X80_BIAS - 100) continue;
             r = x80_add(r, x80_mul(s, o));

@@ -40,6 +40,34 @@ def _host_chain(keep, obs_rows, restart, pows, uniform, ploidy):
     return out
 
 
+def _host_posterior(a, b, gid, order):
+    """posterior() of the host (src/genotype.cpp:1387-1522) on one node's alpha and beta rows in long double: the sum of a * b in entry
+    order, the posteriors, their sums per genotype string in entry order, the first maximum in string order and the first entry of that
+    string with the largest posterior -> (the call's probability, its entry); (None, 0xFFFFFFFF) when the denominator is zero."""
+    n = len(a)
+    p_ = a * b
+    den = LD(0)
+    for g in range(n):
+        den = den + p_[g]
+    if den == 0:
+        return None, 0xFFFFFFFF
+    post = p_ / den
+    sums = {}
+    for g in range(n):
+        sums[gid[g]] = sums.get(gid[g], LD(0)) + post[g]
+    best, best_id = LD(-1), None
+    for k in order:
+        if k == 0xFF:
+            break
+        if sums.get(k, LD(0)) > best:
+            best, best_id = sums.get(k, LD(0)), k
+    mx, win = LD(0), 0xFFFFFFFF
+    for g in range(n):
+        if gid[g] == best_id and mx < post[g]:
+            mx, win = post[g], g
+    return best, win
+
+
 @pytest.mark.parametrize("ploidy,n_hap,waves", [(2, 15, 4), (2, 15, 2), (2, 5, 4), (1, 9, 2), (3, 6, 4), (4, 5, 2)])
 def test_recursion_equals_x87(ploidy, n_hap, waves, monkeypatch):
     """waves: the kernel with four wavefronts per chain (what a launch of few chains gets) or two (a launch of many)."""
@@ -145,27 +173,10 @@ def test_posterior_on_the_device_equals_x87():
         ctx.close()
     n_called = 0
     for r in range(n_rows):
-        a, b = ab[fwd[r]], ab[bwd[r]]
-        den = LD(0)
-        for g in range(n):
-            den = den + a[g] * b[g]
-        if den == 0:
+        best, win = _host_posterior(ab[fwd[r]], ab[bwd[r]], gid[r], order[r])
+        if best is None:
             assert winner[r] == 0xFFFFFFFF
             continue
-        post = (a * b) / den
-        sums = {}
-        for g in range(n):
-            sums[gid[r, g]] = sums.get(gid[r, g], LD(0)) + post[g]
-        best, best_id = LD(-1), None
-        for k in order[r]:
-            if k == 0xFF:
-                break
-            if sums[k] > best:
-                best, best_id = sums[k], k
-        mx, win = LD(0), 0xFFFFFFFF
-        for g in range(n):
-            if gid[r, g] == best_id and mx < post[g]:
-                mx, win = post[g], g
         assert winner[r] == win and prob[r] == best, r
         n_called += win != 0xFFFFFFFF
     assert n_called > 20
@@ -312,28 +323,10 @@ def test_recursion_and_posterior_beyond_128_genotypes_equal_x87(ploidy, n_hap, n
     assert (ab > 0).any() and (ab == 0).any()
     n_called = 0
     for r in range(n_rows):
-        a, b = ab[fwd[r]], ab[bwd[r]]
-        den = LD(0)
-        p_ = a * b
-        for g in range(n):
-            den = den + p_[g]
-        if den == 0:
+        best, win = _host_posterior(ab[fwd[r]], ab[bwd[r]], gid[r], order[r])
+        if best is None:
             assert winner[r] == 0xFFFFFFFF
             continue
-        post = p_ / den
-        sums = {}
-        for g in range(n):
-            sums[gid[r, g]] = sums.get(gid[r, g], LD(0)) + post[g]
-        best, best_id = LD(-1), None
-        for k in order[r]:
-            if k == 0xFF:
-                break
-            if sums[k] > best:
-                best, best_id = sums[k], k
-        mx, win = LD(0), 0xFFFFFFFF
-        for g in range(n):
-            if gid[r, g] == best_id and mx < post[g]:
-                mx, win = post[g], g
         assert winner[r] == win and prob[r] == best, r
         n_called += win != 0xFFFFFFFF
     assert n_called >= n_rows // 2
