@@ -176,7 +176,8 @@ int vgmi_count_kernel_ms(vgmi_ctx *ctx, float *ms, uint64_t *launches);
  *           src/fastq_kmer.cpp:97-105) for REGULAR four-line FASTQ records; the host only moves file text (plain, or
  *           what it inflated) into pinned buffers.  One stream per input file; streams of one context may be driven
  *           from different host threads side by side (everything else of a context stays single-threaded).
- *   open     after vgmi_counts_reset, odd k
+ *   open     after vgmi_counts_reset, any k (even k counts read by read: the reads' offsets in the read block and their
+ *            number are made on the device too, from the block's newlines)
  *   acquire  the next pinned staging buffer (waits until the device has taken the previous contents)
  *   commit   n_bytes of file text, continuing where the previous commit ended: copied, parsed and counted
  *            asynchronously

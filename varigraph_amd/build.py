@@ -33,7 +33,7 @@ def _hipcc():
     raise RuntimeError("hipcc not found: the HIP extension cannot be built")
 
 
-VGMI_SOURCES = ("vgmi_kernels.hip", "vgmi_xtable.hip", "vgmi_ctable.hip", "vgmi_ctdefer.hip", "vgmi_ptable.hip", "vgmi_fastq.hip", "vgmi_bam.hip", "vgmi_fasta.hip", "vgmi_inflate.hip",
+VGMI_SOURCES = ("vgmi_kernels.hip", "vgmi_xtable.hip", "vgmi_ctable.hip", "vgmi_ctdefer.hip", "vgmi_ptable.hip", "vgmi_fastq.hip", "vgmi_bam.hip", "vgmi_fasta.hip", "vgmi_readoff.hip", "vgmi_inflate.hip",
                 "vgmi_gunzip.hip", "vgmi_bloom_bin.hip", "vgmi_hmm.hip", "vgmi_api.cpp", "vgmi_api_table.cpp", "vgmi_api_rccl.cpp",
                 "vgmi_api_fastq.cpp", "vgmi_api_bloom.cpp", "vgmi_api_hmm.cpp")
 

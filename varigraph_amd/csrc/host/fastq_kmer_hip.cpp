@@ -394,6 +394,8 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     }
     res.n_reads = n_rec;
     res.read_base = n_bases;
+    if (std::getenv("VGH_TIMING"))      // (what tells a run served by the device-side reader from one the host reader served, at any k)
+        std::fprintf(stderr, "[varigraph-mi] '%s': %llu reads from the device-side reader\n", path.c_str(), (unsigned long long)n_rec);
     // what the device did not take: the text after the last complete record (an unterminated last line, or nothing), or
     // -- once it met a record that is not a regular four-line one -- the rest of the stream from that record on; for
     // block gzip also the file from the first member the device did not take or could not vouch for
@@ -438,7 +440,7 @@ void FastqKmerHip::build_fastq_index()
     mReadNum = 0;
 
     const char* force_host = std::getenv("VGH_HOST_PARSE");
-    if ((k_ & 1) && !(force_host && force_host[0] == '1')) {
+    if (!(force_host && force_host[0] == '1')) {
         // device-side record parsing: one worker per file (two at a time: the files of a pair), each moving file text
         // through its own pinned buffers and HIP stream
         const size_t n_par = std::min<size_t>(std::min<size_t>(threads_, 2), files_.size());

@@ -324,7 +324,7 @@ int main_genotype(int argc, char** argv)
     // while the graph still loads, not inside the first sample's counting (0.3 s for 12 M pairs, 0.15 s of it allocation): a stream
     // that is closed leaves its buffers in the context's pool
     auto warm_fastq = [&](vgmi_ctx* ctx) {
-        if (!(g.k & 1) || samples.empty()) return;
+        if (samples.empty()) return;
         vgmi_fastq* fq[2] = {nullptr, nullptr};
         const size_t n_streams = std::min<size_t>(2, std::get<1>(samples[0]).size());
         for (size_t i = 0; i < n_streams; ++i)

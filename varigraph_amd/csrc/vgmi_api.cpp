@@ -250,10 +250,11 @@ void rows_geometry(vgmi_ctx* c, bool flds, uint32_t& grid, uint32_t& block)
     else      { block = 256;  grid = (uint32_t)c->n_cu * 8; }
 }
 
-// n_bytes_dev != nullptr: the block's length lives in device memory (device-side FASTQ parser); n_bytes is then only an
-// upper bound and the kernels derive their geometry themselves (odd k only)
+// n_bytes_dev != nullptr: the block's length lives in device memory (device-side readers); n_bytes is then only an
+// upper bound and the kernels derive their geometry themselves.  Even k needs the reads as well: d_read_off[0 .. *n_reads_dev]
+// in device memory, offsets from d_bases, and n_reads a bound on their number (the launch of a lane per read is sized by it)
 int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_t* d_read_off, size_t n_reads,
-                 hipStream_t st, const unsigned long long* n_bytes_dev)
+                 hipStream_t st, const unsigned long long* n_bytes_dev, const unsigned long long* n_reads_dev)
 {
     if (n_bytes == 0) return VGMI_OK;
     const uint32_t k = c->hdr.k;
@@ -267,8 +268,34 @@ int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_
     }
     if (!e0 || !e1) return fail(c, VGMI_E_HIP, "hipEventCreate failed");
     HIPCHK(c, hipEventRecord(e0, st));
-    if (n_bytes_dev) {
-        if (!(k & 1)) return fail(c, VGMI_E_INVALID, "device-side block length: odd k only");
+    if (n_bytes_dev && !(k & 1) && (!d_read_off || !n_reads_dev))
+        return fail(c, VGMI_E_INVALID, "even k with a device-side block length: the reads' offsets and their number (d_read_off, n_reads_dev) are missing");
+    if (n_bytes_dev && !(k & 1)) {
+        // the three branches of even k below, in the same stream order, with everything that follows from the block's length derived in the
+        // kernels (tail27 tells them which fast kernel sits between the debit pass and the tail).  A block under one row leaves the debit
+        // pass and the fast kernel nothing to do, and the tail takes every read.
+        if (c->tv.xt.cb && !c->force_generic) {
+            int rcx = xt_clamp_if_due(c, n_bytes, st);
+            if (rcx) return rcx;
+            unsigned long long* list = nullptr;
+            int rcl = debit_list_of(c, st, &list);
+            if (rcl) return rcl;
+            p.tail27 = 2;
+            HIPCHK(c, launch_even_debit_dev(p, d_read_off, n_reads, n_reads_dev, list, VG_DEBIT_LIST, st));
+            { int rcc = launch_ctable_count(c, p, n_bytes, st); if (rcc) return rcc; }
+            HIPCHK(c, launch_seq_dev(p, d_read_off, n_reads, n_reads_dev, st));
+        } else if (c->fastk_small && c->tv.pt.index && !c->force_generic) {
+            unsigned long long* list = nullptr;
+            int rcl = debit_list_of(c, st, &list);
+            if (rcl) return rcl;
+            p.tail27 = 4;
+            HIPCHK(c, launch_even_debit_dev(p, d_read_off, n_reads, n_reads_dev, list, VG_DEBIT_LIST, st));
+            HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
+            HIPCHK(c, launch_seq_dev(p, d_read_off, n_reads, n_reads_dev, st));
+        } else {
+            HIPCHK(c, launch_seq_dev(p, d_read_off, n_reads, n_reads_dev, st));
+        }
+    } else if (n_bytes_dev) {
         uint32_t grid, block;
         rows_geometry(c, c->filter_in_lds, grid, block);
         if ((c->tv.xt.lines || c->tv.xt.cb) && !c->force_generic) {

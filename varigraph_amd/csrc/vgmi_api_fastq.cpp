@@ -50,6 +50,10 @@ struct vgmi_fastq {
     // FASTA text instead of FASTQ text (vgmi_fastq_open_fasta; vgmi_fasta.hip): its per-line and per-record arrays
     bool fasta = false;
     uint8_t* d_fa = nullptr;
+    // even k: the number of reads of the chunk just parsed (8 bytes), a word per tile of the newline scan, the reads' offsets in the read
+    // block (vgmi_readoff.hip); allocated by the first chunk counted against an even-k table
+    uint8_t* d_even = nullptr;
+    uint64_t cap_reads = 0;
 };
 
 namespace {
@@ -67,7 +71,7 @@ extern "C++" void vgapi::fastq_free(vgmi_fastq* f)
     }
     for (void* p : {(void*)f->d_packed, (void*)f->d_tile, (void*)f->d_nlpos, (void*)f->d_rec, (void*)f->d_off, (void*)f->d_bsum,
                     (void*)f->d_state, (void*)f->d_comp, (void*)f->d_members, (void*)f->d_status, (void*)f->d_crc, (void*)f->d_verdict,
-                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa})
+                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa, (void*)f->d_even})
         if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         if (f->h_members[i]) (void)hipHostFree(f->h_members[i]);
@@ -81,7 +85,6 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
     if (!c || !out) return VGMI_E_INVALID;
     *out = nullptr;
     if (!c->has_table) return fail(c, VGMI_E_STATE, "no table");
-    if (!(c->hdr.k & 1)) return fail(c, VGMI_E_STATE, "the device-side FASTQ parser serves odd k (even k: host reader + vgmi_reads_submit)");
     HIPCHK(c, hipSetDevice(c->device));
     size_t want_cap = c->buffer_bytes < (16u << 20) ? (16u << 20) : (c->buffer_bytes > (1u << 30) ? (1u << 30) : c->buffer_bytes);
     // Text per chunk on the device.  Block-gzip input inflates one member (64 KiB of text) per wavefront: a chunk below
@@ -238,6 +241,36 @@ hipError_t parse_chunk(vgmi_fastq* f, int i, uint32_t n_new, const uint32_t* n_n
 }
 }  // namespace
 
+namespace {
+// The count kernels over the read block of the chunk just parsed.  Its length is on the device (FqState::packed_bytes); `bound` is what
+// the host knows of it: the carried tail + the chunk's text.  Odd k needs no more.  Even k counts read by read: the reads' offsets and
+// their number are made on the device from the block's newlines and passed on.
+int count_chunk(vgmi_fastq* f, size_t bound)
+{
+    vgmi_ctx* c = f->c;
+    const char* const block = reinterpret_cast<const char*>(f->d_packed);
+    if (c->hdr.k & 1) return launch_count(c, block, bound, nullptr, 0, f->stream, &f->d_state->packed_bytes);
+    // Reads a chunk can hold: every reader stops at more lines / candidates than its arrays take, which leaves the FASTQ parser
+    // cap_lines / 4 records, the BAM parser cap_lines / 4 candidates and the FASTA parser (cap_lines + 1) / 2 + 1 records
+    // (fasta_cap_rec): cap_lines / 2 + 4 bounds them all.  A read takes two bytes of the block at least (a base and its '\n'),
+    // so this chunk holds no more than bound / 2.
+    const size_t n_tiles = read_offsets_tiles(f->text_cap + f->tail_max);
+    const size_t tile_bytes = (n_tiles * 4 + 7) & ~(size_t)7;
+    if (!f->d_even) {
+        f->cap_reads = (uint64_t)f->cap_lines / 2 + 4;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&f->d_even), 8 + tile_bytes + (f->cap_reads + 1) * 8));
+        HIPCHK(c, hipMemsetAsync(f->d_even, 0, 8, f->stream));
+    }
+    unsigned long long* const n_reads_dev = reinterpret_cast<unsigned long long*>(f->d_even);
+    uint32_t* const tile = reinterpret_cast<uint32_t*>(f->d_even + 8);
+    uint64_t* const read_off = reinterpret_cast<uint64_t*>(f->d_even + 8 + tile_bytes);
+    if (bound > f->text_cap + f->tail_max) return fail(c, VGMI_E_INVALID, "read block larger than the stream's buffers");
+    HIPCHK(c, launch_read_offsets(f->d_packed, bound, &f->d_state->packed_bytes, tile, read_off, f->cap_reads, n_reads_dev, f->stream));
+    const uint64_t reads_bound = std::min<uint64_t>(f->cap_reads, bound / 2);
+    return launch_count(c, block, bound, read_off, (size_t)reads_bound, f->stream, &f->d_state->packed_bytes, n_reads_dev);
+}
+}  // namespace
+
 extern "C" {
 
 int vgmi_fastq_acquire(vgmi_fastq* f, char** host_buf, size_t* capacity)
@@ -292,8 +325,7 @@ int vgmi_fastq_commit(vgmi_fastq* f, size_t n_bytes)
     f->h_busy[i] = true;
     HIPCHK(c, parse_chunk(f, i, (uint32_t)n_bytes, nullptr));
     // the read block's length is on the device: the count kernels fetch it (upper bound here: tail + chunk)
-    int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + n_bytes, nullptr, 0, f->stream,
-                          &f->d_state->packed_bytes);
+    int rc = count_chunk(f, f->tail_max + n_bytes);
     if (rc) return rc;
     f->next = i ^ 1;
     return VGMI_OK;
@@ -456,13 +488,11 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
         bb.tail_max = b.tail_max;
         bb.n_ref = f->n_ref;
         HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
-        int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + (size_t)text, nullptr, 0, f->stream,
-                              &f->d_state->packed_bytes);
+        int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
     } else if (text) {
         HIPCHK(c, parse_chunk(f, i, text, &f->d_verdict->good_bytes));
-        int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + (size_t)text, nullptr, 0, f->stream,
-                              &f->d_state->packed_bytes);
+        int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
     }
     f->next = i ^ 1;
@@ -840,7 +870,7 @@ int vgmi_fastq_commit_gzip(vgmi_fastq* f, size_t n_bytes, int at_eof, size_t* ta
     if (n_text) *n_text = text_total;
     if (text_total) {
         HIPCHK(c, parse_chunk(f, i, (uint32_t)text_total, nullptr));
-        const int rc = launch_count(c, reinterpret_cast<const char*>(f->d_packed), f->tail_max + text_total, nullptr, 0, f->stream, &f->d_state->packed_bytes);
+        const int rc = count_chunk(f, f->tail_max + text_total);
         if (rc) return rc;
         f->next = i ^ 1;
     }

@@ -167,7 +167,7 @@ bool xtable_wanted(const ImageHeader& h);
 bool ctable_wanted(const ImageHeader& h);
 // vgmi_api.cpp: counting
 int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_t* d_read_off, size_t n_reads, hipStream_t st,
-                 const unsigned long long* n_bytes_dev = nullptr);
+                 const unsigned long long* n_bytes_dev = nullptr, const unsigned long long* n_reads_dev = nullptr);
 int collect_timing(vgmi_ctx* c);
 int ensure_stage(vgmi_ctx* c, Stage& s);
 int sync_stages(vgmi_ctx* c);

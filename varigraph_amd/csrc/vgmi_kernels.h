@@ -431,6 +431,16 @@ hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, ui
 #define VG_DEBIT_LIST (1u << 20)      // positions of non-bases one launch can hand to its walk launch (8 MiB per stream; the rest is walked in the scan)
 #define VG_DEBIT_SUBLISTS 256u       // ... in that many lists of equal size, one counter each (64 bytes apart, behind the positions)
 hipError_t launch_even_debit(const RowParams& p, const uint64_t* read_off, uint64_t n_reads, unsigned long long* list, uint32_t list_cap, hipStream_t st);
+// even k behind the device-side readers: the block's length (p.n_bytes_dev) and the number of reads (n_reads_dev) live in device memory, p.n_bytes
+// and n_reads_bound are the host's bounds, p.tail27 names the fast kernel between the debit pass and the tail (2: context table, 4: path table)
+hipError_t launch_even_debit_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev,
+                                 unsigned long long* list, uint32_t list_cap, hipStream_t st);
+hipError_t launch_seq_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev, hipStream_t st);
+// where the reads of a '\n'-joined read block start (vgmi_readoff.hip): read_off[0 .. n] and n = *n_reads_dev from the block's newlines, its
+// length read from device memory; n_bytes_bound sizes the grid, tile holds a word per 16 KiB of it, cap_reads bounds the offsets written
+hipError_t launch_read_offsets(const uint8_t* packed, uint64_t n_bytes_bound, const unsigned long long* n_bytes_dev, uint32_t* tile, uint64_t* read_off,
+                               uint64_t cap_reads, unsigned long long* n_reads_dev, hipStream_t st);
+size_t read_offsets_tiles(uint64_t n_bytes_bound);
 hipError_t launch_table_clear(const TableView& t, hipStream_t st);
 hipError_t launch_table_insert(const TableView& t, const uint64_t* keys, uint64_t n, uint32_t k, uint32_t* key_slot,
                                uint32_t* filter_rw, uint32_t* grid_rw, bool grid12, uint32_t* status, hipStream_t st);

@@ -1858,15 +1858,47 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
 // (src/kmer.cpp:134 `continue` before ++l; :145 only l is reset).
 // ------------------------------------------------------------------------------------------
 #define VG_SEQ_LDS 16384u   // bytes of read text a wavefront stages (64 reads of up to ~250 bases)
-template <int MODE>
-__global__ __launch_bounds__(256) void seq_kernel(RowParams p, const uint64_t* read_off, uint64_t n_reads)
+
+// even k behind the device-side readers (DEV forms of the kernels below): the first position whose k-mer ends belong to the exact tail,
+// derived from the block's length as rows_kernel derives it from tail27 (2: single 768-byte rows of the context-table kernel, 4: pairs of
+// 1 024-byte rows of count27s_kernel<true, K>, 0: no fast kernel in front) -- the debit pass, the fast kernel and the tail must agree on it
+__device__ __forceinline__ uint64_t even_emit_from(uint32_t tail27, uint64_t n_bytes)
+{
+    if (tail27 == 2) {
+        const uint64_t rows = n_bytes / 768;
+        return rows ? rows * 768 - 1 : 0;
+    }
+    return tail27 == 4 ? (n_bytes / 2048) * 2048 : 0;
+}
+
+// DEV: the block's length (p.n_bytes_dev), the number of reads (n_reads_dev) and emit_from come from device memory; n_reads is then only
+// the bound the grid was sized by.  Behind a fast kernel (p.tail27) the launch is a small fixed grid: lane g takes read r0 + g, r0 the
+// first read that ends behind emit_from (launch_seq_dev).
+template <int MODE, bool DEV = false>
+__global__ __launch_bounds__(256) void seq_kernel(RowParams p, const uint64_t* read_off, uint64_t n_reads, const unsigned long long* n_reads_dev = nullptr)
 {
     // The 64 reads of a wavefront are one contiguous stretch of the block: it is copied into LDS with coalesced 16-byte
     // loads and every lane walks ITS read there (a lane per read straight from global memory touches 64 different
     // lines per step and thrashes the 32 KiB L1).  Stretches longer than the staging area are read in place.
     __shared__ __attribute__((aligned(16))) uint8_t s_text[4][VG_SEQ_LDS];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t n_bytes = p.n_bytes, emit_from = p.emit_from;
+    if constexpr (DEV) {
+        n_reads = *n_reads_dev < n_reads ? *n_reads_dev : n_reads;      // (the bound is the offsets' capacity too: never an index beyond them)
+        n_bytes = *p.n_bytes_dev;
+        emit_from = even_emit_from(p.tail27, n_bytes);
+        if (p.tail27) {      // (uniform) the reads in front of r0 end at or in front of emit_from
+            if (emit_from >= n_bytes) return;
+            uint64_t lo = 0, hi = n_reads;
+            while (lo < hi) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (read_off[mid + 1] <= emit_from) lo = mid + 1;
+                else hi = mid;
+            }
+            r += lo;
+        }
+    }
     const uint64_t r_first = r - lane;
     bool staged = false;
     uint64_t stage_base = 0;
@@ -1874,10 +1906,10 @@ __global__ __launch_bounds__(256) void seq_kernel(RowParams p, const uint64_t* r
         const uint64_t r_last = r_first + 64 < n_reads ? r_first + 64 : n_reads;
         const uint64_t b = read_off[r_first] & ~15ULL, e = read_off[r_last];
         // (the exact tail behind a fast kernel: reads that end in front of emit_from have nothing to count)
-        if (MODE == MODE_COUNT && e <= p.emit_from) return;
-        if (e - b <= VG_SEQ_LDS && e <= ((p.n_bytes + 15) & ~15ULL)) {
+        if (MODE == MODE_COUNT && e <= emit_from) return;
+        if (e - b <= VG_SEQ_LDS && e <= ((n_bytes + 15) & ~15ULL)) {
             for (uint64_t o = b + lane * 16u; o < e; o += 1024)
-                *reinterpret_cast<uint4*>(&s_text[wave][o - b]) = load_chunk(p.bases, p.n_bytes, o);
+                *reinterpret_cast<uint4*>(&s_text[wave][o - b]) = load_chunk(p.bases, n_bytes, o);
             staged = true;
             stage_base = b;
         }
@@ -1906,7 +1938,7 @@ __global__ __launch_bounds__(256) void seq_kernel(RowParams p, const uint64_t* r
                 if (l >= K) {
                     const uint64_t canon = fwd < rc ? fwd : rc;
                     if (MODE == MODE_COUNT) {
-                        if (i >= p.emit_from && filter_test_global(p.table, canon)) table_count(p.table, canon);
+                        if (i >= emit_from && filter_test_global(p.table, canon)) table_count(p.table, canon);
                     } else if (MODE == MODE_BLOOM) {
                         bloom_add_key(p.bloom, vg_hash64(canon, mask) << 8 | K);
                     } else {
@@ -1981,7 +2013,7 @@ __device__ __forceinline__ void debit_codes16(const vg_u32x4 v, uint32_t t0, boo
     }
 }
 
-__device__ __forceinline__ void debit_behind_non_base(const RowParams& p, uint64_t i, uint64_t lo, uint64_t hi)
+__device__ __forceinline__ void debit_behind_non_base(const RowParams& p, uint64_t n_bytes, uint64_t i, uint64_t lo, uint64_t hi)
 {
     const uint8_t* const bases = p.bases;
     const uint32_t K = p.k;
@@ -2007,7 +2039,7 @@ __device__ __forceinline__ void debit_behind_non_base(const RowParams& p, uint64
     };
     uint64_t back_from = i, on_from = i + 1;      // where the byte-by-byte walks take over
     bool more = true;
-    if (i >= 32 && i + 33 <= p.n_bytes) {
+    if (i >= 32 && i + 33 <= n_bytes) {
         vg_u32x4 f0, f1, b0, b1;
         __builtin_memcpy(&f0, bases + i + 1, 16);
         __builtin_memcpy(&f1, bases + i + 17, 16);
@@ -2063,18 +2095,32 @@ constexpr uint32_t VG_DEBIT_PIECES = 4;      // 16-byte pieces per lane: a workg
 // (the list: a non-base with a base behind it is work for ONE lane -- 10-20 us of it, four loads and a hundred steps -- and a workgroup of
 // the scan meets 1.6 of them in its 16 KiB: walked where they are found, the scan ran at 0.6 TB/s, every workgroup waiting for a lane.
 // The scan only writes their positions down, a second launch walks them a lane each; what does not fit the list is walked on the spot.)
+// DEV (even k behind the device-side readers): n_bytes, the number of reads and emit_from -- hence limit, hi and the choice between the
+// 16-byte loads and the byte walk -- come from device memory; the host sized the grid by the staged text's capacity, and a workgroup
+// past the real end returns at once.  (A 16-byte load justified by the host's bound would read past the text.)
+template <bool DEV = false>
 __global__ __launch_bounds__(256) void even_debit_kernel(RowParams p, const uint64_t* __restrict__ read_off, uint64_t n_reads,
-                                                         unsigned long long* __restrict__ list, uint32_t list_cap, unsigned int* list_n)
+                                                         unsigned long long* __restrict__ list, uint32_t list_cap, unsigned int* list_n,
+                                                         const unsigned long long* n_reads_dev = nullptr)
 {
-    const uint64_t limit = p.emit_from < p.n_bytes ? p.emit_from : p.n_bytes;
+    uint64_t n_bytes = p.n_bytes, emit_from = p.emit_from;
+    if constexpr (DEV) {
+        n_bytes = *p.n_bytes_dev;
+        n_reads = *n_reads_dev < n_reads ? *n_reads_dev : n_reads;      // (the bound is the offsets' capacity too)
+        emit_from = even_emit_from(p.tail27, n_bytes);
+    }
+    const uint64_t limit = emit_from < n_bytes ? emit_from : n_bytes;
+    if constexpr (DEV) {
+        if ((uint64_t)blockIdx.x * (256u * 16u * VG_DEBIT_PIECES) >= limit) return;
+    }
     const uint64_t base = (uint64_t)blockIdx.x * (256u * 16u * VG_DEBIT_PIECES) + threadIdx.x * 16u;
     vg_u32x4 v[VG_DEBIT_PIECES];
 #pragma unroll
     for (uint32_t t = 0; t < VG_DEBIT_PIECES; ++t) {
         const uint64_t a = base + (uint64_t)t * 4096u;
-        if (a + 16 <= p.n_bytes) v[t] = __builtin_nontemporal_load(reinterpret_cast<const vg_u32x4*>(p.bases + a));
+        if (a + 16 <= n_bytes) v[t] = __builtin_nontemporal_load(reinterpret_cast<const vg_u32x4*>(p.bases + a));
         else {
-            const uint4 c = a < limit ? load_chunk(p.bases, p.n_bytes, a) : make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);
+            const uint4 c = a < limit ? load_chunk(p.bases, n_bytes, a) : make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);
             v[t] = vg_u32x4{c.x, c.y, c.z, c.w};
         }
     }
@@ -2102,20 +2148,27 @@ __global__ __launch_bounds__(256) void even_debit_kernel(RowParams p, const uint
             const uint32_t sub = blockIdx.x & (VG_DEBIT_SUBLISTS - 1u), sub_cap = list_cap / VG_DEBIT_SUBLISTS;
             const uint32_t at = atomicAdd(list_n + 16u * sub, 1u);
             if (at < sub_cap) list[(size_t)sub * sub_cap + at] = i;
-            else debit_behind_non_base(p, i, lo, hi);
+            else debit_behind_non_base(p, n_bytes, i, lo, hi);
         }
     }
 }
 
+template <bool DEV = false>
 __global__ __launch_bounds__(256) void even_debit_walk_kernel(RowParams p, const uint64_t* __restrict__ read_off, uint64_t n_reads,
                                                               const unsigned long long* __restrict__ list, uint32_t list_cap,
-                                                              const unsigned int* __restrict__ list_n)
+                                                              const unsigned int* __restrict__ list_n, const unsigned long long* n_reads_dev = nullptr)
 {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, sub_cap = list_cap / VG_DEBIT_SUBLISTS, sub = g / sub_cap;
+    uint64_t n_bytes = p.n_bytes, emit_from = p.emit_from;
+    if constexpr (DEV) {
+        n_bytes = *p.n_bytes_dev;
+        n_reads = *n_reads_dev < n_reads ? *n_reads_dev : n_reads;      // (the bound is the offsets' capacity too)
+        emit_from = even_emit_from(p.tail27, n_bytes);
+    }
     if (g >= list_cap || g - sub * sub_cap >= list_n[16u * sub] || n_reads == 0) return;
-    const uint64_t limit = p.emit_from < p.n_bytes ? p.emit_from : p.n_bytes;
+    const uint64_t limit = emit_from < n_bytes ? emit_from : n_bytes;
     const uint64_t lo = read_off[0], hi = read_off[n_reads] < limit ? read_off[n_reads] : limit;
-    debit_behind_non_base(p, list[g], lo, hi);
+    debit_behind_non_base(p, n_bytes, list[g], lo, hi);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2493,10 +2546,10 @@ hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, ui
     const uint32_t block = 256;
     const uint32_t grid = (uint32_t)((n_reads + block - 1) / block);
     if (grid == 0) return hipSuccess;
-    if (mode == MODE_COUNT) hipLaunchKernelGGL((seq_kernel<MODE_COUNT>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads);
-    else if (mode == MODE_KEYS) hipLaunchKernelGGL((seq_kernel<MODE_KEYS>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads);
+    if (mode == MODE_COUNT) hipLaunchKernelGGL((seq_kernel<MODE_COUNT, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
+    else if (mode == MODE_KEYS) hipLaunchKernelGGL((seq_kernel<MODE_KEYS, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
     else if (mode == MODE_DEBIT) return hipErrorInvalidValue;      // launch_even_debit
-    else hipLaunchKernelGGL((seq_kernel<MODE_BLOOM>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads);
+    else hipLaunchKernelGGL((seq_kernel<MODE_BLOOM, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
     return hipGetLastError();
 }
 
@@ -2508,8 +2561,39 @@ hipError_t launch_even_debit(const RowParams& p, const uint64_t* read_off, uint6
     unsigned int* const list_n = reinterpret_cast<unsigned int*>(list + list_cap);
     hipError_t e = hipMemsetAsync(list_n, 0, VG_DEBIT_SUBLISTS * 64, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(even_debit_kernel, dim3((uint32_t)((limit + per_wg - 1) / per_wg)), dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n);
-    hipLaunchKernelGGL(even_debit_walk_kernel, dim3((list_cap + 255) / 256), dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n);
+    hipLaunchKernelGGL(even_debit_kernel<false>, dim3((uint32_t)((limit + per_wg - 1) / per_wg)), dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n,
+                       (const unsigned long long*)nullptr);
+    hipLaunchKernelGGL(even_debit_walk_kernel<false>, dim3((list_cap + 255) / 256), dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n,
+                       (const unsigned long long*)nullptr);
+    return hipGetLastError();
+}
+
+// ... with the block's length and the number of reads in device memory (p.n_bytes_dev, n_reads_dev; p.tail27 names the fast kernel that
+// follows): the scan's grid covers p.n_bytes, the host's bound on the length
+hipError_t launch_even_debit_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev,
+                                 unsigned long long* list, uint32_t list_cap, hipStream_t st)
+{
+    const uint64_t per_wg = 256u * 16u * VG_DEBIT_PIECES;
+    if (p.n_bytes == 0) return hipSuccess;
+    unsigned int* const list_n = reinterpret_cast<unsigned int*>(list + list_cap);
+    hipError_t e = hipMemsetAsync(list_n, 0, VG_DEBIT_SUBLISTS * 64, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(even_debit_kernel<true>, dim3((uint32_t)((p.n_bytes + per_wg - 1) / per_wg)), dim3(256), 0, st, p, read_off, n_reads_bound, list, list_cap,
+                       list_n, n_reads_dev);
+    hipLaunchKernelGGL(even_debit_walk_kernel<true>, dim3((list_cap + 255) / 256), dim3(256), 0, st, p, read_off, n_reads_bound, list, list_cap, list_n, n_reads_dev);
+    return hipGetLastError();
+}
+
+// seq_kernel<MODE_COUNT> with the block's length and the number of reads in device memory.  p.tail27 == 0: every read, a lane per read
+// the chunk can hold (n_reads_bound).  Else the exact tail behind a fast kernel: the text at or behind emit_from is under two rows
+// (2 047 bytes behind pairs of 1 024-byte rows, 768 behind single 768-byte rows), a read takes two bytes of it at least (a base and its
+// '\n'), so the reads that end behind emit_from are the one that straddles it and 1 023 more at most: five workgroups of 256 lanes.
+hipError_t launch_seq_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev, hipStream_t st)
+{
+    const uint32_t block = 256;
+    const uint32_t grid = p.tail27 ? 5u : (uint32_t)((n_reads_bound + block - 1) / block);
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL((seq_kernel<MODE_COUNT, true>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads_bound, n_reads_dev);
     return hipGetLastError();
 }
 
