@@ -497,6 +497,26 @@ int vgmi_hmm_emissions_select_wide(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used
 int vgmi_hmm_tallies_select_wide(vgmi_ctx *ctx, uint32_t bit_len, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count,
                                  const uint32_t *row_win, const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b,
                                  uint32_t n_used, uint32_t n_windows, const uint8_t *win_used, uint32_t *out, uint8_t *unique_out);
+/* ---- ... and a POLYPLOID sample over such a panel: vgmi_hmm_emissions_select_ploidy, its second launch and vgmi_hmm_tallies_ploidy with
+ * every mask over haplotype ids W words wide (word i: haplotypes 64 i .. 64 i + 63).  Ids in win_haps go up to 8 * bit_len - 2; the mask
+ * of a window's genotypes' haplotypes is derived from win_haps.  Ploidy 2 .. 8 and n_gt 1 .. 64 for the emissions, ploidy 2 .. 4 and n_gt
+ * 1 .. 128 for the tallies, where an id at or beyond 8 * bit_len - 1 or outside win_sel_mask reads (0, 0).  The part is a part like any
+ * other for _part_set_rows, _part_calls and _part_fetch; of the three fix launches it takes _part_fix_rows_ploidy_wide only
+ * (fix_mask: W words per fix), and that launch takes no other part.
+ * VGMI_E_INVALID: bit_len outside 1 .. 32, an id at or beyond 8 * bit_len - 1 in a window's list or in win_top_mask, ploidy, n_gt or a
+ * window's count out of range, a row outside the entries or the windows.  VGMI_E_STATE: entries not uploaded by entries_upload_wide or
+ * with another bit_len (so neither coverage nor alive bytes); the wrong fix launch for a part. */
+int vgmi_hmm_emissions_select_ploidy_wide(vgmi_ctx *ctx, uint32_t n_gt, uint32_t ploidy, uint32_t n_windows, const uint32_t *win_n_gt,
+                                          const uint8_t *win_haps /* n_windows x n_gt x ploidy */, const uint64_t *win_top_mask /* n_windows x W */,
+                                          uint32_t bit_len, float ave, double lower, double upper, const void *tables, uint64_t n_rows,
+                                          const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win,
+                                          const uint64_t *gt0 /* n_rows x W */, uint32_t *n_kept_out, uint8_t *flags_out, vgmi_hmm_part **out);
+int vgmi_hmm_part_fix_rows_ploidy_wide(vgmi_hmm_part *part, uint64_t n, const uint64_t *rows, const uint32_t *fix_off, const uint32_t *fix_j,
+                                       const uint64_t *fix_mask /* fix_off[n] x W */);
+int vgmi_hmm_tallies_ploidy_wide(vgmi_ctx *ctx, uint32_t bit_len, uint32_t ploidy, uint32_t n_gt, uint32_t n_windows, const uint32_t *win_n_gt,
+                                 const uint8_t *win_haps, const uint64_t *win_sel_mask /* n_windows x W */, uint64_t n_rows,
+                                 const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win, const uint32_t *winner,
+                                 int use_alive, uint32_t *out /* n_rows x ploidy x 2 */, uint8_t *unique_out);
 /* the part's emission rows back on the host (n_rows x n_gt long doubles): tests and diagnostics */
 int vgmi_hmm_part_fetch(vgmi_hmm_part *part, void *obs_out);
 void vgmi_hmm_part_free(vgmi_hmm_part *part);

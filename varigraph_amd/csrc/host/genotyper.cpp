@@ -32,6 +32,7 @@
 
 #include "../vgmi_device.h"
 #include "entry_bits.hpp"
+#include "id_masks.hpp"
 #include "fixed1.hpp"
 #include "mem_advice.hpp"
 #include "node_flanks.hpp"
@@ -987,6 +988,13 @@ bool knob_off(const char* name)
 {
     const char* e = getenv(name);
     return e && e[0] == '0';
+}
+
+// ... but for the ones that are asked for: on only if the variable starts with '1'
+bool knob_on(const char* name)
+{
+    const char* e = getenv(name);
+    return e && e[0] == '1';
 }
 
 void device_check(vgmi_ctx* dev, int rc, const char* what)
@@ -2193,7 +2201,7 @@ void Genotyper::flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, u
     }
 }
 
-void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap_id)
+void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap_id, bool wide_ids)
 {
     std::vector<uint64_t> all_rows, f_rows;
     std::vector<long double> all_obs;
@@ -2212,6 +2220,10 @@ void Genotyper::upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap
     fl.n_fixed = f_rows.size();
     if (!all_rows.empty()) device_check(dev_, vgmi_hmm_part_set_rows(part, all_rows.size(), all_rows.data(), all_obs.data()), "device HMM emissions: ");
     if (f_rows.empty()) return;
+    if (wide_ids) {      // ... over a panel of 48 to 254 haplotypes: W words of haplotype ids per fix
+        device_check(dev_, vgmi_hmm_part_fix_rows_ploidy_wide(part, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
+        return;
+    }
     if (by_hap_id) {      // a part with a genotype list per window: the masks are over haplotype ids already
         device_check(dev_, vgmi_hmm_part_fix_rows_wide(part, f_rows.size(), f_rows.data(), f_off.data(), f_j.data(), f_m.data()), "device HMM emissions: ");
         return;
@@ -2714,6 +2726,9 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
 // device's recursion takes one list length per part: the windows are dealt into parts by the length of their lists (SelectedPart), each
 // with its own emission launch, keep matrix per window and 1 / n_gt, and its own tally launch (vgmi_hmm_tallies_ploidy) over the same lists:
 // the lines of a polyploid sample are written from the device's numbers as a diploid sample's are.
+// Over a graph of 7 to 32 bytes of haplotype bits (Run::wide) the entries are on the device as bytes and every mask over haplotype ids is
+// mask_words words: a diploid sample always (4.16), a polyploid one when VGH_HMM_WIDE_PLOIDY_DEVICE=1 asks for it and its windows name at
+// most 64 haplotypes, the width of the masks over places that the sequence checks and gt0 work on (4.18; id_masks.hpp).
 struct Genotyper::SelectedSample {
     float ave = 0;
     double lower = 256.0f, upper = -0.1f;
@@ -2782,7 +2797,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     }
     ss.tab = emission_table(ss.ave, ss.ploidy);
     ss.wide = r.packed == nullptr;
-    if (ss.wide && (!r.wide || ss.blocks)) throw std::runtime_error("internal: a sample without packed entries on the selected path");
+    if (ss.wide && !r.wide) throw std::runtime_error("internal: a sample without packed entries on the selected path");
     ss.mask_words = ss.wide ? vgh::words_of((uint32_t)g_.bitlen) : 1u;
     const uint32_t bit_len = (uint32_t)g_.bitlen;
     if (!entries_uploaded_) {
@@ -2959,21 +2974,27 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
             // ... and the rows' reference-allele masks over haplotype ids
             w_n.assign(nwp, (uint32_t)n_gt);
             w_haps.resize(nwp * n_gt * ss.ploidy);
-            w_mask.resize(nwp);
-            std::vector<uint64_t> gt0_ids(n_rows, 0);
+            const size_t W = ss.mask_words;      // (packed entries: one word per window, row and fix)
+            w_mask.resize(nwp * W);
+            std::vector<uint64_t> gt0_ids(n_rows * W, 0);
             for (size_t lw = 0; lw < nwp; ++lw) {
                 const size_t wi = pt.wins[lw];
-                w_mask[lw] = ss.win_mask[wi];      // (a polyploid sample: packed entries, one word per window)
+                std::copy_n(&ss.win_mask[wi * W], W, &w_mask[lw * W]);
                 for (size_t gi = 0; gi < n_gt; ++gi)
                     for (uint32_t q = 0; q < ss.ploidy; ++q) w_haps[(lw * n_gt + gi) * ss.ploidy + q] = (uint8_t)ss.win_gts[wi][gi][q];
                 const std::vector<uint16_t>& used = ss.win_used[wi];
-                for (size_t rr = win_row0[lw]; rr < win_row0[lw + 1]; ++rr)
-                    for (size_t p = 0; p < used.size(); ++p) gt0_ids[rr] |= ((pt.gt0[rr] >> p) & 1ull) << used[p];
+                for (size_t rr = win_row0[lw]; rr < win_row0[lw + 1]; ++rr) vgh::places_to_ids(pt.gt0[rr], used.data(), used.size(), &gt0_ids[rr * W]);
             }
-            device_check(dev_, vgmi_hmm_emissions_select_ploidy(dev_, (uint32_t)n_gt, ss.ploidy, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(),
-                                                                (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(), pt.e_count.data(),
-                                                                pt.row_win.data(), gt0_ids.data(), n_kept.data(), flags.data(), &ph.p),
-                         "device HMM emissions: ");
+            if (ss.wide)
+                device_check(dev_, vgmi_hmm_emissions_select_ploidy_wide(dev_, (uint32_t)n_gt, ss.ploidy, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(),
+                                                                         (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
+                                                                         pt.e_count.data(), pt.row_win.data(), gt0_ids.data(), n_kept.data(), flags.data(), &ph.p),
+                             "device HMM emissions: ");
+            else
+                device_check(dev_, vgmi_hmm_emissions_select_ploidy(dev_, (uint32_t)n_gt, ss.ploidy, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(),
+                                                                    (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(), pt.e_count.data(),
+                                                                    pt.row_win.data(), gt0_ids.data(), n_kept.data(), flags.data(), &ph.p),
+                             "device HMM emissions: ");
         } else {
             const std::vector<uint16_t> gt0_16(pt.gt0.begin(), pt.gt0.end());      // (<= 16 places)
             if (ss.wide)      // (a diploid sample has one part: its windows are the run's, in order, and so are the masks)
@@ -3015,16 +3036,17 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
                     ++pruned_nodes;
                 }
                 if (!(flags[rr] & 1u)) continue;
-                const size_t before = fl.fix_j[lw].size();
+                const size_t before = fl.fix_j[lw].size(), before_m = fl.fix_mask[lw].size();
                 flagged_row(fl, lw, rr, chr, row_node[rr], haps, pt.gt0[rr], r, sc, n_kept[rr]);
                 // (sequence_fixes counts along the list and over the places of `used`; the device along the row's range -- and, with a list
-                // per window, over haplotype ids)
-                for (size_t q = before; q < fl.fix_j[lw].size(); ++q) {
-                    fl.fix_j[lw][q] = node.kmers[fl.fix_j[lw][q]] - (uint32_t)pt.e_begin[rr];
-                    if (!ss.blocks) continue;
-                    uint64_t ids = 0;
-                    for (size_t p = 0; p < haps.used.size(); ++p) ids |= ((fl.fix_mask[lw][q] >> p) & 1ull) << haps.used[p];
-                    fl.fix_mask[lw][q] = ids;
+                // per window, over haplotype ids: mask_words words per fix)
+                for (size_t q = before; q < fl.fix_j[lw].size(); ++q) fl.fix_j[lw][q] = node.kmers[fl.fix_j[lw][q]] - (uint32_t)pt.e_begin[rr];
+                if (ss.blocks) {
+                    const size_t W = ss.mask_words;
+                    const std::vector<uint64_t> places(fl.fix_mask[lw].begin() + (ptrdiff_t)before_m, fl.fix_mask[lw].end());
+                    fl.fix_mask[lw].resize(before_m);
+                    fl.fix_mask[lw].resize(before_m + places.size() * W, 0);
+                    for (size_t q = 0; q < places.size(); ++q) vgh::places_to_ids(places[q], haps.used.data(), haps.used.size(), &fl.fix_mask[lw][before_m + q * W]);
                 }
             }
         });
@@ -3032,7 +3054,7 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
         if (pruned_nodes.load()) lists_whole_.store(false, std::memory_order_relaxed);
         alive_stale_.store(false);      // (hidden_states above walked lists that were pruned already: nothing left them)
         t_a = s.since_begin();
-        upload_flagged(fl, ph.p, ss.blocks);
+        upload_flagged(fl, ph.p, ss.blocks, ss.blocks && ss.wide);
         ss.n_host_rows += fl.n_host;
         ss.n_fixed_rows += fl.n_fixed;
         t_rows = s.since_begin();
@@ -3088,9 +3110,15 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
     if (device_tallies && n_steps && ss.blocks && device_tally_ploidy(ss.ploidy)) {
         tally.resize(2 * (size_t)ss.ploidy * n_rows);
         tally_uniq.resize(n_rows);
-        device_check(dev_, vgmi_hmm_tallies_ploidy(dev_, ss.ploidy, (uint32_t)n_gt, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(), n_rows, pt.e_begin.data(),
-                                                   pt.e_count.data(), pt.row_win.data(), winner.data(), 1, tally.data(), tally_uniq.data()),
-                     "device tallies: ");
+        if (ss.wide)
+            device_check(dev_, vgmi_hmm_tallies_ploidy_wide(dev_, (uint32_t)g_.bitlen, ss.ploidy, (uint32_t)n_gt, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(),
+                                                            n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(), 1, tally.data(),
+                                                            tally_uniq.data()),
+                         "device tallies: ");
+        else
+            device_check(dev_, vgmi_hmm_tallies_ploidy(dev_, ss.ploidy, (uint32_t)n_gt, (uint32_t)nwp, w_n.data(), w_haps.data(), w_mask.data(), n_rows, pt.e_begin.data(),
+                                                       pt.e_count.data(), pt.row_win.data(), winner.data(), 1, tally.data(), tally_uniq.data()),
+                         "device tallies: ");
         ss.n_ploidy_tally_rows += n_rows;
     }
     if (device_tallies && n_steps && !ss.blocks) {
@@ -3151,7 +3179,9 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
     r.cfg = &cfg;
     r.haploid_num = std::min(cfg.haploid_num, n_hap_);
     if (g_.bitlen <= 6) fill_packed(r, cfg.threads);
-    else r.wide = g_.bitlen <= 32 && cfg.sample_ploidy == 2 && !knob_off("VGH_HMM_WIDE_DEVICE");
+    else      // (a polyploid sample over such a graph only when asked: VGH_HMM_WIDE_PLOIDY_DEVICE=1, DESIGN_INGEST_HMM.md 4.18)
+        r.wide = g_.bitlen <= 32 && !knob_off("VGH_HMM_WIDE_DEVICE") &&
+                 (cfg.sample_ploidy == 2 || (knob_on("VGH_HMM_WIDE_PLOIDY_DEVICE") && vgh::wide_ploidy_sample(g_.bitlen, cfg.sample_ploidy, r.haploid_num)));
     reset_calls();
 
     RunShared s(r);

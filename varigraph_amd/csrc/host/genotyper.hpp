@@ -188,7 +188,7 @@ private:
     void flagged_row(FlaggedRows& fl, size_t wi, size_t rr, Chrom& chr, uint32_t node_i, const WindowHaps& h, uint64_t gt0, const Run& r,
                      FlaggedScratch& sc, uint32_t& n_kept);
     // by_hap_id: the part has a genotype list per window and fl's masks are over haplotype ids (vgmi_hmm_part_fix_rows_wide)
-    void upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap_id = false);
+    void upload_flagged(FlaggedRows& fl, vgmi_hmm_part* part, bool by_hap_id = false, bool wide_ids = false);
     // a node the HMM works on, in window order; at: where its scores are (a place in the window or a row of the part), -1: it has none
     struct Seen { uint32_t start, end; int64_t at; };
     struct StepArrays;

@@ -18,6 +18,10 @@ struct vgmi_hmm_part {
     // a part of vgmi_hmm_emissions_select_wide (W words of haplotype bits per entry; 0: none of the above): its launch, for vgmi_hmm_part_fix_rows
     uint32_t wide_words = 0;
     HmmEmitWideParams emit_wide{};
+    // a part of vgmi_hmm_emissions_select_ploidy_wide (a genotype list per window AND W words per entry; 0: none of the above): its launch, for
+    // vgmi_hmm_part_fix_rows_ploidy_wide
+    uint32_t win_wide_words = 0;
+    HmmEmitWinWideParams emit_win_wide{};
 };
 
 namespace {
@@ -127,6 +131,36 @@ private:
     size_t bytes_ = 0;
     hipStream_t st_ = nullptr;
     hipError_t e_ = hipSuccess;
+};
+
+// VGMI_HMM_TIMING=1 for a staged call: upload / kernel / download, milliseconds on stderr (diagnostics)
+struct HmmCallTimes {
+    bool on;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit HmmCallTimes(bool wanted = true) : on(wanted && getenv("VGMI_HMM_TIMING") != nullptr)
+    {
+        if (on)
+            for (auto& x : ev) (void)hipEventCreate(&x);
+    }
+    ~HmmCallTimes()
+    {
+        if (on)
+            for (auto& x : ev) (void)hipEventDestroy(x);
+    }
+    void mark(int i, hipStream_t st) { if (on) (void)hipEventRecord(ev[i], st); }
+    void report(HmmCall& call, const char* what, uint64_t n_rows, uint32_t bit_len)
+    {
+        if (!on) return;
+        call.sync();
+        float up = 0, kern = 0, down = 0;
+        if (call.ok()) {
+            (void)hipEventElapsedTime(&up, ev[0], ev[1]);
+            (void)hipEventElapsedTime(&kern, ev[1], ev[2]);
+            (void)hipEventElapsedTime(&down, ev[2], ev[3]);
+        }
+        fprintf(stderr, "[vgmi] HMM %s call, %u bytes of haplotype bits: %llu rows, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", what, bit_len,
+                (unsigned long long)n_rows, up, kern, down);
+    }
 };
 
 // ---- input checks (`who` names the call in the message) ----
@@ -472,6 +506,15 @@ hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t*
 
 hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t* rows, const uint32_t* off, const uint32_t* j, const uint64_t* mask, hipStream_t st)
 {
+    if (part.win_wide_words) {      // (W words of haplotype ids per fix; the entries' bits are W words)
+        HmmEmitWinWideParams Q = part.emit_win_wide;
+        Q.e.n_items = n;
+        Q.e.fix_rows = rows;
+        Q.e.fix_off = off;
+        Q.e.fix_j = j;
+        Q.e.fix_mask = reinterpret_cast<const unsigned long long*>(mask);
+        return launch_hmm_emissions_win_wide(Q, part.win_wide_words, st);
+    }
     HmmEmitWinParams P = part.emit_win;
     P.n_items = n;
     P.fix_rows = rows;
@@ -481,8 +524,9 @@ hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t*
     return launch_hmm_emissions_win(P, st);
 }
 
+// mask_words: how many Masks a fix holds (W for a part of vgmi_hmm_emissions_select_ploidy_wide, else one)
 template <class Mask>
-int hmm_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const uint32_t* fix_off, const uint32_t* fix_j, const Mask* fix_mask)
+int hmm_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const uint32_t* fix_off, const uint32_t* fix_j, const Mask* fix_mask, uint32_t mask_words = 1)
 {
     vgmi_ctx* c = part->c;
     const uint32_t n_fix = fix_off[n];
@@ -494,16 +538,22 @@ int hmm_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const ui
                 return fail(c, VGMI_E_INVALID, "HMM emissions: a row's fixes must name its entries in ascending order");
     }
     HmmCall call(c);
-    const size_t o_rows = call.add(n * 8), o_off = call.add((n + 1) * 4), o_j = call.add((size_t)n_fix * 4), o_m = call.add((size_t)n_fix * sizeof(Mask));
+    const size_t o_rows = call.add(n * 8), o_off = call.add((n + 1) * 4), o_j = call.add((size_t)n_fix * 4), o_m = call.add((size_t)n_fix * mask_words * sizeof(Mask));
     if (int rc = call.begin("HMM emissions")) return rc;
+    HmmCallTimes tm(part->win_wide_words != 0);      // (the diagnostics of the calls that have them)
+    tm.mark(0, call.stream());
     call.upload(o_rows, rows, n * 8);
     call.upload(o_off, fix_off, (n + 1) * 4);
     call.upload(o_j, fix_j, (size_t)n_fix * 4);
-    call.upload(o_m, fix_mask, (size_t)n_fix * sizeof(Mask));
+    call.upload(o_m, fix_mask, (size_t)n_fix * mask_words * sizeof(Mask));
+    tm.mark(1, call.stream());
     call.run([&] {
         return hmm_launch_fix(*part, n, call.at<const uint64_t>(o_rows), call.at<const uint32_t>(o_off), call.at<const uint32_t>(o_j), call.at<const Mask>(o_m),
                               call.stream());
     });
+    tm.mark(2, call.stream());
+    tm.mark(3, call.stream());
+    tm.report(call, "emission fix", n, part->emit_win_wide.e.bl8 / 8);
     HIPCHK(c, call.finish());
     return VGMI_OK;
 }
@@ -529,35 +579,6 @@ int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len)
     return VGMI_OK;
 }
 
-// VGMI_HMM_TIMING=1 for a staged call: upload / kernel / download, milliseconds on stderr (diagnostics)
-struct HmmCallTimes {
-    bool on = getenv("VGMI_HMM_TIMING") != nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    HmmCallTimes()
-    {
-        if (on)
-            for (auto& x : ev) (void)hipEventCreate(&x);
-    }
-    ~HmmCallTimes()
-    {
-        if (on)
-            for (auto& x : ev) (void)hipEventDestroy(x);
-    }
-    void mark(int i, hipStream_t st) { if (on) (void)hipEventRecord(ev[i], st); }
-    void report(HmmCall& call, const char* what, uint64_t n_rows, uint32_t bit_len)
-    {
-        if (!on) return;
-        call.sync();
-        float up = 0, kern = 0, down = 0;
-        if (call.ok()) {
-            (void)hipEventElapsedTime(&up, ev[0], ev[1]);
-            (void)hipEventElapsedTime(&kern, ev[1], ev[2]);
-            (void)hipEventElapsedTime(&down, ev[2], ev[3]);
-        }
-        fprintf(stderr, "[vgmi] HMM %s call, %u bytes of haplotype bits: %llu rows, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", what, bit_len,
-                (unsigned long long)n_rows, up, kern, down);
-    }
-};
 }  // namespace
 
 extern "C" {
@@ -697,6 +718,7 @@ int vgmi_hmm_part_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows
 {
     if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
     if (n == 0) return VGMI_OK;
+    if (part->win_wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part's fixes are W-word masks over haplotype ids (vgmi_hmm_part_fix_rows_ploidy_wide)");
     if (part->per_window_lists) return fail(part->c, VGMI_E_INVALID, "HMM emissions: this part's fixes are masks over haplotype ids (vgmi_hmm_part_fix_rows_wide)");
     return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask);
 }
@@ -776,6 +798,7 @@ int vgmi_hmm_part_fix_rows_wide(vgmi_hmm_part* part, uint64_t n, const uint64_t*
 {
     if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
     if (n == 0) return VGMI_OK;
+    if (part->win_wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part's fixes are W-word masks over haplotype ids (vgmi_hmm_part_fix_rows_ploidy_wide)");
     if (!part->per_window_lists) return fail(part->c, VGMI_E_INVALID, "HMM emissions: this part's fixes are masks over the `used` list (vgmi_hmm_part_fix_rows)");
     return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask);
 }
@@ -1275,6 +1298,139 @@ int vgmi_hmm_tallies_select_wide(vgmi_ctx* c, uint32_t bit_len, uint64_t n_rows,
     call.download(unique_out, o_uni, n_rows);
     tm.mark(3, call.stream());
     tm.report(call, "tally", n_rows, bit_len);
+    HIPCHK(c, call.finish());
+    return VGMI_OK;
+}
+
+// ---- a POLYPLOID sample over such a panel (vgmi.h): vgmi_hmm_emissions_select_ploidy and vgmi_hmm_tallies_ploidy with every mask over
+// haplotype ids W words wide
+int vgmi_hmm_emissions_select_ploidy_wide(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_windows, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                          const uint64_t* win_top_mask, uint32_t bit_len, float ave, double lower, double upper, const void* tables,
+                                          uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint64_t* gt0,
+                                          uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    if (!c || !tables || !out) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 8) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..64 genotypes of 2..8 haplotypes per window");
+    if (n_windows < 1 || !win_n_gt || !win_haps || !win_top_mask) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their genotype lists");
+    if (n_rows && (!entry_begin || !entry_count || !row_win || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
+    if (int rc = hmm_check_wide(c, "HMM emissions", bit_len)) return rc;
+    const uint32_t W = c->hmm_words, n_ids = 8 * bit_len - 1;      // the last bit is no haplotype
+    std::vector<uint64_t> used_mask((size_t)n_windows * W, 0);
+    for (uint32_t w = 0; w < n_windows; ++w) {
+        if (win_n_gt[w] < 1 || win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM emissions: a window's genotype count outside 1..n_gt");
+        for (size_t i = 0; i < (size_t)win_n_gt[w] * ploidy; ++i) {
+            const uint32_t hap = win_haps[(size_t)w * n_gt * ploidy + i];
+            if (hap >= n_ids) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype's haplotype outside the haplotype bits");
+            used_mask[(size_t)w * W + (hap >> 6)] |= 1ull << (hap & 63u);
+        }
+        for (uint32_t i = 0; i < W; ++i) {
+            const uint64_t hap_bits = n_ids >= 64u * (i + 1u) ? ~0ull : n_ids <= 64u * i ? 0ull : (1ull << (n_ids - 64u * i)) - 1ull;
+            if (win_top_mask[(size_t)w * W + i] & ~hap_bits) return fail(c, VGMI_E_INVALID, "HMM emissions: a drawn haplotype outside the haplotype bits");
+        }
+    }
+    if (int rc = hmm_check_rows(c, "HMM emissions", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    *out = nullptr;
+    HmmEmitCall ec(c, n_rows, (size_t)8 * W, ploidy);
+    HmmCall& call = ec.call;
+    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_mask = (size_t)n_windows * 8 * W;      // row_win | win_n_gt | win_haps | win_top_mask | win_used_mask
+    const size_t o_rw = call.add(n_rows * 4), o_wn = call.add((size_t)n_windows * 4), o_wh = call.add(b_haps), o_wm = call.add(b_mask), o_wu = call.add(b_mask);
+    if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
+    HmmCallTimes tm;
+    tm.mark(0, call.stream());
+    call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_wn, win_n_gt, (size_t)n_windows * 4);
+    call.upload(o_wh, win_haps, b_haps);
+    call.upload(o_wm, win_top_mask, b_mask);
+    call.upload(o_wu, used_mask.data(), b_mask);
+    HmmEmitWinWideParams Q{};
+    HmmEmitWinParams& P = Q.e;
+    Q.f = c->d_hmm_f;
+    Q.bits = c->d_hmm_bits;
+    P.cov = c->d_hmm_cov;
+    P.alive = c->d_hmm_alive;
+    P.entry_begin = call.at<const uint64_t>(ec.o_eb);
+    P.entry_count = call.at<const uint32_t>(ec.o_ec);
+    P.row_win = call.at<const uint32_t>(o_rw);
+    P.gt0 = call.at<const unsigned long long>(ec.o_g0);
+    P.n_gt = n_gt;
+    P.ploidy = ploidy;
+    P.bl8 = 8 * bit_len;
+    P.ave = ave;
+    P.lower = lower;
+    P.upper = upper;
+    P.tables = call.at(ec.o_tab);
+    P.win_n_gt = call.at<const uint32_t>(o_wn);
+    P.win_haps = call.at(o_wh);
+    P.win_top_mask = call.at<const unsigned long long>(o_wm);
+    P.win_used_mask = call.at<const unsigned long long>(o_wu);
+    P.obs = ec.part->d_obs;
+    P.n_kept = call.at<uint32_t>(ec.o_nk);
+    P.flags = call.at(ec.o_fl);
+    P.n_items = n_rows;
+    tm.mark(1, call.stream());
+    call.run([&] { return launch_hmm_emissions_win_wide(Q, W, call.stream()); });
+    tm.mark(2, call.stream());
+    ec.part->win_wide_words = W;
+    ec.part->emit_win_wide = Q;
+    if (tm.on) {      // (finish() fetches them again: the figure is the diagnostics')
+        call.download(n_kept_out, ec.o_nk, n_rows * 4);
+        call.download(flags_out, ec.o_fl, n_rows);
+        tm.mark(3, call.stream());
+        tm.report(call, "emission (a genotype list per window)", n_rows, bit_len);
+    }
+    return ec.finish(entry_count, n_kept_out, flags_out, out);
+}
+
+// the second launch of such a part: fix_mask holds W words of haplotype ids per fix
+int vgmi_hmm_part_fix_rows_ploidy_wide(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const uint32_t* fix_off, const uint32_t* fix_j, const uint64_t* fix_mask)
+{
+    if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
+    if (!part->win_wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part is none of vgmi_hmm_emissions_select_ploidy_wide");
+    if (n == 0) return VGMI_OK;
+    return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask, part->win_wide_words);
+}
+
+int vgmi_hmm_tallies_ploidy_wide(vgmi_ctx* c, uint32_t bit_len, uint32_t ploidy, uint32_t n_gt, uint32_t n_windows, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                 const uint64_t* win_sel_mask, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                                 const uint32_t* winner, int use_alive, uint32_t* out, uint8_t* unique_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !winner || !out || !unique_out)) || !win_haps || !win_sel_mask) return VGMI_E_INVALID;
+    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || n_gt > 128 || n_windows < 1)
+        return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes of 2..4 haplotypes in at least one window");
+    if (int rc = hmm_check_wide(c, "HMM tallies", bit_len)) return rc;
+    if (win_n_gt)
+        for (uint32_t w = 0; w < n_windows; ++w)
+            if (win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM tallies: a window with more genotypes than the lists are wide");
+    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_rows == 0) return VGMI_OK;
+    const uint32_t W = c->hmm_words;
+    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_out = n_rows * 8 * ploidy, b_mask = (size_t)n_windows * 8 * W;
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(row_win ? n_rows * 4 : 0), o_win = call.add(n_rows * 4),
+                 o_out = call.add(b_out), o_uni = call.add(n_rows), o_ng = call.add(win_n_gt ? (size_t)n_windows * 4 : 0), o_haps = call.add(b_haps),
+                 o_mask = call.add(b_mask);
+    if (int rc = call.begin("HMM tallies")) return rc;
+    HmmCallTimes tm;
+    tm.mark(0, call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    if (row_win) call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_win, winner, n_rows * 4);
+    if (win_n_gt) call.upload(o_ng, win_n_gt, (size_t)n_windows * 4);
+    call.upload(o_haps, win_haps, b_haps);
+    call.upload(o_mask, win_sel_mask, b_mask);
+    tm.mark(1, call.stream());
+    call.run([&] {
+        return launch_hmm_tally_ploidy_wide(W, c->d_hmm_f, c->d_hmm_bits, c->d_hmm_cov, use_alive ? c->d_hmm_alive : nullptr, call.at<const uint64_t>(o_beg),
+                                            call.at<const uint32_t>(o_cnt), row_win ? call.at<const uint32_t>(o_rw) : nullptr, call.at<const uint32_t>(o_win),
+                                            win_n_gt ? call.at<const uint32_t>(o_ng) : nullptr, call.at(o_haps), call.at<const unsigned long long>(o_mask), n_gt,
+                                            ploidy, 8 * bit_len, n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
+    });
+    tm.mark(2, call.stream());
+    call.download(out, o_out, b_out);
+    call.download(unique_out, o_uni, n_rows);
+    tm.mark(3, call.stream());
+    tm.report(call, "tally (polyploid)", n_rows, bit_len);
     HIPCHK(c, call.finish());
     return VGMI_OK;
 }

@@ -936,7 +936,7 @@ __global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long lo
 // ---- panels of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry's haplotype bits are W = 1, 2 or 4 words ----------------------------
 // The packed word above holds six bytes of haplotype bits.  Here an entry is its multiplicity byte f[e] and its bit vector as it stands
 // in the graph, little-endian in W 64-bit words, zero-padded, entry-major: bits[e * W + i] -- one contiguous 8, 16 or 32-byte load.
-// The last bit of the vector (bit bl8 - 1) is the flag it is everywhere, never a haplotype.  The three kernels keep the layouts of their
+// The last bit of the vector (bit bl8 - 1) is the flag it is everywhere, never a haplotype.  The kernels keep the layouts of their
 // namesakes: row, window and every haplotype id are wavefront-uniform where they were, so the words of an entry, the window's mask and
 // the choice of the word that holds a haplotype stay on the scalar side.  A register array of W words is only ever indexed by an
 // unrolled loop's counter; the word of haplotype `hap` is picked by a chain over W (hmm_pick_word) or loaded on its own (the tallies).
@@ -1102,6 +1102,211 @@ __global__ __launch_bounds__(256) void hmm_tally_wide_kernel(const uint8_t* __re
     out[4 * r + 2] = num_b;
     out[4 * r + 3] = sum_b;
     uniq[r] = (uint8_t)u;
+}
+
+// hmm_emissions_win_kernel<MAXP> for a polyploid sample over such a panel: a wavefront per row, a lane per genotype of the row's window,
+// four wavefronts and kWinRows rows per workgroup, the term tables staged once.  Every mask over haplotype ids -- the drawn haplotypes, the
+// blocks' haplotypes, the row's reference-allele bits, a fix -- is W words, and so is `om`, the haplotypes that count as carrying an entry:
+// all of them wavefront-uniform.  Only a lane's ids differ, so the lane picks the word of each id out of `om` by hmm_pick_word's masks
+// (an indexed read of `om` is what becomes scratch) and sums the bits, a repeated id every time it stands.
+template <uint32_t MAXP, uint32_t W>
+__global__ __launch_bounds__(256) void hmm_emissions_win_wide_kernel(HmmEmitWinWideParams Q)
+{
+    __shared__ uint64_t s_tm[(MAXP + 1u) * 256u];
+    __shared__ int32_t s_te[(MAXP + 1u) * 256u];
+    const HmmEmitWinParams& P = Q.e;
+    hmm_stage_tables<256>(P.tables, P.ploidy, s_tm, s_te);      // (its barrier is the only one: from here on the wavefronts go their own ways)
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = threadIdx.x & 63u;
+    const uint32_t lb_word = (P.bl8 - 1u) >> 6, lb_bit = (P.bl8 - 1u) & 63u;
+    for (uint32_t k = wave; k < kWinRows; k += 4u) {
+        const uint64_t item = (uint64_t)blockIdx.x * kWinRows + k;
+        if (item >= P.n_items) break;
+        const uint64_t rowi = P.fix_rows ? P.fix_rows[item] : item;
+        uint32_t fp = P.fix_rows ? P.fix_off[item] : 0u;
+        const uint32_t fe = P.fix_rows ? P.fix_off[item + 1] : 0u;
+        const uint64_t e0 = P.entry_begin[rowi];
+        const uint32_t cnt = P.entry_count[rowi];
+        const uint32_t w = P.row_win[rowi];
+        unsigned long long gt0[W], top_mask[W], used_mask[W];
+#pragma unroll
+        for (uint32_t i = 0; i < W; ++i) {
+            gt0[i] = P.gt0[rowi * W + i];
+            top_mask[i] = P.win_top_mask[(size_t)w * W + i];
+            used_mask[i] = P.win_used_mask[(size_t)w * W + i];
+        }
+        const uint32_t n_here = P.win_n_gt[w];
+        const bool active = g < n_here;
+        uint32_t hap_word[MAXP] = {0}, hap_bit[MAXP] = {0};
+        if (active) {
+#pragma unroll
+            for (uint32_t q = 0; q < MAXP; ++q)      // (unrolled with the places beyond `ploidy` left out: the arrays stay in registers)
+                if (q < P.ploidy) {
+                    const uint32_t hap = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
+                    hap_word[q] = W > 1u ? hap >> 6 : 0u;
+                    hap_bit[q] = hap & 63u;
+                }
+        }
+        VgN80 prod;
+        prod.m = 1ULL << 63;      // 1.0L
+        prod.e = VG_X80_BIAS;
+        uint32_t kept = 0, flag = 0;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint64_t e = e0 + j;
+            if (P.alive[e] == 0) continue;      // pruned by an earlier window's or sample's selection
+            unsigned long long b[W], met = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < W; ++i) {
+                b[i] = Q.bits[e * W + i];
+                met |= b[i] & top_mask[i];
+            }
+            const uint32_t c = P.cov[e], f = Q.f[e];
+            if (met == 0) {
+                if (g == 0 && !P.fix_rows) P.alive[e] = 0;      // the prune: by the DRAWN haplotypes
+                continue;
+            }
+            ++kept;
+            const uint32_t lb = (uint32_t)(hmm_pick_word<W>(b, lb_word) >> lb_bit) & 1u;
+            const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
+            unsigned long long om[W], any = 0;      // the score: over the BLOCKS' haplotypes
+#pragma unroll
+            for (uint32_t i = 0; i < W; ++i) {
+                om[i] = (b[i] | (in_interval ? gt0[i] : 0ull)) & used_mask[i];
+                any |= om[i];
+            }
+            if ((double)c < P.lower && f >= 2u && any != 0) flag |= 1u;
+            if (fp < fe && P.fix_j[fp] == j) {      // (the second launch: haplotypes whose sequence does not hold this k-mer do not carry it)
+#pragma unroll
+                for (uint32_t i = 0; i < W; ++i) om[i] &= ~P.fix_mask[(size_t)fp * W + i];
+                ++fp;
+            }
+            if (!active) continue;
+            const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
+            uint32_t h = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < MAXP; ++q)      // (a repeated id counts at every place it stands)
+                if (q < P.ploidy) h += (uint32_t)(hmm_pick_word<W>(om, hap_word[q]) >> hap_bit[q]) & 1u;
+            const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
+            const uint32_t ti = h * 256u + cc;
+            VgN80 t;
+            t.m = s_tm[ti];
+            t.e = s_te[ti];
+            prod = n80_mul(prod, t);
+        }
+        if (active) x80_store(P.obs + (rowi * P.n_gt + g) * 16, n80_to(prod));
+        else if (g < P.n_gt) *reinterpret_cast<uint4*>(P.obs + (rowi * P.n_gt + g) * 16) = make_uint4(0, 0, 0, 0);
+        if (g == 0 && !P.fix_rows) {
+            P.n_kept[rowi] = kept;
+            P.flags[rowi] = (uint8_t)flag;
+        }
+    }
+}
+
+// hmm_tally_ploidy_kernel over such a panel: a wavefront per row, a lane per entry, 64 entries a turn; a place counts if its id is a
+// haplotype (below bl8 - 1) that the window's W-word mask holds, and every lane loads the one word of its entry that holds the id
+template <uint32_t W>
+__global__ __launch_bounds__(256) void hmm_tally_ploidy_wide_kernel(const uint8_t* __restrict__ f, const unsigned long long* __restrict__ bits,
+                                                                    const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
+                                                                    const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
+                                                                    const uint32_t* __restrict__ row_win, const uint32_t* __restrict__ winner,
+                                                                    const uint32_t* __restrict__ win_n_gt, const uint8_t* __restrict__ win_haps,
+                                                                    const unsigned long long* __restrict__ win_sel_mask, uint32_t n_gt, uint32_t ploidy,
+                                                                    uint32_t bl8, uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
+{
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    for (uint32_t k = wave; k < kTallyRows; k += 4u) {
+        const uint64_t r = (uint64_t)blockIdx.x * kTallyRows + k;
+        if (r >= n_rows) break;
+        const uint32_t w = row_win ? row_win[r] : 0u;
+        const uint32_t g = winner[r];
+        uint32_t num[4] = {0, 0, 0, 0}, sum[4] = {0, 0, 0, 0}, u = 0;
+        if (g < (win_n_gt ? win_n_gt[w] : n_gt)) {
+            uint32_t id_word[4] = {0, 0, 0, 0}, id_bit[4] = {0, 0, 0, 0};
+            bool ok[4] = {false, false, false, false};
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)      // (unrolled with the places beyond `ploidy` left out: the arrays stay in registers)
+                if (q < ploidy) {
+                    const uint32_t h = win_haps[((size_t)w * n_gt + g) * ploidy + q];
+                    const bool is_hap = h < bl8 - 1u;      // (then h >> 6 < W)
+                    const uint32_t hw = is_hap && W > 1u ? h >> 6 : 0u;
+                    ok[q] = is_hap && ((win_sel_mask[(size_t)w * W + hw] >> (h & 63u)) & 1ull);
+                    id_word[q] = ok[q] ? hw : 0u;
+                    id_bit[q] = ok[q] ? h & 63u : 0u;
+                }
+            const uint64_t e0 = entry_begin[r];
+            const uint32_t cnt = entry_count[r];
+            for (uint32_t base = 0; base < cnt; base += 64u) {      // (every lane takes every turn: the ballots are the wavefront's)
+                const uint32_t j = base + lane;
+                const uint64_t e = e0 + j;
+                const bool in = j < cnt && (!alive || alive[e] != 0);
+                const uint32_t c = in ? cov[e] : 0u;
+                const uint32_t fm = in ? f[e] : 2u;
+                u += (uint32_t)__popcll(__ballot(fm <= 1u));
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) {
+                    const unsigned long long word = in && ok[q] ? bits[e * W + id_word[q]] : 0ull;
+                    const bool hit = (word >> id_bit[q]) & 1ull;
+                    num[q] += (uint32_t)__popcll(__ballot(hit));
+                    sum[q] += hit ? c : 0u;
+                }
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)
+                for (uint32_t d = 32; d; d >>= 1) sum[q] += (uint32_t)__shfl_xor((int)sum[q], (int)d);
+            if (u > 255u) u = 255u;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)
+                if (q < ploidy) {
+                    out[(r * ploidy + q) * 2] = num[q];
+                    out[(r * ploidy + q) * 2 + 1] = sum[q];
+                }
+            uniq[r] = (uint8_t)u;
+        }
+    }
+}
+
+namespace {
+template <uint32_t W>
+hipError_t launch_emissions_win_wide_as(const HmmEmitWinWideParams& Q, hipStream_t st)
+{
+    const dim3 grid((uint32_t)((Q.e.n_items + kWinRows - 1) / kWinRows));
+    if (Q.e.ploidy > 4) hipLaunchKernelGGL((hmm_emissions_win_wide_kernel<8, W>), grid, dim3(256), 0, st, Q);
+    else hipLaunchKernelGGL((hmm_emissions_win_wide_kernel<4, W>), grid, dim3(256), 0, st, Q);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_hmm_emissions_win_wide(const HmmEmitWinWideParams& Q, uint32_t W, hipStream_t st)
+{
+    const HmmEmitWinParams& P = Q.e;
+    if (P.n_items == 0) return hipSuccess;
+    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 8 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask ||
+        !P.gt0 || !Q.f || !Q.bits || P.bl8 < 8 || P.bl8 > 64u * W)
+        return hipErrorInvalidValue;
+    switch (W) {
+        case 1: return launch_emissions_win_wide_as<1>(Q, st);
+        case 2: return launch_emissions_win_wide_as<2>(Q, st);
+        case 4: return launch_emissions_win_wide_as<4>(Q, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_hmm_tally_ploidy_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
+                                        const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
+                                        const uint32_t* win_n_gt, const uint8_t* win_haps, const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy,
+                                        uint32_t bl8, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
+{
+    if (n_rows == 0) return hipSuccess;
+    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || !win_haps || !win_sel_mask || !f || !bits || bl8 < 8 || bl8 > 64u * W) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((n_rows + kTallyRows - 1) / kTallyRows));
+    switch (W) {
+        case 1: hipLaunchKernelGGL(hmm_tally_ploidy_wide_kernel<1>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, bl8, n_rows, out, uniq); break;
+        case 2: hipLaunchKernelGGL(hmm_tally_ploidy_wide_kernel<2>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, bl8, n_rows, out, uniq); break;
+        case 4: hipLaunchKernelGGL(hmm_tally_ploidy_wide_kernel<4>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, bl8, n_rows, out, uniq); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_hmm_support_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,

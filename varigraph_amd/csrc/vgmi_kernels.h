@@ -370,6 +370,20 @@ hipError_t launch_hmm_support_wide(uint32_t W, const uint8_t* f, const unsigned 
 hipError_t launch_hmm_tally_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
                                  const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
                                  const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
+// Emissions, a polyploid sample with a genotype list per window over such a panel: `e` as vgmi_hmm_emissions_select_ploidy fills it, except
+// that `packed` is not read and every mask over haplotype ids is W words: gt0 per row, win_top_mask and win_used_mask per window, fix_mask
+// per fix; win_haps ids go up to bl8 - 2
+struct HmmEmitWinWideParams {
+    HmmEmitWinParams e;
+    const uint8_t* f;
+    const unsigned long long* bits;
+};
+hipError_t launch_hmm_emissions_win_wide(const HmmEmitWinWideParams& Q, uint32_t W, hipStream_t st);
+// launch_hmm_tally_ploidy over such a panel: win_sel_mask holds W words per window, an id at or beyond bl8 - 1 reads (0, 0)
+hipError_t launch_hmm_tally_ploidy_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
+                                        const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
+                                        const uint32_t* win_n_gt, const uint8_t* win_haps, const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy,
+                                        uint32_t bl8, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
 hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uint8_t* src, uint32_t n_gt, uint64_t n, hipStream_t st);
 size_t hmm_lds_bytes(uint32_t n_gt, uint32_t ploidy);
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,

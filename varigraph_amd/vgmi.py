@@ -110,6 +110,10 @@ def load_library():
         "vgmi_hmm_emissions_select_wide": (i32, [vp, u32, u32, vp, vp, u32, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
                                                  vp, vp, C.POINTER(vp)]),
         "vgmi_hmm_tallies_select_wide": (i32, [vp, u32, C.c_uint64, vp, vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+        "vgmi_hmm_emissions_select_ploidy_wide": (i32, [vp, u32, u32, u32, vp, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
+                                                        vp, vp, C.POINTER(vp)]),
+        "vgmi_hmm_part_fix_rows_ploidy_wide": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
+        "vgmi_hmm_tallies_ploidy_wide": (i32, [vp, u32, u32, u32, u32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_int, vp, vp]),
         "vgmi_hmm_part_set_rows": (i32, [vp, C.c_uint64, vp, vp]),
         "vgmi_hmm_part_fix_rows": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
         "vgmi_hmm_plan_create": (i32, [vp, u32, u32, vp, u32, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, u32, vp, vp, vp, vp, C.POINTER(vp)]),
@@ -824,6 +828,61 @@ class Context:
         uniq = np.full(max(n_rows, 1), 0xEE, dtype=np.uint8)
         self._chk(self._l.vgmi_hmm_tallies_select_wide(self._h, bit_len, n_rows, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(winner), pos_a.size,
                                                         _ptr(pos_a), _ptr(pos_b), win_used.shape[1], win_used.shape[0], _ptr(win_used), _ptr(out), _ptr(uniq)))
+        return out[:n_rows], uniq[:n_rows]
+
+    def hmm_emissions_select_ploidy_wide(self, ploidy, win_n_gt, win_haps, win_top_mask, bit_len, ave, lower, upper, tables, entry_begin, entry_count,
+                                         row_win, gt0, fixes=None):
+        """vgmi_hmm_emissions_select_ploidy_wide (+ _part_fix_rows_ploidy_wide) + _part_fetch: hmm_emissions_select_ploidy over entries of
+        bit_len bytes.  win_top_mask (n_windows, W), gt0 (rows, W) and the fixes' masks (fixes, W) are words over haplotype ids.
+        Returns (obs (rows, n_gt) longdouble, n_kept, flags)."""
+        win_n_gt = np.ascontiguousarray(win_n_gt, dtype=np.uint32)
+        win_haps = np.ascontiguousarray(win_haps, dtype=np.uint8)
+        win_top_mask = np.ascontiguousarray(win_top_mask, dtype=np.uint64)
+        tables = np.ascontiguousarray(tables, dtype=np.longdouble)
+        entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
+        entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
+        row_win = np.ascontiguousarray(row_win, dtype=np.uint32)
+        gt0 = np.ascontiguousarray(gt0, dtype=np.uint64)
+        words = 1 if bit_len <= 8 else 2 if bit_len <= 16 else 4
+        assert win_haps.ndim == 3 and win_haps.shape[2] == ploidy and tables.size == 256 * (ploidy + 1) and win_n_gt.size == win_haps.shape[0]
+        n_rows, n_gt = entry_begin.size, win_haps.shape[1]
+        assert (win_top_mask.size == win_haps.shape[0] * words and gt0.size == n_rows * words) or not 1 <= bit_len <= 32
+        n_kept = np.zeros(max(n_rows, 1), dtype=np.uint32)
+        flags = np.zeros(max(n_rows, 1), dtype=np.uint8)
+        part = C.c_void_p()
+        self._chk(self._l.vgmi_hmm_emissions_select_ploidy_wide(self._h, n_gt, ploidy, win_haps.shape[0], _ptr(win_n_gt), _ptr(win_haps), _ptr(win_top_mask),
+                                                                 bit_len, float(ave), float(lower), float(upper), _ptr(tables), n_rows, _ptr(entry_begin),
+                                                                 _ptr(entry_count), _ptr(row_win), _ptr(gt0), _ptr(n_kept), _ptr(flags), C.byref(part)))
+        try:
+            if fixes is not None:
+                f_rows, f_off, f_j, f_m = (np.ascontiguousarray(a, dtype=t) for a, t in zip(fixes, (np.uint64, np.uint32, np.uint32, np.uint64)))
+                assert f_m.size == f_j.size * words
+                self._chk(self._l.vgmi_hmm_part_fix_rows_ploidy_wide(part, f_rows.size, _ptr(f_rows), _ptr(f_off), _ptr(f_j), _ptr(f_m)))
+            obs = np.zeros((n_rows, n_gt), dtype=np.longdouble)
+            self._chk(self._l.vgmi_hmm_part_fetch(part, _ptr(obs)))
+        finally:
+            self._l.vgmi_hmm_part_free(part)
+        return obs, n_kept[:n_rows], flags[:n_rows]
+
+    def hmm_tallies_ploidy_wide(self, bit_len, ploidy, win_haps, win_sel_mask, entry_begin, entry_count, winner, row_win=None, win_n_gt=None, use_alive=True):
+        """vgmi_hmm_tallies_ploidy_wide: hmm_tallies_ploidy over entries of bit_len bytes; win_sel_mask (n_windows, W) words."""
+        win_haps = np.ascontiguousarray(win_haps, dtype=np.uint8)
+        win_sel_mask = np.ascontiguousarray(win_sel_mask, dtype=np.uint64)
+        entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
+        entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
+        winner = np.ascontiguousarray(winner, dtype=np.uint32)
+        row_win = None if row_win is None else np.ascontiguousarray(row_win, dtype=np.uint32)
+        win_n_gt = None if win_n_gt is None else np.ascontiguousarray(win_n_gt, dtype=np.uint32)
+        words = 1 if bit_len <= 8 else 2 if bit_len <= 16 else 4
+        assert win_haps.ndim == 3 and win_haps.shape[2] == ploidy and entry_count.size == winner.size == entry_begin.size
+        assert win_sel_mask.size == win_haps.shape[0] * words or not 1 <= bit_len <= 32
+        assert (row_win is None or row_win.size == entry_begin.size) and (win_n_gt is None or win_n_gt.size == win_haps.shape[0])
+        n_rows, width = entry_begin.size, 2 * max(int(ploidy), 1)
+        out = np.full((max(n_rows, 1), width), 0xDEADBEEF, dtype=np.uint32)
+        uniq = np.full(max(n_rows, 1), 0xEE, dtype=np.uint8)
+        self._chk(self._l.vgmi_hmm_tallies_ploidy_wide(self._h, bit_len, ploidy, win_haps.shape[1], win_haps.shape[0], _ptr(win_n_gt), _ptr(win_haps),
+                                                        _ptr(win_sel_mask), n_rows, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(winner),
+                                                        int(bool(use_alive)), _ptr(out), _ptr(uniq)))
         return out[:n_rows], uniq[:n_rows]
 
     def hmm_tallies_ploidy(self, ploidy, win_haps, win_sel_mask, entry_begin, entry_count, winner, row_win=None, win_n_gt=None, use_alive=True):
