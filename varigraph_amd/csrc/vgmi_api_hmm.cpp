@@ -12,16 +12,11 @@ struct vgmi_hmm_part {
     uint8_t* d_small = nullptr;
     size_t small_bytes = 0;
     std::vector<uint32_t> entry_count;      // (host copy: fix_j is checked against it)
-    // a part of vgmi_hmm_emissions_select_ploidy (a genotype list per window): its launch, for vgmi_hmm_part_fix_rows_wide
+    // a part of vgmi_hmm_emissions_select_ploidy, _wide (a genotype list per window): its launch instead, for vgmi_hmm_part_fix_rows_wide and
+    // vgmi_hmm_part_fix_rows_ploidy_wide
     bool per_window_lists = false;
     HmmEmitWinParams emit_win{};
-    // a part of vgmi_hmm_emissions_select_wide (W words of haplotype bits per entry; 0: none of the above): its launch, for vgmi_hmm_part_fix_rows
-    uint32_t wide_words = 0;
-    HmmEmitWideParams emit_wide{};
-    // a part of vgmi_hmm_emissions_select_ploidy_wide (a genotype list per window AND W words per entry; 0: none of the above): its launch, for
-    // vgmi_hmm_part_fix_rows_ploidy_wide
-    uint32_t win_wide_words = 0;
-    HmmEmitWinWideParams emit_win_wide{};
+    uint32_t wide_words = 0;      // of a _wide call: W words of haplotype bits per entry, and per mask over haplotype ids; 0: packed entries
 };
 
 namespace {
@@ -148,16 +143,23 @@ struct HmmCallTimes {
             for (auto& x : ev) (void)hipEventDestroy(x);
     }
     void mark(int i, hipStream_t st) { if (on) (void)hipEventRecord(ev[i], st); }
-    void report(HmmCall& call, const char* what, uint64_t n_rows, uint32_t bit_len)
+    // waits for the call; false: the diagnostics are off
+    bool times(HmmCall& call, float& up, float& kern, float& down)
     {
-        if (!on) return;
+        if (!on) return false;
         call.sync();
-        float up = 0, kern = 0, down = 0;
+        up = kern = down = 0;
         if (call.ok()) {
             (void)hipEventElapsedTime(&up, ev[0], ev[1]);
             (void)hipEventElapsedTime(&kern, ev[1], ev[2]);
             (void)hipEventElapsedTime(&down, ev[2], ev[3]);
         }
+        return true;
+    }
+    void report(HmmCall& call, const char* what, uint64_t n_rows, uint32_t bit_len)
+    {
+        float up, kern, down;
+        if (!times(call, up, kern, down)) return;
         fprintf(stderr, "[vgmi] HMM %s call, %u bytes of haplotype bits: %llu rows, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", what, bit_len,
                 (unsigned long long)n_rows, up, kern, down);
     }
@@ -368,14 +370,53 @@ int hmm_run(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, const uint8_t* keep, ui
     return VGMI_OK;
 }
 
+// the entries of vgmi_hmm_entries_upload_wide leave the context (a replaced table, either form)
+void hmm_wide_free(vgmi_ctx* c)
+{
+    if (c->d_hmm_f) (void)hipFree(c->d_hmm_f);
+    if (c->d_hmm_bits) (void)hipFree(c->d_hmm_bits);
+    c->d_hmm_f = nullptr;
+    c->d_hmm_bits = nullptr;
+    c->hmm_bit_len = 0;
+    c->hmm_words = 0;
+}
+
+// a _wide call's width against the upload's: VGMI_E_INVALID for a width no upload can have, VGMI_E_STATE for another form or width
+int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len)
+{
+    if (bit_len < 1 || bit_len > 32) return fail(c, VGMI_E_INVALID, std::string(who) + ": 1..32 bytes of haplotype bits");
+    if (!c->d_hmm_bits || !c->d_hmm_f || !c->d_hmm_cov || !c->d_hmm_alive)
+        return fail(c, VGMI_E_STATE, std::string(who) + ": upload the entries with vgmi_hmm_entries_upload_wide first");
+    if (bit_len != c->hmm_bit_len) return fail(c, VGMI_E_STATE, std::string(who) + ": the entries were uploaded with another number of bytes of haplotype bits");
+    return VGMI_OK;
+}
+
+// The storage form an entry point stands for.  A packed call and its _wide namesake are one implementation below; the form says which
+// upload it reads, how it is checked, how many words a mask over haplotype ids has, and whether VGMI_HMM_TIMING reports the call (the
+// packed calls that never did still do not).
+struct HmmForm {
+    bool wide;
+    uint32_t bit_len;      // the call's (packed: where the call has one)
+    // the upload is there and is this form's; `missing`: the packed call's words for none
+    int check(vgmi_ctx* c, const char* who, const char* missing, bool need_alive = true) const
+    {
+        if (wide) return hmm_check_wide(c, who, bit_len);
+        if (!c->d_hmm_entries || !c->d_hmm_cov || (need_alive && !c->d_hmm_alive)) return fail(c, VGMI_E_STATE, std::string(who) + ": " + missing);
+        return VGMI_OK;
+    }
+    uint32_t words(const vgmi_ctx* c) const { return wide ? c->hmm_words : 1u; }
+    HmmEntries entries(const vgmi_ctx* c) const { return wide ? HmmEntries{c->d_hmm_f, c->hmm_words, c->d_hmm_bits} : HmmEntries{nullptr, 0u, c->d_hmm_entries}; }
+    uint32_t n_ids() const { return 8 * bit_len - 1; }      // the last bit is no haplotype
+};
+
 struct HmmSelect {      // haplotypes selected per window (vgmi_hmm_emissions_select)
     uint32_t n_windows;
     const uint8_t* win_used;          // n_windows x n_used
-    const uint64_t* win_top_mask;     // n_windows
+    const uint64_t* win_top_mask;     // n_windows x the form's words
     const uint32_t* row_win;          // n_rows
 };
 
-// What the two emission entry points share: the part with its block of scores, and a staged call whose block -- entry_begin | entry_count |
+// What the emission entry points share: the part with its block of scores, and a staged call whose block -- entry_begin | entry_count |
 // gt0 | tables | n_kept | flags | the entry point's own arrays -- stays with the part (a fix launch reads the row arrays and tables again).
 // Until finish() has handed the part out, the destructor takes it apart.
 struct HmmEmitCall {
@@ -412,9 +453,16 @@ struct HmmEmitCall {
         call.upload(o_tab, tables, tab_bytes);
         return VGMI_OK;
     }
-    // after the launch: the rows' counts and flags come back, the part goes out
-    int finish(const uint32_t* entry_count, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+    // after the launch (between tm's marks 2 and 3; `what` names the call in the diagnostics): the rows' counts and flags come back, the
+    // part goes out
+    int finish(HmmCallTimes& tm, const char* what, uint32_t bit_len, const uint32_t* entry_count, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
     {
+        if (tm.on) {      // (fetched again below: the figure is the diagnostics')
+            call.download(n_kept_out, o_nk, n_rows * 4);
+            call.download(flags_out, o_fl, n_rows);
+            tm.mark(3, call.stream());
+            tm.report(call, what, n_rows, bit_len);
+        }
         call.download(n_kept_out, o_nk, n_rows * 4);
         call.download(flags_out, o_fl, n_rows);
         HIPCHK(c, call.finish(&part->d_small, &part->small_bytes));
@@ -425,9 +473,10 @@ struct HmmEmitCall {
     }
 };
 
-int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t* used, const uint8_t* pos, uint64_t top_mask,
-                       uint32_t bit_len, float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin,
-                       const uint32_t* entry_count, const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out, const HmmSelect* sel)
+// genotypes as places in a list of haplotypes: the whole panel's one list (sel == nullptr, packed entries only), or a list per window
+int hmm_emissions_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_gt, uint32_t ploidy, uint32_t n_used, const uint8_t* used, const uint8_t* pos, uint64_t top_mask,
+                       float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
+                       const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out, const HmmSelect* sel)
 {
     if (!c || !used || !pos || !tables || !out) return VGMI_E_INVALID;
     if (ploidy < 2 || ploidy > 8 || (sel && ploidy != 2)) return fail(c, VGMI_E_INVALID, "HMM emissions: genotypes of 2..8 haplotypes");
@@ -441,17 +490,20 @@ int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_u
             if (pos[(size_t)g * ploidy + q] >= n_used) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype names a haplotype outside the list");
     }
     if (n_rows && (!entry_begin || !entry_count || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
-    if (n_used < 1 || n_used > 16 || bit_len < 1 || bit_len > 6) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes over 1..16 haplotypes, 1..6 bytes of haplotype bits");
-    if (!c->d_hmm_entries) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
+    if (n_used < 1 || n_used > 16 || (!form.wide && (form.bit_len < 1 || form.bit_len > 6)))
+        return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes over 1..16 haplotypes, 1..6 bytes of haplotype bits");
+    if (!form.wide && !c->d_hmm_entries) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
     if (int rc = hmm_check_rows(c, "HMM emissions", n_rows, entry_begin, entry_count, sel ? sel->row_win : nullptr, sel ? sel->n_windows : 0)) return rc;
     *out = nullptr;
     HmmEmitCall ec(c, n_rows, 2, ploidy);
     HmmCall& call = ec.call;
-    const size_t n_win = sel ? sel->n_windows : 0;      // per-window selection: row_win | win_used | win_top_mask
-    const size_t o_rw = call.add(sel ? n_rows * 4 : 0), o_wu = call.add(n_win * 16), o_wm = call.add(n_win * 8);
+    const size_t n_win = sel ? sel->n_windows : 0, b_mask = n_win * 8 * form.words(c);      // per-window selection: row_win | win_used | win_top_mask
+    const size_t o_rw = call.add(sel ? n_rows * 4 : 0), o_wu = call.add(n_win * 16), o_wm = call.add(b_mask);
     std::vector<uint8_t> wu16;
     if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
-    P.packed = c->d_hmm_entries;
+    HmmCallTimes tm(form.wide);
+    tm.mark(0, call.stream());
+    P.ent = form.entries(c);
     P.cov = c->d_hmm_cov;
     P.entry_begin = call.at<const uint64_t>(ec.o_eb);
     P.entry_count = call.at<const uint32_t>(ec.o_ec);
@@ -459,8 +511,8 @@ int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_u
     P.row_lo = 0;
     P.n_gt = n_gt;
     P.n_used = n_used;
-    P.bl8 = 8 * bit_len;
-    memcpy(P.used, used, n_used);
+    P.bl8 = 8 * form.bit_len;
+    if (!sel) memcpy(P.used, used, n_used);
     P.ploidy = ploidy;
     P.top_mask = top_mask;
     P.ave = ave;
@@ -474,28 +526,96 @@ int hmm_emissions_impl(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint32_t n_u
         wu16 = hmm_used16(sel->win_used, n_win, n_used);
         call.upload(o_rw, sel->row_win, n_rows * 4);
         call.upload(o_wu, wu16.data(), wu16.size());
-        call.upload(o_wm, sel->win_top_mask, n_win * 8);
+        call.upload(o_wm, sel->win_top_mask, b_mask);
         P.row_win = call.at<const uint32_t>(o_rw);
         P.win_used = call.at(o_wu);
         P.win_top_mask = call.at<const unsigned long long>(o_wm);
         P.alive = c->d_hmm_alive;
     }
+    tm.mark(1, call.stream());
     call.run([&] { return launch_hmm_emissions(P, n_rows, call.stream()); });
+    tm.mark(2, call.stream());
     ec.part->emit = P;
-    return ec.finish(entry_count, n_kept_out, flags_out, out);
+    ec.part->wide_words = P.ent.W;
+    return ec.finish(tm, "emission", form.bit_len, entry_count, n_kept_out, flags_out, out);
 }
 
-// a part's flagged rows scored again (vgmi_hmm_part_fix_rows, _wide): the part's own launch with the fixes attached
+// a genotype LIST per window (vgmi_hmm_emissions_select_ploidy, _wide); `shape` and `who_rows`: the form's words for a refused shape and
+// for hmm_check_rows
+int hmm_emissions_win_impl(vgmi_ctx* c, const HmmForm& form, const char* shape, const char* who_rows, uint32_t n_gt, uint32_t ploidy, uint32_t n_windows,
+                           const uint32_t* win_n_gt, const uint8_t* win_haps, const uint64_t* win_top_mask, float ave, double lower, double upper,
+                           const void* tables, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                           const uint64_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    if (!c || !tables || !out) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 8 || (!form.wide && (form.bit_len < 1 || form.bit_len > 6))) return fail(c, VGMI_E_INVALID, shape);
+    if (n_windows < 1 || !win_n_gt || !win_haps || !win_top_mask) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their genotype lists");
+    if (n_rows && (!entry_begin || !entry_count || !row_win || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
+    if (int rc = form.check(c, "HMM emissions", "upload the entries first")) return rc;
+    const uint32_t W = form.words(c), n_ids = form.n_ids();
+    std::vector<uint64_t> used_mask((size_t)n_windows * W, 0);
+    for (uint32_t w = 0; w < n_windows; ++w) {
+        if (win_n_gt[w] < 1 || win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM emissions: a window's genotype count outside 1..n_gt");
+        for (size_t i = 0; i < (size_t)win_n_gt[w] * ploidy; ++i) {
+            const uint32_t hap = win_haps[(size_t)w * n_gt * ploidy + i];
+            if (hap >= n_ids) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype's haplotype outside the haplotype bits");
+            used_mask[(size_t)w * W + (hap >> 6)] |= 1ull << (hap & 63u);
+        }
+        for (uint32_t i = 0; i < W; ++i) {
+            const uint64_t hap_bits = n_ids >= 64u * (i + 1u) ? ~0ull : n_ids <= 64u * i ? 0ull : (1ull << (n_ids - 64u * i)) - 1ull;
+            if (win_top_mask[(size_t)w * W + i] & ~hap_bits) return fail(c, VGMI_E_INVALID, "HMM emissions: a drawn haplotype outside the haplotype bits");
+        }
+    }
+    if (int rc = hmm_check_rows(c, who_rows, n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    *out = nullptr;
+    HmmEmitCall ec(c, n_rows, (size_t)8 * W, ploidy);
+    HmmCall& call = ec.call;
+    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_mask = (size_t)n_windows * 8 * W;      // row_win | win_n_gt | win_haps | win_top_mask | win_used_mask
+    const size_t o_rw = call.add(n_rows * 4), o_wn = call.add((size_t)n_windows * 4), o_wh = call.add(b_haps), o_wm = call.add(b_mask), o_wu = call.add(b_mask);
+    if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
+    HmmCallTimes tm(form.wide);
+    tm.mark(0, call.stream());
+    ec.part->per_window_lists = true;
+    call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_wn, win_n_gt, (size_t)n_windows * 4);
+    call.upload(o_wh, win_haps, b_haps);
+    call.upload(o_wm, win_top_mask, b_mask);
+    call.upload(o_wu, used_mask.data(), b_mask);
+    HmmEmitWinParams P{};
+    P.ent = form.entries(c);
+    P.cov = c->d_hmm_cov;
+    P.alive = c->d_hmm_alive;
+    P.entry_begin = call.at<const uint64_t>(ec.o_eb);
+    P.entry_count = call.at<const uint32_t>(ec.o_ec);
+    P.row_win = call.at<const uint32_t>(o_rw);
+    P.gt0 = call.at<const unsigned long long>(ec.o_g0);
+    P.n_gt = n_gt;
+    P.ploidy = ploidy;
+    P.bl8 = 8 * form.bit_len;
+    P.ave = ave;
+    P.lower = lower;
+    P.upper = upper;
+    P.tables = call.at(ec.o_tab);
+    P.win_n_gt = call.at<const uint32_t>(o_wn);
+    P.win_haps = call.at(o_wh);
+    P.win_top_mask = call.at<const unsigned long long>(o_wm);
+    P.win_used_mask = call.at<const unsigned long long>(o_wu);
+    P.obs = ec.part->d_obs;
+    P.n_kept = call.at<uint32_t>(ec.o_nk);
+    P.flags = call.at(ec.o_fl);
+    P.n_items = n_rows;
+    tm.mark(1, call.stream());
+    call.run([&] { return launch_hmm_emissions_win(P, call.stream()); });
+    tm.mark(2, call.stream());
+    ec.part->emit_win = P;
+    ec.part->wide_words = P.ent.W;
+    return ec.finish(tm, "emission (a genotype list per window)", form.bit_len, entry_count, n_kept_out, flags_out, out);
+}
+
+// a part's flagged rows scored again (vgmi_hmm_part_fix_rows*): the part's own launch with the fixes attached -- masks over the places of
+// a window's list, or (W words of) haplotype ids
 hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t* rows, const uint32_t* off, const uint32_t* j, const uint16_t* mask, hipStream_t st)
 {
-    if (part.wide_words) {      // (the same masks over the places of a window's list; the entries' bits are W words)
-        HmmEmitWideParams Q = part.emit_wide;
-        Q.e.fix_rows = rows;
-        Q.e.fix_off = off;
-        Q.e.fix_j = j;
-        Q.e.fix_mask = mask;
-        return launch_hmm_emissions_wide(Q, part.wide_words, n, st);
-    }
     HmmEmitParams P = part.emit;
     P.fix_rows = rows;
     P.fix_off = off;
@@ -506,15 +626,6 @@ hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t*
 
 hipError_t hmm_launch_fix(const vgmi_hmm_part& part, uint64_t n, const uint64_t* rows, const uint32_t* off, const uint32_t* j, const uint64_t* mask, hipStream_t st)
 {
-    if (part.win_wide_words) {      // (W words of haplotype ids per fix; the entries' bits are W words)
-        HmmEmitWinWideParams Q = part.emit_win_wide;
-        Q.e.n_items = n;
-        Q.e.fix_rows = rows;
-        Q.e.fix_off = off;
-        Q.e.fix_j = j;
-        Q.e.fix_mask = reinterpret_cast<const unsigned long long*>(mask);
-        return launch_hmm_emissions_win_wide(Q, part.win_wide_words, st);
-    }
     HmmEmitWinParams P = part.emit_win;
     P.n_items = n;
     P.fix_rows = rows;
@@ -540,7 +651,7 @@ int hmm_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const ui
     HmmCall call(c);
     const size_t o_rows = call.add(n * 8), o_off = call.add((n + 1) * 4), o_j = call.add((size_t)n_fix * 4), o_m = call.add((size_t)n_fix * mask_words * sizeof(Mask));
     if (int rc = call.begin("HMM emissions")) return rc;
-    HmmCallTimes tm(part->win_wide_words != 0);      // (the diagnostics of the calls that have them)
+    HmmCallTimes tm(part->per_window_lists && part->wide_words);      // (the diagnostics of the calls that have them)
     tm.mark(0, call.stream());
     call.upload(o_rows, rows, n * 8);
     call.upload(o_off, fix_off, (n + 1) * 4);
@@ -553,29 +664,139 @@ int hmm_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const ui
     });
     tm.mark(2, call.stream());
     tm.mark(3, call.stream());
-    tm.report(call, "emission fix", n, part->emit_win_wide.e.bl8 / 8);
+    tm.report(call, "emission fix", n, part->emit_win.bl8 / 8);
     HIPCHK(c, call.finish());
     return VGMI_OK;
 }
 
-// the entries of vgmi_hmm_entries_upload_wide leave the context (a replaced table, either form)
-void hmm_wide_free(vgmi_ctx* c)
+// selection support (vgmi_hmm_support, _wide)
+int hmm_support_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
+                     const uint32_t* row_win, uint32_t* support_out)
 {
-    if (c->d_hmm_f) (void)hipFree(c->d_hmm_f);
-    if (c->d_hmm_bits) (void)hipFree(c->d_hmm_bits);
-    c->d_hmm_f = nullptr;
-    c->d_hmm_bits = nullptr;
-    c->hmm_bit_len = 0;
-    c->hmm_words = 0;
+    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win)) || (n_windows && !support_out)) return VGMI_E_INVALID;
+    if (!form.wide && (n_hap < 1 || n_hap > 48)) return fail(c, VGMI_E_INVALID, "HMM support: 1..48 haplotypes");
+    if (int rc = form.check(c, "HMM support", "upload the entries and the sample's coverage first")) return rc;
+    if (form.wide && (n_hap < 1 || n_hap > form.n_ids())) return fail(c, VGMI_E_INVALID, "HMM support: more haplotypes than the haplotype bits hold");
+    if (int rc = hmm_check_rows(c, "HMM support", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_windows == 0) return VGMI_OK;
+    const size_t b_sup = (size_t)n_windows * n_hap * 4;
+    if (n_rows == 0) {
+        memset(support_out, 0, b_sup);
+        return VGMI_OK;
+    }
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_sup = call.add(b_sup);
+    if (int rc = call.begin("HMM support")) return rc;
+    HmmCallTimes tm(form.wide);
+    tm.mark(0, call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    call.upload(o_win, row_win, n_rows * 4);
+    call.zero(o_sup, b_sup);
+    tm.mark(1, call.stream());
+    call.run([&] {
+        return launch_hmm_support(form.entries(c), c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg), call.at<const uint32_t>(o_cnt),
+                                  call.at<const uint32_t>(o_win), n_rows, n_hap, call.at<uint32_t>(o_sup), call.stream());
+    });
+    tm.mark(2, call.stream());
+    call.download(support_out, o_sup, b_sup);
+    tm.mark(3, call.stream());
+    tm.report(call, "support", n_rows, form.bit_len);
+    HIPCHK(c, call.finish());
+    return VGMI_OK;
 }
 
-// a _wide call's width against the upload's: VGMI_E_INVALID for a width no upload can have, VGMI_E_STATE for another form or width
-int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len)
+// the calls' tallies with the haplotypes selected per window (vgmi_hmm_tallies_select, _wide); n_ids: the ids a selected haplotype may have
+int hmm_tallies_select_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_ids, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
+                            const uint32_t* row_win, const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used,
+                            uint32_t n_windows, const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
 {
-    if (bit_len < 1 || bit_len > 32) return fail(c, VGMI_E_INVALID, std::string(who) + ": 1..32 bytes of haplotype bits");
-    if (!c->d_hmm_bits || !c->d_hmm_f || !c->d_hmm_cov || !c->d_hmm_alive)
-        return fail(c, VGMI_E_STATE, std::string(who) + ": upload the entries with vgmi_hmm_entries_upload_wide first");
-    if (bit_len != c->hmm_bit_len) return fail(c, VGMI_E_STATE, std::string(who) + ": the entries were uploaded with another number of bytes of haplotype bits");
+    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win || !winner || !out || !unique_out)) || !pos_a || !pos_b || !win_used) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16 || n_windows < 1) return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes over 1..16 haplotypes");
+    if (int rc = form.check(c, "HMM tallies", "upload the entries and the sample's coverage first")) return rc;
+    for (uint32_t g = 0; g < n_gt; ++g)
+        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM tallies: a genotype names a haplotype outside the list");
+    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
+        if (win_used[i] >= n_ids) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
+    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_rows == 0) return VGMI_OK;
+    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used), pos_ab = hmm_pos_pairs(pos_a, pos_b, n_gt);
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_out = call.add(n_rows * 16),
+                 o_uni = call.add(n_rows), o_pos = call.add(pos_ab.size()), o_wu = call.add(wu16.size());
+    if (int rc = call.begin("HMM tallies")) return rc;
+    HmmCallTimes tm(form.wide);
+    tm.mark(0, call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_win, winner, n_rows * 4);
+    call.upload(o_pos, pos_ab.data(), pos_ab.size());
+    call.upload(o_wu, wu16.data(), wu16.size());
+    tm.mark(1, call.stream());
+    call.run([&] {
+        return launch_hmm_tally_select(form.entries(c), c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg), call.at<const uint32_t>(o_cnt),
+                                       call.at<const uint32_t>(o_rw), call.at<const uint32_t>(o_win), call.at(o_pos), call.at(o_wu), n_gt, n_rows,
+                                       call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
+    });
+    tm.mark(2, call.stream());
+    call.download(out, o_out, n_rows * 16);
+    call.download(unique_out, o_uni, n_rows);
+    tm.mark(3, call.stream());
+    tm.report(call, "tally", n_rows, form.bit_len);
+    HIPCHK(c, call.finish());
+    return VGMI_OK;
+}
+
+// the tallies of a polyploid call (vgmi_hmm_tallies_ploidy, _wide)
+int hmm_tallies_ploidy_impl(vgmi_ctx* c, const HmmForm& form, uint32_t ploidy, uint32_t n_gt, uint32_t n_windows, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                            const uint64_t* win_sel_mask, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                            const uint32_t* winner, int use_alive, uint32_t* out, uint8_t* unique_out)
+{
+    if (!c || (n_rows && (!entry_begin || !entry_count || !winner || !out || !unique_out)) || !win_haps || !win_sel_mask) return VGMI_E_INVALID;
+    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || n_gt > 128 || n_windows < 1)
+        return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes of 2..4 haplotypes in at least one window");
+    if (int rc = form.check(c, "HMM tallies", "upload the entries and the sample's coverage first", use_alive != 0)) return rc;
+    if (win_n_gt)
+        for (uint32_t w = 0; w < n_windows; ++w)
+            if (win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM tallies: a window with more genotypes than the lists are wide");
+    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
+    if (n_rows == 0) return VGMI_OK;
+    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_out = n_rows * 8 * ploidy, b_mask = (size_t)n_windows * 8 * form.words(c);
+    HmmCall call(c);
+    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(row_win ? n_rows * 4 : 0), o_win = call.add(n_rows * 4),
+                 o_out = call.add(b_out), o_uni = call.add(n_rows), o_ng = call.add(win_n_gt ? (size_t)n_windows * 4 : 0), o_haps = call.add(b_haps),
+                 o_mask = call.add(b_mask);
+    if (int rc = call.begin("HMM tallies")) return rc;
+    HmmCallTimes tm;
+    tm.mark(0, call.stream());
+    call.upload(o_beg, entry_begin, n_rows * 8);
+    call.upload(o_cnt, entry_count, n_rows * 4);
+    if (row_win) call.upload(o_rw, row_win, n_rows * 4);
+    call.upload(o_win, winner, n_rows * 4);
+    if (win_n_gt) call.upload(o_ng, win_n_gt, (size_t)n_windows * 4);
+    call.upload(o_haps, win_haps, b_haps);
+    call.upload(o_mask, win_sel_mask, b_mask);
+    tm.mark(1, call.stream());
+    call.run([&] {
+        return launch_hmm_tally_ploidy(form.entries(c), c->d_hmm_cov, use_alive ? c->d_hmm_alive : nullptr, call.at<const uint64_t>(o_beg),
+                                       call.at<const uint32_t>(o_cnt), row_win ? call.at<const uint32_t>(o_rw) : nullptr, call.at<const uint32_t>(o_win),
+                                       win_n_gt ? call.at<const uint32_t>(o_ng) : nullptr, call.at(o_haps), call.at<const unsigned long long>(o_mask), n_gt, ploidy,
+                                       8 * form.bit_len, n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
+    });
+    tm.mark(2, call.stream());
+    call.download(out, o_out, b_out);
+    call.download(unique_out, o_uni, n_rows);
+    tm.mark(3, call.stream());
+    if (form.wide) {
+        tm.report(call, "tally (polyploid)", n_rows, form.bit_len);
+    } else {      // (the packed call's own line, older than report()'s)
+        float up, kern, down;
+        if (tm.times(call, up, kern, down))
+            fprintf(stderr, "[vgmi] HMM tally call: %llu rows of %u haplotypes, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", (unsigned long long)n_rows,
+                    ploidy, up, kern, down);
+    }
+    HIPCHK(c, call.finish());
     return VGMI_OK;
 }
 
@@ -631,30 +852,7 @@ int vgmi_hmm_alive_fetch(vgmi_ctx* c, uint8_t* alive_out, size_t n)
 int vgmi_hmm_support(vgmi_ctx* c, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
                      const uint32_t* row_win, uint32_t* support_out)
 {
-    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win)) || (n_windows && !support_out)) return VGMI_E_INVALID;
-    if (n_hap < 1 || n_hap > 48) return fail(c, VGMI_E_INVALID, "HMM support: 1..48 haplotypes");
-    if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM support: upload the entries and the sample's coverage first");
-    if (int rc = hmm_check_rows(c, "HMM support", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    if (n_windows == 0) return VGMI_OK;
-    const size_t b_sup = (size_t)n_windows * n_hap * 4;
-    if (n_rows == 0) {
-        memset(support_out, 0, b_sup);
-        return VGMI_OK;
-    }
-    HmmCall call(c);
-    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_sup = call.add(b_sup);
-    if (int rc = call.begin("HMM support")) return rc;
-    call.upload(o_beg, entry_begin, n_rows * 8);
-    call.upload(o_cnt, entry_count, n_rows * 4);
-    call.upload(o_win, row_win, n_rows * 4);
-    call.zero(o_sup, b_sup);
-    call.run([&] {
-        return launch_hmm_support(c->d_hmm_entries, c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg), call.at<const uint32_t>(o_cnt),
-                                  call.at<const uint32_t>(o_win), n_rows, n_hap, call.at<uint32_t>(o_sup), call.stream());
-    });
-    call.download(support_out, o_sup, b_sup);
-    HIPCHK(c, call.finish());
-    return VGMI_OK;
+    return hmm_support_impl(c, HmmForm{false, 0}, n_hap, n_windows, n_rows, entry_begin, entry_count, row_win, support_out);
 }
 
 
@@ -684,8 +882,8 @@ int vgmi_hmm_emissions_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy, uint3
                               uint32_t bit_len, float ave, double lower, double upper, const void* tables, uint64_t n_rows, const uint64_t* entry_begin,
                               const uint32_t* entry_count, const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
 {
-    return hmm_emissions_impl(c, n_gt, ploidy, n_used, used, pos, top_mask, bit_len, ave, lower, upper, tables, n_rows, entry_begin, entry_count, gt0, n_kept_out,
-                              flags_out, out, nullptr);
+    return hmm_emissions_impl(c, HmmForm{false, bit_len}, n_gt, ploidy, n_used, used, pos, top_mask, ave, lower, upper, tables, n_rows, entry_begin, entry_count, gt0,
+                              n_kept_out, flags_out, out, nullptr);
 }
 
 // ---- emission scores with the haplotypes selected per window (-n below the panel's haplotypes, a diploid sample) ----------------------
@@ -705,8 +903,8 @@ int vgmi_hmm_emissions_select(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const
     for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
         if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a selected haplotype outside the haplotype bits");
     const HmmSelect sel{n_windows, win_used, win_top_mask, row_win};
-    return hmm_emissions_impl(c, n_gt, 2, n_used, win_used, hmm_pos_pairs(pos_a, pos_b, n_gt).data(), 0, bit_len, ave, lower, upper, tables, n_rows, entry_begin,
-                              entry_count, gt0, n_kept_out, flags_out, out, &sel);
+    return hmm_emissions_impl(c, HmmForm{false, bit_len}, n_gt, 2, n_used, win_used, hmm_pos_pairs(pos_a, pos_b, n_gt).data(), 0, ave, lower, upper, tables, n_rows,
+                              entry_begin, entry_count, gt0, n_kept_out, flags_out, out, &sel);
 }
 
 
@@ -718,7 +916,7 @@ int vgmi_hmm_part_fix_rows(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows
 {
     if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
     if (n == 0) return VGMI_OK;
-    if (part->win_wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part's fixes are W-word masks over haplotype ids (vgmi_hmm_part_fix_rows_ploidy_wide)");
+    if (part->per_window_lists && part->wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part's fixes are W-word masks over haplotype ids (vgmi_hmm_part_fix_rows_ploidy_wide)");
     if (part->per_window_lists) return fail(part->c, VGMI_E_INVALID, "HMM emissions: this part's fixes are masks over haplotype ids (vgmi_hmm_part_fix_rows_wide)");
     return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask);
 }
@@ -734,63 +932,9 @@ int vgmi_hmm_emissions_select_ploidy(vgmi_ctx* c, uint32_t n_gt, uint32_t ploidy
                                      uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint64_t* gt0,
                                      uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
 {
-    if (!c || !tables || !out) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 8 || bit_len < 1 || bit_len > 6)
-        return fail(c, VGMI_E_INVALID, "HMM emissions: 1..64 genotypes of 2..8 haplotypes per window, 1..6 bytes of haplotype bits");
-    if (n_windows < 1 || !win_n_gt || !win_haps || !win_top_mask) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their genotype lists");
-    if (n_rows && (!entry_begin || !entry_count || !row_win || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
-    if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM emissions: upload the entries first");
-    const uint64_t hap_bits = (1ull << (8 * bit_len - 1)) - 1ull;      // the last bit is no haplotype
-    std::vector<uint64_t> used_mask(n_windows, 0);
-    for (uint32_t w = 0; w < n_windows; ++w) {
-        if (win_n_gt[w] < 1 || win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM emissions: a window's genotype count outside 1..n_gt");
-        for (size_t i = 0; i < (size_t)win_n_gt[w] * ploidy; ++i) {
-            const uint8_t hap = win_haps[(size_t)w * n_gt * ploidy + i];
-            if (hap >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype's haplotype outside the haplotype bits");
-            used_mask[w] |= 1ull << hap;
-        }
-        if (win_top_mask[w] & ~hap_bits) return fail(c, VGMI_E_INVALID, "HMM emissions: a drawn haplotype outside the haplotype bits");
-    }
-    if (int rc = hmm_check_rows(c, "HMM emissions: a row outside the entries or the windows", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    *out = nullptr;
-    HmmEmitCall ec(c, n_rows, 8, ploidy);
-    HmmCall& call = ec.call;
-    const size_t b_haps = (size_t)n_windows * n_gt * ploidy;      // row_win | win_n_gt | win_haps | win_top_mask | win_used_mask
-    const size_t o_rw = call.add(n_rows * 4), o_wn = call.add((size_t)n_windows * 4), o_wh = call.add(b_haps), o_wm = call.add((size_t)n_windows * 8),
-                 o_wu = call.add((size_t)n_windows * 8);
-    if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
-    ec.part->per_window_lists = true;
-    call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_wn, win_n_gt, (size_t)n_windows * 4);
-    call.upload(o_wh, win_haps, b_haps);
-    call.upload(o_wm, win_top_mask, (size_t)n_windows * 8);
-    call.upload(o_wu, used_mask.data(), (size_t)n_windows * 8);
-    HmmEmitWinParams P{};
-    P.packed = c->d_hmm_entries;
-    P.cov = c->d_hmm_cov;
-    P.alive = c->d_hmm_alive;
-    P.entry_begin = call.at<const uint64_t>(ec.o_eb);
-    P.entry_count = call.at<const uint32_t>(ec.o_ec);
-    P.row_win = call.at<const uint32_t>(o_rw);
-    P.gt0 = call.at<const unsigned long long>(ec.o_g0);
-    P.n_gt = n_gt;
-    P.ploidy = ploidy;
-    P.bl8 = 8 * bit_len;
-    P.ave = ave;
-    P.lower = lower;
-    P.upper = upper;
-    P.tables = call.at(ec.o_tab);
-    P.win_n_gt = call.at<const uint32_t>(o_wn);
-    P.win_haps = call.at(o_wh);
-    P.win_top_mask = call.at<const unsigned long long>(o_wm);
-    P.win_used_mask = call.at<const unsigned long long>(o_wu);
-    P.obs = ec.part->d_obs;
-    P.n_kept = call.at<uint32_t>(ec.o_nk);
-    P.flags = call.at(ec.o_fl);
-    P.n_items = n_rows;
-    call.run([&] { return launch_hmm_emissions_win(P, call.stream()); });
-    ec.part->emit_win = P;
-    return ec.finish(entry_count, n_kept_out, flags_out, out);
+    return hmm_emissions_win_impl(c, HmmForm{false, bit_len}, "HMM emissions: 1..64 genotypes of 2..8 haplotypes per window, 1..6 bytes of haplotype bits",
+                                  "HMM emissions: a row outside the entries or the windows", n_gt, ploidy, n_windows, win_n_gt, win_haps, win_top_mask, ave, lower, upper,
+                                  tables, n_rows, entry_begin, entry_count, row_win, gt0, n_kept_out, flags_out, out);
 }
 
 // vgmi_hmm_part_fix_rows for such a part: fix_mask[i] holds the haplotype IDS entry fix_j[i] loses
@@ -798,7 +942,7 @@ int vgmi_hmm_part_fix_rows_wide(vgmi_hmm_part* part, uint64_t n, const uint64_t*
 {
     if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
     if (n == 0) return VGMI_OK;
-    if (part->win_wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part's fixes are W-word masks over haplotype ids (vgmi_hmm_part_fix_rows_ploidy_wide)");
+    if (part->per_window_lists && part->wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part's fixes are W-word masks over haplotype ids (vgmi_hmm_part_fix_rows_ploidy_wide)");
     if (!part->per_window_lists) return fail(part->c, VGMI_E_INVALID, "HMM emissions: this part's fixes are masks over the `used` list (vgmi_hmm_part_fix_rows)");
     return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask);
 }
@@ -999,35 +1143,8 @@ int vgmi_hmm_tallies_select(vgmi_ctx* c, uint64_t n_rows, const uint64_t* entry_
                             const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used, uint32_t n_windows,
                             const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
 {
-    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win || !winner || !out || !unique_out)) || !pos_a || !pos_b || !win_used) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16 || n_windows < 1) return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes over 1..16 haplotypes");
-    if (!c->d_hmm_entries || !c->d_hmm_cov || !c->d_hmm_alive) return fail(c, VGMI_E_STATE, "HMM tallies: upload the entries and the sample's coverage first");
-    for (uint32_t g = 0; g < n_gt; ++g)
-        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM tallies: a genotype names a haplotype outside the list");
-    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
-        if (win_used[i] >= 48) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
-    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    if (n_rows == 0) return VGMI_OK;
-    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used), pos_ab = hmm_pos_pairs(pos_a, pos_b, n_gt);
-    HmmCall call(c);
-    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_out = call.add(n_rows * 16),
-                 o_uni = call.add(n_rows), o_pos = call.add(pos_ab.size()), o_wu = call.add(wu16.size());
-    if (int rc = call.begin("HMM tallies")) return rc;
-    call.upload(o_beg, entry_begin, n_rows * 8);
-    call.upload(o_cnt, entry_count, n_rows * 4);
-    call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_win, winner, n_rows * 4);
-    call.upload(o_pos, pos_ab.data(), pos_ab.size());
-    call.upload(o_wu, wu16.data(), wu16.size());
-    call.run([&] {
-        return launch_hmm_tally_select(c->d_hmm_entries, c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg), call.at<const uint32_t>(o_cnt),
-                                       call.at<const uint32_t>(o_rw), call.at<const uint32_t>(o_win), call.at(o_pos), call.at(o_wu), n_gt, n_rows,
-                                       call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
-    });
-    call.download(out, o_out, n_rows * 16);
-    call.download(unique_out, o_uni, n_rows);
-    HIPCHK(c, call.finish());
-    return VGMI_OK;
+    return hmm_tallies_select_impl(c, HmmForm{false, 0}, 48, n_rows, entry_begin, entry_count, row_win, winner, n_gt, pos_a, pos_b, n_used, n_windows, win_used, out,
+                                   unique_out);
 }
 
 
@@ -1038,61 +1155,8 @@ int vgmi_hmm_tallies_ploidy(vgmi_ctx* c, uint32_t ploidy, uint32_t n_gt, uint32_
                             const uint64_t* win_sel_mask, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
                             const uint32_t* winner, int use_alive, uint32_t* out, uint8_t* unique_out)
 {
-    if (!c || (n_rows && (!entry_begin || !entry_count || !winner || !out || !unique_out)) || !win_haps || !win_sel_mask) return VGMI_E_INVALID;
-    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || n_gt > 128 || n_windows < 1)
-        return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes of 2..4 haplotypes in at least one window");
-    if (!c->d_hmm_entries || !c->d_hmm_cov || (use_alive && !c->d_hmm_alive))
-        return fail(c, VGMI_E_STATE, "HMM tallies: upload the entries and the sample's coverage first");
-    if (win_n_gt)
-        for (uint32_t w = 0; w < n_windows; ++w)
-            if (win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM tallies: a window with more genotypes than the lists are wide");
-    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    if (n_rows == 0) return VGMI_OK;
-    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_out = n_rows * 8 * ploidy;
-    HmmCall call(c);
-    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(row_win ? n_rows * 4 : 0), o_win = call.add(n_rows * 4),
-                 o_out = call.add(b_out), o_uni = call.add(n_rows), o_ng = call.add(win_n_gt ? (size_t)n_windows * 4 : 0), o_haps = call.add(b_haps),
-                 o_mask = call.add((size_t)n_windows * 8);
-    if (int rc = call.begin("HMM tallies")) return rc;
-    // VGMI_HMM_TIMING=1: upload / kernel / download, milliseconds on stderr (diagnostics)
-    const bool timing = getenv("VGMI_HMM_TIMING") != nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (timing)
-        for (auto& x : ev) (void)hipEventCreate(&x);
-    if (timing) (void)hipEventRecord(ev[0], call.stream());
-    call.upload(o_beg, entry_begin, n_rows * 8);
-    call.upload(o_cnt, entry_count, n_rows * 4);
-    if (row_win) call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_win, winner, n_rows * 4);
-    if (win_n_gt) call.upload(o_ng, win_n_gt, (size_t)n_windows * 4);
-    call.upload(o_haps, win_haps, b_haps);
-    call.upload(o_mask, win_sel_mask, (size_t)n_windows * 8);
-    call.run([&] {
-        if (timing) (void)hipEventRecord(ev[1], call.stream());
-        const hipError_t e = launch_hmm_tally_ploidy(c->d_hmm_entries, c->d_hmm_cov, use_alive ? c->d_hmm_alive : nullptr, call.at<const uint64_t>(o_beg),
-                                       call.at<const uint32_t>(o_cnt), row_win ? call.at<const uint32_t>(o_rw) : nullptr, call.at<const uint32_t>(o_win),
-                                       win_n_gt ? call.at<const uint32_t>(o_ng) : nullptr, call.at(o_haps), call.at<const unsigned long long>(o_mask), n_gt, ploidy,
-                                       n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
-        if (timing) (void)hipEventRecord(ev[2], call.stream());
-        return e;
-    });
-    call.download(out, o_out, b_out);
-    call.download(unique_out, o_uni, n_rows);
-    if (timing) {
-        (void)hipEventRecord(ev[3], call.stream());
-        call.sync();
-        float up = 0, kern = 0, down = 0;
-        if (call.ok()) {
-            (void)hipEventElapsedTime(&up, ev[0], ev[1]);
-            (void)hipEventElapsedTime(&kern, ev[1], ev[2]);
-            (void)hipEventElapsedTime(&down, ev[2], ev[3]);
-        }
-        fprintf(stderr, "[vgmi] HMM tally call: %llu rows of %u haplotypes, upload %.2f ms, kernel %.2f ms, download %.2f ms\n", (unsigned long long)n_rows,
-                ploidy, up, kern, down);
-        for (auto& x : ev) (void)hipEventDestroy(x);
-    }
-    HIPCHK(c, call.finish());
-    return VGMI_OK;
+    return hmm_tallies_ploidy_impl(c, HmmForm{false, 0}, ploidy, n_gt, n_windows, win_n_gt, win_haps, win_sel_mask, n_rows, entry_begin, entry_count, row_win, winner,
+                                   use_alive, out, unique_out);
 }
 
 
@@ -1161,36 +1225,7 @@ int vgmi_hmm_entries_upload_wide(vgmi_ctx* c, const uint8_t* f, const uint8_t* b
 int vgmi_hmm_support_wide(vgmi_ctx* c, uint32_t bit_len, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t* entry_begin,
                           const uint32_t* entry_count, const uint32_t* row_win, uint32_t* support_out)
 {
-    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win)) || (n_windows && !support_out)) return VGMI_E_INVALID;
-    if (int rc = hmm_check_wide(c, "HMM support", bit_len)) return rc;
-    if (n_hap < 1 || n_hap > 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM support: more haplotypes than the haplotype bits hold");
-    if (int rc = hmm_check_rows(c, "HMM support", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    if (n_windows == 0) return VGMI_OK;
-    const size_t b_sup = (size_t)n_windows * n_hap * 4;
-    if (n_rows == 0) {
-        memset(support_out, 0, b_sup);
-        return VGMI_OK;
-    }
-    HmmCall call(c);
-    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_sup = call.add(b_sup);
-    if (int rc = call.begin("HMM support")) return rc;
-    HmmCallTimes tm;
-    tm.mark(0, call.stream());
-    call.upload(o_beg, entry_begin, n_rows * 8);
-    call.upload(o_cnt, entry_count, n_rows * 4);
-    call.upload(o_win, row_win, n_rows * 4);
-    call.zero(o_sup, b_sup);
-    tm.mark(1, call.stream());
-    call.run([&] {
-        return launch_hmm_support_wide(c->hmm_words, c->d_hmm_f, c->d_hmm_bits, c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg),
-                                       call.at<const uint32_t>(o_cnt), call.at<const uint32_t>(o_win), n_rows, n_hap, call.at<uint32_t>(o_sup), call.stream());
-    });
-    tm.mark(2, call.stream());
-    call.download(support_out, o_sup, b_sup);
-    tm.mark(3, call.stream());
-    tm.report(call, "support", n_rows, bit_len);
-    HIPCHK(c, call.finish());
-    return VGMI_OK;
+    return hmm_support_impl(c, HmmForm{true, bit_len}, n_hap, n_windows, n_rows, entry_begin, entry_count, row_win, support_out);
 }
 
 int vgmi_hmm_emissions_select_wide(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_windows,
@@ -1205,101 +1240,18 @@ int vgmi_hmm_emissions_select_wide(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, 
     if (int rc = hmm_check_wide(c, "HMM emissions", bit_len)) return rc;
     for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
         if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a selected haplotype outside the haplotype bits");
-    HmmEmitWideParams Q{};
-    HmmEmitParams& P = Q.e;
-    for (uint32_t g = 0; g < n_gt; ++g) {
-        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype names a haplotype outside the list");
-        P.pos_a[g] = pos_a[g];
-        P.pos_b[g] = pos_b[g];
-    }
-    if (int rc = hmm_check_rows(c, "HMM emissions", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    *out = nullptr;
-    const uint32_t W = c->hmm_words;
-    HmmEmitCall ec(c, n_rows, 2, 2);
-    HmmCall& call = ec.call;
-    const size_t o_rw = call.add(n_rows * 4), o_wu = call.add((size_t)n_windows * 16), o_wm = call.add((size_t)n_windows * 8 * W);
-    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used);
-    if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
-    HmmCallTimes tm;
-    tm.mark(0, call.stream());
-    call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_wu, wu16.data(), wu16.size());
-    call.upload(o_wm, win_top_mask, (size_t)n_windows * 8 * W);
-    Q.f = c->d_hmm_f;
-    Q.bits = c->d_hmm_bits;
-    P.cov = c->d_hmm_cov;
-    P.alive = c->d_hmm_alive;
-    P.entry_begin = call.at<const uint64_t>(ec.o_eb);
-    P.entry_count = call.at<const uint32_t>(ec.o_ec);
-    P.gt0 = call.at<const uint16_t>(ec.o_g0);
-    P.row_lo = 0;
-    P.n_gt = n_gt;
-    P.n_used = n_used;
-    P.bl8 = 8 * bit_len;
-    P.ploidy = 2;
-    P.ave = ave;
-    P.lower = lower;
-    P.upper = upper;
-    P.tables = call.at(ec.o_tab);
-    P.obs = ec.part->d_obs;
-    P.n_kept = call.at<uint32_t>(ec.o_nk);
-    P.flags = call.at(ec.o_fl);
-    P.row_win = call.at<const uint32_t>(o_rw);
-    P.win_used = call.at(o_wu);
-    P.win_top_mask = call.at<const unsigned long long>(o_wm);
-    tm.mark(1, call.stream());
-    call.run([&] { return launch_hmm_emissions_wide(Q, W, n_rows, call.stream()); });
-    tm.mark(2, call.stream());
-    ec.part->wide_words = W;
-    ec.part->emit_wide = Q;
-    if (tm.on) {      // (finish() fetches them again: the figure is the diagnostics')
-        call.download(n_kept_out, ec.o_nk, n_rows * 4);
-        call.download(flags_out, ec.o_fl, n_rows);
-        tm.mark(3, call.stream());
-        tm.report(call, "emission", n_rows, bit_len);
-    }
-    return ec.finish(entry_count, n_kept_out, flags_out, out);
+    const HmmSelect sel{n_windows, win_used, win_top_mask, row_win};
+    return hmm_emissions_impl(c, HmmForm{true, bit_len}, n_gt, 2, n_used, win_used, hmm_pos_pairs(pos_a, pos_b, n_gt).data(), 0, ave, lower, upper, tables, n_rows,
+                              entry_begin, entry_count, gt0, n_kept_out, flags_out, out, &sel);
 }
 
 int vgmi_hmm_tallies_select_wide(vgmi_ctx* c, uint32_t bit_len, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
                                  const uint32_t* row_win, const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used,
                                  uint32_t n_windows, const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
 {
-    if (!c || (n_rows && (!entry_begin || !entry_count || !row_win || !winner || !out || !unique_out)) || !pos_a || !pos_b || !win_used) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16 || n_windows < 1) return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes over 1..16 haplotypes");
-    if (int rc = hmm_check_wide(c, "HMM tallies", bit_len)) return rc;
-    for (uint32_t g = 0; g < n_gt; ++g)
-        if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM tallies: a genotype names a haplotype outside the list");
-    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
-        if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
-    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    if (n_rows == 0) return VGMI_OK;
-    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used), pos_ab = hmm_pos_pairs(pos_a, pos_b, n_gt);
-    HmmCall call(c);
-    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_out = call.add(n_rows * 16),
-                 o_uni = call.add(n_rows), o_pos = call.add(pos_ab.size()), o_wu = call.add(wu16.size());
-    if (int rc = call.begin("HMM tallies")) return rc;
-    HmmCallTimes tm;
-    tm.mark(0, call.stream());
-    call.upload(o_beg, entry_begin, n_rows * 8);
-    call.upload(o_cnt, entry_count, n_rows * 4);
-    call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_win, winner, n_rows * 4);
-    call.upload(o_pos, pos_ab.data(), pos_ab.size());
-    call.upload(o_wu, wu16.data(), wu16.size());
-    tm.mark(1, call.stream());
-    call.run([&] {
-        return launch_hmm_tally_wide(c->hmm_words, c->d_hmm_f, c->d_hmm_bits, c->d_hmm_cov, c->d_hmm_alive, call.at<const uint64_t>(o_beg),
-                                     call.at<const uint32_t>(o_cnt), call.at<const uint32_t>(o_rw), call.at<const uint32_t>(o_win), call.at(o_pos), call.at(o_wu),
-                                     n_gt, n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
-    });
-    tm.mark(2, call.stream());
-    call.download(out, o_out, n_rows * 16);
-    call.download(unique_out, o_uni, n_rows);
-    tm.mark(3, call.stream());
-    tm.report(call, "tally", n_rows, bit_len);
-    HIPCHK(c, call.finish());
-    return VGMI_OK;
+    const HmmForm form{true, bit_len};
+    return hmm_tallies_select_impl(c, form, form.n_ids(), n_rows, entry_begin, entry_count, row_win, winner, n_gt, pos_a, pos_b, n_used, n_windows, win_used, out,
+                                   unique_out);
 }
 
 // ---- a POLYPLOID sample over such a panel (vgmi.h): vgmi_hmm_emissions_select_ploidy and vgmi_hmm_tallies_ploidy with every mask over
@@ -1309,130 +1261,25 @@ int vgmi_hmm_emissions_select_ploidy_wide(vgmi_ctx* c, uint32_t n_gt, uint32_t p
                                           uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint64_t* gt0,
                                           uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
 {
-    if (!c || !tables || !out) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > 64 || ploidy < 2 || ploidy > 8) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..64 genotypes of 2..8 haplotypes per window");
-    if (n_windows < 1 || !win_n_gt || !win_haps || !win_top_mask) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their genotype lists");
-    if (n_rows && (!entry_begin || !entry_count || !row_win || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
-    if (int rc = hmm_check_wide(c, "HMM emissions", bit_len)) return rc;
-    const uint32_t W = c->hmm_words, n_ids = 8 * bit_len - 1;      // the last bit is no haplotype
-    std::vector<uint64_t> used_mask((size_t)n_windows * W, 0);
-    for (uint32_t w = 0; w < n_windows; ++w) {
-        if (win_n_gt[w] < 1 || win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM emissions: a window's genotype count outside 1..n_gt");
-        for (size_t i = 0; i < (size_t)win_n_gt[w] * ploidy; ++i) {
-            const uint32_t hap = win_haps[(size_t)w * n_gt * ploidy + i];
-            if (hap >= n_ids) return fail(c, VGMI_E_INVALID, "HMM emissions: a genotype's haplotype outside the haplotype bits");
-            used_mask[(size_t)w * W + (hap >> 6)] |= 1ull << (hap & 63u);
-        }
-        for (uint32_t i = 0; i < W; ++i) {
-            const uint64_t hap_bits = n_ids >= 64u * (i + 1u) ? ~0ull : n_ids <= 64u * i ? 0ull : (1ull << (n_ids - 64u * i)) - 1ull;
-            if (win_top_mask[(size_t)w * W + i] & ~hap_bits) return fail(c, VGMI_E_INVALID, "HMM emissions: a drawn haplotype outside the haplotype bits");
-        }
-    }
-    if (int rc = hmm_check_rows(c, "HMM emissions", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    *out = nullptr;
-    HmmEmitCall ec(c, n_rows, (size_t)8 * W, ploidy);
-    HmmCall& call = ec.call;
-    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_mask = (size_t)n_windows * 8 * W;      // row_win | win_n_gt | win_haps | win_top_mask | win_used_mask
-    const size_t o_rw = call.add(n_rows * 4), o_wn = call.add((size_t)n_windows * 4), o_wh = call.add(b_haps), o_wm = call.add(b_mask), o_wu = call.add(b_mask);
-    if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
-    HmmCallTimes tm;
-    tm.mark(0, call.stream());
-    call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_wn, win_n_gt, (size_t)n_windows * 4);
-    call.upload(o_wh, win_haps, b_haps);
-    call.upload(o_wm, win_top_mask, b_mask);
-    call.upload(o_wu, used_mask.data(), b_mask);
-    HmmEmitWinWideParams Q{};
-    HmmEmitWinParams& P = Q.e;
-    Q.f = c->d_hmm_f;
-    Q.bits = c->d_hmm_bits;
-    P.cov = c->d_hmm_cov;
-    P.alive = c->d_hmm_alive;
-    P.entry_begin = call.at<const uint64_t>(ec.o_eb);
-    P.entry_count = call.at<const uint32_t>(ec.o_ec);
-    P.row_win = call.at<const uint32_t>(o_rw);
-    P.gt0 = call.at<const unsigned long long>(ec.o_g0);
-    P.n_gt = n_gt;
-    P.ploidy = ploidy;
-    P.bl8 = 8 * bit_len;
-    P.ave = ave;
-    P.lower = lower;
-    P.upper = upper;
-    P.tables = call.at(ec.o_tab);
-    P.win_n_gt = call.at<const uint32_t>(o_wn);
-    P.win_haps = call.at(o_wh);
-    P.win_top_mask = call.at<const unsigned long long>(o_wm);
-    P.win_used_mask = call.at<const unsigned long long>(o_wu);
-    P.obs = ec.part->d_obs;
-    P.n_kept = call.at<uint32_t>(ec.o_nk);
-    P.flags = call.at(ec.o_fl);
-    P.n_items = n_rows;
-    tm.mark(1, call.stream());
-    call.run([&] { return launch_hmm_emissions_win_wide(Q, W, call.stream()); });
-    tm.mark(2, call.stream());
-    ec.part->win_wide_words = W;
-    ec.part->emit_win_wide = Q;
-    if (tm.on) {      // (finish() fetches them again: the figure is the diagnostics')
-        call.download(n_kept_out, ec.o_nk, n_rows * 4);
-        call.download(flags_out, ec.o_fl, n_rows);
-        tm.mark(3, call.stream());
-        tm.report(call, "emission (a genotype list per window)", n_rows, bit_len);
-    }
-    return ec.finish(entry_count, n_kept_out, flags_out, out);
+    return hmm_emissions_win_impl(c, HmmForm{true, bit_len}, "HMM emissions: 1..64 genotypes of 2..8 haplotypes per window", "HMM emissions", n_gt, ploidy, n_windows,
+                                  win_n_gt, win_haps, win_top_mask, ave, lower, upper, tables, n_rows, entry_begin, entry_count, row_win, gt0, n_kept_out, flags_out, out);
 }
 
 // the second launch of such a part: fix_mask holds W words of haplotype ids per fix
 int vgmi_hmm_part_fix_rows_ploidy_wide(vgmi_hmm_part* part, uint64_t n, const uint64_t* rows, const uint32_t* fix_off, const uint32_t* fix_j, const uint64_t* fix_mask)
 {
     if (!part || (n && (!rows || !fix_off))) return VGMI_E_INVALID;
-    if (!part->win_wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part is none of vgmi_hmm_emissions_select_ploidy_wide");
+    if (!part->per_window_lists || !part->wide_words) return fail(part->c, VGMI_E_STATE, "HMM emissions: this part is none of vgmi_hmm_emissions_select_ploidy_wide");
     if (n == 0) return VGMI_OK;
-    return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask, part->win_wide_words);
+    return hmm_fix_rows(part, n, rows, fix_off, fix_j, fix_mask, part->wide_words);
 }
 
 int vgmi_hmm_tallies_ploidy_wide(vgmi_ctx* c, uint32_t bit_len, uint32_t ploidy, uint32_t n_gt, uint32_t n_windows, const uint32_t* win_n_gt, const uint8_t* win_haps,
                                  const uint64_t* win_sel_mask, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
                                  const uint32_t* winner, int use_alive, uint32_t* out, uint8_t* unique_out)
 {
-    if (!c || (n_rows && (!entry_begin || !entry_count || !winner || !out || !unique_out)) || !win_haps || !win_sel_mask) return VGMI_E_INVALID;
-    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || n_gt > 128 || n_windows < 1)
-        return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes of 2..4 haplotypes in at least one window");
-    if (int rc = hmm_check_wide(c, "HMM tallies", bit_len)) return rc;
-    if (win_n_gt)
-        for (uint32_t w = 0; w < n_windows; ++w)
-            if (win_n_gt[w] > n_gt) return fail(c, VGMI_E_INVALID, "HMM tallies: a window with more genotypes than the lists are wide");
-    if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
-    if (n_rows == 0) return VGMI_OK;
-    const uint32_t W = c->hmm_words;
-    const size_t b_haps = (size_t)n_windows * n_gt * ploidy, b_out = n_rows * 8 * ploidy, b_mask = (size_t)n_windows * 8 * W;
-    HmmCall call(c);
-    const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(row_win ? n_rows * 4 : 0), o_win = call.add(n_rows * 4),
-                 o_out = call.add(b_out), o_uni = call.add(n_rows), o_ng = call.add(win_n_gt ? (size_t)n_windows * 4 : 0), o_haps = call.add(b_haps),
-                 o_mask = call.add(b_mask);
-    if (int rc = call.begin("HMM tallies")) return rc;
-    HmmCallTimes tm;
-    tm.mark(0, call.stream());
-    call.upload(o_beg, entry_begin, n_rows * 8);
-    call.upload(o_cnt, entry_count, n_rows * 4);
-    if (row_win) call.upload(o_rw, row_win, n_rows * 4);
-    call.upload(o_win, winner, n_rows * 4);
-    if (win_n_gt) call.upload(o_ng, win_n_gt, (size_t)n_windows * 4);
-    call.upload(o_haps, win_haps, b_haps);
-    call.upload(o_mask, win_sel_mask, b_mask);
-    tm.mark(1, call.stream());
-    call.run([&] {
-        return launch_hmm_tally_ploidy_wide(W, c->d_hmm_f, c->d_hmm_bits, c->d_hmm_cov, use_alive ? c->d_hmm_alive : nullptr, call.at<const uint64_t>(o_beg),
-                                            call.at<const uint32_t>(o_cnt), row_win ? call.at<const uint32_t>(o_rw) : nullptr, call.at<const uint32_t>(o_win),
-                                            win_n_gt ? call.at<const uint32_t>(o_ng) : nullptr, call.at(o_haps), call.at<const unsigned long long>(o_mask), n_gt,
-                                            ploidy, 8 * bit_len, n_rows, call.at<uint32_t>(o_out), call.at(o_uni), call.stream());
-    });
-    tm.mark(2, call.stream());
-    call.download(out, o_out, b_out);
-    call.download(unique_out, o_uni, n_rows);
-    tm.mark(3, call.stream());
-    tm.report(call, "tally (polyploid)", n_rows, bit_len);
-    HIPCHK(c, call.finish());
-    return VGMI_OK;
+    return hmm_tallies_ploidy_impl(c, HmmForm{true, bit_len}, ploidy, n_gt, n_windows, win_n_gt, win_haps, win_sel_mask, n_rows, entry_begin, entry_count, row_win,
+                                   winner, use_alive, out, unique_out);
 }
 
 int vgmi_hmm_part_fetch(vgmi_hmm_part* part, void* obs_out)

@@ -579,65 +579,148 @@ __device__ __forceinline__ void hmm_stage_tables(const uint8_t* tables, uint32_t
     __syncthreads();
 }
 
-// SELECT (vgmi_hmm_emissions_select): -n picks fewer haplotypes than the panel has, so every window has drawn its own.  The row names its
-// window, the window supplies `used` and the mask (ids up to 46: every shift of the bits is 64 bits wide); an entry that is no longer in
-// its node's list is passed over, and an entry no selected haplotype carries LEAVES the list here, for good (src/genotype.cpp:673-686,
-// 815-818: the next window, the next sample score what is left).  Every lane takes the same decisions; lane 0 writes them down.
+// ---- how a node-list entry is read: two storage forms, one kernel body per family -----------------------------------------------------
+// packed (vgmi_hmm_entries_upload): one 64-bit word per entry, multiplicity << 8 | haplotype bits << 16 -- up to six bytes of bits.
+// wide (vgmi_hmm_entries_upload_wide, panels of 48 to 254 haplotypes): the multiplicity byte f[e] and the bit vector as it stands in the
+// graph, little-endian in W = 1, 2 or 4 64-bit words, zero-padded, entry-major: bits[e * W + i] -- one contiguous 8, 16 or 32-byte load.
+// The last bit of the vector (bit bl8 - 1) is the flag it is everywhere, never a haplotype.
+// A reader E states, for entry e:
+//   E::W            words of haplotype bits per entry, and per mask over haplotype ids (a window's, a row's gt0, a fix's)
+//   E::kMaxHap      the most haplotypes a panel has in this form (the support kernel's counters in LDS)
+//   E::kDiploidOnly the place form of the emissions is launched for pairs of selected haplotypes only (no pos_more, no whole lists)
+//   head(e)         what ONE load of the entry gives before anything is known about it: packed the word, wide nothing
+//   mult(h, e)      the multiplicity: out of the head, or f[e]
+//   word(h, e, i)   word i of the haplotype bits: out of the head, or bits[e * W + i]
+//   carries(h, e, hap)  one haplotype's bit when only that is wanted (the tallies): out of the head, or the one word that holds it
+//   hap_mask(n, i)  word i of the mask of the first n haplotypes
+// So a packed kernel loads an entry once, wherever the body asks for its parts, and a wide one loads each part where it is asked for.
+// A register array of W words is only ever indexed by an unrolled loop's counter; the word of haplotype `hap` is picked by a chain
+// over W (hmm_pick_word) or loaded on its own (the tallies).  (The polyploid tally is not read through a reader: see there.)  Row, window and every haplotype id are wavefront-uniform where the
+// kernels say so, in either form: the words of an entry, the window's mask and the choice of a word stay on the scalar side.
+struct HmmPackedEntries {
+    static constexpr uint32_t W = 1, kMaxHap = 48;
+    static constexpr bool kDiploidOnly = false;
+    const unsigned long long* __restrict__ words;
+    struct Head {
+        unsigned long long word;
+    };
+    static __device__ __forceinline__ HmmPackedEntries of(const uint8_t*, const unsigned long long* words) { return HmmPackedEntries{words}; }
+    __device__ __forceinline__ Head head(uint64_t e) const { return Head{words[e]}; }
+    __device__ __forceinline__ uint32_t mult(const Head& h, uint64_t) const { return (uint32_t)(h.word >> 8) & 0xFFu; }
+    __device__ __forceinline__ unsigned long long word(const Head& h, uint64_t, uint32_t) const { return h.word >> 16; }
+    __device__ __forceinline__ bool carries(const Head& h, uint64_t, uint32_t hap) const { return ((h.word >> 16) >> hap) & 1ull; }
+    static __device__ __forceinline__ unsigned long long hap_mask(uint32_t n, uint32_t) { return (1ull << n) - 1ull; }      // n <= 48
+};
+
+template <uint32_t WORDS>
+struct HmmWideEntries {
+    static constexpr uint32_t W = WORDS, kMaxHap = 256;
+    static constexpr bool kDiploidOnly = true;
+    const uint8_t* __restrict__ f;
+    const unsigned long long* __restrict__ bits;
+    struct Head {};
+    static __device__ __forceinline__ HmmWideEntries of(const uint8_t* f, const unsigned long long* words) { return HmmWideEntries{f, words}; }
+    __device__ __forceinline__ Head head(uint64_t) const { return Head{}; }
+    __device__ __forceinline__ uint32_t mult(const Head&, uint64_t e) const { return f[e]; }
+    __device__ __forceinline__ unsigned long long word(const Head&, uint64_t e, uint32_t i) const { return bits[e * W + i]; }
+    __device__ __forceinline__ bool carries(const Head&, uint64_t e, uint32_t hap) const { return (bits[e * W + (W > 1u ? hap >> 6 : 0u)] >> (hap & 63u)) & 1ull; }
+    static __device__ __forceinline__ unsigned long long hap_mask(uint32_t n, uint32_t i)      // n <= 64 W - 1
+    {
+        return n >= 64u * (i + 1u) ? ~0ull : n <= 64u * i ? 0ull : (1ull << (n - 64u * i)) - 1ull;
+    }
+};
+
+template <uint32_t W>
+__device__ __forceinline__ unsigned long long hmm_pick_word(const unsigned long long (&b)[W], uint32_t wi)
+{
+    if (W == 1u) return b[0];
+    unsigned long long w = 0;      // (masks, not selects: a chain of selects over an array is what the compiler turns back into an index)
+#pragma unroll
+    for (uint32_t i = 0; i < W; ++i) w |= b[i] & (0ull - (unsigned long long)(wi == i));
+    return w;
+}
+
+// bit `id` of W words
+template <uint32_t W>
+__device__ __forceinline__ uint32_t hmm_bit_of(const unsigned long long (&b)[W], uint32_t id)
+{
+    if (W == 1u) return (uint32_t)(b[0] >> id) & 1u;      // (id < 64: no word to choose, no bits to mask off the shift)
+    return (uint32_t)(hmm_pick_word<W>(b, id >> 6) >> (id & 63u)) & 1u;
+}
+
+// SELECT (vgmi_hmm_emissions_select, _wide): -n picks fewer haplotypes than the panel has, so every window has drawn its own.  The row names
+// its window, the window supplies `used` and the W-word mask; an entry that is no longer in its node's list is passed over, and an entry no
+// selected haplotype carries -- no word of it meets the mask -- LEAVES the list here, for good (src/genotype.cpp:673-686, 815-818: the next
+// window, the next sample score what is left).  Every lane takes the same decisions; lane 0 writes them down.  From `om` -- at most 16 bits
+// over the places of the list -- on nothing depends on the entries' form.
 // MAXP: the most haplotypes a genotype may have.  The tables are sized by it -- 4: 1 280 terms, 15 360 bytes of LDS, what a diploid, tri- or
 // tetraploid launch has always asked for; 8: 2 304 terms, 27 648 bytes, for ploidy 5 .. 8 only (a workgroup per row: a larger table for
 // everyone would cost every diploid launch workgroups per CU).
-template <bool SELECT, uint32_t MAXP>
+template <class E, bool SELECT, uint32_t MAXP>
 __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
 {
+    constexpr uint32_t W = E::W;
+    static_assert(SELECT || W == 1u, "one mask for every row is one word");
     __shared__ uint64_t s_tm[(MAXP + 1u) * 256u];      // (ploidy + 1) x 256 terms: up to MAXP haplotypes per genotype
     __shared__ int32_t s_te[(MAXP + 1u) * 256u];
+    const uint32_t ploidy = E::kDiploidOnly ? 2u : P.ploidy;
     const uint32_t g = threadIdx.x;
-    hmm_stage_tables<128>(P.tables, P.ploidy, s_tm, s_te);
+    hmm_stage_tables<128>(P.tables, ploidy, s_tm, s_te);
     const uint64_t rowi = P.fix_rows ? P.fix_rows[blockIdx.x] : P.row_lo + blockIdx.x;
     uint32_t fp = P.fix_rows ? P.fix_off[blockIdx.x] : 0u;
     const uint32_t fe = P.fix_rows ? P.fix_off[blockIdx.x + 1] : 0u;
     const uint64_t e0 = P.entry_begin[rowi];
     const uint32_t cnt = P.entry_count[rowi], gt0 = P.gt0[rowi];
     const bool active = g < P.n_gt;
-    unsigned long long top_mask = P.top_mask;
+    unsigned long long top_mask[W];
     const uint8_t* wused = nullptr;
     if (SELECT) {
         const uint32_t w = P.row_win[rowi];
-        top_mask = P.win_top_mask[w];
+#pragma unroll
+        for (uint32_t i = 0; i < W; ++i) top_mask[i] = P.win_top_mask[(size_t)w * W + i];
         wused = P.win_used + (size_t)w * 16u;
+    } else {
+        top_mask[0] = P.top_mask;
     }
     const uint32_t pa = P.pos_a[active ? g : 0u], pb = P.pos_b[active ? g : 0u];
-    const uint32_t pc = P.ploidy > 2u ? P.pos_more[0][active ? g : 0u] : 0u, pd = P.ploidy > 3u ? P.pos_more[1][active ? g : 0u] : 0u;
+    const uint32_t pc = ploidy > 2u ? P.pos_more[0][active ? g : 0u] : 0u, pd = ploidy > 3u ? P.pos_more[1][active ? g : 0u] : 0u;
     uint32_t pe[MAXP > 4u ? MAXP - 4u : 1u] = {0};      // the fifth to the eighth haplotype's places (unrolled: the array stays in registers)
     if (MAXP > 4u) {
 #pragma unroll
         for (uint32_t q = 4; q < MAXP; ++q)
-            if (q < P.ploidy) pe[q - 4u] = P.pos_more[q - 2u][active ? g : 0u];
+            if (q < ploidy) pe[q - 4u] = P.pos_more[q - 2u][active ? g : 0u];
     }
     VgN80 prod;
     prod.m = 1ULL << 63;      // 1.0L
     prod.e = VG_X80_BIAS;
     uint32_t kept = 0, flag = 0;
+    const E ent = E::of(P.ent.f, P.ent.words);
     for (uint32_t j = 0; j < cnt; ++j) {
-        if (SELECT && P.alive[e0 + j] == 0) continue;      // pruned by an earlier window's or sample's selection
-        const unsigned long long w = P.packed[e0 + j];
-        const uint32_t c = P.cov[e0 + j], f = (uint32_t)(w >> 8) & 0xFFu;
-        const unsigned long long bits = w >> 16;
-        const uint32_t lb = (uint32_t)(bits >> (P.bl8 - 1u)) & 1u;
-        if ((bits & top_mask) == 0) {
+        const uint64_t e = e0 + j;
+        if (SELECT && P.alive[e] == 0) continue;      // pruned by an earlier window's or sample's selection
+        const typename E::Head hd = ent.head(e);
+        unsigned long long b[W], met = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < W; ++i) {
+            b[i] = ent.word(hd, e, i);
+            met |= b[i] & top_mask[i];
+        }
+        const uint32_t c = P.cov[e], f = ent.mult(hd, e);
+        if (met == 0) {
             if (SELECT) {
-                if (g == 0 && !P.fix_rows) P.alive[e0 + j] = 0;      // the prune
+                if (g == 0 && !P.fix_rows) P.alive[e] = 0;      // the prune
             } else {
                 flag |= 2u;      // the host would drop it from the list: this path does not prune
             }
             continue;
         }
         ++kept;
+        const uint32_t lb = hmm_bit_of<W>(b, P.bl8 - 1u);
         const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
         uint32_t om = 0;
         for (uint32_t p = 0; p < P.n_used; ++p) {
             const uint32_t hap = SELECT ? (uint32_t)wused[p] : (uint32_t)P.used[p];
-            const uint32_t one = (in_interval && ((gt0 >> p) & 1u)) ? 1u : (uint32_t)((bits >> hap) & 1ull);
+            const uint32_t one = (in_interval && ((gt0 >> p) & 1u)) ? 1u : hmm_bit_of<W>(b, hap);
             om |= one << p;
         }
         if ((double)c < P.lower && f >= 2u && om != 0) flag |= 1u;
@@ -647,12 +730,12 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
         }
         const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
         uint32_t h = ((om >> pa) & 1u) + ((om >> pb) & 1u);
-        if (P.ploidy > 2u) h += (om >> pc) & 1u;
-        if (P.ploidy > 3u) h += (om >> pd) & 1u;
+        if (ploidy > 2u) h += (om >> pc) & 1u;
+        if (ploidy > 3u) h += (om >> pd) & 1u;
         if (MAXP > 4u) {
 #pragma unroll
             for (uint32_t q = 4; q < MAXP; ++q)
-                if (q < P.ploidy) h += (om >> pe[q - 4u]) & 1u;
+                if (q < ploidy) h += (om >> pe[q - 4u]) & 1u;
         }
         const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
         const uint32_t ti = h * 256u + cc;
@@ -668,25 +751,27 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     }
 }
 
-// ---- ... with a genotype LIST per window (vgmi_hmm_emissions_select_ploidy): a polyploid sample under -n ----------------------------
+// ---- ... with a genotype LIST per window (vgmi_hmm_emissions_select_ploidy, _wide): a polyploid sample under -n ------------------------
 // The genotypes of a window are the blocks of `ploidy` consecutive haplotypes that hold a drawn haplotype (src/genotype.cpp:846-873): 1 ..
 // -n of them, another number in every window, over up to -n x ploidy haplotypes of which only the drawn ones decide the prune.  So
 // nothing is a place in a 16-entry `used` list here: genotype g of window w names its haplotypes by id (win_haps), and every mask -- the
-// drawn haplotypes (the prune), the blocks' haplotypes (who counts as carrying), the row's reference-allele bits, a fix -- is 64 bits over
-// haplotype ids.  Which haplotypes carry an entry is then two mask operations for the whole wavefront instead of a loop over places, and
-// a lane's copy number is the sum over its `ploidy` ids with repeats (haplotype 0 stands several times in a truncated or all-zero block
-// and counts each time, as the host's flat list does).
+// drawn haplotypes (the prune), the blocks' haplotypes (who counts as carrying), the row's reference-allele bits, a fix -- is W words over
+// haplotype ids, and so is `om`, the haplotypes that count as carrying an entry.  That is a few mask operations for the whole wavefront
+// instead of a loop over places, and a lane's copy number is the sum over its `ploidy` ids with repeats (haplotype 0 stands several times
+// in a truncated or all-zero block and counts each time, as the host's flat list does).  Only a lane's ids differ: it picks the word of
+// each id out of `om` by hmm_pick_word's masks (an indexed read of `om` is what becomes scratch).
 // A wavefront takes a row: the lists are 1 .. 16 genotypes long, a second wavefront per row would idle entirely; lanes beyond the window's
 // count idle through the entry loop (and write a zero score: the part's rows are n_gt wide).  Every decision about an entry -- dead,
-// pruned, flagged, fixed -- is the same for the whole wavefront: the row is made wavefront-uniform (readfirstlane), so the entry's word,
+// pruned, flagged, fixed -- is the same for the whole wavefront: the row is made wavefront-uniform (readfirstlane), so the entry's words,
 // coverage and alive byte are scalar loads and the branches are uniform.  The term tables, (ploidy + 1) x 256 entries of 12 bytes, are
 // staged in LDS once per workgroup of four wavefronts, which takes kWinRows rows: a workgroup per row (the kernel above) would spend more
 // on staging 15 KB than on a list of some fifty entries.
 // MAXP as in hmm_emissions_kernel: 15 360 bytes of tables for ploidy 2 .. 4, 27 648 for ploidy 5 .. 8.
 constexpr uint32_t kWinRows = 16;
-template <uint32_t MAXP>
+template <class E, uint32_t MAXP>
 __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams P)
 {
+    constexpr uint32_t W = E::W;
     __shared__ uint64_t s_tm[(MAXP + 1u) * 256u];
     __shared__ int32_t s_te[(MAXP + 1u) * 256u];
     hmm_stage_tables<256>(P.tables, P.ploidy, s_tm, s_te);      // (its barrier is the only one: from here on the wavefronts go their own ways)
@@ -699,14 +784,20 @@ __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams
         const uint32_t fe = P.fix_rows ? P.fix_off[item + 1] : 0u;
         const uint64_t e0 = P.entry_begin[rowi];
         const uint32_t cnt = P.entry_count[rowi];
-        const unsigned long long gt0 = P.gt0[rowi];
+        unsigned long long gt0[W], top_mask[W], used_mask[W];
+#pragma unroll
+        for (uint32_t i = 0; i < W; ++i) gt0[i] = P.gt0[rowi * W + i];
         const uint32_t w = P.row_win[rowi];
-        const unsigned long long top_mask = P.win_top_mask[w], used_mask = P.win_used_mask[w];
+#pragma unroll
+        for (uint32_t i = 0; i < W; ++i) {
+            top_mask[i] = P.win_top_mask[(size_t)w * W + i];
+            used_mask[i] = P.win_used_mask[(size_t)w * W + i];
+        }
         const uint32_t n_here = P.win_n_gt[w];
         const bool active = g < n_here;
         uint32_t hap[MAXP] = {0};
         if (active) {
-            if (MAXP > 4u) {
+            if (MAXP > 4u || W > 1u) {
 #pragma unroll
                 for (uint32_t q = 0; q < MAXP; ++q)      // (unrolled with the places beyond `ploidy` left out: the array stays in registers)
                     if (q < P.ploidy) hap[q] = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
@@ -718,33 +809,46 @@ __global__ __launch_bounds__(256) void hmm_emissions_win_kernel(HmmEmitWinParams
         prod.m = 1ULL << 63;      // 1.0L
         prod.e = VG_X80_BIAS;
         uint32_t kept = 0, flag = 0;
+        const E ent = E::of(P.ent.f, P.ent.words);
         for (uint32_t j = 0; j < cnt; ++j) {
-            if (P.alive[e0 + j] == 0) continue;      // pruned by an earlier window's or sample's selection
-            const unsigned long long word = P.packed[e0 + j];
-            const uint32_t c = P.cov[e0 + j], f = (uint32_t)(word >> 8) & 0xFFu;
-            const unsigned long long bits = word >> 16;
-            const uint32_t lb = (uint32_t)(bits >> (P.bl8 - 1u)) & 1u;
-            if ((bits & top_mask) == 0) {
-                if (g == 0 && !P.fix_rows) P.alive[e0 + j] = 0;      // the prune: by the DRAWN haplotypes
+            const uint64_t e = e0 + j;
+            if (P.alive[e] == 0) continue;      // pruned by an earlier window's or sample's selection
+            const typename E::Head hd = ent.head(e);
+            unsigned long long b[W], met = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < W; ++i) {
+                b[i] = ent.word(hd, e, i);
+                met |= b[i] & top_mask[i];
+            }
+            const uint32_t c = P.cov[e], f = ent.mult(hd, e);
+            if (met == 0) {
+                if (g == 0 && !P.fix_rows) P.alive[e] = 0;      // the prune: by the DRAWN haplotypes
                 continue;
             }
             ++kept;
+            const uint32_t lb = hmm_bit_of<W>(b, P.bl8 - 1u);
             const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
-            unsigned long long om = (bits | (in_interval ? gt0 : 0ull)) & used_mask;      // the score: over the BLOCKS' haplotypes
-            if ((double)c < P.lower && f >= 2u && om != 0) flag |= 1u;
+            unsigned long long om[W], any = 0;      // the score: over the BLOCKS' haplotypes
+#pragma unroll
+            for (uint32_t i = 0; i < W; ++i) {
+                om[i] = (b[i] | (in_interval ? gt0[i] : 0ull)) & used_mask[i];
+                any |= om[i];
+            }
+            if ((double)c < P.lower && f >= 2u && any != 0) flag |= 1u;
             if (fp < fe && P.fix_j[fp] == j) {      // (the second launch: haplotypes whose sequence does not hold this k-mer do not carry it)
-                om &= ~P.fix_mask[fp];
+#pragma unroll
+                for (uint32_t i = 0; i < W; ++i) om[i] &= ~P.fix_mask[(size_t)fp * W + i];
                 ++fp;
             }
             if (!active) continue;
             const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
-            uint32_t h = (uint32_t)((om >> hap[0]) & 1ull) + (uint32_t)((om >> hap[1]) & 1ull);
-            if (P.ploidy > 2u) h += (uint32_t)((om >> hap[2]) & 1ull);
-            if (P.ploidy > 3u) h += (uint32_t)((om >> hap[3]) & 1ull);
+            uint32_t h = hmm_bit_of<W>(om, hap[0]) + hmm_bit_of<W>(om, hap[1]);
+            if (P.ploidy > 2u) h += hmm_bit_of<W>(om, hap[2]);
+            if (P.ploidy > 3u) h += hmm_bit_of<W>(om, hap[3]);
             if (MAXP > 4u) {
 #pragma unroll
                 for (uint32_t q = 4; q < MAXP; ++q)      // (a repeated id counts at every place it stands)
-                    if (q < P.ploidy) h += (uint32_t)((om >> hap[q]) & 1ull);
+                    if (q < P.ploidy) h += hmm_bit_of<W>(om, hap[q]);
             }
             const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
             const uint32_t ti = h * 256u + cc;
@@ -774,17 +878,18 @@ __global__ __launch_bounds__(128) void hmm_scatter_rows_kernel(uint8_t* obs, con
 // Per row (node) with a called genotype g = (hap_a[g], hap_b[g]): over the node's entries, how many k-mers each called haplotype
 // carries and the sum of their coverages (the caller divides), and how many k-mers have multiplicity <= 1 (clamped at 255).  A
 // haplotype outside the panel or the selection reads as (0, 0), as on the host.  One lane per row: the entries of a node are ~50
-// consecutive words.
-// SELECT (vgmi_hmm_tallies_select), haplotypes selected per window: hap_ab holds places in the row's window's list (win_used), and only
-// the entries still in the node's list count -- the unique-k-mer count as well (posterior() walks the pruned list)
-template <bool SELECT>
-__global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
-                                                        const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
-                                                        const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win,
-                                                        const uint32_t* __restrict__ winner, const uint8_t* __restrict__ hap_ab,
-                                                        const uint8_t* __restrict__ win_used, uint32_t n_gt, uint32_t n_hap, unsigned long long sel_mask,
-                                                        uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
+// consecutive words, or per entry the two words that hold the called haplotypes.
+// SELECT (vgmi_hmm_tallies_select, _wide), haplotypes selected per window: hap_ab holds places in the row's window's list (win_used), and
+// only the entries still in the node's list count -- the unique-k-mer count as well (posterior() walks the pruned list)
+template <class E, bool SELECT>
+__global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long* __restrict__ words, const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
+                                                        const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
+                                                        const uint32_t* __restrict__ row_win, const uint32_t* __restrict__ winner,
+                                                        const uint8_t* __restrict__ hap_ab, const uint8_t* __restrict__ win_used, uint32_t n_gt, uint32_t n_hap,
+                                                        unsigned long long sel_mask, uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq,
+                                                        const uint8_t* __restrict__ f)
 {
+    const E ent = E::of(f, words);
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r >= n_rows) return;
     uint32_t num_a = 0, sum_a = 0, num_b = 0, sum_b = 0, u = 0;
@@ -803,13 +908,13 @@ __global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long
         const uint64_t e0 = entry_begin[r];
         const uint32_t cnt = entry_count[r];
         for (uint32_t j = 0; j < cnt; ++j) {
-            if (SELECT && alive[e0 + j] == 0) continue;
-            const unsigned long long w = packed[e0 + j];
-            const uint32_t c = cov[e0 + j];
-            const unsigned long long bits = w >> 16;
-            if (((uint32_t)(w >> 8) & 0xFFu) <= 1u && u < 255u) ++u;
-            if (ok_a && ((bits >> ha) & 1ull)) { ++num_a; sum_a += c; }
-            if (ok_b && ((bits >> hb) & 1ull)) { ++num_b; sum_b += c; }
+            const uint64_t e = e0 + j;
+            if (SELECT && alive[e] == 0) continue;
+            const typename E::Head hd = ent.head(e);
+            const uint32_t c = cov[e];
+            if (ent.mult(hd, e) <= 1u && u < 255u) ++u;
+            if (ok_a && ent.carries(hd, e, ha)) { ++num_a; sum_a += c; }
+            if (ok_b && ent.carries(hd, e, hb)) { ++num_b; sum_b += c; }
         }
     }
     out[4 * r] = num_a;
@@ -819,6 +924,9 @@ __global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long
     uniq[r] = (uint8_t)u;
 }
 
+// (This family alone stays a PAIR of kernels: written once over the reader, the body was 5 to 7 % slower on the device in both forms
+// -- DESIGN_INGEST_HMM.md 4.19.  The two differ in what an entry's load is and in which ids count: packed any id below 64 that the mask
+// holds, wide the ids below bl8 - 1.  One launcher and one implementation of the C ABI serve both.)
 // ---- ... of a POLYPLOID call (vgmi_hmm_tallies_ploidy): the called genotype is `ploidy` haplotype ids of the row's window's list ---------
 // win_haps as the emission launch of such a sample takes them; an id that stands several times (haplotype 0 in a truncated or all-zero
 // block) is tallied at every place it stands, an id outside win_sel_mask[w] -- not drawn, not in the panel -- or beyond 63 reads (0, 0), a
@@ -883,320 +991,6 @@ __global__ __launch_bounds__(256) void hmm_tally_ploidy_kernel(const unsigned lo
                     out[(r * ploidy + q) * 2 + 1] = sum[q];
                 }
             uniq[r] = (uint8_t)u;
-        }
-    }
-}
-
-// ---- selection support of the windows (src/genotype.cpp:500-560: what haplotype_selection sums before the gamma draws) ---------------
-// support[w][hap] = sum of c over the alive entries of window w's rows with c > 1 and multiplicity <= 1 that haplotype `hap` carries.
-// 32-bit integer sums: any order of additions gives the host's number.  A workgroup takes kSupportRows consecutive rows, a wavefront a
-// row at a time, a lane an entry; the sums of a workgroup are gathered in LDS and leave it as one atomic per haplotype and window (rows
-// come window after window, so a workgroup nearly always sees one window).
-constexpr uint32_t kSupportRows = 64;
-__global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long long* __restrict__ packed, const uint8_t* __restrict__ cov,
-                                                          const uint8_t* __restrict__ alive, const uint64_t* __restrict__ entry_begin,
-                                                          const uint32_t* __restrict__ entry_count, const uint32_t* __restrict__ row_win, uint64_t n_rows,
-                                                          uint32_t n_hap, uint32_t* __restrict__ support)
-{
-    __shared__ uint32_t s_sup[48];
-    const uint64_t r0 = (uint64_t)blockIdx.x * kSupportRows;
-    const uint64_t r1 = r0 + kSupportRows < n_rows ? r0 + kSupportRows : n_rows;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const unsigned long long hap_mask = (1ull << n_hap) - 1ull;      // n_hap <= 48
-    uint64_t ra = r0;
-    while (ra < r1) {      // the rows [ra, rb) of one window
-        const uint32_t w = row_win[ra];
-        uint64_t rb = ra + 1;
-        while (rb < r1 && row_win[rb] == w) ++rb;
-        if (threadIdx.x < 48u) s_sup[threadIdx.x] = 0;
-        __syncthreads();
-        for (uint64_t r = ra + wave; r < rb; r += 4) {
-            const uint64_t e0 = entry_begin[r];
-            const uint32_t cnt = entry_count[r];
-            for (uint32_t j = lane; j < cnt; j += 64u) {
-                if (alive[e0 + j] == 0) continue;
-                const unsigned long long word = packed[e0 + j];
-                const uint32_t c = cov[e0 + j];
-                if (c <= 1u || ((uint32_t)(word >> 8) & 0xFFu) > 1u) continue;
-                unsigned long long bits = (word >> 16) & hap_mask;
-                while (bits) {
-                    const uint32_t hap = (uint32_t)__ffsll((long long)bits) - 1u;
-                    bits &= bits - 1ull;
-                    atomicAdd(&s_sup[hap], c);
-                }
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
-        __syncthreads();
-        ra = rb;
-    }
-}
-
-// ---- panels of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry's haplotype bits are W = 1, 2 or 4 words ----------------------------
-// The packed word above holds six bytes of haplotype bits.  Here an entry is its multiplicity byte f[e] and its bit vector as it stands
-// in the graph, little-endian in W 64-bit words, zero-padded, entry-major: bits[e * W + i] -- one contiguous 8, 16 or 32-byte load.
-// The last bit of the vector (bit bl8 - 1) is the flag it is everywhere, never a haplotype.  The kernels keep the layouts of their
-// namesakes: row, window and every haplotype id are wavefront-uniform where they were, so the words of an entry, the window's mask and
-// the choice of the word that holds a haplotype stay on the scalar side.  A register array of W words is only ever indexed by an
-// unrolled loop's counter; the word of haplotype `hap` is picked by a chain over W (hmm_pick_word) or loaded on its own (the tallies).
-template <uint32_t W>
-__device__ __forceinline__ unsigned long long hmm_pick_word(const unsigned long long (&b)[W], uint32_t wi)
-{
-    unsigned long long w = 0;      // (masks, not selects: a chain of selects over an array is what the compiler turns back into an index)
-#pragma unroll
-    for (uint32_t i = 0; i < W; ++i) w |= b[i] & (0ull - (unsigned long long)(wi == i));
-    return w;
-}
-
-// hmm_support_kernel for up to 255 haplotypes: a wavefront per row, a lane per entry, the set bits walked word by word
-template <uint32_t W>
-__global__ __launch_bounds__(256) void hmm_support_wide_kernel(const uint8_t* __restrict__ f, const unsigned long long* __restrict__ bits,
-                                                               const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
-                                                               const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
-                                                               const uint32_t* __restrict__ row_win, uint64_t n_rows, uint32_t n_hap,
-                                                               uint32_t* __restrict__ support)
-{
-    __shared__ uint32_t s_sup[256];
-    const uint64_t r0 = (uint64_t)blockIdx.x * kSupportRows;
-    const uint64_t r1 = r0 + kSupportRows < n_rows ? r0 + kSupportRows : n_rows;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    unsigned long long hap_mask[W];      // the first n_hap bits (n_hap <= 64 W - 1)
-#pragma unroll
-    for (uint32_t i = 0; i < W; ++i) hap_mask[i] = n_hap >= 64u * (i + 1u) ? ~0ull : n_hap <= 64u * i ? 0ull : (1ull << (n_hap - 64u * i)) - 1ull;
-    uint64_t ra = r0;
-    while (ra < r1) {      // the rows [ra, rb) of one window
-        const uint32_t w = row_win[ra];
-        uint64_t rb = ra + 1;
-        while (rb < r1 && row_win[rb] == w) ++rb;
-        s_sup[threadIdx.x] = 0;
-        __syncthreads();
-        for (uint64_t r = ra + wave; r < rb; r += 4) {
-            const uint64_t e0 = entry_begin[r];
-            const uint32_t cnt = entry_count[r];
-            for (uint32_t j = lane; j < cnt; j += 64u) {
-                const uint64_t e = e0 + j;
-                if (alive[e] == 0) continue;
-                const uint32_t c = cov[e];
-                if (c <= 1u || (uint32_t)f[e] > 1u) continue;
-#pragma unroll
-                for (uint32_t i = 0; i < W; ++i) {
-                    unsigned long long word = bits[e * W + i] & hap_mask[i];
-                    while (word) {
-                        const uint32_t hap = 64u * i + (uint32_t)__ffsll((long long)word) - 1u;
-                        word &= word - 1ull;
-                        atomicAdd(&s_sup[hap], c);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
-        __syncthreads();
-        ra = rb;
-    }
-}
-
-// hmm_emissions_kernel<true, 4> for a diploid sample over such a panel: a workgroup per row, a lane per pair of places.  The prune asks
-// whether ANY word of the entry meets the window's mask; from `om` -- at most 16 bits over the places of the window's list -- on it is
-// that kernel: the same term tables in LDS (15 360 bytes), the same products.
-template <uint32_t W>
-__global__ __launch_bounds__(128) void hmm_emissions_wide_kernel(HmmEmitWideParams Q)
-{
-    __shared__ uint64_t s_tm[5u * 256u];
-    __shared__ int32_t s_te[5u * 256u];
-    const HmmEmitParams& P = Q.e;
-    const uint32_t g = threadIdx.x;
-    hmm_stage_tables<128>(P.tables, 2u, s_tm, s_te);
-    const uint64_t rowi = P.fix_rows ? P.fix_rows[blockIdx.x] : P.row_lo + blockIdx.x;
-    uint32_t fp = P.fix_rows ? P.fix_off[blockIdx.x] : 0u;
-    const uint32_t fe = P.fix_rows ? P.fix_off[blockIdx.x + 1] : 0u;
-    const uint64_t e0 = P.entry_begin[rowi];
-    const uint32_t cnt = P.entry_count[rowi], gt0 = P.gt0[rowi];
-    const bool active = g < P.n_gt;
-    const uint32_t w = P.row_win[rowi];
-    unsigned long long top_mask[W];
-#pragma unroll
-    for (uint32_t i = 0; i < W; ++i) top_mask[i] = P.win_top_mask[(size_t)w * W + i];
-    const uint8_t* const wused = P.win_used + (size_t)w * 16u;
-    const uint32_t pa = P.pos_a[active ? g : 0u], pb = P.pos_b[active ? g : 0u];
-    const uint32_t lb_word = (P.bl8 - 1u) >> 6, lb_bit = (P.bl8 - 1u) & 63u;
-    VgN80 prod;
-    prod.m = 1ULL << 63;      // 1.0L
-    prod.e = VG_X80_BIAS;
-    uint32_t kept = 0, flag = 0;
-    for (uint32_t j = 0; j < cnt; ++j) {
-        const uint64_t e = e0 + j;
-        if (P.alive[e] == 0) continue;      // pruned by an earlier window's or sample's selection
-        unsigned long long b[W], met = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < W; ++i) {
-            b[i] = Q.bits[e * W + i];
-            met |= b[i] & top_mask[i];
-        }
-        const uint32_t c = P.cov[e], f = Q.f[e];
-        if (met == 0) {
-            if (g == 0 && !P.fix_rows) P.alive[e] = 0;      // the prune
-            continue;
-        }
-        ++kept;
-        const uint32_t lb = (uint32_t)(hmm_pick_word<W>(b, lb_word) >> lb_bit) & 1u;
-        const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
-        uint32_t om = 0;
-        for (uint32_t p = 0; p < P.n_used; ++p) {
-            const uint32_t hap = (uint32_t)wused[p];
-            const uint32_t one = (in_interval && ((gt0 >> p) & 1u)) ? 1u : (uint32_t)((hmm_pick_word<W>(b, hap >> 6) >> (hap & 63u)) & 1ull);
-            om |= one << p;
-        }
-        if ((double)c < P.lower && f >= 2u && om != 0) flag |= 1u;
-        if (fp < fe && P.fix_j[fp] == j) {      // (the second launch: haplotypes whose sequence does not hold this k-mer do not carry it)
-            om &= ~(uint32_t)P.fix_mask[fp];
-            ++fp;
-        }
-        const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
-        const uint32_t h = ((om >> pa) & 1u) + ((om >> pb) & 1u);
-        const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
-        const uint32_t ti = h * 256u + cc;
-        VgN80 t;
-        t.m = s_tm[ti];
-        t.e = s_te[ti];
-        prod = n80_mul(prod, t);
-    }
-    if (active) x80_store(P.obs + (rowi * P.n_gt + g) * 16, n80_to(prod));
-    if (g == 0 && !P.fix_rows) {
-        P.n_kept[rowi] = kept;
-        P.flags[rowi] = (uint8_t)flag;
-    }
-}
-
-// hmm_tally_kernel<true> over such a panel: a lane per row, and per entry the two words that hold the called haplotypes
-template <uint32_t W>
-__global__ __launch_bounds__(256) void hmm_tally_wide_kernel(const uint8_t* __restrict__ f, const unsigned long long* __restrict__ bits,
-                                                             const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
-                                                             const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
-                                                             const uint32_t* __restrict__ row_win, const uint32_t* __restrict__ winner,
-                                                             const uint8_t* __restrict__ pos_ab, const uint8_t* __restrict__ win_used, uint32_t n_gt,
-                                                             uint64_t n_rows, uint32_t* __restrict__ out, uint8_t* __restrict__ uniq)
-{
-    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_rows) return;
-    uint32_t num_a = 0, sum_a = 0, num_b = 0, sum_b = 0, u = 0;
-    const uint32_t g = winner[r];
-    if (g < n_gt) {
-        const uint8_t* used = win_used + (size_t)row_win[r] * 16u;
-        const uint32_t ha = used[pos_ab[2u * g]], hb = used[pos_ab[2u * g + 1u]];
-        const uint32_t wa = W > 1u ? ha >> 6 : 0u, wb = W > 1u ? hb >> 6 : 0u;
-        const uint64_t e0 = entry_begin[r];
-        const uint32_t cnt = entry_count[r];
-        for (uint32_t j = 0; j < cnt; ++j) {
-            const uint64_t e = e0 + j;
-            if (alive[e] == 0) continue;
-            const uint32_t c = cov[e];
-            if ((uint32_t)f[e] <= 1u && u < 255u) ++u;
-            if ((bits[e * W + wa] >> (ha & 63u)) & 1ull) { ++num_a; sum_a += c; }
-            if ((bits[e * W + wb] >> (hb & 63u)) & 1ull) { ++num_b; sum_b += c; }
-        }
-    }
-    out[4 * r] = num_a;
-    out[4 * r + 1] = sum_a;
-    out[4 * r + 2] = num_b;
-    out[4 * r + 3] = sum_b;
-    uniq[r] = (uint8_t)u;
-}
-
-// hmm_emissions_win_kernel<MAXP> for a polyploid sample over such a panel: a wavefront per row, a lane per genotype of the row's window,
-// four wavefronts and kWinRows rows per workgroup, the term tables staged once.  Every mask over haplotype ids -- the drawn haplotypes, the
-// blocks' haplotypes, the row's reference-allele bits, a fix -- is W words, and so is `om`, the haplotypes that count as carrying an entry:
-// all of them wavefront-uniform.  Only a lane's ids differ, so the lane picks the word of each id out of `om` by hmm_pick_word's masks
-// (an indexed read of `om` is what becomes scratch) and sums the bits, a repeated id every time it stands.
-template <uint32_t MAXP, uint32_t W>
-__global__ __launch_bounds__(256) void hmm_emissions_win_wide_kernel(HmmEmitWinWideParams Q)
-{
-    __shared__ uint64_t s_tm[(MAXP + 1u) * 256u];
-    __shared__ int32_t s_te[(MAXP + 1u) * 256u];
-    const HmmEmitWinParams& P = Q.e;
-    hmm_stage_tables<256>(P.tables, P.ploidy, s_tm, s_te);      // (its barrier is the only one: from here on the wavefronts go their own ways)
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = threadIdx.x & 63u;
-    const uint32_t lb_word = (P.bl8 - 1u) >> 6, lb_bit = (P.bl8 - 1u) & 63u;
-    for (uint32_t k = wave; k < kWinRows; k += 4u) {
-        const uint64_t item = (uint64_t)blockIdx.x * kWinRows + k;
-        if (item >= P.n_items) break;
-        const uint64_t rowi = P.fix_rows ? P.fix_rows[item] : item;
-        uint32_t fp = P.fix_rows ? P.fix_off[item] : 0u;
-        const uint32_t fe = P.fix_rows ? P.fix_off[item + 1] : 0u;
-        const uint64_t e0 = P.entry_begin[rowi];
-        const uint32_t cnt = P.entry_count[rowi];
-        const uint32_t w = P.row_win[rowi];
-        unsigned long long gt0[W], top_mask[W], used_mask[W];
-#pragma unroll
-        for (uint32_t i = 0; i < W; ++i) {
-            gt0[i] = P.gt0[rowi * W + i];
-            top_mask[i] = P.win_top_mask[(size_t)w * W + i];
-            used_mask[i] = P.win_used_mask[(size_t)w * W + i];
-        }
-        const uint32_t n_here = P.win_n_gt[w];
-        const bool active = g < n_here;
-        uint32_t hap_word[MAXP] = {0}, hap_bit[MAXP] = {0};
-        if (active) {
-#pragma unroll
-            for (uint32_t q = 0; q < MAXP; ++q)      // (unrolled with the places beyond `ploidy` left out: the arrays stay in registers)
-                if (q < P.ploidy) {
-                    const uint32_t hap = P.win_haps[((size_t)w * P.n_gt + g) * P.ploidy + q];
-                    hap_word[q] = W > 1u ? hap >> 6 : 0u;
-                    hap_bit[q] = hap & 63u;
-                }
-        }
-        VgN80 prod;
-        prod.m = 1ULL << 63;      // 1.0L
-        prod.e = VG_X80_BIAS;
-        uint32_t kept = 0, flag = 0;
-        for (uint32_t j = 0; j < cnt; ++j) {
-            const uint64_t e = e0 + j;
-            if (P.alive[e] == 0) continue;      // pruned by an earlier window's or sample's selection
-            unsigned long long b[W], met = 0;
-#pragma unroll
-            for (uint32_t i = 0; i < W; ++i) {
-                b[i] = Q.bits[e * W + i];
-                met |= b[i] & top_mask[i];
-            }
-            const uint32_t c = P.cov[e], f = Q.f[e];
-            if (met == 0) {
-                if (g == 0 && !P.fix_rows) P.alive[e] = 0;      // the prune: by the DRAWN haplotypes
-                continue;
-            }
-            ++kept;
-            const uint32_t lb = (uint32_t)(hmm_pick_word<W>(b, lb_word) >> lb_bit) & 1u;
-            const bool in_interval = lb == 1u && (double)c >= P.lower && (double)c <= P.upper;
-            unsigned long long om[W], any = 0;      // the score: over the BLOCKS' haplotypes
-#pragma unroll
-            for (uint32_t i = 0; i < W; ++i) {
-                om[i] = (b[i] | (in_interval ? gt0[i] : 0ull)) & used_mask[i];
-                any |= om[i];
-            }
-            if ((double)c < P.lower && f >= 2u && any != 0) flag |= 1u;
-            if (fp < fe && P.fix_j[fp] == j) {      // (the second launch: haplotypes whose sequence does not hold this k-mer do not carry it)
-#pragma unroll
-                for (uint32_t i = 0; i < W; ++i) om[i] &= ~P.fix_mask[(size_t)fp * W + i];
-                ++fp;
-            }
-            if (!active) continue;
-            const uint32_t fj = (lb == 1u && f == 1u) ? 2u : f;
-            uint32_t h = 0;
-#pragma unroll
-            for (uint32_t q = 0; q < MAXP; ++q)      // (a repeated id counts at every place it stands)
-                if (q < P.ploidy) h += (uint32_t)(hmm_pick_word<W>(om, hap_word[q]) >> hap_bit[q]) & 1u;
-            const uint32_t cc = hmm_most_likely_depth(h, c, fj, P.ave, P.upper);
-            const uint32_t ti = h * 256u + cc;
-            VgN80 t;
-            t.m = s_tm[ti];
-            t.e = s_te[ti];
-            prod = n80_mul(prod, t);
-        }
-        if (active) x80_store(P.obs + (rowi * P.n_gt + g) * 16, n80_to(prod));
-        else if (g < P.n_gt) *reinterpret_cast<uint4*>(P.obs + (rowi * P.n_gt + g) * 16) = make_uint4(0, 0, 0, 0);
-        if (g == 0 && !P.fix_rows) {
-            P.n_kept[rowi] = kept;
-            P.flags[rowi] = (uint8_t)flag;
         }
     }
 }
@@ -1266,101 +1060,86 @@ __global__ __launch_bounds__(256) void hmm_tally_ploidy_wide_kernel(const uint8_
     }
 }
 
+// ---- selection support of the windows (src/genotype.cpp:500-560: what haplotype_selection sums before the gamma draws) ---------------
+// support[w][hap] = sum of c over the alive entries of window w's rows with c > 1 and multiplicity <= 1 that haplotype `hap` carries.
+// 32-bit integer sums: any order of additions gives the host's number.  A workgroup takes kSupportRows consecutive rows, a wavefront a
+// row at a time, a lane an entry, the set bits walked word by word; the sums of a workgroup are gathered in LDS (E::kMaxHap counters) and
+// leave it as one atomic per haplotype and window (rows come window after window, so a workgroup nearly always sees one window).
+constexpr uint32_t kSupportRows = 64;
+template <class E>
+__global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long long* __restrict__ words, const uint8_t* __restrict__ cov, const uint8_t* __restrict__ alive,
+                                                          const uint64_t* __restrict__ entry_begin, const uint32_t* __restrict__ entry_count,
+                                                          const uint32_t* __restrict__ row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* __restrict__ support,
+                                                          const uint8_t* __restrict__ f)
+{
+    constexpr uint32_t W = E::W;
+    const E ent = E::of(f, words);
+    __shared__ uint32_t s_sup[E::kMaxHap];
+    const uint64_t r0 = (uint64_t)blockIdx.x * kSupportRows;
+    const uint64_t r1 = r0 + kSupportRows < n_rows ? r0 + kSupportRows : n_rows;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    unsigned long long hap_mask[W];      // the first n_hap bits
+#pragma unroll
+    for (uint32_t i = 0; i < W; ++i) hap_mask[i] = E::hap_mask(n_hap, i);
+    uint64_t ra = r0;
+    while (ra < r1) {      // the rows [ra, rb) of one window
+        const uint32_t w = row_win[ra];
+        uint64_t rb = ra + 1;
+        while (rb < r1 && row_win[rb] == w) ++rb;
+        if (threadIdx.x < E::kMaxHap) s_sup[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint64_t r = ra + wave; r < rb; r += 4) {
+            const uint64_t e0 = entry_begin[r];
+            const uint32_t cnt = entry_count[r];
+            for (uint32_t j = lane; j < cnt; j += 64u) {
+                const uint64_t e = e0 + j;
+                if (alive[e] == 0) continue;
+                const typename E::Head hd = ent.head(e);
+                const uint32_t c = cov[e];
+                if (c <= 1u || ent.mult(hd, e) > 1u) continue;
+#pragma unroll
+                for (uint32_t i = 0; i < W; ++i) {
+                    unsigned long long word = ent.word(hd, e, i) & hap_mask[i];
+                    while (word) {
+                        const uint32_t hap = 64u * i + (uint32_t)__ffsll((long long)word) - 1u;
+                        word &= word - 1ull;
+                        atomicAdd(&s_sup[hap], c);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
+        __syncthreads();
+        ra = rb;
+    }
+}
+
 namespace {
-template <uint32_t W>
-hipError_t launch_emissions_win_wide_as(const HmmEmitWinWideParams& Q, hipStream_t st)
+// the run-time form and word count of the entries as the compile-time reader: launch(reader) for one of the four
+template <class Launch>
+hipError_t hmm_with_entries(const HmmEntries& ent, Launch&& launch)
 {
-    const dim3 grid((uint32_t)((Q.e.n_items + kWinRows - 1) / kWinRows));
-    if (Q.e.ploidy > 4) hipLaunchKernelGGL((hmm_emissions_win_wide_kernel<8, W>), grid, dim3(256), 0, st, Q);
-    else hipLaunchKernelGGL((hmm_emissions_win_wide_kernel<4, W>), grid, dim3(256), 0, st, Q);
-    return hipGetLastError();
+    switch (ent.W) {
+        case 0: return launch(HmmPackedEntries{});
+        case 1: return launch(HmmWideEntries<1>{});
+        case 2: return launch(HmmWideEntries<2>{});
+        case 4: return launch(HmmWideEntries<4>{});
+        default: return hipErrorInvalidValue;
+    }
 }
+
+// wide entries come with both arrays and a bit length their W words hold; the packed calls have never been asked
+bool hmm_entries_fit(const HmmEntries& ent, uint32_t bl8) { return ent.W == 0 || (ent.f && ent.words && bl8 >= 8 && bl8 <= 64u * ent.W); }
 }  // namespace
-
-hipError_t launch_hmm_emissions_win_wide(const HmmEmitWinWideParams& Q, uint32_t W, hipStream_t st)
-{
-    const HmmEmitWinParams& P = Q.e;
-    if (P.n_items == 0) return hipSuccess;
-    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 8 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask ||
-        !P.gt0 || !Q.f || !Q.bits || P.bl8 < 8 || P.bl8 > 64u * W)
-        return hipErrorInvalidValue;
-    switch (W) {
-        case 1: return launch_emissions_win_wide_as<1>(Q, st);
-        case 2: return launch_emissions_win_wide_as<2>(Q, st);
-        case 4: return launch_emissions_win_wide_as<4>(Q, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_hmm_tally_ploidy_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
-                                        const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
-                                        const uint32_t* win_n_gt, const uint8_t* win_haps, const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy,
-                                        uint32_t bl8, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
-{
-    if (n_rows == 0) return hipSuccess;
-    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || !win_haps || !win_sel_mask || !f || !bits || bl8 < 8 || bl8 > 64u * W) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)((n_rows + kTallyRows - 1) / kTallyRows));
-    switch (W) {
-        case 1: hipLaunchKernelGGL(hmm_tally_ploidy_wide_kernel<1>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, bl8, n_rows, out, uniq); break;
-        case 2: hipLaunchKernelGGL(hmm_tally_ploidy_wide_kernel<2>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, bl8, n_rows, out, uniq); break;
-        case 4: hipLaunchKernelGGL(hmm_tally_ploidy_wide_kernel<4>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, bl8, n_rows, out, uniq); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_hmm_support_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
-                                   const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap,
-                                   uint32_t* support, hipStream_t st)
-{
-    if (n_rows == 0) return hipSuccess;
-    if (n_hap < 1 || n_hap > 64u * W - 1u || n_hap > 255u) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)((n_rows + kSupportRows - 1) / kSupportRows));
-    switch (W) {
-        case 1: hipLaunchKernelGGL(hmm_support_wide_kernel<1>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, n_rows, n_hap, support); break;
-        case 2: hipLaunchKernelGGL(hmm_support_wide_kernel<2>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, n_rows, n_hap, support); break;
-        case 4: hipLaunchKernelGGL(hmm_support_wide_kernel<4>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, n_rows, n_hap, support); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_hmm_emissions_wide(const HmmEmitWideParams& Q, uint32_t W, uint64_t n_rows, hipStream_t st)
-{
-    if (n_rows == 0) return hipSuccess;
-    const HmmEmitParams& P = Q.e;
-    if (P.ploidy != 2 || !P.row_win || !P.win_used || !P.win_top_mask || !P.alive || !Q.f || !Q.bits || P.bl8 < 8 || P.bl8 > 64u * W) return hipErrorInvalidValue;
-    switch (W) {
-        case 1: hipLaunchKernelGGL(hmm_emissions_wide_kernel<1>, dim3((uint32_t)n_rows), dim3(128), 0, st, Q); break;
-        case 2: hipLaunchKernelGGL(hmm_emissions_wide_kernel<2>, dim3((uint32_t)n_rows), dim3(128), 0, st, Q); break;
-        case 4: hipLaunchKernelGGL(hmm_emissions_wide_kernel<4>, dim3((uint32_t)n_rows), dim3(128), 0, st, Q); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_hmm_tally_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
-                                 const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
-                                 const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
-{
-    if (n_rows == 0) return hipSuccess;
-    const dim3 grid((uint32_t)((n_rows + 255) / 256));
-    switch (W) {
-        case 1: hipLaunchKernelGGL(hmm_tally_wide_kernel<1>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, pos_ab, win_used, n_gt, n_rows, out, uniq); break;
-        case 2: hipLaunchKernelGGL(hmm_tally_wide_kernel<2>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, pos_ab, win_used, n_gt, n_rows, out, uniq); break;
-        case 4: hipLaunchKernelGGL(hmm_tally_wide_kernel<4>, grid, dim3(256), 0, st, f, bits, cov, alive, entry_begin, entry_count, row_win, winner, pos_ab, win_used, n_gt, n_rows, out, uniq); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
 
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,
                             const uint8_t* hap_ab, uint32_t n_gt, uint32_t n_hap, unsigned long long sel_mask, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
                             hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(hmm_tally_kernel<false>, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, nullptr, entry_begin, entry_count, nullptr,
-                       winner, hap_ab, nullptr, n_gt, n_hap, sel_mask, n_rows, out, uniq);
+    hipLaunchKernelGGL((hmm_tally_kernel<HmmPackedEntries, false>), dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, nullptr, entry_begin,
+                       entry_count, nullptr, winner, hap_ab, nullptr, n_gt, n_hap, sel_mask, n_rows, out, uniq, nullptr);
     return hipGetLastError();
 }
 
@@ -1374,59 +1153,87 @@ hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uin
 hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    if (P.ploidy < 2 || P.ploidy > 8) return hipErrorInvalidValue;
-    if (P.row_win) {
-        if (!P.win_used || !P.win_top_mask || !P.alive) return hipErrorInvalidValue;
-        if (P.ploidy > 4) return hipErrorInvalidValue;      // (selection per window by places: a diploid sample's)
-        hipLaunchKernelGGL((hmm_emissions_kernel<true, 4>), dim3((uint32_t)n_rows), dim3(128), 0, st, P);
-    } else if (P.ploidy > 4) {
-        hipLaunchKernelGGL((hmm_emissions_kernel<false, 8>), dim3((uint32_t)n_rows), dim3(128), 0, st, P);
-    } else {
-        hipLaunchKernelGGL((hmm_emissions_kernel<false, 4>), dim3((uint32_t)n_rows), dim3(128), 0, st, P);
-    }
-    return hipGetLastError();
+    if (P.ploidy < 2 || P.ploidy > 8 || !hmm_entries_fit(P.ent, P.bl8)) return hipErrorInvalidValue;
+    if (P.row_win && (!P.win_used || !P.win_top_mask || !P.alive)) return hipErrorInvalidValue;
+    return hmm_with_entries(P.ent, [&](auto ent) {
+        using E = decltype(ent);
+        const dim3 grid((uint32_t)n_rows), block(128);
+        if constexpr (E::kDiploidOnly) {
+            if (P.ploidy != 2 || !P.row_win) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((hmm_emissions_kernel<E, true, 4>), grid, block, 0, st, P);
+        } else if (P.row_win) {
+            if (P.ploidy > 4) return hipErrorInvalidValue;      // (selection per window by places: a diploid sample's)
+            hipLaunchKernelGGL((hmm_emissions_kernel<E, true, 4>), grid, block, 0, st, P);
+        } else if (P.ploidy > 4) {
+            hipLaunchKernelGGL((hmm_emissions_kernel<E, false, 8>), grid, block, 0, st, P);
+        } else {
+            hipLaunchKernelGGL((hmm_emissions_kernel<E, false, 4>), grid, block, 0, st, P);
+        }
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_hmm_emissions_win(const HmmEmitWinParams& P, hipStream_t st)
 {
     if (P.n_items == 0) return hipSuccess;
-    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 8 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask)
+    if (P.n_gt < 1 || P.n_gt > 64 || P.ploidy < 2 || P.ploidy > 8 || !P.alive || !P.row_win || !P.win_n_gt || !P.win_haps || !P.win_top_mask || !P.win_used_mask ||
+        (P.ent.W && !P.gt0) || !hmm_entries_fit(P.ent, P.bl8))
         return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)((P.n_items + kWinRows - 1) / kWinRows));
-    if (P.ploidy > 4) hipLaunchKernelGGL(hmm_emissions_win_kernel<8>, grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL(hmm_emissions_win_kernel<4>, grid, dim3(256), 0, st, P);
-    return hipGetLastError();
+    return hmm_with_entries(P.ent, [&](auto ent) {
+        using E = decltype(ent);
+        const dim3 grid((uint32_t)((P.n_items + kWinRows - 1) / kWinRows));
+        if (P.ploidy > 4) hipLaunchKernelGGL((hmm_emissions_win_kernel<E, 8>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((hmm_emissions_win_kernel<E, 4>), grid, dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_hmm_support(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
-                              const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st)
+hipError_t launch_hmm_support(const HmmEntries& ent, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin, const uint32_t* entry_count,
+                              const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    if (n_hap < 1 || n_hap > 48) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hmm_support_kernel, dim3((uint32_t)((n_rows + kSupportRows - 1) / kSupportRows)), dim3(256), 0, st, packed, cov, alive, entry_begin,
-                       entry_count, row_win, n_rows, n_hap, support);
-    return hipGetLastError();
+    if (n_hap < 1 || n_hap > (ent.W ? 64u * ent.W - 1u : 48u) || n_hap > 255u) return hipErrorInvalidValue;
+    return hmm_with_entries(ent, [&](auto e) {
+        hipLaunchKernelGGL(hmm_support_kernel<decltype(e)>, dim3((uint32_t)((n_rows + kSupportRows - 1) / kSupportRows)), dim3(256), 0, st, ent.words, cov, alive,
+                           entry_begin, entry_count, row_win, n_rows, n_hap, support, ent.f);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
-                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab,
-                                   const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st)
+hipError_t launch_hmm_tally_select(const HmmEntries& ent, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin, const uint32_t* entry_count,
+                                   const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows,
+                                   uint32_t* out, uint8_t* uniq, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(hmm_tally_kernel<true>, dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, packed, cov, alive, entry_begin, entry_count, row_win,
-                       winner, pos_ab, win_used, n_gt, 0u, 0ull, n_rows, out, uniq);
-    return hipGetLastError();
+    return hmm_with_entries(ent, [&](auto e) {
+        hipLaunchKernelGGL((hmm_tally_kernel<decltype(e), true>), dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, ent.words, cov, alive, entry_begin,
+                           entry_count, row_win, winner, pos_ab, win_used, n_gt, 0u, 0ull, n_rows, out, uniq, ent.f);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_hmm_tally_ploidy(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
-                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
-                                   const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
+hipError_t launch_hmm_tally_ploidy(const HmmEntries& ent, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin, const uint32_t* entry_count,
+                                   const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                   const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint32_t bl8, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
                                    hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || !win_haps || !win_sel_mask) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hmm_tally_ploidy_kernel, dim3((uint32_t)((n_rows + kTallyRows - 1) / kTallyRows)), dim3(256), 0, st, packed, cov, alive, entry_begin,
-                       entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt, ploidy, n_rows, out, uniq);
+    if (ploidy < 2 || ploidy > 4 || n_gt < 1 || !win_haps || !win_sel_mask || !hmm_entries_fit(ent, bl8)) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((n_rows + kTallyRows - 1) / kTallyRows));
+    auto wide = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ent.f, ent.words, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps, win_sel_mask, n_gt,
+                           ploidy, bl8, n_rows, out, uniq);
+    };
+    switch (ent.W) {      // (the one family that is a pair of kernels: no reader to turn the form into)
+        case 0:
+            hipLaunchKernelGGL(hmm_tally_ploidy_kernel, grid, dim3(256), 0, st, ent.words, cov, alive, entry_begin, entry_count, row_win, winner, win_n_gt, win_haps,
+                               win_sel_mask, n_gt, ploidy, n_rows, out, uniq);
+            break;
+        case 1: wide(hmm_tally_ploidy_wide_kernel<1>); break;
+        case 2: wide(hmm_tally_ploidy_wide_kernel<2>); break;
+        case 4: wide(hmm_tally_ploidy_wide_kernel<4>); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

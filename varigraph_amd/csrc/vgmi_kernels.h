@@ -271,10 +271,20 @@ struct HmmPostParams {
     uint32_t* winner;               // per row: the entry that makes the call; 0xFFFFFFFF: none
 };
 hipError_t launch_hmm_posterior(const HmmPostParams& P, uint64_t n_rows, hipStream_t st);
+// The node-list entries in either storage form (the kernels read them through one reader per form, vgmi_hmm.hip).  Packed: `words` holds
+// one word per entry, multiplicity << 8 | haplotype bits << 16 (the low byte is not used, up to six bytes of bits), f is null and W is 0.
+// Wide, panels of 48 to 254 haplotypes: f[e] is the multiplicity byte and words[e * W + i] the bit vector in W = 1, 2 or 4 64-bit words,
+// little-endian, zero-padded.  Every mask over haplotype ids that goes with wide entries is W words (one word with packed ones).
+// (`words` stands last: it is the packed kernels' first argument, and their argument blocks keep their shape behind it.)
+struct HmmEntries {
+    const uint8_t* f;
+    uint32_t W;
+    const unsigned long long* words;
+};
 // emission scores of a window's nodes on the device (hidden states + observable states of src/genotype.cpp:640-830, 960-1000) for the
 // case every k-mer list is whole and every genotype is a pair of haplotypes (vgmi_hmm_emissions in vgmi.h)
 struct HmmEmitParams {
-    const unsigned long long* packed;   // per node-list entry: multiplicity << 8 | haplotype bits << 16 (the low byte is not used)
+    HmmEntries ent;
     const uint8_t* cov;                 // per node-list entry: this sample's coverage
     const uint64_t* entry_begin;        // per row: its node's entries
     const uint32_t* entry_count;
@@ -300,8 +310,9 @@ struct HmmEmitParams {
     const uint16_t* fix_mask;
     // haplotypes selected per window (-n below the panel's haplotypes, a diploid sample: vgmi_hmm_emissions_select).  Null row_win: the
     // one selection above serves every row.  Else row r belongs to window row_win[r], whose haplotypes are win_used[16 w ..] (n_used of
-    // them, ids up to 46) with the mask win_top_mask[w]; `alive` says which entries are still in their node's list, and an alive entry
-    // no selected haplotype carries is marked dead there -- the forward pass's prune (src/genotype.cpp:673-686, 815-818)
+    // them, ids up to bl8 - 2) with the mask win_top_mask[w] (W words per window with wide entries, which are taken in this form and for
+    // pairs only); `alive` says which entries are still in their node's list, and an alive entry no selected haplotype carries is marked
+    // dead there -- the forward pass's prune (src/genotype.cpp:673-686, 815-818)
     const uint32_t* row_win;
     const uint8_t* win_used;
     const unsigned long long* win_top_mask;
@@ -310,10 +321,11 @@ struct HmmEmitParams {
 hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStream_t st);
 // ... with a genotype list per window (a polyploid sample under -n: vgmi_hmm_emissions_select_ploidy).  Window w has win_n_gt[w] <= n_gt
 // genotypes; genotype g of it is the `ploidy` haplotype IDS win_haps[(w * n_gt + g) * ploidy ..] (repeats count each time).  Every mask is
-// 64 bits over haplotype ids (up to 8 * bitlen - 2): win_top_mask the drawn haplotypes (the prune), win_used_mask the genotypes'
-// haplotypes (who counts as carrying an entry), gt0 the row's haplotypes with the reference allele, fix_mask what an entry loses.
+// 64 bits (wide entries: W words) over haplotype ids (up to 8 * bitlen - 2), per row, window or fix: win_top_mask the drawn haplotypes
+// (the prune), win_used_mask the genotypes' haplotypes (who counts as carrying an entry), gt0 the row's haplotypes with the reference
+// allele, fix_mask what an entry loses.
 struct HmmEmitWinParams {
-    const unsigned long long* packed;
+    HmmEntries ent;
     const uint8_t* cov;
     uint8_t* alive;
     const uint64_t* entry_begin;        // per row
@@ -339,51 +351,22 @@ struct HmmEmitWinParams {
 };
 hipError_t launch_hmm_emissions_win(const HmmEmitWinParams& P, hipStream_t st);
 // selection support of every window (src/genotype.cpp:500-560): support[w * n_hap + hap] += c over the alive entries of the window's rows
-// with c > 1 and multiplicity <= 1 whose bit `hap` is set; `support` is zeroed by the caller
-hipError_t launch_hmm_support(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
-                              const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st);
+// with c > 1 and multiplicity <= 1 whose bit `hap` is set; `support` is zeroed by the caller.  n_hap <= 48 packed, <= 64 W - 1 wide
+hipError_t launch_hmm_support(const HmmEntries& ent, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin, const uint32_t* entry_count,
+                              const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st);
 // the calls' tallies with per-window selection: genotype g of a row of window w is (win_used[16 w + pos_a[g]], win_used[16 w + pos_b[g]]);
 // only alive entries count
-hipError_t launch_hmm_tally_select(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
-                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab,
-                                   const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
+hipError_t launch_hmm_tally_select(const HmmEntries& ent, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin, const uint32_t* entry_count,
+                                   const uint32_t* row_win, const uint32_t* winner, const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows,
+                                   uint32_t* out, uint8_t* uniq, hipStream_t st);
 // the tallies of a polyploid call: genotype g of a row of window w (row_win == nullptr: window 0) is the `ploidy` ids
-// win_haps[(w * n_gt + g) * ploidy ..], each tallied where it stands if win_sel_mask[w] holds it; a winner >= win_n_gt[w] (nullptr: n_gt)
+// win_haps[(w * n_gt + g) * ploidy ..], each tallied where it stands if win_sel_mask (one word per window packed, W wide) holds it and it
+// is a haplotype (packed: below 64; wide: below bl8 - 1, which the packed form does not read); a winner >= win_n_gt[w] (nullptr: n_gt)
 // reads zeros; alive == nullptr: every entry counts.  out: n_rows x ploidy x (k-mers, coverage sum)
-hipError_t launch_hmm_tally_ploidy(const unsigned long long* packed, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin,
-                                   const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
-                                   const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
+hipError_t launch_hmm_tally_ploidy(const HmmEntries& ent, const uint8_t* cov, const uint8_t* alive, const uint64_t* entry_begin, const uint32_t* entry_count,
+                                   const uint32_t* row_win, const uint32_t* winner, const uint32_t* win_n_gt, const uint8_t* win_haps,
+                                   const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy, uint32_t bl8, uint64_t n_rows, uint32_t* out, uint8_t* uniq,
                                    hipStream_t st);
-// ---- panels of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry is its multiplicity byte f[e] and its haplotype bits in W = 1, 2 or 4
-// 64-bit words, little-endian, zero-padded, entry-major (bits[e * W + i]).  The launches keep the contracts of their namesakes above.
-// Emissions, a diploid sample with haplotypes selected per window: `e` as vgmi_hmm_emissions_select fills it, except that `packed` is not
-// read, win_top_mask holds W words per window and win_used ids go up to bl8 - 2
-struct HmmEmitWideParams {
-    HmmEmitParams e;
-    const uint8_t* f;
-    const unsigned long long* bits;
-};
-hipError_t launch_hmm_emissions_wide(const HmmEmitWideParams& Q, uint32_t W, uint64_t n_rows, hipStream_t st);
-hipError_t launch_hmm_support_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
-                                   const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap,
-                                   uint32_t* support, hipStream_t st);
-hipError_t launch_hmm_tally_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
-                                 const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
-                                 const uint8_t* pos_ab, const uint8_t* win_used, uint32_t n_gt, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
-// Emissions, a polyploid sample with a genotype list per window over such a panel: `e` as vgmi_hmm_emissions_select_ploidy fills it, except
-// that `packed` is not read and every mask over haplotype ids is W words: gt0 per row, win_top_mask and win_used_mask per window, fix_mask
-// per fix; win_haps ids go up to bl8 - 2
-struct HmmEmitWinWideParams {
-    HmmEmitWinParams e;
-    const uint8_t* f;
-    const unsigned long long* bits;
-};
-hipError_t launch_hmm_emissions_win_wide(const HmmEmitWinWideParams& Q, uint32_t W, hipStream_t st);
-// launch_hmm_tally_ploidy over such a panel: win_sel_mask holds W words per window, an id at or beyond bl8 - 1 reads (0, 0)
-hipError_t launch_hmm_tally_ploidy_wide(uint32_t W, const uint8_t* f, const unsigned long long* bits, const uint8_t* cov, const uint8_t* alive,
-                                        const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint32_t* winner,
-                                        const uint32_t* win_n_gt, const uint8_t* win_haps, const unsigned long long* win_sel_mask, uint32_t n_gt, uint32_t ploidy,
-                                        uint32_t bl8, uint64_t n_rows, uint32_t* out, uint8_t* uniq, hipStream_t st);
 hipError_t launch_hmm_scatter_rows(uint8_t* obs, const uint64_t* rows, const uint8_t* src, uint32_t n_gt, uint64_t n, hipStream_t st);
 size_t hmm_lds_bytes(uint32_t n_gt, uint32_t ploidy);
 hipError_t launch_hmm_tally(const unsigned long long* packed, const uint8_t* cov, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* winner,
