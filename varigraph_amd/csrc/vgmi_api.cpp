@@ -250,16 +250,36 @@ void rows_geometry(vgmi_ctx* c, bool flds, uint32_t& grid, uint32_t& block)
     else      { block = 256;  grid = (uint32_t)c->n_cu * 8; }
 }
 
-// n_bytes_dev != nullptr: the block's length lives in device memory (device-side readers); n_bytes is then only an
-// upper bound and the kernels derive their geometry themselves.  Even k needs the reads as well: d_read_off[0 .. *n_reads_dev]
-// in device memory, offsets from d_bases, and n_reads a bound on their number (the launch of a lane per read is sized by it)
+// launch geometry of count27_kernel.  The global-filter variant is random-access bound: more than ~16 waves per CU only adds L2 thrash
+static void count27_geometry(vgmi_ctx* c, bool lds_filter, uint32_t& grid, uint32_t& block)
+{
+    if (lds_filter) { block = 1024; grid = (uint32_t)c->n_cu; }
+    else            { block = 256;  grid = (uint32_t)c->n_cu * (c->wgs_per_cu ? c->wgs_per_cu : 4); }
+}
+
+// Every read block goes through here.  Which kernel serves which graph, how a block is split between the fast kernel and the exact tail,
+// and which launches follow from that are decided in vgmi_count_plan.h (count_plan, vg_row_split); this function only carries the plan out,
+// in stream order: clamp, debit pass (even k), fast kernel, tail.
+// n_bytes_dev != nullptr: the block's length lives in device memory (device-side readers); n_bytes is then only an upper bound and the
+// kernels derive their geometry themselves (RowParams::tail27).  Even k needs the reads as well: d_read_off[0 .. *n_reads_dev] in device
+// memory, offsets from d_bases, and n_reads a bound on their number (the launch of a lane per read is sized by it)
 int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_t* d_read_off, size_t n_reads,
                  hipStream_t st, const unsigned long long* n_bytes_dev, const unsigned long long* n_reads_dev)
 {
     if (n_bytes == 0) return VGMI_OK;
     const uint32_t k = c->hdr.k;
+    if (!(k & 1) && n_bytes_dev && (!d_read_off || !n_reads_dev))
+        return fail(c, VGMI_E_INVALID, "even k with a device-side block length: the reads' offsets and their number (d_read_off, n_reads_dev) are missing");
+    if (!(k & 1) && !n_bytes_dev && !d_read_off) return fail(c, VGMI_E_INVALID, "even k needs read offsets");
+    if (!n_bytes_dev) n_reads_dev = nullptr;
+    vg_count_caps caps{};
+    caps.xt_cb = c->tv.xt.cb != nullptr, caps.xt_lines = c->tv.xt.lines != nullptr;
+    caps.fast27 = c->fast27, caps.fast27_lds = c->fast27_lds, caps.fast27_small = c->fast27_small;
+    caps.fastk_small = c->fastk_small, caps.pt_index = c->tv.pt.index != nullptr, caps.force_generic = c->force_generic;
+    const vg_count_plan pl = count_plan(caps, k, n_bytes, n_bytes_dev != nullptr);
     RowParams p = row_params(c, d_bases, n_bytes, k);
     p.n_bytes_dev = n_bytes_dev;
+    p.row_end = pl.row_end, p.emit_from = pl.emit_from, p.row_begin = pl.row_begin, p.tail27 = pl.tail27;
     hipEvent_t e0, e1;
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -268,149 +288,36 @@ int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_
     }
     if (!e0 || !e1) return fail(c, VGMI_E_HIP, "hipEventCreate failed");
     HIPCHK(c, hipEventRecord(e0, st));
-    if (n_bytes_dev && !(k & 1) && (!d_read_off || !n_reads_dev))
-        return fail(c, VGMI_E_INVALID, "even k with a device-side block length: the reads' offsets and their number (d_read_off, n_reads_dev) are missing");
-    if (n_bytes_dev && !(k & 1)) {
-        // the three branches of even k below, in the same stream order, with everything that follows from the block's length derived in the
-        // kernels (tail27 tells them which fast kernel sits between the debit pass and the tail).  A block under one row leaves the debit
-        // pass and the fast kernel nothing to do, and the tail takes every read.
-        if (c->tv.xt.cb && !c->force_generic) {
-            int rcx = xt_clamp_if_due(c, n_bytes, st);
-            if (rcx) return rcx;
-            unsigned long long* list = nullptr;
-            int rcl = debit_list_of(c, st, &list);
-            if (rcl) return rcl;
-            p.tail27 = 2;
-            HIPCHK(c, launch_even_debit_dev(p, d_read_off, n_reads, n_reads_dev, list, VG_DEBIT_LIST, st));
-            { int rcc = launch_ctable_count(c, p, n_bytes, st); if (rcc) return rcc; }
-            HIPCHK(c, launch_seq_dev(p, d_read_off, n_reads, n_reads_dev, st));
-        } else if (c->fastk_small && c->tv.pt.index && !c->force_generic) {
-            unsigned long long* list = nullptr;
-            int rcl = debit_list_of(c, st, &list);
-            if (rcl) return rcl;
-            p.tail27 = 4;
-            HIPCHK(c, launch_even_debit_dev(p, d_read_off, n_reads, n_reads_dev, list, VG_DEBIT_LIST, st));
-            HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
-            HIPCHK(c, launch_seq_dev(p, d_read_off, n_reads, n_reads_dev, st));
-        } else {
-            HIPCHK(c, launch_seq_dev(p, d_read_off, n_reads, n_reads_dev, st));
-        }
-    } else if (n_bytes_dev) {
-        uint32_t grid, block;
-        rows_geometry(c, c->filter_in_lds, grid, block);
-        if ((c->tv.xt.lines || c->tv.xt.cb) && !c->force_generic) {
-            int rcx = xt_clamp_if_due(c, n_bytes, st);
-            if (rcx) return rcx;
-            if (c->tv.xt.cb) { int rcc = launch_ctable_count(c, p, n_bytes, st); if (rcc) return rcc; }
-            else HIPCHK(c, launch_count27x(p, c->tv.xt, (uint32_t)c->n_cu * 8, st));
-            p.tail27 = 2;
-            HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, 1, block, st));
-        } else if ((c->fast27_small || (c->fastk_small && c->tv.pt.index)) && !c->force_generic) {
-            HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
-            p.tail27 = c->fast27_small ? 3 : 4;
-            HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, 1, block, st));
-        } else if (c->fast27 && !c->force_generic) {
-            uint32_t g27, b27;
-            if (c->fast27_lds) { b27 = 1024; g27 = (uint32_t)c->n_cu; }
-            else { b27 = 256; g27 = (uint32_t)c->n_cu * (c->wgs_per_cu ? c->wgs_per_cu : 4); }
-            HIPCHK(c, launch_count27(c->fast27_lds, p, g27, b27, st));
-            p.tail27 = 1;
-            HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, 1, block, st));
-        } else {
-            HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, grid, block, st));
-        }
-    } else if (k & 1) {
-        uint32_t grid, block;
-        rows_geometry(c, c->filter_in_lds, grid, block);
-        if ((c->tv.xt.lines || c->tv.xt.cb) && !c->force_generic) {
-            // context table / grid-16-mer table: complete 768-byte rows -> count27c_kernel / count27x_kernel, the ends behind them -> the generic kernel
-            const uint64_t rows = n_bytes / 768;
-            uint64_t emit_from = 0;
-            int rcx = xt_clamp_if_due(c, n_bytes, st);
-            if (rcx) return rcx;
-            if (rows) {
-                if (c->tv.xt.cb) { int rcc = launch_ctable_count(c, p, n_bytes, st); if (rcc) return rcc; }
-                else HIPCHK(c, launch_count27x(p, c->tv.xt, (uint32_t)c->n_cu * 8, st));
-                emit_from = rows * 768 - 1;
-            }
-            if (emit_from < n_bytes) {
-                p.emit_from = emit_from;
-                p.row_begin = emit_from >> 10;
-                HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, 1, block, st));
-            }
-        } else if ((c->fast27_small || (c->fastk_small && c->tv.pt.index)) && !c->force_generic) {
-            // complete pairs of 1 024-byte rows -> count27s_kernel: lane L of a row covers the k-mers ending at stream positions
-            // 16 L - 1 .. 16 L + 14 of the row (k < 27, the grid of 8: 16 L .. 16 L + 15); the generic kernel takes the ends behind
-            // the last pair, from the last position of the last full row on (k < 27: from the first position behind it)
-            p.row_end = (n_bytes / 2048) * 2;
-            uint64_t emit_from = 0;
-            if (p.row_end) {
-                HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
-                emit_from = p.row_end * 1024 - (c->fast27_small ? 1 : 0);
-            }
-            if (emit_from < n_bytes) {
-                p.emit_from = emit_from;
-                p.row_begin = emit_from >> 10;
-                HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, 1, block, st));
-            }
-        } else if (c->fast27 && !c->force_generic) {
-            // complete 768-byte rows -> fast kernel.  It covers every k-mer whose run starts at one of its
-            // grid positions; the generic kernel takes the ends after that: the ragged tail plus the last
-            // position of the last full row.
-            p.row_end = (n_bytes / 1536) * 2;   // VG_ROW27: count27_kernel walks complete 768-byte rows, two per iteration
-            uint64_t emit_from = 0;
-            if (p.row_end) {
-                if (c->fast27_lds) { block = 1024; grid = (uint32_t)c->n_cu; }
-                else {
-                    // global-filter variant: random-access bound; more than ~16 waves per CU only adds
-                    // L2 thrash
-                    block = 256;
-                    grid = (uint32_t)c->n_cu * (c->wgs_per_cu ? c->wgs_per_cu : 4);
-                }
-                HIPCHK(c, launch_count27(c->fast27_lds, p, grid, block, st));
-                // lane L of a row covers the k-mers ending at stream positions 12L - 1 .. 12L + 10
-                emit_from = p.row_end * 768 - 1;
-            }
-            if (emit_from < n_bytes) {
-                p.emit_from = emit_from;
-                p.row_begin = emit_from >> 10;
-                rows_geometry(c, c->filter_in_lds, grid, block);
-                HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, 1, block, st));
-            }
-        } else {
-            HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, grid, block, st));
-        }
-    } else {
-        if (!d_read_off) return fail(c, VGMI_E_INVALID, "even k needs read offsets");
-        if (c->tv.xt.cb && !c->force_generic && n_bytes >= 768) {
-            // k = 20 .. 24 on a large graph: complete 768-byte rows through countkc_kernel<K> over the context table, the debit pass ahead of it,
-            // the literal state machine for the ends behind the rows (its lookups go through the same table: table_count)
-            const uint64_t rows = n_bytes / 768;
-            p.emit_from = rows * 768 - 1;
-            int rcx = xt_clamp_if_due(c, n_bytes, st);
-            if (rcx) return rcx;
-            unsigned long long* list = nullptr;
-            int rcl = debit_list_of(c, st, &list);
-            if (rcl) return rcl;
-            HIPCHK(c, launch_even_debit(p, d_read_off, n_reads, list, VG_DEBIT_LIST, st));
-            { int rcc = launch_ctable_count(c, p, n_bytes, st); if (rcc) return rcc; }
-            HIPCHK(c, launch_seq(K_MODE_COUNT, p, d_read_off, n_reads, st));
-        } else if (c->fastk_small && c->tv.pt.index && !c->force_generic && n_bytes >= 2048) {
-            // k = 20 .. 24 on a small graph: the windows of k bases through count27s_kernel<true, K> (complete pairs of rows), in front of
-            // it the pass that takes back what the reference's run counter suppresses, behind it the literal state machine for the
-            // ends the rows do not cover
-            p.row_end = (n_bytes / 2048) * 2;
-            p.emit_from = p.row_end * 1024;
-            unsigned long long* list = nullptr;
-            int rcl = debit_list_of(c, st, &list);
-            if (rcl) return rcl;
-            HIPCHK(c, launch_even_debit(p, d_read_off, n_reads, list, VG_DEBIT_LIST, st));
-            HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
-            if (p.emit_from < n_bytes) HIPCHK(c, launch_seq(K_MODE_COUNT, p, d_read_off, n_reads, st));
-        } else {
-            HIPCHK(c, launch_seq(K_MODE_COUNT, p, d_read_off, n_reads, st));
-        }
+    if (pl.clamp) {
+        int rc = xt_clamp_if_due(c, n_bytes, st);
+        if (rc) return rc;
     }
+    if (pl.debit) {
+        unsigned long long* list = nullptr;
+        int rc = debit_list_of(c, st, &list);
+        if (rc) return rc;
+        HIPCHK(c, launch_even_debit(p, d_read_off, n_reads, list, VG_DEBIT_LIST, st, n_reads_dev));
+    }
+    uint32_t grid, block;
+    switch (pl.launch_fast ? pl.fast : VG_FAST_NONE) {
+    case VG_FAST_TABLE:
+        if (caps.xt_cb) { int rc = launch_ctable_count(c, p, n_bytes, st); if (rc) return rc; }
+        else HIPCHK(c, launch_count27x(p, c->tv.xt, (uint32_t)c->n_cu * 8, st));
+        break;
+    case VG_FAST_SMALL27:
+    case VG_FAST_SMALLK:
+        HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
+        break;
+    case VG_FAST_ROWS27:
+        count27_geometry(c, caps.fast27_lds, grid, block);
+        HIPCHK(c, launch_count27(caps.fast27_lds, p, grid, block, st));
+        break;
+    }
+    if (pl.tail == VG_TAIL_ROWS) {
+        rows_geometry(c, c->filter_in_lds, grid, block);
+        HIPCHK(c, launch_rows(K_MODE_COUNT, c->filter_in_lds, p, pl.tail_full ? grid : 1, block, st));
+    } else if (pl.tail == VG_TAIL_SEQ)
+        HIPCHK(c, launch_seq(K_MODE_COUNT, p, d_read_off, n_reads, st, n_reads_dev));      // (its own grid: a lane per read, or five workgroups)
     HIPCHK(c, hipEventRecord(e1, st));
     std::lock_guard<std::mutex> lk(c->mu);
     c->timed.emplace_back(e0, e1);

@@ -1,7 +1,7 @@
 // vgmi_ctx.h -- what the files of the C ABI (vgmi_api*.cpp; include/vgmi.h) share: the context, the table image's header, the error
 // macro and the helpers one file defines for the others (namespace vgapi).  Internal: nothing here is part of the ABI.
 //
-//   vgmi_api.cpp         contexts, read counting (launch_count: which kernel serves which graph), read-out, timing
+//   vgmi_api.cpp         contexts, read counting (launch_count carries out vgmi_count_plan.h: which kernel serves which graph), read-out, timing
 //   vgmi_api_table.cpp   the table image: layout, upload / import / export / clone, the path / context / grid-16-mer tables built from it
 //   vgmi_api_rccl.cpp    the image over RCCL (one process per GPU)
 //   vgmi_api_fastq.cpp   FASTQ text on the device: records, block-gzip and gzip members

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_count_plan.h"
 #include "vgmi_ctable.h"
 #include "vgmi_device.h"
 
@@ -87,18 +88,18 @@ struct RowParams {
     const uint8_t* bases;
     uint64_t n_bytes;
     uint64_t row_begin;   // rows_kernel: first 1 KiB row to process (earlier rows only provide the halo)
-    uint64_t row_end;     // count27_kernel: one past the last row; every row below it is complete
-    uint64_t emit_from;   // rows_kernel<COUNT>: only k-mers ENDING at stream position >= emit_from are counted (the
-                          // fast kernel covers the ends up to its last grid offset)
+    uint64_t row_end;     // count27_kernel, count27s_kernel: one past the last row; every row below it is complete (vg_row_split, vgmi_count_plan.h)
+    uint64_t emit_from;   // the exact tail (rows_kernel<COUNT>, seq_kernel<COUNT>) counts only k-mers ENDING at stream position >= emit_from, the
+                          // debit pass works in front of it: the fast kernel covers the ends up to there (vg_row_split)
     uint32_t k;
     uint32_t dbg;         // ablations of count27_kernel only (VGMI_DBG; counts are wrong with any of them): 1 = scan
                           // only (candidate runs dropped), 32 = one probing lane per run, 64 = collisions dropped; 128 = K3 without the per-wave
                           // privatisation (same filter, A/B only)
     uint32_t* status;     // bit0 empty read, bit1 bad key, bit2 duplicate key
     const unsigned long long* n_bytes_dev;   // count kernels: when set, the block's length is read from device memory (the
-                          // device-side FASTQ parser knows it, the host does not) and n_bytes / row_end / row_begin /
-                          // emit_from are derived from it in the kernel; tail27 tells rows_kernel it runs behind count27_kernel
-    uint32_t tail27;      // 1 behind count27_kernel, 2 behind count27x_kernel, 3 behind count27s_kernel, 4 behind count27s_kernel<true, K < 27> (it covers every end inside its rows)
+                          // device-side readers know it, the host does not) and n_bytes / row_end / row_begin / emit_from are
+                          // derived from it in the kernel, by vg_row_split(tail27, length)
+    uint32_t tail27;      // with n_bytes_dev: the fast kernel this block goes through (vg_fast, vgmi_count_plan.h); else 0
     uint32_t l1_min;      // count27s_kernel<true>: queued runs that start a round of the path-table look-up (VGMI_L1_MIN; default 60, at most 64: one lane per run)
     TableView table;      // MODE_COUNT
     uint64_t* keys_out;   // MODE_KEYS
@@ -424,15 +425,13 @@ hipError_t launch_ptable_check(const uint32_t* pos_of_key, uint64_t n, uint64_t 
 hipError_t launch_ptable_fill(const TableView& t, const uint32_t* key_slot, const uint32_t* pos_of_key, uint64_t n, ulonglong2* P, hipStream_t st);
 hipError_t launch_rows(int mode, bool flds, const RowParams& p, uint32_t grid, uint32_t block, hipStream_t st);
 hipError_t launch_bloom_even(const RowParams& p, hipStream_t st);   // even k, one long sequence (K3)
-hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, uint64_t n_reads, hipStream_t st);
+// n_reads_dev (MODE_COUNT only): the block's length (p.n_bytes_dev) and the number of reads live in device memory, p.n_bytes and n_reads are the
+// host's bounds, p.tail27 names the fast kernel in front (vg_fast)
+hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, uint64_t n_reads, hipStream_t st, const unsigned long long* n_reads_dev = nullptr);
 #define VG_DEBIT_LIST (1u << 20)      // positions of non-bases one launch can hand to its walk launch (8 MiB per stream; the rest is walked in the scan)
 #define VG_DEBIT_SUBLISTS 256u       // ... in that many lists of equal size, one counter each (64 bytes apart, behind the positions)
-hipError_t launch_even_debit(const RowParams& p, const uint64_t* read_off, uint64_t n_reads, unsigned long long* list, uint32_t list_cap, hipStream_t st);
-// even k behind the device-side readers: the block's length (p.n_bytes_dev) and the number of reads (n_reads_dev) live in device memory, p.n_bytes
-// and n_reads_bound are the host's bounds, p.tail27 names the fast kernel between the debit pass and the tail (2: context table, 4: path table)
-hipError_t launch_even_debit_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev,
-                                 unsigned long long* list, uint32_t list_cap, hipStream_t st);
-hipError_t launch_seq_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev, hipStream_t st);
+hipError_t launch_even_debit(const RowParams& p, const uint64_t* read_off, uint64_t n_reads, unsigned long long* list, uint32_t list_cap, hipStream_t st,
+                             const unsigned long long* n_reads_dev = nullptr);      // n_reads_dev: as for launch_seq
 // where the reads of a '\n'-joined read block start (vgmi_readoff.hip): read_off[0 .. n] and n = *n_reads_dev from the block's newlines, its
 // length read from device memory; n_bytes_bound sizes the grid, tile holds a word per 16 KiB of it, cap_reads bounds the offsets written
 hipError_t launch_read_offsets(const uint8_t* packed, uint64_t n_bytes_bound, const unsigned long long* n_bytes_dev, uint32_t* tile, uint64_t* read_off,

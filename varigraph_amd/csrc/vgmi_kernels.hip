@@ -345,13 +345,7 @@ __global__ __launch_bounds__(1024) void rows_kernel(RowParams p)
     uint64_t n_bytes = p.n_bytes, row_begin = p.row_begin, emit_from = p.emit_from;
     if (p.n_bytes_dev) {
         n_bytes = *p.n_bytes_dev;
-        emit_from = 0;
-        if (p.tail27) {   // behind count27_kernel: the ends it does not cover (see launch_count in vgmi_api.cpp)
-            // 1: count27_kernel (pairs of 768-byte rows), 2: count27x_kernel (single rows), 3: count27s_kernel (pairs of 1 024-byte rows)
-            const uint64_t row_bytes = p.tail27 >= 3 ? 1024u : 768u;
-            const uint64_t row_end27 = p.tail27 == 2 ? n_bytes / 768 : (n_bytes / (2 * row_bytes)) * 2;
-            emit_from = row_end27 ? row_end27 * row_bytes - (p.tail27 == 4 ? 0u : 1u) : 0;
-        }
+        emit_from = vg_row_split(p.tail27, n_bytes).emit_from;      // behind a fast kernel: the ends it does not cover (vgmi_count_plan.h)
         row_begin = emit_from >> 10;
         if (emit_from >= n_bytes) return;
     }
@@ -888,11 +882,11 @@ __global__ __launch_bounds__(LDS_BM ? 1024 : 256) void count27_kernel(RowParams 
     const uint32_t hb_log2 = p.table.home_bucket_log2;
     const bool hb_off = p.table.home_by_offset != 0;
 
-    // rows [0, row_end) are complete 768-byte rows (row_end is even, see vgmi_api.cpp), so every load below is an
+    // rows [0, row_end) are complete 768-byte rows (row_end is even: vg_row_split, vgmi_count_plan.h), so every load below is an
     // unconditional, perfectly coalesced dwordx3 (the ragged tail goes to rows_kernel).  A wave walks a
     // contiguous range of row PAIRS: two rows per iteration give every wave two independent dependency chains
     // (LUT reads -> permutes -> filter word), which four waves per SIMD need to keep the VALU fed.
-    const uint64_t total_pairs = p.n_bytes_dev ? *p.n_bytes_dev / (2 * VG_ROW27) : p.row_end >> 1;   // device-side block length: vgmi_fastq.hip
+    const uint64_t total_pairs = p.n_bytes_dev ? *p.n_bytes_dev / (2 * VG_ROW27) : p.row_end >> 1;   // device-side block length: vg_row_split(VG_FAST_ROWS27).row_end / 2, spelt out (through the call the row loop's instruction stream moves)
     const uint64_t total_waves = (uint64_t)gridDim.x * nwaves;
     const uint64_t ppw = (total_pairs + total_waves - 1) / total_waves;
     // the wave index is uniform: keep the row counters in SGPRs
@@ -1239,7 +1233,7 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
     const uint64_t cap_mask = p.table.cap_mask;
 
     // rows [0, row_end) are complete 1 024-byte rows, row_end even: a wave walks a contiguous range of row PAIRS
-    const uint64_t total_pairs = p.n_bytes_dev ? *p.n_bytes_dev / (2 * VG_ROW27S) : p.row_end >> 1;
+    const uint64_t total_pairs = p.n_bytes_dev ? *p.n_bytes_dev / (2 * VG_ROW27S) : p.row_end >> 1;      // (vg_row_split(VG_FAST_SMALL27).row_end / 2, as in count27_kernel)
     const uint64_t total_waves = (uint64_t)gridDim.x * nwaves;
     const uint64_t ppw = (total_pairs + total_waves - 1) / total_waves;
     const uint64_t gw = (uint64_t)blockIdx.x * nwaves + wave_u;
@@ -1859,21 +1853,12 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
 // ------------------------------------------------------------------------------------------
 #define VG_SEQ_LDS 16384u   // bytes of read text a wavefront stages (64 reads of up to ~250 bases)
 
-// even k behind the device-side readers (DEV forms of the kernels below): the first position whose k-mer ends belong to the exact tail,
-// derived from the block's length as rows_kernel derives it from tail27 (2: single 768-byte rows of the context-table kernel, 4: pairs of
-// 1 024-byte rows of count27s_kernel<true, K>, 0: no fast kernel in front) -- the debit pass, the fast kernel and the tail must agree on it
-__device__ __forceinline__ uint64_t even_emit_from(uint32_t tail27, uint64_t n_bytes)
-{
-    if (tail27 == 2) {
-        const uint64_t rows = n_bytes / 768;
-        return rows ? rows * 768 - 1 : 0;
-    }
-    return tail27 == 4 ? (n_bytes / 2048) * 2048 : 0;
-}
+// even k behind the device-side readers (DEV forms of the kernels below): emit_from, the first position whose k-mer ends belong to the exact
+// tail, comes from the block's length as rows_kernel derives it -- the debit pass, the fast kernel and the tail read one split (vgmi_count_plan.h)
 
 // DEV: the block's length (p.n_bytes_dev), the number of reads (n_reads_dev) and emit_from come from device memory; n_reads is then only
 // the bound the grid was sized by.  Behind a fast kernel (p.tail27) the launch is a small fixed grid: lane g takes read r0 + g, r0 the
-// first read that ends behind emit_from (launch_seq_dev).
+// first read that ends behind emit_from (launch_seq with n_reads_dev).
 template <int MODE, bool DEV = false>
 __global__ __launch_bounds__(256) void seq_kernel(RowParams p, const uint64_t* read_off, uint64_t n_reads, const unsigned long long* n_reads_dev = nullptr)
 {
@@ -1887,7 +1872,7 @@ __global__ __launch_bounds__(256) void seq_kernel(RowParams p, const uint64_t* r
     if constexpr (DEV) {
         n_reads = *n_reads_dev < n_reads ? *n_reads_dev : n_reads;      // (the bound is the offsets' capacity too: never an index beyond them)
         n_bytes = *p.n_bytes_dev;
-        emit_from = even_emit_from(p.tail27, n_bytes);
+        emit_from = vg_row_split(p.tail27, n_bytes).emit_from;
         if (p.tail27) {      // (uniform) the reads in front of r0 end at or in front of emit_from
             if (emit_from >= n_bytes) return;
             uint64_t lo = 0, hi = n_reads;
@@ -2107,7 +2092,7 @@ __global__ __launch_bounds__(256) void even_debit_kernel(RowParams p, const uint
     if constexpr (DEV) {
         n_bytes = *p.n_bytes_dev;
         n_reads = *n_reads_dev < n_reads ? *n_reads_dev : n_reads;      // (the bound is the offsets' capacity too)
-        emit_from = even_emit_from(p.tail27, n_bytes);
+        emit_from = vg_row_split(p.tail27, n_bytes).emit_from;
     }
     const uint64_t limit = emit_from < n_bytes ? emit_from : n_bytes;
     if constexpr (DEV) {
@@ -2163,7 +2148,7 @@ __global__ __launch_bounds__(256) void even_debit_walk_kernel(RowParams p, const
     if constexpr (DEV) {
         n_bytes = *p.n_bytes_dev;
         n_reads = *n_reads_dev < n_reads ? *n_reads_dev : n_reads;      // (the bound is the offsets' capacity too)
-        emit_from = even_emit_from(p.tail27, n_bytes);
+        emit_from = vg_row_split(p.tail27, n_bytes).emit_from;
     }
     if (g >= list_cap || g - sub * sub_cap >= list_n[16u * sub] || n_reads == 0) return;
     const uint64_t limit = emit_from < n_bytes ? emit_from : n_bytes;
@@ -2541,12 +2526,19 @@ hipError_t launch_rows(int mode, bool flds, const RowParams& p, uint32_t grid, u
     return launch_rows_t<MODE_BLOOM, false>(p, grid, block, st);
 }
 
-hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, uint64_t n_reads, hipStream_t st)
+// n_reads_dev: seq_kernel<MODE_COUNT> with the block's length and the number of reads in device memory.  p.tail27 == 0: every read, a lane per read
+// the chunk can hold (n_reads, the bound).  Else the exact tail behind a fast kernel: the text at or behind emit_from is under two rows
+// (vg_row_split), a read takes two bytes of it at least (a base and its '\n'), so the reads that end behind emit_from are the one that
+// straddles it and 1 023 more at most: five workgroups of 256 lanes.
+hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, uint64_t n_reads, hipStream_t st, const unsigned long long* n_reads_dev)
 {
     const uint32_t block = 256;
-    const uint32_t grid = (uint32_t)((n_reads + block - 1) / block);
+    const uint32_t grid = n_reads_dev && p.tail27 ? 5u : (uint32_t)((n_reads + block - 1) / block);
     if (grid == 0) return hipSuccess;
-    if (mode == MODE_COUNT) hipLaunchKernelGGL((seq_kernel<MODE_COUNT, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
+    if (n_reads_dev) {
+        if (mode != MODE_COUNT) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((seq_kernel<MODE_COUNT, true>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, n_reads_dev);
+    } else if (mode == MODE_COUNT) hipLaunchKernelGGL((seq_kernel<MODE_COUNT, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
     else if (mode == MODE_KEYS) hipLaunchKernelGGL((seq_kernel<MODE_KEYS, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
     else if (mode == MODE_DEBIT) return hipErrorInvalidValue;      // launch_even_debit
     else hipLaunchKernelGGL((seq_kernel<MODE_BLOOM, false>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads, (const unsigned long long*)nullptr);
@@ -2554,46 +2546,24 @@ hipError_t launch_seq(int mode, const RowParams& p, const uint64_t* read_off, ui
 }
 
 // list: list_cap positions and, behind them, the counters (one allocation per stream that counts even k: vgmi_api.cpp)
-hipError_t launch_even_debit(const RowParams& p, const uint64_t* read_off, uint64_t n_reads, unsigned long long* list, uint32_t list_cap, hipStream_t st)
+// n_reads_dev: the block's length and the number of reads live in device memory (p.n_bytes_dev; p.tail27 names the fast kernel that follows,
+// n_reads is a bound): the scan's grid covers p.n_bytes, the host's bound on the length, and the kernels find their limit themselves
+hipError_t launch_even_debit(const RowParams& p, const uint64_t* read_off, uint64_t n_reads, unsigned long long* list, uint32_t list_cap, hipStream_t st,
+                             const unsigned long long* n_reads_dev)
 {
-    const uint64_t limit = p.emit_from < p.n_bytes ? p.emit_from : p.n_bytes, per_wg = 256u * 16u * VG_DEBIT_PIECES;
-    if (limit == 0 || n_reads == 0) return hipSuccess;
+    const uint64_t limit = n_reads_dev || p.n_bytes < p.emit_from ? p.n_bytes : p.emit_from, per_wg = 256u * 16u * VG_DEBIT_PIECES;
+    if (limit == 0 || (n_reads == 0 && !n_reads_dev)) return hipSuccess;
     unsigned int* const list_n = reinterpret_cast<unsigned int*>(list + list_cap);
     hipError_t e = hipMemsetAsync(list_n, 0, VG_DEBIT_SUBLISTS * 64, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(even_debit_kernel<false>, dim3((uint32_t)((limit + per_wg - 1) / per_wg)), dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n,
-                       (const unsigned long long*)nullptr);
-    hipLaunchKernelGGL(even_debit_walk_kernel<false>, dim3((list_cap + 255) / 256), dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n,
-                       (const unsigned long long*)nullptr);
-    return hipGetLastError();
-}
-
-// ... with the block's length and the number of reads in device memory (p.n_bytes_dev, n_reads_dev; p.tail27 names the fast kernel that
-// follows): the scan's grid covers p.n_bytes, the host's bound on the length
-hipError_t launch_even_debit_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev,
-                                 unsigned long long* list, uint32_t list_cap, hipStream_t st)
-{
-    const uint64_t per_wg = 256u * 16u * VG_DEBIT_PIECES;
-    if (p.n_bytes == 0) return hipSuccess;
-    unsigned int* const list_n = reinterpret_cast<unsigned int*>(list + list_cap);
-    hipError_t e = hipMemsetAsync(list_n, 0, VG_DEBIT_SUBLISTS * 64, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(even_debit_kernel<true>, dim3((uint32_t)((p.n_bytes + per_wg - 1) / per_wg)), dim3(256), 0, st, p, read_off, n_reads_bound, list, list_cap,
-                       list_n, n_reads_dev);
-    hipLaunchKernelGGL(even_debit_walk_kernel<true>, dim3((list_cap + 255) / 256), dim3(256), 0, st, p, read_off, n_reads_bound, list, list_cap, list_n, n_reads_dev);
-    return hipGetLastError();
-}
-
-// seq_kernel<MODE_COUNT> with the block's length and the number of reads in device memory.  p.tail27 == 0: every read, a lane per read
-// the chunk can hold (n_reads_bound).  Else the exact tail behind a fast kernel: the text at or behind emit_from is under two rows
-// (2 047 bytes behind pairs of 1 024-byte rows, 768 behind single 768-byte rows), a read takes two bytes of it at least (a base and its
-// '\n'), so the reads that end behind emit_from are the one that straddles it and 1 023 more at most: five workgroups of 256 lanes.
-hipError_t launch_seq_dev(const RowParams& p, const uint64_t* read_off, uint64_t n_reads_bound, const unsigned long long* n_reads_dev, hipStream_t st)
-{
-    const uint32_t block = 256;
-    const uint32_t grid = p.tail27 ? 5u : (uint32_t)((n_reads_bound + block - 1) / block);
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL((seq_kernel<MODE_COUNT, true>), dim3(grid), dim3(block), 0, st, p, read_off, n_reads_bound, n_reads_dev);
+    const dim3 scan((uint32_t)((limit + per_wg - 1) / per_wg)), walk((list_cap + 255) / 256);
+    if (n_reads_dev) {
+        hipLaunchKernelGGL(even_debit_kernel<true>, scan, dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n, n_reads_dev);
+        hipLaunchKernelGGL(even_debit_walk_kernel<true>, walk, dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n, n_reads_dev);
+    } else {
+        hipLaunchKernelGGL(even_debit_kernel<false>, scan, dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n, n_reads_dev);
+        hipLaunchKernelGGL(even_debit_walk_kernel<false>, walk, dim3(256), 0, st, p, read_off, n_reads, list, list_cap, list_n, n_reads_dev);
+    }
     return hipGetLastError();
 }
 
