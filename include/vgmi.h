@@ -170,6 +170,12 @@ int vgmi_counts_import_device(vgmi_ctx *ctx, const uint32_t *dev_counts /* n_key
 /* Accumulated GPU time (HIP events on the context stream) of the read-counting kernel since
  * the last reset, and the number of launches; for roofline accounting. */
 int vgmi_count_kernel_ms(vgmi_ctx *ctx, float *ms, uint64_t *launches);
+/* Small graphs (the path table): the count kernel drops a candidate run whose index bucket is DONE -- every k-mer the
+ * run's windows could equal has reached the clamp.  This recomputes that property from the index, the k-mer-start bits and
+ * the saturation bits alone, after everything submitted so far, and compares: out[0] buckets that can become done,
+ * out[1] buckets marked done, out[2] marked done but not fully saturated (0, always), out[3] fully saturated but not
+ * marked (0 once the stream is idle; every such bucket with VGMI_PT_DONE=0).  All zero without a path table. */
+int vgmi_pt_done_check(vgmi_ctx *ctx, uint64_t out[4]);
 
 /* ---- device-side FASTQ parsing -----------------------------------------------------------------
  * replaces: kseq_read + the per-record sequence copy of FastqKmer::fastq_file_open (include/kseq.h:192-232,

@@ -76,10 +76,11 @@ void free_table(vgmi_ctx* c)
     } else if (c->d_ct_buckets) (void)hipFree(c->d_ct_buckets);
     c->d_ct_buckets = nullptr;
     c->ct_entries = c->ct_unitigs = c->ct_moved = 0;
-    for (void* q : {(void*)c->d_pt_index, (void*)c->d_pt_S, (void*)c->d_pt_VB, (void*)c->d_pt_SB, (void*)c->d_pt_SLOT, (void*)c->d_pt_PLACE})
+    for (void* q : {(void*)c->d_pt_index, (void*)c->d_pt_S, (void*)c->d_pt_VB, (void*)c->d_pt_SB, (void*)c->d_pt_SLOT, (void*)c->d_pt_PLACE,
+                    (void*)c->d_pt_BKT, (void*)c->d_pt_NEED})
         if (q) (void)hipFree(q);
     c->d_pt_index = nullptr;
-    c->d_pt_S = c->d_pt_VB = c->d_pt_SB = c->d_pt_SLOT = c->d_pt_PLACE = nullptr;
+    c->d_pt_S = c->d_pt_VB = c->d_pt_SB = c->d_pt_SLOT = c->d_pt_PLACE = c->d_pt_BKT = c->d_pt_NEED = nullptr;
     c->tv.pt = PathView{};
     c->d_xt_lines = nullptr;
     c->d_xt_counts = nullptr;
@@ -704,6 +705,26 @@ int vgmi_count_kernel_ms(vgmi_ctx* c, float* ms, uint64_t* launches)
     if (rc) return rc;
     if (ms) *ms = c->kernel_ms;
     if (launches) *launches = c->launches;
+    return VGMI_OK;
+}
+
+int vgmi_pt_done_check(vgmi_ctx* c, uint64_t out[4])
+{
+    if (!c || !out) return VGMI_E_INVALID;
+    if (!c->has_table) return fail(c, VGMI_E_STATE, "no table");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!c->tv.pt.index) return VGMI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = sync_stages(c);
+    if (rc) return rc;
+    unsigned long long* d = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), 32));
+    hipError_t he = hipMemsetAsync(d, 0, 32, c->stream);
+    if (he == hipSuccess) he = launch_ptable_done_check(c->tv.pt, c->hdr.k, d, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he == hipSuccess) he = hipMemcpy(out, d, 32, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHK(c, he);
     return VGMI_OK;
 }
 

@@ -427,8 +427,8 @@ int build_xtable(vgmi_ctx* c)
 }
 
 // the path table of small graphs, derived from the compact image like the grid-16-mer table of large ones (after an upload,
-// an import and a clone alike); VGMI_PTABLE=0 keeps count27s_kernel on the hash table alone (A/B).  SB and PC are per-sample state
-// and start at zero here, whatever the image's history.  The device orders the
+// an import and a clone alike); VGMI_PTABLE=0 keeps count27s_kernel on the hash table alone (A/B).  SB, PC and the buckets' CNT and
+// DONE are per-sample state and start at zero here, whatever the image's history.  The device orders the
 // k-mers along their unitigs (vgmi_ptable.hip); the layout of the sequence and the index is host work over <= 65 536 k-mers.
 int build_ptable(vgmi_ctx* c)
 {
@@ -568,17 +568,65 @@ int build_ptable(vgmi_ctx* c)
     }
     c->pt_slow_cx = slow_cx;
     c->pt_bucket_ovf = bucket_ovf;
+    // Buckets whose every k-mer is saturated (VGMI_PT_DONE=0: none of this).  BKT: the bucket of every effective place -- a
+    // listed place q, and flip - q, where a read that carries the 12-mer reversed is compared (the kernel's `flip`).  NEED: the bucket's
+    // pairs (effective place q, position x in [q, q + W)) with a start bit; a bucket with a slow-path flag -- its runs take the hash
+    // table and must keep doing so -- or without any pair gets a NEED no count reaches.
+    const char* dnv = getenv("VGMI_PT_DONE");
+    const bool pt_done = !(dnv && dnv[0] == '0');
+    const size_t n_buckets = (size_t)1 << bucket_log2;
+    const uint32_t W = K == 27 ? 16u : 8u, flip = (uint32_t)Tp - (K == 27 ? 42u : 2u * K - 12u);
+    std::vector<uint32_t> BKT, NEED;
+    if (pt_done) {
+        BKT.assign((size_t)Tp + 64, VG_PT_NO_BUCKET);
+        NEED.assign(n_buckets, 0u);
+        std::vector<uint8_t> never(n_buckets, 0);
+        for (size_t b = 0; b < n_buckets; ++b) {
+            const unsigned long long* B = &index[b << 2];
+            if (B[0] >> 62 & 1) never[b] = 1;
+            for (int e = 0; e < 2; ++e) {
+                const unsigned long long lo = B[2 * e], hi = B[2 * e + 1];
+                if (hi >> 38 & 1) never[b] = 1;
+                const uint32_t q[4] = {(uint32_t)(lo >> 24) & 0x7FFFFu, (uint32_t)(lo >> 43) & 0x7FFFFu, (uint32_t)hi & 0x7FFFFu, (uint32_t)(hi >> 19) & 0x7FFFFu};
+                for (int i = 0; i < 4 && q[0] != 0; ++i) {
+                    if (q[i] == 0) continue;
+                    for (const uint32_t at : {q[i], flip - q[i]}) {
+                        if (at >= Tp || (BKT[at] != VG_PT_NO_BUCKET && BKT[at] != (uint32_t)b)) {      // (cannot happen: one 12-mer per place)
+                            never[b] = 1;
+                            if (at < Tp) never[BKT[at]] = 1;
+                            continue;
+                        }
+                        BKT[at] = (uint32_t)b;
+                    }
+                }
+            }
+        }
+        for (uint64_t at = 0; at < Tp; ++at) {
+            if (BKT[at] == VG_PT_NO_BUCKET) continue;
+            for (uint32_t j = 0; j < W && at + j < Tp; ++j) NEED[BKT[at]] += vb[at + j];
+        }
+        for (size_t b = 0; b < n_buckets; ++b)
+            if (never[b] || NEED[b] == 0) NEED[b] = 0xFFFFFFFFu;
+    }
     he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_index), index.size() * 8);
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_S), S.size() * 4);
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_VB), VB.size() * 4);
     // the saturation bits and, behind them, the position counters: one allocation, one memset per sample (vgmi_counts_reset)
-    const size_t pc_words = (size_t)Tp + 64;
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SB), (VB.size() + pc_words) * 4);
+    // ... and the buckets' CNT and DONE (PathView)
+    const size_t pc_words = (size_t)Tp + 64, cnt_words = pt_done ? n_buckets : 0, done_words = pt_done ? (n_buckets + 31) / 32 : 0;
+    const size_t sb_words = VB.size() + pc_words + cnt_words + done_words;
+    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SB), sb_words * 4);
+    if (pt_done) {
+        if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_BKT), BKT.size() * 4);
+        if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_NEED), NEED.size() * 4);
+        if (he == hipSuccess) he = hipMemcpy(c->d_pt_BKT, BKT.data(), BKT.size() * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(c->d_pt_NEED, NEED.data(), NEED.size() * 4, hipMemcpyHostToDevice);
+    }
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SLOT), (size_t)(Tp + 64) * 4);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_index, index.data(), index.size() * 8, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_S, S.data(), S.size() * 4, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_VB, VB.data(), VB.size() * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemset(c->d_pt_SB, 0, (VB.size() + pc_words) * 4);
+    if (he == hipSuccess) he = hipMemset(c->d_pt_SB, 0, sb_words * 4);
     if (he == hipSuccess) he = hipMemset(c->d_pt_SLOT, 0, (size_t)(Tp + 64) * 4);
     if (he == hipSuccess) he = hipMemcpy(c->d_pt_SLOT, slot.data(), (size_t)Tp * 4, hipMemcpyHostToDevice);
     {   // slot -> place: the slow paths -- the hash-table fallback of runs the index does not cover, the generic kernel on the
@@ -589,7 +637,7 @@ int build_ptable(vgmi_ctx* c)
         if (he == hipSuccess) he = hipMemcpy(c->d_pt_PLACE, place_of_slot.data(), h.cap * 4, hipMemcpyHostToDevice);
     }
     HIPCHK(c, he);
-    c->pt_sb_bytes = (VB.size() + pc_words) * 4;
+    c->pt_sb_bytes = sb_words * 4;
     if (getenv("VGMI_VERBOSE"))
         fprintf(stderr, "[vgmi] path table: %llu k-mers in %llu chains, %llu bases, %llu 12-mers with a fifth place, %llu buckets with a third 12-mer\n",
                 (unsigned long long)n, (unsigned long long)chains, (unsigned long long)Tp, (unsigned long long)slow_cx, (unsigned long long)bucket_ovf);
@@ -602,6 +650,12 @@ int build_ptable(vgmi_ctx* c)
     // VGMI_PT_POSCOUNT=0 keeps the drain's increments on the hash table's counters (A/B)
     const char* pcv = getenv("VGMI_PT_POSCOUNT");
     c->tv.pt.PC = pcv && pcv[0] == '0' ? nullptr : c->d_pt_SB + VB.size();
+    if (pt_done) {
+        c->tv.pt.BKT = c->d_pt_BKT;
+        c->tv.pt.NEED = c->d_pt_NEED;
+        c->tv.pt.CNT = c->d_pt_SB + VB.size() + pc_words;
+        c->tv.pt.DONE = c->tv.pt.CNT + cnt_words;
+    }
     c->tv.pt.bucket_log2 = bucket_log2;
     c->tv.pt.Tp = (uint32_t)Tp;
     return VGMI_OK;

@@ -100,7 +100,8 @@ struct vgmi_ctx {
     uint64_t ct_entries = 0, ct_unitigs = 0, ct_moved = 0;   // entries built, unitigs they came from, entries not in their home bucket
     unsigned long long* d_pt_index = nullptr;   // path table of small graphs (build_ptable): 12-mer -> places in the unitig sequence
     uint32_t *d_pt_S = nullptr, *d_pt_VB = nullptr, *d_pt_SB = nullptr, *d_pt_SLOT = nullptr, *d_pt_PLACE = nullptr;   // sequence, k-mer starts, saturation bits, slots, places by slot
-    size_t pt_sb_bytes = 0;                     // d_pt_SB's bytes: the saturation bits and the position counters behind them (PathView::PC)
+    uint32_t *d_pt_BKT = nullptr, *d_pt_NEED = nullptr;   // buckets whose every k-mer is saturated: the static side (PathView::BKT, ::NEED)
+    size_t pt_sb_bytes = 0;                     // d_pt_SB's bytes: the saturation bits and, behind them, the position counters (PathView::PC) and the buckets' CNT and DONE
     uint64_t pt_slow_cx = 0, pt_bucket_ovf = 0;  // 12-mers with more than two places / buckets with a third 12-mer (those runs take the hash table)
     uint64_t xt_over_keys = 0;                  // pairs (key, 16-mer) that overflowed in the last build
     uint8_t* d_sat_dirty = nullptr;   // compact format: 2048-slot regions holding a saturation flag (the reset sweeps those)

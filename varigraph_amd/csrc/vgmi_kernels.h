@@ -51,9 +51,18 @@ struct PathView {
     const uint32_t* PLACE;             // per hash-table slot: the place (first half of S) where its k-mer starts, 0: none -- for the slow paths' saturation bits
     uint32_t* PC;                      // per base position: what the path-table drain has counted of the k-mer that starts here or at the mirrored
                                        // place (the cell of the smaller of the two); a k-mer's count is counts[slot] + PC[cell].  nullptr: not in use
+    // buckets whose every k-mer is saturated (VGMI_PT_DONE=0: DONE is nullptr and none of the four is in use).  Static:
+    const uint32_t* BKT;               // per base position: the bucket of the index entry this position is an effective place of (a listed
+                                       // place or the mirror of one), VG_PT_NO_BUCKET: none
+    const uint32_t* NEED;              // per bucket: the pairs (effective place q of an entry of the bucket, position x in [q, q + windows)) with
+                                       // the start bit VB[x] set; 0xFFFFFFFF: never done (a slow-path flag in the bucket, or no pair at all)
+    // ... per sample, behind SB and PC in their allocation:
+    uint32_t* CNT;                     // per bucket: its pairs whose position is saturated (pt_done_event)
+    uint32_t* DONE;                    // bit per bucket: CNT has reached NEED -- a run of this bucket has no hit left to count
     uint32_t bucket_log2;
     uint32_t Tp;                       // bases in S, pads included: S[Tp - 1 - j] is the complement of S[j]
 };
+#define VG_PT_NO_BUCKET 0xFFFFFFFFu
 
 struct TableView {
     VgSlot* slots;              // cap entries (16-byte format) or nullptr
@@ -422,6 +431,7 @@ hipError_t launch_count27s(const RowParams& p, uint32_t grid, hipStream_t st);  
 hipError_t launch_ptable_order(const TableView& t, const uint32_t* key_slot, uint64_t n, uint32_t* key_of_slot, uint32_t* link, uint32_t* link2,
                                uint32_t* pos_of_key, unsigned long long* cursor, uint32_t* mark, uint32_t* status, hipStream_t st, uint32_t align = 1);
 hipError_t launch_ptable_check(const uint32_t* pos_of_key, uint64_t n, uint64_t total, uint32_t* mark, uint32_t* status, hipStream_t st);
+hipError_t launch_ptable_done_check(const PathView& pt, uint32_t k, unsigned long long* out, hipStream_t st);      // out: four counts, zeroed by the caller
 hipError_t launch_ptable_fill(const TableView& t, const uint32_t* key_slot, const uint32_t* pos_of_key, uint64_t n, ulonglong2* P, hipStream_t st);
 hipError_t launch_rows(int mode, bool flds, const RowParams& p, uint32_t grid, uint32_t block, hipStream_t st);
 hipError_t launch_bloom_even(const RowParams& p, hipStream_t st);   // even k, one long sequence (K3)

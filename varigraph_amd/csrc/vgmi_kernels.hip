@@ -155,6 +155,37 @@ __device__ __forceinline__ uint32_t pt_counted(const TableView& t, uint64_t s)
     return pc ? *pc : 0u;
 }
 
+// Buckets of the path table whose every k-mer is saturated (PathView::BKT .. DONE).  An EVENT: the saturation bit of
+// position x has just been turned on -- the atomicOr that set it returned it clear, so one caller raises it, once per sample; pos and
+// its mirror raise one each.  Step j of an event, j = 0 .. windows - 1, looks at q = x - j: where q is an effective place of an index
+// entry, one more pair of that entry's bucket is saturated, and the addition that completes the bucket's pairs marks the bucket done.
+// HOT: in the row loop of count27s_kernel, where every memory operation is issued and waited for by hand (see count27_kernel).
+__device__ __forceinline__ uint32_t vm_load_dword_sync(const uint32_t* ptr);
+__device__ __forceinline__ void vm_load_and_inc_sync(const uint32_t* ld, uint32_t* at, uint32_t one, uint32_t& v, uint32_t& old);
+__device__ __forceinline__ void vm_atomic_or_sync(uint32_t* ptr, uint32_t bits);
+template <bool HOT>
+__device__ __forceinline__ void pt_done_step(const uint32_t* BKT, const uint32_t* NEED, uint32_t* CNT, uint32_t* DONE, uint32_t q)
+{
+    if constexpr (HOT) {
+        const uint32_t b = vm_load_dword_sync(BKT + q);
+        if (b == VG_PT_NO_BUCKET) return;
+        uint32_t need, old;
+        vm_load_and_inc_sync(NEED + b, CNT + b, 1u, need, old);
+        if (old + 1u == need) vm_atomic_or_sync(DONE + (b >> 5), 1u << (b & 31u));
+    } else {
+        const uint32_t b = BKT[q];
+        if (b == VG_PT_NO_BUCKET) return;
+        if (atomicAdd(&CNT[b], 1u) + 1u == NEED[b]) atomicOr(&DONE[b >> 5], 1u << (b & 31u));
+    }
+}
+// a whole event by the lane that raised it (the generic kernels: a few per k-mer and sample; count27s_kernel spreads the steps over lanes)
+__device__ __forceinline__ void pt_done_event(const PathView& pt, uint32_t k, uint32_t x)
+{
+    if (!pt.DONE) return;
+    const uint32_t W = k == 27u ? 16u : 8u;
+    for (uint32_t j = 0; j < W; ++j) pt_done_step<false>(pt.BKT, pt.NEED, pt.CNT, pt.DONE, x - j);
+}
+
 // exact-table probe + saturating count of one canonical k-mer (generic kernels; either table format)
 __device__ __forceinline__ uint64_t table_home(const TableView& t, uint64_t canon)
 {
@@ -187,8 +218,8 @@ __device__ __forceinline__ void table_count(const TableView& t, uint64_t canon)
                         const uint32_t pos = t.pt.PLACE[s];
                         if (pos != 0u) {
                             const uint32_t mir = t.pt.Tp - t.k - pos;
-                            atomicOr(&t.pt.SB[pos >> 5], 1u << (pos & 31u));
-                            atomicOr(&t.pt.SB[mir >> 5], 1u << (mir & 31u));
+                            if (!(atomicOr(&t.pt.SB[pos >> 5], 1u << (pos & 31u)) >> (pos & 31u) & 1u)) pt_done_event(t.pt, t.k, pos);
+                            if (!(atomicOr(&t.pt.SB[mir >> 5], 1u << (mir & 31u)) >> (mir & 31u) & 1u)) pt_done_event(t.pt, t.k, mir);
                         }
                     }
                 }
@@ -584,6 +615,18 @@ __device__ __forceinline__ void vmp_load_index(const void* ptr)     // 32 bytes:
 {
     asm volatile("global_load_dwordx4 v[108:111], %0, off ; VGHOT\n\tglobal_load_dwordx4 v[112:115], %0, off offset:16 ; VGHOT" : : "v"(ptr) : VG_HOT_CLOBBERS_P);
 }
+// the word of PathView::DONE that holds the bucket's bit: issued IN FRONT of the index load (loads return in order: it has landed when
+// the bucket has), into v76 -- place 0's start bits, idle until phase 2 has read this
+__device__ __forceinline__ void vmp_load_done(const void* ptr)
+{
+    asm volatile("global_load_dword v76, %0, off ; VGHOT" : : "v"(ptr) : VG_HOT_CLOBBERS_P);
+}
+__device__ __forceinline__ uint32_t vmp_done_value()     // after the wait for the index bucket, before a place is loaded
+{
+    uint32_t v;
+    asm volatile("v_mov_b32 %0, v76 ; VGHOT" : "=v"(v));
+    return v;
+}
 #define VG_SEQ_ASM(C, SQ, VBR, SBR) \
     if (c == C) asm volatile("global_load_dwordx4 " SQ ", %0, off ; VGHOT\n\tglobal_load_dwordx2 " VBR ", %1, off ; VGHOT\n\tglobal_load_dwordx2 " SBR ", %2, off ; VGHOT" \
                              : : "v"(sq), "v"(vb), "v"(sb) : VG_HOT_CLOBBERS_P)
@@ -668,6 +711,19 @@ __device__ __forceinline__ uint32_t vm_atomic_inc_sync(uint32_t* ptr, uint32_t o
 {
     uint32_t old;
     asm volatile("global_atomic_add %0, %1, %2, off sc0 ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT" : "=&v"(old) : "v"(ptr), "v"(one) : "memory");
+    return old;
+}
+// ... a dword load and a returning increment that do not depend on each other, one wait for both (pt_done_step)
+__device__ __forceinline__ void vm_load_and_inc_sync(const uint32_t* ld, uint32_t* at, uint32_t one, uint32_t& v, uint32_t& old)
+{
+    asm volatile("global_load_dword %0, %2, off ; VGHOT\n\tglobal_atomic_add %1, %3, %4, off sc0 ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT"
+                 : "=&v"(v), "=&v"(old) : "v"(ld), "v"(at), "v"(one) : "memory");
+}
+// ... an atomic OR that says what the word held (who turned a saturation bit on raises its event)
+__device__ __forceinline__ uint32_t vm_atomic_or_ret_sync(uint32_t* ptr, uint32_t bits)
+{
+    uint32_t old;
+    asm volatile("global_atomic_or %0, %1, %2, off sc0 ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT" : "=&v"(old) : "v"(ptr), "v"(bits) : "memory");
     return old;
 }
 // n = hot operations issued after the one whose result is needed: waits with vmcnt(min(n, 4)) (a drain step of the path-table
@@ -1298,6 +1354,10 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
     uint32_t* const ptSB = p.table.pt.SB;
     const uint32_t* const ptSLOT = p.table.pt.SLOT;
     uint32_t* const ptPC = p.table.pt.PC;
+    const uint32_t* const ptBKT = p.table.pt.BKT;
+    const uint32_t* const ptNEED = p.table.pt.NEED;
+    uint32_t* const ptCNT = p.table.pt.CNT;
+    uint32_t* const ptDONE = p.table.pt.DONE;             // nullptr (VGMI_PT_DONE=0): no bucket is ever done, no event is raised
     const uint32_t pt_Tp = p.table.pt.Tp, pt_bshift = 32u - p.table.pt.bucket_log2;
     const uint32_t l1_min = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.l1_min);
     uint32_t n_after_idx = 8, n_after_seq = 8;            // hot operations issued after the index load / after the last load of phase 2
@@ -1305,12 +1365,33 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
     uint32_t l1_n = 0, l1_phase = 0;                      // wave-uniform: runs in the round, 0 idle / 1 bucket in flight / 2 sequence in flight
     uint32_t pl[4] = {0u, 0u, 0u, 0u};                    // places (0: none)
     bool l1_slow = false;
+    uint32_t l1_done_bit = 0;                             // the run's bucket's bit in the word of DONE that phase 1 asked for
     auto hot = [&](uint32_t k) __attribute__((always_inline)) {
         n_after_row += k;
         n_after_idx += k;
         n_after_seq += k;
     };
-    auto slow_count = [&](uint32_t klo, uint32_t khi) __attribute__((always_inline)) {
+    // the saturation bits of a k-mer's two places; what comes back says which of them THIS call turned on (bit 0: pos, bit 1: mir)
+    auto set_saturated = [&](uint32_t pos, uint32_t mir) __attribute__((always_inline)) -> uint32_t {
+        const uint32_t a = vm_atomic_or_ret_sync(ptSB + (pos >> 5), 1u << (pos & 31u));
+        const uint32_t b = vm_atomic_or_ret_sync(ptSB + (mir >> 5), 1u << (mir & 31u));
+        return ((~a >> (pos & 31u)) & 1u) | (((~b >> (mir & 31u)) & 1u) << 1);
+    };
+    // the events (pt_done_step) of the lanes that have just turned saturation bits on -- `fired` as set_saturated returns it, `pos` the
+    // first of its two places -- one lane's after the other's: lanes 0 .. 15 take the steps of pos, lanes 16 .. 31 those of its mirror,
+    // two or three blocking round trips per event (a lane on its own: 32 to 96, with the wave waiting).  Every lane of the wave calls it.
+    auto done_events = [&](uint32_t fired, uint32_t pos) __attribute__((always_inline)) {
+        constexpr uint32_t W = K == 27 ? 16u : 8u;
+        uint64_t ev = __builtin_amdgcn_ballot_w64(fired != 0);
+        while (ev != 0) {
+            const uint32_t src = (uint32_t)__builtin_ctzll(ev);
+            ev &= ev - 1;
+            const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fired, (int)src), x0 = (uint32_t)__builtin_amdgcn_readlane((int)pos, (int)src);
+            const uint32_t x = lane < 16u ? x0 : pt_Tp - K - x0;
+            if (lane < 32u && (lane & 15u) < W && ((f >> (lane >> 4)) & 1u)) pt_done_step<true>(ptBKT, ptNEED, ptCNT, ptDONE, x - (lane & 15u));
+        }
+    };
+    auto slow_count = [&](uint32_t klo, uint32_t khi, uint32_t& fired, uint32_t& at) __attribute__((always_inline)) {
         // a window of a run whose 12-mer the index does not cover: through the hash table, on the spot (rare)
         const uint64_t kmer = (uint64_t)khi << 32 | klo, rc = vg_revcomp(kmer, K);
         if (!(K & 1u) && kmer == rc) return;      // src/kmer.cpp:134
@@ -1327,9 +1408,8 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
                     // ... and at both of the k-mer's places in the path table, as bump_all does: later hits through the table skip their atomic
                     const uint32_t pos = vm_load_dword_sync(p.table.pt.PLACE + sl);
                     if (pos != 0u) {
-                        const uint32_t mir = pt_Tp - K - pos;
-                        vm_atomic_or_sync(ptSB + (pos >> 5), 1u << (pos & 31u));
-                        vm_atomic_or_sync(ptSB + (mir >> 5), 1u << (mir & 31u));
+                        fired = set_saturated(pos, pt_Tp - K - pos);      // (its events: the caller, with the whole wave)
+                        at = pos;
                     }
                 }
                 break;
@@ -1343,11 +1423,16 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
         l1_n = run_n < 64u ? run_n : 64u;
         if (lane < l1_n && !(VG_DBG(p.dbg) & 2048u)) {      // 2048: ablation (wrong counts): the runs are popped and forgotten
             l1_run = *reinterpret_cast<lds_u4_rw*>((uintptr_t)(rq_base + rq_wrap(run_head + lane) * 16u));
-            vmp_load_index(pt_index + ((uint64_t)(vg_idx_hash(l1_run.w & 0xFFFFFFu) >> pt_bshift) << 2));
+            const uint32_t bucket = vg_idx_hash(l1_run.w & 0xFFFFFFu) >> pt_bshift;
+            if (ptDONE != nullptr) {
+                vmp_load_done(ptDONE + (bucket >> 5));
+                l1_done_bit = 1u << (bucket & 31u);
+            }
+            vmp_load_index(pt_index + ((uint64_t)bucket << 2));
         }
         run_head = rq_wrap(run_head + l1_n);
         run_n -= l1_n;
-        hot(2);
+        hot(ptDONE != nullptr ? 3 : 2);
         n_after_idx = 0;
         l1_phase = 1;
         __builtin_amdgcn_wave_barrier();
@@ -1357,7 +1442,10 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
         vm_wait4(n_after_idx);
         const uint4 e0 = vmp_index_value<0>(), e1 = vmp_index_value<1>();
         const uint32_t cx = l1_run.w & 0xFFFFFFu;
-        const bool act = lane < l1_n && !(VG_DBG(p.dbg) & (1024u | 2048u));
+        // a run whose bucket is done takes no part in the round: every k-mer its windows could equal is saturated, and nothing in the
+        // bucket sends a run to the hash table
+        const bool done = ptDONE != nullptr && (vmp_done_value() & l1_done_bit) != 0;
+        const bool act = lane < l1_n && !done && !(VG_DBG(p.dbg) & (1024u | 2048u));
         const bool as_is = ((l1_run.w >> 24) & 1u) != 0;
         // entry: x[0:24) the 12-mer, places 0 and 1 in x[24:32) : y[0:11) and y[11:30), y[30] "some 12-mer found no entry in this
         // bucket" (first entry only); places 2 and 3 in z[0:19) and z[19:32) : w[0:6), w[6] "more than four places"
@@ -1376,6 +1464,10 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
         pl[1] = ok && q1 != 0 ? (as_is ? q1 : flip - q1) : 0u;
         pl[2] = ok && q2 != 0 ? (as_is ? q2 : flip - q2) : 0u;
         pl[3] = ok && q3 != 0 ? (as_is ? q3 : flip - q3) : 0u;
+        if (__builtin_amdgcn_ballot_w64(ok || l1_slow) == 0) {      // nothing to compare and nothing for the hash table: the round ends here
+            l1_phase = 0;
+            return;
+        }
         if (__builtin_amdgcn_ballot_w64(pl[0] != 0)) {
             if (pl[0] != 0) vmp_load_place<0>(ptS + (pl[0] >> 4), ptVB + (pl[0] >> 5), ptSB + (pl[0] >> 5));
             hot(3);
@@ -1458,6 +1550,7 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
                     off[q] = on && ((t >> (lane & 15u)) & 1u) ? (pos < mir ? pos : mir) << 2 : 0xFFFFFFFFu;
                 }
                 vm_atomic_inc4_masked_sync(ptPC, off, one, old);
+                uint32_t fired[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if (off[q] != 0xFFFFFFFFu && old[q] == 254u) {
@@ -1469,9 +1562,12 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
                         if (!(K & 1u) && (int32_t)vm_load_dword_sync(counts + sl) < 0) continue;
                         vm_atomic_or_sync(reinterpret_cast<uint32_t*>(&slots8[sl]) + 1, (uint32_t)(VG_SLOT_SAT >> 32));
                         vm_store_byte_sync(p.table.sat_dirty + (sl >> VG_SAT_REGION_LOG2), 1u);
-                        vm_atomic_or_sync(ptSB + (pos >> 5), 1u << (pos & 31u));
-                        vm_atomic_or_sync(ptSB + (mir >> 5), 1u << (mir & 31u));
+                        fired[q] = set_saturated(pos, mir);
                     }
+                }
+                if (ptDONE != nullptr && __builtin_amdgcn_ballot_w64((fired[0] | fired[1] | fired[2] | fired[3]) != 0) != 0) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) done_events(fired[q], off[q] >> 2);
                 }
             }
             return;
@@ -1482,8 +1578,9 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
         // counter of its first window (its own address: a shared dummy would serialise every padded lane of the device).
 #pragma unroll 1
         while (__builtin_amdgcn_ballot_w64(todo != 0) != 0) {
+            uint32_t pos[4] = {0u, 0u, 0u, 0u}, fired[4] = {0u, 0u, 0u, 0u};
             if (todo != 0) {
-                uint32_t pos[4], sl[4], old[4];
+                uint32_t sl[4], old[4];
                 bool live[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -1502,11 +1599,13 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
                         // and the slow path look there) and at both of its places in the path table
                         vm_atomic_or_sync(reinterpret_cast<uint32_t*>(&slots8[sl[q]]) + 1, (uint32_t)(VG_SLOT_SAT >> 32));
                         vm_store_byte_sync(p.table.sat_dirty + (sl[q] >> VG_SAT_REGION_LOG2), 1u);
-                        const uint32_t mir = pt_Tp - K - pos[q];
-                        vm_atomic_or_sync(ptSB + (pos[q] >> 5), 1u << (pos[q] & 31u));
-                        vm_atomic_or_sync(ptSB + (mir >> 5), 1u << (mir & 31u));
+                        fired[q] = set_saturated(pos[q], pt_Tp - K - pos[q]);
                     }
                 }
+            }
+            if (ptDONE != nullptr && __builtin_amdgcn_ballot_w64((fired[0] | fired[1] | fired[2] | fired[3]) != 0) != 0) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) done_events(fired[q], pos[q]);
             }
         }
     };
@@ -1537,19 +1636,21 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
                 left &= left - 1;
                 const uint32_t rx = (uint32_t)__builtin_amdgcn_readlane((int)l1_run.x, (int)src), ry = (uint32_t)__builtin_amdgcn_readlane((int)l1_run.y, (int)src);
                 const uint32_t rz = (uint32_t)__builtin_amdgcn_readlane((int)l1_run.z, (int)src), rw = (uint32_t)__builtin_amdgcn_readlane((int)l1_run.w, (int)src);
+                uint32_t fired = 0, at = 0;      // a window's k-mer reached the clamp on this path: its events, with the whole wave
                 if constexpr (K != 27) {
                     // (window j = the K bases from run base j on: bits [2 (7 - j), + 2 K) of the run's two words)
                     if (lane < 8u && (((rz & 0xFFu) >> lane) & 1u)) {
                         const uint32_t sh2 = 2u * (7u - lane);
-                        slow_count(funnel(ry, rx, sh2), (ry >> sh2) & MASK_HI);
+                        slow_count(funnel(ry, rx, sh2), (ry >> sh2) & MASK_HI, fired, at);
                     }
-                    continue;
+                } else {
+                    const uint32_t v16 = (rz >> 20) | ((rw >> 28) << 12);
+                    if (lane < 16u && ((v16 >> lane) & 1u)) {
+                        const uint32_t sh2 = 2u * (15u - lane);
+                        slow_count(funnel(ry, rx, sh2), funnel(rz, ry, sh2) & MASK_HI, fired, at);
+                    }
                 }
-                const uint32_t v16 = (rz >> 20) | ((rw >> 28) << 12);
-                if (lane < 16u && ((v16 >> lane) & 1u)) {
-                    const uint32_t sh2 = 2u * (15u - lane);
-                    slow_count(funnel(ry, rx, sh2), funnel(rz, ry, sh2) & MASK_HI);
-                }
+                if (ptDONE != nullptr) done_events(fired, at);
             }
         }
         l1_phase = 0;

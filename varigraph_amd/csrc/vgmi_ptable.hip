@@ -151,6 +151,50 @@ __global__ void pt_fill_kernel(TableView t, const uint32_t* key_slot, const uint
     P[2 * n - 1 - pos] = make_ulonglong2(as_is ? R : K, slot);
 }
 
+// The done bits of the path table's buckets against what they claim (vgmi_pt_done_check; tests): a thread per bucket walks the
+// bucket's index entries and decides FROM THE INDEX, VB AND SB ALONE -- neither BKT nor NEED nor CNT -- whether the bucket can become
+// done (an entry, no slow-path flag, a start bit under some window of some effective place) and whether every such start position
+// is saturated.  out: {buckets that can become done, marked done, marked done but not saturated, saturated but not marked}.
+__global__ void pt_done_check_kernel(PathView pt, uint32_t k, unsigned long long* out)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >> pt.bucket_log2) return;
+    const unsigned long long* B = pt.index + ((size_t)b << 2);
+    const uint32_t W = k == 27u ? 16u : 8u, flip = pt.Tp - (k == 27u ? 42u : 2u * k - 12u);
+    bool never = (B[0] >> 62 & 1) != 0, all = true;
+    uint32_t pairs = 0;
+    for (int e = 0; e < 2; ++e) {
+        const unsigned long long lo = B[2 * e], hi = B[2 * e + 1];
+        const uint32_t q[4] = {(uint32_t)(lo >> 24) & 0x7FFFFu, (uint32_t)(lo >> 43) & 0x7FFFFu, (uint32_t)hi & 0x7FFFFu, (uint32_t)(hi >> 19) & 0x7FFFFu};
+        if (q[0] == 0) continue;
+        never |= (hi >> 38 & 1) != 0;
+        for (int i = 0; i < 4; ++i) {
+            if (q[i] == 0) continue;
+            for (int m = 0; m < 2; ++m) {
+                const uint32_t at = m ? flip - q[i] : q[i];
+                for (uint32_t x = at; x < at + W; ++x) {
+                    if (!(pt.VB[x >> 5] >> (x & 31u) & 1u)) continue;
+                    ++pairs;
+                    all &= (pt.SB[x >> 5] >> (x & 31u) & 1u) != 0;
+                }
+            }
+        }
+    }
+    const bool can = !never && pairs != 0;
+    const bool marked = pt.DONE && (pt.DONE[b >> 5] >> (b & 31u) & 1u);
+    if (can) atomicAdd(out + 0, 1ULL);
+    if (marked) atomicAdd(out + 1, 1ULL);
+    if (marked && !(can && all)) atomicAdd(out + 2, 1ULL);
+    if (can && all && !marked) atomicAdd(out + 3, 1ULL);
+}
+
+hipError_t launch_ptable_done_check(const PathView& pt, uint32_t k, unsigned long long* out, hipStream_t st)
+{
+    const uint32_t n = 1u << pt.bucket_log2;
+    hipLaunchKernelGGL(pt_done_check_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pt, k, out);
+    return hipGetLastError();
+}
+
 // mark == nullptr: no check here (a caller that aligns the chains checks with launch_ptable_check once it knows the total)
 hipError_t launch_ptable_order(const TableView& t, const uint32_t* key_slot, uint64_t n, uint32_t* key_of_slot, uint32_t* link, uint32_t* link2,
                                uint32_t* pos_of_key, unsigned long long* cursor, uint32_t* mark, uint32_t* status, hipStream_t st, uint32_t align)

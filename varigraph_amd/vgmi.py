@@ -63,6 +63,7 @@ def load_library():
         "vgmi_counts_finish": (i32, [vp, vp, vp, vp]),
         "vgmi_counts_finish_device": (i32, [vp, vp, vp, vp]),
         "vgmi_count_kernel_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(u64)]),
+        "vgmi_pt_done_check": (i32, [vp, C.POINTER(u64)]),
         "vgmi_counts_export_device": (i32, [vp, vp]),
         "vgmi_counts_import_device": (i32, [vp, vp]),
         "vgmi_fastq_open": (i32, [vp, C.POINTER(vp)]),
@@ -326,6 +327,13 @@ class Context:
         ms, n = C.c_float(), C.c_uint64()
         self._chk(self._l.vgmi_count_kernel_ms(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def pt_done_check(self):
+        """Small graphs: (buckets that can become done, marked done, marked but not fully saturated, saturated but not marked) --
+        the path table's done bits against the index and the saturation bits (vgmi_pt_done_check)."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self._l.vgmi_pt_done_check(self._h, out))
+        return tuple(int(v) for v in out)
 
     def fastq_text(self, text, piece=None):
         """Device-side FASTQ parser over one stream of file text (bytes), committed in pieces of `piece` bytes (default:
