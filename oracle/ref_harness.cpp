@@ -9,6 +9,7 @@
 //   ConstructIndex::load_index / graph2node                              (include/construct_index.hpp)
 //   FastqKmer::build_fastq_index                                         (include/fastq_kmer.hpp)
 //   Varigraph::get_hom_kmer / get_hom_kmer_c / cal_hap_kmer_cov          (include/varigraph.hpp)
+//   GENOTYPE::find_most_likely_depth / calculate_poisson_interval        (include/genotype.hpp)
 //
 // Sub-commands (all output is little-endian binary or plain text on stdout):
 //   hash64 K                      stdin: one hex canonical k-mer value per line -> hash64 hex
@@ -21,6 +22,8 @@
 //                                 (seeds are random unless this is the det_shim build, ref_harness_det)
 //   count GRAPH THREADS OUT FQ...  load_index + build_fastq_index; writes OUT (see below); prints timing
 //   sample GRAPH THREADS PLOIDY USEDEPTH OUT FQ...   count + graph2node + hom-kmer statistics
+//   depthrule AVE OUT [LOWER UPPER]  GENOTYPE::find_most_likely_depth for every (h, c, f); AVE the hex bits of a float, LOWER and
+//                                 UPPER of two doubles (else GENOTYPE::calculate_poisson_interval); prints the bits it used
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -227,6 +230,36 @@ static int cmd_count(int argc, char** argv, bool sample) {
     return 0;
 }
 
+// GENOTYPE::find_most_likely_depth (src/genotype.cpp:1136-1158) over its whole domain: h 0..8, c 0..255, f 1..255 for one average and
+// one interval.  OUT: 9 x 256 x 255 bytes, [h][c][f - 1].  The interval is GENOTYPE::calculate_poisson_interval's of the average, as
+// observable_states calls it (:985-987: the float average handed over as a double), unless both bounds are given.
+static int cmd_depthrule(int argc, char** argv) {
+    uint32_t ab = (uint32_t)strtoul(argv[2], nullptr, 16);
+    float ave;
+    memcpy(&ave, &ab, 4);
+    double lower = 256.0f, upper = -0.1f;
+    if (argc >= 6) {
+        uint64_t lb = strtoull(argv[4], nullptr, 16), ub = strtoull(argv[5], nullptr, 16);
+        memcpy(&lower, &lb, 8);
+        memcpy(&upper, &ub, 8);
+    } else {
+        GENOTYPE::calculate_poisson_interval(ave, lower, upper);
+    }
+    ofstream o(argv[3], ios::binary);
+    for (int h = 0; h <= 8; ++h)
+        for (int c = 0; c < 256; ++c)
+            for (int f = 1; f < 256; ++f) {
+                uint8_t hh = (uint8_t)h, cc = (uint8_t)c, ff = (uint8_t)f;
+                GENOTYPE::find_most_likely_depth(hh, cc, ff, ave, lower, upper);
+                put<uint8_t>(o, cc);
+            }
+    uint64_t lb, ub;
+    memcpy(&lb, &lower, 8);
+    memcpy(&ub, &upper, 8);
+    printf("ave_bits %08x\nlower_bits %016llx\nupper_bits %016llx\n", ab, (unsigned long long)lb, (unsigned long long)ub);
+    return o.good() ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: ref_harness <cmd> ...\n"); return 2; }
     string c = argv[1];
@@ -238,6 +271,7 @@ int main(int argc, char** argv) {
     if (c == "mbf" && argc >= 5) return cmd_mbf(argc, argv);
     if (c == "count" && argc >= 6) return cmd_count(argc, argv, false);
     if (c == "sample" && argc >= 8) return cmd_count(argc, argv, true);
+    if (c == "depthrule" && (argc == 4 || argc == 6)) return cmd_depthrule(argc, argv);
     fprintf(stderr, "bad command line\n");
     return 2;
 }
