@@ -176,6 +176,13 @@ int vgmi_count_kernel_ms(vgmi_ctx *ctx, float *ms, uint64_t *launches);
  * out[1] buckets marked done, out[2] marked done but not fully saturated (0, always), out[3] fully saturated but not
  * marked (0 once the stream is idle; every such bucket with VGMI_PT_DONE=0).  All zero without a path table. */
 int vgmi_pt_done_check(vgmi_ctx *ctx, uint64_t out[4]);
+/* Small graphs: deep into a sample the count kernel probes a LIVE image of its grid filter, one that holds only the 12-mers of
+ * buckets not yet done (VGMI_PT_LIVE, VGMI_PT_LIVE_BYTES).  This recomputes from the keys and the done bits alone, after everything
+ * submitted so far: out[0] 12-mers of the keys whose bucket is not done and whose bits are not all set in the image in use
+ * (0, always), out[1] words of the image with a bit the static filter lacks (0, always), out[2] the image's set bits, out[3]
+ * refreshes since the reset that built a new image.  With no image in use the static filter is the image.  All zero without a
+ * path table. */
+int vgmi_pt_live_check(vgmi_ctx *ctx, uint64_t out[4]);
 
 /* ---- device-side FASTQ parsing -----------------------------------------------------------------
  * replaces: kseq_read + the per-record sequence copy of FastqKmer::fastq_file_open (include/kseq.h:192-232,

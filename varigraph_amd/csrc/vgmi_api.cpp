@@ -81,6 +81,13 @@ void free_table(vgmi_ctx* c)
         if (q) (void)hipFree(q);
     c->d_pt_index = nullptr;
     c->d_pt_S = c->d_pt_VB = c->d_pt_SB = c->d_pt_SLOT = c->d_pt_PLACE = c->d_pt_BKT = c->d_pt_NEED = nullptr;
+    if (c->d_pt_live) (void)hipFree(c->d_pt_live);
+    c->d_pt_live = nullptr;
+    for (auto& e : c->live_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    live_drop(c);
     c->tv.pt = PathView{};
     c->d_xt_lines = nullptr;
     c->d_xt_counts = nullptr;
@@ -258,6 +265,71 @@ static void count27_geometry(vgmi_ctx* c, bool lds_filter, uint32_t& grid, uint3
     else            { block = 256;  grid = (uint32_t)c->n_cu * (c->wgs_per_cu ? c->wgs_per_cu : 4); }
 }
 
+void live_drop(vgmi_ctx* c)
+{
+    std::lock_guard<std::mutex> lk(c->live_mu);
+    c->live_bytes = 0;
+    c->live_due = c->live_unit;
+    c->live_n = 0;
+}
+
+// count27s_kernel over the block's pairs of rows with the live filter in place of the static grid filter -- in the fast kernel's
+// copy of the parameters alone: the exact tail and the debit pass keep `p`.  Refreshes are due at L, 4 L, 16 L, ... bytes counted here since
+// the reset.  A block whose length the host knows is cut at a due point it crosses, at a boundary of row pairs with a pair at least on
+// either side: head, build, rest with the new image (the first wave of the rest walks the pair in front of the cut as halo, as waves
+// inside a launch do; a k-mer across the cut is counted once, by the rest).  Where no cut is possible, and behind a block whose length
+// lives in device memory (n_bytes is then its bound), a due refresh runs behind the block.
+// Streams: image j is written by build j alone, between two resets, and every launch that is handed it on another stream than the
+// build's waits for the build's event first; so does a build for the image it may copy.
+static int launch_small_live(vgmi_ctx* c, const RowParams& p, size_t n_bytes, hipStream_t st)
+{
+    if (!c->d_pt_live || !p.table.pt.DONE) {      // VGMI_PT_LIVE=0, VGMI_PT_DONE=0, no path table
+        HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
+        return VGMI_OK;
+    }
+    std::lock_guard<std::mutex> lk(c->live_mu);
+    RowParams pf = p;
+    auto image = [&](uint32_t j) { return c->d_pt_live + (size_t)j * VG_GRID_LDS_WORDS; };
+    auto use_current = [&]() -> hipError_t {      // pf.table.grid: the image in use, its build finished as far as `st` is concerned
+        if (c->live_n == 0) return hipSuccess;
+        const uint32_t j = c->live_n - 1;
+        pf.table.grid = image(j);
+        return c->live_st[j] == st ? hipSuccess : hipStreamWaitEvent(st, c->live_ev[j], 0);
+    };
+    auto refresh = [&]() -> hipError_t {      // the due point is served (a cut lies up to a pair of rows in front of it), and those behind it that the block has passed
+        do c->live_due *= c->live_factor;
+        while (c->live_due <= c->live_bytes);
+        if (c->live_n >= VG_LIVE_IMAGES) return hipSuccess;
+        hipError_t e = use_current();      // (the build reads the image in use)
+        const uint32_t j = c->live_n;
+        if (e == hipSuccess) e = launch_ptable_live_build(c->tv, c->d_key_slot, c->hdr.n_keys, pf.table.grid, image(j), j, st);
+        if (e == hipSuccess) e = hipEventRecord(c->live_ev[j], st);
+        if (e != hipSuccess) return e;
+        c->live_st[j] = st;
+        c->live_n = j + 1;
+        return hipSuccess;
+    };
+    const uint64_t base = c->live_bytes, pairs = p.n_bytes_dev ? 0 : p.row_end >> 1;
+    uint64_t from = 0;
+    while (pairs) {
+        // the next due point inside the block, as a pair of rows
+        const uint64_t cut = c->live_due > base ? (c->live_due - base) >> 11 : 0;
+        if (c->live_due >= base + n_bytes || cut <= from || cut >= pairs) break;
+        HIPCHK(c, use_current());
+        pf.pair_begin = from, pf.row_end = 2 * cut;
+        HIPCHK(c, launch_count27s(pf, (uint32_t)c->n_cu, st));
+        c->live_bytes = base + (cut << 11);
+        HIPCHK(c, refresh());
+        from = cut;
+    }
+    HIPCHK(c, use_current());
+    pf.pair_begin = from, pf.row_end = p.row_end;
+    HIPCHK(c, launch_count27s(pf, (uint32_t)c->n_cu, st));
+    c->live_bytes = base + n_bytes;
+    if (c->live_due <= c->live_bytes) HIPCHK(c, refresh());
+    return VGMI_OK;
+}
+
 // Every read block goes through here.  Which kernel serves which graph, how a block is split between the fast kernel and the exact tail,
 // and which launches follow from that are decided in vgmi_count_plan.h (count_plan, vg_row_split); this function only carries the plan out,
 // in stream order: clamp, debit pass (even k), fast kernel, tail.
@@ -306,9 +378,11 @@ int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_
         else HIPCHK(c, launch_count27x(p, c->tv.xt, (uint32_t)c->n_cu * 8, st));
         break;
     case VG_FAST_SMALL27:
-    case VG_FAST_SMALLK:
-        HIPCHK(c, launch_count27s(p, (uint32_t)c->n_cu, st));
+    case VG_FAST_SMALLK: {
+        int rc = launch_small_live(c, p, n_bytes, st);
+        if (rc) return rc;
         break;
+    }
     case VG_FAST_ROWS27:
         count27_geometry(c, caps.fast27_lds, grid, block);
         HIPCHK(c, launch_count27(caps.fast27_lds, p, grid, block, st));
@@ -525,6 +599,7 @@ int vgmi_counts_reset(vgmi_ctx* c)
     if (c->d_counts) HIPCHK(c, hipMemsetAsync(c->d_counts, 0, c->n_counts * 4, c->stream));
     if (!c->tv.xt.counts && (!c->d_counts || c->tv.slots8)) HIPCHK(c, launch_counts_reset(c->tv, c->stream));   // in-slot counters / saturation flags
     if (c->tv.pt.SB) HIPCHK(c, hipMemsetAsync(c->d_pt_SB, 0, c->pt_sb_bytes, c->stream));                       // ... and their copies in the path table
+    live_drop(c);                                                                                             // (DONE is cleared: the static grid filter is back in use)
     HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4, c->stream));
     // host blocks are counted on the stages' own (non-blocking) streams: their next launch waits for this reset
     HIPCHK(c, hipEventRecord(c->reset_done, c->stream));
@@ -688,6 +763,7 @@ static int counts_xfer(vgmi_ctx* c, uint32_t* dev, bool import)
     if (c->tv.xt.counts) HIPCHK(c, launch_xcounts_xfer(c->tv.xt, c->d_xt_id, dev, c->hdr.n_keys, import, c->stream));
     else HIPCHK(c, launch_counts_xfer(c->tv, c->d_key_slot, dev, c->hdr.n_keys, import, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (import) live_drop(c);      // the counters are replaced
     return VGMI_OK;
 }
 
@@ -723,6 +799,35 @@ int vgmi_pt_done_check(vgmi_ctx* c, uint64_t out[4])
     if (he == hipSuccess) he = launch_ptable_done_check(c->tv.pt, c->hdr.k, d, c->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
     if (he == hipSuccess) he = hipMemcpy(out, d, 32, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHK(c, he);
+    return VGMI_OK;
+}
+
+int vgmi_pt_live_check(vgmi_ctx* c, uint64_t out[4])
+{
+    if (!c || !out) return VGMI_E_INVALID;
+    if (!c->has_table) return fail(c, VGMI_E_STATE, "no table");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!c->tv.pt.index || !c->tv.grid || c->hdr.grid_words_log2 != VG_GRID_LDS_WORDS_LOG2) return VGMI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = sync_stages(c);
+    if (rc) return rc;
+    HIPCHK(c, hipDeviceSynchronize());      // (an image may have been built on a reader's stream)
+    const uint32_t* image = c->tv.grid;
+    {
+        std::lock_guard<std::mutex> lk(c->live_mu);
+        if (c->d_pt_live && c->live_n) image = c->d_pt_live + (size_t)(c->live_n - 1) * VG_GRID_LDS_WORDS;
+    }
+    unsigned long long* d = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), 32));
+    hipError_t he = hipMemsetAsync(d, 0, 32, c->stream);
+    if (he == hipSuccess) he = launch_ptable_live_check(c->tv, c->d_key_slot, c->hdr.n_keys, image, d, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he == hipSuccess) he = hipMemcpy(out, d, 24, hipMemcpyDeviceToHost);
+    uint32_t builds = 0;
+    if (he == hipSuccess && c->tv.pt.DONE_N) he = hipMemcpy(&builds, c->tv.pt.DONE_N + 2, 4, hipMemcpyDeviceToHost);
+    out[3] = builds;
     (void)hipFree(d);
     HIPCHK(c, he);
     return VGMI_OK;

@@ -614,7 +614,8 @@ int build_ptable(vgmi_ctx* c)
     // the saturation bits and, behind them, the position counters: one allocation, one memset per sample (vgmi_counts_reset)
     // ... and the buckets' CNT and DONE (PathView)
     const size_t pc_words = (size_t)Tp + 64, cnt_words = pt_done ? n_buckets : 0, done_words = pt_done ? (n_buckets + 31) / 32 : 0;
-    const size_t sb_words = VB.size() + pc_words + cnt_words + done_words;
+    const size_t live_words = pt_done ? VG_LIVE_WORDS : 0;      // DONE_N and the live filter's words behind it
+    const size_t sb_words = VB.size() + pc_words + cnt_words + done_words + live_words;
     if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_SB), sb_words * 4);
     if (pt_done) {
         if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&c->d_pt_BKT), BKT.size() * 4);
@@ -655,6 +656,23 @@ int build_ptable(vgmi_ctx* c)
         c->tv.pt.NEED = c->d_pt_NEED;
         c->tv.pt.CNT = c->d_pt_SB + VB.size() + pc_words;
         c->tv.pt.DONE = c->tv.pt.CNT + cnt_words;
+        c->tv.pt.DONE_N = c->tv.pt.DONE + done_words;
+    }
+    // The live filter: images of the grid filter without the 12-mers of done buckets, refreshed as the sample gets deeper
+    // (launch_small_live, vgmi_api.cpp).  VGMI_PT_LIVE=0: none (A/B); VGMI_PT_LIVE_BYTES: the first refresh's due point, L (default 1 GiB; the next ones at 4 L, 16 L, ...)
+    {
+        const char* lv = getenv("VGMI_PT_LIVE");
+        const char* lb = getenv("VGMI_PT_LIVE_BYTES");
+        const unsigned long long unit = lb ? strtoull(lb, nullptr, 10) : 1ull << 30;
+        c->live_unit = unit < 2048 ? 2048 : unit;
+        const char* lf = getenv("VGMI_PT_LIVE_FACTOR");      // (the spacing of the due points, for measuring: profiles/pt_live.json)
+        const int factor = lf ? atoi(lf) : 4;
+        c->live_factor = (uint32_t)(factor < 2 ? 2 : factor > 16 ? 16 : factor);
+        live_drop(c);
+        if (pt_done && !(lv && lv[0] == '0') && c->tv.grid && h.grid_words_log2 == VG_GRID_LDS_WORDS_LOG2) {
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_pt_live), (size_t)VG_LIVE_IMAGES * VG_GRID_LDS_WORDS * 4));
+            for (auto& e : c->live_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
     }
     c->tv.pt.bucket_log2 = bucket_log2;
     c->tv.pt.Tp = (uint32_t)Tp;

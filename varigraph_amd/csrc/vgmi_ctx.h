@@ -102,6 +102,17 @@ struct vgmi_ctx {
     uint32_t *d_pt_S = nullptr, *d_pt_VB = nullptr, *d_pt_SB = nullptr, *d_pt_SLOT = nullptr, *d_pt_PLACE = nullptr;   // sequence, k-mer starts, saturation bits, slots, places by slot
     uint32_t *d_pt_BKT = nullptr, *d_pt_NEED = nullptr;   // buckets whose every k-mer is saturated: the static side (PathView::BKT, ::NEED)
     size_t pt_sb_bytes = 0;                     // d_pt_SB's bytes: the saturation bits and, behind them, the position counters (PathView::PC) and the buckets' CNT and DONE
+    // the live filter (VGMI_PT_LIVE=0: d_pt_live is null and none of this is in use): VG_LIVE_IMAGES images of the grid filter,
+    // one per refresh of a sample, none rewritten between resets.  All under live_mu, which a launch holds from the choice of its image to
+    // the record of the build it queues: another stream is never handed an image whose event is not recorded yet.  (Order: live_mu, then mu.)
+    uint32_t* d_pt_live = nullptr;
+    std::mutex live_mu;
+    uint64_t live_unit = 1ull << 30;            // L: refreshes are due at L, 4 L, 16 L, ... bytes counted on the path (VGMI_PT_LIVE_BYTES)
+    uint32_t live_factor = 4;                   // ... the 4 (VGMI_PT_LIVE_FACTOR, 2 .. 16: for measuring; VG_LIVE_IMAGES is sized for 4)
+    uint64_t live_bytes = 0, live_due = 0;      // bytes counted on fast paths 3 and 4 since the reset; the next due point
+    uint32_t live_n = 0;                        // builds queued since the reset: image live_n - 1 is the one in use (0: the static filter)
+    hipEvent_t live_ev[VG_LIVE_IMAGES] = {};    // recorded behind build j ...
+    hipStream_t live_st[VG_LIVE_IMAGES] = {};   // ... on this stream
     uint64_t pt_slow_cx = 0, pt_bucket_ovf = 0;  // 12-mers with more than two places / buckets with a third 12-mer (those runs take the hash table)
     uint64_t xt_over_keys = 0;                  // pairs (key, 16-mer) that overflowed in the last build
     uint8_t* d_sat_dirty = nullptr;   // compact format: 2048-slot regions holding a saturation flag (the reset sweeps those)
@@ -169,6 +180,7 @@ bool ctable_wanted(const ImageHeader& h);
 // vgmi_api.cpp: counting
 int launch_count(vgmi_ctx* c, const char* d_bases, size_t n_bytes, const uint64_t* d_read_off, size_t n_reads, hipStream_t st,
                  const unsigned long long* n_bytes_dev = nullptr, const unsigned long long* n_reads_dev = nullptr);
+void live_drop(vgmi_ctx* c);      // the live filter's image is dropped, the static filter is back in use: wherever DONE is cleared or the counters are replaced
 int collect_timing(vgmi_ctx* c);
 int ensure_stage(vgmi_ctx* c, Stage& s);
 int sync_stages(vgmi_ctx* c);

@@ -245,6 +245,19 @@ VG_HD void vg_grid12_probe(uint32_t mer12, uint32_t& word, uint32_t& mask)
     mask = (1u << (h2 >> 27)) | (1u << ((h2 >> 22) & 31u)) | (1u << ((h2 >> 17) & 31u));
 }
 
+// the k - 11 twelve-mers of a graph k-mer (16 at k = 27) as the grid filter holds them: f(canonical 12-mer, filter word, its three bits).
+// One loop under the static filter's build (table_insert_kernel) and the live filter's (vgmi_ptable.hip).
+template <class F>
+VG_HD void vg_grid12_of_kmer(uint64_t canon, uint32_t k, F f)
+{
+    for (uint32_t off = 0; off + 11u < k; ++off) {
+        const uint32_t mer = (uint32_t)(canon >> (2 * off)) & 0xFFFFFFu, rc = vg_revcomp12(mer);
+        uint32_t w, m;
+        vg_grid12_probe(mer, w, m);
+        f(mer < rc ? mer : rc, w, m);
+    }
+}
+
 // bucket hash of the path table's 12-mer index (build_ptable, count27s_kernel: once per run, not per position -- two 32-bit multiplies
 // are affordable here, and the plain multiplicative hash left three times the expected number of overfull buckets)
 VG_HD uint32_t vg_idx_hash(uint32_t cx)

@@ -59,10 +59,20 @@ struct PathView {
     // ... per sample, behind SB and PC in their allocation:
     uint32_t* CNT;                     // per bucket: its pairs whose position is saturated (pt_done_event)
     uint32_t* DONE;                    // bit per bucket: CNT has reached NEED -- a run of this bucket has no hit left to count
+    uint32_t* DONE_N;                  // VG_LIVE_WORDS words, cleared with DONE: the live filter's book-keeping (vgmi_ptable.hip) and, from word 16 on,
+                                       // the number of bits set in DONE, in 64 parts 64 bytes apart (vg_done_n_part: the addition that sets a bit
+                                       // counts it in the part of its bucket)
     uint32_t bucket_log2;
     uint32_t Tp;                       // bases in S, pads included: S[Tp - 1 - j] is the complement of S[j]
 };
 #define VG_PT_NO_BUCKET 0xFFFFFFFFu
+// the live filter: images of the 12-mer grid filter that hold only the 12-mers of buckets not yet done, one per refresh
+#define VG_LIVE_IMAGES 8u             // refreshes of one sample that build an image (due at L, 4 L, 16 L, ... bytes: 16 TiB with L = 1 GiB)
+#define VG_LIVE_WORDS (16u + 64u * 16u)      // PathView::DONE_N[1] the done buckets at the last build, [2] builds that made a new image, [4 + j] build j
+                                      // found their number changed (pt_live_begin_kernel decides, pt_live_build_kernel follows); [16 + 16 s] part s of
+                                      // the number of done buckets.  (Parts: in a deep sample the buckets become done within a short stretch of a launch, and
+                                      // 5e4 returning additions to ONE word cost the bench's step 0.6 ms.)
+__host__ __device__ inline uint32_t vg_done_n_part(uint32_t bucket) { return 16u + ((bucket & 63u) << 4); }
 
 struct TableView {
     VgSlot* slots;              // cap entries (16-byte format) or nullptr
@@ -97,6 +107,8 @@ struct RowParams {
     const uint8_t* bases;
     uint64_t n_bytes;
     uint64_t row_begin;   // rows_kernel: first 1 KiB row to process (earlier rows only provide the halo)
+    uint64_t pair_begin;  // count27s_kernel: the first pair of rows this launch counts (a block cut at a refresh of the live filter, launch_count;
+                          // `bases` still points at the block's start, pair pair_begin - 1 is walked as halo); 0 with n_bytes_dev
     uint64_t row_end;     // count27_kernel, count27s_kernel: one past the last row; every row below it is complete (vg_row_split, vgmi_count_plan.h)
     uint64_t emit_from;   // the exact tail (rows_kernel<COUNT>, seq_kernel<COUNT>) counts only k-mers ENDING at stream position >= emit_from, the
                           // debit pass works in front of it: the fast kernel covers the ends up to there (vg_row_split)
@@ -432,6 +444,10 @@ hipError_t launch_ptable_order(const TableView& t, const uint32_t* key_slot, uin
                                uint32_t* pos_of_key, unsigned long long* cursor, uint32_t* mark, uint32_t* status, hipStream_t st, uint32_t align = 1);
 hipError_t launch_ptable_check(const uint32_t* pos_of_key, uint64_t n, uint64_t total, uint32_t* mark, uint32_t* status, hipStream_t st);
 hipError_t launch_ptable_done_check(const PathView& pt, uint32_t k, unsigned long long* out, hipStream_t st);      // out: four counts, zeroed by the caller
+// the live filter: image `dst` from the keys and DONE (a copy of `src`, the image in use, where no bucket has become done since the last
+// build); `build` numbers the sample's refreshes.  launch_ptable_live_check: vgmi_pt_live_check's four counts, zeroed by the caller
+hipError_t launch_ptable_live_build(const TableView& t, const uint32_t* key_slot, uint64_t n, const uint32_t* src, uint32_t* dst, uint32_t build, hipStream_t st);
+hipError_t launch_ptable_live_check(const TableView& t, const uint32_t* key_slot, uint64_t n, const uint32_t* image, unsigned long long* out, hipStream_t st);
 hipError_t launch_ptable_fill(const TableView& t, const uint32_t* key_slot, const uint32_t* pos_of_key, uint64_t n, ulonglong2* P, hipStream_t st);
 hipError_t launch_rows(int mode, bool flds, const RowParams& p, uint32_t grid, uint32_t block, hipStream_t st);
 hipError_t launch_bloom_even(const RowParams& p, hipStream_t st);   // even k, one long sequence (K3)

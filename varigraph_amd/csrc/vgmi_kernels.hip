@@ -163,19 +163,27 @@ __device__ __forceinline__ uint32_t pt_counted(const TableView& t, uint64_t s)
 __device__ __forceinline__ uint32_t vm_load_dword_sync(const uint32_t* ptr);
 __device__ __forceinline__ void vm_load_and_inc_sync(const uint32_t* ld, uint32_t* at, uint32_t one, uint32_t& v, uint32_t& old);
 __device__ __forceinline__ void vm_atomic_or_sync(uint32_t* ptr, uint32_t bits);
+__device__ __forceinline__ void vm_atomic_add_sync(uint32_t* ptr, uint32_t v);
+// (DONE_N counts the bits of DONE, behind the bit it counts: the live filter's build looks at it to see whether anything changed)
 template <bool HOT>
-__device__ __forceinline__ void pt_done_step(const uint32_t* BKT, const uint32_t* NEED, uint32_t* CNT, uint32_t* DONE, uint32_t q)
+__device__ __forceinline__ void pt_done_step(const uint32_t* BKT, const uint32_t* NEED, uint32_t* CNT, uint32_t* DONE, uint32_t* DONE_N, uint32_t q)
 {
     if constexpr (HOT) {
         const uint32_t b = vm_load_dword_sync(BKT + q);
         if (b == VG_PT_NO_BUCKET) return;
         uint32_t need, old;
         vm_load_and_inc_sync(NEED + b, CNT + b, 1u, need, old);
-        if (old + 1u == need) vm_atomic_or_sync(DONE + (b >> 5), 1u << (b & 31u));
+        if (old + 1u == need) {
+            vm_atomic_or_sync(DONE + (b >> 5), 1u << (b & 31u));
+            vm_atomic_add_sync(DONE_N + vg_done_n_part(b), 1u);
+        }
     } else {
         const uint32_t b = BKT[q];
         if (b == VG_PT_NO_BUCKET) return;
-        if (atomicAdd(&CNT[b], 1u) + 1u == NEED[b]) atomicOr(&DONE[b >> 5], 1u << (b & 31u));
+        if (atomicAdd(&CNT[b], 1u) + 1u == NEED[b]) {
+            atomicOr(&DONE[b >> 5], 1u << (b & 31u));
+            atomicAdd(DONE_N + vg_done_n_part(b), 1u);
+        }
     }
 }
 // a whole event by the lane that raised it (the generic kernels: a few per k-mer and sample; count27s_kernel spreads the steps over lanes)
@@ -183,7 +191,7 @@ __device__ __forceinline__ void pt_done_event(const PathView& pt, uint32_t k, ui
 {
     if (!pt.DONE) return;
     const uint32_t W = k == 27u ? 16u : 8u;
-    for (uint32_t j = 0; j < W; ++j) pt_done_step<false>(pt.BKT, pt.NEED, pt.CNT, pt.DONE, x - j);
+    for (uint32_t j = 0; j < W; ++j) pt_done_step<false>(pt.BKT, pt.NEED, pt.CNT, pt.DONE, pt.DONE_N, x - j);
 }
 
 // exact-table probe + saturating count of one canonical k-mer (generic kernels; either table format)
@@ -815,6 +823,10 @@ __device__ __forceinline__ void vm_atomic_or_sync(uint32_t* ptr, uint32_t bits)
 {
     asm volatile("global_atomic_or %0, %1, off ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT" : : "v"(ptr), "v"(bits) : "memory");
 }
+__device__ __forceinline__ void vm_atomic_add_sync(uint32_t* ptr, uint32_t v)
+{
+    asm volatile("global_atomic_add %0, %1, off ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT" : : "v"(ptr), "v"(v) : "memory");
+}
 __device__ __forceinline__ void vm_store_byte_sync(uint8_t* ptr, uint32_t v)
 {
     asm volatile("global_store_byte %0, %1, off ; VGHOT\n\ts_waitcnt vmcnt(0) ; VGHOT" : : "v"(ptr), "v"(v) : "memory");
@@ -1289,11 +1301,13 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
     const uint64_t cap_mask = p.table.cap_mask;
 
     // rows [0, row_end) are complete 1 024-byte rows, row_end even: a wave walks a contiguous range of row PAIRS
+    // (a launch behind a cut of the block -- launch_count, the live filter's refreshes -- walks [pair_begin, total_pairs); pair_begin is 0 otherwise)
     const uint64_t total_pairs = p.n_bytes_dev ? *p.n_bytes_dev / (2 * VG_ROW27S) : p.row_end >> 1;      // (vg_row_split(VG_FAST_SMALL27).row_end / 2, as in count27_kernel)
+    const uint64_t pair_begin = p.n_bytes_dev ? 0u : p.pair_begin;
     const uint64_t total_waves = (uint64_t)gridDim.x * nwaves;
-    const uint64_t ppw = (total_pairs + total_waves - 1) / total_waves;
+    const uint64_t ppw = (total_pairs - pair_begin + total_waves - 1) / total_waves;
     const uint64_t gw = (uint64_t)blockIdx.x * nwaves + wave_u;
-    const uint64_t r0v = gw * ppw;
+    const uint64_t r0v = pair_begin + gw * ppw;
     const uint64_t r1v = r0v + ppw < total_pairs ? r0v + ppw : total_pairs;
     const uint64_t r0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(r0v >> 32)) << 32) |
                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r0v);
@@ -1357,6 +1371,7 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
     const uint32_t* const ptBKT = p.table.pt.BKT;
     const uint32_t* const ptNEED = p.table.pt.NEED;
     uint32_t* const ptCNT = p.table.pt.CNT;
+    uint32_t* const ptDONE_N = p.table.pt.DONE_N;
     uint32_t* const ptDONE = p.table.pt.DONE;             // nullptr (VGMI_PT_DONE=0): no bucket is ever done, no event is raised
     const uint32_t pt_Tp = p.table.pt.Tp, pt_bshift = 32u - p.table.pt.bucket_log2;
     const uint32_t l1_min = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.l1_min);
@@ -1388,7 +1403,7 @@ __global__ __launch_bounds__(1024) void count27s_kernel(RowParams p)
             ev &= ev - 1;
             const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fired, (int)src), x0 = (uint32_t)__builtin_amdgcn_readlane((int)pos, (int)src);
             const uint32_t x = lane < 16u ? x0 : pt_Tp - K - x0;
-            if (lane < 32u && (lane & 15u) < W && ((f >> (lane >> 4)) & 1u)) pt_done_step<true>(ptBKT, ptNEED, ptCNT, ptDONE, x - (lane & 15u));
+            if (lane < 32u && (lane & 15u) < W && ((f >> (lane >> 4)) & 1u)) pt_done_step<true>(ptBKT, ptNEED, ptCNT, ptDONE, ptDONE_N, x - (lane & 15u));
         }
     };
     auto slow_count = [&](uint32_t klo, uint32_t khi, uint32_t& fired, uint32_t& at) __attribute__((always_inline)) {
@@ -2394,11 +2409,7 @@ __global__ void table_insert_kernel(TableView t, const uint64_t* keys, uint64_t 
     key_slot[i] = (uint32_t)s;
     atomicOr(&filter_rw[vg_fhash_word(canon) >> t.filter_shift], vg_fhash_bits(canon, t.filter_words_log2));
     if (grid_rw && grid12) {   // small graphs: the k - 11 twelve-mers of the k-mer (16 at k = 27; vgmi_device.h, VG_GRID12_*)
-        for (uint32_t off = 0; off + 11u < k; ++off) {
-            uint32_t w, m;
-            vg_grid12_probe((uint32_t)(canon >> (2 * off)) & 0xFFFFFFu, w, m);
-            atomicOr(&grid_rw[w], m);
-        }
+        vg_grid12_of_kmer(canon, k, [&](uint32_t, uint32_t w, uint32_t m) { atomicOr(&grid_rw[w], m); });
     } else if (grid_rw) {   // k = 27 only: the 12 sixteen-mers of the k-mer (canonicalised inside vg_grid_probe, which
                      // makes the reverse complement's twelve the same entries)
         const bool wide = t.grid_words_log2 != VG_GRID_LDS_WORDS_LOG2;   // global variant: 64-bit entries + offset bits

@@ -195,6 +195,77 @@ hipError_t launch_ptable_done_check(const PathView& pt, uint32_t k, unsigned lon
     return hipGetLastError();
 }
 
+// ---- the live filter: the grid filter less the 12-mers of done buckets ----
+// A refresh is two launches in stream order.  pt_live_begin_kernel clears the image and one thread decides, for every block of the build
+// alike, whether anything has changed: the number of done buckets (the parts of DONE_N) against its value at the last build.  The words behind DONE_N (VG_LIVE_WORDS) are cleared
+// with DONE.
+__global__ void pt_live_begin_kernel(PathView pt, uint32_t* dst, uint32_t build)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < VG_GRID_LDS_WORDS / 4) reinterpret_cast<uint4*>(dst)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (i == 0) {
+        uint32_t n = 0;
+        for (uint32_t s = 0; s < 64u; ++s) n += atomicAdd(pt.DONE_N + vg_done_n_part(s), 0u);
+        const uint32_t changed = n != pt.DONE_N[1];
+        pt.DONE_N[1] = n;
+        pt.DONE_N[4 + build] = changed;
+        if (changed) pt.DONE_N[2] += 1u;
+    }
+}
+
+// Nothing changed: the image in use stays -- `dst` becomes a copy of it, and the keys are not looked at.  Else the keys' 12-mers as
+// table_insert_kernel sets them (vg_grid12_of_kmer), those of done buckets left out.  DONE may gain bits on other streams while this
+// runs: a bit not yet seen leaves its 12-mers in the image, which only sends their runs the long way (DONE is monotone between resets).
+__global__ void pt_live_build_kernel(TableView t, const uint32_t* key_slot, uint64_t n, const uint32_t* src, uint32_t* dst, uint32_t build)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!t.pt.DONE_N[4 + build]) {
+        for (uint64_t w = i; w < VG_GRID_LDS_WORDS / 4; w += (uint64_t)gridDim.x * blockDim.x)
+            reinterpret_cast<uint4*>(dst)[w] = reinterpret_cast<const uint4*>(src)[w];
+        return;
+    }
+    if (i >= n) return;
+    const uint32_t bshift = 32u - t.pt.bucket_log2;
+    vg_grid12_of_kmer(t.slots8[key_slot[i]] & PT_MASK54, t.k, [&](uint32_t cm, uint32_t w, uint32_t m) {
+        const uint32_t bucket = vg_idx_hash(cm) >> bshift;      // (as phase 1 of the drain finds it)
+        if (!(t.pt.DONE[bucket >> 5] >> (bucket & 31u) & 1u)) atomicOr(&dst[w], m);
+    });
+}
+
+hipError_t launch_ptable_live_build(const TableView& t, const uint32_t* key_slot, uint64_t n, const uint32_t* src, uint32_t* dst, uint32_t build, hipStream_t st)
+{
+    if (n == 0 || !t.pt.DONE || build >= VG_LIVE_IMAGES) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_live_begin_kernel, dim3(VG_GRID_LDS_WORDS / 4 / 256), dim3(256), 0, st, t.pt, dst, build);
+    hipLaunchKernelGGL(pt_live_build_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, t, key_slot, n, src, dst, build);
+    return hipGetLastError();
+}
+
+// vgmi_pt_live_check, from the keys and DONE alone: out[0] 12-mers of the keys whose bucket is not done and whose three bits are not all
+// in `image`; out[1] words of the image with a bit the static filter lacks; out[2] the image's bits
+__global__ void pt_live_check_kernel(TableView t, const uint32_t* key_slot, uint64_t n, const uint32_t* image, unsigned long long* out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < VG_GRID_LDS_WORDS) {
+        const uint32_t w = image[i];
+        if (w & ~t.grid[i]) atomicAdd(out + 1, 1ULL);
+        if (w) atomicAdd(out + 2, (unsigned long long)__popc(w));
+    }
+    if (i >= n) return;
+    const uint32_t bshift = 32u - t.pt.bucket_log2;
+    vg_grid12_of_kmer(t.slots8[key_slot[i]] & PT_MASK54, t.k, [&](uint32_t cm, uint32_t w, uint32_t m) {
+        const uint32_t bucket = vg_idx_hash(cm) >> bshift;
+        const bool done = t.pt.DONE && (t.pt.DONE[bucket >> 5] >> (bucket & 31u) & 1u);
+        if (!done && (image[w] & m) != m) atomicAdd(out + 0, 1ULL);
+    });
+}
+
+hipError_t launch_ptable_live_check(const TableView& t, const uint32_t* key_slot, uint64_t n, const uint32_t* image, unsigned long long* out, hipStream_t st)
+{
+    const uint64_t threads = n > VG_GRID_LDS_WORDS ? n : VG_GRID_LDS_WORDS;
+    hipLaunchKernelGGL(pt_live_check_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, t, key_slot, n, image, out);
+    return hipGetLastError();
+}
+
 // mark == nullptr: no check here (a caller that aligns the chains checks with launch_ptable_check once it knows the total)
 hipError_t launch_ptable_order(const TableView& t, const uint32_t* key_slot, uint64_t n, uint32_t* key_of_slot, uint32_t* link, uint32_t* link2,
                                uint32_t* pos_of_key, unsigned long long* cursor, uint32_t* mark, uint32_t* status, hipStream_t st, uint32_t align)

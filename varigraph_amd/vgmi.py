@@ -64,6 +64,7 @@ def load_library():
         "vgmi_counts_finish_device": (i32, [vp, vp, vp, vp]),
         "vgmi_count_kernel_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(u64)]),
         "vgmi_pt_done_check": (i32, [vp, C.POINTER(u64)]),
+        "vgmi_pt_live_check": (i32, [vp, C.POINTER(u64)]),
         "vgmi_counts_export_device": (i32, [vp, vp]),
         "vgmi_counts_import_device": (i32, [vp, vp]),
         "vgmi_fastq_open": (i32, [vp, C.POINTER(vp)]),
@@ -333,6 +334,13 @@ class Context:
         the path table's done bits against the index and the saturation bits (vgmi_pt_done_check)."""
         out = (C.c_uint64 * 4)()
         self._chk(self._l.vgmi_pt_done_check(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def pt_live_check(self):
+        """Small graphs: (live 12-mers missing from the grid filter's image in use, words of it with a bit the static filter lacks,
+        its set bits, refreshes since the reset that built a new image) -- vgmi_pt_live_check."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self._l.vgmi_pt_live_check(self._h, out))
         return tuple(int(v) for v in out)
 
     def fastq_text(self, text, piece=None):
