@@ -81,6 +81,13 @@ int64_t vgh_fastx_read_all_mt(const char *path, uint32_t decode_threads, char **
  * l_seq > 0; SEQ decoded as stored).  Returns the number of reads, or <0 (vgh_last_error: "'<path>': not a valid BAM record at
  * decompressed byte N (<what>)", or a file that is not BAM).  *read_base gets sum(l_seq). */
 int64_t vgh_bam_read_all(const char *path, uint32_t decode_threads, char **block_out, size_t *n_bytes_out, uint64_t *read_base);
+/* A FASTA/Q or BAM file (by its content, as vgh_sample_count decides) through the host reader with a minimum base quality: the same
+ * block with every base whose quality is below min_base_quality written as 'N' (the rule of vgmi_fastq_set_min_quality: FASTQ byte
+ * < 33 + q, BAM QUAL[i] < q and no masking where QUAL[0] is 0xff, FASTA untouched).  *masked_bases (may be NULL) = bases masked;
+ * *read_base as without the option.  VGMI_E_INVALID for min_base_quality > 93.  What the host legs of vgh_sample_count_q apply.
+ * Like the two entries above, an entry for tests of the readers: the three share one loop, this one with the bound. */
+int64_t vgh_reads_read_all_q(const char *path, uint32_t decode_threads, uint32_t min_base_quality, char **block_out, size_t *n_bytes_out,
+                             uint64_t *read_base, uint64_t *masked_bases);
 /* What the device path of vgh_sample_count makes of an input file, from its first bytes (no device involved): kind = "plain" |
  * "gzip" | "bgzf"; first_byte = the first byte of its text (-1: it has none); bam = block gzip whose text starts with "BAM\1";
  * fasta = the text starts with '>' and goes to the device's FASTA parser (VGH_DEVICE_FASTA=0: never).  Any pointer may be NULL. */
@@ -112,6 +119,14 @@ typedef struct vgh_sample_stats {
 int vgh_sample_count(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fastq_paths, size_t n_files,
                      uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
                      uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats);
+/* The same with a minimum base quality (0..93; 0 = off, which is vgh_sample_count): a base of a FASTQ / BAM record whose quality is
+ * below it is counted as 'N' -- by the device kernels (vgmi_fastq_set_min_quality) and, by the same rule, wherever the host reader
+ * serves (a tail record, the stream behind an irregular record, a pipe, VGH_HOST_PARSE=1, ...).  read_base, n_reads and the depth
+ * statistics are those of the unmasked files.  *masked_bases (may be NULL) = bases masked, device and host together. */
+int vgh_sample_count_q(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fastq_paths, size_t n_files,
+                       uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
+                       uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
+                       uint64_t *masked_bases);
 
 /* Coverage statistics alone (Varigraph::kmer_read / cal_ave_cov_kmer): hist = masked coverage histogram
  * (vgmi_counts_finish).  Fills read_depth, hap_kmer_coverage, max_coverage, hom_coverage of *stats; returns

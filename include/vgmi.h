@@ -260,6 +260,16 @@ int vgmi_fastq_gzip_status(vgmi_fastq *fq, uint64_t *device_text_bytes, uint32_t
 int vgmi_fastq_bgzf_status(vgmi_fastq *fq, int *failed, uint64_t *good_compressed_bytes, uint32_t *reason);
 int vgmi_fastq_close(vgmi_fastq *fq, uint64_t *n_records, uint64_t *n_bases, uint64_t *consumed_bytes, int *stopped,
                      char *tail_out, size_t tail_cap, size_t *tail_len);
+/* Minimum base quality q (0..93; 0 = off, the default): a base whose quality is below q goes into the read block as 'N', so it
+ * breaks the k-mer window like any N; record lengths, n_bases and the reads' offsets stay those of the unmasked text.
+ *   FASTQ  base i is masked when quality byte i, as an unsigned byte, is < 33 + q (Phred+33)
+ *   BAM    base i is masked when QUAL[i] < q, in record order whatever the strand; a record whose QUAL[0] is 0xff stores no
+ *          qualities and is not masked; records the read filter drops do not count
+ *   FASTA  no qualities: accepted without effect
+ * Before the stream's first commit only: VGMI_E_STATE afterwards, VGMI_E_INVALID for q > 93; the stream serves on after either. */
+int vgmi_fastq_set_min_quality(vgmi_fastq *fq, uint32_t q);
+/* Bases masked so far in the records the device has accepted (waits for the stream).  Valid until vgmi_fastq_close. */
+int vgmi_fastq_masked_bases(vgmi_fastq *fq, uint64_t *n);
 
 /* K1 alone: the key every position of a read block emits, for emitter parity tests.
  * keys_out[i] = key of the k-mer ENDING at byte i, or UINT64_MAX when the reference emits nothing

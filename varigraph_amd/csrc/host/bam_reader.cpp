@@ -130,8 +130,21 @@ long BamReader::next()
         const unsigned char* s = r + 36 + l_rn + 4 * (size_t)n_cig;
         seq_.resize(l_seq);
         for (uint32_t i = 0; i < l_seq; ++i) seq_[i] = nt16[(s[i >> 1] >> ((~i & 1) << 2)) & 15];
+        qual_.assign(reinterpret_cast<const char*>(s + (l_seq + 1) / 2), l_seq);
         return (long)l_seq;
     }
+}
+
+uint64_t BamReader::mask_below(uint32_t q)
+{
+    if (q == 0 || qual_.size() != seq_.size() || qual_.empty() || (unsigned char)qual_[0] == 0xFFu) return 0;
+    uint64_t n = 0;
+    for (size_t i = 0; i < seq_.size(); ++i)
+        if ((unsigned char)qual_[i] < q) {
+            seq_[i] = 'N';
+            ++n;
+        }
+    return n;
 }
 
 }  // namespace vgh

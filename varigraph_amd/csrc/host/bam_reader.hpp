@@ -27,6 +27,10 @@ public:
     // >= 0: sequence length (seq() holds it); -1: end of the data
     long next();
     const std::string& seq() const { return seq_; }
+    const std::string& qual() const { return qual_; }   // the record's QUAL bytes as stored (l_seq of them; QUAL[0] == 0xff: none stored)
+    // Minimum base quality q (the rule of vgmi_fastq_set_min_quality): base i of seq() becomes 'N' where QUAL[i] < q, in record order;
+    // a record whose QUAL[0] is 0xff is not masked.  Returns the number of bases masked.
+    uint64_t mask_below(uint32_t q);
 
 private:
     bool fill(size_t n);   // at least n bytes buffered; false if the data ends first
@@ -39,7 +43,7 @@ private:
     uint64_t off_ = 0;
     uint64_t header_bytes_ = 0;
     int32_t n_ref_ = 0;
-    std::string seq_;
+    std::string seq_, qual_;
 };
 
 // the bytes of `path` as ByteSource::open delivers them; is_bam: block gzip whose text starts with "BAM\1" (decided from content)

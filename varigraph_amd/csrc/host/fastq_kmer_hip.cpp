@@ -29,7 +29,15 @@ struct Block {
     std::vector<char> bytes;
     size_t n_reads = 0;
     uint64_t read_base = 0;
+    uint64_t masked = 0;
 };
+
+// VGH_TIMING: what the minimum base quality did to one file (nothing is printed without the option)
+void report_masked(const std::string& path, uint64_t masked, uint32_t min_q)
+{
+    if (min_q && std::getenv("VGH_TIMING"))
+        std::fprintf(stderr, "[varigraph-mi] '%s': %llu bases below Q%u masked\n", path.c_str(), (unsigned long long)masked, min_q);
+}
 
 struct Channel {  // parser threads -> submitting thread
     std::mutex mu;
@@ -40,8 +48,9 @@ struct Channel {  // parser threads -> submitting thread
     std::string error;
 };
 
-void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads)
+void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads, uint32_t min_q)
 {
+    uint64_t file_masked = 0;
     auto grab = [&]() {
         std::unique_lock<std::mutex> lk(ch.mu);
         ch.cv_free.wait(lk, [&] { return !ch.free_list.empty(); });
@@ -50,6 +59,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         b->bytes.clear();
         b->n_reads = 0;
         b->read_base = 0;
+        b->masked = 0;
         return b;
     };
     auto push = [&](std::unique_ptr<Block> b) {
@@ -60,6 +70,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
     auto run = [&](auto& rd) {
         std::unique_ptr<Block> cur = grab();
         while (rd.next() >= 0) {  // stops at EOF (-1) and at the first truncated record (-2)
+            const uint64_t masked = min_q ? rd.mask_below(min_q) : 0;
             const std::string& s = rd.seq();
             // `string sequence = ks->seq.s` (src/fastq_kmer.cpp:101) ends at the first NUL, while
             // mReadBase adds the full ks->seq.l (:105)
@@ -73,6 +84,8 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
             cur->bytes.push_back('\n');
             cur->n_reads++;
             cur->read_base += s.size();
+            cur->masked += masked;
+            file_masked += masked;
         }
         if (cur->n_reads) push(std::move(cur));
         else {
@@ -90,6 +103,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
             FastxReader rd(std::move(src));
             run(rd);
         }
+        report_masked(path, file_masked, min_q);
     } catch (const std::exception& e) {
         std::lock_guard<std::mutex> lk(ch.mu);
         if (ch.error.empty()) ch.error = e.what();
@@ -104,8 +118,8 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
 // records of `rd` (from a record boundary on; FastxReader or BamReader) through the host reader into read blocks and vgmi_reads_submit;
 // the context's host-block path is single-threaded, hence the mutex shared by the files of one sample
 template <class Reader>
-void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_bytes, std::mutex& submit_mu, uint64_t& n_reads,
-              uint64_t& read_base)
+void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_bytes, std::mutex& submit_mu, uint32_t min_q, uint64_t& n_reads,
+              uint64_t& read_base, uint64_t& masked)
 {
     std::vector<char> block;
     block.reserve(block_bytes + 1024);
@@ -118,6 +132,7 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
         in_block = 0;
     };
     while (rd.next() >= 0) {
+        if (min_q) masked += rd.mask_below(min_q);        // the device kernels' rule, wherever the host reader serves
         const std::string& s = rd.seq();
         const size_t len = strnlen(s.data(), s.size());   // src/fastq_kmer.cpp:101 vs :105, see parse_file
         if (len == 0) throw std::runtime_error("'" + path + "': empty read sequence (the reference aborts on assert(len > 0), kmer.cpp:124)");
@@ -209,10 +224,10 @@ InputSniff sniff_input(const std::string& path)
 namespace {
 
 struct DeviceFileResult {
-    uint64_t n_reads = 0, read_base = 0;
+    uint64_t n_reads = 0, read_base = 0, masked = 0;
 };
 
-DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t block_bytes, unsigned threads, std::mutex& submit_mu)
+DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t block_bytes, unsigned threads, std::mutex& submit_mu, uint32_t min_q)
 {
     DeviceFileResult res;
     int fd = ::open(path.c_str(), O_RDONLY);
@@ -230,10 +245,10 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         std::unique_ptr<ByteSource> src = open_sniffed(path, threads, is_bam);   // (a BAM pipe: recognised from its first decoded bytes)
         if (is_bam) {
             BamReader rd(std::move(src), path);
-            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
         } else {
             FastxReader rd(std::move(src));
-            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
         }
         return res;
     }
@@ -256,7 +271,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         bgzf = false;
         if (bam) {
             BamReader rd(ByteSource::open(path, threads), path);
-            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
             return res;
         }
     }
@@ -272,6 +287,11 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     // text whose first byte is '>': FASTA records, single-line or wrapped, joined on the device (vgmi_fasta.hip); the hand-over is the
     // FASTQ stream's -- the last record, which only the end of the data completes, comes back as the tail
     if ((bam ? vgmi_fastq_open_bam(ctx, bam_header, bam_n_ref, &fq) : fasta ? vgmi_fastq_open_fasta(ctx, &fq) : vgmi_fastq_open(ctx, &fq)) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+    if (min_q && vgmi_fastq_set_min_quality(fq, min_q) != VGMI_OK) {
+        const std::string why = vgmi_last_error(ctx);
+        (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        throw std::runtime_error(why);
+    }
     uint64_t n_rec = 0, n_bases = 0, consumed = 0;
     int stopped = 0;
     std::vector<char> tail(1u << 20);
@@ -282,6 +302,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     uint64_t comp_good = 0;           // ... of which the device vouches for (everything unless a member failed)
     auto close_stream = [&]() {
         if (bgzf && vgmi_fastq_bgzf_status(fq, &inflate_failed, &comp_good, nullptr) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+        if (min_q && vgmi_fastq_masked_bases(fq, &res.masked) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         closed = true;
         if (vgmi_fastq_close(fq, &n_rec, &n_bases, &consumed, &stopped, tail.data(), tail.size(), &tail_len) != VGMI_OK)
             throw std::runtime_error(vgmi_last_error(ctx));
@@ -405,18 +426,18 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         if (stopped || inflate_failed || comp_taken < file_size || tail_len) {
             BamReader rd(ByteSource::open(path, threads), path);
             rd.skip_to(consumed);
-            host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
         }
     } else if (stopped || gz_gave_up) {       // (the host decodes the file from its start and passes over the text the device has counted)
         FastxReader rd(ByteSource::skip(ByteSource::open(path, threads), consumed));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
     } else if (bgzf && (inflate_failed ? comp_good : comp_taken) < file_size) {
         const uint64_t at = inflate_failed ? comp_good : comp_taken;
         FastxReader rd(ByteSource::concat(ByteSource::from_memory(tail.data(), tail_len), ByteSource::open_at(path, at, threads)));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
     } else if (tail_len) {
         FastxReader rd(ByteSource::from_memory(tail.data(), tail_len));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, res.n_reads, res.read_base);
+        host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
     }
     return res;
 }
@@ -429,7 +450,20 @@ FastqKmerHip::FastqKmerHip(vgmi_ctx* ctx, const std::vector<std::string>& fastqF
 {
 }
 
+FastqKmerHipQ::FastqKmerHipQ(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads,
+                             uint32_t min_base_quality, size_t block_bytes)
+    : FastqKmerHip(ctx, fastqFileNameVec, kmerLen, threads, block_bytes), min_q_(min_base_quality)
+{
+    if (min_q_ > 93) throw std::runtime_error("minimum base quality " + std::to_string(min_q_) + " is out of range (0..93, Phred+33)");
+}
+
 void FastqKmerHip::build_fastq_index()
+{
+    uint64_t masked = 0;
+    count_files(0, masked);
+}
+
+void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
 {
     if (files_.empty()) throw std::runtime_error("Parameter error: -f");  // src/fastq_kmer.cpp:42-45
     uint32_t k_tab = 0;
@@ -438,6 +472,7 @@ void FastqKmerHip::build_fastq_index()
     if (vgmi_counts_reset(ctx_) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx_));
     mReadBase = 0;
     mReadNum = 0;
+    masked = 0;
 
     const char* force_host = std::getenv("VGH_HOST_PARSE");
     if (!(force_host && force_host[0] == '1')) {
@@ -453,10 +488,12 @@ void FastqKmerHip::build_fastq_index()
                 const size_t i = next.fetch_add(1);
                 if (i >= files_.size()) return;
                 try {
-                    const DeviceFileResult r = device_file(ctx_, files_[i], block_bytes_, io_threads, submit_mu);
+                    const DeviceFileResult r = device_file(ctx_, files_[i], block_bytes_, io_threads, submit_mu, min_q);
+                    report_masked(files_[i], r.masked, min_q);
                     std::lock_guard<std::mutex> lk(res_mu);
                     mReadBase += r.read_base;
                     mReadNum += r.n_reads;
+                    masked += r.masked;
                 } catch (const std::exception& e) {
                     std::lock_guard<std::mutex> lk(res_mu);
                     if (err.empty()) err = e.what();
@@ -487,7 +524,7 @@ void FastqKmerHip::build_fastq_index()
     auto start_more = [&]() {  // called with ch.mu held
         while (ch.producers < n_par && next_file < files_.size()) {
             ch.producers++;
-            workers.emplace_back(parse_file, files_[next_file++], std::ref(ch), block_bytes_, decode_threads);
+            workers.emplace_back(parse_file, files_[next_file++], std::ref(ch), block_bytes_, decode_threads, min_q);
         }
     };
     std::string err;
@@ -510,6 +547,7 @@ void FastqKmerHip::build_fastq_index()
                     err = vgmi_last_error(ctx_);
                 mReadBase += b->read_base;
                 mReadNum += b->n_reads;
+                masked += b->masked;
             }
             lk.lock();
             ch.free_list.push_back(std::move(b));

@@ -40,12 +40,37 @@ public:
 
     double kernel_seconds() const { return kernel_s_; }
 
+protected:
+    // build_fastq_index with a minimum base quality (0: off); masked_bases gets the bases counted as 'N' for their quality
+    void count_files(uint32_t min_base_quality, uint64_t& masked_bases);
+
 private:
     vgmi_ctx* ctx_;
     std::vector<std::string> files_;
     uint32_t k_, threads_;
     size_t block_bytes_;
     double kernel_s_ = 0;
+};
+
+// FastqKmerHip with a minimum base quality (0..93; 0 = off): a base of a FASTQ / BAM record whose quality is below it is counted as
+// 'N' (the rule of vgmi_fastq_set_min_quality, on the device and wherever the host reader serves); mReadBase and mReadNum do not
+// change with it.  A class of its own: FastqKmerHip keeps its constructor and its size, so a program built against the earlier
+// header -- the integration binary of integration/varigraph_hip.hpp -- runs against this library as it is.  Nothing of the base is
+// hidden: the masked count has its own name, build_fastq_index_masked, and the inherited build_fastq_index stays what it is for
+// every FastqKmerHip -- the count without a bound.
+class FastqKmerHipQ : public FastqKmerHip {
+public:
+    uint64_t mMaskedBases = 0;  // bases counted as 'N' for their quality, device and host readers together
+
+    // throws std::runtime_error for min_base_quality > 93
+    FastqKmerHipQ(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads,
+                  uint32_t min_base_quality = 0, size_t block_bytes = 32u << 20);
+
+    // build_fastq_index with the bound applied; fills mMaskedBases
+    void build_fastq_index_masked() { count_files(min_q_, mMaskedBases); }
+
+private:
+    uint32_t min_q_;
 };
 
 // What the device path makes of an input file, decided from its first bytes alone (no device involved): the container by the

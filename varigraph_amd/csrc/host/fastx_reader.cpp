@@ -103,4 +103,17 @@ long FastxReader::next()
     return (long)seq_.size();
 }
 
+uint64_t FastxReader::mask_below(uint32_t q)
+{
+    if (q == 0 || qual_.size() != seq_.size()) return 0;
+    const unsigned bound = 33u + q;
+    uint64_t n = 0;
+    for (size_t i = 0; i < seq_.size(); ++i)
+        if ((unsigned char)qual_[i] < bound) {
+            seq_[i] = 'N';
+            ++n;
+        }
+    return n;
+}
+
 }  // namespace vgh

@@ -30,6 +30,10 @@ public:
     long next();
     const std::string& seq() const { return seq_; }
     const std::string& name() const { return name_; }  // up to the first whitespace of the header line
+    const std::string& qual() const { return qual_; }  // the record's quality lines joined (empty for a FASTA record)
+    // Minimum base quality q (the rule of vgmi_fastq_set_min_quality): base i of seq() becomes 'N' where quality byte i, as an unsigned
+    // byte, is < 33 + q.  Returns the number of bases masked; a FASTA record has no qualities and stays as it is.
+    uint64_t mask_below(uint32_t q);
     const char* source_kind() const { return src_->kind(); }
 
 private:

@@ -44,6 +44,7 @@ struct Options {
                                    // counting thread and one table replica per device
     int buffer_mib = 100;   // main.cu default
     bool procs = false;     // --procs: one PROCESS per device of --gpus, the table image handed on by one RCCL broadcast
+    int min_base_quality = 0;   // --min-base-quality: bases of FASTQ / BAM reads below it are counted as N (0: off); the ranks of --procs inherit it
 };
 
 // --procs: what the ranks share (one page, mapped before the fork): rank 0's RCCL id, whether it is there, whether anyone gave up
@@ -69,6 +70,7 @@ void usage(const char* argv0)
               << "    --sv                   structural variants only\n"
               << "    --min-support   FLOAT  minimum site quality (GQ) [0]\n"
               << "    --use-depth            use the sequencing depth as the depth of homozygous k-mers\n"
+              << "    --min-base-quality INT count a base of a FASTQ / BAM read whose quality (Phred+33) is below INT as N, 0-93 [0: off]\n"
               << "    --gpu           INT    device ordinal [0]\n"
               << "    --gpus          LIST   several devices, e.g. 0,1,2,3: samples are counted on them in parallel\n"
               << "    --procs                one process per device of --gpus (samples dealt round robin, -t shared out); the table is\n"
@@ -161,7 +163,7 @@ int main_genotype(int argc, char** argv)
         {"gpu", required_argument, 0, 7},          {"buffer", required_argument, 0, 8},
         {"gpus", required_argument, 0, 9},         {"debug", no_argument, 0, 'D'},
         {"threads", required_argument, 0, 't'},    {"help", no_argument, 0, 'h'},
-        {"procs", no_argument, 0, 10},
+        {"procs", no_argument, 0, 10},             {"min-base-quality", required_argument, 0, 11},
         {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -189,6 +191,7 @@ int main_genotype(int argc, char** argv)
         }
         case 8: o.buffer_mib = opt_int("--buffer", optarg); break;
         case 10: o.procs = true; break;
+        case 11: o.min_base_quality = opt_int("--min-base-quality", optarg); break;
         case 't': o.hmm.threads = std::max(opt_int("-t", optarg), 1); break;
         case 'D': debug = true; break;
         default: usage(argv[0]); return 1;
@@ -210,6 +213,7 @@ int main_genotype(int argc, char** argv)
         std::cerr << "[varigraph-mi] Parameter warning: --granularity. The chromosome granularity is less than 1000bp (" << o.hmm.chr_len_thread << " bp).\n";
     if (o.hmm.transition != "fre" && o.hmm.transition != "rec") die("Parameter error: -m. The transition probability type must be either 'fre' or 'rec'.");
     if (o.buffer_mib < 1) die("Parameter error: --buffer. The buffer size must be at least 1 MiB.");
+    if (o.min_base_quality < 0 || o.min_base_quality > 93) die("Parameter error: --min-base-quality. The provided value must be between 0 and 93 (inclusive).");
 
     const auto t0 = std::chrono::steady_clock::now();
     auto secs = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -622,8 +626,8 @@ int main_genotype(int argc, char** argv)
                 }
                 const auto& [name, files] = samples[s];
                 const double ts = secs();
-                vgh::FastqKmerHip fk(ctx, files, g.k, count_threads);
-                fk.build_fastq_index();
+                vgh::FastqKmerHipQ fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality);
+                fk.build_fastq_index_masked();
                 counted(s, fk, dev_i, ts);
             }
         } catch (const std::exception& e) {

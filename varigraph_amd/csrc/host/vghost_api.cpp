@@ -24,6 +24,34 @@ struct vgh_genotyper {
 
 static thread_local std::string g_err;
 
+namespace {
+// every record of `rd` (FastxReader or BamReader) as a '\n'-joined block in malloc'ed memory, bases below quality q masked (0: none);
+// the number of reads, or VGMI_E_NOMEM.  A sequence ends at its first NUL, read_base counts it whole (src/fastq_kmer.cpp:101 vs :105).
+template <class Reader>
+int64_t reads_block(Reader& rd, uint32_t q, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases)
+{
+    std::string block;
+    int64_t n = 0;
+    uint64_t rb = 0, masked = 0;
+    while (rd.next() >= 0) {
+        if (q) masked += rd.mask_below(q);
+        const std::string& s = rd.seq();
+        block.append(s.data(), strnlen(s.data(), s.size()));
+        block.push_back('\n');
+        rb += s.size();
+        ++n;
+    }
+    char* p = static_cast<char*>(malloc(block.size() ? block.size() : 1));
+    if (!p) return VGMI_E_NOMEM;
+    memcpy(p, block.data(), block.size());
+    *block_out = p;
+    *n_bytes_out = block.size();
+    if (read_base) *read_base = rb;
+    if (masked_bases) *masked_bases = masked;
+    return n;
+}
+}  // namespace
+
 extern "C" {
 
 const char* vgh_last_error(void) { return g_err.c_str(); }
@@ -122,23 +150,7 @@ int64_t vgh_fastx_read_all_mt(const char* path, uint32_t decode_threads, char** 
             strncpy(source_kind, rd.source_kind(), 7);
             source_kind[7] = 0;
         }
-        std::string block;
-        int64_t n = 0;
-        uint64_t rb = 0;
-        while (rd.next() >= 0) {
-            const std::string& s = rd.seq();
-            block.append(s.data(), strnlen(s.data(), s.size()));
-            block.push_back('\n');
-            rb += s.size();
-            ++n;
-        }
-        char* p = static_cast<char*>(malloc(block.size() ? block.size() : 1));
-        if (!p) return VGMI_E_NOMEM;
-        memcpy(p, block.data(), block.size());
-        *block_out = p;
-        *n_bytes_out = block.size();
-        if (read_base) *read_base = rb;
-        return n;
+        return reads_block(rd, 0, block_out, n_bytes_out, read_base, nullptr);
     } catch (const std::exception& e) {
         g_err = e.what();
         return VGMI_E_INVALID;
@@ -153,22 +165,30 @@ int64_t vgh_bam_read_all(const char* path, uint32_t decode_threads, char** block
         std::unique_ptr<vgh::ByteSource> src = vgh::open_sniffed(path, decode_threads ? decode_threads : 1, is_bam);
         if (!is_bam) throw std::runtime_error(std::string("'") + path + "': not a BAM file (block gzip starting with BAM\\1)");
         vgh::BamReader rd(std::move(src), path);
-        std::string block;
-        int64_t n = 0;
-        uint64_t rb = 0;
-        while (rd.next() >= 0) {
-            block += rd.seq();
-            block.push_back('\n');
-            rb += rd.seq().size();
-            ++n;
+        return reads_block(rd, 0, block_out, n_bytes_out, read_base, nullptr);
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return VGMI_E_INVALID;
+    }
+}
+
+int64_t vgh_reads_read_all_q(const char* path, uint32_t decode_threads, uint32_t min_base_quality, char** block_out, size_t* n_bytes_out,
+                             uint64_t* read_base, uint64_t* masked_bases)
+{
+    if (!path || !block_out || !n_bytes_out) return VGMI_E_INVALID;
+    if (min_base_quality > 93) {
+        g_err = "minimum base quality " + std::to_string(min_base_quality) + " is out of range (0..93, Phred+33)";
+        return VGMI_E_INVALID;
+    }
+    try {
+        bool is_bam = false;
+        std::unique_ptr<vgh::ByteSource> src = vgh::open_sniffed(path, decode_threads ? decode_threads : 1, is_bam);
+        if (is_bam) {
+            vgh::BamReader rd(std::move(src), path);
+            return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases);
         }
-        char* p = static_cast<char*>(malloc(block.size() ? block.size() : 1));
-        if (!p) return VGMI_E_NOMEM;
-        memcpy(p, block.data(), block.size());
-        *block_out = p;
-        *n_bytes_out = block.size();
-        if (read_base) *read_base = rb;
-        return n;
+        vgh::FastxReader rd(std::move(src));
+        return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases);
     } catch (const std::exception& e) {
         g_err = e.what();
         return VGMI_E_INVALID;
@@ -244,12 +264,21 @@ int vgh_sample_count(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fastq
                      uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
                      vgh_sample_stats* stats)
 {
+    return vgh_sample_count_q(h, ctx, fastq_paths, n_files, threads, sample_ploidy, use_depth, cov_out, cov_node_out, hist_out, stats, 0, nullptr);
+}
+
+int vgh_sample_count_q(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fastq_paths, size_t n_files, uint32_t threads,
+                       uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
+                       vgh_sample_stats* stats, uint32_t min_base_quality, uint64_t* masked_bases)
+{
     if (!h || !ctx || (!fastq_paths && n_files)) return VGMI_E_INVALID;
+    if (masked_bases) *masked_bases = 0;
     try {
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<std::string> files(fastq_paths, fastq_paths + n_files);
-        vgh::FastqKmerHip fk(ctx, files, h->g.k, threads);
-        fk.build_fastq_index();
+        vgh::FastqKmerHipQ fk(ctx, files, h->g.k, threads, min_base_quality);
+        fk.build_fastq_index_masked();
+        if (masked_bases) *masked_bases = fk.mMaskedBases;
         uint64_t hist[256];
         fk.fetch(cov_out, cov_node_out, hist);
         if (hist_out) memcpy(hist_out, hist, sizeof hist);

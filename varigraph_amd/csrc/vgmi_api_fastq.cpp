@@ -54,6 +54,9 @@ struct vgmi_fastq {
     // block (vgmi_readoff.hip); allocated by the first chunk counted against an even-k table
     uint8_t* d_even = nullptr;
     uint64_t cap_reads = 0;
+    // minimum base quality (vgmi_fastq_set_min_quality): 0 = off; fixed once bytes have been committed
+    uint32_t min_quality = 0;
+    bool committed = false;
 };
 
 namespace {
@@ -118,6 +121,8 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->gz_text = 0;
             r->bam = false;
             r->fasta = false;
+            r->min_quality = 0;
+            r->committed = false;
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -229,6 +234,7 @@ hipError_t parse_chunk(vgmi_fastq* f, int i, uint32_t n_new, const uint32_t* n_n
     b.state = f->d_state;
     b.cap_lines = f->cap_lines;
     b.tail_max = f->tail_max;
+    b.min_qual = f->min_quality ? 33u + f->min_quality : 0u;      // Phred+33
     if (!f->fasta) return launch_fastq_chunk(b, n_new, f->stream, n_new_dev);
     FaBuffers a{};
     a.q = b;
@@ -319,6 +325,7 @@ int vgmi_fastq_commit(vgmi_fastq* f, size_t n_bytes)
     const int i = f->acquired;
     f->acquired = -1;
     if (n_bytes == 0) return VGMI_OK;
+    f->committed = true;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(f->d_raw[i] + f->tail_max, f->h_stage[i], n_bytes, hipMemcpyHostToDevice, f->stream));
     HIPCHK(c, hipEventRecord(f->h_done[i], f->stream));
@@ -374,6 +381,7 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
     if (f->acquired < 0) return fail(c, VGMI_E_STATE, "no buffer acquired");
     if (n_bytes > f->cap) return fail(c, VGMI_E_INVALID, "more bytes than the buffer holds");
     const int i = f->acquired;
+    if (n_bytes) f->committed = true;
     HIPCHK(c, hipSetDevice(c->device));
     if (!f->d_members) {      // (d_comp may be there already: a stream of the pool that served an ordinary gzip file)
         f->max_members = (uint32_t)(f->text_cap / 4096) + 1024;     // bgzip members compress 64 KiB each; tiny ones are rare
@@ -487,6 +495,7 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
         bb.bam = f->d_bam;
         bb.tail_max = b.tail_max;
         bb.n_ref = f->n_ref;
+        bb.min_qual = f->min_quality;
         HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
         int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
@@ -770,6 +779,7 @@ int vgmi_fastq_commit_gzip(vgmi_fastq* f, size_t n_bytes, int at_eof, size_t* ta
     if (f->bam) return fail(c, VGMI_E_STATE, "a BAM stream takes block gzip (vgmi_fastq_commit_bgzf)");
     const int i = f->acquired;
     f->acquired = -1;
+    if (n_bytes) f->committed = true;
     HIPCHK(c, hipSetDevice(c->device));
     const unsigned char* p = reinterpret_cast<const unsigned char*>(f->h_stage[i]);
     size_t pos = 0;               // staged bytes dealt with
@@ -908,6 +918,29 @@ int vgmi_fastq_bgzf_status(vgmi_fastq* f, int* failed, uint64_t* good_compressed
         for (uint32_t k = 0; k < v.first_bad_member && mi < f->member_size.size(); ++k) bytes += f->member_size[mi++];
     }
     if (good_compressed_bytes) *good_compressed_bytes = bytes;
+    return VGMI_OK;
+}
+
+int vgmi_fastq_set_min_quality(vgmi_fastq* f, uint32_t q)
+{
+    if (!f) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    if (q > 93) return fail(c, VGMI_E_INVALID, "minimum base quality " + std::to_string(q) + " is out of range (0..93, Phred+33)");
+    if (f->committed) return fail(c, VGMI_E_STATE, "the minimum base quality is set before the stream's first commit");
+    f->min_quality = f->fasta ? 0u : q;      // FASTA text has no qualities
+    return VGMI_OK;
+}
+
+int vgmi_fastq_masked_bases(vgmi_fastq* f, uint64_t* n)
+{
+    if (!f || !n) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    *n = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(f->stream));
+    unsigned long long v = 0;
+    HIPCHK(c, hipMemcpy(&v, &f->d_state->n_masked, sizeof v, hipMemcpyDeviceToHost));
+    *n = v;
     return VGMI_OK;
 }
 

@@ -280,6 +280,47 @@ __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* raw, con
     }
 }
 
+// B8 with a minimum base quality: the same decode, and the lane that decodes byte k of SEQ loads QUAL[2k] and QUAL[2k + 1] -- QUAL
+// lies (l_seq + 1) / 2 bytes behind SEQ inside the record (the candidate test has checked that it fits), base i pairs with QUAL[i] in
+// record order whatever the strand flag says.  A base whose QUAL is below `bound` is decoded as 'N'; a record whose QUAL[0] is 0xff
+// stores no qualities and is decoded as it is.  Records the filter drops (rec_bytes == 0) are not looked at.  The masked bases are
+// summed over the workgroup and added to FqState::n_masked once.
+__global__ __launch_bounds__(256) void bam_decode_mask_kernel(const uint8_t* raw, FqState* st, const BamState* bs, const uint32_t* cand,
+                                                              const uint32_t* rec_bytes, const uint32_t* out_off, uint8_t* packed, uint32_t cap,
+                                                              uint32_t bound)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;   // (uniform)
+    const char* nt16 = "=ACMGRSVTWYHKDBN";
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    uint32_t masked = 0;
+    for (uint32_t i = wave; i < n; i += n_waves) {
+        const uint32_t nb = rec_bytes[i];
+        if (!nb) continue;
+        const uint32_t o = cand[i], l_seq = nb - 1;
+        const uint32_t s = o + 36u + raw[o + 12] + 4u * (bam_ld32(raw, o + 16) & 0xFFFFu);
+        const uint32_t q = s + (l_seq + 1u) / 2u;
+        const uint32_t lim = raw[q] == 0xFFu ? 0u : bound;   // (uniform over the wavefront)
+        uint8_t* dst = packed + out_off[i];
+        for (uint32_t k = lane; 2 * k < l_seq; k += 64) {
+            const uint32_t b = raw[s + k];
+            const bool low0 = raw[q + 2 * k] < lim;
+            dst[2 * k] = low0 ? 'N' : nt16[b >> 4];
+            masked += low0;
+            if (2 * k + 1 < l_seq) {
+                const bool low1 = raw[q + 2 * k + 1] < lim;
+                dst[2 * k + 1] = low1 ? 'N' : nt16[b & 15u];
+                masked += low1;
+            }
+        }
+        if (lane == 0) dst[l_seq] = '\n';
+    }
+    const uint32_t t = block_reduce_add(masked, sh);
+    if (threadIdx.x == 0 && t) atomicAdd(&st->n_masked, (unsigned long long)t);
+}
+
 // B9: chunk bookkeeping (one thread)
 __global__ void bam_finish_kernel(const uint8_t* raw, FqState* st, const BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
                                   const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max, int32_t n_ref)
@@ -370,7 +411,10 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
     e = launch_scan_small(b.block_sum, n_rblk, nullptr, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(bam_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.bam, b.block_sum, b.out_off, 1, b.cap_cand);
-    hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
+    if (b.min_qual)
+        hipLaunchKernelGGL(bam_decode_mask_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed,
+                           b.cap_cand, b.min_qual);
+    else hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
     hipLaunchKernelGGL(bam_finish_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_cand,
                        b.tail_max, b.n_ref);
     hipLaunchKernelGGL(bam_carry_kernel, dim3(1), dim3(256), 0, s, b.raw, b.raw_next, b.state, b.bam, b.tail_max);

@@ -25,6 +25,9 @@
 //   K5 scan of the packed lengths -> K6 copy of every sequence line into the '\n'-joined read block ->
 //   K7 bookkeeping (records, bases, consumed bytes, tail) -> K8 tail carried into the other raw buffer ->
 //   the count kernels run on the packed block with its length read from device memory (RowParams::n_bytes_dev).
+// With a minimum base quality (FqBuffers::min_qual; vgmi_fastq_set_min_quality) K6 is fq_pack_mask_kernel: the copy reads line 4 next
+// to line 2 and writes 'N' for every base whose quality byte is below the bound.  Not the reference's behaviour (it has no such
+// option): the result is the reference's on a file with those bases written as N.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -253,6 +256,32 @@ __global__ __launch_bounds__(256) void fq_pack_kernel(const uint8_t* raw, const 
     }
 }
 
+// K6 with a minimum base quality: the same copy, and the wavefront loads the record's quality line (one byte behind newline 4r + 2,
+// as long as the sequence: K4's check) with the same lane mapping; a base whose quality byte is below `bound` goes out as 'N', which
+// the count kernels read as code 4 -- it breaks the k-mer window like any N.  Lengths and offsets are those of the plain copy.
+// The masked bases are summed over the workgroup and added to FqState::n_masked once.
+__global__ __launch_bounds__(256) void fq_pack_mask_kernel(const uint8_t* raw, FqState* st, const uint32_t* nlpos, const uint32_t* out_off,
+                                                           uint8_t* packed, uint32_t bound)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t good = st->n_good;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    uint32_t masked = 0;
+    for (uint32_t r = wave; r < good; r += n_waves) {
+        const uint32_t b = nlpos[4 * r] + 1, e = nlpos[4 * r + 1];   // [b, e) = the sequence, raw[e] = '\n'
+        const uint32_t q = nlpos[4 * r + 2] + 1;                     // [q, q + e - b) = its qualities
+        uint8_t* dst = packed + out_off[r];
+        for (uint32_t i = lane; i <= e - b; i += 64) {
+            const bool low = i < e - b && raw[q + i] < bound;
+            dst[i] = low ? (uint8_t)'N' : raw[b + i];
+            masked += low;
+        }
+    }
+    const uint32_t t = block_reduce_add(masked, sh);
+    if (threadIdx.x == 0 && t) atomicAdd(&st->n_masked, (unsigned long long)t);
+}
+
 // K8: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(256) void fq_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, uint32_t tail_max)
 {
@@ -313,7 +342,8 @@ hipError_t launch_fastq_chunk(const FqBuffers& b, uint32_t n_new, hipStream_t s,
     hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, b.block_sum, n_rblk, (uint32_t*)nullptr);
     hipLaunchKernelGGL(fq_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.block_sum, b.out_off, 1, b.cap_lines);
     hipLaunchKernelGGL(fq_finish_kernel, dim3(1), dim3(1), 0, s, b.state, b.nlpos, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_lines, b.tail_max);
-    hipLaunchKernelGGL(fq_pack_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.out_off, b.packed);
+    if (b.min_qual) hipLaunchKernelGGL(fq_pack_mask_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.out_off, b.packed, b.min_qual);
+    else hipLaunchKernelGGL(fq_pack_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.out_off, b.packed);
     hipLaunchKernelGGL(fq_carry_kernel, dim3(1), dim3(256), 0, s, b.raw, b.raw_next, b.state, b.tail_max);
     return hipGetLastError();
 }

@@ -133,6 +133,7 @@ struct FqState {                       // device-resident, one per open stream
     unsigned long long n_bases;        // their sequence bytes (mReadBase)
     unsigned long long consumed;       // file text bytes taken by the device: the host reader resumes here
     unsigned long long packed_bytes;   // read block of the chunk just parsed (the count kernels' n_bytes)
+    unsigned long long n_masked;       // bases of the accepted records written as 'N' for their quality (min_qual; 0 without it)
     uint32_t stopped;                  // sticky: the device parser has handed the rest of the stream to the host reader
     uint32_t tail_len;                 // bytes of an incomplete record carried into the next chunk
     uint32_t start;                    // where this chunk's text begins in the raw buffer (tail_max - previous tail_len)
@@ -150,6 +151,7 @@ struct FqBuffers {
     uint32_t* block_sum;               // scan scratch
     FqState* state;
     uint32_t cap_lines, tail_max;
+    uint32_t min_qual;                 // 0: off; else a base whose quality byte is below it (Phred+33: 33 + Q) is packed as 'N'
 };
 hipError_t launch_fastq_init(FqState* st, uint32_t tail_max, hipStream_t s);
 // n_new_dev (may be null): the chunk is cut to min(n_new, *n_new_dev) bytes on the device (text in front of a block-gzip
@@ -199,6 +201,7 @@ struct BamBuffers {
     BamState* bam;
     uint32_t cap_cand, tail_max;
     int32_t n_ref;
+    uint32_t min_qual;                 // 0: off; else a base whose QUAL byte is below it is decoded as 'N' (a record without QUAL: none)
 };
 hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s);
 hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);

@@ -62,6 +62,11 @@ def lib():
     l.vgh_sample_count.restype = C.c_int
     l.vgh_sample_count.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp,
                                    C.POINTER(SampleStats)]
+    l.vgh_sample_count_q.restype = C.c_int
+    l.vgh_sample_count_q.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.POINTER(C.c_uint64)]
+    l.vgh_reads_read_all_q.restype = C.c_int64
+    l.vgh_reads_read_all_q.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]
     l.vgh_bloom_reference_seeds.restype = C.c_int
     l.vgh_bloom_reference_seeds.argtypes = [C.c_uint32, C.c_uint32, vp]
     l.vgh_make_mbf.restype = C.c_int
@@ -150,21 +155,28 @@ class Graph:
             raise RuntimeError(self._l.vgh_last_error().decode())
         return cov, rb.value
 
-    def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True):
+    def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True, min_base_quality=0):
         """FastqKmerHip::build_fastq_index + coverage statistics for one sample.  require_depth=False: a sample too thin
         for the coverage peak (the reference exits with "Failed to retrieve depth information") still returns its
-        counters."""
+        counters.  min_base_quality: bases of FASTQ / BAM reads whose quality is below it are counted as N (vgh_sample_count_q);
+        stats["masked_bases"] = how many, device and host readers together."""
         i = self.info
         cov = np.empty(i["n_keys"], dtype=np.uint8)
         cov_node = np.empty(i["n_node_entries"], dtype=np.uint8)
         hist = np.zeros(256, dtype=np.uint64)
         st = SampleStats()
         arr = (C.c_char_p * len(fastq_paths))(*[os.fsencode(p) for p in fastq_paths])
-        rc = self._l.vgh_sample_count(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
-                                      vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st))
+        masked = C.c_uint64()
+        if min_base_quality:
+            rc = self._l.vgh_sample_count_q(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
+                                            vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality, C.byref(masked))
+        else:
+            rc = self._l.vgh_sample_count(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
+                                          vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st))
         if rc and (require_depth or b"Failed to retrieve depth" not in self._l.vgh_last_error()):
             raise vgmi.VgmiError(rc, self._l.vgh_last_error().decode())
         stats = {f[0]: getattr(st, f[0]) for f in SampleStats._fields_}
+        stats["masked_bases"] = masked.value
         return cov, cov_node, hist, stats
 
 
@@ -258,6 +270,21 @@ def fastx_read_all(path, decode_threads=1, with_kind=False):
     if with_kind:
         return block, int(cnt), rb.value, kind.value.decode()
     return block, int(cnt), rb.value
+
+
+def reads_read_all_q(path, min_base_quality, decode_threads=1):
+    """A FASTA/Q or BAM file through the host reader with a minimum base quality (vgh_reads_read_all_q): (block, n_reads, read_base,
+    masked_bases) -- the block fastx_read_all / bam_read_all give, with the bases below the bound as N."""
+    l = lib()
+    p, n, rb, mb = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64()
+    cnt = l.vgh_reads_read_all_q(os.fsencode(path), decode_threads, min_base_quality, C.byref(p), C.byref(n), C.byref(rb), C.byref(mb))
+    if cnt < 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    try:
+        block = _arr(p.value, n.value, np.uint8)
+    finally:
+        l.vgh_free(p)
+    return block, int(cnt), rb.value, mb.value
 
 
 def sniff_input(path):

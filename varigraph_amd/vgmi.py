@@ -79,6 +79,8 @@ def load_library():
         "vgmi_fastq_gzip_status": (i32, [vp, C.POINTER(u64), C.POINTER(u32)]),
         "vgmi_gunzip_buffer": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(i32), C.POINTER(u32)]),
         "vgmi_fastq_close": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), vp, sz, C.POINTER(sz)]),
+        "vgmi_fastq_set_min_quality": (i32, [vp, u32]),
+        "vgmi_fastq_masked_bases": (i32, [vp, C.POINTER(u64)]),
         "vgmi_sketch_keys": (i32, [vp, vp, sz, vp, sz, u32, vp]),
         "vgmi_bloom_params": (i32, [u64, C.c_double, C.POINTER(u64), C.POINTER(u32)]),
         "vgmi_bloom_create": (i32, [vp, u64, u32, vp]),
@@ -199,6 +201,7 @@ class Context:
         self._h = h
         self.n_keys = 0
         self.n_node_entries = 0
+        self._quality_streams = set()      # open streams on which vgmi_fastq_set_min_quality was called
 
     def close(self):
         if getattr(self, "_h", None):
@@ -343,12 +346,36 @@ class Context:
         self._chk(self._l.vgmi_pt_live_check(self._h, out))
         return tuple(int(v) for v in out)
 
-    def fastq_text(self, text, piece=None):
+    def fastq_text(self, text, piece=None, min_quality=0):
         """Device-side FASTQ parser over one stream of file text (bytes), committed in pieces of `piece` bytes (default:
-        whole staging buffers).  Returns dict(n_records, n_bases, consumed, stopped, tail)."""
+        whole staging buffers).  min_quality: bases whose quality is below it are counted as N (vgmi_fastq_set_min_quality; 0 = off).
+        Returns dict(n_records, n_bases, consumed, stopped, tail, masked_bases)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        self._set_min_quality(fq, min_quality)
         return self._text_stream(fq, text, piece)
+
+    def _set_min_quality(self, fq, min_quality):
+        """vgmi_fastq_set_min_quality on a stream just opened; a refusal closes the stream and raises.  The int 0 (the default) does
+        not call the C entry at all: the stream is the one it was before the option existed.  A tuple calls it once per value, in
+        order and also with 0 -- (0,) and (20, 0) are how the tests show that setting 0 is the same as never setting anything."""
+        if isinstance(min_quality, int) and not min_quality:
+            return
+        for q in (min_quality,) if isinstance(min_quality, int) else min_quality:
+            rc = self._l.vgmi_fastq_set_min_quality(fq, q)
+            if rc:
+                msg = self._l.vgmi_last_error(self._h).decode()
+                self._l.vgmi_fastq_close(fq, None, None, None, None, None, 0, None)
+                raise VgmiError(rc, msg)
+        self._quality_streams.add(fq.value)
+
+    def _masked_bases(self, fq):
+        """vgmi_fastq_masked_bases of a stream about to be closed; a stream whose setter was never called is not asked (0)"""
+        if fq.value not in self._quality_streams:
+            return 0
+        self._quality_streams.discard(fq.value)
+        n = C.c_uint64()
+        return n.value if self._l.vgmi_fastq_masked_bases(fq, C.byref(n)) == 0 else None
 
     def fasta_text(self, text, piece=None):
         """Device-side FASTA parser (vgmi_fastq_open_fasta) over one stream of file text, as fastq_text.  The last record of the text
@@ -373,16 +400,18 @@ class Context:
         finally:
             nr, nb, cons, st, tl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int(), C.c_size_t()
             tail = C.create_string_buffer(1 << 20)
+            masked = self._masked_bases(fq)
             rc = self._l.vgmi_fastq_close(fq, C.byref(nr), C.byref(nb), C.byref(cons), C.byref(st), tail, 1 << 20, C.byref(tl))
         self._chk(rc)
         return {"n_records": nr.value, "n_bases": nb.value, "consumed": cons.value, "stopped": bool(st.value),
-                "tail": tail.raw[:tl.value]}
+                "tail": tail.raw[:tl.value], "masked_bases": masked}
 
-    def fastq_bgzf(self, comp, piece=None):
+    def fastq_bgzf(self, comp, piece=None, min_quality=0):
         """Block-gzip bytes through the device inflate + parser.  Returns the dict of fastq_text plus inflate_failed,
         good_compressed_bytes, taken (compressed bytes handed over as whole members)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        self._set_min_quality(fq, min_quality)
         return self._bgzf_stream(fq, comp, piece)
 
     def fasta_bgzf(self, comp, piece=None):
@@ -391,12 +420,13 @@ class Context:
         self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
         return self._bgzf_stream(fq, comp, piece)
 
-    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None):
+    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0):
         """A BAM file's block-gzip bytes through the device inflate + BAM record kernels (vgmi_fastq_open_bam): header_bytes = the
         header's length in the decompressed stream (magic to the last reference), n_ref its number of references.  Returns the dict of fastq_bgzf; consumed
         counts decompressed bytes, header included."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_bam(self._h, header_bytes, n_ref, C.byref(fq)))
+        self._set_min_quality(fq, min_quality)
         return self._bgzf_stream(fq, comp, piece)
 
     def _bgzf_stream(self, fq, comp, piece):
@@ -427,17 +457,19 @@ class Context:
         finally:
             nr, nbs, cons, st, tl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int(), C.c_size_t()
             tail = C.create_string_buffer(1 << 20)
+            masked = self._masked_bases(fq)
             rc = self._l.vgmi_fastq_close(fq, C.byref(nr), C.byref(nbs), C.byref(cons), C.byref(st), tail, 1 << 20, C.byref(tl))
         self._chk(rc)
         return {"n_records": nr.value, "n_bases": nbs.value, "consumed": cons.value, "stopped": bool(st.value),
-                "tail": tail.raw[:tl.value], "inflate_failed": bool(failed.value), "good_compressed_bytes": good.value,
+                "tail": tail.raw[:tl.value], "masked_bases": masked, "inflate_failed": bool(failed.value), "good_compressed_bytes": good.value,
                 "reason": reason.value, "taken": total_taken}
 
-    def fastq_gzip(self, comp, piece=None):
+    def fastq_gzip(self, comp, piece=None, min_quality=0):
         """Ordinary gzip bytes through the device inflate + parser (vgmi_fastq_commit_gzip).  Returns the dict of fastq_text plus stop
         (1 data over, 2 the device gave up), device_text_bytes, reason, taken (compressed bytes used up)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        self._set_min_quality(fq, min_quality)
         return self._gzip_stream(fq, comp, piece)
 
     def fasta_gzip(self, comp, piece=None):
@@ -475,9 +507,11 @@ class Context:
         finally:
             nr, nbs, cons, sp, tl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int(), C.c_size_t()
             tail = C.create_string_buffer(1 << 20)
+            masked = self._masked_bases(fq)
             rc = self._l.vgmi_fastq_close(fq, C.byref(nr), C.byref(nbs), C.byref(cons), C.byref(sp), tail, 1 << 20, C.byref(tl))
         self._chk(rc)
         return {"n_records": nr.value, "n_bases": nbs.value, "consumed": cons.value, "stopped": bool(sp.value), "tail": tail.raw[:tl.value],
+                "masked_bases": masked,
                 "stop": stop, "device_text_bytes": dtext.value, "reason": reason.value, "taken": total_taken}
 
     def gunzip(self, comp, cap):
