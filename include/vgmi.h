@@ -520,6 +520,29 @@ int vgmi_hmm_emissions_select_wide(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used
 int vgmi_hmm_tallies_select_wide(vgmi_ctx *ctx, uint32_t bit_len, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count,
                                  const uint32_t *row_win, const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b,
                                  uint32_t n_used, uint32_t n_windows, const uint8_t *win_used, uint32_t *out, uint8_t *unique_out);
+/* ---- ... and a DIPLOID sample over a panel of 255 to 511 haplotypes: 33 to 64 bytes of haplotype bits per entry -----------------------
+ * The _wide calls' contracts, with these differences: bit_len is 33 .. 64 and an entry becomes W = 8 words (64 bytes) on the device; a
+ * haplotype id no longer fits a byte, so win_used is 16 bits per id (ids up to 8 * bit_len - 2, at most 510); n_hap goes up to
+ * 8 * bit_len - 1, at most 511; win_top_mask is n_windows x 8 words.  gt0 and fix_mask stay masks over the at most 16 places: a part
+ * made by emissions_select_wide16 is scored again by vgmi_hmm_part_fix_rows, and _part_set_rows, _part_calls, _part_calls_fre and
+ * _part_fetch serve it as any part.  The table is the one a _wide upload makes (either upload replaces the other's arrays), and
+ * vgmi_hmm_sample_upload, _alive_upload and _alive_fetch serve it.
+ * VGMI_E_INVALID (the context serves on): bit_len outside 33 .. 64, n_hap outside 1 .. 8 * bit_len - 1, a win_used id at or beyond
+ * 8 * bit_len - 1, n_used outside 1 .. 16, n_gt outside 1 .. 128, a row outside the entries or the windows.  VGMI_E_STATE: a _wide16 call
+ * on packed entries, on _wide entries or on none, or with another bit_len than the upload's; a _wide or packed call on _wide16 entries. */
+int vgmi_hmm_entries_upload_wide16(vgmi_ctx *ctx, const uint8_t *f, const uint8_t *bits /* n_entries x bit_len */, size_t n_entries, uint32_t bit_len);
+int vgmi_hmm_entries_reserve_wide16(vgmi_ctx *ctx, size_t n_entries, uint32_t bit_len);
+int vgmi_hmm_entries_fill_wide16(vgmi_ctx *ctx, size_t first, size_t n, const uint8_t *f, const uint8_t *bits /* n x bit_len */);
+int vgmi_hmm_support_wide16(vgmi_ctx *ctx, uint32_t bit_len, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t *entry_begin,
+                            const uint32_t *entry_count, const uint32_t *row_win, uint32_t *support_out /* n_windows x n_hap */);
+int vgmi_hmm_emissions_select_wide16(vgmi_ctx *ctx, uint32_t n_gt, uint32_t n_used, const uint8_t *pos_a, const uint8_t *pos_b, uint32_t n_windows,
+                                     const uint16_t *win_used /* n_windows x n_used */, const uint64_t *win_top_mask /* n_windows x 8 */,
+                                     uint32_t bit_len, float ave, double lower, double upper, const void *tables, uint64_t n_rows,
+                                     const uint64_t *entry_begin, const uint32_t *entry_count, const uint32_t *row_win, const uint16_t *gt0,
+                                     uint32_t *n_kept_out, uint8_t *flags_out, vgmi_hmm_part **out);
+int vgmi_hmm_tallies_select_wide16(vgmi_ctx *ctx, uint32_t bit_len, uint64_t n_rows, const uint64_t *entry_begin, const uint32_t *entry_count,
+                                   const uint32_t *row_win, const uint32_t *winner, uint32_t n_gt, const uint8_t *pos_a, const uint8_t *pos_b,
+                                   uint32_t n_used, uint32_t n_windows, const uint16_t *win_used, uint32_t *out, uint8_t *unique_out);
 /* ---- ... and a POLYPLOID sample over such a panel: vgmi_hmm_emissions_select_ploidy, its second launch and vgmi_hmm_tallies_ploidy with
  * every mask over haplotype ids W words wide (word i: haplotypes 64 i .. 64 i + 63).  Ids in win_haps go up to 8 * bit_len - 2; the mask
  * of a window's genotypes' haplotypes is derived from win_haps.  Ploidy 2 .. 8 and n_gt 1 .. 64 for the emissions, ploidy 2 .. 4 and n_gt

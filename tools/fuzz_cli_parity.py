@@ -4,8 +4,9 @@ genome size, variant mix, cohort size and ploidy, k, construct mode, reads per s
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
   fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy]
 --max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from.
---max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100 and 127 diploid VCF samples, as
-far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 255 haplotypes, 7 to 32 bytes of haplotype bits per k-mer.
+--max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100, 127, 130, 160 and 255 diploid
+VCF samples, as far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 511 haplotypes, 7 to 64 bytes of haplotype bits
+per k-mer (N = 127 draws what it drew before the last three were added; a seed's case depends on N, as it always has).
 --only-wide-ploidy runs, of the seeds given, only those whose draw is a polyploid sample (ploidy 3 and more) over a cohort of 49 or more
 haplotypes (DESIGN_INGEST_HMM 4.18; with VGH_HMM_WIDE_PLOIDY_DEVICE=1 in the environment the device path of such samples); the others are
 passed over before anything is built.  Every seed keeps its case."""
@@ -62,7 +63,7 @@ def dress(path, rng):
 
 
 MAX_PLOIDY = 4      # --max-ploidy N: ploidy 5 .. N joins both draws (DESIGN_INGEST_HMM 4.15: the device's HMM for samples of ploidy 5 .. 8)
-MAX_VCF_SAMPLES = 7      # --max-vcf-samples N: diploid cohorts of up to N samples (DESIGN_INGEST_HMM 4.16: the device's HMM over panels of 48 to 254 haplotypes)
+MAX_VCF_SAMPLES = 7      # --max-vcf-samples N: diploid cohorts of up to N samples (DESIGN_INGEST_HMM 4.16, 4.21: the device's HMM over panels of 48 to 511 haplotypes)
 ONLY_WIDE_PLOIDY = False      # --only-wide-ploidy: seeds whose draw is anything else are passed over
 FORCE = {}      # --k K / --genome G on the command line: the drawn value replaced (round 6: campaigns of k = 28 over graphs on either side of 65 536 k-mers)
 
@@ -73,7 +74,7 @@ def case(seed):
     genome = int(pick([40_000, 90_000, 200_000, 400_000, 1_500_000, 1_500_000]))      # (the last: more than 65 536 k-mers with dense variants -- the context table at any k)
     more_ploidy = list(range(5, MAX_PLOIDY + 1))
     vploidy = pick([2, 2, 2, 3, 4] + more_ploidy)
-    more_samples = [n for n in (24, 33, 48, 64, 100, 127) if n <= MAX_VCF_SAMPLES]
+    more_samples = [n for n in (24, 33, 48, 64, 100, 127, 130, 160, 255) if n <= MAX_VCF_SAMPLES]
     n_samples = pick([1, 2, 3, 5, 7] + more_samples) if vploidy <= 2 else pick([1, 2, 3])
     k = pick([27, 27, 27, 21, 25, 22, 28, 15, 11, 19, 23, 20, 24, 26])
     k = FORCE.get("k", k)

@@ -2,7 +2,7 @@
 // list count as carrying the k-mer (hidden_states' rules, src/genotype.cpp:690-760) and whether a drawn haplotype carries it at all (the
 // prune, :673-686).  Two forms of the same reading:
 //   packed   one 64-bit word per entry -- coverage | multiplicity << 8 | haplotype bits << 16 -- for graphs of up to six bytes of bits
-//   bytes    coverage, multiplicity and the entry's `bl` bytes as they stand in the graph's bit vectors, for 7 to 32 bytes (up to 254
+//   bytes    coverage, multiplicity and the entry's `bl` bytes as they stand in the graph's bit vectors, for 7 to 64 bytes (up to 511
 //            haplotypes); masks over haplotype ids are then W = words_of(bl) 64-bit words, word i holding haplotypes 64 i .. 64 i + 63
 // In both the LAST bit of the vector (bit 8 bl - 1) is a flag, never a haplotype.  The device's kernels read the same entries the same way
 // (vgmi_hmm.hip); tests/native/entry_bits_check.cpp holds the two forms against each other and against a literal model.
@@ -13,7 +13,7 @@
 
 namespace vgh {
 
-inline uint32_t words_of(uint32_t bl) { return bl <= 8 ? 1u : bl <= 16 ? 2u : 4u; }
+inline uint32_t words_of(uint32_t bl) { return bl <= 8 ? 1u : bl <= 16 ? 2u : bl <= 32 ? 4u : 8u; }
 
 // 2: the entry asks for the haplotypes' sequences (under-covered, multi-copy); 1: it is checked once they are there; 0: neither
 inline uint32_t entry_low_multi(uint8_t c, uint8_t f, double lower) { return (c < lower && f >= 2) ? 2u : (!(c > lower || f <= 1)) ? 1u : 0u; }

@@ -1828,15 +1828,17 @@ void Genotyper::fill_packed(Run& r, uint32_t threads)
     r.packed = packed_.data();
 }
 
-// The graph's half of every entry for a panel of 48 to 254 haplotypes -- multiplicity and the 7 to 32 bytes of haplotype bits -- to the
+// The graph's half of every entry for a panel of 48 to 511 haplotypes -- multiplicity and the 7 to 64 bytes of haplotype bits -- to the
 // device, once per graph and context: gathered through node_key_index chunk by chunk into a staging buffer (threaded like fill_packed)
-// and handed over (vgmi_hmm_entries_fill_wide); no second copy of n_entries x bitlen bytes is kept on the host.
+// and handed over (vgmi_hmm_entries_fill_wide, above 32 bytes _wide16); no second copy of n_entries x bitlen bytes is kept on the host.
 void Genotyper::upload_entries_wide(uint32_t threads)
 {
     const size_t n_entries = g_.node_key_index.size(), bl = g_.bitlen;
     const auto t0 = std::chrono::steady_clock::now();
-    device_check(dev_, vgmi_hmm_entries_reserve_wide(dev_, n_entries, (uint32_t)bl), "device HMM emissions: ");
-    constexpr size_t kChunk = (size_t)1 << 22;      // entries per hand-over: at most 128 MiB of bits
+    const bool ids16 = bl > 32;
+    device_check(dev_, ids16 ? vgmi_hmm_entries_reserve_wide16(dev_, n_entries, (uint32_t)bl) : vgmi_hmm_entries_reserve_wide(dev_, n_entries, (uint32_t)bl),
+                 "device HMM emissions: ");
+    const size_t kChunk = (size_t)1 << (ids16 ? 21 : 22);      // entries per hand-over: at most 128 MiB of bits
     const size_t chunk = std::min(kChunk, std::max<size_t>(n_entries, 1));
     std::vector<uint8_t> f(chunk), bits(chunk * bl);
     const uint32_t nt = std::max(1u, threads);
@@ -1855,7 +1857,8 @@ void Genotyper::upload_entries_wide(uint32_t threads)
         for (uint32_t t = 1; t < nt; ++t) fill.emplace_back(part, m * t / nt, m * (t + 1) / nt);
         part(0, m / nt);
         for (auto& th : fill) th.join();
-        device_check(dev_, vgmi_hmm_entries_fill_wide(dev_, lo, m, f.data(), bits.data()), "device HMM emissions: ");
+        device_check(dev_, ids16 ? vgmi_hmm_entries_fill_wide16(dev_, lo, m, f.data(), bits.data()) : vgmi_hmm_entries_fill_wide(dev_, lo, m, f.data(), bits.data()),
+                     "device HMM emissions: ");
     }
     if (g_phase_on)
         std::fprintf(stderr, "[varigraph-mi] HMM haplotype bits on the device: %zu bytes per entry (%zu entries, %.3f s)\n", bl, n_entries,
@@ -1963,7 +1966,7 @@ Genotyper::DevicePaths Genotyper::device_paths(const Run& r, const std::vector<T
         const size_t need = 3 * total_room * sel_n_gt * sizeof(long double) * ((4 + dev_parts_ - 1) / dev_parts_) + (size_t(1) << 30);
         return vgmi_device_memory(dev_, &free_b, &total_b) != VGMI_OK || need <= free_b - free_b / 10;
     }());
-    // A graph of 7 to 32 bytes of haplotype bits (48 to 254 haplotypes) has no packed words: a diploid sample's entries go to the device as
+    // A graph of 7 to 64 bytes of haplotype bits (48 to 511 haplotypes) has no packed words: a diploid sample's entries go to the device as
     // bytes (r.wide), once per graph and context -- W words and a multiplicity byte per entry that have to fit as well
     bool wide_fits = true;
     if (r.wide && !entries_uploaded_) {
@@ -2726,8 +2729,8 @@ void Genotyper::panel_part(RunShared& s, PanelSample& ps, size_t part)
 // device's recursion takes one list length per part: the windows are dealt into parts by the length of their lists (SelectedPart), each
 // with its own emission launch, keep matrix per window and 1 / n_gt, and its own tally launch (vgmi_hmm_tallies_ploidy) over the same lists:
 // the lines of a polyploid sample are written from the device's numbers as a diploid sample's are.
-// Over a graph of 7 to 32 bytes of haplotype bits (Run::wide) the entries are on the device as bytes and every mask over haplotype ids is
-// mask_words words: a diploid sample always (4.16), a polyploid one when VGH_HMM_WIDE_PLOIDY_DEVICE=1 asks for it and its windows name at
+// Over a graph of 7 to 64 bytes of haplotype bits (Run::wide) the entries are on the device as bytes and every mask over haplotype ids is
+// mask_words words: a diploid sample always (4.16; above 32 bytes the _wide16 calls with 16-bit ids, 4.21), a polyploid one up to 32 bytes when VGH_HMM_WIDE_PLOIDY_DEVICE=1 asks for it and its windows name at
 // most 64 haplotypes, the width of the masks over places that the sequence checks and gt0 work on (4.18; id_masks.hpp).
 struct Genotyper::SelectedSample {
     float ave = 0;
@@ -2741,9 +2744,11 @@ struct Genotyper::SelectedSample {
     std::vector<std::vector<std::vector<uint16_t>>> win_gts;
     std::vector<GenotypeList> win_glist;
     std::vector<uint8_t> win_used8;          // diploid: the drawn haplotypes as the device takes them
+    std::vector<uint16_t> win_used16;        // ... above 32 bytes of haplotype bits, where an id does not fit a byte (ids16)
+    bool ids16 = false;
     std::vector<uint64_t> win_mask;          // the drawn haplotypes: mask_words words per window (one unless the entries are bytes)
     uint32_t mask_words = 1;
-    bool wide = false;                       // the entries are on the device as bytes (7 to 32 of them): the _wide calls
+    bool wide = false;                       // the entries are on the device as bytes (7 to 64 of them): the _wide calls, _wide16 above 32
     bool by_freq = false;                    // `-m fre`: no keep matrix, no powers; per window the table of its genotypes' haplotypes' scores
     std::vector<std::vector<long double>> win_freq;
     // what the VGH_TIMING line sums over the parts
@@ -2800,6 +2805,7 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     if (ss.wide && !r.wide) throw std::runtime_error("internal: a sample without packed entries on the selected path");
     ss.mask_words = ss.wide ? vgh::words_of((uint32_t)g_.bitlen) : 1u;
     const uint32_t bit_len = (uint32_t)g_.bitlen;
+    ss.ids16 = ss.wide && bit_len > 32;
     if (!entries_uploaded_) {
         if (ss.wide) upload_entries_wide(s.n_threads);
         else device_check(dev_, vgmi_hmm_entries_upload(dev_, packed_.data(), packed_.size()), "device HMM emissions: ");
@@ -2851,7 +2857,10 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     const int64_t ta = s.since_begin();
     // 1. the support the draw is weighted by, on the device
     std::vector<uint32_t> support(nw * n_hap_, 0);
-    if (ss.wide)
+    if (ss.ids16)
+        device_check(dev_, vgmi_hmm_support_wide16(dev_, bit_len, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
+                     "device HMM support: ");
+    else if (ss.wide)
         device_check(dev_, vgmi_hmm_support_wide(dev_, bit_len, n_hap_, (uint32_t)nw, sup_begin.size(), sup_begin.data(), sup_count.data(), sup_win.data(), support.data()),
                      "device HMM support: ");
     else
@@ -2863,7 +2872,8 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
     ss.win_used.resize(ss.blocks ? nw : 0);
     ss.win_gts.resize(nw);
     ss.win_glist.resize(nw);
-    ss.win_used8.assign(ss.blocks ? 0 : nw * n_used, 0);
+    ss.win_used8.assign(ss.blocks || ss.ids16 ? 0 : nw * n_used, 0);
+    ss.win_used16.assign(ss.ids16 ? nw * n_used : 0, 0);
     ss.win_mask.assign(nw * ss.mask_words, 0);
     ss.win_freq.resize(ss.by_freq ? nw : 0);
     std::vector<uint64_t> gt0(n_rows ? n_rows : 1, 0);
@@ -2881,7 +2891,8 @@ Genotyper::Emitted Genotyper::hmm_selected(RunShared& s)
             std::sort(used.begin(), used.end());
             used.erase(std::unique(used.begin(), used.end()), used.end());
         } else {
-            for (size_t p = 0; p < n_used; ++p) ss.win_used8[wi * n_used + p] = (uint8_t)top[p];
+            if (ss.ids16) std::copy(top.begin(), top.end(), ss.win_used16.begin() + wi * n_used);
+            else for (size_t p = 0; p < n_used; ++p) ss.win_used8[wi * n_used + p] = (uint8_t)top[p];
             ss.win_gts[wi].resize(n_gt);
             for (size_t gi = 0; gi < n_gt; ++gi) ss.win_gts[wi][gi] = {top[ss.pos_a[gi]], top[ss.pos_b[gi]]};
         }
@@ -2997,7 +3008,12 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
                              "device HMM emissions: ");
         } else {
             const std::vector<uint16_t> gt0_16(pt.gt0.begin(), pt.gt0.end());      // (<= 16 places)
-            if (ss.wide)      // (a diploid sample has one part: its windows are the run's, in order, and so are the masks)
+            if (ss.ids16)
+                device_check(dev_, vgmi_hmm_emissions_select_wide16(dev_, (uint32_t)n_gt, ss.n_drawn, ss.pos_a.data(), ss.pos_b.data(), (uint32_t)nwp, ss.win_used16.data(),
+                                                                    ss.win_mask.data(), (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
+                                                                    pt.e_count.data(), pt.row_win.data(), gt0_16.data(), n_kept.data(), flags.data(), &ph.p),
+                             "device HMM emissions: ");
+            else if (ss.wide)      // (a diploid sample has one part: its windows are the run's, in order, and so are the masks)
                 device_check(dev_, vgmi_hmm_emissions_select_wide(dev_, (uint32_t)n_gt, ss.n_drawn, ss.pos_a.data(), ss.pos_b.data(), (uint32_t)nwp, ss.win_used8.data(),
                                                                   ss.win_mask.data(), (uint32_t)g_.bitlen, ave, lower, upper, ss.tab.data(), n_rows, pt.e_begin.data(),
                                                                   pt.e_count.data(), pt.row_win.data(), gt0_16.data(), n_kept.data(), flags.data(), &ph.p),
@@ -3124,7 +3140,12 @@ size_t Genotyper::selected_part(RunShared& s, SelectedSample& ss, const Selected
     if (device_tallies && n_steps && !ss.blocks) {
         tally.resize(4 * n_rows);
         tally_uniq.resize(n_rows);
-        if (ss.wide)
+        if (ss.ids16)
+            device_check(dev_, vgmi_hmm_tallies_select_wide16(dev_, (uint32_t)g_.bitlen, n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(),
+                                                              (uint32_t)n_gt, ss.pos_a.data(), ss.pos_b.data(), ss.n_drawn, (uint32_t)nwp, ss.win_used16.data(), tally.data(),
+                                                              tally_uniq.data()),
+                         "device tallies: ");
+        else if (ss.wide)
             device_check(dev_, vgmi_hmm_tallies_select_wide(dev_, (uint32_t)g_.bitlen, n_rows, pt.e_begin.data(), pt.e_count.data(), pt.row_win.data(), winner.data(),
                                                             (uint32_t)n_gt, ss.pos_a.data(), ss.pos_b.data(), ss.n_drawn, (uint32_t)nwp, ss.win_used8.data(), tally.data(),
                                                             tally_uniq.data()),
@@ -3179,9 +3200,11 @@ std::string Genotyper::run(const uint8_t* cov, float hap_kmer_coverage, const st
     r.cfg = &cfg;
     r.haploid_num = std::min(cfg.haploid_num, n_hap_);
     if (g_.bitlen <= 6) fill_packed(r, cfg.threads);
-    else      // (a polyploid sample over such a graph only when asked: VGH_HMM_WIDE_PLOIDY_DEVICE=1, DESIGN_INGEST_HMM.md 4.18)
-        r.wide = g_.bitlen <= 32 && !knob_off("VGH_HMM_WIDE_DEVICE") &&
-                 (cfg.sample_ploidy == 2 || (knob_on("VGH_HMM_WIDE_PLOIDY_DEVICE") && vgh::wide_ploidy_sample(g_.bitlen, cfg.sample_ploidy, r.haploid_num)));
+    else      // (a polyploid sample over such a graph only when asked and up to 32 bytes: VGH_HMM_WIDE_PLOIDY_DEVICE=1, DESIGN_INGEST_HMM.md 4.18; a diploid one
+              // up to 64 bytes, 4.21)
+        r.wide = !knob_off("VGH_HMM_WIDE_DEVICE") &&
+                 ((cfg.sample_ploidy == 2 && g_.bitlen <= 64) ||
+                  (knob_on("VGH_HMM_WIDE_PLOIDY_DEVICE") && vgh::wide_ploidy_sample(g_.bitlen, cfg.sample_ploidy, r.haploid_num)));
     reset_calls();
 
     RunShared s(r);

@@ -159,7 +159,7 @@ private:
 
     // ---- run(), step by step
     void fill_packed(Run& r, uint32_t threads);
-    void upload_entries_wide(uint32_t threads);      // 7 to 32 bytes of haplotype bits per entry: the graph's half of the entries to dev_
+    void upload_entries_wide(uint32_t threads);      // 7 to 64 bytes of haplotype bits per entry: the graph's half of the entries to dev_
     void reset_calls();
     std::vector<Task> windows(const GenotypeConfig& cfg);
     DevicePaths device_paths(const Run& r, const std::vector<Task>& tasks, std::vector<WindowWork>& works, bool refuse_select) const;

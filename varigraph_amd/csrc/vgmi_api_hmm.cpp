@@ -226,12 +226,20 @@ std::vector<uint8_t> hmm_pos_pairs(const uint8_t* pos_a, const uint8_t* pos_b, u
     return pos;
 }
 
-// a window's haplotypes in 16 bytes, whatever n_used
-std::vector<uint8_t> hmm_used16(const uint8_t* win_used, size_t n_windows, uint32_t n_used)
+// a window's haplotypes in 16 ids, whatever n_used; an id is id_bytes wide (1, or 2 for the _wide16 calls)
+std::vector<uint8_t> hmm_used16(const void* win_used, size_t n_windows, uint32_t n_used, uint32_t id_bytes = 1)
 {
-    std::vector<uint8_t> wu16(n_windows * 16, 0);
-    for (size_t w = 0; w < n_windows; ++w) memcpy(&wu16[w * 16], win_used + w * n_used, n_used);
+    std::vector<uint8_t> wu16(n_windows * 16 * id_bytes, 0);
+    for (size_t w = 0; w < n_windows; ++w) memcpy(&wu16[w * 16 * id_bytes], static_cast<const uint8_t*>(win_used) + w * n_used * id_bytes, (size_t)n_used * id_bytes);
     return wu16;
+}
+
+// every id of a window's list is a haplotype of the bit vector
+bool hmm_ids_below(const void* win_used, size_t n, uint32_t id_bytes, uint32_t n_ids)
+{
+    for (size_t i = 0; i < n; ++i)
+        if ((id_bytes == 2 ? static_cast<const uint16_t*>(win_used)[i] : static_cast<const uint8_t*>(win_used)[i]) >= n_ids) return false;
+    return true;
 }
 
 // recursion (+ posterior when gid is given) in one pass over device buffers: alpha / beta leave the device only if `out` asks.
@@ -382,11 +390,13 @@ void hmm_wide_free(vgmi_ctx* c)
 }
 
 // a _wide call's width against the upload's: VGMI_E_INVALID for a width no upload can have, VGMI_E_STATE for another form or width
-int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len)
+// (ids16: a _wide16 call, whose uploads have 33 to 64 bytes -- so a call of one family on the other's entries differs in width)
+int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len, bool ids16 = false)
 {
-    if (bit_len < 1 || bit_len > 32) return fail(c, VGMI_E_INVALID, std::string(who) + ": 1..32 bytes of haplotype bits");
+    if (ids16 && (bit_len < 33 || bit_len > 64)) return fail(c, VGMI_E_INVALID, std::string(who) + ": 33..64 bytes of haplotype bits");
+    if (!ids16 && (bit_len < 1 || bit_len > 32)) return fail(c, VGMI_E_INVALID, std::string(who) + ": 1..32 bytes of haplotype bits");
     if (!c->d_hmm_bits || !c->d_hmm_f || !c->d_hmm_cov || !c->d_hmm_alive)
-        return fail(c, VGMI_E_STATE, std::string(who) + ": upload the entries with vgmi_hmm_entries_upload_wide first");
+        return fail(c, VGMI_E_STATE, std::string(who) + (ids16 ? ": upload the entries with vgmi_hmm_entries_upload_wide16 first" : ": upload the entries with vgmi_hmm_entries_upload_wide first"));
     if (bit_len != c->hmm_bit_len) return fail(c, VGMI_E_STATE, std::string(who) + ": the entries were uploaded with another number of bytes of haplotype bits");
     return VGMI_OK;
 }
@@ -397,21 +407,23 @@ int hmm_check_wide(vgmi_ctx* c, const char* who, uint32_t bit_len)
 struct HmmForm {
     bool wide;
     uint32_t bit_len;      // the call's (packed: where the call has one)
+    bool ids16 = false;    // a _wide16 call: 33 to 64 bytes, a window's drawn haplotypes as 16-bit ids
     // the upload is there and is this form's; `missing`: the packed call's words for none
     int check(vgmi_ctx* c, const char* who, const char* missing, bool need_alive = true) const
     {
-        if (wide) return hmm_check_wide(c, who, bit_len);
+        if (wide) return hmm_check_wide(c, who, bit_len, ids16);
         if (!c->d_hmm_entries || !c->d_hmm_cov || (need_alive && !c->d_hmm_alive)) return fail(c, VGMI_E_STATE, std::string(who) + ": " + missing);
         return VGMI_OK;
     }
     uint32_t words(const vgmi_ctx* c) const { return wide ? c->hmm_words : 1u; }
     HmmEntries entries(const vgmi_ctx* c) const { return wide ? HmmEntries{c->d_hmm_f, c->hmm_words, c->d_hmm_bits} : HmmEntries{nullptr, 0u, c->d_hmm_entries}; }
     uint32_t n_ids() const { return 8 * bit_len - 1; }      // the last bit is no haplotype
+    uint32_t id_bytes() const { return ids16 ? 2u : 1u; }
 };
 
 struct HmmSelect {      // haplotypes selected per window (vgmi_hmm_emissions_select)
     uint32_t n_windows;
-    const uint8_t* win_used;          // n_windows x n_used
+    const void* win_used;             // n_windows x n_used ids of the form's width
     const uint64_t* win_top_mask;     // n_windows x the form's words
     const uint32_t* row_win;          // n_rows
 };
@@ -498,7 +510,7 @@ int hmm_emissions_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_gt, uint32_t
     HmmEmitCall ec(c, n_rows, 2, ploidy);
     HmmCall& call = ec.call;
     const size_t n_win = sel ? sel->n_windows : 0, b_mask = n_win * 8 * form.words(c);      // per-window selection: row_win | win_used | win_top_mask
-    const size_t o_rw = call.add(sel ? n_rows * 4 : 0), o_wu = call.add(n_win * 16), o_wm = call.add(b_mask);
+    const size_t o_rw = call.add(sel ? n_rows * 4 : 0), o_wu = call.add(n_win * 16 * form.id_bytes()), o_wm = call.add(b_mask);
     std::vector<uint8_t> wu16;
     if (int rc = ec.begin(n_gt, entry_begin, entry_count, gt0, tables)) return rc;
     HmmCallTimes tm(form.wide);
@@ -523,7 +535,7 @@ int hmm_emissions_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_gt, uint32_t
     P.n_kept = call.at<uint32_t>(ec.o_nk);
     P.flags = call.at(ec.o_fl);
     if (sel) {
-        wu16 = hmm_used16(sel->win_used, n_win, n_used);
+        wu16 = hmm_used16(sel->win_used, n_win, n_used, form.id_bytes());
         call.upload(o_rw, sel->row_win, n_rows * 4);
         call.upload(o_wu, wu16.data(), wu16.size());
         call.upload(o_wm, sel->win_top_mask, b_mask);
@@ -709,18 +721,17 @@ int hmm_support_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_hap, uint32_t 
 // the calls' tallies with the haplotypes selected per window (vgmi_hmm_tallies_select, _wide); n_ids: the ids a selected haplotype may have
 int hmm_tallies_select_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_ids, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
                             const uint32_t* row_win, const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used,
-                            uint32_t n_windows, const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
+                            uint32_t n_windows, const void* win_used, uint32_t* out, uint8_t* unique_out)
 {
     if (!c || (n_rows && (!entry_begin || !entry_count || !row_win || !winner || !out || !unique_out)) || !pos_a || !pos_b || !win_used) return VGMI_E_INVALID;
     if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16 || n_windows < 1) return fail(c, VGMI_E_INVALID, "HMM tallies: 1..128 genotypes over 1..16 haplotypes");
     if (int rc = form.check(c, "HMM tallies", "upload the entries and the sample's coverage first")) return rc;
     for (uint32_t g = 0; g < n_gt; ++g)
         if (pos_a[g] >= n_used || pos_b[g] >= n_used) return fail(c, VGMI_E_INVALID, "HMM tallies: a genotype names a haplotype outside the list");
-    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
-        if (win_used[i] >= n_ids) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
+    if (!hmm_ids_below(win_used, (size_t)n_windows * n_used, form.id_bytes(), n_ids)) return fail(c, VGMI_E_INVALID, "HMM tallies: a selected haplotype outside the haplotype bits");
     if (int rc = hmm_check_rows(c, "HMM tallies", n_rows, entry_begin, entry_count, row_win, n_windows)) return rc;
     if (n_rows == 0) return VGMI_OK;
-    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used), pos_ab = hmm_pos_pairs(pos_a, pos_b, n_gt);
+    const std::vector<uint8_t> wu16 = hmm_used16(win_used, n_windows, n_used, form.id_bytes()), pos_ab = hmm_pos_pairs(pos_a, pos_b, n_gt);
     HmmCall call(c);
     const size_t o_beg = call.add(n_rows * 8), o_cnt = call.add(n_rows * 4), o_rw = call.add(n_rows * 4), o_win = call.add(n_rows * 4), o_out = call.add(n_rows * 16),
                  o_uni = call.add(n_rows), o_pos = call.add(pos_ab.size()), o_wu = call.add(wu16.size());
@@ -1161,10 +1172,13 @@ int vgmi_hmm_tallies_ploidy(vgmi_ctx* c, uint32_t ploidy, uint32_t n_gt, uint32_
 
 
 // ---- a diploid sample over a panel of 48 to 254 haplotypes (vgmi.h): the entries as a multiplicity byte and W words of haplotype bits ----
-int vgmi_hmm_entries_reserve_wide(vgmi_ctx* c, size_t n, uint32_t bit_len)
+namespace {
+// vgmi_hmm_entries_reserve_wide (1 to 32 bytes) and _wide16 (33 to 64): one table in the context, whichever call made it
+int hmm_entries_reserve_impl(vgmi_ctx* c, size_t n, uint32_t bit_len, bool ids16)
 {
     if (!c) return VGMI_E_INVALID;
-    if (bit_len < 1 || bit_len > 32) return fail(c, VGMI_E_INVALID, "HMM entries: 1..32 bytes of haplotype bits");
+    if (ids16 && (bit_len < 33 || bit_len > 64)) return fail(c, VGMI_E_INVALID, "HMM entries: 33..64 bytes of haplotype bits");
+    if (!ids16 && (bit_len < 1 || bit_len > 32)) return fail(c, VGMI_E_INVALID, "HMM entries: 1..32 bytes of haplotype bits");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->d_hmm_entries) (void)hipFree(c->d_hmm_entries);
     if (c->d_hmm_cov) (void)hipFree(c->d_hmm_cov);
@@ -1174,7 +1188,7 @@ int vgmi_hmm_entries_reserve_wide(vgmi_ctx* c, size_t n, uint32_t bit_len)
     c->d_hmm_cov = nullptr;
     c->d_hmm_alive = nullptr;
     c->hmm_n_entries = n;
-    const uint32_t W = bit_len <= 8 ? 1u : bit_len <= 16 ? 2u : 4u;
+    const uint32_t W = bit_len <= 8 ? 1u : bit_len <= 16 ? 2u : bit_len <= 32 ? 4u : 8u;
     if (hipMalloc(reinterpret_cast<void**>(&c->d_hmm_f), n ? n : 1) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&c->d_hmm_bits), (n ? n : 1) * 8 * W) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&c->d_hmm_cov), n ? n : 1) != hipSuccess ||
@@ -1196,10 +1210,28 @@ int vgmi_hmm_entries_reserve_wide(vgmi_ctx* c, size_t n, uint32_t bit_len)
     return VGMI_OK;
 }
 
-int vgmi_hmm_entries_fill_wide(vgmi_ctx* c, size_t first, size_t n, const uint8_t* f, const uint8_t* bits)
+// the _wide and _wide16 emission entry points: win_used holds ids of the form's width
+int hmm_emissions_select_wide_impl(vgmi_ctx* c, const HmmForm& form, uint32_t n_gt, uint32_t n_used, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_windows,
+                                   const void* win_used, const uint64_t* win_top_mask, float ave, double lower, double upper, const void* tables, uint64_t n_rows,
+                                   const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win, const uint16_t* gt0, uint32_t* n_kept_out,
+                                   uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    if (!c || !pos_a || !pos_b || !tables || !out) return VGMI_E_INVALID;
+    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes over 1..16 haplotypes");
+    if (n_windows < 1 || !win_used || !win_top_mask || (n_rows && !row_win)) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their selections");
+    if (n_rows && (!entry_begin || !entry_count || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
+    if (int rc = form.check(c, "HMM emissions", "")) return rc;
+    if (!hmm_ids_below(win_used, (size_t)n_windows * n_used, form.id_bytes(), form.n_ids()))
+        return fail(c, VGMI_E_INVALID, "HMM emissions: a selected haplotype outside the haplotype bits");
+    const HmmSelect sel{n_windows, win_used, win_top_mask, row_win};
+    return hmm_emissions_impl(c, form, n_gt, 2, n_used, static_cast<const uint8_t*>(win_used), hmm_pos_pairs(pos_a, pos_b, n_gt).data(), 0, ave, lower, upper, tables,
+                              n_rows, entry_begin, entry_count, gt0, n_kept_out, flags_out, out, &sel);
+}
+// vgmi_hmm_entries_fill_wide and _wide16: each fills the table its own reserve made
+int hmm_entries_fill_impl(vgmi_ctx* c, size_t first, size_t n, const uint8_t* f, const uint8_t* bits, bool ids16)
 {
     if (!c || (n && (!f || !bits))) return VGMI_E_INVALID;
-    if (!c->d_hmm_bits || !c->d_hmm_f) return fail(c, VGMI_E_STATE, "HMM entries: reserve the entries first");
+    if (!c->d_hmm_bits || !c->d_hmm_f || (c->hmm_words == 8) != ids16) return fail(c, VGMI_E_STATE, "HMM entries: reserve the entries first");
     if (first > c->hmm_n_entries || n > c->hmm_n_entries - first) return fail(c, VGMI_E_INVALID, "HMM entries: a range outside the reserved entries");
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t W = c->hmm_words, bl = c->hmm_bit_len;
@@ -1214,6 +1246,11 @@ int vgmi_hmm_entries_fill_wide(vgmi_ctx* c, size_t first, size_t n, const uint8_
     if (n) HIPCHK(c, hipMemcpy(c->d_hmm_f + first, f, n, hipMemcpyHostToDevice));
     return VGMI_OK;
 }
+}  // namespace
+
+int vgmi_hmm_entries_reserve_wide(vgmi_ctx* c, size_t n, uint32_t bit_len) { return hmm_entries_reserve_impl(c, n, bit_len, false); }
+
+int vgmi_hmm_entries_fill_wide(vgmi_ctx* c, size_t first, size_t n, const uint8_t* f, const uint8_t* bits) { return hmm_entries_fill_impl(c, first, n, f, bits, false); }
 
 int vgmi_hmm_entries_upload_wide(vgmi_ctx* c, const uint8_t* f, const uint8_t* bits, size_t n, uint32_t bit_len)
 {
@@ -1233,16 +1270,8 @@ int vgmi_hmm_emissions_select_wide(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, 
                                    const void* tables, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
                                    const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
 {
-    if (!c || !pos_a || !pos_b || !tables || !out) return VGMI_E_INVALID;
-    if (n_gt < 1 || n_gt > 128 || n_used < 1 || n_used > 16) return fail(c, VGMI_E_INVALID, "HMM emissions: 1..128 genotypes over 1..16 haplotypes");
-    if (n_windows < 1 || !win_used || !win_top_mask || (n_rows && !row_win)) return fail(c, VGMI_E_INVALID, "HMM emissions: windows without their selections");
-    if (n_rows && (!entry_begin || !entry_count || !gt0 || !n_kept_out || !flags_out)) return fail(c, VGMI_E_INVALID, "HMM emissions: rows without their arrays");
-    if (int rc = hmm_check_wide(c, "HMM emissions", bit_len)) return rc;
-    for (size_t i = 0; i < (size_t)n_windows * n_used; ++i)
-        if (win_used[i] >= 8 * bit_len - 1) return fail(c, VGMI_E_INVALID, "HMM emissions: a selected haplotype outside the haplotype bits");
-    const HmmSelect sel{n_windows, win_used, win_top_mask, row_win};
-    return hmm_emissions_impl(c, HmmForm{true, bit_len}, n_gt, 2, n_used, win_used, hmm_pos_pairs(pos_a, pos_b, n_gt).data(), 0, ave, lower, upper, tables, n_rows,
-                              entry_begin, entry_count, gt0, n_kept_out, flags_out, out, &sel);
+    return hmm_emissions_select_wide_impl(c, HmmForm{true, bit_len}, n_gt, n_used, pos_a, pos_b, n_windows, win_used, win_top_mask, ave, lower, upper, tables, n_rows,
+                                          entry_begin, entry_count, row_win, gt0, n_kept_out, flags_out, out);
 }
 
 int vgmi_hmm_tallies_select_wide(vgmi_ctx* c, uint32_t bit_len, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
@@ -1250,6 +1279,43 @@ int vgmi_hmm_tallies_select_wide(vgmi_ctx* c, uint32_t bit_len, uint64_t n_rows,
                                  uint32_t n_windows, const uint8_t* win_used, uint32_t* out, uint8_t* unique_out)
 {
     const HmmForm form{true, bit_len};
+    return hmm_tallies_select_impl(c, form, form.n_ids(), n_rows, entry_begin, entry_count, row_win, winner, n_gt, pos_a, pos_b, n_used, n_windows, win_used, out,
+                                   unique_out);
+}
+
+// ---- a diploid sample over a panel of 255 to 511 haplotypes (vgmi.h): 33 to 64 bytes of haplotype bits in eight words per entry, the
+// drawn haplotypes of a window as 16-bit ids.  The table is the context's one wide table: either upload replaces the other's arrays.
+int vgmi_hmm_entries_reserve_wide16(vgmi_ctx* c, size_t n, uint32_t bit_len) { return hmm_entries_reserve_impl(c, n, bit_len, true); }
+
+int vgmi_hmm_entries_fill_wide16(vgmi_ctx* c, size_t first, size_t n, const uint8_t* f, const uint8_t* bits) { return hmm_entries_fill_impl(c, first, n, f, bits, true); }
+
+int vgmi_hmm_entries_upload_wide16(vgmi_ctx* c, const uint8_t* f, const uint8_t* bits, size_t n, uint32_t bit_len)
+{
+    if (!c || (n && (!f || !bits))) return VGMI_E_INVALID;
+    if (int rc = vgmi_hmm_entries_reserve_wide16(c, n, bit_len)) return rc;
+    return vgmi_hmm_entries_fill_wide16(c, 0, n, f, bits);
+}
+
+int vgmi_hmm_support_wide16(vgmi_ctx* c, uint32_t bit_len, uint32_t n_hap, uint32_t n_windows, uint64_t n_rows, const uint64_t* entry_begin,
+                            const uint32_t* entry_count, const uint32_t* row_win, uint32_t* support_out)
+{
+    return hmm_support_impl(c, HmmForm{true, bit_len, true}, n_hap, n_windows, n_rows, entry_begin, entry_count, row_win, support_out);
+}
+
+int vgmi_hmm_emissions_select_wide16(vgmi_ctx* c, uint32_t n_gt, uint32_t n_used, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_windows,
+                                     const uint16_t* win_used, const uint64_t* win_top_mask, uint32_t bit_len, float ave, double lower, double upper,
+                                     const void* tables, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count, const uint32_t* row_win,
+                                     const uint16_t* gt0, uint32_t* n_kept_out, uint8_t* flags_out, vgmi_hmm_part** out)
+{
+    return hmm_emissions_select_wide_impl(c, HmmForm{true, bit_len, true}, n_gt, n_used, pos_a, pos_b, n_windows, win_used, win_top_mask, ave, lower, upper, tables,
+                                          n_rows, entry_begin, entry_count, row_win, gt0, n_kept_out, flags_out, out);
+}
+
+int vgmi_hmm_tallies_select_wide16(vgmi_ctx* c, uint32_t bit_len, uint64_t n_rows, const uint64_t* entry_begin, const uint32_t* entry_count,
+                                   const uint32_t* row_win, const uint32_t* winner, uint32_t n_gt, const uint8_t* pos_a, const uint8_t* pos_b, uint32_t n_used,
+                                   uint32_t n_windows, const uint16_t* win_used, uint32_t* out, uint8_t* unique_out)
+{
+    const HmmForm form{true, bit_len, true};
     return hmm_tallies_select_impl(c, form, form.n_ids(), n_rows, entry_begin, entry_count, row_win, winner, n_gt, pos_a, pos_b, n_used, n_windows, win_used, out,
                                    unique_out);
 }

@@ -72,8 +72,8 @@ struct vgmi_ctx {
     uint8_t* d_hmm_cov = nullptr;                    // vgmi_hmm_sample_upload: this sample's coverage per entry
     uint8_t* d_hmm_alive = nullptr;                  // per entry: still in its node's list (vgmi_hmm_alive_upload; pruned by vgmi_hmm_emissions_select)
     size_t hmm_n_entries = 0;
-    // vgmi_hmm_entries_upload_wide (panels of 48 to 254 haplotypes) in place of d_hmm_entries: a multiplicity byte and W words of haplotype
-    // bits per entry; hmm_bit_len is 0 unless the entries were uploaded that way
+    // vgmi_hmm_entries_upload_wide (panels of 48 to 254 haplotypes) or _wide16 (255 to 511: hmm_words 8) in place of d_hmm_entries: a
+    // multiplicity byte and W words of haplotype bits per entry; hmm_bit_len is 0 unless the entries were uploaded that way
     uint8_t* d_hmm_f = nullptr;
     unsigned long long* d_hmm_bits = nullptr;
     uint32_t hmm_bit_len = 0, hmm_words = 0;

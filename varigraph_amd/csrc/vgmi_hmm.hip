@@ -13,6 +13,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "vg_x80.h"
 #include "vgmi_kernels.h"
 
@@ -581,12 +583,14 @@ __device__ __forceinline__ void hmm_stage_tables(const uint8_t* tables, uint32_t
 
 // ---- how a node-list entry is read: two storage forms, one kernel body per family -----------------------------------------------------
 // packed (vgmi_hmm_entries_upload): one 64-bit word per entry, multiplicity << 8 | haplotype bits << 16 -- up to six bytes of bits.
-// wide (vgmi_hmm_entries_upload_wide, panels of 48 to 254 haplotypes): the multiplicity byte f[e] and the bit vector as it stands in the
-// graph, little-endian in W = 1, 2 or 4 64-bit words, zero-padded, entry-major: bits[e * W + i] -- one contiguous 8, 16 or 32-byte load.
+// wide (vgmi_hmm_entries_upload_wide, panels of 48 to 254 haplotypes; _wide16, up to 511): the multiplicity byte f[e] and the bit vector as it
+// stands in the graph, little-endian in W = 1, 2, 4 or 8 64-bit words, zero-padded, entry-major: bits[e * W + i] -- one contiguous 8, 16, 32
+// or 64-byte load.
 // The last bit of the vector (bit bl8 - 1) is the flag it is everywhere, never a haplotype.
 // A reader E states, for entry e:
 //   E::W            words of haplotype bits per entry, and per mask over haplotype ids (a window's, a row's gt0, a fix's)
 //   E::kMaxHap      the most haplotypes a panel has in this form (the support kernel's counters in LDS)
+//   E::Id           what a window's list of drawn haplotypes (win_used) holds: a byte, or 16 bits where ids go beyond 255 (W = 8)
 //   E::kDiploidOnly the place form of the emissions is launched for pairs of selected haplotypes only (no pos_more, no whole lists)
 //   head(e)         what ONE load of the entry gives before anything is known about it: packed the word, wide nothing
 //   mult(h, e)      the multiplicity: out of the head, or f[e]
@@ -600,6 +604,7 @@ __device__ __forceinline__ void hmm_stage_tables(const uint8_t* tables, uint32_t
 struct HmmPackedEntries {
     static constexpr uint32_t W = 1, kMaxHap = 48;
     static constexpr bool kDiploidOnly = false;
+    using Id = uint8_t;
     const unsigned long long* __restrict__ words;
     struct Head {
         unsigned long long word;
@@ -614,8 +619,9 @@ struct HmmPackedEntries {
 
 template <uint32_t WORDS>
 struct HmmWideEntries {
-    static constexpr uint32_t W = WORDS, kMaxHap = 256;
+    static constexpr uint32_t W = WORDS, kMaxHap = WORDS > 4u ? 512 : 256;
     static constexpr bool kDiploidOnly = true;
+    using Id = typename std::conditional<(WORDS > 4u), uint16_t, uint8_t>::type;
     const uint8_t* __restrict__ f;
     const unsigned long long* __restrict__ bits;
     struct Head {};
@@ -673,12 +679,12 @@ __global__ __launch_bounds__(128) void hmm_emissions_kernel(HmmEmitParams P)
     const uint32_t cnt = P.entry_count[rowi], gt0 = P.gt0[rowi];
     const bool active = g < P.n_gt;
     unsigned long long top_mask[W];
-    const uint8_t* wused = nullptr;
+    const typename E::Id* wused = nullptr;
     if (SELECT) {
         const uint32_t w = P.row_win[rowi];
 #pragma unroll
         for (uint32_t i = 0; i < W; ++i) top_mask[i] = P.win_top_mask[(size_t)w * W + i];
-        wused = P.win_used + (size_t)w * 16u;
+        wused = reinterpret_cast<const typename E::Id*>(P.win_used) + (size_t)w * 16u;
     } else {
         top_mask[0] = P.top_mask;
     }
@@ -898,7 +904,7 @@ __global__ __launch_bounds__(256) void hmm_tally_kernel(const unsigned long long
         uint32_t ha = hap_ab[2u * g], hb = hap_ab[2u * g + 1u];
         bool ok_a = true, ok_b = true;
         if (SELECT) {
-            const uint8_t* used = win_used + (size_t)row_win[r] * 16u;
+            const typename E::Id* used = reinterpret_cast<const typename E::Id*>(win_used) + (size_t)row_win[r] * 16u;
             ha = used[ha];
             hb = used[hb];
         } else {
@@ -1086,7 +1092,11 @@ __global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long lo
         const uint32_t w = row_win[ra];
         uint64_t rb = ra + 1;
         while (rb < r1 && row_win[rb] == w) ++rb;
-        if (threadIdx.x < E::kMaxHap) s_sup[threadIdx.x] = 0;
+        if (E::kMaxHap <= 256u) {
+            if (threadIdx.x < E::kMaxHap) s_sup[threadIdx.x] = 0;
+        } else {      // (more counters than lanes)
+            for (uint32_t h = threadIdx.x; h < E::kMaxHap; h += 256u) s_sup[h] = 0;
+        }
         __syncthreads();
         for (uint64_t r = ra + wave; r < rb; r += 4) {
             const uint64_t e0 = entry_begin[r];
@@ -1109,17 +1119,25 @@ __global__ __launch_bounds__(256) void hmm_support_kernel(const unsigned long lo
             }
         }
         __syncthreads();
-        if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
+        if (E::kMaxHap <= 256u) {
+            if (threadIdx.x < n_hap && s_sup[threadIdx.x] != 0) atomicAdd(&support[(size_t)w * n_hap + threadIdx.x], s_sup[threadIdx.x]);
+        } else {
+            for (uint32_t h = threadIdx.x; h < n_hap; h += 256u)
+                if (s_sup[h] != 0) atomicAdd(&support[(size_t)w * n_hap + h], s_sup[h]);
+        }
         __syncthreads();
         ra = rb;
     }
 }
 
 namespace {
-// the run-time form and word count of the entries as the compile-time reader: launch(reader) for one of the four
-template <class Launch>
+// the run-time form and word count of the entries as the compile-time reader: launch(reader) for one of the five.  W = 8 is taken by the
+// launchers that say so (WITH8: a diploid sample's support, emissions by places with their fixes, tallies); a genotype list per window is not
+template <bool WITH8 = false, class Launch>
 hipError_t hmm_with_entries(const HmmEntries& ent, Launch&& launch)
 {
+    if constexpr (WITH8)
+        if (ent.W == 8) return launch(HmmWideEntries<8>{});
     switch (ent.W) {
         case 0: return launch(HmmPackedEntries{});
         case 1: return launch(HmmWideEntries<1>{});
@@ -1155,7 +1173,7 @@ hipError_t launch_hmm_emissions(const HmmEmitParams& P, uint64_t n_rows, hipStre
     if (n_rows == 0) return hipSuccess;
     if (P.ploidy < 2 || P.ploidy > 8 || !hmm_entries_fit(P.ent, P.bl8)) return hipErrorInvalidValue;
     if (P.row_win && (!P.win_used || !P.win_top_mask || !P.alive)) return hipErrorInvalidValue;
-    return hmm_with_entries(P.ent, [&](auto ent) {
+    return hmm_with_entries<true>(P.ent, [&](auto ent) {
         using E = decltype(ent);
         const dim3 grid((uint32_t)n_rows), block(128);
         if constexpr (E::kDiploidOnly) {
@@ -1192,8 +1210,8 @@ hipError_t launch_hmm_support(const HmmEntries& ent, const uint8_t* cov, const u
                               const uint32_t* row_win, uint64_t n_rows, uint32_t n_hap, uint32_t* support, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    if (n_hap < 1 || n_hap > (ent.W ? 64u * ent.W - 1u : 48u) || n_hap > 255u) return hipErrorInvalidValue;
-    return hmm_with_entries(ent, [&](auto e) {
+    if (n_hap < 1 || n_hap > (ent.W ? 64u * ent.W - 1u : 48u) || (ent.W <= 4 && n_hap > 255u)) return hipErrorInvalidValue;
+    return hmm_with_entries<true>(ent, [&](auto e) {
         hipLaunchKernelGGL(hmm_support_kernel<decltype(e)>, dim3((uint32_t)((n_rows + kSupportRows - 1) / kSupportRows)), dim3(256), 0, st, ent.words, cov, alive,
                            entry_begin, entry_count, row_win, n_rows, n_hap, support, ent.f);
         return hipGetLastError();
@@ -1205,7 +1223,7 @@ hipError_t launch_hmm_tally_select(const HmmEntries& ent, const uint8_t* cov, co
                                    uint32_t* out, uint8_t* uniq, hipStream_t st)
 {
     if (n_rows == 0) return hipSuccess;
-    return hmm_with_entries(ent, [&](auto e) {
+    return hmm_with_entries<true>(ent, [&](auto e) {
         hipLaunchKernelGGL((hmm_tally_kernel<decltype(e), true>), dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, st, ent.words, cov, alive, entry_begin,
                            entry_count, row_win, winner, pos_ab, win_used, n_gt, 0u, 0ull, n_rows, out, uniq, ent.f);
         return hipGetLastError();

@@ -299,7 +299,9 @@ hipError_t launch_hmm_posterior(const HmmPostParams& P, uint64_t n_rows, hipStre
 // The node-list entries in either storage form (the kernels read them through one reader per form, vgmi_hmm.hip).  Packed: `words` holds
 // one word per entry, multiplicity << 8 | haplotype bits << 16 (the low byte is not used, up to six bytes of bits), f is null and W is 0.
 // Wide, panels of 48 to 254 haplotypes: f[e] is the multiplicity byte and words[e * W + i] the bit vector in W = 1, 2 or 4 64-bit words,
-// little-endian, zero-padded.  Every mask over haplotype ids that goes with wide entries is W words (one word with packed ones).
+// little-endian, zero-padded; W = 8 for 255 to 511 haplotypes (a diploid sample's support, emissions by places and tallies only), where a
+// window's drawn haplotypes (win_used) are 16-bit ids.  Every mask over haplotype ids that goes with wide entries is W words (one word
+// with packed ones).
 // (`words` stands last: it is the packed kernels' first argument, and their argument blocks keep their shape behind it.)
 struct HmmEntries {
     const uint8_t* f;
@@ -339,7 +341,7 @@ struct HmmEmitParams {
     // pairs only); `alive` says which entries are still in their node's list, and an alive entry no selected haplotype carries is marked
     // dead there -- the forward pass's prune (src/genotype.cpp:673-686, 815-818)
     const uint32_t* row_win;
-    const uint8_t* win_used;
+    const uint8_t* win_used;            // (16 ids per window: bytes, or 16-bit ids with entries of eight words)
     const unsigned long long* win_top_mask;
     uint8_t* alive;
 };

@@ -114,6 +114,13 @@ def load_library():
         "vgmi_hmm_emissions_select_wide": (i32, [vp, u32, u32, vp, vp, u32, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
                                                  vp, vp, C.POINTER(vp)]),
         "vgmi_hmm_tallies_select_wide": (i32, [vp, u32, C.c_uint64, vp, vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+        "vgmi_hmm_entries_upload_wide16": (i32, [vp, vp, vp, sz, u32]),
+        "vgmi_hmm_entries_reserve_wide16": (i32, [vp, sz, u32]),
+        "vgmi_hmm_entries_fill_wide16": (i32, [vp, sz, sz, vp, vp]),
+        "vgmi_hmm_support_wide16": (i32, [vp, u32, u32, u32, C.c_uint64, vp, vp, vp, vp]),
+        "vgmi_hmm_emissions_select_wide16": (i32, [vp, u32, u32, vp, vp, u32, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
+                                                   vp, vp, C.POINTER(vp)]),
+        "vgmi_hmm_tallies_select_wide16": (i32, [vp, u32, C.c_uint64, vp, vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
         "vgmi_hmm_emissions_select_ploidy_wide": (i32, [vp, u32, u32, u32, vp, vp, vp, u32, C.c_float, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp,
                                                         vp, vp, C.POINTER(vp)]),
         "vgmi_hmm_part_fix_rows_ploidy_wide": (i32, [vp, C.c_uint64, vp, vp, vp, vp]),
@@ -808,52 +815,59 @@ class Context:
                                                    _ptr(pos_b), win_used.shape[1], win_used.shape[0], _ptr(win_used), _ptr(out), _ptr(uniq)))
         return out[:n_rows], uniq[:n_rows]
 
-    # ---- ... over a panel of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry is a multiplicity byte and bit_len bytes of haplotype bits
-    def hmm_entries_upload_wide(self, f, bits, bit_len, cov_node=None, alive=None):
+    # ---- ... over a panel of 48 to 254 haplotypes (vgmi_hmm_*_wide): an entry is a multiplicity byte and bit_len bytes of haplotype bits;
+    # of 255 to 511 haplotypes (vgmi_hmm_*_wide16): 33 to 64 bytes, eight words per entry, win_used as 16-bit ids.  One body per call, the
+    # family by `ids16`.
+    def _wide_fn(self, name, ids16):
+        return getattr(self._l, name + ("_wide16" if ids16 else "_wide"))
+
+    def hmm_entries_upload_wide(self, f, bits, bit_len, cov_node=None, alive=None, ids16=False):
         """vgmi_hmm_entries_upload_wide (every entry alive again), then optionally _sample_upload and _alive_upload.  bits: (n_entries,
         bit_len) uint8, the entries' bit vectors as they stand in the graph."""
         f = np.ascontiguousarray(f, dtype=np.uint8)
         bits = np.ascontiguousarray(bits, dtype=np.uint8)
-        assert bits.size == f.size * bit_len or not 1 <= bit_len <= 32
-        self._chk(self._l.vgmi_hmm_entries_upload_wide(self._h, _ptr(f), _ptr(bits), f.size, bit_len))
+        lo, hi = (33, 64) if ids16 else (1, 32)
+        assert bits.size == f.size * bit_len or not lo <= bit_len <= hi
+        self._chk(self._wide_fn("vgmi_hmm_entries_upload", ids16)(self._h, _ptr(f), _ptr(bits), f.size, bit_len))
         self._hmm_n_entries = f.size
         if cov_node is not None:
             self.hmm_sample_upload(cov_node)
         if alive is not None:
             self.hmm_alive_upload(alive)
 
-    def hmm_support_wide(self, bit_len, n_hap, n_windows, entry_begin, entry_count, row_win):
+    def hmm_support_wide(self, bit_len, n_hap, n_windows, entry_begin, entry_count, row_win, ids16=False):
         """vgmi_hmm_support_wide: (n_windows, n_hap) uint32 sums over the alive entries of every window's rows."""
         entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
         entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
         row_win = np.ascontiguousarray(row_win, dtype=np.uint32)
         out = np.full((n_windows, max(n_hap, 1)), 0xDEADBEEF, dtype=np.uint32)
-        self._chk(self._l.vgmi_hmm_support_wide(self._h, bit_len, n_hap, n_windows, entry_begin.size, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win),
-                                                _ptr(out)))
+        self._chk(self._wide_fn("vgmi_hmm_support", ids16)(self._h, bit_len, n_hap, n_windows, entry_begin.size, _ptr(entry_begin), _ptr(entry_count),
+                                                           _ptr(row_win), _ptr(out)))
         return out
 
     def hmm_emissions_select_wide(self, pos_a, pos_b, win_used, win_top_mask, bit_len, ave, lower, upper, tables, entry_begin, entry_count, row_win, gt0,
-                                  fixes=None):
+                                  fixes=None, ids16=False):
         """vgmi_hmm_emissions_select_wide (+ _part_fix_rows) + _part_fetch: hmm_emissions_select with win_top_mask (n_windows, W) words."""
         pos_a = np.ascontiguousarray(pos_a, dtype=np.uint8)
         pos_b = np.ascontiguousarray(pos_b, dtype=np.uint8)
-        win_used = np.ascontiguousarray(win_used, dtype=np.uint8)
+        win_used = np.ascontiguousarray(win_used, dtype=np.uint16 if ids16 else np.uint8)
         win_top_mask = np.ascontiguousarray(win_top_mask, dtype=np.uint64)
         tables = np.ascontiguousarray(tables, dtype=np.longdouble)
         entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
         entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
         row_win = np.ascontiguousarray(row_win, dtype=np.uint32)
         gt0 = np.ascontiguousarray(gt0, dtype=np.uint16)
-        words = 1 if bit_len <= 8 else 2 if bit_len <= 16 else 4
-        assert tables.size == 768 and win_used.ndim == 2 and (win_top_mask.size == win_used.shape[0] * words or not 1 <= bit_len <= 32)
+        words = 8 if ids16 else 1 if bit_len <= 8 else 2 if bit_len <= 16 else 4
+        lo, hi = (33, 64) if ids16 else (1, 32)
+        assert tables.size == 768 and win_used.ndim == 2 and (win_top_mask.size == win_used.shape[0] * words or not lo <= bit_len <= hi)
         n_rows, n_gt = entry_begin.size, pos_a.size
         n_kept = np.zeros(max(n_rows, 1), dtype=np.uint32)
         flags = np.zeros(max(n_rows, 1), dtype=np.uint8)
         part = C.c_void_p()
-        self._chk(self._l.vgmi_hmm_emissions_select_wide(self._h, n_gt, win_used.shape[1], _ptr(pos_a), _ptr(pos_b), win_used.shape[0], _ptr(win_used),
-                                                          _ptr(win_top_mask), bit_len, float(ave), float(lower), float(upper), _ptr(tables), n_rows,
-                                                          _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(gt0), _ptr(n_kept), _ptr(flags),
-                                                          C.byref(part)))
+        self._chk(self._wide_fn("vgmi_hmm_emissions_select", ids16)(self._h, n_gt, win_used.shape[1], _ptr(pos_a), _ptr(pos_b), win_used.shape[0],
+                                                                     _ptr(win_used), _ptr(win_top_mask), bit_len, float(ave), float(lower), float(upper),
+                                                                     _ptr(tables), n_rows, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(gt0),
+                                                                     _ptr(n_kept), _ptr(flags), C.byref(part)))
         try:
             if fixes is not None:
                 f_rows, f_off, f_j, f_m = (np.ascontiguousarray(a, dtype=t) for a, t in zip(fixes, (np.uint64, np.uint32, np.uint32, np.uint16)))
@@ -864,7 +878,7 @@ class Context:
             self._l.vgmi_hmm_part_free(part)
         return obs, n_kept[:n_rows], flags[:n_rows]
 
-    def hmm_tallies_select_wide(self, bit_len, entry_begin, entry_count, row_win, winner, pos_a, pos_b, win_used):
+    def hmm_tallies_select_wide(self, bit_len, entry_begin, entry_count, row_win, winner, pos_a, pos_b, win_used, ids16=False):
         """vgmi_hmm_tallies_select_wide: returns (out (rows, 4) uint32, unique (rows,) uint8) as hmm_tallies_select does."""
         entry_begin = np.ascontiguousarray(entry_begin, dtype=np.uint64)
         entry_count = np.ascontiguousarray(entry_count, dtype=np.uint32)
@@ -872,13 +886,33 @@ class Context:
         winner = np.ascontiguousarray(winner, dtype=np.uint32)
         pos_a = np.ascontiguousarray(pos_a, dtype=np.uint8)
         pos_b = np.ascontiguousarray(pos_b, dtype=np.uint8)
-        win_used = np.ascontiguousarray(win_used, dtype=np.uint8)
+        win_used = np.ascontiguousarray(win_used, dtype=np.uint16 if ids16 else np.uint8)
         n_rows = entry_begin.size
         out = np.full((max(n_rows, 1), 4), 0xDEADBEEF, dtype=np.uint32)
         uniq = np.full(max(n_rows, 1), 0xEE, dtype=np.uint8)
-        self._chk(self._l.vgmi_hmm_tallies_select_wide(self._h, bit_len, n_rows, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(winner), pos_a.size,
-                                                        _ptr(pos_a), _ptr(pos_b), win_used.shape[1], win_used.shape[0], _ptr(win_used), _ptr(out), _ptr(uniq)))
+        self._chk(self._wide_fn("vgmi_hmm_tallies_select", ids16)(self._h, bit_len, n_rows, _ptr(entry_begin), _ptr(entry_count), _ptr(row_win), _ptr(winner),
+                                                                   pos_a.size, _ptr(pos_a), _ptr(pos_b), win_used.shape[1], win_used.shape[0], _ptr(win_used),
+                                                                   _ptr(out), _ptr(uniq)))
         return out[:n_rows], uniq[:n_rows]
+
+    # the _wide16 calls under their own names (33 to 64 bytes of haplotype bits, ids up to 510)
+    def hmm_entries_upload_wide16(self, f, bits, bit_len, cov_node=None, alive=None):
+        """vgmi_hmm_entries_upload_wide16: hmm_entries_upload_wide for 33 to 64 bytes of haplotype bits."""
+        self.hmm_entries_upload_wide(f, bits, bit_len, cov_node, alive, ids16=True)
+
+    def hmm_support_wide16(self, bit_len, n_hap, n_windows, entry_begin, entry_count, row_win):
+        """vgmi_hmm_support_wide16: n_hap up to 8 * bit_len - 1, at most 511."""
+        return self.hmm_support_wide(bit_len, n_hap, n_windows, entry_begin, entry_count, row_win, ids16=True)
+
+    def hmm_emissions_select_wide16(self, pos_a, pos_b, win_used, win_top_mask, bit_len, ave, lower, upper, tables, entry_begin, entry_count, row_win, gt0,
+                                    fixes=None):
+        """vgmi_hmm_emissions_select_wide16 (+ _part_fix_rows) + _part_fetch: win_used holds 16-bit ids, win_top_mask (n_windows, 8) words."""
+        return self.hmm_emissions_select_wide(pos_a, pos_b, win_used, win_top_mask, bit_len, ave, lower, upper, tables, entry_begin, entry_count, row_win, gt0,
+                                              fixes, ids16=True)
+
+    def hmm_tallies_select_wide16(self, bit_len, entry_begin, entry_count, row_win, winner, pos_a, pos_b, win_used):
+        """vgmi_hmm_tallies_select_wide16: win_used holds 16-bit ids."""
+        return self.hmm_tallies_select_wide(bit_len, entry_begin, entry_count, row_win, winner, pos_a, pos_b, win_used, ids16=True)
 
     def hmm_emissions_select_ploidy_wide(self, ploidy, win_n_gt, win_haps, win_top_mask, bit_len, ave, lower, upper, tables, entry_begin, entry_count,
                                          row_win, gt0, fixes=None):
