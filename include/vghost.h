@@ -88,6 +88,14 @@ int64_t vgh_bam_read_all(const char *path, uint32_t decode_threads, char **block
  * Like the two entries above, an entry for tests of the readers: the three share one loop, this one with the bound. */
 int64_t vgh_reads_read_all_q(const char *path, uint32_t decode_threads, uint32_t min_base_quality, char **block_out, size_t *n_bytes_out,
                              uint64_t *read_base, uint64_t *masked_bases);
+/* The same with subsampling (the rule of vgmi_fastq_set_subsample; fraction 1 = off): the file's reads are numbered first_number,
+ * first_number + 1, ... in file order (FASTA/Q: the records; BAM: the records that pass the read filter) and the block holds the
+ * kept ones only; *read_base and *masked_bases are theirs.  *next_number (may be NULL) = first_number + the reads numbered.  Returns
+ * the number of kept reads.  VGMI_E_INVALID for a fraction that is NaN, <= 0 or > 1.  first_number > 0 is the host reader taking a
+ * file over from the device: reading a whole file from number n gives what a reader that starts n reads into it would. */
+int64_t vgh_reads_read_all_s(const char *path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, char **block_out, size_t *n_bytes_out, uint64_t *read_base, uint64_t *masked_bases,
+                             uint64_t *next_number);
 /* What the device path of vgh_sample_count makes of an input file, from its first bytes (no device involved): kind = "plain" |
  * "gzip" | "bgzf"; first_byte = the first byte of its text (-1: it has none); bam = block gzip whose text starts with "BAM\1";
  * fasta = the text starts with '>' and goes to the device's FASTA parser (VGH_DEVICE_FASTA=0: never).  Any pointer may be NULL. */
@@ -127,6 +135,15 @@ int vgh_sample_count_q(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fas
                        uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
                        uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
                        uint64_t *masked_bases);
+/* The same with subsampling as well (genotype --subsample F --subsample-seed S): read i of every file -- numbered per file, in file
+ * order -- is kept iff the rule of vgmi_fastq_set_subsample says so, on the device and, from the device's number on, wherever the
+ * host reader serves; fraction 1 is off, which is vgh_sample_count_q.  A dropped read is not a read: read_base, n_reads and the depth
+ * statistics are those of the kept reads.  *reads_seen, *reads_kept (may be NULL) = the files' reads and how many were counted;
+ * *masked_bases as above, of the kept reads.  VGMI_E_INVALID for a fraction that is NaN, <= 0 or > 1. */
+int vgh_sample_count_s(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fastq_paths, size_t n_files,
+                       uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
+                       uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
+                       double fraction, uint64_t seed, uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases);
 
 /* Coverage statistics alone (Varigraph::kmer_read / cal_ave_cov_kmer): hist = masked coverage histogram
  * (vgmi_counts_finish).  Fills read_depth, hap_kmer_coverage, max_coverage, hom_coverage of *stats; returns

@@ -270,6 +270,22 @@ int vgmi_fastq_close(vgmi_fastq *fq, uint64_t *n_records, uint64_t *n_bases, uin
 int vgmi_fastq_set_min_quality(vgmi_fastq *fq, uint32_t q);
 /* Bases masked so far in the records the device has accepted (waits for the stream).  Valid until vgmi_fastq_close. */
 int vgmi_fastq_masked_bases(vgmi_fastq *fq, uint64_t *n);
+/* Subsampling: keep a seeded fraction of the stream's reads (1.0 = off, the default; the stream is then the one that never called
+ * this).  The reads are numbered i = 0, 1, 2, ... in stream order -- FASTQ and FASTA: the records; BAM: the records that pass the read
+ * filter (flag & 0x900 == 0 and l_seq > 0; a record the filter drops has no number, and the mates of an interleaved BAM have
+ * different numbers) -- and read i is kept iff z(i, seed) < T, all arithmetic mod 2^64:
+ *   T = (uint64_t)(fraction * 2^64)
+ *   x = (i + 1) * 0x9E3779B97F4A7C15 + seed;  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;
+ *   z = x ^ (x >> 31)
+ * so the kept set depends on the stream's content, the fraction and the seed alone, and two files of equal record count keep the
+ * same numbers under one seed.  A dropped read is not a read: nothing of it reaches the read block, n_records, n_bases or (with a
+ * minimum base quality, in either order of the two setters) the masked bases; consumed_bytes stays the stream's bytes.
+ * Before the stream's first commit only: VGMI_E_STATE afterwards, VGMI_E_INVALID for a fraction that is NaN, <= 0 or > 1; the
+ * stream serves on after either, and the last value set holds. */
+int vgmi_fastq_set_subsample(vgmi_fastq *fq, double fraction, uint64_t seed);
+/* Reads numbered so far in the records the device has accepted (*seen: the number the host reader goes on with) and how many of them
+ * were kept (*kept: n_records); waits for the stream.  Without subsampling both are n_records.  Valid until vgmi_fastq_close. */
+int vgmi_fastq_subsample_stats(vgmi_fastq *fq, uint64_t *seen, uint64_t *kept);
 
 /* K1 alone: the key every position of a read block emits, for emitter parity tests.
  * keys_out[i] = key of the k-mer ENDING at byte i, or UINT64_MAX when the reference emits nothing

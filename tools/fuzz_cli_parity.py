@@ -2,14 +2,17 @@
 """Drawn end-to-end cases through both CLIs (the unmodified reference, oracle/_ref/varigraph_det, and varigraph-mi) on one GPU box:
 genome size, variant mix, cohort size and ploidy, k, construct mode, reads per sample and every genotype option are drawn from a seed;
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
-  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy]
+  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample]
 --max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from.
 --max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100, 127, 130, 160 and 255 diploid
 VCF samples, as far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 511 haplotypes, 7 to 64 bytes of haplotype bits
 per k-mer (N = 127 draws what it drew before the last three were added; a seed's case depends on N, as it always has).
 --only-wide-ploidy runs, of the seeds given, only those whose draw is a polyploid sample (ploidy 3 and more) over a cohort of 49 or more
 haplotypes (DESIGN_INGEST_HMM 4.18; with VGH_HMM_WIDE_PLOIDY_DEVICE=1 in the environment the device path of such samples); the others are
-passed over before anything is built.  Every seed keeps its case."""
+passed over before anything is built.  Every seed keeps its case.
+--subsample (off by default: every seed draws the case it always drew) gives half of the cases a fraction and a seed for `genotype --subsample`,
+drawn from a generator of their own behind the case's; varigraph-mi then reads the case's files with the option and the reference the
+filtered files this script writes with the Python model of the rule (tests/subsample_cases.py): the same VCFs, or both refuse."""
 import gzip, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -65,7 +68,19 @@ def dress(path, rng):
 MAX_PLOIDY = 4      # --max-ploidy N: ploidy 5 .. N joins both draws (DESIGN_INGEST_HMM 4.15: the device's HMM for samples of ploidy 5 .. 8)
 MAX_VCF_SAMPLES = 7      # --max-vcf-samples N: diploid cohorts of up to N samples (DESIGN_INGEST_HMM 4.16, 4.21: the device's HMM over panels of 48 to 511 haplotypes)
 ONLY_WIDE_PLOIDY = False      # --only-wide-ploidy: seeds whose draw is anything else are passed over
+SUBSAMPLE = False      # --subsample: a drawn case may get a fraction and a seed (DESIGN_INGEST_HMM 4.22)
 FORCE = {}      # --k K / --genome G on the command line: the drawn value replaced (round 6: campaigns of k = 28 over graphs on either side of 65 536 k-mers)
+
+
+def filtered(path, fraction, sub_seed):
+    """the reads of a FASTQ file (plain, gzip of any number of members, block gzip) that the rule keeps, as a plain four-line file"""
+    import subsample_cases
+    raw = open(path, "rb").read()
+    text = gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw
+    if not text.endswith(b"\n"): text += b"\n"
+    out = path + ".kept.fq"
+    open(out, "wb").write(subsample_cases.filtered_fastq_text(text, fraction, sub_seed)[0])
+    return out
 
 
 def case(seed):
@@ -111,17 +126,24 @@ def case(seed):
         if (rcs["native"] == 0) != (rcs["cpu"] == 0): return "CONSTRUCT STATUS DIFFERS " + str(rcs), desc
         if rcs["cpu"] != 0: return "both refuse construct", desc
         if open(graphs["native"], "rb").read() != open(graphs["cpu"], "rb").read(): return "GRAPH DIFFERS", desc
-        cfg = ""
+        cfg, cfg_kept, sub = "", "", None
+        if SUBSAMPLE:      # a generator of its own: the case's draws stay what they were
+            srng = np.random.default_rng([int(seed), 0x5AB5])
+            if srng.random() < 0.5:
+                sub = ([0.5, 0.25, 0.9, 0.05, 0.999][int(srng.integers(0, 5))], int(srng.integers(0, 2 ** 63)) * 2 + int(srng.integers(0, 2)))
+                desc += f", --subsample {sub[0]} --subsample-seed {sub[1]}"
         for i in range(n_reads_samples):
             who = int(rng.integers(0, n_samples))
             haps = synth.sample_haplotypes(ref, variants, gts, who, vploidy)
             fq = tc._write_fastq(os.path.join(work, f"s{i}"), haps, pairs, seed=int(seed) * 10 + i)
             fq = [dress(f, rng) for f in fq]
             cfg += f"ind{i} " + " ".join(fq) + "\n"
+            if sub: cfg_kept += f"ind{i} " + " ".join(filtered(f, *sub) for f in fq) + "\n"
         outs, codes = {}, {}
         for name, exe, more in (("native", tc.CLI, ["--gpu", "0"]), ("cpu", tc.REF, [])):
             d = os.path.join(work, name); os.makedirs(d)
-            open(os.path.join(d, "samples.cfg"), "w").write(cfg)
+            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if sub and name == "cpu" else cfg)
+            if sub and name == "native": more = more + ["--subsample", repr(sub[0]), "--subsample-seed", str(sub[1])]
             try:
                 r = subprocess.run([exe, "genotype", "--load-graph", graphs["cpu"], "-s", "samples.cfg", "-t", "6"] + gopts + more, cwd=d, capture_output=True, text=True, env=tc.ENV, timeout=150)
             except subprocess.TimeoutExpired:
@@ -150,6 +172,7 @@ if __name__ == "__main__":
         if a == "--max-ploidy": MAX_PLOIDY = int(sys.argv[i + 1])
         if a == "--max-vcf-samples": MAX_VCF_SAMPLES = int(sys.argv[i + 1])
         if a == "--only-wide-ploidy": ONLY_WIDE_PLOIDY = True
+        if a == "--subsample": SUBSAMPLE = True
     bad = passed_over = 0
     for s in range(first, first + n):
         t0 = time.time()

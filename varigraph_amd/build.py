@@ -121,7 +121,8 @@ def build_host(force=False, verbose=False):
     srcs = sorted(os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".cpp") and not f.startswith("main_"))
     if not srcs:
         return None
-    deps = srcs + [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".hpp") or f.endswith(".h")] + [
+    deps = srcs + [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".hpp") or f.endswith(".h")] + sorted(
+        os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
         os.path.join(ROOT, "include", "vgmi.h"), os.path.join(ROOT, "include", "vghost.h")]
     deps = [d for d in deps if os.path.exists(d)]
     if not force and not _newer(HOSTLIB, deps + [LIB]):

@@ -127,6 +127,7 @@ long BamReader::next()
         pos_ += 4 + (size_t)bs;
         off_ += 4 + (uint64_t)bs;
         if ((flag & 0x900u) || l_seq == 0) continue;
+        if (!rule_.keep(number_++)) continue;
         const unsigned char* s = r + 36 + l_rn + 4 * (size_t)n_cig;
         seq_.resize(l_seq);
         for (uint32_t i = 0; i < l_seq; ++i) seq_[i] = nt16[(s[i >> 1] >> ((~i & 1) << 2)) & 15];

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "byte_source.hpp"
+#include "../vgmi_subsample.h"
 
 namespace vgh {
 
@@ -26,6 +27,15 @@ public:
 
     // >= 0: sequence length (seq() holds it); -1: end of the data
     long next();
+    // Subsampling (vgmi_subsample.h): the reads -- the records that pass the filter above; the others have no number -- that next() comes
+    // to from here on are numbered first_number, first_number + 1, ... and the ones the rule drops are passed over undecoded.
+    // first_number: 0 at the start of a file, the device's n_seen where this reader takes a stream over.
+    void subsample(const SubsampleRule& rule, uint64_t first_number)
+    {
+        rule_ = rule;
+        number_ = first_number;
+    }
+    uint64_t next_number() const { return number_; }
     const std::string& seq() const { return seq_; }
     const std::string& qual() const { return qual_; }   // the record's QUAL bytes as stored (l_seq of them; QUAL[0] == 0xff: none stored)
     // Minimum base quality q (the rule of vgmi_fastq_set_min_quality): base i of seq() becomes 'N' where QUAL[i] < q, in record order;
@@ -44,6 +54,8 @@ private:
     uint64_t header_bytes_ = 0;
     int32_t n_ref_ = 0;
     std::string seq_, qual_;
+    SubsampleRule rule_;
+    uint64_t number_ = 0;
 };
 
 // the bytes of `path` as ByteSource::open delivers them; is_bam: block gzip whose text starts with "BAM\1" (decided from content)

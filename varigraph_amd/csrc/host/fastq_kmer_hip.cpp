@@ -32,6 +32,25 @@ struct Block {
     uint64_t masked = 0;
 };
 
+// what a file's readers apply besides parsing: the minimum base quality (0: off) and the subsampling rule (fraction 1: off)
+struct ReadOpts {
+    uint32_t min_q = 0;
+    SubsampleRule sub;
+};
+
+struct DeviceFileResult {
+    uint64_t n_reads = 0, read_base = 0, masked = 0;
+    uint64_t seen = 0;      // the file's reads, numbered by the device and the host reader together; n_reads of them were kept
+};
+
+// VGH_TIMING: what subsampling did to one file (nothing is printed without the option)
+void report_subsample(const std::string& path, uint64_t seen, uint64_t kept, const SubsampleRule& sub)
+{
+    if (sub.on && std::getenv("VGH_TIMING"))
+        std::fprintf(stderr, "[varigraph-mi] '%s': %llu of %llu reads kept (--subsample %g, seed %llu)\n", path.c_str(), (unsigned long long)kept,
+                     (unsigned long long)seen, sub.fraction, (unsigned long long)sub.seed);
+}
+
 // VGH_TIMING: what the minimum base quality did to one file (nothing is printed without the option)
 void report_masked(const std::string& path, uint64_t masked, uint32_t min_q)
 {
@@ -46,11 +65,13 @@ struct Channel {  // parser threads -> submitting thread
     std::vector<std::unique_ptr<Block>> free_list;
     size_t producers = 0;
     std::string error;
+    uint64_t seen = 0;      // reads the finished parsers numbered (all of them without subsampling)
 };
 
-void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads, uint32_t min_q)
+void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads, const ReadOpts o)
 {
-    uint64_t file_masked = 0;
+    const uint32_t min_q = o.min_q;
+    uint64_t file_masked = 0, file_reads = 0, file_seen = 0;
     auto grab = [&]() {
         std::unique_lock<std::mutex> lk(ch.mu);
         ch.cv_free.wait(lk, [&] { return !ch.free_list.empty(); });
@@ -69,6 +90,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
     };
     auto run = [&](auto& rd) {
         std::unique_ptr<Block> cur = grab();
+        if (o.sub.on) rd.subsample(o.sub, 0);      // the whole file through this reader: its reads are numbered from 0
         while (rd.next() >= 0) {  // stops at EOF (-1) and at the first truncated record (-2)
             const uint64_t masked = min_q ? rd.mask_below(min_q) : 0;
             const std::string& s = rd.seq();
@@ -86,7 +108,9 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
             cur->read_base += s.size();
             cur->masked += masked;
             file_masked += masked;
+            ++file_reads;
         }
+        file_seen = o.sub.on ? rd.next_number() : file_reads;
         if (cur->n_reads) push(std::move(cur));
         else {
             std::lock_guard<std::mutex> lk(ch.mu);
@@ -104,6 +128,9 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
             run(rd);
         }
         report_masked(path, file_masked, min_q);
+        report_subsample(path, file_seen, file_reads, o.sub);
+        std::lock_guard<std::mutex> lk(ch.mu);
+        ch.seen += file_seen;
     } catch (const std::exception& e) {
         std::lock_guard<std::mutex> lk(ch.mu);
         if (ch.error.empty()) ch.error = e.what();
@@ -118,9 +145,11 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
 // records of `rd` (from a record boundary on; FastxReader or BamReader) through the host reader into read blocks and vgmi_reads_submit;
 // the context's host-block path is single-threaded, hence the mutex shared by the files of one sample
 template <class Reader>
-void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_bytes, std::mutex& submit_mu, uint32_t min_q, uint64_t& n_reads,
-              uint64_t& read_base, uint64_t& masked)
+void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_bytes, std::mutex& submit_mu, const ReadOpts& o, DeviceFileResult& res)
 {
+    const uint32_t min_q = o.min_q;
+    uint64_t &n_reads = res.n_reads, &read_base = res.read_base, &masked = res.masked;
+    if (o.sub.on) rd.subsample(o.sub, res.seen);      // the device's n_seen (0 where the device took nothing): one numbering per file
     std::vector<char> block;
     block.reserve(block_bytes + 1024);
     size_t in_block = 0;
@@ -144,6 +173,7 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
         read_base += s.size();
     }
     flush();
+    res.seen = o.sub.on ? rd.next_number() : n_reads;
 }
 
 // plain file: `threads` readers fill one pinned buffer side by side (a single read(2) stream moves 3-6 GB/s, the link
@@ -223,12 +253,9 @@ InputSniff sniff_input(const std::string& path)
 
 namespace {
 
-struct DeviceFileResult {
-    uint64_t n_reads = 0, read_base = 0, masked = 0;
-};
-
-DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t block_bytes, unsigned threads, std::mutex& submit_mu, uint32_t min_q)
+DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t block_bytes, unsigned threads, std::mutex& submit_mu, const ReadOpts& o)
 {
+    const uint32_t min_q = o.min_q;
     DeviceFileResult res;
     int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) throw std::runtime_error("'" + path + "': No such file or directory.");
@@ -245,10 +272,10 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         std::unique_ptr<ByteSource> src = open_sniffed(path, threads, is_bam);   // (a BAM pipe: recognised from its first decoded bytes)
         if (is_bam) {
             BamReader rd(std::move(src), path);
-            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
         } else {
             FastxReader rd(std::move(src));
-            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
         }
         return res;
     }
@@ -271,7 +298,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         bgzf = false;
         if (bam) {
             BamReader rd(ByteSource::open(path, threads), path);
-            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
             return res;
         }
     }
@@ -292,7 +319,12 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
         throw std::runtime_error(why);
     }
-    uint64_t n_rec = 0, n_bases = 0, consumed = 0;
+    if (o.sub.on && vgmi_fastq_set_subsample(fq, o.sub.fraction, o.sub.seed) != VGMI_OK) {
+        const std::string why = vgmi_last_error(ctx);
+        (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        throw std::runtime_error(why);
+    }
+    uint64_t n_rec = 0, n_bases = 0, consumed = 0, dev_seen = 0, dev_kept = 0;
     int stopped = 0;
     std::vector<char> tail(1u << 20);
     size_t tail_len = 0;
@@ -303,6 +335,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     auto close_stream = [&]() {
         if (bgzf && vgmi_fastq_bgzf_status(fq, &inflate_failed, &comp_good, nullptr) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         if (min_q && vgmi_fastq_masked_bases(fq, &res.masked) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+        if (o.sub.on && vgmi_fastq_subsample_stats(fq, &dev_seen, &dev_kept) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         closed = true;
         if (vgmi_fastq_close(fq, &n_rec, &n_bases, &consumed, &stopped, tail.data(), tail.size(), &tail_len) != VGMI_OK)
             throw std::runtime_error(vgmi_last_error(ctx));
@@ -415,6 +448,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     }
     res.n_reads = n_rec;
     res.read_base = n_bases;
+    res.seen = o.sub.on ? dev_seen : n_rec;      // where the host reader's numbering goes on
     if (std::getenv("VGH_TIMING"))      // (what tells a run served by the device-side reader from one the host reader served, at any k)
         std::fprintf(stderr, "[varigraph-mi] '%s': %llu reads from the device-side reader\n", path.c_str(), (unsigned long long)n_rec);
     // what the device did not take: the text after the last complete record (an unterminated last line, or nothing), or
@@ -426,18 +460,18 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         if (stopped || inflate_failed || comp_taken < file_size || tail_len) {
             BamReader rd(ByteSource::open(path, threads), path);
             rd.skip_to(consumed);
-            host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+            host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
         }
     } else if (stopped || gz_gave_up) {       // (the host decodes the file from its start and passes over the text the device has counted)
         FastxReader rd(ByteSource::skip(ByteSource::open(path, threads), consumed));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+        host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
     } else if (bgzf && (inflate_failed ? comp_good : comp_taken) < file_size) {
         const uint64_t at = inflate_failed ? comp_good : comp_taken;
         FastxReader rd(ByteSource::concat(ByteSource::from_memory(tail.data(), tail_len), ByteSource::open_at(path, at, threads)));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+        host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
     } else if (tail_len) {
         FastxReader rd(ByteSource::from_memory(tail.data(), tail_len));
-        host_leg(ctx, rd, path, block_bytes, submit_mu, min_q, res.n_reads, res.read_base, res.masked);
+        host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
     }
     return res;
 }
@@ -463,8 +497,27 @@ void FastqKmerHip::build_fastq_index()
     count_files(0, masked);
 }
 
+FastqKmerHipS::FastqKmerHipS(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads,
+                             uint32_t min_base_quality, double fraction, uint64_t seed, size_t block_bytes)
+    : FastqKmerHip(ctx, fastqFileNameVec, kmerLen, threads, block_bytes), min_q_(min_base_quality)
+{
+    if (min_q_ > 93) throw std::runtime_error("minimum base quality " + std::to_string(min_q_) + " is out of range (0..93, Phred+33)");
+    if (!subsample_fraction_valid(fraction))
+        throw std::runtime_error("subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)");
+    rule_ = SubsampleRule(fraction, seed);
+}
+
 void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
 {
+    uint64_t seen = 0;
+    count_files_sampled(min_q, SubsampleRule(), masked, seen);
+}
+
+void FastqKmerHip::count_files_sampled(const uint32_t min_q, const SubsampleRule& sub, uint64_t& masked, uint64_t& seen)
+{
+    ReadOpts o;
+    o.min_q = min_q;
+    o.sub = sub;
     if (files_.empty()) throw std::runtime_error("Parameter error: -f");  // src/fastq_kmer.cpp:42-45
     uint32_t k_tab = 0;
     if (vgmi_table_info(ctx_, nullptr, &k_tab, nullptr, nullptr) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx_));
@@ -473,6 +526,7 @@ void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
     mReadBase = 0;
     mReadNum = 0;
     masked = 0;
+    seen = 0;
 
     const char* force_host = std::getenv("VGH_HOST_PARSE");
     if (!(force_host && force_host[0] == '1')) {
@@ -488,12 +542,14 @@ void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
                 const size_t i = next.fetch_add(1);
                 if (i >= files_.size()) return;
                 try {
-                    const DeviceFileResult r = device_file(ctx_, files_[i], block_bytes_, io_threads, submit_mu, min_q);
+                    const DeviceFileResult r = device_file(ctx_, files_[i], block_bytes_, io_threads, submit_mu, o);
                     report_masked(files_[i], r.masked, min_q);
+                    report_subsample(files_[i], r.seen, r.n_reads, o.sub);
                     std::lock_guard<std::mutex> lk(res_mu);
                     mReadBase += r.read_base;
                     mReadNum += r.n_reads;
                     masked += r.masked;
+                    seen += r.seen;
                 } catch (const std::exception& e) {
                     std::lock_guard<std::mutex> lk(res_mu);
                     if (err.empty()) err = e.what();
@@ -524,7 +580,7 @@ void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
     auto start_more = [&]() {  // called with ch.mu held
         while (ch.producers < n_par && next_file < files_.size()) {
             ch.producers++;
-            workers.emplace_back(parse_file, files_[next_file++], std::ref(ch), block_bytes_, decode_threads, min_q);
+            workers.emplace_back(parse_file, files_[next_file++], std::ref(ch), block_bytes_, decode_threads, o);
         }
     };
     std::string err;
@@ -557,6 +613,7 @@ void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
     }
     for (auto& t : workers) t.join();
     if (!err.empty()) throw std::runtime_error(err);
+    seen = ch.seen;
 }
 
 void FastqKmerHip::fetch(uint8_t* cov, uint8_t* cov_node, uint64_t* hist256)

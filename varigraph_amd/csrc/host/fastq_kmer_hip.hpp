@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "../vgmi_subsample.h"
+
 struct vgmi_ctx;
 
 namespace vgh {
@@ -43,6 +45,8 @@ public:
 protected:
     // build_fastq_index with a minimum base quality (0: off); masked_bases gets the bases counted as 'N' for their quality
     void count_files(uint32_t min_base_quality, uint64_t& masked_bases);
+    // ... and with a subsampling rule (off: count_files); reads_seen gets the files' reads, of which mReadNum were kept and counted
+    void count_files_sampled(uint32_t min_base_quality, const SubsampleRule& sub, uint64_t& masked_bases, uint64_t& reads_seen);
 
 private:
     vgmi_ctx* ctx_;
@@ -71,6 +75,28 @@ public:
 
 private:
     uint32_t min_q_;
+};
+
+// FastqKmerHip with a minimum base quality and subsampling (genotype --subsample F --subsample-seed S; vgmi_subsample.h has the rule): a
+// seeded fraction of every file's reads is kept, on the device and -- from the device's number on -- wherever the host reader
+// serves, so a file counted partly by each gives one answer.  A dropped read is not a read: mReadBase and mReadNum are those of
+// the kept reads, which is what the depth statistics take.  Fraction 1 is off and counts what FastqKmerHipQ counts.  A class of
+// its own for FastqKmerHipQ's reason: FastqKmerHip keeps its constructor symbol and its size.
+class FastqKmerHipS : public FastqKmerHip {
+public:
+    uint64_t mMaskedBases = 0;  // bases of the kept reads counted as 'N' for their quality
+    uint64_t mReadsSeen = 0;    // the files' reads, kept or not (mReadNum: the kept ones)
+
+    // throws std::runtime_error for min_base_quality > 93 and for a fraction that is NaN, <= 0 or > 1
+    FastqKmerHipS(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads,
+                  uint32_t min_base_quality, double fraction, uint64_t seed = 11, size_t block_bytes = 32u << 20);
+
+    // build_fastq_index with the bound and the rule applied; fills mMaskedBases and mReadsSeen
+    void build_fastq_index_sampled() { count_files_sampled(min_q_, rule_, mMaskedBases, mReadsSeen); }
+
+private:
+    uint32_t min_q_;
+    SubsampleRule rule_;
 };
 
 // What the device path makes of an input file, decided from its first bytes alone (no device involved): the container by the

@@ -59,7 +59,15 @@ bool FastxReader::skip_line()
     }
 }
 
-long FastxReader::next()
+long FastxReader::next_sampled()
+{
+    for (;;) {
+        const long r = next_record();
+        if (r < 0 || rule_.keep(number_++)) return r;      // (a truncated record ends the file: it has no number)
+    }
+}
+
+long FastxReader::next_record()
 {
     int c;
     if (last_char_ == 0) {  // jump to the next header line

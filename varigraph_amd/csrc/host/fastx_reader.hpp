@@ -15,6 +15,7 @@
 #include <string>
 
 #include "byte_source.hpp"
+#include "../vgmi_subsample.h"
 
 namespace vgh {
 
@@ -27,7 +28,17 @@ public:
     FastxReader& operator=(const FastxReader&) = delete;
 
     // >= 0: sequence length (seq() holds it); -1: end of file; -2: truncated quality
-    long next();
+    long next() { return rule_.on ? next_sampled() : next_record(); }      // (without the rule: the reader of before, one call)
+    // Subsampling (vgmi_subsample.h): the records next() reads from here on are numbered first_number, first_number + 1, ... and the ones
+    // the rule drops are passed over -- next() returns the kept ones only.  first_number is the file number of the next record: 0 at
+    // the start of a file, the device's n_seen where this reader takes a stream over.  next_number(): the number the record after
+    // the last one read would get (with a rule that is on: without one nothing is numbered).
+    void subsample(const SubsampleRule& rule, uint64_t first_number)
+    {
+        rule_ = rule;
+        number_ = first_number;
+    }
+    uint64_t next_number() const { return number_; }
     const std::string& seq() const { return seq_; }
     const std::string& name() const { return name_; }  // up to the first whitespace of the header line
     const std::string& qual() const { return qual_; }  // the record's quality lines joined (empty for a FASTA record)
@@ -37,6 +48,8 @@ public:
     const char* source_kind() const { return src_->kind(); }
 
 private:
+    long next_record();   // next() without the rule
+    long next_sampled();  // ... and with it: the next record the rule keeps
     int getc();
     // append up to (not including) the next '\n' to s; returns false at EOF with nothing read
     bool get_line(std::string& s, bool append);
@@ -50,6 +63,8 @@ private:
     bool eof_ = false;
     int last_char_ = 0;
     std::string seq_, qual_, name_;
+    SubsampleRule rule_;
+    uint64_t number_ = 0;
 };
 
 }  // namespace vgh

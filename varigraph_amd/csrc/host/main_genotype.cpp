@@ -44,6 +44,8 @@ struct Options {
                                    // counting thread and one table replica per device
     int buffer_mib = 100;   // main.cu default
     bool procs = false;     // --procs: one PROCESS per device of --gpus, the table image handed on by one RCCL broadcast
+    double subsample = 1.0;             // --subsample: the fraction of every file's reads that is kept and counted (1: off); the ranks of --procs inherit both
+    unsigned long long subsample_seed = 11;   // --subsample-seed
     int min_base_quality = 0;   // --min-base-quality: bases of FASTQ / BAM reads below it are counted as N (0: off); the ranks of --procs inherit it
 };
 
@@ -71,6 +73,10 @@ void usage(const char* argv0)
               << "    --min-support   FLOAT  minimum site quality (GQ) [0]\n"
               << "    --use-depth            use the sequencing depth as the depth of homozygous k-mers\n"
               << "    --min-base-quality INT count a base of a FASTQ / BAM read whose quality (Phred+33) is below INT as N, 0-93 [0: off]\n"
+              << "    --subsample     FLOAT  keep this fraction of every file's reads, chosen by --subsample-seed and the read's number in its\n"
+              << "                           file alone: the files of a pair keep the same reads (the mates of an interleaved BAM have\n"
+              << "                           different numbers); the depth statistics are those of the kept reads, 0 < FLOAT <= 1 [1: off]\n"
+              << "    --subsample-seed INT   seed of --subsample, 0 to 2^64-1 [11]\n"
               << "    --gpu           INT    device ordinal [0]\n"
               << "    --gpus          LIST   several devices, e.g. 0,1,2,3: samples are counted on them in parallel\n"
               << "    --procs                one process per device of --gpus (samples dealt round robin, -t shared out); the table is\n"
@@ -108,6 +114,17 @@ unsigned long long opt_u64(const char* name, const char* v)
         return std::stoull(v);
     } catch (const std::exception&) {
         die(std::string("Parameter error: ") + name + ". '" + v + "' is not a non-negative integer.");
+    }
+}
+double opt_double(const char* name, const char* v)
+{
+    try {
+        size_t used = 0;
+        const double d = std::stod(v, &used);
+        if (v[used]) throw std::invalid_argument(v);
+        return d;
+    } catch (const std::exception&) {
+        die(std::string("Parameter error: ") + name + ". '" + v + "' is not a number.");
     }
 }
 float opt_float(const char* name, const char* v)
@@ -164,6 +181,7 @@ int main_genotype(int argc, char** argv)
         {"gpus", required_argument, 0, 9},         {"debug", no_argument, 0, 'D'},
         {"threads", required_argument, 0, 't'},    {"help", no_argument, 0, 'h'},
         {"procs", no_argument, 0, 10},             {"min-base-quality", required_argument, 0, 11},
+        {"subsample", required_argument, 0, 12},   {"subsample-seed", required_argument, 0, 13},
         {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -192,6 +210,8 @@ int main_genotype(int argc, char** argv)
         case 8: o.buffer_mib = opt_int("--buffer", optarg); break;
         case 10: o.procs = true; break;
         case 11: o.min_base_quality = opt_int("--min-base-quality", optarg); break;
+        case 12: o.subsample = opt_double("--subsample", optarg); break;
+        case 13: o.subsample_seed = opt_u64("--subsample-seed", optarg); break;
         case 't': o.hmm.threads = std::max(opt_int("-t", optarg), 1); break;
         case 'D': debug = true; break;
         default: usage(argv[0]); return 1;
@@ -214,6 +234,7 @@ int main_genotype(int argc, char** argv)
     if (o.hmm.transition != "fre" && o.hmm.transition != "rec") die("Parameter error: -m. The transition probability type must be either 'fre' or 'rec'.");
     if (o.buffer_mib < 1) die("Parameter error: --buffer. The buffer size must be at least 1 MiB.");
     if (o.min_base_quality < 0 || o.min_base_quality > 93) die("Parameter error: --min-base-quality. The provided value must be between 0 and 93 (inclusive).");
+    if (!(o.subsample > 0.0 && o.subsample <= 1.0)) die("Parameter error: --subsample. The provided value must be greater than 0 and at most 1.");
 
     const auto t0 = std::chrono::steady_clock::now();
     auto secs = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -626,6 +647,12 @@ int main_genotype(int argc, char** argv)
                 }
                 const auto& [name, files] = samples[s];
                 const double ts = secs();
+                if (o.subsample < 1.0) {
+                    vgh::FastqKmerHipS fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed);
+                    fk.build_fastq_index_sampled();
+                    counted(s, fk, dev_i, ts);
+                    continue;
+                }
                 vgh::FastqKmerHipQ fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality);
                 fk.build_fastq_index_masked();
                 counted(s, fk, dev_i, ts);

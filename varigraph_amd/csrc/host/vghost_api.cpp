@@ -28,8 +28,10 @@ namespace {
 // every record of `rd` (FastxReader or BamReader) as a '\n'-joined block in malloc'ed memory, bases below quality q masked (0: none);
 // the number of reads, or VGMI_E_NOMEM.  A sequence ends at its first NUL, read_base counts it whole (src/fastq_kmer.cpp:101 vs :105).
 template <class Reader>
-int64_t reads_block(Reader& rd, uint32_t q, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases)
+int64_t reads_block(Reader& rd, uint32_t q, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases,
+                    const vgh::SubsampleRule* sub = nullptr, uint64_t first_number = 0, uint64_t* next_number = nullptr)
 {
+    if (sub) rd.subsample(*sub, first_number);
     std::string block;
     int64_t n = 0;
     uint64_t rb = 0, masked = 0;
@@ -48,6 +50,7 @@ int64_t reads_block(Reader& rd, uint32_t q, char** block_out, size_t* n_bytes_ou
     *n_bytes_out = block.size();
     if (read_base) *read_base = rb;
     if (masked_bases) *masked_bases = masked;
+    if (next_number) *next_number = sub && sub->on ? rd.next_number() : first_number + (uint64_t)n;      // (off: every read is kept, nothing numbers them)
     return n;
 }
 }  // namespace
@@ -195,6 +198,35 @@ int64_t vgh_reads_read_all_q(const char* path, uint32_t decode_threads, uint32_t
     }
 }
 
+int64_t vgh_reads_read_all_s(const char* path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases,
+                             uint64_t* next_number)
+{
+    if (!path || !block_out || !n_bytes_out) return VGMI_E_INVALID;
+    if (min_base_quality > 93) {
+        g_err = "minimum base quality " + std::to_string(min_base_quality) + " is out of range (0..93, Phred+33)";
+        return VGMI_E_INVALID;
+    }
+    if (!vgh::subsample_fraction_valid(fraction)) {
+        g_err = "subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)";
+        return VGMI_E_INVALID;
+    }
+    try {
+        const vgh::SubsampleRule rule(fraction, seed);
+        bool is_bam = false;
+        std::unique_ptr<vgh::ByteSource> src = vgh::open_sniffed(path, decode_threads ? decode_threads : 1, is_bam);
+        if (is_bam) {
+            vgh::BamReader rd(std::move(src), path);
+            return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
+        }
+        vgh::FastxReader rd(std::move(src));
+        return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return VGMI_E_INVALID;
+    }
+}
+
 int vgh_sniff_input(const char* path, char kind[8], int* first_byte, int* bam, int* fasta)
 {
     if (!path) return VGMI_E_INVALID;
@@ -271,14 +303,27 @@ int vgh_sample_count_q(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fas
                        uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
                        vgh_sample_stats* stats, uint32_t min_base_quality, uint64_t* masked_bases)
 {
+    return vgh_sample_count_s(h, ctx, fastq_paths, n_files, threads, sample_ploidy, use_depth, cov_out, cov_node_out, hist_out, stats,
+                              min_base_quality, 1.0, 0, nullptr, nullptr, masked_bases);
+}
+
+int vgh_sample_count_s(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fastq_paths, size_t n_files, uint32_t threads,
+                       uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
+                       vgh_sample_stats* stats, uint32_t min_base_quality, double fraction, uint64_t seed, uint64_t* reads_seen,
+                       uint64_t* reads_kept, uint64_t* masked_bases)
+{
     if (!h || !ctx || (!fastq_paths && n_files)) return VGMI_E_INVALID;
     if (masked_bases) *masked_bases = 0;
+    if (reads_seen) *reads_seen = 0;
+    if (reads_kept) *reads_kept = 0;
     try {
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<std::string> files(fastq_paths, fastq_paths + n_files);
-        vgh::FastqKmerHipQ fk(ctx, files, h->g.k, threads, min_base_quality);
-        fk.build_fastq_index_masked();
+        vgh::FastqKmerHipS fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed);
+        fk.build_fastq_index_sampled();
         if (masked_bases) *masked_bases = fk.mMaskedBases;
+        if (reads_seen) *reads_seen = fk.mReadsSeen;
+        if (reads_kept) *reads_kept = fk.mReadNum;
         uint64_t hist[256];
         fk.fetch(cov_out, cov_node_out, hist);
         if (hist_out) memcpy(hist_out, hist, sizeof hist);

@@ -2,6 +2,8 @@
 // inflated by vgmi_inflate.hip, ordinary gzip by vgmi_gunzip.hip
 #include "vgmi_ctx.h"
 
+#include "vgmi_subsample.h"
+
 extern "C" {
 
 /* ---------------------------------------------------------------- device-side FASTQ parsing */
@@ -57,6 +59,11 @@ struct vgmi_fastq {
     // minimum base quality (vgmi_fastq_set_min_quality): 0 = off; fixed once bytes have been committed
     uint32_t min_quality = 0;
     bool committed = false;
+    // subsampling (vgmi_fastq_set_subsample): on == 0 = off; fixed once bytes have been committed.  d_fa_sub: the FASTA parser's extra
+    // scan scratch (FaBuffers::bsum_hdr), allocated by the first chunk of a FASTA stream that subsamples
+    SubParams sub{};
+    double sub_fraction = 1.0;
+    unsigned long long* d_fa_sub = nullptr;
 };
 
 namespace {
@@ -74,7 +81,7 @@ extern "C++" void vgapi::fastq_free(vgmi_fastq* f)
     }
     for (void* p : {(void*)f->d_packed, (void*)f->d_tile, (void*)f->d_nlpos, (void*)f->d_rec, (void*)f->d_off, (void*)f->d_bsum,
                     (void*)f->d_state, (void*)f->d_comp, (void*)f->d_members, (void*)f->d_status, (void*)f->d_crc, (void*)f->d_verdict,
-                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa, (void*)f->d_even})
+                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa, (void*)f->d_even, (void*)f->d_fa_sub})
         if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         if (f->h_members[i]) (void)hipHostFree(f->h_members[i]);
@@ -123,6 +130,8 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->fasta = false;
             r->min_quality = 0;
             r->committed = false;
+            r->sub = SubParams{};
+            r->sub_fraction = 1.0;
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -235,6 +244,7 @@ hipError_t parse_chunk(vgmi_fastq* f, int i, uint32_t n_new, const uint32_t* n_n
     b.cap_lines = f->cap_lines;
     b.tail_max = f->tail_max;
     b.min_qual = f->min_quality ? 33u + f->min_quality : 0u;      // Phred+33
+    b.sub = f->sub;
     if (!f->fasta) return launch_fastq_chunk(b, n_new, f->stream, n_new_dev);
     FaBuffers a{};
     a.q = b;
@@ -243,6 +253,11 @@ hipError_t parse_chunk(vgmi_fastq* f, int i, uint32_t n_new, const uint32_t* n_n
     a.dest = reinterpret_cast<uint32_t*>(a.bsum + ((size_t)f->cap_lines / 1024 + 2));
     a.rec_d = a.dest + ((size_t)f->cap_lines + 2);
     a.rec_pos = a.rec_d + fasta_cap_rec(f->cap_lines);
+    if (f->sub.on && !f->d_fa_sub) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_fa_sub), ((size_t)f->cap_lines / 1024 + 2) * 8);
+        if (e != hipSuccess) return e;
+    }
+    a.bsum_hdr = f->d_fa_sub;
     return launch_fasta_chunk(a, n_new, f->stream, n_new_dev);
 }
 }  // namespace
@@ -496,6 +511,7 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
         bb.tail_max = b.tail_max;
         bb.n_ref = f->n_ref;
         bb.min_qual = f->min_quality;
+        bb.sub = f->sub;
         HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
         int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
@@ -941,6 +957,37 @@ int vgmi_fastq_masked_bases(vgmi_fastq* f, uint64_t* n)
     unsigned long long v = 0;
     HIPCHK(c, hipMemcpy(&v, &f->d_state->n_masked, sizeof v, hipMemcpyDeviceToHost));
     *n = v;
+    return VGMI_OK;
+}
+
+int vgmi_fastq_set_subsample(vgmi_fastq* f, double fraction, uint64_t seed)
+{
+    if (!f) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    if (!vgh::subsample_fraction_valid(fraction))
+        return fail(c, VGMI_E_INVALID, "subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)");
+    if (f->committed) return fail(c, VGMI_E_STATE, "the subsampling fraction is set before the stream's first commit");
+    f->sub = SubParams{};      // 1: off, the stream that never called this
+    f->sub_fraction = fraction;
+    if (fraction < 1.0) {
+        f->sub.on = 1;
+        f->sub.seed = seed;
+        f->sub.threshold = vgh::subsample_threshold(fraction);
+    }
+    return VGMI_OK;
+}
+
+int vgmi_fastq_subsample_stats(vgmi_fastq* f, uint64_t* seen, uint64_t* kept)
+{
+    if (!f || !seen || !kept) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    *seen = *kept = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(f->stream));
+    FqState st{};
+    HIPCHK(c, hipMemcpy(&st, f->d_state, sizeof st, hipMemcpyDeviceToHost));
+    *kept = st.n_records;
+    *seen = f->sub.on ? st.n_seen : st.n_records;      // off: every read the device accepted is kept, and nothing numbers them
     return VGMI_OK;
 }
 

@@ -22,9 +22,13 @@
 //   B6 l_seq + 1 of every kept record of the chain, B7 scan -> B8 4-bit decode, a wavefront per record ->
 //   B9 bookkeeping (records, bases, consumed bytes, tail; where the chain ends) -> B10 tail carried into the other raw buffer.
 // Offsets are absolute in the raw buffer (tail_max bytes of carry area, then the chunk), so they fit 32 bits.
+// With subsampling (BamBuffers::sub; vgmi_fastq_set_subsample) a read's number in the file is FqState::n_seen + its rank among the
+// chain's reads: between B6 and B7, bam_rank_kernel scans the reads (B7's two phases) and turns rec_bytes of those the rule drops
+// to 0, which B7 and B8 pass over as they pass over the records the filter drops; B9 is bam_finish_sub_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_subsample.h"
 #include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
 
@@ -357,6 +361,74 @@ __global__ void bam_finish_kernel(const uint8_t* raw, FqState* st, const BamStat
     st->tail_len = tail;
 }
 
+// ---- subsampling, off the default path ------------------------------------------------------------------------------------------
+// Between B6 and B7: the rank of every read among the chain's reads -- block sums (phase 0), then (after launch_scan_small over
+// the sums) the ranks; read number n_seen + rank of the file is kept or its rec_bytes turned to 0.  The reads dropped are added up
+// in BamState::n_dropped: n_kept stays the chain's reads.
+__global__ __launch_bounds__(1024) void bam_rank_kernel(uint32_t* rec_bytes, const FqState* st, BamState* bs, uint32_t* block_sum, int phase,
+                                                       uint32_t cap, unsigned long long seed, unsigned long long threshold)
+{
+    __shared__ uint32_t sh[16];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    if (blockIdx.x * 1024u >= n) {      // (uniform) the launch is sized for the capacity
+        if (phase == 0 && threadIdx.x == 0) block_sum[blockIdx.x] = 0;
+        return;
+    }
+    const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+    const bool read = i < n && rec_bytes[i] != 0u;
+    uint32_t tot;
+    const uint32_t ex = block_scan_excl(read ? 1u : 0u, sh, &tot);
+    if (phase == 0) {
+        if (threadIdx.x == 0) block_sum[blockIdx.x] = tot;
+        return;
+    }
+    const bool drop = read && !vgh::subsample_keep(st->n_seen + block_sum[blockIdx.x] + ex, seed, threshold);
+    if (drop) rec_bytes[i] = 0;
+    const uint32_t d = block_reduce_add(drop ? 1u : 0u, sh);
+    if (threadIdx.x == 0 && d) atomicAdd(&bs->n_dropped, d);
+}
+
+// B9: the chain's reads move n_seen on, the kept ones are the chunk's records
+__global__ void bam_finish_sub_kernel(const uint8_t* raw, FqState* st, BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                      const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max,
+                                      int32_t n_ref)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    uint32_t reads = 0, kept = 0, packed = 0, chain_end = st->start, tail = 0;
+    if (!st->stopped) {
+        const uint32_t n = bs->n_cand;
+        if (n > cap) {
+            st->stopped = 1;     // more candidates than the arrays hold: nothing of this chunk is taken, the host resumes at its first byte
+        } else {
+            if (bs->last != BAM_NONE) {
+                const uint32_t o = cand[bs->last];
+                chain_end = o + 4u + bam_ld32(raw, o);
+                reads = bs->n_kept;
+                kept = reads - bs->n_dropped;
+                packed = out_off[n - 1] + rec_bytes[n - 1];
+            }
+            if (chain_end < end) {
+                // what follows the chain: the front of a record the next chunk completes, or something the host must judge
+                uint32_t block_size = 0;
+                const int r = bam_check(raw, chain_end, end, n_ref, &block_size);
+                if (r == 1 && (end - chain_end < 4u || block_size <= tail_max - 4u)) tail = end - chain_end;
+                else st->stopped = 1;     // not a valid record, or one longer than the carry (whole or not: never a candidate)
+            }
+        }
+    }
+    bs->n_dropped = 0;
+    st->n_good = kept;
+    st->packed_bytes = packed;
+    st->n_seen += reads;
+    st->n_records += kept;
+    st->n_bases += packed - kept;
+    st->consumed += chain_end - st->start;
+    st->consumed_end = chain_end;
+    st->tail_len = tail;
+}
+
 // B10: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(256) void bam_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, BamState* bs, uint32_t tail_max)
 {
@@ -407,6 +479,14 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         src = dst;
     }
     hipLaunchKernelGGL(bam_keep_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
+    if (b.sub.on) {
+        hipLaunchKernelGGL(bam_rank_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.bam, b.block_sum, 0, b.cap_cand, b.sub.seed,
+                           b.sub.threshold);
+        e = launch_scan_small(b.block_sum, n_rblk, nullptr, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(bam_rank_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.bam, b.block_sum, 1, b.cap_cand, b.sub.seed,
+                           b.sub.threshold);
+    }
     hipLaunchKernelGGL(bam_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.bam, b.block_sum, b.out_off, 0, b.cap_cand);
     e = launch_scan_small(b.block_sum, n_rblk, nullptr, s);
     if (e != hipSuccess) return e;
@@ -415,8 +495,12 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_decode_mask_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed,
                            b.cap_cand, b.min_qual);
     else hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
-    hipLaunchKernelGGL(bam_finish_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_cand,
-                       b.tail_max, b.n_ref);
+    if (b.sub.on)
+        hipLaunchKernelGGL(bam_finish_sub_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
+                           b.cap_cand, b.tail_max, b.n_ref);
+    else
+        hipLaunchKernelGGL(bam_finish_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_cand,
+                           b.tail_max, b.n_ref);
     hipLaunchKernelGGL(bam_carry_kernel, dim3(1), dim3(256), 0, s, b.raw, b.raw_next, b.state, b.bam, b.tail_max);
     return hipGetLastError();
 }

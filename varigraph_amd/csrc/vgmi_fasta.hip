@@ -30,9 +30,13 @@
 //   A6 records without a sequence byte, or longer than the carry, marked -> A7 bookkeeping (records, bases, consumed bytes, tail) ->
 //   A8 copy of the sequence lines in front of the last accepted record's end, 16 lanes per line (a wrapped line of 60-80 bases is
 //      one pass of dword stores), a whole wavefront with 16-byte stores per line of 512 bytes and more -> A9 carry.
+// With subsampling (FqBuffers::sub; vgmi_fastq_set_subsample) A4, A7 and A8 are their *_sub forms: a line's record number -- the header
+// lines in front of it, a scan of its own -- decides first whether its record is read FqState::n_seen + number of the file and kept;
+// the lines of a dropped record and its closing '\n' add nothing to the scanned bytes, so the block closes up over it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_subsample.h"
 #include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
 
@@ -262,6 +266,145 @@ __global__ __launch_bounds__(256) void fa_pack_kernel(const uint8_t* raw, const 
     }
 }
 
+// ---- subsampling: A4, A7 and A8 again, off the default path ---------------------------------------------------------------------
+// A4 in three phases.  0: header lines per block -> bsum_hdr (A5 scans it).  1 and 2: the header lines in front of line i give its
+// record's number, the rule says whether that record is kept, and the scanned value is A4's with the bytes of a dropped record's lines
+// and the 1 of its header line (the record's '\n') left out: block sums -> bsum (A5 again), then everything A4 writes.  dest of a
+// line that is not copied is FA_NONE; rec_d[r + 1] == rec_d[r] says that record r was dropped.
+__global__ __launch_bounds__(1024) void fa_lines_sub_kernel(const uint8_t* raw, FqState* st, const uint32_t* nlpos, uint32_t tail_max, uint32_t n_new,
+                                                            const uint32_t* n_new_dev, unsigned long long* bsum_hdr, unsigned long long* bsum,
+                                                            uint32_t* dest, uint32_t* rec_d, uint32_t* rec_pos, int phase, uint32_t cap_lines,
+                                                            unsigned long long seed, unsigned long long threshold)
+{
+    __shared__ unsigned long long sh[16];
+    if (fa_skip(st, cap_lines)) return;
+    const uint32_t end = fa_end(tail_max, n_new, n_new_dev);
+    const uint32_t L = fa_n_lines(st, nlpos, end);
+    if (blockIdx.x * 1024u >= L) return;      // (uniform) the launch is sized for the arrays' capacity
+    const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+    uint32_t s = 0, c = '\n', len = 0;
+    bool hdr = false;
+    if (i < L) {
+        s = i ? nlpos[i - 1] + 1 : st->start;
+        const uint32_t e = i < st->n_lines ? nlpos[i] : end;
+        if (s < e) c = raw[s];
+        hdr = c == '>' || c == '@';
+        if (!hdr && c != '+' && c != '\n') len = e - s;
+    }
+    unsigned long long tot;
+    const unsigned long long exh = fa_block_scan_excl(hdr ? 1ull << 32 : 0ull, sh, &tot);
+    if (phase == 0) {
+        if (threadIdx.x == 0) bsum_hdr[blockIdx.x] = tot;
+        return;
+    }
+    const uint32_t n_hdr = (uint32_t)((bsum_hdr[blockIdx.x] + exh) >> 32);      // header lines in front of line i
+    bool keep = false;
+    if (hdr || len) keep = vgh::subsample_keep(st->n_seen + (hdr ? n_hdr : n_hdr ? n_hdr - 1u : 0u), seed, threshold);
+    const unsigned long long v = hdr ? (1ull << 32) | (keep ? 1u : 0u) : keep ? len : 0u;
+    const unsigned long long ex = fa_block_scan_excl(v, sh, &tot);
+    if (phase == 1) {
+        if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+        return;
+    }
+    if (i >= L) return;
+    const unsigned long long e = bsum[blockIdx.x] + ex;
+    const uint32_t hi = (uint32_t)(e >> 32), lo = (uint32_t)e;
+    dest[i] = keep && len ? lo - 1u : FA_NONE;      // (a kept sequence line follows its record's header line: lo >= 1)
+    if (hdr) {
+        if (hi < fasta_cap_rec(cap_lines)) {
+            rec_d[hi] = lo;
+            rec_pos[hi] = s;
+        }
+    } else if (c == '+' && hi) {
+        atomicMin(&st->first_bad, hi - 1u);
+    }
+}
+
+// A7: one workgroup counts the kept records among the accepted ones (rec_d moves on over a kept record: by its '\n' at least), then
+// thread 0 does A7's bookkeeping and moves n_seen on by every accepted record
+__global__ __launch_bounds__(1024) void fa_finish_sub_kernel(const uint8_t* raw, FqState* st, const unsigned long long* total, const uint32_t* rec_d,
+                                                            const uint32_t* rec_pos, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap_lines,
+                                                            uint32_t tail_max)
+{
+    __shared__ uint32_t sh[16];
+    const uint32_t end = fa_end(tail_max, n_new, n_new_dev);
+    const bool live = !st->stopped && st->start < end;
+    const uint32_t first_bad = st->first_bad;
+    bool unfit = false;
+    uint32_t good = 0, H = 0;
+    if (live) {
+        const uint32_t c0 = raw[st->start];
+        unfit = st->dirty || st->n_lines > cap_lines || (c0 != '>' && c0 != '@');
+        if (!unfit) {
+            H = (uint32_t)(*total >> 32);     // >= 1: line 0 is a header line; record H - 1 is the one carried
+            good = first_bad < H - 1u ? first_bad : H - 1u;
+        }
+    }
+    uint32_t mine = 0;
+    for (uint32_t r = threadIdx.x; r < good; r += blockDim.x) mine += rec_d[r + 1] > rec_d[r];
+    const uint32_t kept = block_reduce_add(mine, sh);      // (its barriers: every thread has read the state before thread 0 writes it)
+    if (threadIdx.x) return;
+    uint32_t consumed_end = st->start, packed = 0;
+    if (live) {
+        if (unfit) {
+            st->stopped = 1;     // nothing of this chunk is taken: the host reader resumes at its first byte
+        } else {
+            if (first_bad < H) st->stopped = 1;
+            consumed_end = rec_pos[good];
+            packed = rec_d[good];
+        }
+    }
+    st->n_good = good;
+    st->packed_bytes = packed;
+    st->n_seen += good;
+    st->n_records += kept;
+    st->n_bases += packed - kept;
+    st->consumed += consumed_end - st->start;
+    st->consumed_end = consumed_end;
+    uint32_t tail = st->stopped ? 0u : end - consumed_end;
+    if (tail > tail_max) {      // a record longer than the carry buffer (a contig, not a read): the host reader's
+        st->stopped = 1;
+        tail = 0;
+    }
+    st->tail_len = tail;
+}
+
+// A8: the '\n' behind every kept accepted record, and the lines that have a place in the block (dest != FA_NONE)
+__global__ __launch_bounds__(256) void fa_pack_sub_kernel(const uint8_t* raw, const FqState* st, const uint32_t* nlpos, const uint32_t* dest,
+                                                          const uint32_t* rec_d, uint8_t* packed)
+{
+    const uint32_t good = st->n_good;
+    if (!good) return;
+    const uint32_t stop = st->consumed_end, start = st->start, n_nl = st->n_lines;
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, n_thr = gridDim.x * blockDim.x;
+    for (uint32_t r = tid + 1; r <= good; r += n_thr)
+        if (rec_d[r] > rec_d[r - 1]) packed[rec_d[r] - 1u] = '\n';
+    const uint32_t lane = threadIdx.x & 63u, sub = lane >> 4, l16 = lane & 15u;
+    for (uint32_t i0 = (tid >> 6) * 4u; i0 < n_nl; i0 += (n_thr >> 6) * 4u) {
+        const uint32_t i = i0 + sub;
+        uint32_t b = 0, len = 0, d = 0;
+        if (i < n_nl) {
+            b = i ? nlpos[i - 1] + 1 : start;
+            if (b < stop) {
+                const uint32_t e = nlpos[i], c = b < e ? raw[b] : '\n';
+                if (c != '>' && c != '@' && c != '+' && c != '\n' && dest[i] != FA_NONE) {
+                    len = e - b;
+                    d = dest[i];
+                }
+            }
+        }
+        if (len && len < FA_LONG) fa_copy<4u>(raw, b, len, packed + d, l16, 16u);
+        if (__any(len >= FA_LONG)) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                const uint32_t qb = __shfl(b, q * 16), ql = __shfl(len, q * 16), qd = __shfl(d, q * 16);
+                if (ql >= FA_LONG) fa_copy<16u>(raw, qb, ql, packed + qd, lane, 64u);
+            }
+        }
+        if (__builtin_amdgcn_readfirstlane(b) >= stop) break;     // (uniform; lines are in file order: nothing further lies in front of stop)
+    }
+}
+
 // A9: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(1024) void fa_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, uint32_t tail_max)
 {
@@ -285,6 +428,21 @@ hipError_t launch_fasta_chunk(const FaBuffers& b, uint32_t n_new, hipStream_t s,
     const uint32_t n_lblk = q.cap_lines / 1024u + 1;      // cap_lines + 1 lines at most
     const uint32_t cap_rec = fasta_cap_rec(q.cap_lines);
     const uint32_t rgrid = (cap_rec + 255u) / 256u < 2048u ? (cap_rec + 255u) / 256u : 2048u;
+    if (q.sub.on) {
+        for (int phase = 0; phase < 3; ++phase) {
+            hipLaunchKernelGGL(fa_lines_sub_kernel, dim3(n_lblk), dim3(1024), 0, s, q.raw, q.state, q.nlpos, q.tail_max, n_new, n_new_dev, b.bsum_hdr,
+                               b.bsum, b.dest, b.rec_d, b.rec_pos, phase, q.cap_lines, q.sub.seed, q.sub.threshold);
+            if (phase < 2)
+                hipLaunchKernelGGL(fa_scan_sums_kernel, dim3(1), dim3(1024), 0, s, q.state, q.nlpos, q.tail_max, n_new, n_new_dev,
+                                   phase ? b.bsum : b.bsum_hdr, b.total, q.cap_lines);
+        }
+        hipLaunchKernelGGL(fa_records_kernel, dim3(rgrid), dim3(256), 0, s, q.state, b.total, b.rec_d, b.rec_pos, q.cap_lines, q.tail_max);
+        hipLaunchKernelGGL(fa_finish_sub_kernel, dim3(1), dim3(1024), 0, s, q.raw, q.state, b.total, b.rec_d, b.rec_pos, n_new, n_new_dev, q.cap_lines,
+                           q.tail_max);
+        hipLaunchKernelGGL(fa_pack_sub_kernel, dim3(2048), dim3(256), 0, s, q.raw, q.state, q.nlpos, b.dest, b.rec_d, q.packed);
+        hipLaunchKernelGGL(fa_carry_kernel, dim3(1), dim3(1024), 0, s, q.raw, q.raw_next, q.state, q.tail_max);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(fa_lines_kernel, dim3(n_lblk), dim3(1024), 0, s, q.raw, q.state, q.nlpos, q.tail_max, n_new, n_new_dev, b.bsum, b.dest, b.rec_d,
                        b.rec_pos, 0, q.cap_lines);
     hipLaunchKernelGGL(fa_scan_sums_kernel, dim3(1), dim3(1024), 0, s, q.state, q.nlpos, q.tail_max, n_new, n_new_dev, b.bsum, b.total, q.cap_lines);

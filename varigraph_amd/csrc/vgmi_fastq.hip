@@ -28,9 +28,13 @@
 // With a minimum base quality (FqBuffers::min_qual; vgmi_fastq_set_min_quality) K6 is fq_pack_mask_kernel: the copy reads line 4 next
 // to line 2 and writes 'N' for every base whose quality byte is below the bound.  Not the reference's behaviour (it has no such
 // option): the result is the reference's on a file with those bases written as N.
+// With subsampling (FqBuffers::sub; vgmi_fastq_set_subsample) K4, K7 and K6 are their *_sub forms: record r of the chunk is read
+// FqState::n_seen + r of the file, a read the rule drops gets packed length 0, so the scan closes the block up over it, the copy skips
+// it, and the bookkeeping counts the kept records among the accepted ones.  Without it the chunk launches the kernels above.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_subsample.h"
 #include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
 
@@ -282,6 +286,90 @@ __global__ __launch_bounds__(256) void fq_pack_mask_kernel(const uint8_t* raw, F
     if (threadIdx.x == 0 && t) atomicAdd(&st->n_masked, (unsigned long long)t);
 }
 
+// ---- subsampling: K4, K7 and K6 again, off the default path ---------------------------------------------------------------------
+// K4: the same checks (first_bad is found exactly as without the option); a record the rule drops has packed length 0
+__global__ __launch_bounds__(256) void fq_records_sub_kernel(const uint8_t* raw, FqState* st, const uint32_t* nlpos, uint32_t* rec_bytes,
+                                                             uint32_t cap_lines, unsigned long long seed, unsigned long long threshold)
+{
+    if (st->stopped || st->dirty || st->n_lines > cap_lines) return;
+    const uint32_t R = st->n_lines >> 2;
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const uint32_t s0 = r ? nlpos[4 * r - 1] + 1 : st->start;
+    const uint32_t e0 = nlpos[4 * r], e1 = nlpos[4 * r + 1], e2 = nlpos[4 * r + 2], e3 = nlpos[4 * r + 3];
+    const uint32_t len = e1 - e0 - 1;
+    const uint32_t c1 = raw[e0 + 1];
+    const bool ok = raw[s0] == '@' && len >= 1 && c1 != '@' && c1 != '+' && c1 != '>' && raw[e1 + 1] == '+' && e3 - e2 - 1 == len;
+    rec_bytes[r] = vgh::subsample_keep(st->n_seen + r, seed, threshold) ? len + 1 : 0u;
+    if (!ok) atomicMin(&st->first_bad, r);
+}
+
+// K7: one workgroup.  `packed - good` is no longer the bases: the kept records among the accepted ones are counted (rec_bytes != 0),
+// then thread 0 does K7's bookkeeping and moves n_seen on by every accepted record, kept or not.
+__global__ __launch_bounds__(1024) void fq_finish_sub_kernel(FqState* st, const uint32_t* nlpos, const uint32_t* rec_bytes, const uint32_t* out_off,
+                                                            uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap_lines, uint32_t tail_max)
+{
+    __shared__ uint32_t sh[16];
+    const uint32_t end = fq_end(tail_max, n_new, n_new_dev);
+    const bool stopped = st->stopped, unfit = st->dirty || st->n_lines > cap_lines;
+    const uint32_t R = st->n_lines >> 2, first_bad = st->first_bad;
+    uint32_t good = 0;
+    if (!stopped && !unfit) good = first_bad < R ? first_bad : R;
+    uint32_t mine = 0;
+    for (uint32_t r = threadIdx.x; r < good; r += blockDim.x) mine += rec_bytes[r] != 0u;
+    const uint32_t kept = block_reduce_add(mine, sh);      // (its barriers: every thread has read the state before thread 0 writes it)
+    if (threadIdx.x) return;
+    uint32_t consumed_end = st->start, packed = 0;
+    if (!stopped) {
+        if (unfit) {
+            st->stopped = 1;     // nothing of this chunk is taken: the host reader resumes at its first byte
+        } else {
+            if (first_bad < R) st->stopped = 1;
+            if (good) {
+                consumed_end = nlpos[4 * good - 1] + 1;
+                packed = out_off[good - 1] + rec_bytes[good - 1];
+            }
+        }
+    }
+    st->n_good = good;
+    st->packed_bytes = packed;
+    st->n_seen += good;
+    st->n_records += kept;
+    st->n_bases += packed - kept;
+    st->consumed += consumed_end - st->start;
+    st->consumed_end = consumed_end;
+    uint32_t tail = st->stopped ? 0u : end - consumed_end;
+    if (tail > tail_max) {      // a "record" longer than the carry buffer: not a short-read FASTQ
+        st->stopped = 1;
+        tail = 0;
+    }
+    st->tail_len = tail;
+}
+
+// K6 and its mask form (bound == 0: no qualities are loaded): a record whose packed length is 0 is skipped, its qualities included
+__global__ __launch_bounds__(256) void fq_pack_sub_kernel(const uint8_t* raw, FqState* st, const uint32_t* nlpos, const uint32_t* rec_bytes,
+                                                          const uint32_t* out_off, uint8_t* packed, uint32_t bound)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t good = st->n_good;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    uint32_t masked = 0;
+    for (uint32_t r = wave; r < good; r += n_waves) {
+        if (!rec_bytes[r]) continue;                                 // (uniform over the wavefront)
+        const uint32_t b = nlpos[4 * r] + 1, e = nlpos[4 * r + 1];   // [b, e) = the sequence, raw[e] = '\n'
+        const uint32_t q = nlpos[4 * r + 2] + 1;                     // [q, q + e - b) = its qualities
+        uint8_t* dst = packed + out_off[r];
+        for (uint32_t i = lane; i <= e - b; i += 64) {
+            const bool low = bound && i < e - b && raw[q + i] < bound;
+            dst[i] = low ? (uint8_t)'N' : raw[b + i];
+            masked += low;
+        }
+    }
+    const uint32_t t = block_reduce_add(masked, sh);
+    if (threadIdx.x == 0 && t) atomicAdd(&st->n_masked, (unsigned long long)t);
+}
+
 // K8: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(256) void fq_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, uint32_t tail_max)
 {
@@ -337,10 +425,20 @@ hipError_t launch_fastq_chunk(const FqBuffers& b, uint32_t n_new, hipStream_t s,
     hipLaunchKernelGGL(fq_count_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.tile);
     hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, b.tile, n_tiles, &b.state->n_lines);
     hipLaunchKernelGGL(fq_nlpos_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.tile, b.nlpos, b.cap_lines);
-    hipLaunchKernelGGL(fq_records_kernel, dim3((cap_rec + 255u) / 256u), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines);
+    if (b.sub.on)
+        hipLaunchKernelGGL(fq_records_sub_kernel, dim3((cap_rec + 255u) / 256u), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines,
+                           b.sub.seed, b.sub.threshold);
+    else hipLaunchKernelGGL(fq_records_kernel, dim3((cap_rec + 255u) / 256u), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines);
     hipLaunchKernelGGL(fq_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.block_sum, b.out_off, 0, b.cap_lines);
     hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, b.block_sum, n_rblk, (uint32_t*)nullptr);
     hipLaunchKernelGGL(fq_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.block_sum, b.out_off, 1, b.cap_lines);
+    if (b.sub.on) {
+        hipLaunchKernelGGL(fq_finish_sub_kernel, dim3(1), dim3(1024), 0, s, b.state, b.nlpos, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_lines,
+                           b.tail_max);
+        hipLaunchKernelGGL(fq_pack_sub_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.out_off, b.packed, b.min_qual);
+        hipLaunchKernelGGL(fq_carry_kernel, dim3(1), dim3(256), 0, s, b.raw, b.raw_next, b.state, b.tail_max);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(fq_finish_kernel, dim3(1), dim3(1), 0, s, b.state, b.nlpos, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_lines, b.tail_max);
     if (b.min_qual) hipLaunchKernelGGL(fq_pack_mask_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.out_off, b.packed, b.min_qual);
     else hipLaunchKernelGGL(fq_pack_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.out_off, b.packed);

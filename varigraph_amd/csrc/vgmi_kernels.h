@@ -138,7 +138,17 @@ struct FqState {                       // device-resident, one per open stream
     uint32_t tail_len;                 // bytes of an incomplete record carried into the next chunk
     uint32_t start;                    // where this chunk's text begins in the raw buffer (tail_max - previous tail_len)
     uint32_t consumed_end;             // end of the last accepted record of this chunk
-    uint32_t n_lines, n_good, first_bad, dirty;   // per chunk
+    uint32_t n_lines, n_good, first_bad, dirty;   // per chunk (n_good: the records the copy kernel walks -- FASTQ / FASTA: the accepted ones, also
+                                       // those subsampling drops; BAM: the reads counted into n_records.  Nothing reads it after the chunk)
+    unsigned long long n_seen;         // subsampling only (SubParams; 0 without it): reads numbered so far since the stream was opened, kept or
+                                       // not -- the file number of this chunk's first read.  Last, so that every other field stays where it was
+};
+// Subsampling (vgmi_fastq_set_subsample): read i of the file is kept iff subsample_keep(i, seed, threshold) (vgmi_subsample.h).  A
+// dropped read is not a read: it adds nothing to the read block, n_records or n_bases.  on == 0: the chunk launches the kernels it
+// launched before the option existed.
+struct SubParams {
+    uint32_t on;
+    unsigned long long seed, threshold;
 };
 struct FqBuffers {
     const uint8_t* raw;                // tail_max bytes of carry area + the chunk
@@ -152,6 +162,7 @@ struct FqBuffers {
     FqState* state;
     uint32_t cap_lines, tail_max;
     uint32_t min_qual;                 // 0: off; else a base whose quality byte is below it (Phred+33: 33 + Q) is packed as 'N'
+    SubParams sub;                     // rec_bytes of a dropped record is 0
 };
 hipError_t launch_fastq_init(FqState* st, uint32_t tail_max, hipStream_t s);
 // n_new_dev (may be null): the chunk is cut to min(n_new, *n_new_dev) bytes on the device (text in front of a block-gzip
@@ -171,6 +182,7 @@ struct FaBuffers {
     uint32_t* dest;                    // per line: offset in the packed block (cap_lines + 2)
     uint32_t* rec_d;                   // per record: offset of its sequence in the packed block (fasta_cap_rec entries)
     uint32_t* rec_pos;                 // per record: where its header line starts in the raw buffer (fasta_cap_rec entries)
+    unsigned long long* bsum_hdr;      // subsampling only: header lines per 1024 lines (scan scratch like bsum): a line's record number comes first
 };
 // Entries of the per-record arrays.  A record in front of the first one without a sequence byte takes two lines or more, so that
 // one's number and its successor's lie below (cap_lines + 1) / 2 + 1 however many header lines a chunk holds: header lines beyond
@@ -184,7 +196,7 @@ struct BamState {                      // device-resident, one per open BAM stre
     uint32_t n_cand;                   // per chunk: offsets where a whole, valid record could start
     uint32_t last;                     // per chunk: the last record of the chain from the chunk's start (BAM_NONE: none)
     uint32_t n_kept;                   // per chunk: records of the chain that are read (flag & 0x900 == 0, l_seq > 0)
-    uint32_t pad;
+    uint32_t n_dropped;                // per chunk, subsampling only (0 without it): reads among n_kept that the rule dropped
 };
 struct BamBuffers {
     const uint8_t* raw;                // tail_max bytes of carry area + the chunk
@@ -202,6 +214,7 @@ struct BamBuffers {
     uint32_t cap_cand, tail_max;
     int32_t n_ref;
     uint32_t min_qual;                 // 0: off; else a base whose QUAL byte is below it is decoded as 'N' (a record without QUAL: none)
+    SubParams sub;                     // rec_bytes of a dropped read is turned to 0 before the scan
 };
 hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s);
 hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);

@@ -64,6 +64,12 @@ def lib():
                                    C.POINTER(SampleStats)]
     l.vgh_sample_count_q.restype = C.c_int
     l.vgh_sample_count_q.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.POINTER(C.c_uint64)]
+    l.vgh_sample_count_s.restype = C.c_int
+    l.vgh_sample_count_s.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.c_double, C.c_uint64, C.POINTER(C.c_uint64),
+                                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    l.vgh_reads_read_all_s.restype = C.c_int64
+    l.vgh_reads_read_all_s.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.POINTER(vp),
+                                       C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     l.vgh_reads_read_all_q.restype = C.c_int64
     l.vgh_reads_read_all_q.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]
@@ -155,19 +161,25 @@ class Graph:
             raise RuntimeError(self._l.vgh_last_error().decode())
         return cov, rb.value
 
-    def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True, min_base_quality=0):
+    def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True, min_base_quality=0,
+                     subsample=None):
         """FastqKmerHip::build_fastq_index + coverage statistics for one sample.  require_depth=False: a sample too thin
         for the coverage peak (the reference exits with "Failed to retrieve depth information") still returns its
         counters.  min_base_quality: bases of FASTQ / BAM reads whose quality is below it are counted as N (vgh_sample_count_q);
-        stats["masked_bases"] = how many, device and host readers together."""
+        stats["masked_bases"] = how many, device and host readers together.  subsample=(F, S): a seeded fraction of every file's
+        reads is kept (vgh_sample_count_s); stats then has reads_seen and reads_kept, and n_reads / read_base are the kept reads'."""
         i = self.info
         cov = np.empty(i["n_keys"], dtype=np.uint8)
         cov_node = np.empty(i["n_node_entries"], dtype=np.uint8)
         hist = np.zeros(256, dtype=np.uint64)
         st = SampleStats()
         arr = (C.c_char_p * len(fastq_paths))(*[os.fsencode(p) for p in fastq_paths])
-        masked = C.c_uint64()
-        if min_base_quality:
+        masked, seen, kept = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if subsample is not None:
+            rc = self._l.vgh_sample_count_s(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
+                                            vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
+                                            float(subsample[0]), int(subsample[1]), C.byref(seen), C.byref(kept), C.byref(masked))
+        elif min_base_quality:
             rc = self._l.vgh_sample_count_q(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
                                             vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality, C.byref(masked))
         else:
@@ -177,6 +189,8 @@ class Graph:
             raise vgmi.VgmiError(rc, self._l.vgh_last_error().decode())
         stats = {f[0]: getattr(st, f[0]) for f in SampleStats._fields_}
         stats["masked_bases"] = masked.value
+        if subsample is not None:
+            stats["reads_seen"], stats["reads_kept"] = seen.value, kept.value
         return cov, cov_node, hist, stats
 
 
@@ -285,6 +299,22 @@ def reads_read_all_q(path, min_base_quality, decode_threads=1):
     finally:
         l.vgh_free(p)
     return block, int(cnt), rb.value, mb.value
+
+
+def reads_read_all_s(path, fraction, seed, first_number=0, min_base_quality=0, decode_threads=1):
+    """A FASTA/Q or BAM file through the host reader with subsampling (vgh_reads_read_all_s): (block, n_kept, read_base, masked_bases,
+    next_number) -- the block of reads_read_all_q with the dropped reads left out, the file's reads numbered from first_number."""
+    l = lib()
+    p, n, rb, mb, nx = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    cnt = l.vgh_reads_read_all_s(os.fsencode(path), decode_threads, min_base_quality, fraction, seed, first_number, C.byref(p), C.byref(n),
+                                 C.byref(rb), C.byref(mb), C.byref(nx))
+    if cnt < 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    try:
+        block = _arr(p.value, n.value, np.uint8)
+    finally:
+        l.vgh_free(p)
+    return block, int(cnt), rb.value, mb.value, nx.value
 
 
 def sniff_input(path):

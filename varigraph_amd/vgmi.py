@@ -81,6 +81,8 @@ def load_library():
         "vgmi_fastq_close": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), vp, sz, C.POINTER(sz)]),
         "vgmi_fastq_set_min_quality": (i32, [vp, u32]),
         "vgmi_fastq_masked_bases": (i32, [vp, C.POINTER(u64)]),
+        "vgmi_fastq_set_subsample": (i32, [vp, C.c_double, u64]),
+        "vgmi_fastq_subsample_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "vgmi_sketch_keys": (i32, [vp, vp, sz, vp, sz, u32, vp]),
         "vgmi_bloom_params": (i32, [u64, C.c_double, C.POINTER(u64), C.POINTER(u32)]),
         "vgmi_bloom_create": (i32, [vp, u64, u32, vp]),
@@ -209,6 +211,7 @@ class Context:
         self.n_keys = 0
         self.n_node_entries = 0
         self._quality_streams = set()      # open streams on which vgmi_fastq_set_min_quality was called
+        self._subsample_streams = set()    # open streams on which vgmi_fastq_set_subsample was called
 
     def close(self):
         if getattr(self, "_h", None):
@@ -353,13 +356,14 @@ class Context:
         self._chk(self._l.vgmi_pt_live_check(self._h, out))
         return tuple(int(v) for v in out)
 
-    def fastq_text(self, text, piece=None, min_quality=0):
+    def fastq_text(self, text, piece=None, min_quality=0, subsample=None, subsample_first=False):
         """Device-side FASTQ parser over one stream of file text (bytes), committed in pieces of `piece` bytes (default:
         whole staging buffers).  min_quality: bases whose quality is below it are counted as N (vgmi_fastq_set_min_quality; 0 = off).
-        Returns dict(n_records, n_bases, consumed, stopped, tail, masked_bases)."""
+        subsample=(F, S): a seeded fraction of the reads is kept (vgmi_fastq_set_subsample); the dict then has n_seen, the reads the
+        device numbered, and n_records counts the kept ones.  Returns dict(n_records, n_bases, consumed, stopped, tail, masked_bases)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
-        self._set_min_quality(fq, min_quality)
+        self._set_options(fq, min_quality, subsample, subsample_first)
         return self._text_stream(fq, text, piece)
 
     def _set_min_quality(self, fq, min_quality):
@@ -376,6 +380,39 @@ class Context:
                 raise VgmiError(rc, msg)
         self._quality_streams.add(fq.value)
 
+    def _set_options(self, fq, min_quality, subsample, subsample_first=False):
+        """The two setters on a stream just opened, the minimum base quality first unless subsample_first."""
+        if subsample_first:
+            self._set_subsample(fq, subsample)
+        self._set_min_quality(fq, min_quality)
+        if not subsample_first:
+            self._set_subsample(fq, subsample)
+
+    def _set_subsample(self, fq, subsample):
+        """vgmi_fastq_set_subsample on a stream just opened; a refusal closes the stream and raises.  None (the default) does not call
+        the C entry at all.  (F, S) calls it once, a list of such pairs once per pair, in order -- [(0.5, 11), (1.0, 11)] is how the
+        tests show that setting 1.0 is the same as never setting anything."""
+        if subsample is None:
+            return
+        for f, seed in [subsample] if isinstance(subsample, tuple) else subsample:
+            rc = self._l.vgmi_fastq_set_subsample(fq, f, seed)
+            if rc:
+                msg = self._l.vgmi_last_error(self._h).decode()
+                self._l.vgmi_fastq_close(fq, None, None, None, None, None, 0, None)
+                raise VgmiError(rc, msg)
+        self._subsample_streams.add(fq.value)
+
+    def _with_seen(self, fq, res):
+        """res, the dict a stream is about to return, with n_seen (vgmi_fastq_subsample_stats) when its setter was called; called
+        in front of vgmi_fastq_close.  A stream whose setter was never called is not asked and res stays as it is."""
+        if fq.value in self._subsample_streams:
+            self._subsample_streams.discard(fq.value)
+            seen, kept = C.c_uint64(), C.c_uint64()
+            ok = self._l.vgmi_fastq_subsample_stats(fq, C.byref(seen), C.byref(kept)) == 0
+            res["n_seen"] = seen.value if ok else None
+            res["n_kept"] = kept.value if ok else None
+        return res
+
     def _masked_bases(self, fq):
         """vgmi_fastq_masked_bases of a stream about to be closed; a stream whose setter was never called is not asked (0)"""
         if fq.value not in self._quality_streams:
@@ -384,11 +421,12 @@ class Context:
         n = C.c_uint64()
         return n.value if self._l.vgmi_fastq_masked_bases(fq, C.byref(n)) == 0 else None
 
-    def fasta_text(self, text, piece=None):
+    def fasta_text(self, text, piece=None, subsample=None):
         """Device-side FASTA parser (vgmi_fastq_open_fasta) over one stream of file text, as fastq_text.  The last record of the text
         is never taken by the device: it comes back as `tail`, from its header line on."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
+        self._set_subsample(fq, subsample)
         return self._text_stream(fq, text, piece)
 
     def _text_stream(self, fq, text, piece):
@@ -408,32 +446,34 @@ class Context:
             nr, nb, cons, st, tl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int(), C.c_size_t()
             tail = C.create_string_buffer(1 << 20)
             masked = self._masked_bases(fq)
+            sub = self._with_seen(fq, {})
             rc = self._l.vgmi_fastq_close(fq, C.byref(nr), C.byref(nb), C.byref(cons), C.byref(st), tail, 1 << 20, C.byref(tl))
         self._chk(rc)
         return {"n_records": nr.value, "n_bases": nb.value, "consumed": cons.value, "stopped": bool(st.value),
-                "tail": tail.raw[:tl.value], "masked_bases": masked}
+                "tail": tail.raw[:tl.value], "masked_bases": masked, **sub}
 
-    def fastq_bgzf(self, comp, piece=None, min_quality=0):
+    def fastq_bgzf(self, comp, piece=None, min_quality=0, subsample=None):
         """Block-gzip bytes through the device inflate + parser.  Returns the dict of fastq_text plus inflate_failed,
         good_compressed_bytes, taken (compressed bytes handed over as whole members)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
-        self._set_min_quality(fq, min_quality)
+        self._set_options(fq, min_quality, subsample)
         return self._bgzf_stream(fq, comp, piece)
 
-    def fasta_bgzf(self, comp, piece=None):
+    def fasta_bgzf(self, comp, piece=None, subsample=None):
         """Block-gzip FASTA through the device inflate + FASTA parser.  Returns the dict of fastq_bgzf."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
+        self._set_subsample(fq, subsample)
         return self._bgzf_stream(fq, comp, piece)
 
-    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0):
+    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0, subsample=None, subsample_first=False):
         """A BAM file's block-gzip bytes through the device inflate + BAM record kernels (vgmi_fastq_open_bam): header_bytes = the
         header's length in the decompressed stream (magic to the last reference), n_ref its number of references.  Returns the dict of fastq_bgzf; consumed
         counts decompressed bytes, header included."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_bam(self._h, header_bytes, n_ref, C.byref(fq)))
-        self._set_min_quality(fq, min_quality)
+        self._set_options(fq, min_quality, subsample, subsample_first)
         return self._bgzf_stream(fq, comp, piece)
 
     def _bgzf_stream(self, fq, comp, piece):
@@ -465,24 +505,26 @@ class Context:
             nr, nbs, cons, st, tl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int(), C.c_size_t()
             tail = C.create_string_buffer(1 << 20)
             masked = self._masked_bases(fq)
+            sub = self._with_seen(fq, {})
             rc = self._l.vgmi_fastq_close(fq, C.byref(nr), C.byref(nbs), C.byref(cons), C.byref(st), tail, 1 << 20, C.byref(tl))
         self._chk(rc)
         return {"n_records": nr.value, "n_bases": nbs.value, "consumed": cons.value, "stopped": bool(st.value),
                 "tail": tail.raw[:tl.value], "masked_bases": masked, "inflate_failed": bool(failed.value), "good_compressed_bytes": good.value,
-                "reason": reason.value, "taken": total_taken}
+                "reason": reason.value, "taken": total_taken, **sub}
 
-    def fastq_gzip(self, comp, piece=None, min_quality=0):
+    def fastq_gzip(self, comp, piece=None, min_quality=0, subsample=None):
         """Ordinary gzip bytes through the device inflate + parser (vgmi_fastq_commit_gzip).  Returns the dict of fastq_text plus stop
         (1 data over, 2 the device gave up), device_text_bytes, reason, taken (compressed bytes used up)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
-        self._set_min_quality(fq, min_quality)
+        self._set_options(fq, min_quality, subsample)
         return self._gzip_stream(fq, comp, piece)
 
-    def fasta_gzip(self, comp, piece=None):
+    def fasta_gzip(self, comp, piece=None, subsample=None):
         """Ordinary gzip FASTA through the device inflate + FASTA parser.  Returns the dict of fastq_gzip."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
+        self._set_subsample(fq, subsample)
         return self._gzip_stream(fq, comp, piece)
 
     def _gzip_stream(self, fq, comp, piece):
@@ -515,11 +557,12 @@ class Context:
             nr, nbs, cons, sp, tl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int(), C.c_size_t()
             tail = C.create_string_buffer(1 << 20)
             masked = self._masked_bases(fq)
+            sub = self._with_seen(fq, {})
             rc = self._l.vgmi_fastq_close(fq, C.byref(nr), C.byref(nbs), C.byref(cons), C.byref(sp), tail, 1 << 20, C.byref(tl))
         self._chk(rc)
         return {"n_records": nr.value, "n_bases": nbs.value, "consumed": cons.value, "stopped": bool(sp.value), "tail": tail.raw[:tl.value],
                 "masked_bases": masked,
-                "stop": stop, "device_text_bytes": dtext.value, "reason": reason.value, "taken": total_taken}
+                "stop": stop, "device_text_bytes": dtext.value, "reason": reason.value, "taken": total_taken, **sub}
 
     def gunzip(self, comp, cap):
         """An ordinary gzip member through the device pipeline (vgmi_gunzip_buffer): (text bytes, compressed bytes consumed, member
