@@ -96,6 +96,16 @@ int64_t vgh_reads_read_all_q(const char *path, uint32_t decode_threads, uint32_t
 int64_t vgh_reads_read_all_s(const char *path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
                              uint64_t first_number, char **block_out, size_t *n_bytes_out, uint64_t *read_base, uint64_t *masked_bases,
                              uint64_t *next_number);
+/* The same with the read filter of BAM files (the rule of vgmi_fastq_set_bam_filter, which has the parameters' ranges; bam_tag NULL:
+ * no tag bound; exclude 0x900, require 0, min_mapq 0, no tag: vgh_reads_read_all_s): a record the filter drops is not a read, and
+ * subsampling numbers the reads that passed.  *bam_records, *bam_reads (may be NULL) = the valid records examined and the reads
+ * among them, before subsampling.  A record whose auxiliary fields cannot be walked ends the call with "'<path>': not a valid BAM
+ * record at decompressed byte N (auxiliary fields)".  A FASTA/Q file is read as without the filter.  VGMI_E_INVALID for a parameter
+ * out of range. */
+int64_t vgh_reads_read_all_f(const char *path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char *bam_tag,
+                             double bam_min_value, char **block_out, size_t *n_bytes_out, uint64_t *read_base, uint64_t *masked_bases,
+                             uint64_t *next_number, uint64_t *bam_records, uint64_t *bam_reads);
 /* What the device path of vgh_sample_count makes of an input file, from its first bytes (no device involved): kind = "plain" |
  * "gzip" | "bgzf"; first_byte = the first byte of its text (-1: it has none); bam = block gzip whose text starts with "BAM\1";
  * fasta = the text starts with '>' and goes to the device's FASTA parser (VGH_DEVICE_FASTA=0: never).  Any pointer may be NULL. */
@@ -144,6 +154,19 @@ int vgh_sample_count_s(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fas
                        uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
                        uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
                        double fraction, uint64_t seed, uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases);
+/* The same with the read filter of BAM files (genotype --bam-exclude-flags / --bam-require-flags / --bam-min-mapq / --bam-min-tag; the
+ * rule and the parameters' ranges: vgmi_fastq_set_bam_filter): applied on the device and wherever the host decoder serves -- the
+ * hand-over, pipes, VGH_HOST_PARSE=1, VGH_HOST_INFLATE=1.  A dropped record is not a read: subsampling numbers the reads that
+ * passed, read_base, n_reads and the depth statistics are theirs.  FASTQ and FASTA files among the paths are untouched.  The default
+ * parameters (0x900, 0, 0, NULL) are vgh_sample_count_s.  *bam_records, *bam_reads (may be NULL) = the BAM files' valid records
+ * and the reads among them, the two readers' counts added.  A record whose auxiliary fields cannot be walked (tag bound only) ends
+ * the call with the host decoder's error, "... (auxiliary fields)".  VGMI_E_INVALID for a parameter out of range. */
+int vgh_sample_count_f(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fastq_paths, size_t n_files,
+                       uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
+                       uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
+                       double fraction, uint64_t seed, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq,
+                       const char *bam_tag, double bam_min_value, uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases,
+                       uint64_t *bam_records, uint64_t *bam_reads);
 
 /* Coverage statistics alone (Varigraph::kmer_read / cal_ave_cov_kmer): hist = masked coverage histogram
  * (vgmi_counts_finish).  Fills read_depth, hap_kmer_coverage, max_coverage, hom_coverage of *stats; returns

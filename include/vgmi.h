@@ -225,7 +225,8 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq *fq, size_t n_bytes, size_t *taken, size_t
  * close as for FASTQ; commit and commit_gzip are refused.  The reads are the records with flag & 0x900 == 0 and l_seq > 0, their
  * 4-bit SEQ decoded as stored.  close: n_records / n_bases = those reads and their bases; consumed_bytes = a record boundary in the
  * decompressed stream (header included); stopped != 0: the record there is not a valid BAM record, or is longer than the 1 MiB
- * carry -- the host decoder takes the stream over at consumed_bytes. */
+ * carry, or (with a tag bound, vgmi_fastq_set_bam_filter) has auxiliary fields that cannot be walked -- the host decoder takes the
+ * stream over at consumed_bytes. */
 int vgmi_fastq_open_bam(vgmi_ctx *ctx, uint64_t header_bytes, int32_t n_ref, vgmi_fastq **out);
 /* A FASTA stream (vgmi_fasta.hip): text whose first byte is '>', single-line or wrapped.  acquire / commit / commit_bgzf /
  * commit_gzip / the status calls / close as for FASTQ.  Line by line, as kseq_read does (include/kseq.h:208-215): a line that
@@ -286,6 +287,25 @@ int vgmi_fastq_set_subsample(vgmi_fastq *fq, double fraction, uint64_t seed);
 /* Reads numbered so far in the records the device has accepted (*seen: the number the host reader goes on with) and how many of them
  * were kept (*kept: n_records); waits for the stream.  Without subsampling both are n_records.  Valid until vgmi_fastq_close. */
 int vgmi_fastq_subsample_stats(vgmi_fastq *fq, uint64_t *seen, uint64_t *kept);
+/* The read filter of a BAM stream (csrc/vgmi_bam_filter.h has the rule, once for the device and the host decoder).  A valid record is
+ * a read iff l_seq > 0, (flag & exclude) == 0, (flag & require) == require, mapq >= min_mapq (255 passes; an unmapped record's 0
+ * fails a positive bound) and -- with tag != NULL, two bytes -- the FIRST auxiliary field with that tag is numeric (c C s S i I f d)
+ * and its value, as a double, is >= min_value (NaN fails; absent or of type A Z H B: not a read -- `samtools view -e '[tg]>=v'`).
+ * Defaults: exclude 0x900, require 0, min_mapq 0, no tag; exclude REPLACES the default as `samtools fastq -F` does, so 0xF00 adds
+ * QC failures and duplicates, and a value without 0x900 lets secondary and supplementary records in.  The all-default call makes
+ * the stream the one that never called this; a FASTQ or FASTA stream accepts the call without effect.
+ * A record the filter drops is not a read: subsampling numbers the reads that passed, a minimum base quality masks only them, and
+ * n_records / n_bases are theirs; consumed_bytes stays the stream's bytes.  Auxiliary bytes are read only with a tag bound and only
+ * of records that passed the other tests, up to the first field with the tag.  A walk fault (one or two bytes left in front of the
+ * record's end, an unknown type or B subtype, a value running past the record's end, a Z / H without NUL) makes the record invalid:
+ * close returns stopped != 0 with consumed_bytes at its first byte, the records in front of it counted.
+ * Before the stream's first commit only: VGMI_E_STATE afterwards.  VGMI_E_INVALID: exclude or require above 0xFFFF, min_mapq above
+ * 255, a tag whose first byte is not a letter or whose second is not a letter or digit, a NaN bound.  The stream serves on after
+ * either, the last value set holds, and the three setters may be called in any order. */
+int vgmi_fastq_set_bam_filter(vgmi_fastq *fq, uint32_t exclude, uint32_t require, uint32_t min_mapq, const char *tag, double min_value);
+/* Records of the chain examined and the reads among them (before subsampling) in what the device has accepted; waits for the
+ * stream.  VGMI_E_STATE on a stream without a filter.  Valid until vgmi_fastq_close. */
+int vgmi_fastq_bam_filter_stats(vgmi_fastq *fq, uint64_t *records, uint64_t *reads);
 
 /* K1 alone: the key every position of a read block emits, for emitter parity tests.
  * keys_out[i] = key of the k-mer ENDING at byte i, or UINT64_MAX when the reference emits nothing

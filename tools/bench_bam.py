@@ -1,10 +1,14 @@
 """bench_bam.py -- a sample's reads through vgh_sample_count as unaligned BAM and as block-gzip FASTQ of the same reads, with the same
 member size (0xff00 bytes of text), in one process: reads/s of each, alternating, median of --reps.  Prints one JSON line.
 
-    python tools/bench_bam.py [--reads 20000000] [--reps 3] [--dir DIR] [--only bam|fastq]
+    python tools/bench_bam.py [--reads 20000000] [--reps 3] [--dir DIR] [--only bam|fastq] [--filter [--tags 8]]
 
 The reads are 150 bp drawn from the C1 cohort's haplotypes (tests/golden/c1) by the seeded generator; the BAM records are unmapped
-(flag 4, refID -1), named, with a quality string and no aux fields -- what a sequencer's uBAM holds."""
+(flag 4, refID -1), named, with a quality string and no aux fields -- what a sequencer's uBAM holds.
+
+--filter: the BAM's records carry rq as f (a tenth below 0.99) behind --tags short integer tags (0: a PacBio-like uBAM; 8: an
+aligned-style record), a tenth are marked duplicate and 3 % QC-fail; the legs are the BAM with the default read filter, with exclude
+0xF00 and with the tag bound rq >= 0.99 (vgh_sample_count_f), reads/s counted over the file's records."""
 import argparse
 import json
 import os
@@ -55,11 +59,12 @@ class BgzfWriter:
         self.f.close()
 
 
-def _records(rows, first):
-    """fixed-layout uBAM records of the reads `rows` (n x 150 ASCII): name 'r%09d', no CIGAR, SEQ, QUAL 30, no aux"""
+def _records(rows, first, n_tags=None):
+    """fixed-layout uBAM records of the reads `rows` (n x 150 ASCII): name 'r%09d', no CIGAR, SEQ, QUAL 30, no aux; n_tags (--filter):
+    n_tags fields 'X<d>C' <d>, then rq:f, and drawn duplicate / QC-fail flags"""
     n = rows.shape[0]
     name = 11
-    size = 4 + 32 + name + L // 2 + L
+    size = 4 + 32 + name + L // 2 + L + (0 if n_tags is None else 4 * n_tags + 7)
     rec = np.zeros((n, size), dtype=np.uint8)
     fixed = struct.pack("<iiiBBHHHiiii", size - 4, -1, -1, name, 0, 4680, 0, 4, L, -1, -1, 0)
     rec[:, :36] = np.frombuffer(fixed, dtype=np.uint8)
@@ -71,7 +76,21 @@ def _records(rows, first):
     code[NT16] = np.arange(16, dtype=np.uint8)
     c = code[rows]
     rec[:, 36 + name:36 + name + L // 2] = c[:, 0::2] << 4 | c[:, 1::2]
-    rec[:, 36 + name + L // 2:] = 30
+    q0 = 36 + name + L // 2
+    rec[:, q0:q0 + L] = 30
+    if n_tags is not None:
+        rng = np.random.default_rng(first + 1)
+        flag = np.full(n, 4, dtype=np.uint16)
+        flag[rng.random(n) < 0.1] |= 0x400
+        flag[rng.random(n) < 0.03] |= 0x200
+        rec[:, 18:20] = flag.view(np.uint8).reshape(n, 2)
+        a = q0 + L
+        for t in range(n_tags):
+            rec[:, a:a + 4] = np.frombuffer(b"X%dC" % (t % 10) + bytes([t]), dtype=np.uint8)
+            a += 4
+        rec[:, a:a + 3] = np.frombuffer(b"rqf", dtype=np.uint8)
+        rq = np.where(rng.random(n) < 0.9, rng.uniform(0.99, 1.0, n), rng.uniform(0.9, 0.99, n)).astype("<f4")
+        rec[:, a + 3:a + 7] = rq.view(np.uint8).reshape(n, 4)
     return rec
 
 
@@ -90,7 +109,7 @@ def _fastq(rows, first):
     return m
 
 
-def make_files(d, n_reads, haps, level):
+def make_files(d, n_reads, haps, level, n_tags=None):
     bam, fq = os.path.join(d, "reads.bam"), os.path.join(d, "reads.fq.gz")
     with ThreadPoolExecutor(16) as pool:
         wb, wf = BgzfWriter(bam, level, pool), BgzfWriter(fq, level, pool)
@@ -99,7 +118,7 @@ def make_files(d, n_reads, haps, level):
         for first in range(0, n_reads, PIECE):
             n = min(PIECE, n_reads - first)
             rows = vgmi.synth_reads_host(4242, first, n, L, haps).reshape(n, L + 1)[:, :L]
-            wb.write(_records(rows, first).tobytes())
+            wb.write(_records(rows, first, n_tags).tobytes())
             wf.write(_fastq(rows, first).tobytes())
         wb.close()
         wf.close()
@@ -113,6 +132,8 @@ def main():
     ap.add_argument("--level", type=int, default=1)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--only", choices=["bam", "fastq"], default=None)
+    ap.add_argument("--filter", action="store_true", help="the read-filter legs: default, exclude 0xF00, rq >= 0.99")
+    ap.add_argument("--tags", type=int, default=0, help="--filter: short tags in front of rq in every record")
     a = ap.parse_args()
     gdir = os.path.join(ROOT, "tests", "golden", "c1")
     meta = json.load(open(os.path.join(gdir, "meta.json")))
@@ -121,28 +142,34 @@ def main():
     haps = synth.sample_haplotypes(ref, variants, gts, 0, meta["ploidy"])
     tmp = tempfile.TemporaryDirectory(dir=a.dir)
     t0 = time.perf_counter()
-    bam, fq = make_files(tmp.name, a.reads, haps, a.level)
+    bam, fq = make_files(tmp.name, a.reads, haps, a.level, a.tags if a.filter else None)
     t_make = time.perf_counter() - t0
     g = host.Graph(os.path.join(gdir, "graph.bin.gz"))
     ctx = vgmi.Context(0)
     g.upload(ctx)
     legs = {"bam": bam, "fastq": fq} if a.only is None else {a.only: bam if a.only == "bam" else fq}
+    filters = {}
+    if a.filter:
+        legs = {"bam": bam, "bam_exclude": bam, "bam_tag": bam}
+        filters = {"bam_exclude": dict(exclude=0xF00), "bam_tag": dict(tag=b"rq", min_value=0.99)}
     rates, stats = {k: [] for k in legs}, {}
     g.sample_count(ctx, [bam], threads=16, require_depth=False)      # warm-up: code objects, pinned buffers
     for _ in range(a.reps):
         for k, p in legs.items():
             t = time.perf_counter()
-            cov, _, hist, st = g.sample_count(ctx, [p], threads=16, require_depth=False)
+            cov, _, hist, st = g.sample_count(ctx, [p], threads=16, require_depth=False, bam_filter=filters.get(k))
             dt = time.perf_counter() - t
-            rates[k].append(st["n_reads"] / dt)
+            rates[k].append((a.reads if a.filter else st["n_reads"]) / dt)      # (--filter: the file's records per second)
             stats[k] = (st["n_reads"], st["read_base"], hist.tobytes())
-    if len(stats) == 2:
+    if len(stats) == 2 and not a.filter:
         assert stats["bam"] == stats["fastq"], "BAM and FASTQ legs count differently"
     out = {"tool": "bench_bam", "reads": a.reads, "read_len": L, "member_text_bytes": MEMBER, "level": a.level,
            "bytes": {k: os.path.getsize(p) for k, p in (("bam", bam), ("fastq", fq))}, "make_s": round(t_make, 1),
            "reads_per_s": {k: float("%.4g" % statistics.median(v)) for k, v in rates.items()},
            "runs": {k: ["%.4g" % x for x in v] for k, v in rates.items()}}
-    if len(stats) == 2:
+    if a.filter:
+        out["filter"] = {"tags": a.tags, "reads_passed": {k: stats[k][0] for k in stats}}
+    if len(stats) == 2 and not a.filter:
         out["bam_over_fastq"] = round(out["reads_per_s"]["bam"] / out["reads_per_s"]["fastq"], 3)
     print(json.dumps(out))
     ctx.close()

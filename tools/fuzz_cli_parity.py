@@ -2,7 +2,7 @@
 """Drawn end-to-end cases through both CLIs (the unmodified reference, oracle/_ref/varigraph_det, and varigraph-mi) on one GPU box:
 genome size, variant mix, cohort size and ploidy, k, construct mode, reads per sample and every genotype option are drawn from a seed;
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
-  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample]
+  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample] [--bam-filter]
 --max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from.
 --max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100, 127, 130, 160 and 255 diploid
 VCF samples, as far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 511 haplotypes, 7 to 64 bytes of haplotype bits
@@ -12,7 +12,10 @@ haplotypes (DESIGN_INGEST_HMM 4.18; with VGH_HMM_WIDE_PLOIDY_DEVICE=1 in the env
 passed over before anything is built.  Every seed keeps its case.
 --subsample (off by default: every seed draws the case it always drew) gives half of the cases a fraction and a seed for `genotype --subsample`,
 drawn from a generator of their own behind the case's; varigraph-mi then reads the case's files with the option and the reference the
-filtered files this script writes with the Python model of the rule (tests/subsample_cases.py): the same VCFs, or both refuse."""
+filtered files this script writes with the Python model of the rule (tests/subsample_cases.py): the same VCFs, or both refuse.
+--bam-filter (off by default, and only for cases --subsample left alone) turns the read files of half of the cases into BAM files with
+drawn flags, MAPQ and an rq field, and draws a read filter (DESIGN_INGEST_HMM 4.23): varigraph-mi reads the BAM files with the filter's
+options, the reference the twin FASTQ of the records that pass by the Python model (tests/bam_filter_cases.py)."""
 import gzip, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -68,6 +71,7 @@ def dress(path, rng):
 MAX_PLOIDY = 4      # --max-ploidy N: ploidy 5 .. N joins both draws (DESIGN_INGEST_HMM 4.15: the device's HMM for samples of ploidy 5 .. 8)
 MAX_VCF_SAMPLES = 7      # --max-vcf-samples N: diploid cohorts of up to N samples (DESIGN_INGEST_HMM 4.16, 4.21: the device's HMM over panels of 48 to 511 haplotypes)
 ONLY_WIDE_PLOIDY = False      # --only-wide-ploidy: seeds whose draw is anything else are passed over
+BAM_FILTER = False      # --bam-filter: a drawn case may get BAM read files and a read filter (DESIGN_INGEST_HMM 4.23)
 SUBSAMPLE = False      # --subsample: a drawn case may get a fraction and a seed (DESIGN_INGEST_HMM 4.22)
 FORCE = {}      # --k K / --genome G on the command line: the drawn value replaced (round 6: campaigns of k = 28 over graphs on either side of 65 536 k-mers)
 
@@ -81,6 +85,32 @@ def filtered(path, fraction, sub_seed):
     out = path + ".kept.fq"
     open(out, "wb").write(subsample_cases.filtered_fastq_text(text, fraction, sub_seed)[0])
     return out
+
+
+BAM_FILTERS = ((["--bam-exclude-flags", "0xF00"], dict(exclude=0xF00)), (["--bam-exclude-flags", "0x400"], dict(exclude=0x400)),
+               (["--bam-min-mapq", "20"], dict(min_mapq=20)), (["--bam-min-tag", "rq:0.99"], dict(tag=b"rq", min_value=0.99)),
+               (["--bam-exclude-flags", "0xD00", "--bam-require-flags", "0x1", "--bam-min-mapq", "5", "--bam-min-tag", "rq:0.95"],
+                dict(exclude=0xD00, require=0x1, min_mapq=5, tag=b"rq", min_value=0.95)))
+
+
+def as_bam(path, brng, filt):
+    """a read file of the case as a BAM with drawn flags, MAPQ and rq -> (the BAM, the twin FASTQ of the records that pass `filt`)"""
+    import bam_filter_cases as F, bam_py, quality_mask_cases
+    raw = open(path, "rb").read()
+    text = gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw
+    if not text.endswith(b"\n"): text += b"\n"
+    recs = []
+    for name, seq, qual in quality_mask_cases.records_of(text):
+        flag = (1 if brng.random() < 0.7 else 0) | (0x10 if brng.random() < 0.5 else 0)
+        for bit, p in ((0x100, 0.03), (0x200, 0.05), (0x400, 0.12), (0x800, 0.03)):
+            if brng.random() < p: flag |= bit
+        rq = 1.0 - 0.1 * float(brng.random()) ** 3      # (0.9, 1]: 46 % at or above 0.99, 79 % at or above 0.95
+        recs.append(bam_py.Rec(name.split()[0], seq.upper(), flag=flag, mapq=int(brng.choice((0, 3, 20, 60, 255))), qual=bytes(min(max(c - 33, 0), 93) for c in qual),
+                               aux=F.aux(b"NM", "C", 2) + F.aux(b"RG", "Z", b"g1") + F.aux(b"rq", "f", rq)))
+    bam_py.write_bam(path + ".bam", recs, level=int(brng.integers(1, 7)), block=int(brng.integers(2000, 0xff01)))
+    passing, _, _, at = F.apply(recs, F.Filter(**filt))
+    assert at is None
+    return path + ".bam", bam_py.twin_fastq(path + ".twin.fq", passing)
 
 
 def case(seed):
@@ -132,6 +162,12 @@ def case(seed):
             if srng.random() < 0.5:
                 sub = ([0.5, 0.25, 0.9, 0.05, 0.999][int(srng.integers(0, 5))], int(srng.integers(0, 2 ** 63)) * 2 + int(srng.integers(0, 2)))
                 desc += f", --subsample {sub[0]} --subsample-seed {sub[1]}"
+        bamf = None
+        if BAM_FILTER and sub is None:      # a generator of its own, as above
+            brng = np.random.default_rng([int(seed), 0xBA3F])
+            if brng.random() < 0.5:
+                bamf = BAM_FILTERS[int(brng.integers(0, len(BAM_FILTERS)))]
+                desc += ", BAM read files, " + " ".join(bamf[0])
         for i in range(n_reads_samples):
             who = int(rng.integers(0, n_samples))
             haps = synth.sample_haplotypes(ref, variants, gts, who, vploidy)
@@ -139,10 +175,15 @@ def case(seed):
             fq = [dress(f, rng) for f in fq]
             cfg += f"ind{i} " + " ".join(fq) + "\n"
             if sub: cfg_kept += f"ind{i} " + " ".join(filtered(f, *sub) for f in fq) + "\n"
+            if bamf:
+                pairs_ = [as_bam(f, brng, bamf[1]) for f in fq]
+                cfg = cfg[:cfg.rindex(f"ind{i} ")] + f"ind{i} " + " ".join(b for b, _ in pairs_) + "\n"
+                cfg_kept += f"ind{i} " + " ".join(t for _, t in pairs_) + "\n"
         outs, codes = {}, {}
         for name, exe, more in (("native", tc.CLI, ["--gpu", "0"]), ("cpu", tc.REF, [])):
             d = os.path.join(work, name); os.makedirs(d)
-            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if sub and name == "cpu" else cfg)
+            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if (sub or bamf) and name == "cpu" else cfg)
+            if bamf and name == "native": more = more + bamf[0]
             if sub and name == "native": more = more + ["--subsample", repr(sub[0]), "--subsample-seed", str(sub[1])]
             try:
                 r = subprocess.run([exe, "genotype", "--load-graph", graphs["cpu"], "-s", "samples.cfg", "-t", "6"] + gopts + more, cwd=d, capture_output=True, text=True, env=tc.ENV, timeout=150)
@@ -173,6 +214,7 @@ if __name__ == "__main__":
         if a == "--max-vcf-samples": MAX_VCF_SAMPLES = int(sys.argv[i + 1])
         if a == "--only-wide-ploidy": ONLY_WIDE_PLOIDY = True
         if a == "--subsample": SUBSAMPLE = True
+        if a == "--bam-filter": BAM_FILTER = True
     bad = passed_over = 0
     for s in range(first, first + n):
         t0 = time.time()

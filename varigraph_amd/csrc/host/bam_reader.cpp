@@ -8,6 +8,18 @@ namespace vgh {
 namespace {
 uint32_t le32(const unsigned char* p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
+// a record's bytes for bam_filter_verdict: offsets from its block_size field
+struct RecordBytes {
+    const unsigned char* r;
+    uint32_t u8(size_t p) const { return r[p]; }
+    uint32_t u32(size_t p) const { return le32(r + p); }
+    size_t find_nul(size_t p, size_t end) const
+    {
+        const void* z = memchr(r + p, 0, end - p);
+        return z ? (size_t)(static_cast<const unsigned char*>(z) - r) : end;
+    }
+};
+
 // bytes already taken from a source, then the rest of it
 class PrefixSource final : public ByteSource {
 public:
@@ -124,9 +136,14 @@ long BamReader::next()
         if (l_rn == 0) bad(at, "l_read_name is 0");
         if (32ull + l_rn + 4ull * n_cig + (l_seq + 1ull) / 2 + l_seq > bs) bad(at, "fields longer than block_size");
         if (r[36 + l_rn - 1] != 0) bad(at, "read name not NUL-terminated");
+        // the rule of vgmi_bam_filter.h (with every parameter at its default: flag & 0x900 == 0 and l_seq > 0)
+        const int verdict = bam_filter_verdict(filt_, RecordBytes{r}, (size_t)0, bs, l_rn, (uint32_t)r[13], n_cig, flag, l_seq, (double*)nullptr);
+        if (verdict == BAM_FILTER_FAULT) bad(at, "auxiliary fields");
         pos_ += 4 + (size_t)bs;
         off_ += 4 + (uint64_t)bs;
-        if ((flag & 0x900u) || l_seq == 0) continue;
+        ++records_;
+        if (verdict != BAM_FILTER_READ) continue;
+        ++reads_;
         if (!rule_.keep(number_++)) continue;
         const unsigned char* s = r + 36 + l_rn + 4 * (size_t)n_cig;
         seq_.resize(l_seq);

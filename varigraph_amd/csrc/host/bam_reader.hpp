@@ -2,7 +2,7 @@
 // (vgmi_fastq_open_bam).  It takes the stream where the device cannot (a record it stops at, a damaged member, a pipe), it is the
 // reader of the host-parse path (even k), and it is the yardstick of the device kernels (vgmi_bam.hip).
 //   reads     records with flag & 0x900 == 0 (no secondary, no supplementary alignment) and l_seq > 0 -- what `samtools fastq`
-//             writes by default; QC-fail, duplicate and unmapped records are reads too
+//             writes by default; QC-fail, duplicate and unmapped records are reads too.  filter() configures the rule.
 //   sequence  the 4-bit SEQ field through "=ACMGRSVTWYHKDBN", as stored (no reverse complement: the k-mers are canonical)
 // A record that is not valid throws "'<path>': not a valid BAM record at decompressed byte N (<what>)", N = its first byte.
 #pragma once
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "byte_source.hpp"
+#include "../vgmi_bam_filter.h"
 #include "../vgmi_subsample.h"
 
 namespace vgh {
@@ -36,6 +37,12 @@ public:
         number_ = first_number;
     }
     uint64_t next_number() const { return number_; }
+    // The read filter (vgmi_bam_filter.h; on == 0: the default above): from here on next() applies the configured rule in the default's
+    // place, in front of subsampling.  A record whose auxiliary fields cannot be walked throws as the invalid record it is, "(auxiliary
+    // fields)".  records() / reads(): valid records examined since, and the reads among them (before subsampling).
+    void filter(const BamFilterParams& f) { filt_ = f; }
+    uint64_t records() const { return records_; }
+    uint64_t reads() const { return reads_; }
     const std::string& seq() const { return seq_; }
     const std::string& qual() const { return qual_; }   // the record's QUAL bytes as stored (l_seq of them; QUAL[0] == 0xff: none stored)
     // Minimum base quality q (the rule of vgmi_fastq_set_min_quality): base i of seq() becomes 'N' where QUAL[i] < q, in record order;
@@ -56,6 +63,8 @@ private:
     std::string seq_, qual_;
     SubsampleRule rule_;
     uint64_t number_ = 0;
+    BamFilterParams filt_ = bam_filter_params();
+    uint64_t records_ = 0, reads_ = 0;
 };
 
 // the bytes of `path` as ByteSource::open delivers them; is_bam: block gzip whose text starts with "BAM\1" (decided from content)

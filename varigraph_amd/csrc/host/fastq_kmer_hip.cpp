@@ -15,6 +15,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <thread>
+#include <type_traits>
 
 #include "bam_reader.hpp"
 #include "fast_inflate.hpp"
@@ -32,16 +33,54 @@ struct Block {
     uint64_t masked = 0;
 };
 
-// what a file's readers apply besides parsing: the minimum base quality (0: off) and the subsampling rule (fraction 1: off)
+// what a file's readers apply besides parsing: the minimum base quality (0: off), the subsampling rule (fraction 1: off) and the
+// read filter of BAM files (on == 0: the default)
 struct ReadOpts {
     uint32_t min_q = 0;
     SubsampleRule sub;
+    BamFilterParams filt = bam_filter_params();
 };
 
 struct DeviceFileResult {
     uint64_t n_reads = 0, read_base = 0, masked = 0;
     uint64_t seen = 0;      // the file's reads, numbered by the device and the host reader together; n_reads of them were kept
+    uint64_t bam_records = 0, bam_reads = 0;      // with a read filter, a BAM file: records examined and the reads among them, device and host reader together
+    bool bam = false;
 };
+
+// the options a filter was made of, as the command line spells them
+std::string filter_text(const BamFilterParams& f)
+{
+    char buf[160];
+    std::string t;
+    if (f.exclude != 0x900u) std::snprintf(buf, sizeof buf, "--bam-exclude-flags 0x%X", f.exclude), t += buf;
+    if (f.require) std::snprintf(buf, sizeof buf, "%s--bam-require-flags 0x%X", t.empty() ? "" : " ", f.require), t += buf;
+    if (f.min_mapq) std::snprintf(buf, sizeof buf, "%s--bam-min-mapq %u", t.empty() ? "" : " ", f.min_mapq), t += buf;
+    if (f.tag) std::snprintf(buf, sizeof buf, "%s--bam-min-tag %c%c:%g", t.empty() ? "" : " ", (char)(f.tag & 0xFF), (char)(f.tag >> 8 & 0xFF), f.min_value), t += buf;
+    return t;
+}
+
+// VGH_TIMING: what the read filter did to one BAM file (nothing is printed without the options)
+void report_filter(const std::string& path, uint64_t records, uint64_t reads, const BamFilterParams& f)
+{
+    if (f.on && std::getenv("VGH_TIMING"))
+        std::fprintf(stderr, "[varigraph-mi] '%s': %llu of %llu BAM records are reads (%s)\n", path.c_str(), (unsigned long long)reads,
+                     (unsigned long long)records, filter_text(f).c_str());
+}
+
+// the filter goes to a BAM reader alone; FASTA/Q records are untouched
+template <class Reader>
+void set_filter(Reader& rd, const ReadOpts& o)
+{
+    if constexpr (std::is_same_v<Reader, BamReader>)
+        if (o.filt.on) rd.filter(o.filt);
+}
+template <class Reader>
+void add_filter_counts(const Reader& rd, const ReadOpts& o, uint64_t& records, uint64_t& reads)
+{
+    if constexpr (std::is_same_v<Reader, BamReader>)
+        if (o.filt.on) records += rd.records(), reads += rd.reads();
+}
 
 // VGH_TIMING: what subsampling did to one file (nothing is printed without the option)
 void report_subsample(const std::string& path, uint64_t seen, uint64_t kept, const SubsampleRule& sub)
@@ -66,12 +105,13 @@ struct Channel {  // parser threads -> submitting thread
     size_t producers = 0;
     std::string error;
     uint64_t seen = 0;      // reads the finished parsers numbered (all of them without subsampling)
+    uint64_t bam_records = 0, bam_reads = 0;      // with a read filter: the BAM files' records and the reads among them
 };
 
 void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads, const ReadOpts o)
 {
     const uint32_t min_q = o.min_q;
-    uint64_t file_masked = 0, file_reads = 0, file_seen = 0;
+    uint64_t file_masked = 0, file_reads = 0, file_seen = 0, bam_records = 0, bam_reads = 0;
     auto grab = [&]() {
         std::unique_lock<std::mutex> lk(ch.mu);
         ch.cv_free.wait(lk, [&] { return !ch.free_list.empty(); });
@@ -91,6 +131,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
     auto run = [&](auto& rd) {
         std::unique_ptr<Block> cur = grab();
         if (o.sub.on) rd.subsample(o.sub, 0);      // the whole file through this reader: its reads are numbered from 0
+        set_filter(rd, o);
         while (rd.next() >= 0) {  // stops at EOF (-1) and at the first truncated record (-2)
             const uint64_t masked = min_q ? rd.mask_below(min_q) : 0;
             const std::string& s = rd.seq();
@@ -111,6 +152,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
             ++file_reads;
         }
         file_seen = o.sub.on ? rd.next_number() : file_reads;
+        add_filter_counts(rd, o, bam_records, bam_reads);
         if (cur->n_reads) push(std::move(cur));
         else {
             std::lock_guard<std::mutex> lk(ch.mu);
@@ -129,8 +171,11 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         }
         report_masked(path, file_masked, min_q);
         report_subsample(path, file_seen, file_reads, o.sub);
+        if (is_bam) report_filter(path, bam_records, bam_reads, o.filt);
         std::lock_guard<std::mutex> lk(ch.mu);
         ch.seen += file_seen;
+        ch.bam_records += bam_records;
+        ch.bam_reads += bam_reads;
     } catch (const std::exception& e) {
         std::lock_guard<std::mutex> lk(ch.mu);
         if (ch.error.empty()) ch.error = e.what();
@@ -150,6 +195,8 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
     const uint32_t min_q = o.min_q;
     uint64_t &n_reads = res.n_reads, &read_base = res.read_base, &masked = res.masked;
     if (o.sub.on) rd.subsample(o.sub, res.seen);      // the device's n_seen (0 where the device took nothing): one numbering per file
+    set_filter(rd, o);
+    if (std::is_same_v<Reader, BamReader>) res.bam = true;
     std::vector<char> block;
     block.reserve(block_bytes + 1024);
     size_t in_block = 0;
@@ -174,6 +221,7 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
     }
     flush();
     res.seen = o.sub.on ? rd.next_number() : n_reads;
+    add_filter_counts(rd, o, res.bam_records, res.bam_reads);
 }
 
 // plain file: `threads` readers fill one pinned buffer side by side (a single read(2) stream moves 3-6 GB/s, the link
@@ -324,6 +372,16 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
         throw std::runtime_error(why);
     }
+    const bool filtered = bam && o.filt.on;
+    if (filtered) {
+        const char tag[2] = {(char)(o.filt.tag & 0xFF), (char)(o.filt.tag >> 8 & 0xFF)};
+        if (vgmi_fastq_set_bam_filter(fq, o.filt.exclude, o.filt.require, o.filt.min_mapq, o.filt.tag ? tag : nullptr, o.filt.min_value) != VGMI_OK) {
+            const std::string why = vgmi_last_error(ctx);
+            (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+            throw std::runtime_error(why);
+        }
+    }
+    res.bam = bam;
     uint64_t n_rec = 0, n_bases = 0, consumed = 0, dev_seen = 0, dev_kept = 0;
     int stopped = 0;
     std::vector<char> tail(1u << 20);
@@ -336,6 +394,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         if (bgzf && vgmi_fastq_bgzf_status(fq, &inflate_failed, &comp_good, nullptr) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         if (min_q && vgmi_fastq_masked_bases(fq, &res.masked) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         if (o.sub.on && vgmi_fastq_subsample_stats(fq, &dev_seen, &dev_kept) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+        if (filtered && vgmi_fastq_bam_filter_stats(fq, &res.bam_records, &res.bam_reads) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         closed = true;
         if (vgmi_fastq_close(fq, &n_rec, &n_bases, &consumed, &stopped, tail.data(), tail.size(), &tail_len) != VGMI_OK)
             throw std::runtime_error(vgmi_last_error(ctx));
@@ -515,9 +574,28 @@ void FastqKmerHip::count_files(const uint32_t min_q, uint64_t& masked)
 
 void FastqKmerHip::count_files_sampled(const uint32_t min_q, const SubsampleRule& sub, uint64_t& masked, uint64_t& seen)
 {
+    uint64_t records = 0, reads = 0;
+    count_files_filtered(min_q, sub, bam_filter_params(), masked, seen, records, reads);
+}
+
+FastqKmerHipF::FastqKmerHipF(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads,
+                             uint32_t min_base_quality, double fraction, uint64_t seed, const BamFilterParams& filter, size_t block_bytes)
+    : FastqKmerHip(ctx, fastqFileNameVec, kmerLen, threads, block_bytes), min_q_(min_base_quality), filt_(filter)
+{
+    if (min_q_ > 93) throw std::runtime_error("minimum base quality " + std::to_string(min_q_) + " is out of range (0..93, Phred+33)");
+    if (!subsample_fraction_valid(fraction))
+        throw std::runtime_error("subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)");
+    rule_ = SubsampleRule(fraction, seed);
+}
+
+void FastqKmerHip::count_files_filtered(const uint32_t min_q, const SubsampleRule& sub, const BamFilterParams& filt, uint64_t& masked,
+                                        uint64_t& seen, uint64_t& bam_records, uint64_t& bam_reads)
+{
     ReadOpts o;
     o.min_q = min_q;
     o.sub = sub;
+    o.filt = filt;
+    bam_records = bam_reads = 0;
     if (files_.empty()) throw std::runtime_error("Parameter error: -f");  // src/fastq_kmer.cpp:42-45
     uint32_t k_tab = 0;
     if (vgmi_table_info(ctx_, nullptr, &k_tab, nullptr, nullptr) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx_));
@@ -545,7 +623,10 @@ void FastqKmerHip::count_files_sampled(const uint32_t min_q, const SubsampleRule
                     const DeviceFileResult r = device_file(ctx_, files_[i], block_bytes_, io_threads, submit_mu, o);
                     report_masked(files_[i], r.masked, min_q);
                     report_subsample(files_[i], r.seen, r.n_reads, o.sub);
+                    if (r.bam) report_filter(files_[i], r.bam_records, r.bam_reads, o.filt);
                     std::lock_guard<std::mutex> lk(res_mu);
+                    bam_records += r.bam_records;
+                    bam_reads += r.bam_reads;
                     mReadBase += r.read_base;
                     mReadNum += r.n_reads;
                     masked += r.masked;
@@ -614,6 +695,8 @@ void FastqKmerHip::count_files_sampled(const uint32_t min_q, const SubsampleRule
     for (auto& t : workers) t.join();
     if (!err.empty()) throw std::runtime_error(err);
     seen = ch.seen;
+    bam_records = ch.bam_records;
+    bam_reads = ch.bam_reads;
 }
 
 void FastqKmerHip::fetch(uint8_t* cov, uint8_t* cov_node, uint64_t* hist256)

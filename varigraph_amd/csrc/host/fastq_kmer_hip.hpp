@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../vgmi_bam_filter.h"
 #include "../vgmi_subsample.h"
 
 struct vgmi_ctx;
@@ -47,6 +48,9 @@ protected:
     void count_files(uint32_t min_base_quality, uint64_t& masked_bases);
     // ... and with a subsampling rule (off: count_files); reads_seen gets the files' reads, of which mReadNum were kept and counted
     void count_files_sampled(uint32_t min_base_quality, const SubsampleRule& sub, uint64_t& masked_bases, uint64_t& reads_seen);
+    // ... and with a read filter for the BAM files (on == 0: count_files_sampled); bam_records / bam_reads get their records and the reads among them
+    void count_files_filtered(uint32_t min_base_quality, const SubsampleRule& sub, const BamFilterParams& filter, uint64_t& masked_bases,
+                              uint64_t& reads_seen, uint64_t& bam_records, uint64_t& bam_reads);
 
 private:
     vgmi_ctx* ctx_;
@@ -97,6 +101,29 @@ public:
 private:
     uint32_t min_q_;
     SubsampleRule rule_;
+};
+
+// FastqKmerHipS with a read filter for BAM files (genotype --bam-exclude-flags / --bam-require-flags / --bam-min-mapq / --bam-min-tag;
+// vgmi_bam_filter.h has the rule): a record the filter drops is not a read, on the device and wherever the host decoder serves;
+// subsampling numbers the reads that passed.  FASTQ and FASTA files are untouched.  filter.on == 0 counts what FastqKmerHipS counts.  A
+// class of its own for FastqKmerHipQ's reason.
+class FastqKmerHipF : public FastqKmerHip {
+public:
+    uint64_t mMaskedBases = 0;  // bases of the kept reads counted as 'N' for their quality
+    uint64_t mReadsSeen = 0;    // the files' reads, kept or not (mReadNum: the kept ones)
+    uint64_t mBamRecords = 0;   // with a filter: the BAM files' valid records ...
+    uint64_t mBamReads = 0;     // ... and the reads among them (before subsampling)
+
+    // throws std::runtime_error for min_base_quality > 93 and for a fraction that is NaN, <= 0 or > 1; filter: bam_filter_params of valid parameters
+    FastqKmerHipF(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads, uint32_t min_base_quality,
+                  double fraction, uint64_t seed, const BamFilterParams& filter, size_t block_bytes = 32u << 20);
+
+    void build_fastq_index_filtered() { count_files_filtered(min_q_, rule_, filt_, mMaskedBases, mReadsSeen, mBamRecords, mBamReads); }
+
+private:
+    uint32_t min_q_;
+    SubsampleRule rule_;
+    BamFilterParams filt_;
 };
 
 // What the device path makes of an input file, decided from its first bytes alone (no device involved): the container by the

@@ -46,6 +46,12 @@ struct Options {
     bool procs = false;     // --procs: one PROCESS per device of --gpus, the table image handed on by one RCCL broadcast
     double subsample = 1.0;             // --subsample: the fraction of every file's reads that is kept and counted (1: off); the ranks of --procs inherit both
     unsigned long long subsample_seed = 11;   // --subsample-seed
+    // the read filter of BAM files (vgmi_bam_filter.h); the ranks of --procs inherit all four
+    long long bam_exclude = 0x900;      // --bam-exclude-flags
+    long long bam_require = 0;          // --bam-require-flags
+    long long bam_min_mapq = 0;         // --bam-min-mapq
+    std::string bam_tag;                // --bam-min-tag TAG:VALUE (empty: none)
+    double bam_tag_value = 0.0;
     int min_base_quality = 0;   // --min-base-quality: bases of FASTQ / BAM reads below it are counted as N (0: off); the ranks of --procs inherit it
 };
 
@@ -77,6 +83,14 @@ void usage(const char* argv0)
               << "                           file alone: the files of a pair keep the same reads (the mates of an interleaved BAM have\n"
               << "                           different numbers); the depth statistics are those of the kept reads, 0 < FLOAT <= 1 [1: off]\n"
               << "    --subsample-seed INT   seed of --subsample, 0 to 2^64-1 [11]\n"
+              << "    --bam-exclude-flags INT  a BAM record with any of these flag bits is not a read; decimal or 0x hex, 0-65535. The value\n"
+              << "                           REPLACES the default (as samtools fastq -F): 0xD00 adds duplicates, 0xF00 QC failures as well,\n"
+              << "                           a value without 0x900 lets secondary and supplementary records in [0x900]\n"
+              << "    --bam-require-flags INT  a BAM record is a read only with all of these flag bits, 0-65535 [0]\n"
+              << "    --bam-min-mapq  INT    a BAM record is a read only with MAPQ >= INT, 0-255; 255 passes, and an unmapped record's\n"
+              << "                           MAPQ 0 does not pass a positive bound: unaligned BAM loses every read [0]\n"
+              << "    --bam-min-tag   TAG:VALUE  a BAM record is a read only if its first TAG field is numeric and >= VALUE, e.g. rq:0.99\n"
+              << "                           or qs:10 (samtools view -e '[rq]>=0.99'); a record without the tag is not a read [none]\n"
               << "    --gpu           INT    device ordinal [0]\n"
               << "    --gpus          LIST   several devices, e.g. 0,1,2,3: samples are counted on them in parallel\n"
               << "    --procs                one process per device of --gpus (samples dealt round robin, -t shared out); the table is\n"
@@ -112,6 +126,19 @@ unsigned long long opt_u64(const char* name, const char* v)
     try {
         if (v[0] == '-') throw std::invalid_argument(v);
         return std::stoull(v);
+    } catch (const std::exception&) {
+        die(std::string("Parameter error: ") + name + ". '" + v + "' is not a non-negative integer.");
+    }
+}
+// decimal or 0x hex, nothing behind the digits
+long long opt_flags(const char* name, const char* v)
+{
+    try {
+        size_t used = 0;
+        if (v[0] == '-' || v[0] == '+') throw std::invalid_argument(v);
+        const long long r = std::stoll(v, &used, v[0] == '0' && (v[1] == 'x' || v[1] == 'X') ? 16 : 10);
+        if (used == 0 || v[used]) throw std::invalid_argument(v);
+        return r;
     } catch (const std::exception&) {
         die(std::string("Parameter error: ") + name + ". '" + v + "' is not a non-negative integer.");
     }
@@ -182,6 +209,8 @@ int main_genotype(int argc, char** argv)
         {"threads", required_argument, 0, 't'},    {"help", no_argument, 0, 'h'},
         {"procs", no_argument, 0, 10},             {"min-base-quality", required_argument, 0, 11},
         {"subsample", required_argument, 0, 12},   {"subsample-seed", required_argument, 0, 13},
+        {"bam-exclude-flags", required_argument, 0, 14}, {"bam-require-flags", required_argument, 0, 15},
+        {"bam-min-mapq", required_argument, 0, 16}, {"bam-min-tag", required_argument, 0, 17},
         {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -212,6 +241,17 @@ int main_genotype(int argc, char** argv)
         case 11: o.min_base_quality = opt_int("--min-base-quality", optarg); break;
         case 12: o.subsample = opt_double("--subsample", optarg); break;
         case 13: o.subsample_seed = opt_u64("--subsample-seed", optarg); break;
+        case 14: o.bam_exclude = opt_flags("--bam-exclude-flags", optarg); break;
+        case 15: o.bam_require = opt_flags("--bam-require-flags", optarg); break;
+        case 16: o.bam_min_mapq = opt_flags("--bam-min-mapq", optarg); break;
+        case 17: {
+            const std::string a = optarg;
+            if (a.size() < 4 || a[2] != ':' || !vgh::bam_filter_tag_valid(a.c_str()))
+                die("Parameter error: --bam-min-tag. Expected TAG:VALUE, the tag a letter followed by a letter or digit.");
+            o.bam_tag = a.substr(0, 2);
+            o.bam_tag_value = opt_double("--bam-min-tag", a.c_str() + 3);
+            break;
+        }
         case 't': o.hmm.threads = std::max(opt_int("-t", optarg), 1); break;
         case 'D': debug = true; break;
         default: usage(argv[0]); return 1;
@@ -235,6 +275,12 @@ int main_genotype(int argc, char** argv)
     if (o.buffer_mib < 1) die("Parameter error: --buffer. The buffer size must be at least 1 MiB.");
     if (o.min_base_quality < 0 || o.min_base_quality > 93) die("Parameter error: --min-base-quality. The provided value must be between 0 and 93 (inclusive).");
     if (!(o.subsample > 0.0 && o.subsample <= 1.0)) die("Parameter error: --subsample. The provided value must be greater than 0 and at most 1.");
+    if (o.bam_exclude > 65535) die("Parameter error: --bam-exclude-flags. The provided value must be between 0 and 65535 (inclusive).");
+    if (o.bam_require > 65535) die("Parameter error: --bam-require-flags. The provided value must be between 0 and 65535 (inclusive).");
+    if (o.bam_min_mapq > 255) die("Parameter error: --bam-min-mapq. The provided value must be between 0 and 255 (inclusive).");
+    if (o.bam_tag_value != o.bam_tag_value) die("Parameter error: --bam-min-tag. The bound must be a number, not NaN.");
+    const vgh::BamFilterParams bam_filter = vgh::bam_filter_params((uint32_t)o.bam_exclude, (uint32_t)o.bam_require, (uint32_t)o.bam_min_mapq,
+                                                                   o.bam_tag.empty() ? nullptr : o.bam_tag.c_str(), o.bam_tag_value);
 
     const auto t0 = std::chrono::steady_clock::now();
     auto secs = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -647,6 +693,12 @@ int main_genotype(int argc, char** argv)
                 }
                 const auto& [name, files] = samples[s];
                 const double ts = secs();
+                if (bam_filter.on) {
+                    vgh::FastqKmerHipF fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed, bam_filter);
+                    fk.build_fastq_index_filtered();
+                    counted(s, fk, dev_i, ts);
+                    continue;
+                }
                 if (o.subsample < 1.0) {
                     vgh::FastqKmerHipS fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed);
                     fk.build_fastq_index_sampled();

@@ -227,6 +227,46 @@ int64_t vgh_reads_read_all_s(const char* path, uint32_t decode_threads, uint32_t
     }
 }
 
+int64_t vgh_reads_read_all_f(const char* path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag,
+                             double bam_min_value, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases,
+                             uint64_t* next_number, uint64_t* bam_records, uint64_t* bam_reads)
+{
+    if (!path || !block_out || !n_bytes_out) return VGMI_E_INVALID;
+    if (bam_records) *bam_records = 0;
+    if (bam_reads) *bam_reads = 0;
+    if (min_base_quality > 93) {
+        g_err = "minimum base quality " + std::to_string(min_base_quality) + " is out of range (0..93, Phred+33)";
+        return VGMI_E_INVALID;
+    }
+    if (!vgh::subsample_fraction_valid(fraction)) {
+        g_err = "subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)";
+        return VGMI_E_INVALID;
+    }
+    if (const int bad = vgh::bam_filter_invalid(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value)) {
+        g_err = vgh::bam_filter_invalid_text(bad);
+        return VGMI_E_INVALID;
+    }
+    try {
+        const vgh::SubsampleRule rule(fraction, seed);
+        bool is_bam = false;
+        std::unique_ptr<vgh::ByteSource> src = vgh::open_sniffed(path, decode_threads ? decode_threads : 1, is_bam);
+        if (is_bam) {
+            vgh::BamReader rd(std::move(src), path);
+            rd.filter(vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value));
+            const int64_t n = reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
+            if (bam_records) *bam_records = rd.records();
+            if (bam_reads) *bam_reads = rd.reads();
+            return n;
+        }
+        vgh::FastxReader rd(std::move(src));
+        return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return VGMI_E_INVALID;
+    }
+}
+
 int vgh_sniff_input(const char* path, char kind[8], int* first_byte, int* bam, int* fasta)
 {
     if (!path) return VGMI_E_INVALID;
@@ -312,18 +352,37 @@ int vgh_sample_count_s(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fas
                        vgh_sample_stats* stats, uint32_t min_base_quality, double fraction, uint64_t seed, uint64_t* reads_seen,
                        uint64_t* reads_kept, uint64_t* masked_bases)
 {
+    return vgh_sample_count_f(h, ctx, fastq_paths, n_files, threads, sample_ploidy, use_depth, cov_out, cov_node_out, hist_out, stats,
+                              min_base_quality, fraction, seed, 0x900u, 0, 0, nullptr, 0.0, reads_seen, reads_kept, masked_bases, nullptr, nullptr);
+}
+
+int vgh_sample_count_f(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fastq_paths, size_t n_files, uint32_t threads,
+                       uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
+                       vgh_sample_stats* stats, uint32_t min_base_quality, double fraction, uint64_t seed, uint32_t bam_exclude,
+                       uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag, double bam_min_value, uint64_t* reads_seen,
+                       uint64_t* reads_kept, uint64_t* masked_bases, uint64_t* bam_records, uint64_t* bam_reads)
+{
     if (!h || !ctx || (!fastq_paths && n_files)) return VGMI_E_INVALID;
     if (masked_bases) *masked_bases = 0;
     if (reads_seen) *reads_seen = 0;
     if (reads_kept) *reads_kept = 0;
+    if (bam_records) *bam_records = 0;
+    if (bam_reads) *bam_reads = 0;
+    if (const int bad = vgh::bam_filter_invalid(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value)) {
+        g_err = vgh::bam_filter_invalid_text(bad);
+        return VGMI_E_INVALID;
+    }
     try {
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<std::string> files(fastq_paths, fastq_paths + n_files);
-        vgh::FastqKmerHipS fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed);
-        fk.build_fastq_index_sampled();
+        vgh::FastqKmerHipF fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed,
+                              vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value));
+        fk.build_fastq_index_filtered();
         if (masked_bases) *masked_bases = fk.mMaskedBases;
         if (reads_seen) *reads_seen = fk.mReadsSeen;
         if (reads_kept) *reads_kept = fk.mReadNum;
+        if (bam_records) *bam_records = fk.mBamRecords;
+        if (bam_reads) *bam_reads = fk.mBamReads;
         uint64_t hist[256];
         fk.fetch(cov_out, cov_node_out, hist);
         if (hist_out) memcpy(hist_out, hist, sizeof hist);

@@ -2,6 +2,7 @@
 // inflated by vgmi_inflate.hip, ordinary gzip by vgmi_gunzip.hip
 #include "vgmi_ctx.h"
 
+#include "vgmi_bam_filter.h"
 #include "vgmi_subsample.h"
 
 extern "C" {
@@ -64,6 +65,8 @@ struct vgmi_fastq {
     SubParams sub{};
     double sub_fraction = 1.0;
     unsigned long long* d_fa_sub = nullptr;
+    // the read filter of a BAM stream (vgmi_fastq_set_bam_filter): on == 0 = the default rule; fixed once bytes have been committed
+    vgh::BamFilterParams filt{};
 };
 
 namespace {
@@ -132,6 +135,7 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->committed = false;
             r->sub = SubParams{};
             r->sub_fraction = 1.0;
+            r->filt = vgh::BamFilterParams{};
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -512,6 +516,7 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
         bb.n_ref = f->n_ref;
         bb.min_qual = f->min_quality;
         bb.sub = f->sub;
+        bb.filt = f->filt;
         HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
         int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
@@ -988,6 +993,32 @@ int vgmi_fastq_subsample_stats(vgmi_fastq* f, uint64_t* seen, uint64_t* kept)
     HIPCHK(c, hipMemcpy(&st, f->d_state, sizeof st, hipMemcpyDeviceToHost));
     *kept = st.n_records;
     *seen = f->sub.on ? st.n_seen : st.n_records;      // off: every read the device accepted is kept, and nothing numbers them
+    return VGMI_OK;
+}
+
+int vgmi_fastq_set_bam_filter(vgmi_fastq* f, uint32_t exclude, uint32_t require, uint32_t min_mapq, const char* tag, double min_value)
+{
+    if (!f) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    if (const int bad = vgh::bam_filter_invalid(exclude, require, min_mapq, tag, min_value)) return fail(c, VGMI_E_INVALID, vgh::bam_filter_invalid_text(bad));
+    if (f->committed) return fail(c, VGMI_E_STATE, "the BAM read filter is set before the stream's first commit");
+    // all defaults: off, the stream that never called this; FASTQ and FASTA text has no records to filter
+    f->filt = f->bam ? vgh::bam_filter_params(exclude, require, min_mapq, tag, min_value) : vgh::BamFilterParams{};
+    return VGMI_OK;
+}
+
+int vgmi_fastq_bam_filter_stats(vgmi_fastq* f, uint64_t* records, uint64_t* reads)
+{
+    if (!f || !records || !reads) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    *records = *reads = 0;
+    if (!f->filt.on || !f->d_bam) return fail(c, VGMI_E_STATE, "the stream has no BAM read filter");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(f->stream));
+    BamState bs{};
+    HIPCHK(c, hipMemcpy(&bs, f->d_bam, sizeof bs, hipMemcpyDeviceToHost));
+    *records = bs.tot_records;
+    *reads = bs.tot_reads;
     return VGMI_OK;
 }
 

@@ -25,9 +25,13 @@
 // With subsampling (BamBuffers::sub; vgmi_fastq_set_subsample) a read's number in the file is FqState::n_seen + its rank among the
 // chain's reads: between B6 and B7, bam_rank_kernel scans the reads (B7's two phases) and turns rec_bytes of those the rule drops
 // to 0, which B7 and B8 pass over as they pass over the records the filter drops; B9 is bam_finish_sub_kernel.
+// With a configured read filter (BamBuffers::filt; vgmi_fastq_set_bam_filter, the rule in vgmi_bam_filter.h) B6 is
+// bam_keep_filter_kernel, with a tag bound bam_cut_kernel ends the chain in front of a record whose auxiliary fields cannot be walked,
+// and B9 is bam_finish_filter_kernel / bam_finish_filter_sub_kernel; the kernels between run on the rec_bytes these leave.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_bam_filter.h"
 #include "vgmi_subsample.h"
 #include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
@@ -429,6 +433,160 @@ __global__ void bam_finish_sub_kernel(const uint8_t* raw, FqState* st, BamState*
     st->tail_len = tail;
 }
 
+// ---- the configured read filter, off the default path ------------------------------------------------------------------------------
+// a record's bytes for the rule of vgmi_bam_filter.h: offsets in the raw buffer, dwords by two aligned loads and a funnel shift, the
+// NUL of a Z / H value by aligned dwords (the bytes in front of p are made non-zero; the lowest flagged byte of the zero-byte test
+// is exact).  Every load lies below `end` rounded up to a dword plus one dword: inside the raw buffer's slack.
+struct BamBytes {
+    const uint8_t* raw;
+    __device__ __forceinline__ uint32_t u8(uint32_t p) const { return raw[p]; }
+    __device__ __forceinline__ uint32_t u32(uint32_t p) const { return bam_ld32(raw, p); }
+    __device__ __forceinline__ uint32_t find_nul(uint32_t p, uint32_t end) const
+    {
+        uint32_t a = p & ~3u;
+        uint32_t w = *reinterpret_cast<const uint32_t*>(raw + a) | ((1u << (8u * (p & 3u))) - 1u);
+        for (;;) {
+            const uint32_t z = (w - 0x01010101u) & ~w & 0x80808080u;
+            if (z) {
+                const uint32_t q = a + ((uint32_t)__builtin_ctz(z) >> 3);
+                return q < end ? q : end;
+            }
+            a += 4u;
+            if (a >= end) return end;
+            w = *reinterpret_cast<const uint32_t*>(raw + a);
+        }
+    }
+};
+
+// B6 with a filter set: rec_bytes by bam_filter_verdict, a lane per chain record -- the fixed fields decide most records, a B array is
+// passed over by arithmetic and only a Z / H value is scanned, a dword a step, so a wavefront per record would idle 63 lanes on
+// all but the longest strings.  The chain's records and the reads among them are summed per workgroup; the smallest chain index whose
+// auxiliary walk faulted goes to BamState::first_fault (rare: one atomic per such lane).
+__global__ __launch_bounds__(256) void bam_keep_filter_kernel(const uint8_t* raw, BamState* bs, const uint32_t* cand, const uint32_t* j0,
+                                                               const uint8_t* mark, uint32_t* rec_bytes, uint32_t cap, vgh::BamFilterParams f)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    const BamBytes bytes{raw};
+    uint32_t kept = 0, chain = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint32_t b = 0;
+        if (mark[i]) {
+            const uint32_t o = cand[i];
+            const uint32_t w12 = bam_ld32(raw, o + 12), w16 = bam_ld32(raw, o + 16), l_seq = bam_ld32(raw, o + 20);
+            const int v = vgh::bam_filter_verdict(f, bytes, o, bam_ld32(raw, o), w12 & 0xFFu, (w12 >> 8) & 0xFFu, w16 & 0xFFFFu, w16 >> 16, l_seq,
+                                                  (double*)nullptr);
+            ++chain;
+            if (v == vgh::BAM_FILTER_READ) {
+                b = l_seq + 1;
+                ++kept;
+            } else if (v == vgh::BAM_FILTER_FAULT) {
+                atomicMin(&bs->first_fault, i);
+            }
+            if (j0[i] == n) bs->last = i;
+        }
+        rec_bytes[i] = b;
+    }
+    const uint32_t t = block_reduce_add(kept, sh);
+    const uint32_t c = block_reduce_add(chain, sh);
+    if (threadIdx.x == 0 && t) atomicAdd(&bs->n_kept, t);
+    if (threadIdx.x == 0 && c) atomicAdd(&bs->n_chain, c);
+}
+
+// Behind B6 with a tag bound: the chain is cut at the smallest faulted index.  Chain order is candidate order, so the records at and behind
+// it are the marked candidates i >= first_fault: their rec_bytes become 0 and they leave the sums.  `last` becomes the chain
+// record in front of the fault -- the marked one whose successor it is -- or none where the fault is the chain's first record.
+__global__ __launch_bounds__(256) void bam_cut_kernel(const FqState* st, BamState* bs, const uint32_t* cand, const uint32_t* j0, const uint8_t* mark,
+                                                       uint32_t* rec_bytes, uint32_t cap)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t n = bs->n_cand, ff = bs->first_fault;
+    if (n > cap || ff == BAM_NONE) return;   // (uniform)
+    uint32_t kept = 0, chain = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if (!mark[i]) continue;
+        if (i < ff) {
+            if (j0[i] == ff) bs->last = i;
+            continue;
+        }
+        if (i == ff && cand[i] == st->start) bs->last = BAM_NONE;
+        ++chain;
+        if (rec_bytes[i]) {
+            ++kept;
+            rec_bytes[i] = 0;
+        }
+    }
+    const uint32_t t = block_reduce_add(kept, sh);
+    const uint32_t c = block_reduce_add(chain, sh);
+    if (threadIdx.x == 0 && t) atomicSub(&bs->n_kept, t);
+    if (threadIdx.x == 0 && c) atomicSub(&bs->n_chain, c);
+}
+
+// B9 with a filter set (SUB: and subsampling): a walk fault stops the device at the faulted record's first byte, which is where the
+// cut chain ends -- bam_check would pass that record, its fixed fields are valid.  The stream's totals move on, the per-chunk
+// members of the filter are re-armed.
+template <bool SUB>
+__device__ __forceinline__ void bam_finish_filter(const uint8_t* raw, FqState* st, BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                                  const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max,
+                                                  int32_t n_ref)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    uint32_t reads = 0, kept = 0, chain = 0, packed = 0, chain_end = st->start, tail = 0;
+    if (!st->stopped) {
+        const uint32_t n = bs->n_cand;
+        if (n > cap) {
+            st->stopped = 1;     // more candidates than the arrays hold: nothing of this chunk is taken, the host resumes at its first byte
+        } else {
+            if (bs->last != BAM_NONE) {
+                const uint32_t o = cand[bs->last];
+                chain_end = o + 4u + bam_ld32(raw, o);
+                reads = bs->n_kept;
+                chain = bs->n_chain;
+                kept = SUB ? reads - bs->n_dropped : reads;
+                packed = out_off[n - 1] + rec_bytes[n - 1];
+            }
+            if (bs->first_fault != BAM_NONE) {
+                st->stopped = 1;     // the record at chain_end has auxiliary fields the walk cannot pass: the host names it
+            } else if (chain_end < end) {
+                // what follows the chain: the front of a record the next chunk completes, or something the host must judge
+                uint32_t block_size = 0;
+                const int r = bam_check(raw, chain_end, end, n_ref, &block_size);
+                if (r == 1 && (end - chain_end < 4u || block_size <= tail_max - 4u)) tail = end - chain_end;
+                else st->stopped = 1;     // not a valid record, or one longer than the carry (whole or not: never a candidate)
+            }
+        }
+    }
+    bs->n_dropped = 0;
+    bs->n_chain = 0;
+    bs->first_fault = BAM_NONE;
+    bs->tot_records += chain;
+    bs->tot_reads += reads;
+    st->n_good = kept;
+    st->packed_bytes = packed;
+    if (SUB) st->n_seen += reads;
+    st->n_records += kept;
+    st->n_bases += packed - kept;
+    st->consumed += chain_end - st->start;
+    st->consumed_end = chain_end;
+    st->tail_len = tail;
+}
+
+__global__ void bam_finish_filter_kernel(const uint8_t* raw, FqState* st, BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                         const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max,
+                                         int32_t n_ref)
+{
+    bam_finish_filter<false>(raw, st, bs, cand, rec_bytes, out_off, n_new, n_new_dev, cap, tail_max, n_ref);
+}
+
+__global__ void bam_finish_filter_sub_kernel(const uint8_t* raw, FqState* st, BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                             const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max,
+                                             int32_t n_ref)
+{
+    bam_finish_filter<true>(raw, st, bs, cand, rec_bytes, out_off, n_new, n_new_dev, cap, tail_max, n_ref);
+}
+
 // B10: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(256) void bam_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, BamState* bs, uint32_t tail_max)
 {
@@ -449,6 +607,7 @@ __global__ void bam_init_kernel(BamState* bs, unsigned long long header_bytes)
     *bs = BamState{};
     bs->hdr_left = header_bytes;
     bs->last = BAM_NONE;
+    bs->first_fault = BAM_NONE;
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
@@ -478,7 +637,13 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_jump_kernel, dim3(grid), dim3(256), 0, s, b.bam, src, dst, b.mark, r, b.cap_cand);
         src = dst;
     }
-    hipLaunchKernelGGL(bam_keep_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
+    if (b.filt.on) {
+        hipLaunchKernelGGL(bam_keep_filter_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand, b.filt);
+        if (b.filt.tag)      // (without a tag bound no auxiliary byte is read: nothing can fault)
+            hipLaunchKernelGGL(bam_cut_kernel, dim3(grid), dim3(256), 0, s, b.state, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
+    } else {
+        hipLaunchKernelGGL(bam_keep_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
+    }
     if (b.sub.on) {
         hipLaunchKernelGGL(bam_rank_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.bam, b.block_sum, 0, b.cap_cand, b.sub.seed,
                            b.sub.threshold);
@@ -495,7 +660,13 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_decode_mask_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed,
                            b.cap_cand, b.min_qual);
     else hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
-    if (b.sub.on)
+    if (b.filt.on && b.sub.on)
+        hipLaunchKernelGGL(bam_finish_filter_sub_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
+                           b.cap_cand, b.tail_max, b.n_ref);
+    else if (b.filt.on)
+        hipLaunchKernelGGL(bam_finish_filter_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
+                           b.cap_cand, b.tail_max, b.n_ref);
+    else if (b.sub.on)
         hipLaunchKernelGGL(bam_finish_sub_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
                            b.cap_cand, b.tail_max, b.n_ref);
     else

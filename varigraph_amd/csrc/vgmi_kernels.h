@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_bam_filter.h"
 #include "vgmi_count_plan.h"
 #include "vgmi_ctable.h"
 #include "vgmi_device.h"
@@ -197,6 +198,11 @@ struct BamState {                      // device-resident, one per open BAM stre
     uint32_t last;                     // per chunk: the last record of the chain from the chunk's start (BAM_NONE: none)
     uint32_t n_kept;                   // per chunk: records of the chain that are read (flag & 0x900 == 0, l_seq > 0)
     uint32_t n_dropped;                // per chunk, subsampling only (0 without it): reads among n_kept that the rule dropped
+    // with a read filter only (BamFilterParams; vgmi_fastq_set_bam_filter), last, so that every other member stays where it was:
+    uint32_t n_chain;                  // per chunk: records of the chain (n_kept: the reads among them, by the configured rule)
+    uint32_t first_fault;              // per chunk: the smallest chain index whose auxiliary walk faulted (BAM_NONE: none)
+    unsigned long long tot_records;    // since the stream was opened: chain records examined in what the device has accepted
+    unsigned long long tot_reads;      // ... and the reads among them (before subsampling)
 };
 struct BamBuffers {
     const uint8_t* raw;                // tail_max bytes of carry area + the chunk
@@ -215,6 +221,7 @@ struct BamBuffers {
     int32_t n_ref;
     uint32_t min_qual;                 // 0: off; else a base whose QUAL byte is below it is decoded as 'N' (a record without QUAL: none)
     SubParams sub;                     // rec_bytes of a dropped read is turned to 0 before the scan
+    vgh::BamFilterParams filt;         // on == 0: flag & 0x900 == 0 and l_seq > 0, by bam_keep_kernel; else bam_keep_filter_kernel's rule
 };
 hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s);
 hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);

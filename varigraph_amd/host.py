@@ -70,6 +70,12 @@ def lib():
     l.vgh_reads_read_all_s.restype = C.c_int64
     l.vgh_reads_read_all_s.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.POINTER(vp),
                                        C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    l.vgh_sample_count_f.restype = C.c_int
+    l.vgh_sample_count_f.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                   C.c_char_p, C.c_double] + [C.POINTER(C.c_uint64)] * 5
+    l.vgh_reads_read_all_f.restype = C.c_int64
+    l.vgh_reads_read_all_f.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_char_p, C.c_double, C.POINTER(vp), C.POINTER(C.c_size_t)] + [C.POINTER(C.c_uint64)] * 5
     l.vgh_reads_read_all_q.restype = C.c_int64
     l.vgh_reads_read_all_q.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]
@@ -162,12 +168,14 @@ class Graph:
         return cov, rb.value
 
     def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True, min_base_quality=0,
-                     subsample=None):
+                     subsample=None, bam_filter=None):
         """FastqKmerHip::build_fastq_index + coverage statistics for one sample.  require_depth=False: a sample too thin
         for the coverage peak (the reference exits with "Failed to retrieve depth information") still returns its
         counters.  min_base_quality: bases of FASTQ / BAM reads whose quality is below it are counted as N (vgh_sample_count_q);
         stats["masked_bases"] = how many, device and host readers together.  subsample=(F, S): a seeded fraction of every file's
-        reads is kept (vgh_sample_count_s); stats then has reads_seen and reads_kept, and n_reads / read_base are the kept reads'."""
+        reads is kept (vgh_sample_count_s); stats then has reads_seen and reads_kept, and n_reads / read_base are the kept reads'.
+        bam_filter=dict(exclude=0x900, require=0, min_mapq=0, tag=None, min_value=0.0), any key optional: the read filter of BAM files
+        (vgh_sample_count_f); stats then has bam_records and bam_reads."""
         i = self.info
         cov = np.empty(i["n_keys"], dtype=np.uint8)
         cov_node = np.empty(i["n_node_entries"], dtype=np.uint8)
@@ -175,7 +183,14 @@ class Graph:
         st = SampleStats()
         arr = (C.c_char_p * len(fastq_paths))(*[os.fsencode(p) for p in fastq_paths])
         masked, seen, kept = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        if subsample is not None:
+        recs, rds = C.c_uint64(), C.c_uint64()
+        if bam_filter is not None:
+            f, fs = bam_filter_args(bam_filter), subsample if subsample is not None else (1.0, 0)
+            rc = self._l.vgh_sample_count_f(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
+                                            vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
+                                            float(fs[0]), int(fs[1]), *f, C.byref(seen), C.byref(kept), C.byref(masked),
+                                            C.byref(recs), C.byref(rds))
+        elif subsample is not None:
             rc = self._l.vgh_sample_count_s(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
                                             vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
                                             float(subsample[0]), int(subsample[1]), C.byref(seen), C.byref(kept), C.byref(masked))
@@ -191,6 +206,8 @@ class Graph:
         stats["masked_bases"] = masked.value
         if subsample is not None:
             stats["reads_seen"], stats["reads_kept"] = seen.value, kept.value
+        if bam_filter is not None:
+            stats["bam_records"], stats["bam_reads"] = recs.value, rds.value
         return cov, cov_node, hist, stats
 
 
@@ -315,6 +332,29 @@ def reads_read_all_s(path, fraction, seed, first_number=0, min_base_quality=0, d
     finally:
         l.vgh_free(p)
     return block, int(cnt), rb.value, mb.value, nx.value
+
+
+def bam_filter_args(bam_filter):
+    """(exclude, require, min_mapq, tag, min_value) of a bam_filter dict as the C entries take them"""
+    tag = bam_filter.get("tag")
+    return (int(bam_filter.get("exclude", 0x900)), int(bam_filter.get("require", 0)), int(bam_filter.get("min_mapq", 0)),
+            None if tag is None else (tag if isinstance(tag, bytes) else tag.encode()), float(bam_filter.get("min_value", 0.0)))
+
+
+def reads_read_all_f(path, bam_filter, fraction=1.0, seed=11, first_number=0, min_base_quality=0, decode_threads=1):
+    """A BAM (or FASTA/Q) file through the host reader with the read filter (vgh_reads_read_all_f): (block, n_kept, read_base,
+    masked_bases, next_number, bam_records, bam_reads).  bam_filter: the dict of Graph.sample_count."""
+    l = lib()
+    p, n, rb, mb, nx, rc, rd = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    cnt = l.vgh_reads_read_all_f(os.fsencode(path), decode_threads, min_base_quality, fraction, seed, first_number, *bam_filter_args(bam_filter),
+                                 C.byref(p), C.byref(n), C.byref(rb), C.byref(mb), C.byref(nx), C.byref(rc), C.byref(rd))
+    if cnt < 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    try:
+        block = _arr(p.value, n.value, np.uint8)
+    finally:
+        l.vgh_free(p)
+    return block, int(cnt), rb.value, mb.value, nx.value, rc.value, rd.value
 
 
 def sniff_input(path):

@@ -83,6 +83,8 @@ def load_library():
         "vgmi_fastq_masked_bases": (i32, [vp, C.POINTER(u64)]),
         "vgmi_fastq_set_subsample": (i32, [vp, C.c_double, u64]),
         "vgmi_fastq_subsample_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "vgmi_fastq_set_bam_filter": (i32, [vp, u32, u32, u32, C.c_char_p, C.c_double]),
+        "vgmi_fastq_bam_filter_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "vgmi_sketch_keys": (i32, [vp, vp, sz, vp, sz, u32, vp]),
         "vgmi_bloom_params": (i32, [u64, C.c_double, C.POINTER(u64), C.POINTER(u32)]),
         "vgmi_bloom_create": (i32, [vp, u64, u32, vp]),
@@ -212,6 +214,7 @@ class Context:
         self.n_node_entries = 0
         self._quality_streams = set()      # open streams on which vgmi_fastq_set_min_quality was called
         self._subsample_streams = set()    # open streams on which vgmi_fastq_set_subsample was called
+        self._filter_streams = set()       # open streams on which vgmi_fastq_set_bam_filter was called
 
     def close(self):
         if getattr(self, "_h", None):
@@ -356,7 +359,7 @@ class Context:
         self._chk(self._l.vgmi_pt_live_check(self._h, out))
         return tuple(int(v) for v in out)
 
-    def fastq_text(self, text, piece=None, min_quality=0, subsample=None, subsample_first=False):
+    def fastq_text(self, text, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None):
         """Device-side FASTQ parser over one stream of file text (bytes), committed in pieces of `piece` bytes (default:
         whole staging buffers).  min_quality: bases whose quality is below it are counted as N (vgmi_fastq_set_min_quality; 0 = off).
         subsample=(F, S): a seeded fraction of the reads is kept (vgmi_fastq_set_subsample); the dict then has n_seen, the reads the
@@ -364,6 +367,7 @@ class Context:
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
         self._set_options(fq, min_quality, subsample, subsample_first)
+        self._set_bam_filter(fq, bam_filter)      # (accepted without effect: the text has no BAM records)
         return self._text_stream(fq, text, piece)
 
     def _set_min_quality(self, fq, min_quality):
@@ -402,6 +406,23 @@ class Context:
                 raise VgmiError(rc, msg)
         self._subsample_streams.add(fq.value)
 
+    def _set_bam_filter(self, fq, bam_filter):
+        """vgmi_fastq_set_bam_filter on a stream just opened; a refusal closes the stream and raises.  None (the default) does not
+        call the C entry at all.  A dict(exclude, require, min_mapq, tag, min_value; any key optional) calls it once, a list of
+        dicts once per dict, in order: the last value set holds."""
+        if bam_filter is None:
+            return
+        for f in [bam_filter] if isinstance(bam_filter, dict) else bam_filter:
+            tag = f.get("tag")
+            tag = None if tag is None else (tag if isinstance(tag, bytes) else tag.encode())
+            rc = self._l.vgmi_fastq_set_bam_filter(fq, f.get("exclude", 0x900), f.get("require", 0), f.get("min_mapq", 0), tag,
+                                                   float(f.get("min_value", 0.0)))
+            if rc:
+                msg = self._l.vgmi_last_error(self._h).decode()
+                self._l.vgmi_fastq_close(fq, None, None, None, None, None, 0, None)
+                raise VgmiError(rc, msg)
+        self._filter_streams.add(fq.value)
+
     def _with_seen(self, fq, res):
         """res, the dict a stream is about to return, with n_seen (vgmi_fastq_subsample_stats) when its setter was called; called
         in front of vgmi_fastq_close.  A stream whose setter was never called is not asked and res stays as it is."""
@@ -411,6 +432,13 @@ class Context:
             ok = self._l.vgmi_fastq_subsample_stats(fq, C.byref(seen), C.byref(kept)) == 0
             res["n_seen"] = seen.value if ok else None
             res["n_kept"] = kept.value if ok else None
+        if fq.value in self._filter_streams:
+            self._filter_streams.discard(fq.value)
+            recs, reads = C.c_uint64(), C.c_uint64()
+            rc = self._l.vgmi_fastq_bam_filter_stats(fq, C.byref(recs), C.byref(reads))
+            res["filter_stats_rc"] = rc      # VGMI_E_STATE: the stream has no filter (every parameter at its default, or not a BAM stream)
+            res["bam_records"] = recs.value if rc == 0 else None
+            res["bam_reads"] = reads.value if rc == 0 else None
         return res
 
     def _masked_bases(self, fq):
@@ -421,12 +449,13 @@ class Context:
         n = C.c_uint64()
         return n.value if self._l.vgmi_fastq_masked_bases(fq, C.byref(n)) == 0 else None
 
-    def fasta_text(self, text, piece=None, subsample=None):
+    def fasta_text(self, text, piece=None, subsample=None, bam_filter=None):
         """Device-side FASTA parser (vgmi_fastq_open_fasta) over one stream of file text, as fastq_text.  The last record of the text
         is never taken by the device: it comes back as `tail`, from its header line on."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
         self._set_subsample(fq, subsample)
+        self._set_bam_filter(fq, bam_filter)
         return self._text_stream(fq, text, piece)
 
     def _text_stream(self, fq, text, piece):
@@ -467,13 +496,25 @@ class Context:
         self._set_subsample(fq, subsample)
         return self._bgzf_stream(fq, comp, piece)
 
-    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0, subsample=None, subsample_first=False):
+    def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None,
+                 filter_order=0):
         """A BAM file's block-gzip bytes through the device inflate + BAM record kernels (vgmi_fastq_open_bam): header_bytes = the
         header's length in the decompressed stream (magic to the last reference), n_ref its number of references.  Returns the dict of fastq_bgzf; consumed
         counts decompressed bytes, header included."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_bam(self._h, header_bytes, n_ref, C.byref(fq)))
-        self._set_options(fq, min_quality, subsample, subsample_first)
+        # bam_filter: the read filter (vgmi_fastq_set_bam_filter; the dict then has bam_records, bam_reads); filter_order 0 / 1 / 2: that
+        # setter in front of, between or behind the other two
+        if filter_order == 0:
+            self._set_bam_filter(fq, bam_filter)
+        if filter_order == 1:
+            (self._set_subsample if subsample_first else self._set_min_quality)(fq, subsample if subsample_first else min_quality)
+            self._set_bam_filter(fq, bam_filter)
+            (self._set_min_quality if subsample_first else self._set_subsample)(fq, min_quality if subsample_first else subsample)
+        else:
+            self._set_options(fq, min_quality, subsample, subsample_first)
+        if filter_order == 2:
+            self._set_bam_filter(fq, bam_filter)
         return self._bgzf_stream(fq, comp, piece)
 
     def _bgzf_stream(self, fq, comp, piece):
