@@ -106,6 +106,18 @@ int64_t vgh_reads_read_all_f(const char *path, uint32_t decode_threads, uint32_t
                              uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char *bam_tag,
                              double bam_min_value, char **block_out, size_t *n_bytes_out, uint64_t *read_base, uint64_t *masked_bases,
                              uint64_t *next_number, uint64_t *bam_records, uint64_t *bam_reads);
+/* The same with regions for BAM files (condition 5 of the rule, vgmi_fastq_set_bam_regions): bam_regions = a comma-separated list of
+ * NAME, NAME:BEG or NAME:BEG-END (1-based inclusive; an item that is a reference name as a whole is that reference, else it is split
+ * at its last ':'), bam_regions_bed = the path of a BED file (columns 1 to 3, 0-based half-open; empty lines and lines starting with
+ * '#', "track" or "browser" skipped; lines whose name the header lacks skipped), either may be NULL, both are joined; bam_unplaced:
+ * records with refID -1 pass.  Resolved against the file's own header.  Both NULL: vgh_reads_read_all_f.  VGMI_E_INVALID with
+ * "'<path>': reference '<name>' of region '<item>' is not in the header", for a BED line with start >= end or a non-number (the
+ * message names the line), for a list that comes out empty, and for bam_unplaced without regions. */
+int64_t vgh_reads_read_all_r(const char *path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char *bam_tag,
+                             double bam_min_value, const char *bam_regions, const char *bam_regions_bed, int bam_unplaced, char **block_out,
+                             size_t *n_bytes_out, uint64_t *read_base, uint64_t *masked_bases, uint64_t *next_number, uint64_t *bam_records,
+                             uint64_t *bam_reads);
 /* What the device path of vgh_sample_count makes of an input file, from its first bytes (no device involved): kind = "plain" |
  * "gzip" | "bgzf"; first_byte = the first byte of its text (-1: it has none); bam = block gzip whose text starts with "BAM\1";
  * fasta = the text starts with '>' and goes to the device's FASTA parser (VGH_DEVICE_FASTA=0: never).  Any pointer may be NULL. */
@@ -167,6 +179,16 @@ int vgh_sample_count_f(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fas
                        double fraction, uint64_t seed, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq,
                        const char *bam_tag, double bam_min_value, uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases,
                        uint64_t *bam_records, uint64_t *bam_reads);
+/* The same with regions for BAM files (genotype --bam-regions / --bam-regions-file / --bam-regions-unplaced; the grammar:
+ * vgh_reads_read_all_r, the rule: vgmi_fastq_set_bam_regions): resolved against every BAM file's own header, decided on the device
+ * and wherever the host decoder serves.  A record outside the regions is not a read, exactly as one the filter drops.  bam_regions
+ * and bam_regions_bed both NULL: vgh_sample_count_f.  *bam_records, *bam_reads are filled with regions alone too. */
+int vgh_sample_count_r(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fastq_paths, size_t n_files,
+                       uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
+                       uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
+                       double fraction, uint64_t seed, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq,
+                       const char *bam_tag, double bam_min_value, const char *bam_regions, const char *bam_regions_bed, int bam_unplaced,
+                       uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases, uint64_t *bam_records, uint64_t *bam_reads);
 
 /* Coverage statistics alone (Varigraph::kmer_read / cal_ave_cov_kmer): hist = masked coverage histogram
  * (vgmi_counts_finish).  Fills read_depth, hap_kmer_coverage, max_coverage, hom_coverage of *stats; returns

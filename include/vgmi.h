@@ -306,6 +306,19 @@ int vgmi_fastq_set_bam_filter(vgmi_fastq *fq, uint32_t exclude, uint32_t require
 /* Records of the chain examined and the reads among them (before subsampling) in what the device has accepted; waits for the
  * stream.  VGMI_E_STATE on a stream without a filter.  Valid until vgmi_fastq_close. */
 int vgmi_fastq_bam_filter_stats(vgmi_fastq *fq, uint64_t *records, uint64_t *reads);
+/* The regions of a BAM stream: condition 5 of the rule in csrc/vgmi_bam_filter.h, between the MAPQ bound and the tag bound.  n
+ * intervals (ref[i], beg[i], end[i]), 0-based and half-open, 0 <= ref < n_ref of vgmi_fastq_open_bam, 0 <= beg < end <= 2^31, in any
+ * order, overlapping or not: the call sorts and merges them.  A record that passed the flag and MAPQ tests is a read only if
+ * refID >= 0 and [pos, endpos) meets an interval of refID -- endpos = pos + 1 for an unmapped record (flag & 0x4), one without CIGAR
+ * or one whose CIGAR consumes no reference, else pos + the summed lengths of its M D N = X operations, as `samtools view -L` -- or if
+ * refID == -1 and `unplaced` is set.  The tag bound's auxiliary walk runs only for records that passed, so a record the regions drop
+ * cannot stop the stream.  Combines with vgmi_fastq_set_bam_filter in either order; everything said there about dropped records
+ * holds, and vgmi_fastq_bam_filter_stats serves a stream with regions too.  n == 0 makes the stream the one that never called
+ * this; a FASTQ or FASTA stream accepts the call without effect.
+ * Before the stream's first commit only: VGMI_E_STATE afterwards.  VGMI_E_INVALID, each with its own message: a ref outside
+ * [0, n_ref), a beg or an end out of range, more than 2^20 intervals left after merging, unplaced != 0 with n == 0.  The stream
+ * serves on after either, with the list it had. */
+int vgmi_fastq_set_bam_regions(vgmi_fastq *fq, uint32_t n, const int32_t *ref, const int64_t *beg, const int64_t *end, int unplaced);
 
 /* K1 alone: the key every position of a read block emits, for emitter parity tests.
  * keys_out[i] = key of the k-mer ENDING at byte i, or UINT64_MAX when the reference emits nothing

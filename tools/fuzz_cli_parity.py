@@ -2,7 +2,7 @@
 """Drawn end-to-end cases through both CLIs (the unmodified reference, oracle/_ref/varigraph_det, and varigraph-mi) on one GPU box:
 genome size, variant mix, cohort size and ploidy, k, construct mode, reads per sample and every genotype option are drawn from a seed;
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
-  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample] [--bam-filter]
+  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample] [--bam-filter] [--bam-regions]
 --max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from.
 --max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100, 127, 130, 160 and 255 diploid
 VCF samples, as far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 511 haplotypes, 7 to 64 bytes of haplotype bits
@@ -15,7 +15,14 @@ drawn from a generator of their own behind the case's; varigraph-mi then reads t
 filtered files this script writes with the Python model of the rule (tests/subsample_cases.py): the same VCFs, or both refuse.
 --bam-filter (off by default, and only for cases --subsample left alone) turns the read files of half of the cases into BAM files with
 drawn flags, MAPQ and an rq field, and draws a read filter (DESIGN_INGEST_HMM 4.23): varigraph-mi reads the BAM files with the filter's
-options, the reference the twin FASTQ of the records that pass by the Python model (tests/bam_filter_cases.py)."""
+options, the reference the twin FASTQ of the records that pass by the Python model (tests/bam_filter_cases.py).
+--bam-regions (off by default, and only for cases the two options above left alone) turns the read files of half of the cases into aligned
+BAM files over four references with drawn positions and CIGARs, and draws a region list, a BED file or both, with or without
+--bam-regions-unplaced (DESIGN_INGEST_HMM 4.24): varigraph-mi reads the BAM files with the options, the reference the twin FASTQ of the
+records that pass by the Python model (tests/bam_region_cases.py).
+  fuzz_cli_parity.py --check-bam-regions <first seed> <cases>
+needs no device: the conversion alone -- drawn records, regions and option text -- through the host decoder (vgh_reads_read_all_r)
+against the model's passing records."""
 import gzip, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -113,6 +120,85 @@ def as_bam(path, brng, filt):
     return path + ".bam", bam_py.twin_fastq(path + ".twin.fq", passing)
 
 
+BAM_REGIONS = False      # --bam-regions: a drawn case may get aligned BAM read files and regions (DESIGN_INGEST_HMM 4.24)
+
+
+def draw_regions(rrng, work):
+    """-> (the options, the intervals as the model takes them, unplaced): one whole reference or none, 1 to 40 intervals on the others,
+    as --bam-regions items, as lines of a BED file (with lines the header lacks), or both"""
+    import bam_region_cases as R
+    names = [n.decode() for n, _ in R.REFS]
+    regions, items, lines = [], [], ["# drawn", "chrUn\t5\t50"]
+    whole = int(rrng.integers(-1, len(names)))
+    if whole >= 0:
+        regions.append((whole, 0, R.WHOLE)); items.append(names[whole])
+    for _ in range(int(rrng.integers(1, 41))):
+        ref, beg = int(rrng.integers(0, len(names))), int(rrng.integers(0, 2500))
+        end = beg + int(rrng.integers(1, 200))
+        regions.append((ref, beg, end))
+        if rrng.random() < 0.5: items.append(f"{names[ref]}:{beg + 1}-{end}")
+        else: lines.append(f"{names[ref]}\t{beg}\t{end}")
+    if rrng.random() < 0.2:      # NAME:BEG, to the end
+        ref, beg = int(rrng.integers(0, len(names))), int(rrng.integers(1500, 2500))
+        regions.append((ref, beg, R.WHOLE)); items.append(f"{names[ref]}:{beg + 1}")
+    opts = []
+    if items: opts += ["--bam-regions", ",".join(items)]
+    if len(lines) > 2:
+        bed = os.path.join(work, "regions.bed")
+        open(bed, "w").write("\n".join(lines + ["chrEBV\t1\t2"]) + "\n")
+        opts += ["--bam-regions-file", bed]
+    unplaced = bool(rrng.random() < 0.5)
+    return opts + (["--bam-regions-unplaced"] if unplaced else []), regions, unplaced
+
+
+def as_region_bam(path, rrng, regions, unplaced):
+    """a read file of the case as an aligned BAM with drawn references, positions and CIGARs -> (the BAM, the twin FASTQ of the records
+    that pass the regions, those records)"""
+    import bam_filter_cases as F, bam_py, bam_region_cases as R, quality_mask_cases
+    raw = open(path, "rb").read()
+    text = gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw
+    if not text.endswith(b"\n"): text += b"\n"
+    recs = []
+    for name, seq, qual in quality_mask_cases.records_of(text):
+        q = bytes(min(max(c - 33, 0), 93) for c in qual)
+        if rrng.random() < 0.05:
+            recs.append(bam_py.Rec(name.split()[0], seq.upper(), flag=4, ref=-1, pos=-1, mapq=0, qual=q))
+            continue
+        flag = (0x10 if rrng.random() < 0.5 else 0) | (4 if rrng.random() < 0.05 else 0) | (0x100 if rrng.random() < 0.03 else 0)
+        cigar = [(int(rrng.integers(1, 60)), R.OPS[int(rrng.integers(0, 9))] if rrng.random() < 0.97 else int(rrng.integers(9, 16)))
+                 for _ in range(int(rrng.integers(0, 6)))]
+        recs.append(bam_py.Rec(name.split()[0], seq.upper(), flag=flag, ref=int(rrng.integers(0, len(R.REFS))), pos=int(rrng.integers(-1, 2700)),
+                               mapq=int(rrng.choice((0, 20, 60))), cigar=cigar, qual=q, aux=F.aux(b"NM", "C", 2)))
+    R.write_bam(path + ".bam", recs)
+    passing, _, _, at = R.apply(recs, F.Filter(), regions, unplaced)
+    assert at is None
+    return path + ".bam", bam_py.twin_fastq(path + ".twin.fq", passing), passing
+
+
+def check_bam_regions(seed):
+    """the conversion without a device: a drawn FASTQ file -> as_region_bam -> the host decoder with the drawn options == the passing records"""
+    import bam_py
+    from varigraph_amd import host
+    rrng = np.random.default_rng([int(seed), 0xBA4E])
+    work = tempfile.mkdtemp(prefix="fuzz_regions_")
+    try:
+        fq = os.path.join(work, "r.fq")
+        with open(fq, "wb") as f:
+            for i in range(int(rrng.integers(50, 600))):
+                n = int(rrng.integers(30, 160))
+                f.write(b"@r%d\n" % i + synth._ACGT[rrng.integers(0, 4, size=n)].tobytes() + b"\n+\n" + bytes(rrng.integers(35, 74, size=n, dtype=np.uint8)) + b"\n")
+        opts, regions, unplaced = draw_regions(rrng, work)
+        bam, twin, passing = as_region_bam(fq, rrng, regions, unplaced)
+        arg = lambda o: opts[opts.index(o) + 1] if o in opts else None
+        block, n, rb = host.reads_read_all_r(bam, arg("--bam-regions"), arg("--bam-regions-file"), unplaced)[:3]
+        want = bam_py.reads_block(passing)
+        twin_n = open(twin, "rb").read().count(b"\n") // 4
+        ok = block.tobytes() == want[0] and (n, rb) == want[1:] and twin_n == n
+        return ("identical (%d of the file's reads pass)" % n if ok else "CONVERSION DIFFERS"), f"seed {seed}: {' '.join(opts)}"
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
 def case(seed):
     rng = np.random.default_rng(seed)
     pick = lambda xs: xs[int(rng.integers(0, len(xs)))]
@@ -168,6 +254,12 @@ def case(seed):
             if brng.random() < 0.5:
                 bamf = BAM_FILTERS[int(brng.integers(0, len(BAM_FILTERS)))]
                 desc += ", BAM read files, " + " ".join(bamf[0])
+        regf = None
+        if BAM_REGIONS and sub is None and bamf is None:      # a generator of its own, as above
+            rrng = np.random.default_rng([int(seed), 0xBA4E])
+            if rrng.random() < 0.5:
+                regf = draw_regions(rrng, work)
+                desc += ", aligned BAM read files, " + " ".join(regf[0])
         for i in range(n_reads_samples):
             who = int(rng.integers(0, n_samples))
             haps = synth.sample_haplotypes(ref, variants, gts, who, vploidy)
@@ -179,11 +271,16 @@ def case(seed):
                 pairs_ = [as_bam(f, brng, bamf[1]) for f in fq]
                 cfg = cfg[:cfg.rindex(f"ind{i} ")] + f"ind{i} " + " ".join(b for b, _ in pairs_) + "\n"
                 cfg_kept += f"ind{i} " + " ".join(t for _, t in pairs_) + "\n"
+            if regf:
+                pairs_ = [as_region_bam(f, rrng, regf[1], regf[2])[:2] for f in fq]
+                cfg = cfg[:cfg.rindex(f"ind{i} ")] + f"ind{i} " + " ".join(b for b, _ in pairs_) + "\n"
+                cfg_kept += f"ind{i} " + " ".join(t for _, t in pairs_) + "\n"
         outs, codes = {}, {}
         for name, exe, more in (("native", tc.CLI, ["--gpu", "0"]), ("cpu", tc.REF, [])):
             d = os.path.join(work, name); os.makedirs(d)
-            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if (sub or bamf) and name == "cpu" else cfg)
+            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if (sub or bamf or regf) and name == "cpu" else cfg)
             if bamf and name == "native": more = more + bamf[0]
+            if regf and name == "native": more = more + regf[0]
             if sub and name == "native": more = more + ["--subsample", repr(sub[0]), "--subsample-seed", str(sub[1])]
             try:
                 r = subprocess.run([exe, "genotype", "--load-graph", graphs["cpu"], "-s", "samples.cfg", "-t", "6"] + gopts + more, cwd=d, capture_output=True, text=True, env=tc.ENV, timeout=150)
@@ -207,6 +304,15 @@ def case(seed):
 
 
 if __name__ == "__main__":
+    if sys.argv[1] == "--check-bam-regions":
+        first, n = int(sys.argv[2]), int(sys.argv[3])
+        bad = 0
+        for s in range(first, first + n):
+            verdict, desc = check_bam_regions(s)
+            bad += "DIFFERS" in verdict
+            print(("!! " if "DIFFERS" in verdict else "ok ") + verdict + " -- " + desc[:200], flush=True)
+        print(f"{n} conversions, {bad} differences")
+        sys.exit(1 if bad else 0)
     first, n = int(sys.argv[1]), int(sys.argv[2])
     for i, a in enumerate(sys.argv):
         if a in ("--k", "--genome"): FORCE[a[2:]] = int(sys.argv[i + 1])
@@ -215,6 +321,7 @@ if __name__ == "__main__":
         if a == "--only-wide-ploidy": ONLY_WIDE_PLOIDY = True
         if a == "--subsample": SUBSAMPLE = True
         if a == "--bam-filter": BAM_FILTER = True
+        if a == "--bam-regions": BAM_REGIONS = True
     bad = passed_over = 0
     for s in range(first, first + n):
         t0 = time.time()

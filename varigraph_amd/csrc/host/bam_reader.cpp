@@ -1,7 +1,9 @@
 #include "bam_reader.hpp"
 
 #include <cstring>
+#include <fstream>
 #include <stdexcept>
+#include <unordered_map>
 
 namespace vgh {
 
@@ -78,7 +80,7 @@ bool BamReader::fill(size_t n)
     return true;
 }
 
-BamReader::BamReader(std::unique_ptr<ByteSource> src, const std::string& path) : src_(std::move(src)), path_(path)
+BamReader::BamReader(std::unique_ptr<ByteSource> src, const std::string& path, bool keep_refs) : src_(std::move(src)), path_(path)
 {
     // magic, l_text, text, n_ref, then per reference l_name, name, l_ref
     uint64_t need = 8;
@@ -98,6 +100,11 @@ BamReader::BamReader(std::unique_ptr<ByteSource> src, const std::string& path) :
         const int32_t l_name = (int32_t)le32(buf_.data() + pos_);
         if (l_name < 0) bad(off_, "negative l_name");
         if (!fill(8 + (size_t)l_name)) bad(off_ + (buf_.size() - pos_), "truncated header");
+        if (keep_refs) {
+            const char* nm = reinterpret_cast<const char*>(buf_.data() + pos_ + 4);
+            ref_names_.emplace_back(nm, strnlen(nm, (size_t)l_name));
+            ref_lengths_.push_back(le32(buf_.data() + pos_ + 4 + (size_t)l_name));
+        }
         pos_ += 8 + (size_t)l_name;
         off_ += 8 + (uint64_t)l_name;
     }
@@ -137,7 +144,11 @@ long BamReader::next()
         if (32ull + l_rn + 4ull * n_cig + (l_seq + 1ull) / 2 + l_seq > bs) bad(at, "fields longer than block_size");
         if (r[36 + l_rn - 1] != 0) bad(at, "read name not NUL-terminated");
         // the rule of vgmi_bam_filter.h (with every parameter at its default: flag & 0x900 == 0 and l_seq > 0)
-        const int verdict = bam_filter_verdict(filt_, RecordBytes{r}, (size_t)0, bs, l_rn, (uint32_t)r[13], n_cig, flag, l_seq, (double*)nullptr);
+        const int verdict =
+            regions_.empty()
+                ? bam_filter_verdict(filt_, RecordBytes{r}, (size_t)0, bs, l_rn, (uint32_t)r[13], n_cig, flag, l_seq, (double*)nullptr)
+                : bam_filter_region_verdict(filt_, BamRegions{regions_.data(), (uint32_t)regions_.size(), unplaced_ ? 1u : 0u}, RecordBytes{r}, (size_t)0,
+                                            bs, l_rn, (uint32_t)r[13], n_cig, flag, l_seq, ref, (int32_t)le32(r + 8), (double*)nullptr);
         if (verdict == BAM_FILTER_FAULT) bad(at, "auxiliary fields");
         pos_ += 4 + (size_t)bs;
         off_ += 4 + (uint64_t)bs;
@@ -151,6 +162,90 @@ long BamReader::next()
         qual_.assign(reinterpret_cast<const char*>(s + (l_seq + 1) / 2), l_seq);
         return (long)l_seq;
     }
+}
+
+namespace {
+// plain decimal digits -> a number below 2^62; false for anything else
+bool region_number(const std::string& t, int64_t& v)
+{
+    if (t.empty() || t.size() > 18) return false;
+    v = 0;
+    for (char c : t) {
+        if (c < '0' || c > '9') return false;
+        v = v * 10 + (c - '0');
+    }
+    return true;
+}
+}  // namespace
+
+std::vector<BamInterval> resolve_bam_regions(const BamRegionSpec& spec, const std::vector<std::string>& ref_names, const std::string& path,
+                                             uint64_t* bed_skipped)
+{
+    std::unordered_map<std::string, int32_t> ids;
+    ids.reserve(ref_names.size());
+    for (size_t i = 0; i < ref_names.size(); ++i) ids.emplace(ref_names[i], (int32_t)i);      // (a repeated name: its first id)
+    std::vector<BamInterval> v;
+    uint64_t skipped = 0;
+    for (size_t a = 0; a < spec.list.size();) {
+        size_t e = spec.list.find(',', a);
+        if (e == std::string::npos) e = spec.list.size();
+        const std::string item = spec.list.substr(a, e - a);
+        a = e + 1;
+        if (item.empty()) continue;
+        auto malformed = [&]() -> void { throw std::runtime_error("region '" + item + "' is not NAME, NAME:BEG or NAME:BEG-END (1-based, BEG <= END <= 2^31)"); };
+        int64_t beg = 0, end = VGH_BAM_REGION_END;
+        auto it = ids.find(item);
+        if (it == ids.end()) {
+            const size_t colon = item.rfind(':');
+            const std::string name = colon == std::string::npos ? item : item.substr(0, colon);
+            it = ids.find(name);
+            if (it == ids.end()) throw std::runtime_error("'" + path + "': reference '" + name + "' of region '" + item + "' is not in the header");
+            const std::string range = item.substr(colon + 1);
+            const size_t dash = range.find('-');
+            int64_t b1 = 0, e1 = 0;
+            if (!region_number(range.substr(0, dash), b1) || b1 < 1 || b1 > VGH_BAM_REGION_END) malformed();
+            beg = b1 - 1;
+            if (dash != std::string::npos) {
+                if (!region_number(range.substr(dash + 1), e1) || e1 < b1 || e1 > VGH_BAM_REGION_END) malformed();
+                end = e1;
+            }
+        }
+        v.push_back(BamInterval{it->second, (uint32_t)beg, (uint32_t)end});
+    }
+    if (!spec.bed.empty()) {
+        std::ifstream in(spec.bed);
+        if (!in) throw std::runtime_error("'" + spec.bed + "': No such file or directory.");
+        std::string line;
+        for (uint64_t no = 1; std::getline(in, line); ++no) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+            std::string col[3];
+            size_t p = 0;
+            int n_col = 0;
+            for (; n_col < 3 && p <= line.size(); ++n_col) {
+                size_t q = line.find_first_of("\t ", p);
+                if (q == std::string::npos) q = line.size();
+                col[n_col] = line.substr(p, q - p);
+                p = line.find_first_not_of("\t ", q);
+                if (p == std::string::npos) p = line.size() + 1;
+            }
+            int64_t b0 = 0, e0 = 0;
+            if (n_col < 3 || !region_number(col[1], b0) || !region_number(col[2], e0) || b0 >= e0 || e0 > VGH_BAM_REGION_END)
+                throw std::runtime_error("'" + spec.bed + "': line " + std::to_string(no) + " is not NAME START END with 0 <= START < END <= 2^31");
+            const auto it = ids.find(col[0]);
+            if (it == ids.end()) {
+                ++skipped;
+                continue;
+            }
+            v.push_back(BamInterval{it->second, (uint32_t)b0, (uint32_t)e0});
+        }
+    }
+    bam_regions_normalise(v);
+    if (v.size() > VGH_BAM_MAX_REGIONS) throw std::runtime_error(bam_regions_invalid_text(5));
+    // (an empty list would mean "no region test" to every reader: a BED file none of whose lines names a reference of this header is refused)
+    if (v.empty() && spec.on()) throw std::runtime_error("'" + path + "': no line of '" + spec.bed + "' names a reference of the header");
+    if (bed_skipped) *bed_skipped = skipped;
+    return v;
 }
 
 uint64_t BamReader::mask_below(uint32_t q)

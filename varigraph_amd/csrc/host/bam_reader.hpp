@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "bam_regions.hpp"
 #include "byte_source.hpp"
 #include "../vgmi_bam_filter.h"
 #include "../vgmi_subsample.h"
@@ -19,8 +20,12 @@ namespace vgh {
 
 class BamReader {
 public:
-    // reads and checks the header
-    BamReader(std::unique_ptr<ByteSource> src, const std::string& path);
+    // reads and checks the header; keep_refs: the references' names and lengths are kept (ref_names(), ref_lengths()) -- only where
+    // regions are resolved against them, a header may hold millions of contigs
+    BamReader(std::unique_ptr<ByteSource> src, const std::string& path, bool keep_refs = false);
+    const std::vector<std::string>& ref_names() const { return ref_names_; }
+    const std::vector<uint32_t>& ref_lengths() const { return ref_lengths_; }
+    const std::string& path() const { return path_; }
     uint64_t header_bytes() const { return header_bytes_; }   // magic .. the last reference, in decompressed bytes
     int32_t n_ref() const { return n_ref_; }
     // passes over the stream up to decompressed byte `offset` (a record boundary at or behind the current position)
@@ -41,6 +46,13 @@ public:
     // place, in front of subsampling.  A record whose auxiliary fields cannot be walked throws as the invalid record it is, "(auxiliary
     // fields)".  records() / reads(): valid records examined since, and the reads among them (before subsampling).
     void filter(const BamFilterParams& f) { filt_ = f; }
+    // The region list (condition 5 of vgmi_bam_filter.h), normalised -- bam_regions_normalise, or resolve_bam_regions below; empty: no
+    // region test.  It combines with filter().
+    void regions(std::vector<BamInterval> list, bool unplaced)
+    {
+        regions_ = std::move(list);
+        unplaced_ = unplaced && !regions_.empty();
+    }
     uint64_t records() const { return records_; }
     uint64_t reads() const { return reads_; }
     const std::string& seq() const { return seq_; }
@@ -65,6 +77,10 @@ private:
     uint64_t number_ = 0;
     BamFilterParams filt_ = bam_filter_params();
     uint64_t records_ = 0, reads_ = 0;
+    std::vector<std::string> ref_names_;
+    std::vector<uint32_t> ref_lengths_;
+    std::vector<BamInterval> regions_;
+    bool unplaced_ = false;
 };
 
 // the bytes of `path` as ByteSource::open delivers them; is_bam: block gzip whose text starts with "BAM\1" (decided from content)

@@ -39,6 +39,8 @@ struct ReadOpts {
     uint32_t min_q = 0;
     SubsampleRule sub;
     BamFilterParams filt = bam_filter_params();
+    BamRegionSpec reg;      // the regions of BAM files (on() false: none), resolved against each file's header
+    bool filtered() const { return filt.on || reg.on(); }
 };
 
 struct DeviceFileResult {
@@ -46,6 +48,7 @@ struct DeviceFileResult {
     uint64_t seen = 0;      // the file's reads, numbered by the device and the host reader together; n_reads of them were kept
     uint64_t bam_records = 0, bam_reads = 0;      // with a read filter, a BAM file: records examined and the reads among them, device and host reader together
     bool bam = false;
+    uint64_t bed_skipped = 0;      // with a BED file: its lines whose reference this file's header lacks
 };
 
 // the options a filter was made of, as the command line spells them
@@ -59,27 +62,42 @@ std::string filter_text(const BamFilterParams& f)
     if (f.tag) std::snprintf(buf, sizeof buf, "%s--bam-min-tag %c%c:%g", t.empty() ? "" : " ", (char)(f.tag & 0xFF), (char)(f.tag >> 8 & 0xFF), f.min_value), t += buf;
     return t;
 }
+std::string filter_text(const ReadOpts& o)
+{
+    std::string t = filter_text(o.filt);
+    auto add = [&](const std::string& a) { t += (t.empty() ? "" : " ") + a; };
+    if (!o.reg.list.empty()) add("--bam-regions " + o.reg.list);
+    if (!o.reg.bed.empty()) add("--bam-regions-file " + o.reg.bed);
+    if (o.reg.unplaced) add("--bam-regions-unplaced");
+    return t;
+}
 
 // VGH_TIMING: what the read filter did to one BAM file (nothing is printed without the options)
-void report_filter(const std::string& path, uint64_t records, uint64_t reads, const BamFilterParams& f)
+void report_filter(const std::string& path, uint64_t records, uint64_t reads, const ReadOpts& o, uint64_t bed_skipped)
 {
-    if (f.on && std::getenv("VGH_TIMING"))
+    if (!o.filtered() || !std::getenv("VGH_TIMING")) return;
+    if (o.reg.bed.empty())
         std::fprintf(stderr, "[varigraph-mi] '%s': %llu of %llu BAM records are reads (%s)\n", path.c_str(), (unsigned long long)reads,
-                     (unsigned long long)records, filter_text(f).c_str());
+                     (unsigned long long)records, filter_text(o).c_str());
+    else
+        std::fprintf(stderr, "[varigraph-mi] '%s': %llu of %llu BAM records are reads (%s; %llu BED lines skipped, reference not in the header)\n",
+                     path.c_str(), (unsigned long long)reads, (unsigned long long)records, filter_text(o).c_str(), (unsigned long long)bed_skipped);
 }
 
 // the filter goes to a BAM reader alone; FASTA/Q records are untouched
 template <class Reader>
-void set_filter(Reader& rd, const ReadOpts& o)
+void set_filter(Reader& rd, const ReadOpts& o, uint64_t* bed_skipped = nullptr)
 {
-    if constexpr (std::is_same_v<Reader, BamReader>)
+    if constexpr (std::is_same_v<Reader, BamReader>) {
         if (o.filt.on) rd.filter(o.filt);
+        if (o.reg.on()) rd.regions(resolve_bam_regions(o.reg, rd.ref_names(), rd.path(), bed_skipped), o.reg.unplaced);      // (a reader opened with keep_refs)
+    }
 }
 template <class Reader>
 void add_filter_counts(const Reader& rd, const ReadOpts& o, uint64_t& records, uint64_t& reads)
 {
     if constexpr (std::is_same_v<Reader, BamReader>)
-        if (o.filt.on) records += rd.records(), reads += rd.reads();
+        if (o.filtered()) records += rd.records(), reads += rd.reads();
 }
 
 // VGH_TIMING: what subsampling did to one file (nothing is printed without the option)
@@ -106,12 +124,13 @@ struct Channel {  // parser threads -> submitting thread
     std::string error;
     uint64_t seen = 0;      // reads the finished parsers numbered (all of them without subsampling)
     uint64_t bam_records = 0, bam_reads = 0;      // with a read filter: the BAM files' records and the reads among them
+    uint64_t bed_skipped = 0;
 };
 
 void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads, const ReadOpts o)
 {
     const uint32_t min_q = o.min_q;
-    uint64_t file_masked = 0, file_reads = 0, file_seen = 0, bam_records = 0, bam_reads = 0;
+    uint64_t file_masked = 0, file_reads = 0, file_seen = 0, bam_records = 0, bam_reads = 0, bed_skipped = 0;
     auto grab = [&]() {
         std::unique_lock<std::mutex> lk(ch.mu);
         ch.cv_free.wait(lk, [&] { return !ch.free_list.empty(); });
@@ -131,7 +150,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
     auto run = [&](auto& rd) {
         std::unique_ptr<Block> cur = grab();
         if (o.sub.on) rd.subsample(o.sub, 0);      // the whole file through this reader: its reads are numbered from 0
-        set_filter(rd, o);
+        set_filter(rd, o, &bed_skipped);
         while (rd.next() >= 0) {  // stops at EOF (-1) and at the first truncated record (-2)
             const uint64_t masked = min_q ? rd.mask_below(min_q) : 0;
             const std::string& s = rd.seq();
@@ -163,7 +182,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         bool is_bam = false;
         std::unique_ptr<ByteSource> src = open_sniffed(path, decode_threads, is_bam);
         if (is_bam) {
-            BamReader rd(std::move(src), path);
+            BamReader rd(std::move(src), path, o.reg.on());
             run(rd);
         } else {
             FastxReader rd(std::move(src));
@@ -171,11 +190,12 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         }
         report_masked(path, file_masked, min_q);
         report_subsample(path, file_seen, file_reads, o.sub);
-        if (is_bam) report_filter(path, bam_records, bam_reads, o.filt);
+        if (is_bam) report_filter(path, bam_records, bam_reads, o, bed_skipped);
         std::lock_guard<std::mutex> lk(ch.mu);
         ch.seen += file_seen;
         ch.bam_records += bam_records;
         ch.bam_reads += bam_reads;
+        ch.bed_skipped += bed_skipped;
     } catch (const std::exception& e) {
         std::lock_guard<std::mutex> lk(ch.mu);
         if (ch.error.empty()) ch.error = e.what();
@@ -195,7 +215,7 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
     const uint32_t min_q = o.min_q;
     uint64_t &n_reads = res.n_reads, &read_base = res.read_base, &masked = res.masked;
     if (o.sub.on) rd.subsample(o.sub, res.seen);      // the device's n_seen (0 where the device took nothing): one numbering per file
-    set_filter(rd, o);
+    set_filter(rd, o, &res.bed_skipped);      // (resolved against this reader's header: the same file, the same list)
     if (std::is_same_v<Reader, BamReader>) res.bam = true;
     std::vector<char> block;
     block.reserve(block_bytes + 1024);
@@ -319,7 +339,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         bool is_bam = false;
         std::unique_ptr<ByteSource> src = open_sniffed(path, threads, is_bam);   // (a BAM pipe: recognised from its first decoded bytes)
         if (is_bam) {
-            BamReader rd(std::move(src), path);
+            BamReader rd(std::move(src), path, o.reg.on());
             host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
         } else {
             FastxReader rd(std::move(src));
@@ -336,16 +356,18 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
     // length and number of references) and decodes wherever the device stops
     uint64_t bam_header = 0;
     int32_t bam_n_ref = 0;
+    std::vector<BamInterval> regions;      // --bam-regions against this file's header
     if (bam) {
         bool is_bam = false;
-        BamReader hdr(open_sniffed(path, 1, is_bam), path);
+        BamReader hdr(open_sniffed(path, 1, is_bam), path, o.reg.on());
         bam_header = hdr.header_bytes();
         bam_n_ref = hdr.n_ref();
+        if (o.reg.on()) regions = resolve_bam_regions(o.reg, hdr.ref_names(), path, &res.bed_skipped);      // (an unknown name ends the file here)
     }
     if (const char* off = std::getenv("VGH_HOST_INFLATE"); off && off[0] == '1' && bgzf) {   // A/B: block gzip through the host's inflate workers
         bgzf = false;
         if (bam) {
-            BamReader rd(ByteSource::open(path, threads), path);
+            BamReader rd(ByteSource::open(path, threads), path, o.reg.on());
             host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
             return res;
         }
@@ -372,8 +394,18 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
         throw std::runtime_error(why);
     }
-    const bool filtered = bam && o.filt.on;
-    if (filtered) {
+    const bool filtered = bam && o.filtered();
+    if (bam && o.reg.on()) {
+        std::vector<int32_t> ref(regions.size());
+        std::vector<int64_t> beg(regions.size()), end(regions.size());
+        for (size_t i = 0; i < regions.size(); ++i) ref[i] = regions[i].ref, beg[i] = regions[i].beg, end[i] = regions[i].end;
+        if (vgmi_fastq_set_bam_regions(fq, (uint32_t)regions.size(), ref.data(), beg.data(), end.data(), o.reg.unplaced ? 1 : 0) != VGMI_OK) {
+            const std::string why = vgmi_last_error(ctx);
+            (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+            throw std::runtime_error(why);
+        }
+    }
+    if (bam && o.filt.on) {
         const char tag[2] = {(char)(o.filt.tag & 0xFF), (char)(o.filt.tag >> 8 & 0xFF)};
         if (vgmi_fastq_set_bam_filter(fq, o.filt.exclude, o.filt.require, o.filt.min_mapq, o.filt.tag ? tag : nullptr, o.filt.min_value) != VGMI_OK) {
             const std::string why = vgmi_last_error(ctx);
@@ -517,7 +549,7 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         // the host decoder from the record the device stopped at, or the first it did not take (behind a damaged or missing member, or
         // the front of a record the data ends inside): from the file's start, passing over the header and what the device counted
         if (stopped || inflate_failed || comp_taken < file_size || tail_len) {
-            BamReader rd(ByteSource::open(path, threads), path);
+            BamReader rd(ByteSource::open(path, threads), path, o.reg.on());
             rd.skip_to(consumed);
             host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
         }
@@ -591,11 +623,31 @@ FastqKmerHipF::FastqKmerHipF(vgmi_ctx* ctx, const std::vector<std::string>& fast
 void FastqKmerHip::count_files_filtered(const uint32_t min_q, const SubsampleRule& sub, const BamFilterParams& filt, uint64_t& masked,
                                         uint64_t& seen, uint64_t& bam_records, uint64_t& bam_reads)
 {
+    uint64_t bed_skipped = 0;
+    count_files_regions(min_q, sub, filt, BamRegionSpec{}, masked, seen, bam_records, bam_reads, bed_skipped);
+}
+
+FastqKmerHipR::FastqKmerHipR(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads,
+                             uint32_t min_base_quality, double fraction, uint64_t seed, const BamFilterParams& filter, const BamRegionSpec& regions,
+                             size_t block_bytes)
+    : FastqKmerHip(ctx, fastqFileNameVec, kmerLen, threads, block_bytes), min_q_(min_base_quality), filt_(filter), reg_(regions)
+{
+    if (min_q_ > 93) throw std::runtime_error("minimum base quality " + std::to_string(min_q_) + " is out of range (0..93, Phred+33)");
+    if (!subsample_fraction_valid(fraction))
+        throw std::runtime_error("subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)");
+    if (reg_.unplaced && !reg_.on()) throw std::runtime_error(bam_regions_invalid_text(4));
+    rule_ = SubsampleRule(fraction, seed);
+}
+
+void FastqKmerHip::count_files_regions(const uint32_t min_q, const SubsampleRule& sub, const BamFilterParams& filt, const BamRegionSpec& regions,
+                                       uint64_t& masked, uint64_t& seen, uint64_t& bam_records, uint64_t& bam_reads, uint64_t& bed_skipped)
+{
     ReadOpts o;
     o.min_q = min_q;
     o.sub = sub;
     o.filt = filt;
-    bam_records = bam_reads = 0;
+    o.reg = regions;
+    bam_records = bam_reads = bed_skipped = 0;
     if (files_.empty()) throw std::runtime_error("Parameter error: -f");  // src/fastq_kmer.cpp:42-45
     uint32_t k_tab = 0;
     if (vgmi_table_info(ctx_, nullptr, &k_tab, nullptr, nullptr) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx_));
@@ -623,10 +675,11 @@ void FastqKmerHip::count_files_filtered(const uint32_t min_q, const SubsampleRul
                     const DeviceFileResult r = device_file(ctx_, files_[i], block_bytes_, io_threads, submit_mu, o);
                     report_masked(files_[i], r.masked, min_q);
                     report_subsample(files_[i], r.seen, r.n_reads, o.sub);
-                    if (r.bam) report_filter(files_[i], r.bam_records, r.bam_reads, o.filt);
+                    if (r.bam) report_filter(files_[i], r.bam_records, r.bam_reads, o, r.bed_skipped);
                     std::lock_guard<std::mutex> lk(res_mu);
                     bam_records += r.bam_records;
                     bam_reads += r.bam_reads;
+                    bed_skipped += r.bed_skipped;
                     mReadBase += r.read_base;
                     mReadNum += r.n_reads;
                     masked += r.masked;
@@ -697,6 +750,7 @@ void FastqKmerHip::count_files_filtered(const uint32_t min_q, const SubsampleRul
     seen = ch.seen;
     bam_records = ch.bam_records;
     bam_reads = ch.bam_reads;
+    bed_skipped = ch.bed_skipped;
 }
 
 void FastqKmerHip::fetch(uint8_t* cov, uint8_t* cov_node, uint64_t* hist256)

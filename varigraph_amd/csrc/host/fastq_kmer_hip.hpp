@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../vgmi_bam_filter.h"
+#include "bam_regions.hpp"
 #include "../vgmi_subsample.h"
 
 struct vgmi_ctx;
@@ -51,6 +52,10 @@ protected:
     // ... and with a read filter for the BAM files (on == 0: count_files_sampled); bam_records / bam_reads get their records and the reads among them
     void count_files_filtered(uint32_t min_base_quality, const SubsampleRule& sub, const BamFilterParams& filter, uint64_t& masked_bases,
                               uint64_t& reads_seen, uint64_t& bam_records, uint64_t& bam_reads);
+    // ... and with regions for the BAM files (regions.on() false: count_files_filtered); bed_skipped gets the BED lines whose reference a
+    // file's header lacks, summed over the BAM files
+    void count_files_regions(uint32_t min_base_quality, const SubsampleRule& sub, const BamFilterParams& filter, const BamRegionSpec& regions,
+                             uint64_t& masked_bases, uint64_t& reads_seen, uint64_t& bam_records, uint64_t& bam_reads, uint64_t& bed_skipped);
 
 private:
     vgmi_ctx* ctx_;
@@ -124,6 +129,34 @@ private:
     uint32_t min_q_;
     SubsampleRule rule_;
     BamFilterParams filt_;
+};
+
+// FastqKmerHipF with regions for BAM files (genotype --bam-regions / --bam-regions-file / --bam-regions-unplaced; condition 5 of
+// vgmi_bam_filter.h): resolved against every BAM file's own header, applied on the device and wherever the host decoder serves.  A
+// reference of --bam-regions that a file's header lacks ends the count with that file's name.  regions.on() false counts what
+// FastqKmerHipF counts.  A class of its own for FastqKmerHipQ's reason.
+class FastqKmerHipR : public FastqKmerHip {
+public:
+    uint64_t mMaskedBases = 0;
+    uint64_t mReadsSeen = 0;
+    uint64_t mBamRecords = 0;   // with a filter or regions: the BAM files' valid records ...
+    uint64_t mBamReads = 0;     // ... and the reads among them (before subsampling)
+    uint64_t mBedSkipped = 0;   // BED lines whose reference a BAM file's header lacks
+
+    // throws as FastqKmerHipF, and for regions.unplaced without a list or a BED file
+    FastqKmerHipR(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads, uint32_t min_base_quality,
+                  double fraction, uint64_t seed, const BamFilterParams& filter, const BamRegionSpec& regions, size_t block_bytes = 32u << 20);
+
+    void build_fastq_index_regions()
+    {
+        count_files_regions(min_q_, rule_, filt_, reg_, mMaskedBases, mReadsSeen, mBamRecords, mBamReads, mBedSkipped);
+    }
+
+private:
+    uint32_t min_q_;
+    SubsampleRule rule_;
+    BamFilterParams filt_;
+    BamRegionSpec reg_;
 };
 
 // What the device path makes of an input file, decided from its first bytes alone (no device involved): the container by the

@@ -52,6 +52,7 @@ struct Options {
     long long bam_min_mapq = 0;         // --bam-min-mapq
     std::string bam_tag;                // --bam-min-tag TAG:VALUE (empty: none)
     double bam_tag_value = 0.0;
+    vgh::BamRegionSpec bam_regions;     // --bam-regions, --bam-regions-file, --bam-regions-unplaced; the ranks of --procs inherit them
     int min_base_quality = 0;   // --min-base-quality: bases of FASTQ / BAM reads below it are counted as N (0: off); the ranks of --procs inherit it
 };
 
@@ -91,6 +92,12 @@ void usage(const char* argv0)
               << "                           MAPQ 0 does not pass a positive bound: unaligned BAM loses every read [0]\n"
               << "    --bam-min-tag   TAG:VALUE  a BAM record is a read only if its first TAG field is numeric and >= VALUE, e.g. rq:0.99\n"
               << "                           or qs:10 (samtools view -e '[rq]>=0.99'); a record without the tag is not a read [none]\n"
+              << "    --bam-regions   LIST   a BAM record is a read only if it overlaps one of these regions, as samtools view -L decides:\n"
+              << "                           comma-separated NAME, NAME:BEG or NAME:BEG-END, 1-based inclusive, resolved against each BAM\n"
+              << "                           file's header; a name the header lacks ends the run [none]\n"
+              << "    --bam-regions-file BED  regions from a BED file (columns 1-3, 0-based half-open), joined with --bam-regions; lines\n"
+              << "                           whose reference a header lacks are skipped [none]\n"
+              << "    --bam-regions-unplaced  with regions: unmapped records without a reference (refID -1) are reads too\n"
               << "    --gpu           INT    device ordinal [0]\n"
               << "    --gpus          LIST   several devices, e.g. 0,1,2,3: samples are counted on them in parallel\n"
               << "    --procs                one process per device of --gpus (samples dealt round robin, -t shared out); the table is\n"
@@ -211,6 +218,8 @@ int main_genotype(int argc, char** argv)
         {"subsample", required_argument, 0, 12},   {"subsample-seed", required_argument, 0, 13},
         {"bam-exclude-flags", required_argument, 0, 14}, {"bam-require-flags", required_argument, 0, 15},
         {"bam-min-mapq", required_argument, 0, 16}, {"bam-min-tag", required_argument, 0, 17},
+        {"bam-regions", required_argument, 0, 18}, {"bam-regions-file", required_argument, 0, 19},
+        {"bam-regions-unplaced", no_argument, 0, 20},
         {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -252,6 +261,9 @@ int main_genotype(int argc, char** argv)
             o.bam_tag_value = opt_double("--bam-min-tag", a.c_str() + 3);
             break;
         }
+        case 18: o.bam_regions.list += (o.bam_regions.list.empty() ? "" : ",") + std::string(optarg); break;
+        case 19: o.bam_regions.bed = optarg; break;
+        case 20: o.bam_regions.unplaced = true; break;
         case 't': o.hmm.threads = std::max(opt_int("-t", optarg), 1); break;
         case 'D': debug = true; break;
         default: usage(argv[0]); return 1;
@@ -279,6 +291,8 @@ int main_genotype(int argc, char** argv)
     if (o.bam_require > 65535) die("Parameter error: --bam-require-flags. The provided value must be between 0 and 65535 (inclusive).");
     if (o.bam_min_mapq > 255) die("Parameter error: --bam-min-mapq. The provided value must be between 0 and 255 (inclusive).");
     if (o.bam_tag_value != o.bam_tag_value) die("Parameter error: --bam-min-tag. The bound must be a number, not NaN.");
+    if (o.bam_regions.unplaced && !o.bam_regions.on())
+        die("Parameter error: --bam-regions-unplaced. It needs --bam-regions or --bam-regions-file.");
     const vgh::BamFilterParams bam_filter = vgh::bam_filter_params((uint32_t)o.bam_exclude, (uint32_t)o.bam_require, (uint32_t)o.bam_min_mapq,
                                                                    o.bam_tag.empty() ? nullptr : o.bam_tag.c_str(), o.bam_tag_value);
 
@@ -693,6 +707,13 @@ int main_genotype(int argc, char** argv)
                 }
                 const auto& [name, files] = samples[s];
                 const double ts = secs();
+                if (o.bam_regions.on()) {
+                    vgh::FastqKmerHipR fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed, bam_filter,
+                                          o.bam_regions);
+                    fk.build_fastq_index_regions();
+                    counted(s, fk, dev_i, ts);
+                    continue;
+                }
                 if (bam_filter.on) {
                     vgh::FastqKmerHipF fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed, bam_filter);
                     fk.build_fastq_index_filtered();

@@ -232,6 +232,17 @@ int64_t vgh_reads_read_all_f(const char* path, uint32_t decode_threads, uint32_t
                              double bam_min_value, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases,
                              uint64_t* next_number, uint64_t* bam_records, uint64_t* bam_reads)
 {
+    return vgh_reads_read_all_r(path, decode_threads, min_base_quality, fraction, seed, first_number, bam_exclude, bam_require, bam_min_mapq, bam_tag,
+                                bam_min_value, nullptr, nullptr, 0, block_out, n_bytes_out, read_base, masked_bases, next_number, bam_records,
+                                bam_reads);
+}
+
+int64_t vgh_reads_read_all_r(const char* path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag,
+                             double bam_min_value, const char* bam_regions, const char* bam_regions_bed, int bam_unplaced, char** block_out,
+                             size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases, uint64_t* next_number, uint64_t* bam_records,
+                             uint64_t* bam_reads)
+{
     if (!path || !block_out || !n_bytes_out) return VGMI_E_INVALID;
     if (bam_records) *bam_records = 0;
     if (bam_reads) *bam_reads = 0;
@@ -247,13 +258,22 @@ int64_t vgh_reads_read_all_f(const char* path, uint32_t decode_threads, uint32_t
         g_err = vgh::bam_filter_invalid_text(bad);
         return VGMI_E_INVALID;
     }
+    vgh::BamRegionSpec reg;
+    reg.list = bam_regions ? bam_regions : "";
+    reg.bed = bam_regions_bed ? bam_regions_bed : "";
+    reg.unplaced = bam_unplaced != 0;
+    if (reg.unplaced && !reg.on()) {
+        g_err = vgh::bam_regions_invalid_text(4);
+        return VGMI_E_INVALID;
+    }
     try {
         const vgh::SubsampleRule rule(fraction, seed);
         bool is_bam = false;
         std::unique_ptr<vgh::ByteSource> src = vgh::open_sniffed(path, decode_threads ? decode_threads : 1, is_bam);
         if (is_bam) {
-            vgh::BamReader rd(std::move(src), path);
+            vgh::BamReader rd(std::move(src), path, reg.on());
             rd.filter(vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value));
+            if (reg.on()) rd.regions(vgh::resolve_bam_regions(reg, rd.ref_names(), path), reg.unplaced);
             const int64_t n = reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
             if (bam_records) *bam_records = rd.records();
             if (bam_reads) *bam_reads = rd.reads();
@@ -362,6 +382,18 @@ int vgh_sample_count_f(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fas
                        uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag, double bam_min_value, uint64_t* reads_seen,
                        uint64_t* reads_kept, uint64_t* masked_bases, uint64_t* bam_records, uint64_t* bam_reads)
 {
+    return vgh_sample_count_r(h, ctx, fastq_paths, n_files, threads, sample_ploidy, use_depth, cov_out, cov_node_out, hist_out, stats,
+                              min_base_quality, fraction, seed, bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value, nullptr, nullptr, 0,
+                              reads_seen, reads_kept, masked_bases, bam_records, bam_reads);
+}
+
+int vgh_sample_count_r(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fastq_paths, size_t n_files, uint32_t threads,
+                       uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
+                       vgh_sample_stats* stats, uint32_t min_base_quality, double fraction, uint64_t seed, uint32_t bam_exclude,
+                       uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag, double bam_min_value, const char* bam_regions,
+                       const char* bam_regions_bed, int bam_unplaced, uint64_t* reads_seen, uint64_t* reads_kept, uint64_t* masked_bases,
+                       uint64_t* bam_records, uint64_t* bam_reads)
+{
     if (!h || !ctx || (!fastq_paths && n_files)) return VGMI_E_INVALID;
     if (masked_bases) *masked_bases = 0;
     if (reads_seen) *reads_seen = 0;
@@ -375,9 +407,13 @@ int vgh_sample_count_f(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fas
     try {
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<std::string> files(fastq_paths, fastq_paths + n_files);
-        vgh::FastqKmerHipF fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed,
-                              vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value));
-        fk.build_fastq_index_filtered();
+        vgh::BamRegionSpec reg;
+        reg.list = bam_regions ? bam_regions : "";
+        reg.bed = bam_regions_bed ? bam_regions_bed : "";
+        reg.unplaced = bam_unplaced != 0;
+        vgh::FastqKmerHipR fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed,
+                              vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value), reg);
+        fk.build_fastq_index_regions();
         if (masked_bases) *masked_bases = fk.mMaskedBases;
         if (reads_seen) *reads_seen = fk.mReadsSeen;
         if (reads_kept) *reads_kept = fk.mReadNum;

@@ -67,6 +67,10 @@ struct vgmi_fastq {
     unsigned long long* d_fa_sub = nullptr;
     // the read filter of a BAM stream (vgmi_fastq_set_bam_filter): on == 0 = the default rule; fixed once bytes have been committed
     vgh::BamFilterParams filt{};
+    // the region list of a BAM stream (vgmi_fastq_set_bam_regions), normalised, in device memory; n_regions == 0 = no region test; fixed
+    // once bytes have been committed.  The allocation (cap_regions intervals) stays with the stream's buffers
+    vgh::BamInterval* d_regions = nullptr;
+    uint32_t cap_regions = 0, n_regions = 0, regions_unplaced = 0;
 };
 
 namespace {
@@ -84,7 +88,7 @@ extern "C++" void vgapi::fastq_free(vgmi_fastq* f)
     }
     for (void* p : {(void*)f->d_packed, (void*)f->d_tile, (void*)f->d_nlpos, (void*)f->d_rec, (void*)f->d_off, (void*)f->d_bsum,
                     (void*)f->d_state, (void*)f->d_comp, (void*)f->d_members, (void*)f->d_status, (void*)f->d_crc, (void*)f->d_verdict,
-                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa, (void*)f->d_even, (void*)f->d_fa_sub})
+                    (void*)f->d_bam, (void*)f->d_mark, (void*)f->d_fa, (void*)f->d_even, (void*)f->d_fa_sub, (void*)f->d_regions})
         if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         if (f->h_members[i]) (void)hipHostFree(f->h_members[i]);
@@ -136,6 +140,7 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->sub = SubParams{};
             r->sub_fraction = 1.0;
             r->filt = vgh::BamFilterParams{};
+            r->n_regions = r->regions_unplaced = 0;
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -517,6 +522,9 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
         bb.min_qual = f->min_quality;
         bb.sub = f->sub;
         bb.filt = f->filt;
+        bb.regions = f->d_regions;
+        bb.n_regions = f->n_regions;
+        bb.regions_unplaced = f->regions_unplaced;
         HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
         int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
@@ -1007,12 +1015,42 @@ int vgmi_fastq_set_bam_filter(vgmi_fastq* f, uint32_t exclude, uint32_t require,
     return VGMI_OK;
 }
 
+int vgmi_fastq_set_bam_regions(vgmi_fastq* f, uint32_t n, const int32_t* ref, const int64_t* beg, const int64_t* end, int unplaced)
+{
+    if (!f || (n && (!ref || !beg || !end))) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    if (f->committed) return fail(c, VGMI_E_STATE, "the BAM regions are set before the stream's first commit");
+    if (!f->bam) return VGMI_OK;      // FASTQ and FASTA text has no records to place
+    uint32_t which = 0;
+    if (const int bad = vgh::bam_regions_invalid(n, ref, beg, end, unplaced, f->n_ref, &which)) return fail(c, VGMI_E_INVALID, vgh::bam_regions_invalid_text(bad));
+    std::vector<vgh::BamInterval> v(n);
+    for (uint32_t i = 0; i < n; ++i) v[i] = vgh::BamInterval{ref[i], (uint32_t)beg[i], (uint32_t)end[i]};
+    vgh::bam_regions_normalise(v);
+    if (v.size() > VGH_BAM_MAX_REGIONS) return fail(c, VGMI_E_INVALID, vgh::bam_regions_invalid_text(5));
+    if (!v.empty()) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (v.size() > f->cap_regions) {
+            if (f->d_regions) HIPCHK(c, hipFree(f->d_regions));
+            f->d_regions = nullptr;
+            f->cap_regions = f->n_regions = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&f->d_regions), v.size() * sizeof(vgh::BamInterval)));
+            f->cap_regions = (uint32_t)v.size();
+        }
+        // (nothing of the stream has been committed: the copy is waited for, the host's list ends with this call)
+        HIPCHK(c, hipMemcpyAsync(f->d_regions, v.data(), v.size() * sizeof(vgh::BamInterval), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(c, hipStreamSynchronize(f->stream));
+    }
+    f->n_regions = (uint32_t)v.size();      // n == 0: the stream that never called this
+    f->regions_unplaced = v.empty() ? 0u : (unplaced ? 1u : 0u);
+    return VGMI_OK;
+}
+
 int vgmi_fastq_bam_filter_stats(vgmi_fastq* f, uint64_t* records, uint64_t* reads)
 {
     if (!f || !records || !reads) return VGMI_E_INVALID;
     vgmi_ctx* c = f->c;
     *records = *reads = 0;
-    if (!f->filt.on || !f->d_bam) return fail(c, VGMI_E_STATE, "the stream has no BAM read filter");
+    if ((!f->filt.on && !f->n_regions) || !f->d_bam) return fail(c, VGMI_E_STATE, "the stream has no BAM read filter and no BAM regions");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(f->stream));
     BamState bs{};

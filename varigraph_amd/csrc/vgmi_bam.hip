@@ -28,6 +28,8 @@
 // With a configured read filter (BamBuffers::filt; vgmi_fastq_set_bam_filter, the rule in vgmi_bam_filter.h) B6 is
 // bam_keep_filter_kernel, with a tag bound bam_cut_kernel ends the chain in front of a record whose auxiliary fields cannot be walked,
 // and B9 is bam_finish_filter_kernel / bam_finish_filter_sub_kernel; the kernels between run on the rec_bytes these leave.
+// With a region list (BamBuffers::regions; vgmi_fastq_set_bam_regions) B6 is bam_keep_region_kernel, the filter's B6 with the region test
+// in front of the tag walk; bam_cut_kernel and B9 as with a filter.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -494,6 +496,43 @@ __global__ __launch_bounds__(256) void bam_keep_filter_kernel(const uint8_t* raw
     if (threadIdx.x == 0 && c) atomicAdd(&bs->n_chain, c);
 }
 
+// B6 with a region list (and whatever filter is set: f holds the defaults where none is): bam_keep_filter_kernel with condition 5 of
+// vgmi_bam_filter.h in front of the tag walk.  The interval list is read from device memory, a binary search per lane: a few KB that
+// every lane of the chunk walks the same top of, so it stays in the L2.  CIGAR dwords are read only where pos lies in front of an
+// interval of its reference, through bam_ld32 like every other field.
+__global__ __launch_bounds__(256) void bam_keep_region_kernel(const uint8_t* raw, BamState* bs, const uint32_t* cand, const uint32_t* j0,
+                                                               const uint8_t* mark, uint32_t* rec_bytes, uint32_t cap, vgh::BamFilterParams f,
+                                                               vgh::BamRegions g)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;
+    const BamBytes bytes{raw};
+    uint32_t kept = 0, chain = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint32_t b = 0;
+        if (mark[i]) {
+            const uint32_t o = cand[i];
+            const uint32_t w12 = bam_ld32(raw, o + 12), w16 = bam_ld32(raw, o + 16), l_seq = bam_ld32(raw, o + 20);
+            const int v = vgh::bam_filter_region_verdict(f, g, bytes, o, bam_ld32(raw, o), w12 & 0xFFu, (w12 >> 8) & 0xFFu, w16 & 0xFFFFu, w16 >> 16,
+                                                         l_seq, (int32_t)bam_ld32(raw, o + 4), (int32_t)bam_ld32(raw, o + 8), (double*)nullptr);
+            ++chain;
+            if (v == vgh::BAM_FILTER_READ) {
+                b = l_seq + 1;
+                ++kept;
+            } else if (v == vgh::BAM_FILTER_FAULT) {
+                atomicMin(&bs->first_fault, i);
+            }
+            if (j0[i] == n) bs->last = i;
+        }
+        rec_bytes[i] = b;
+    }
+    const uint32_t t = block_reduce_add(kept, sh);
+    const uint32_t c = block_reduce_add(chain, sh);
+    if (threadIdx.x == 0 && t) atomicAdd(&bs->n_kept, t);
+    if (threadIdx.x == 0 && c) atomicAdd(&bs->n_chain, c);
+}
+
 // Behind B6 with a tag bound: the chain is cut at the smallest faulted index.  Chain order is candidate order, so the records at and behind
 // it are the marked candidates i >= first_fault: their rec_bytes become 0 and they leave the sums.  `last` becomes the chain
 // record in front of the fault -- the marked one whose successor it is -- or none where the fault is the chain's first record.
@@ -637,7 +676,14 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_jump_kernel, dim3(grid), dim3(256), 0, s, b.bam, src, dst, b.mark, r, b.cap_cand);
         src = dst;
     }
-    if (b.filt.on) {
+    const bool filtered = b.filt.on || b.n_regions;      // B9's filter forms keep the sums either rule needs
+    const vgh::BamFilterParams filt = b.filt.on ? b.filt : vgh::bam_filter_params();
+    if (b.n_regions) {
+        hipLaunchKernelGGL(bam_keep_region_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand, filt,
+                           vgh::BamRegions{b.regions, b.n_regions, b.regions_unplaced});
+        if (filt.tag)
+            hipLaunchKernelGGL(bam_cut_kernel, dim3(grid), dim3(256), 0, s, b.state, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
+    } else if (b.filt.on) {
         hipLaunchKernelGGL(bam_keep_filter_kernel, dim3(grid), dim3(256), 0, s, b.raw, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand, b.filt);
         if (b.filt.tag)      // (without a tag bound no auxiliary byte is read: nothing can fault)
             hipLaunchKernelGGL(bam_cut_kernel, dim3(grid), dim3(256), 0, s, b.state, b.bam, b.cand, b.j0, b.mark, b.rec_bytes, b.cap_cand);
@@ -660,10 +706,10 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_decode_mask_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed,
                            b.cap_cand, b.min_qual);
     else hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
-    if (b.filt.on && b.sub.on)
+    if (filtered && b.sub.on)
         hipLaunchKernelGGL(bam_finish_filter_sub_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
                            b.cap_cand, b.tail_max, b.n_ref);
-    else if (b.filt.on)
+    else if (filtered)
         hipLaunchKernelGGL(bam_finish_filter_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
                            b.cap_cand, b.tail_max, b.n_ref);
     else if (b.sub.on)

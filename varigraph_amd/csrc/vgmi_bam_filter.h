@@ -10,6 +10,7 @@
 //   4  mapq >= min_mapq                        the byte at offset 13 as a number: 255 passes, an unmapped record's 0 fails a positive bound
 //   5  with a tag bound: the FIRST auxiliary field carrying the tag is numeric (c C s S i I f, and d as 8 bytes) and its value, as a
 //      double (integers exact, f promoted), is >= min_value; NaN fails; absent or of type A Z H B: not a read (`samtools view -e '[tg]>=v'`)
+// With a region list (`--bam-regions`, further down) the region test stands between 4 and the tag bound, and the walk waits for it too.
 // The auxiliary walk runs only with a tag bound and only for records that passed 1 to 4.  It goes from behind QUAL to the record's end
 // or to the first field with the tag; what lies behind that field is not looked at.  A field's value takes 1 (A c C), 2 (s S), 4 (i I f)
 // or 8 (d) bytes, up to and including the NUL (Z H), or subtype + 32-bit count + count x size (B, subtype in cCsSiIf).  A walk fault --
@@ -21,6 +22,9 @@
 // p' in [p, end) with a zero byte, or end), p counted as the caller counts: the device reads aligned dwords, the host a byte array.
 #pragma once
 #include <stdint.h>
+
+#include <algorithm>
+#include <vector>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define VGH_BAMF_HD __host__ __device__
@@ -131,6 +135,106 @@ VGH_BAMF_HD inline int bam_filter_verdict(const BamFilterParams& f, const B& b, 
     return v >= f.min_value ? BAM_FILTER_READ : BAM_FILTER_DROP;      // (a NaN value compares false)
 }
 
+// ---- condition 5: the region test (`genotype --bam-regions / --bam-regions-file / --bam-regions-unplaced`) --------------------------
+// With a region list the rule above gains a condition between 4 and the tag bound, which becomes condition 6: the auxiliary walk runs
+// only for records that passed 1 to 5, so a record the region test drops is never walked and cannot fault.
+//   5  refID == -1: the record passes iff `unplaced` is set.  refID >= 0: it passes iff some interval (ref, beg, end) -- 0-based, half
+//      open -- has ref == refID, pos < end and endpos > beg, in signed 64-bit arithmetic.  pos is the signed field at offset 8;
+//      endpos = pos + 1 if flag & 0x4, n_cigar_op == 0 or reflen == 0, else pos + reflen; reflen = the sum of cigar >> 4 over the
+//      operations whose code cigar & 15 is M(0) D(2) N(3) =(7) X(8).  I S H P and the undefined codes 9 to 15 consume nothing.
+// This is bam_endpos with bed_overlap, what `samtools view -L` does on a stream.  An unmapped record without CIGAR at pos == -1 has
+// endpos 0 and overlaps nothing.  The placeholder CIGAR <l_seq>S<reflen>N of a record whose CIGAR is in a CG tag gives the right end.
+// The list is normalised (bam_regions_normalise): sorted by (ref, beg), overlapping or touching intervals of one reference merged, so
+// that beg[i] < end[i] < beg[i + 1] inside a reference.  bam_region_overlap_plain is the definition; bam_region_overlap is what the
+// kernel and the host decoder call, and the stand-alone check holds the one against the other.
+struct BamInterval {
+    int32_t ref;
+    uint32_t beg, end;      // 0 <= beg < end <= 2^31
+};
+
+// a normalised list where the caller keeps it (device or host memory); n == 0: no region test
+struct BamRegions {
+    const BamInterval* iv;
+    uint32_t n;
+    uint32_t unplaced;
+};
+
+#define VGH_BAM_MAX_REGIONS (1u << 20)
+#define VGH_BAM_REGION_END (1ll << 31)
+
+VGH_BAMF_HD inline bool bam_cigar_consumes_ref(uint32_t op)
+{
+    return ((1u << (op & 15u)) & ((1u << 0) | (1u << 2) | (1u << 3) | (1u << 7) | (1u << 8))) != 0;
+}
+
+// the definition: every interval looked at, the whole CIGAR summed (cig: the position of the first CIGAR dword, as B counts)
+template <class B, class Pos>
+VGH_BAMF_HD inline bool bam_region_overlap_plain(const BamRegions& g, const B& b, Pos cig, uint32_t n_cigar_op, uint32_t flag, int32_t ref_id,
+                                                 int32_t pos32)
+{
+    if (ref_id < 0) return g.unplaced != 0;
+    const int64_t pos = pos32;
+    int64_t reflen = 0;
+    for (uint32_t i = 0; i < n_cigar_op; ++i) {
+        const uint32_t c = b.u32(cig + (Pos)(4u * i));
+        if (bam_cigar_consumes_ref(c)) reflen += (int64_t)(c >> 4);
+    }
+    const int64_t endpos = ((flag & 0x4u) || n_cigar_op == 0 || reflen == 0) ? pos + 1 : pos + reflen;
+    for (uint32_t i = 0; i < g.n; ++i)
+        if (g.iv[i].ref == ref_id && pos < (int64_t)g.iv[i].end && endpos > (int64_t)g.iv[i].beg) return true;
+    return false;
+}
+
+// The same verdict on a normalised list by one binary search: j = the last interval with (ref, beg) <= (refID, pos).  pos inside j:
+// an overlap, whatever the CIGAR says (endpos > pos >= beg).  Else the intervals up to j end at or in front of pos, and the only
+// interval the record can reach first is j + 1: none of refID there, or an endpos of pos + 1: no overlap, the CIGAR unread.  Otherwise
+// the CIGAR is summed until pos + reflen passes that interval's beg.
+template <class B, class Pos>
+VGH_BAMF_HD inline bool bam_region_overlap(const BamRegions& g, const B& b, Pos cig, uint32_t n_cigar_op, uint32_t flag, int32_t ref_id, int32_t pos32)
+{
+    if (ref_id < 0) return g.unplaced != 0;
+    const int64_t pos = pos32;
+    const int64_t key = (int64_t)ref_id * (1ll << 32) + pos;      // (beg < 2^31: a negative pos still sorts behind the reference in front)
+    uint32_t lo = 0, hi = g.n;      // the first interval with (ref, beg) > (refID, pos)
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        const int64_t k = (int64_t)g.iv[mid].ref * (1ll << 32) + (int64_t)g.iv[mid].beg;
+        if (k <= key) lo = mid + 1u;
+        else hi = mid;
+    }
+    if (lo > 0 && g.iv[lo - 1u].ref == ref_id && (int64_t)g.iv[lo - 1u].end > pos) return true;
+    if (lo == g.n || g.iv[lo].ref != ref_id) return false;
+    if ((flag & 0x4u) || n_cigar_op == 0) return false;      // endpos = pos + 1 <= beg
+    const int64_t reach = (int64_t)g.iv[lo].beg - pos;       // > 0: the reference length that passes beg
+    int64_t reflen = 0;
+    for (uint32_t i = 0; i < n_cigar_op; ++i) {
+        const uint32_t c = b.u32(cig + (Pos)(4u * i));
+        if (bam_cigar_consumes_ref(c)) {
+            reflen += (int64_t)(c >> 4);
+            if (reflen > reach) return true;
+        }
+    }
+    return false;      // (reflen == 0: endpos = pos + 1 <= beg as well)
+}
+
+// The rule with a region list: bam_filter_verdict with condition 5 in front of the tag bound.  f: the filter's parameters, the defaults
+// of bam_filter_params() where none was configured.  ref_id, pos: the signed fields at offsets 4 and 8.
+template <class B, class Pos>
+VGH_BAMF_HD inline int bam_filter_region_verdict(const BamFilterParams& f, const BamRegions& g, const B& b, Pos o, uint32_t block_size,
+                                                 uint32_t l_read_name, uint32_t mapq, uint32_t n_cigar_op, uint32_t flag, uint32_t l_seq, int32_t ref_id,
+                                                 int32_t pos, double* value)
+{
+    if (l_seq == 0 || (flag & f.exclude) != 0 || (flag & f.require) != f.require || mapq < f.min_mapq) return BAM_FILTER_DROP;
+    if (g.n && !bam_region_overlap(g, b, o + (Pos)(36u + l_read_name), n_cigar_op, flag, ref_id, pos)) return BAM_FILTER_DROP;
+    if (!f.tag) return BAM_FILTER_READ;
+    const Pos aux = o + (Pos)(36u + l_read_name + 4u * n_cigar_op + (l_seq + 1u) / 2u + l_seq);
+    double v = 0.0;
+    const int r = bam_aux_find(b, aux, o + (Pos)4u + (Pos)block_size, f.tag & 0xFFu, (f.tag >> 8) & 0xFFu, &v);
+    if (r != BAM_FILTER_READ) return r;
+    if (value) *value = v;
+    return v >= f.min_value ? BAM_FILTER_READ : BAM_FILTER_DROP;
+}
+
 // ---- the host's side: parameters as the options give them ---------------------------------------------------------------------------
 inline bool bam_filter_tag_valid(const char* t)
 {
@@ -173,6 +277,48 @@ inline BamFilterParams bam_filter_params(uint32_t exclude = 0x900u, uint32_t req
     f.min_value = tag ? min_value : 0.0;
     f.on = exclude != 0x900u || require != 0 || min_mapq != 0 || tag != nullptr;
     return f;
+}
+
+// ---- the host's side of the region list ------------------------------------------------------------------------------------------------
+// 0: fine; else what is wrong with the list as given (1 a ref outside [0, n_ref), 2 a beg outside [0, 2^31), 3 an end outside
+// (beg, 2^31], 4 `unplaced` without a list); *which = the offending item
+inline int bam_regions_invalid(uint32_t n, const int32_t* ref, const int64_t* beg, const int64_t* end, int unplaced, int32_t n_ref, uint32_t* which)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        if (which) *which = i;
+        if (ref[i] < 0 || ref[i] >= n_ref) return 1;
+        if (beg[i] < 0 || beg[i] >= VGH_BAM_REGION_END) return 2;
+        if (end[i] <= beg[i] || end[i] > VGH_BAM_REGION_END) return 3;
+    }
+    if (n == 0 && unplaced) return 4;
+    return 0;
+}
+
+inline const char* bam_regions_invalid_text(int which)
+{
+    switch (which) {
+    case 1: return "a BAM region names a reference outside the file's header";
+    case 2: return "a BAM region's begin is out of range (0 <= beg < 2^31)";
+    case 3: return "a BAM region's end is out of range (beg < end <= 2^31)";
+    case 4: return "unplaced BAM reads are kept only together with a region list";
+    case 5: return "more than 1048576 BAM regions remain after merging";
+    default: return "";
+    }
+}
+
+// valid intervals, any order -> sorted by (ref, beg), overlapping or touching ones of a reference merged
+inline void bam_regions_normalise(std::vector<BamInterval>& v)
+{
+    std::sort(v.begin(), v.end(), [](const BamInterval& a, const BamInterval& b) { return a.ref != b.ref ? a.ref < b.ref : a.beg < b.beg; });
+    size_t m = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (m && v[m - 1].ref == v[i].ref && v[i].beg <= v[m - 1].end) {
+            if (v[i].end > v[m - 1].end) v[m - 1].end = v[i].end;
+        } else {
+            v[m++] = v[i];
+        }
+    }
+    v.resize(m);
 }
 
 }  // namespace vgh

@@ -222,6 +222,11 @@ struct BamBuffers {
     uint32_t min_qual;                 // 0: off; else a base whose QUAL byte is below it is decoded as 'N' (a record without QUAL: none)
     SubParams sub;                     // rec_bytes of a dropped read is turned to 0 before the scan
     vgh::BamFilterParams filt;         // on == 0: flag & 0x900 == 0 and l_seq > 0, by bam_keep_kernel; else bam_keep_filter_kernel's rule
+    // the region list of the stream (vgmi_fastq_set_bam_regions; device memory, normalised), last, so that every other member stays where it
+    // was: n_regions == 0: no region test; else B6 is bam_keep_region_kernel
+    const vgh::BamInterval* regions;
+    uint32_t n_regions;
+    uint32_t regions_unplaced;         // refID == -1 passes the region test
 };
 hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s);
 hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);

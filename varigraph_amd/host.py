@@ -73,6 +73,13 @@ def lib():
     l.vgh_sample_count_f.restype = C.c_int
     l.vgh_sample_count_f.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                                    C.c_char_p, C.c_double] + [C.POINTER(C.c_uint64)] * 5
+    l.vgh_sample_count_r.restype = C.c_int
+    l.vgh_sample_count_r.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                   C.c_char_p, C.c_double, C.c_char_p, C.c_char_p, C.c_int] + [C.POINTER(C.c_uint64)] * 5
+    l.vgh_reads_read_all_r.restype = C.c_int64
+    l.vgh_reads_read_all_r.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_char_p, C.c_double, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp),
+                                       C.POINTER(C.c_size_t)] + [C.POINTER(C.c_uint64)] * 5
     l.vgh_reads_read_all_f.restype = C.c_int64
     l.vgh_reads_read_all_f.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_char_p, C.c_double, C.POINTER(vp), C.POINTER(C.c_size_t)] + [C.POINTER(C.c_uint64)] * 5
@@ -168,14 +175,16 @@ class Graph:
         return cov, rb.value
 
     def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True, min_base_quality=0,
-                     subsample=None, bam_filter=None):
+                     subsample=None, bam_filter=None, bam_regions=None, bam_regions_bed=None, bam_unplaced=False):
         """FastqKmerHip::build_fastq_index + coverage statistics for one sample.  require_depth=False: a sample too thin
         for the coverage peak (the reference exits with "Failed to retrieve depth information") still returns its
         counters.  min_base_quality: bases of FASTQ / BAM reads whose quality is below it are counted as N (vgh_sample_count_q);
         stats["masked_bases"] = how many, device and host readers together.  subsample=(F, S): a seeded fraction of every file's
         reads is kept (vgh_sample_count_s); stats then has reads_seen and reads_kept, and n_reads / read_base are the kept reads'.
         bam_filter=dict(exclude=0x900, require=0, min_mapq=0, tag=None, min_value=0.0), any key optional: the read filter of BAM files
-        (vgh_sample_count_f); stats then has bam_records and bam_reads."""
+        (vgh_sample_count_f); stats then has bam_records and bam_reads.  bam_regions="NAME,NAME:BEG-END,...", bam_regions_bed=a BED
+        file's path, bam_unplaced: the regions of BAM files (vgh_sample_count_r), alone or with bam_filter; stats has bam_records and
+        bam_reads then too."""
         i = self.info
         cov = np.empty(i["n_keys"], dtype=np.uint8)
         cov_node = np.empty(i["n_node_entries"], dtype=np.uint8)
@@ -184,7 +193,15 @@ class Graph:
         arr = (C.c_char_p * len(fastq_paths))(*[os.fsencode(p) for p in fastq_paths])
         masked, seen, kept = C.c_uint64(), C.c_uint64(), C.c_uint64()
         recs, rds = C.c_uint64(), C.c_uint64()
-        if bam_filter is not None:
+        regions = bam_regions is not None or bam_regions_bed is not None or bam_unplaced
+        if regions:
+            f, fs = bam_filter_args(bam_filter or {}), subsample if subsample is not None else (1.0, 0)
+            rc = self._l.vgh_sample_count_r(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
+                                            vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
+                                            float(fs[0]), int(fs[1]), *f, _region_args(bam_regions, bam_regions_bed)[0],
+                                            _region_args(bam_regions, bam_regions_bed)[1], int(bool(bam_unplaced)), C.byref(seen),
+                                            C.byref(kept), C.byref(masked), C.byref(recs), C.byref(rds))
+        elif bam_filter is not None:
             f, fs = bam_filter_args(bam_filter), subsample if subsample is not None else (1.0, 0)
             rc = self._l.vgh_sample_count_f(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
                                             vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
@@ -206,7 +223,7 @@ class Graph:
         stats["masked_bases"] = masked.value
         if subsample is not None:
             stats["reads_seen"], stats["reads_kept"] = seen.value, kept.value
-        if bam_filter is not None:
+        if bam_filter is not None or regions:
             stats["bam_records"], stats["bam_reads"] = recs.value, rds.value
         return cov, cov_node, hist, stats
 
@@ -347,6 +364,31 @@ def reads_read_all_f(path, bam_filter, fraction=1.0, seed=11, first_number=0, mi
     l = lib()
     p, n, rb, mb, nx, rc, rd = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
     cnt = l.vgh_reads_read_all_f(os.fsencode(path), decode_threads, min_base_quality, fraction, seed, first_number, *bam_filter_args(bam_filter),
+                                 C.byref(p), C.byref(n), C.byref(rb), C.byref(mb), C.byref(nx), C.byref(rc), C.byref(rd))
+    if cnt < 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    try:
+        block = _arr(p.value, n.value, np.uint8)
+    finally:
+        l.vgh_free(p)
+    return block, int(cnt), rb.value, mb.value, nx.value, rc.value, rd.value
+
+
+def _region_args(bam_regions, bam_regions_bed):
+    """(list, bed) as the C entries take them: bam_regions a string or a sequence of items, bam_regions_bed a path; None stays NULL"""
+    if bam_regions is not None and not isinstance(bam_regions, (str, bytes)):
+        bam_regions = ",".join(bam_regions)
+    return (None if bam_regions is None else os.fsencode(bam_regions), None if bam_regions_bed is None else os.fsencode(bam_regions_bed))
+
+
+def reads_read_all_r(path, bam_regions=None, bam_regions_bed=None, bam_unplaced=False, bam_filter=None, fraction=1.0, seed=11, first_number=0,
+                     min_base_quality=0, decode_threads=1):
+    """A BAM (or FASTA/Q) file through the host reader with regions (vgh_reads_read_all_r), with or without the read filter: the
+    tuple of reads_read_all_f."""
+    l = lib()
+    p, n, rb, mb, nx, rc, rd = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    cnt = l.vgh_reads_read_all_r(os.fsencode(path), decode_threads, min_base_quality, fraction, seed, first_number,
+                                 *bam_filter_args(bam_filter or {}), *_region_args(bam_regions, bam_regions_bed), int(bool(bam_unplaced)),
                                  C.byref(p), C.byref(n), C.byref(rb), C.byref(mb), C.byref(nx), C.byref(rc), C.byref(rd))
     if cnt < 0:
         raise RuntimeError(l.vgh_last_error().decode())

@@ -85,6 +85,7 @@ def load_library():
         "vgmi_fastq_subsample_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "vgmi_fastq_set_bam_filter": (i32, [vp, u32, u32, u32, C.c_char_p, C.c_double]),
         "vgmi_fastq_bam_filter_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "vgmi_fastq_set_bam_regions": (i32, [vp, u32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
         "vgmi_sketch_keys": (i32, [vp, vp, sz, vp, sz, u32, vp]),
         "vgmi_bloom_params": (i32, [u64, C.c_double, C.POINTER(u64), C.POINTER(u32)]),
         "vgmi_bloom_create": (i32, [vp, u64, u32, vp]),
@@ -423,6 +424,24 @@ class Context:
                 raise VgmiError(rc, msg)
         self._filter_streams.add(fq.value)
 
+    def _set_bam_regions(self, fq, bam_regions, bam_unplaced):
+        """vgmi_fastq_set_bam_regions on a stream just opened; a refusal closes the stream and raises.  None (the default) does not call
+        the C entry at all; a list of (ref, beg, end), 0-based half-open, in any order, calls it once -- the empty list too."""
+        if bam_regions is None:
+            if bam_unplaced:
+                raise ValueError("bam_unplaced needs bam_regions")
+            return
+        n = len(bam_regions)
+        ref = (C.c_int32 * max(n, 1))(*[int(r[0]) for r in bam_regions])
+        beg = (C.c_int64 * max(n, 1))(*[int(r[1]) for r in bam_regions])
+        end = (C.c_int64 * max(n, 1))(*[int(r[2]) for r in bam_regions])
+        rc = self._l.vgmi_fastq_set_bam_regions(fq, n, ref, beg, end, int(bool(bam_unplaced)))
+        if rc:
+            msg = self._l.vgmi_last_error(self._h).decode()
+            self._l.vgmi_fastq_close(fq, None, None, None, None, None, 0, None)
+            raise VgmiError(rc, msg)
+        self._filter_streams.add(fq.value)
+
     def _with_seen(self, fq, res):
         """res, the dict a stream is about to return, with n_seen (vgmi_fastq_subsample_stats) when its setter was called; called
         in front of vgmi_fastq_close.  A stream whose setter was never called is not asked and res stays as it is."""
@@ -497,7 +516,7 @@ class Context:
         return self._bgzf_stream(fq, comp, piece)
 
     def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None,
-                 filter_order=0):
+                 filter_order=0, bam_regions=None, bam_unplaced=False, regions_first=False):
         """A BAM file's block-gzip bytes through the device inflate + BAM record kernels (vgmi_fastq_open_bam): header_bytes = the
         header's length in the decompressed stream (magic to the last reference), n_ref its number of references.  Returns the dict of fastq_bgzf; consumed
         counts decompressed bytes, header included."""
@@ -505,6 +524,10 @@ class Context:
         self._chk(self._l.vgmi_fastq_open_bam(self._h, header_bytes, n_ref, C.byref(fq)))
         # bam_filter: the read filter (vgmi_fastq_set_bam_filter; the dict then has bam_records, bam_reads); filter_order 0 / 1 / 2: that
         # setter in front of, between or behind the other two
+        # bam_regions=[(ref, beg, end), ...], bam_unplaced: the region list (vgmi_fastq_set_bam_regions), set behind the other setters or,
+        # with regions_first, in front of them
+        if regions_first:
+            self._set_bam_regions(fq, bam_regions, bam_unplaced)
         if filter_order == 0:
             self._set_bam_filter(fq, bam_filter)
         if filter_order == 1:
@@ -515,6 +538,8 @@ class Context:
             self._set_options(fq, min_quality, subsample, subsample_first)
         if filter_order == 2:
             self._set_bam_filter(fq, bam_filter)
+        if not regions_first:
+            self._set_bam_regions(fq, bam_regions, bam_unplaced)
         return self._bgzf_stream(fq, comp, piece)
 
     def _bgzf_stream(self, fq, comp, piece):
