@@ -362,7 +362,7 @@ class Context:
 
     def fastq_text(self, text, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None):
         """Device-side FASTQ parser over one stream of file text (bytes), committed in pieces of `piece` bytes (default:
-        whole staging buffers).  min_quality: bases whose quality is below it are counted as N (vgmi_fastq_set_min_quality; 0 = off).
+        whole staging buffers; a list or tuple gives a size per commit, the last one from there on).  min_quality: bases whose quality is below it are counted as N (vgmi_fastq_set_min_quality; 0 = off).
         subsample=(F, S): a seeded fraction of the reads is kept (vgmi_fastq_set_subsample); the dict then has n_seen, the reads the
         device numbered, and n_records counts the kept ones.  Returns dict(n_records, n_bases, consumed, stopped, tail, masked_bases)."""
         fq = C.c_void_p()
@@ -479,12 +479,17 @@ class Context:
 
     def _text_stream(self, fq, text, piece):
         mv = memoryview(text)
-        pos = 0
+        pos, n_call = 0, 0
         try:
             while True:
                 buf, cap = C.c_void_p(), C.c_size_t()
                 self._chk(self._l.vgmi_fastq_acquire(fq, C.byref(buf), C.byref(cap)))
-                n = min(cap.value if piece is None else min(piece, cap.value), len(mv) - pos)
+                if isinstance(piece, (list, tuple)):      # a size per call (the last one from there on)
+                    want = piece[min(n_call, len(piece) - 1)]
+                else:
+                    want = piece
+                n_call += 1
+                n = min(cap.value if want is None else min(want, cap.value), len(mv) - pos)
                 C.memmove(buf, bytes(mv[pos:pos + n]), n)
                 self._chk(self._l.vgmi_fastq_commit(fq, n))
                 pos += n
