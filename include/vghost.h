@@ -118,6 +118,19 @@ int64_t vgh_reads_read_all_r(const char *path, uint32_t decode_threads, uint32_t
                              double bam_min_value, const char *bam_regions, const char *bam_regions_bed, int bam_unplaced, char **block_out,
                              size_t *n_bytes_out, uint64_t *read_base, uint64_t *masked_bases, uint64_t *next_number, uint64_t *bam_records,
                              uint64_t *bam_reads);
+/* The same with the read filter by length and read quality (the rule of vgmi_fastq_set_read_filter, csrc/vgmi_read_filter.h), applied
+ * behind subsampling on the file's own qualities: the block holds the reads that pass.  read_filter NULL or all zero:
+ * vgh_reads_read_all_r.  read_filter_stats (may be NULL): 5 values -- the reads evaluated (those subsampling kept), then the reads
+ * dropped as short, long, low fraction, low mean.  VGMI_E_INVALID, with the field's message, for a field out of range. */
+int64_t vgh_reads_read_all_l(const char *path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char *bam_tag,
+                             double bam_min_value, const char *bam_regions, const char *bam_regions_bed, int bam_unplaced,
+                             const vgmi_read_filter *read_filter, char **block_out, size_t *n_bytes_out, uint64_t *read_base,
+                             uint64_t *masked_bases, uint64_t *next_number, uint64_t *bam_records, uint64_t *bam_reads,
+                             uint64_t *read_filter_stats);
+/* "Q" with at most one fractional digit as tenths of a Phred unit, from its characters alone (never through a double): "7" -> 70,
+ * "7.5" -> 75; VGMI_E_INVALID for a sign, a leading zero in front of a digit, two fractional digits, anything above 93.0 or not a number. */
+int vgh_parse_quality_tenths(const char *text, uint32_t *tenths);
 /* What the device path of vgh_sample_count makes of an input file, from its first bytes (no device involved): kind = "plain" |
  * "gzip" | "bgzf"; first_byte = the first byte of its text (-1: it has none); bam = block gzip whose text starts with "BAM\1";
  * fasta = the text starts with '>' and goes to the device's FASTA parser (VGH_DEVICE_FASTA=0: never).  Any pointer may be NULL. */
@@ -189,6 +202,18 @@ int vgh_sample_count_r(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fas
                        double fraction, uint64_t seed, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq,
                        const char *bam_tag, double bam_min_value, const char *bam_regions, const char *bam_regions_bed, int bam_unplaced,
                        uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases, uint64_t *bam_records, uint64_t *bam_reads);
+/* The same with the read filter by length and read quality (genotype --min-read-length / --max-read-length / --min-read-quality /
+ * --max-low-quality; the rule: vgmi_fastq_set_read_filter): every file's reads that subsampling kept are evaluated, on the device
+ * and wherever the host reader serves, and a read that fails is not a read.  A FASTA file takes the length tests through the host
+ * reader.  read_filter NULL or all zero: vgh_sample_count_r.  read_filter_stats (may be NULL): 5 values as vgh_reads_read_all_l,
+ * summed over the files. */
+int vgh_sample_count_l(const vgh_graph *g, vgmi_ctx *ctx, const char *const *fastq_paths, size_t n_files,
+                       uint32_t threads, uint32_t sample_ploidy, int use_depth, uint8_t *cov_out,
+                       uint8_t *cov_node_out, uint64_t *hist_out, vgh_sample_stats *stats, uint32_t min_base_quality,
+                       double fraction, uint64_t seed, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq,
+                       const char *bam_tag, double bam_min_value, const char *bam_regions, const char *bam_regions_bed, int bam_unplaced,
+                       const vgmi_read_filter *read_filter, uint64_t *reads_seen, uint64_t *reads_kept, uint64_t *masked_bases,
+                       uint64_t *bam_records, uint64_t *bam_reads, uint64_t *read_filter_stats);
 
 /* Coverage statistics alone (Varigraph::kmer_read / cal_ave_cov_kmer): hist = masked coverage histogram
  * (vgmi_counts_finish).  Fills read_depth, hap_kmer_coverage, max_coverage, hom_coverage of *stats; returns

@@ -319,6 +319,27 @@ int vgmi_fastq_bam_filter_stats(vgmi_fastq *fq, uint64_t *records, uint64_t *rea
  * [0, n_ref), a beg or an end out of range, more than 2^20 intervals left after merging, unplaced != 0 with n == 0.  The stream
  * serves on after either, with the list it had. */
 int vgmi_fastq_set_bam_regions(vgmi_fastq *fq, uint32_t n, const int32_t *ref, const int64_t *beg, const int64_t *end, int unplaced);
+/* The read filter: whole reads dropped by length and by read quality (the rule in csrc/vgmi_read_filter.h, integer arithmetic only).
+ * Every field 0 = off, and the all-zero struct makes the stream the one that never called this.
+ *   min_len, max_len   a read shorter than min_len or (max_len != 0) longer than max_len is dropped
+ *   min_mean_q         tenths of a Phred unit, 0 .. 930: dropped if the mean ERROR PROBABILITY of its bases is above 10^(-min_mean_q/100)
+ *                      (sum E[q_i] > E10[min_mean_q] * len over a fixed-point table; equality passes)
+ *   lowq_below, lowq_max_pct   0 .. 93 and 0 .. 100: dropped if strictly more than lowq_max_pct percent of its bases have q < lowq_below
+ * q of a base: FASTQ clamp(byte - 33, 0, 93), BAM min(QUAL, 93); a BAM record whose QUAL[0] is 0xff passes both quality tests.  The
+ * tests apply in the order short, long, low fraction, low mean, and the first that fails is the read's class.  They are evaluated on
+ * the reads subsampling kept (the reads' numbers do not change), on the file's own qualities; a dropped read is not a read, as with
+ * vgmi_fastq_set_subsample.  A FASTA stream accepts quality-only fields without effect and refuses length bounds (VGMI_E_INVALID).
+ * Before the stream's first commit only: VGMI_E_STATE afterwards.  VGMI_E_INVALID, each with its own message: max_len below min_len,
+ * min_mean_q above 930, lowq_below above 93, lowq_max_pct above 100, a percentage without a bound.  The stream serves on after
+ * either, with the rule it had; callable in any order with the other setters. */
+typedef struct vgmi_read_filter {
+    uint32_t min_len, max_len, min_mean_q, lowq_below, lowq_max_pct;
+} vgmi_read_filter;
+int vgmi_fastq_set_read_filter(vgmi_fastq *fq, const vgmi_read_filter *rule);
+/* What the filter did to the reads the device has accepted: *evaluated = the reads subsampling kept (n_records + the four classes),
+ * and the reads dropped by class; waits for the stream.  Without a filter: evaluated = n_records, the classes 0.  Valid until close. */
+int vgmi_fastq_read_filter_stats(vgmi_fastq *fq, uint64_t *evaluated, uint64_t *n_short, uint64_t *n_long, uint64_t *n_low_fraction,
+                                 uint64_t *n_low_mean);
 
 /* K1 alone: the key every position of a read block emits, for emitter parity tests.
  * keys_out[i] = key of the k-mer ENDING at byte i, or UINT64_MAX when the reference emits nothing

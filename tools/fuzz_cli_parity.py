@@ -2,7 +2,7 @@
 """Drawn end-to-end cases through both CLIs (the unmodified reference, oracle/_ref/varigraph_det, and varigraph-mi) on one GPU box:
 genome size, variant mix, cohort size and ploidy, k, construct mode, reads per sample and every genotype option are drawn from a seed;
 graph.bin and every VCF must be byte-identical, or both must refuse.  Prints one line per case and the parameters of any difference.
-  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample] [--bam-filter] [--bam-regions]
+  fuzz_cli_parity.py <first seed> <cases> [--k K] [--genome G] [--max-ploidy N] [--max-vcf-samples N] [--only-wide-ploidy] [--subsample] [--bam-filter] [--bam-regions] [--read-filter]
 --max-ploidy N (default 4: every seed draws the case it always drew) adds ploidy 5 .. N to what the cohort's and the sample's ploidy are drawn from.
 --max-vcf-samples N (default 7: every seed draws the case it always drew) adds cohorts of 24, 33, 48, 64, 100, 127, 130, 160 and 255 diploid
 VCF samples, as far as N allows, to what a diploid cohort's size is drawn from: graphs of 49 to 511 haplotypes, 7 to 64 bytes of haplotype bits
@@ -20,6 +20,10 @@ options, the reference the twin FASTQ of the records that pass by the Python mod
 BAM files over four references with drawn positions and CIGARs, and draws a region list, a BED file or both, with or without
 --bam-regions-unplaced (DESIGN_INGEST_HMM 4.24): varigraph-mi reads the BAM files with the options, the reference the twin FASTQ of the
 records that pass by the Python model (tests/bam_region_cases.py).
+--read-filter (off by default, and only for cases the three options above left alone) gives half of the cases drawn parameters for
+`genotype --min-read-length / --max-read-length / --min-read-quality / --max-low-quality` (DESIGN_INGEST_HMM 4.25) and draws the
+qualities of the case's reads afresh, read by read, from five profiles, so that every test drops some: varigraph-mi reads the case's
+files with the options, the reference the twin files of the reads that pass by the Python model (tests/read_filter_cases.py).
   fuzz_cli_parity.py --check-bam-regions <first seed> <cases>
 needs no device: the conversion alone -- drawn records, regions and option text -- through the host decoder (vgh_reads_read_all_r)
 against the model's passing records."""
@@ -91,6 +95,47 @@ def filtered(path, fraction, sub_seed):
     if not text.endswith(b"\n"): text += b"\n"
     out = path + ".kept.fq"
     open(out, "wb").write(subsample_cases.filtered_fastq_text(text, fraction, sub_seed)[0])
+    return out
+
+
+READ_FILTER = False      # --read-filter: a drawn case may get the read filter by length and read quality (DESIGN_INGEST_HMM 4.25)
+
+
+def draw_read_filter(qrng):
+    """-> (the options, the model's rule): at least one of the four parameters is on"""
+    import read_filter_cases as R
+    while True:
+        min_len, max_len = int(qrng.choice((0, 0, 50, 120))), int(qrng.choice((0, 0, 0, 140, 150)))
+        q_text = str(qrng.choice(("0", "0", "7.5", "10", "12.3", "20.0")))
+        low = (None, None, (15, 40), (10, 20), (20, 0))[int(qrng.integers(0, 5))]
+        if max_len and max_len < min_len: continue
+        if min_len or max_len or q_text != "0" or low: break
+    opts = []
+    if min_len: opts += ["--min-read-length", str(min_len)]
+    if max_len: opts += ["--max-read-length", str(max_len)]
+    if q_text != "0": opts += ["--min-read-quality", q_text]
+    if low: opts += ["--max-low-quality", f"{low[0]}:{low[1]}"]
+    whole, _, frac = q_text.partition(".")
+    return opts, R.Rule(min_len, max_len, int(whole) * 10 + int(frac or 0), *(low or (0, 0)))
+
+
+def redraw_qualities(path, qrng):
+    """the quality lines of a plain four-line FASTQ file drawn afresh, a profile per read (read_filter_cases.drawn_quality)"""
+    import read_filter_cases as R
+    lines = open(path, "rb").read().split(b"\n")
+    for i in range(3, len(lines), 4):
+        lines[i] = R._ph(R.drawn_quality(qrng, len(lines[i]), int(qrng.choice((0, 0, 0, 0, 1, 2, 3, 4)))))
+    open(path, "wb").write(b"\n".join(lines))
+
+
+def passing(path, rule):
+    """the reads of a FASTQ file (plain, gzip of any number of members, block gzip) that pass the rule, as a plain four-line file"""
+    import read_filter_cases as R
+    raw = open(path, "rb").read()
+    text = gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw
+    if not text.endswith(b"\n"): text += b"\n"
+    out = path + ".pass.fq"
+    open(out, "wb").write(R.filtered_fastq_text(text, rule)[0])
     return out
 
 
@@ -260,12 +305,21 @@ def case(seed):
             if rrng.random() < 0.5:
                 regf = draw_regions(rrng, work)
                 desc += ", aligned BAM read files, " + " ".join(regf[0])
+        rff = None
+        if READ_FILTER and sub is None and bamf is None and regf is None:      # a generator of its own, as above
+            qrng = np.random.default_rng([int(seed), 0x4EAD])
+            if qrng.random() < 0.5:
+                rff = draw_read_filter(qrng)
+                desc += ", drawn qualities, " + " ".join(rff[0])
         for i in range(n_reads_samples):
             who = int(rng.integers(0, n_samples))
             haps = synth.sample_haplotypes(ref, variants, gts, who, vploidy)
             fq = tc._write_fastq(os.path.join(work, f"s{i}"), haps, pairs, seed=int(seed) * 10 + i)
+            if rff:
+                for f in fq: redraw_qualities(f, qrng)
             fq = [dress(f, rng) for f in fq]
             cfg += f"ind{i} " + " ".join(fq) + "\n"
+            if rff: cfg_kept += f"ind{i} " + " ".join(passing(f, rff[1]) for f in fq) + "\n"
             if sub: cfg_kept += f"ind{i} " + " ".join(filtered(f, *sub) for f in fq) + "\n"
             if bamf:
                 pairs_ = [as_bam(f, brng, bamf[1]) for f in fq]
@@ -278,7 +332,8 @@ def case(seed):
         outs, codes = {}, {}
         for name, exe, more in (("native", tc.CLI, ["--gpu", "0"]), ("cpu", tc.REF, [])):
             d = os.path.join(work, name); os.makedirs(d)
-            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if (sub or bamf or regf) and name == "cpu" else cfg)
+            open(os.path.join(d, "samples.cfg"), "w").write(cfg_kept if (sub or bamf or regf or rff) and name == "cpu" else cfg)
+            if rff and name == "native": more = more + rff[0]
             if bamf and name == "native": more = more + bamf[0]
             if regf and name == "native": more = more + regf[0]
             if sub and name == "native": more = more + ["--subsample", repr(sub[0]), "--subsample-seed", str(sub[1])]
@@ -322,6 +377,7 @@ if __name__ == "__main__":
         if a == "--subsample": SUBSAMPLE = True
         if a == "--bam-filter": BAM_FILTER = True
         if a == "--bam-regions": BAM_REGIONS = True
+        if a == "--read-filter": READ_FILTER = True
     bad = passed_over = 0
     for s in range(first, first + n):
         t0 = time.time()

@@ -157,6 +157,11 @@ long BamReader::next()
         ++reads_;
         if (!rule_.keep(number_++)) continue;
         const unsigned char* s = r + 36 + l_rn + 4 * (size_t)n_cig;
+        if (rf_.on()) {
+            const int cls = read_filter_class(rf_.p, s + (l_seq + 1) / 2, l_seq, true);
+            ++rf_.n_class[cls];
+            if (cls != READ_PASS) continue;
+        }
         seq_.resize(l_seq);
         for (uint32_t i = 0; i < l_seq; ++i) seq_[i] = nt16[(s[i >> 1] >> ((~i & 1) << 2)) & 15];
         qual_.assign(reinterpret_cast<const char*>(s + (l_seq + 1) / 2), l_seq);

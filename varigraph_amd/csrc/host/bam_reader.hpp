@@ -14,6 +14,7 @@
 #include "bam_regions.hpp"
 #include "byte_source.hpp"
 #include "../vgmi_bam_filter.h"
+#include "../vgmi_read_filter.h"
 #include "../vgmi_subsample.h"
 
 namespace vgh {
@@ -53,6 +54,11 @@ public:
         regions_ = std::move(list);
         unplaced_ = unplaced && !regions_.empty();
     }
+    // The read filter by length and read quality (vgmi_read_filter.h): applied behind subsampling on the record's QUAL bytes as stored (a
+    // record whose QUAL[0] is 0xff passes both quality tests); a read it drops is passed over undecoded.  read_filter().n_class: the
+    // evaluated reads by class ([0]: passed).
+    void read_filter(const ReadFilterRule& rule) { rf_ = rule; }
+    const ReadFilterRule& read_filter() const { return rf_; }
     uint64_t records() const { return records_; }
     uint64_t reads() const { return reads_; }
     const std::string& seq() const { return seq_; }
@@ -81,6 +87,7 @@ private:
     std::vector<uint32_t> ref_lengths_;
     std::vector<BamInterval> regions_;
     bool unplaced_ = false;
+    ReadFilterRule rf_;
 };
 
 // the bytes of `path` as ByteSource::open delivers them; is_bam: block gzip whose text starts with "BAM\1" (decided from content)

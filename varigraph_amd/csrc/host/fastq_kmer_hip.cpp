@@ -40,6 +40,7 @@ struct ReadOpts {
     SubsampleRule sub;
     BamFilterParams filt = bam_filter_params();
     BamRegionSpec reg;      // the regions of BAM files (on() false: none), resolved against each file's header
+    ReadFilterParams rf = read_filter_params();      // the read filter by length and read quality (on == 0: off), behind subsampling
     bool filtered() const { return filt.on || reg.on(); }
 };
 
@@ -49,7 +50,22 @@ struct DeviceFileResult {
     uint64_t bam_records = 0, bam_reads = 0;      // with a read filter, a BAM file: records examined and the reads among them, device and host reader together
     bool bam = false;
     uint64_t bed_skipped = 0;      // with a BED file: its lines whose reference this file's header lacks
+    uint64_t rf_dropped[4] = {0, 0, 0, 0};      // with a read filter: the reads it dropped (short, long, low fraction, low mean), device and host reader together
 };
+
+// VGH_TIMING: what the read filter by length and read quality did to one file (nothing is printed without the options)
+void report_read_filter(const std::string& path, uint64_t kept, const uint64_t dropped[4], const ReadFilterParams& rf)
+{
+    if (rf.on && std::getenv("VGH_TIMING"))
+        std::fprintf(stderr, "[varigraph-mi] '%s': %llu of %llu reads kept (%llu short, %llu long, %llu low fraction, %llu low mean)\n", path.c_str(),
+                     (unsigned long long)kept, (unsigned long long)(kept + dropped[0] + dropped[1] + dropped[2] + dropped[3]), (unsigned long long)dropped[0],
+                     (unsigned long long)dropped[1], (unsigned long long)dropped[2], (unsigned long long)dropped[3]);
+}
+template <class Reader>
+void add_read_filter_counts(const Reader& rd, uint64_t dropped[4])
+{
+    for (int c = 0; c < 4; ++c) dropped[c] += rd.read_filter().n_class[c + 1];
+}
 
 // the options a filter was made of, as the command line spells them
 std::string filter_text(const BamFilterParams& f)
@@ -125,12 +141,14 @@ struct Channel {  // parser threads -> submitting thread
     uint64_t seen = 0;      // reads the finished parsers numbered (all of them without subsampling)
     uint64_t bam_records = 0, bam_reads = 0;      // with a read filter: the BAM files' records and the reads among them
     uint64_t bed_skipped = 0;
+    uint64_t rf_dropped[4] = {0, 0, 0, 0};      // with a read filter: the reads the finished parsers dropped, by class
 };
 
 void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsigned decode_threads, const ReadOpts o)
 {
     const uint32_t min_q = o.min_q;
     uint64_t file_masked = 0, file_reads = 0, file_seen = 0, bam_records = 0, bam_reads = 0, bed_skipped = 0;
+    uint64_t rf_dropped[4] = {0, 0, 0, 0};
     auto grab = [&]() {
         std::unique_lock<std::mutex> lk(ch.mu);
         ch.cv_free.wait(lk, [&] { return !ch.free_list.empty(); });
@@ -151,6 +169,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         std::unique_ptr<Block> cur = grab();
         if (o.sub.on) rd.subsample(o.sub, 0);      // the whole file through this reader: its reads are numbered from 0
         set_filter(rd, o, &bed_skipped);
+        if (o.rf.on) rd.read_filter(ReadFilterRule(o.rf));
         while (rd.next() >= 0) {  // stops at EOF (-1) and at the first truncated record (-2)
             const uint64_t masked = min_q ? rd.mask_below(min_q) : 0;
             const std::string& s = rd.seq();
@@ -172,6 +191,7 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         }
         file_seen = o.sub.on ? rd.next_number() : file_reads;
         add_filter_counts(rd, o, bam_records, bam_reads);
+        add_read_filter_counts(rd, rf_dropped);
         if (cur->n_reads) push(std::move(cur));
         else {
             std::lock_guard<std::mutex> lk(ch.mu);
@@ -191,7 +211,9 @@ void parse_file(const std::string& path, Channel& ch, size_t block_bytes, unsign
         report_masked(path, file_masked, min_q);
         report_subsample(path, file_seen, file_reads, o.sub);
         if (is_bam) report_filter(path, bam_records, bam_reads, o, bed_skipped);
+        report_read_filter(path, file_reads, rf_dropped, o.rf);
         std::lock_guard<std::mutex> lk(ch.mu);
+        for (int c = 0; c < 4; ++c) ch.rf_dropped[c] += rf_dropped[c];
         ch.seen += file_seen;
         ch.bam_records += bam_records;
         ch.bam_reads += bam_reads;
@@ -217,6 +239,7 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
     if (o.sub.on) rd.subsample(o.sub, res.seen);      // the device's n_seen (0 where the device took nothing): one numbering per file
     set_filter(rd, o, &res.bed_skipped);      // (resolved against this reader's header: the same file, the same list)
     if (std::is_same_v<Reader, BamReader>) res.bam = true;
+    if (o.rf.on) rd.read_filter(ReadFilterRule(o.rf));      // the device's rule, wherever the host reader serves: the two readers' class counts add up
     std::vector<char> block;
     block.reserve(block_bytes + 1024);
     size_t in_block = 0;
@@ -242,6 +265,7 @@ void host_leg(vgmi_ctx* ctx, Reader& rd, const std::string& path, size_t block_b
     flush();
     res.seen = o.sub.on ? rd.next_number() : n_reads;
     add_filter_counts(rd, o, res.bam_records, res.bam_reads);
+    add_read_filter_counts(rd, res.rf_dropped);
 }
 
 // plain file: `threads` readers fill one pinned buffer side by side (a single read(2) stream moves 3-6 GB/s, the link
@@ -373,6 +397,13 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         }
     }
 
+    // A FASTA record's length is known on the device only behind the scan that places it: with length bounds the host reader serves the file
+    if (fasta && o.rf.lengths()) {
+        FastxReader rd(ByteSource::open(path, threads));
+        host_leg(ctx, rd, path, block_bytes, submit_mu, o, res);
+        return res;
+    }
+
     // ordinary gzip: inflated on the device too (vgmi_gunzip.hip; VGH_DEVICE_GUNZIP=0: by the host's inflate threads, the A/B and
     // the path that takes over wherever the device gives a stream up)
     bool dev_gunzip = !plain && !bgzf;
@@ -393,6 +424,14 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         const std::string why = vgmi_last_error(ctx);
         (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
         throw std::runtime_error(why);
+    }
+    if (o.rf.on && !fasta) {      // (FASTA text has no qualities, and with length bounds the file went to the host reader above)
+        const vgmi_read_filter r{o.rf.min_len, o.rf.max_len, o.rf.min_mean_q, o.rf.lowq_below, o.rf.lowq_max_pct};
+        if (vgmi_fastq_set_read_filter(fq, &r) != VGMI_OK) {
+            const std::string why = vgmi_last_error(ctx);
+            (void)vgmi_fastq_close(fq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+            throw std::runtime_error(why);
+        }
     }
     const bool filtered = bam && o.filtered();
     if (bam && o.reg.on()) {
@@ -427,6 +466,11 @@ DeviceFileResult device_file(vgmi_ctx* ctx, const std::string& path, size_t bloc
         if (min_q && vgmi_fastq_masked_bases(fq, &res.masked) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         if (o.sub.on && vgmi_fastq_subsample_stats(fq, &dev_seen, &dev_kept) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
         if (filtered && vgmi_fastq_bam_filter_stats(fq, &res.bam_records, &res.bam_reads) != VGMI_OK) throw std::runtime_error(vgmi_last_error(ctx));
+        if (o.rf.on && !fasta) {
+            uint64_t evaluated = 0;
+            if (vgmi_fastq_read_filter_stats(fq, &evaluated, &res.rf_dropped[0], &res.rf_dropped[1], &res.rf_dropped[2], &res.rf_dropped[3]) != VGMI_OK)
+                throw std::runtime_error(vgmi_last_error(ctx));
+        }
         closed = true;
         if (vgmi_fastq_close(fq, &n_rec, &n_bases, &consumed, &stopped, tail.data(), tail.size(), &tail_len) != VGMI_OK)
             throw std::runtime_error(vgmi_last_error(ctx));
@@ -642,7 +686,32 @@ FastqKmerHipR::FastqKmerHipR(vgmi_ctx* ctx, const std::vector<std::string>& fast
 void FastqKmerHip::count_files_regions(const uint32_t min_q, const SubsampleRule& sub, const BamFilterParams& filt, const BamRegionSpec& regions,
                                        uint64_t& masked, uint64_t& seen, uint64_t& bam_records, uint64_t& bam_reads, uint64_t& bed_skipped)
 {
+    uint64_t dropped[4];
+    count_files_read_filter(min_q, sub, filt, regions, read_filter_params(), masked, seen, bam_records, bam_reads, bed_skipped, dropped);
+}
+
+FastqKmerHipL::FastqKmerHipL(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads, uint32_t min_base_quality,
+                             double fraction, uint64_t seed, const BamFilterParams& filter, const BamRegionSpec& regions, const ReadFilterParams& read_filter,
+                             size_t block_bytes)
+    : FastqKmerHip(ctx, fastqFileNameVec, kmerLen, threads, block_bytes), min_q_(min_base_quality), filt_(filter), reg_(regions), rf_(read_filter)
+{
+    if (min_q_ > 93) throw std::runtime_error("minimum base quality " + std::to_string(min_q_) + " is out of range (0..93, Phred+33)");
+    if (!subsample_fraction_valid(fraction))
+        throw std::runtime_error("subsampling fraction " + std::to_string(fraction) + " is out of range (0 < fraction <= 1)");
+    if (reg_.unplaced && !reg_.on()) throw std::runtime_error(bam_regions_invalid_text(4));
+    if (const int bad = read_filter_invalid(rf_.min_len, rf_.max_len, rf_.min_mean_q, rf_.lowq_below, rf_.lowq_max_pct))
+        throw std::runtime_error(read_filter_invalid_text(bad));
+    rf_ = read_filter_params(rf_.min_len, rf_.max_len, rf_.min_mean_q, rf_.lowq_below, rf_.lowq_max_pct);
+    rule_ = SubsampleRule(fraction, seed);
+}
+
+void FastqKmerHip::count_files_read_filter(const uint32_t min_q, const SubsampleRule& sub, const BamFilterParams& filt, const BamRegionSpec& regions,
+                                           const ReadFilterParams& rf, uint64_t& masked, uint64_t& seen, uint64_t& bam_records, uint64_t& bam_reads,
+                                           uint64_t& bed_skipped, uint64_t dropped[4])
+{
     ReadOpts o;
+    o.rf = rf;
+    dropped[0] = dropped[1] = dropped[2] = dropped[3] = 0;
     o.min_q = min_q;
     o.sub = sub;
     o.filt = filt;
@@ -676,7 +745,9 @@ void FastqKmerHip::count_files_regions(const uint32_t min_q, const SubsampleRule
                     report_masked(files_[i], r.masked, min_q);
                     report_subsample(files_[i], r.seen, r.n_reads, o.sub);
                     if (r.bam) report_filter(files_[i], r.bam_records, r.bam_reads, o, r.bed_skipped);
+                    report_read_filter(files_[i], r.n_reads, r.rf_dropped, o.rf);
                     std::lock_guard<std::mutex> lk(res_mu);
+                    for (int c = 0; c < 4; ++c) dropped[c] += r.rf_dropped[c];
                     bam_records += r.bam_records;
                     bam_reads += r.bam_reads;
                     bed_skipped += r.bed_skipped;
@@ -751,6 +822,7 @@ void FastqKmerHip::count_files_regions(const uint32_t min_q, const SubsampleRule
     bam_records = ch.bam_records;
     bam_reads = ch.bam_reads;
     bed_skipped = ch.bed_skipped;
+    for (int c = 0; c < 4; ++c) dropped[c] = ch.rf_dropped[c];
 }
 
 void FastqKmerHip::fetch(uint8_t* cov, uint8_t* cov_node, uint64_t* hist256)

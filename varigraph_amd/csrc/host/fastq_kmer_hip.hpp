@@ -21,6 +21,7 @@
 
 #include "../vgmi_bam_filter.h"
 #include "bam_regions.hpp"
+#include "../vgmi_read_filter.h"
 #include "../vgmi_subsample.h"
 
 struct vgmi_ctx;
@@ -56,6 +57,11 @@ protected:
     // file's header lacks, summed over the BAM files
     void count_files_regions(uint32_t min_base_quality, const SubsampleRule& sub, const BamFilterParams& filter, const BamRegionSpec& regions,
                              uint64_t& masked_bases, uint64_t& reads_seen, uint64_t& bam_records, uint64_t& bam_reads, uint64_t& bed_skipped);
+    // ... and with a read filter by length and read quality for every file (read_filter.on == 0: count_files_regions); dropped gets the reads
+    // it dropped: short, long, low fraction, low mean
+    void count_files_read_filter(uint32_t min_base_quality, const SubsampleRule& sub, const BamFilterParams& filter, const BamRegionSpec& regions,
+                                 const ReadFilterParams& read_filter, uint64_t& masked_bases, uint64_t& reads_seen, uint64_t& bam_records,
+                                 uint64_t& bam_reads, uint64_t& bed_skipped, uint64_t dropped[4]);
 
 private:
     vgmi_ctx* ctx_;
@@ -157,6 +163,37 @@ private:
     SubsampleRule rule_;
     BamFilterParams filt_;
     BamRegionSpec reg_;
+};
+
+// FastqKmerHipR with the read filter by length and read quality (genotype --min-read-length / --max-read-length / --min-read-quality /
+// --max-low-quality; vgmi_read_filter.h has the rule): evaluated on the reads subsampling kept, on the device and wherever the host
+// reader serves, on the file's own qualities.  A dropped read is not a read.  A FASTA file has no qualities: the length tests alone
+// apply, through the host reader.  read_filter.on == 0 counts what FastqKmerHipR counts.  A class of its own for FastqKmerHipQ's reason.
+class FastqKmerHipL : public FastqKmerHip {
+public:
+    uint64_t mMaskedBases = 0;
+    uint64_t mReadsSeen = 0;
+    uint64_t mBamRecords = 0;
+    uint64_t mBamReads = 0;
+    uint64_t mBedSkipped = 0;
+    uint64_t mReadsDropped[4] = {0, 0, 0, 0};   // by the read filter: short, long, low fraction, low mean (evaluated = mReadNum + their sum)
+
+    // throws as FastqKmerHipR, and for read_filter fields out of range (read_filter_invalid)
+    FastqKmerHipL(vgmi_ctx* ctx, const std::vector<std::string>& fastqFileNameVec, uint32_t kmerLen, uint32_t threads, uint32_t min_base_quality,
+                  double fraction, uint64_t seed, const BamFilterParams& filter, const BamRegionSpec& regions, const ReadFilterParams& read_filter,
+                  size_t block_bytes = 32u << 20);
+
+    void build_fastq_index_read_filter()
+    {
+        count_files_read_filter(min_q_, rule_, filt_, reg_, rf_, mMaskedBases, mReadsSeen, mBamRecords, mBamReads, mBedSkipped, mReadsDropped);
+    }
+
+private:
+    uint32_t min_q_;
+    SubsampleRule rule_;
+    BamFilterParams filt_;
+    BamRegionSpec reg_;
+    ReadFilterParams rf_;
 };
 
 // What the device path makes of an input file, decided from its first bytes alone (no device involved): the container by the

@@ -63,7 +63,15 @@ long FastxReader::next_sampled()
 {
     for (;;) {
         const long r = next_record();
-        if (r < 0 || rule_.keep(number_++)) return r;      // (a truncated record ends the file: it has no number)
+        if (r < 0) return r;      // (a truncated record ends the file: it has no number)
+        if (!rule_.keep(number_++)) continue;
+        if (!rf_.on()) return r;
+        const bool fastq = qual_.size() == seq_.size() && !qual_.empty();
+        if (fastq && rf_.p.quality() && seq_.size() > VGH_READ_FILTER_MAX_LEN)
+            throw std::runtime_error("a FASTQ record of " + std::to_string(seq_.size()) + " bases ('" + name_ + "') is too long for --min-read-quality / --max-low-quality (2^31 - 1 at most)");
+        const int cls = read_filter_class(rf_.p, fastq ? reinterpret_cast<const unsigned char*>(qual_.data()) : nullptr, seq_.size(), false);
+        ++rf_.n_class[cls];
+        if (cls == READ_PASS) return r;
     }
 }
 

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "byte_source.hpp"
+#include "../vgmi_read_filter.h"
 #include "../vgmi_subsample.h"
 
 namespace vgh {
@@ -28,7 +29,7 @@ public:
     FastxReader& operator=(const FastxReader&) = delete;
 
     // >= 0: sequence length (seq() holds it); -1: end of file; -2: truncated quality
-    long next() { return rule_.on ? next_sampled() : next_record(); }      // (without the rule: the reader of before, one call)
+    long next() { return rule_.on || rf_.on() ? next_sampled() : next_record(); }      // (without a rule: the reader of before, one call)
     // Subsampling (vgmi_subsample.h): the records next() reads from here on are numbered first_number, first_number + 1, ... and the ones
     // the rule drops are passed over -- next() returns the kept ones only.  first_number is the file number of the next record: 0 at
     // the start of a file, the device's n_seen where this reader takes a stream over.  next_number(): the number the record after
@@ -39,6 +40,12 @@ public:
         number_ = first_number;
     }
     uint64_t next_number() const { return number_; }
+    // The read filter (vgmi_read_filter.h): from here on next() applies the rule behind subsampling -- a record subsampling drops is not
+    // evaluated -- on the record's own quality bytes, and returns the passing records only.  A FASTA record has no qualities: the length
+    // tests alone apply.  read_filter().n_class: the evaluated records by class ([0]: passed).  A record of 2^31 bases or more under a
+    // quality test throws: the rule's sums are exact below that, and such a record is a contig, not a read.
+    void read_filter(const ReadFilterRule& rule) { rf_ = rule; }
+    const ReadFilterRule& read_filter() const { return rf_; }
     const std::string& seq() const { return seq_; }
     const std::string& name() const { return name_; }  // up to the first whitespace of the header line
     const std::string& qual() const { return qual_; }  // the record's quality lines joined (empty for a FASTA record)
@@ -49,7 +56,7 @@ public:
 
 private:
     long next_record();   // next() without the rule
-    long next_sampled();  // ... and with it: the next record the rule keeps
+    long next_sampled();  // ... and with subsampling and / or a read filter: the next record they keep
     int getc();
     // append up to (not including) the next '\n' to s; returns false at EOF with nothing read
     bool get_line(std::string& s, bool append);
@@ -65,6 +72,7 @@ private:
     std::string seq_, qual_, name_;
     SubsampleRule rule_;
     uint64_t number_ = 0;
+    ReadFilterRule rf_;
 };
 
 }  // namespace vgh

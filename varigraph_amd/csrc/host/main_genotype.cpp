@@ -53,6 +53,10 @@ struct Options {
     std::string bam_tag;                // --bam-min-tag TAG:VALUE (empty: none)
     double bam_tag_value = 0.0;
     vgh::BamRegionSpec bam_regions;     // --bam-regions, --bam-regions-file, --bam-regions-unplaced; the ranks of --procs inherit them
+    // the read filter by length and read quality (vgmi_read_filter.h); the ranks of --procs inherit all of it
+    unsigned long long min_read_length = 0, max_read_length = 0;   // --min-read-length, --max-read-length (0: off / none)
+    uint32_t min_read_quality = 0;      // --min-read-quality, in tenths (0: off)
+    uint32_t lowq_below = 0, lowq_max_pct = 0;      // --max-low-quality Q:PCT
     int min_base_quality = 0;   // --min-base-quality: bases of FASTQ / BAM reads below it are counted as N (0: off); the ranks of --procs inherit it
 };
 
@@ -98,6 +102,16 @@ void usage(const char* argv0)
               << "    --bam-regions-file BED  regions from a BED file (columns 1-3, 0-based half-open), joined with --bam-regions; lines\n"
               << "                           whose reference a header lacks are skipped [none]\n"
               << "    --bam-regions-unplaced  with regions: unmapped records without a reference (refID -1) are reads too\n"
+              << "    --min-read-length INT  a read shorter than INT bases is not counted [0: off]\n"
+              << "    --max-read-length INT  a read longer than INT bases is not counted [0: none]\n"
+              << "    --min-read-quality Q   a FASTQ / BAM read whose mean error probability is above that of Phred Q is not counted (as chopper\n"
+              << "                           and NanoFilt -q: the mean of the error probabilities, not of the Phred values); Q from 0 to 93 with\n"
+              << "                           at most one fractional digit, e.g. 7.5 [0: off]\n"
+              << "    --max-low-quality Q:PCT  a FASTQ / BAM read with more than PCT percent of its bases below Phred Q is not counted (as fastp\n"
+              << "                           -q Q -u PCT), Q 1-93, PCT 0-100 [off]\n"
+              << "                           The four apply to the reads --subsample kept and to the file's own qualities, whatever\n"
+              << "                           --min-base-quality masks; they judge each read alone and may drop one mate of a pair and keep the\n"
+              << "                           other; FASTA reads have no qualities and take the length bounds only\n"
               << "    --gpu           INT    device ordinal [0]\n"
               << "    --gpus          LIST   several devices, e.g. 0,1,2,3: samples are counted on them in parallel\n"
               << "    --procs                one process per device of --gpus (samples dealt round robin, -t shared out); the table is\n"
@@ -220,6 +234,8 @@ int main_genotype(int argc, char** argv)
         {"bam-min-mapq", required_argument, 0, 16}, {"bam-min-tag", required_argument, 0, 17},
         {"bam-regions", required_argument, 0, 18}, {"bam-regions-file", required_argument, 0, 19},
         {"bam-regions-unplaced", no_argument, 0, 20},
+        {"min-read-length", required_argument, 0, 21}, {"max-read-length", required_argument, 0, 22},
+        {"min-read-quality", required_argument, 0, 23}, {"max-low-quality", required_argument, 0, 24},
         {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -264,6 +280,23 @@ int main_genotype(int argc, char** argv)
         case 18: o.bam_regions.list += (o.bam_regions.list.empty() ? "" : ",") + std::string(optarg); break;
         case 19: o.bam_regions.bed = optarg; break;
         case 20: o.bam_regions.unplaced = true; break;
+        case 21: o.min_read_length = opt_u64("--min-read-length", optarg); break;
+        case 22: o.max_read_length = opt_u64("--max-read-length", optarg); break;
+        case 23:
+            if (!vgh::read_filter_parse_tenths(optarg, &o.min_read_quality))
+                die("Parameter error: --min-read-quality. The provided value must be between 0 and 93 (inclusive), with at most one fractional digit.");
+            break;
+        case 24: {
+            const std::string a = optarg;
+            const size_t colon = a.find(':');
+            if (colon == std::string::npos || colon == 0 || colon + 1 == a.size()) die("Parameter error: --max-low-quality. Expected Q:PCT, e.g. 15:40.");
+            const unsigned long long q = opt_u64("--max-low-quality", a.substr(0, colon).c_str()), pct = opt_u64("--max-low-quality", a.c_str() + colon + 1);
+            if (q < 1 || q > 93) die("Parameter error: --max-low-quality. The quality must be between 1 and 93 (inclusive).");
+            if (pct > 100) die("Parameter error: --max-low-quality. The percentage must be between 0 and 100 (inclusive).");
+            o.lowq_below = (uint32_t)q;
+            o.lowq_max_pct = (uint32_t)pct;
+            break;
+        }
         case 't': o.hmm.threads = std::max(opt_int("-t", optarg), 1); break;
         case 'D': debug = true; break;
         default: usage(argv[0]); return 1;
@@ -293,6 +326,11 @@ int main_genotype(int argc, char** argv)
     if (o.bam_tag_value != o.bam_tag_value) die("Parameter error: --bam-min-tag. The bound must be a number, not NaN.");
     if (o.bam_regions.unplaced && !o.bam_regions.on())
         die("Parameter error: --bam-regions-unplaced. It needs --bam-regions or --bam-regions-file.");
+    if (o.min_read_length > 0xFFFFFFFFull) die("Parameter error: --min-read-length. The provided value must be between 0 and 4294967295 (inclusive).");
+    if (o.max_read_length > 0xFFFFFFFFull) die("Parameter error: --max-read-length. The provided value must be between 0 and 4294967295 (inclusive).");
+    if (o.max_read_length && o.max_read_length < o.min_read_length) die("Parameter error: --max-read-length. The provided value must not be below --min-read-length.");
+    const vgh::ReadFilterParams read_filter = vgh::read_filter_params((uint32_t)o.min_read_length, (uint32_t)o.max_read_length, o.min_read_quality,
+                                                                      o.lowq_below, o.lowq_max_pct);
     const vgh::BamFilterParams bam_filter = vgh::bam_filter_params((uint32_t)o.bam_exclude, (uint32_t)o.bam_require, (uint32_t)o.bam_min_mapq,
                                                                    o.bam_tag.empty() ? nullptr : o.bam_tag.c_str(), o.bam_tag_value);
 
@@ -707,6 +745,13 @@ int main_genotype(int argc, char** argv)
                 }
                 const auto& [name, files] = samples[s];
                 const double ts = secs();
+                if (read_filter.on) {
+                    vgh::FastqKmerHipL fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed, bam_filter,
+                                          o.bam_regions, read_filter);
+                    fk.build_fastq_index_read_filter();
+                    counted(s, fk, dev_i, ts);
+                    continue;
+                }
                 if (o.bam_regions.on()) {
                     vgh::FastqKmerHipR fk(ctx, files, g.k, count_threads, (uint32_t)o.min_base_quality, o.subsample, o.subsample_seed, bam_filter,
                                           o.bam_regions);

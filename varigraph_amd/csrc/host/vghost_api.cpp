@@ -29,9 +29,11 @@ namespace {
 // the number of reads, or VGMI_E_NOMEM.  A sequence ends at its first NUL, read_base counts it whole (src/fastq_kmer.cpp:101 vs :105).
 template <class Reader>
 int64_t reads_block(Reader& rd, uint32_t q, char** block_out, size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases,
-                    const vgh::SubsampleRule* sub = nullptr, uint64_t first_number = 0, uint64_t* next_number = nullptr)
+                    const vgh::SubsampleRule* sub = nullptr, uint64_t first_number = 0, uint64_t* next_number = nullptr,
+                    const vgh::ReadFilterParams* rf = nullptr, uint64_t* rf_stats = nullptr)
 {
     if (sub) rd.subsample(*sub, first_number);
+    if (rf && rf->on) rd.read_filter(vgh::ReadFilterRule(*rf));
     std::string block;
     int64_t n = 0;
     uint64_t rb = 0, masked = 0;
@@ -51,6 +53,12 @@ int64_t reads_block(Reader& rd, uint32_t q, char** block_out, size_t* n_bytes_ou
     if (read_base) *read_base = rb;
     if (masked_bases) *masked_bases = masked;
     if (next_number) *next_number = sub && sub->on ? rd.next_number() : first_number + (uint64_t)n;      // (off: every read is kept, nothing numbers them)
+    if (rf && rf->on && !(sub && sub->on) && next_number) *next_number = first_number + rd.read_filter().evaluated();
+    if (rf_stats) {
+        const vgh::ReadFilterRule& r = rd.read_filter();
+        rf_stats[0] = rf && rf->on ? r.evaluated() : (uint64_t)n;
+        for (int c = 1; c < 5; ++c) rf_stats[c] = r.n_class[c];
+    }
     return n;
 }
 }  // namespace
@@ -243,7 +251,38 @@ int64_t vgh_reads_read_all_r(const char* path, uint32_t decode_threads, uint32_t
                              size_t* n_bytes_out, uint64_t* read_base, uint64_t* masked_bases, uint64_t* next_number, uint64_t* bam_records,
                              uint64_t* bam_reads)
 {
+    return vgh_reads_read_all_l(path, decode_threads, min_base_quality, fraction, seed, first_number, bam_exclude, bam_require, bam_min_mapq, bam_tag,
+                                bam_min_value, bam_regions, bam_regions_bed, bam_unplaced, nullptr, block_out, n_bytes_out, read_base, masked_bases,
+                                next_number, bam_records, bam_reads, nullptr);
+}
+
+int vgh_parse_quality_tenths(const char* text, uint32_t* tenths)
+{
+    if (!tenths) return VGMI_E_INVALID;
+    if (!vgh::read_filter_parse_tenths(text, tenths)) {
+        g_err = std::string("'") + (text ? text : "") + "' is not a quality of 0 to 93 with at most one fractional digit";
+        return VGMI_E_INVALID;
+    }
+    return VGMI_OK;
+}
+
+int64_t vgh_reads_read_all_l(const char* path, uint32_t decode_threads, uint32_t min_base_quality, double fraction, uint64_t seed,
+                             uint64_t first_number, uint32_t bam_exclude, uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag,
+                             double bam_min_value, const char* bam_regions, const char* bam_regions_bed, int bam_unplaced,
+                             const vgmi_read_filter* read_filter, char** block_out, size_t* n_bytes_out, uint64_t* read_base,
+                             uint64_t* masked_bases, uint64_t* next_number, uint64_t* bam_records, uint64_t* bam_reads, uint64_t* read_filter_stats)
+{
     if (!path || !block_out || !n_bytes_out) return VGMI_E_INVALID;
+    if (read_filter_stats) memset(read_filter_stats, 0, 5 * sizeof(uint64_t));
+    vgh::ReadFilterParams rf = vgh::read_filter_params();
+    if (read_filter) {
+        if (const int bad = vgh::read_filter_invalid(read_filter->min_len, read_filter->max_len, read_filter->min_mean_q, read_filter->lowq_below,
+                                                     read_filter->lowq_max_pct)) {
+            g_err = vgh::read_filter_invalid_text(bad);
+            return VGMI_E_INVALID;
+        }
+        rf = vgh::read_filter_params(read_filter->min_len, read_filter->max_len, read_filter->min_mean_q, read_filter->lowq_below, read_filter->lowq_max_pct);
+    }
     if (bam_records) *bam_records = 0;
     if (bam_reads) *bam_reads = 0;
     if (min_base_quality > 93) {
@@ -274,13 +313,14 @@ int64_t vgh_reads_read_all_r(const char* path, uint32_t decode_threads, uint32_t
             vgh::BamReader rd(std::move(src), path, reg.on());
             rd.filter(vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value));
             if (reg.on()) rd.regions(vgh::resolve_bam_regions(reg, rd.ref_names(), path), reg.unplaced);
-            const int64_t n = reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
+            const int64_t n = reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number, &rf,
+                                          read_filter_stats);
             if (bam_records) *bam_records = rd.records();
             if (bam_reads) *bam_reads = rd.reads();
             return n;
         }
         vgh::FastxReader rd(std::move(src));
-        return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number);
+        return reads_block(rd, min_base_quality, block_out, n_bytes_out, read_base, masked_bases, &rule, first_number, next_number, &rf, read_filter_stats);
     } catch (const std::exception& e) {
         g_err = e.what();
         return VGMI_E_INVALID;
@@ -394,7 +434,29 @@ int vgh_sample_count_r(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fas
                        const char* bam_regions_bed, int bam_unplaced, uint64_t* reads_seen, uint64_t* reads_kept, uint64_t* masked_bases,
                        uint64_t* bam_records, uint64_t* bam_reads)
 {
+    return vgh_sample_count_l(h, ctx, fastq_paths, n_files, threads, sample_ploidy, use_depth, cov_out, cov_node_out, hist_out, stats,
+                              min_base_quality, fraction, seed, bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value, bam_regions,
+                              bam_regions_bed, bam_unplaced, nullptr, reads_seen, reads_kept, masked_bases, bam_records, bam_reads, nullptr);
+}
+
+int vgh_sample_count_l(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fastq_paths, size_t n_files, uint32_t threads,
+                       uint32_t sample_ploidy, int use_depth, uint8_t* cov_out, uint8_t* cov_node_out, uint64_t* hist_out,
+                       vgh_sample_stats* stats, uint32_t min_base_quality, double fraction, uint64_t seed, uint32_t bam_exclude,
+                       uint32_t bam_require, uint32_t bam_min_mapq, const char* bam_tag, double bam_min_value, const char* bam_regions,
+                       const char* bam_regions_bed, int bam_unplaced, const vgmi_read_filter* read_filter, uint64_t* reads_seen,
+                       uint64_t* reads_kept, uint64_t* masked_bases, uint64_t* bam_records, uint64_t* bam_reads, uint64_t* read_filter_stats)
+{
     if (!h || !ctx || (!fastq_paths && n_files)) return VGMI_E_INVALID;
+    if (read_filter_stats) memset(read_filter_stats, 0, 5 * sizeof(uint64_t));
+    vgh::ReadFilterParams rf = vgh::read_filter_params();
+    if (read_filter) {
+        if (const int bad = vgh::read_filter_invalid(read_filter->min_len, read_filter->max_len, read_filter->min_mean_q, read_filter->lowq_below,
+                                                     read_filter->lowq_max_pct)) {
+            g_err = vgh::read_filter_invalid_text(bad);
+            return VGMI_E_INVALID;
+        }
+        rf = vgh::read_filter_params(read_filter->min_len, read_filter->max_len, read_filter->min_mean_q, read_filter->lowq_below, read_filter->lowq_max_pct);
+    }
     if (masked_bases) *masked_bases = 0;
     if (reads_seen) *reads_seen = 0;
     if (reads_kept) *reads_kept = 0;
@@ -411,9 +473,13 @@ int vgh_sample_count_r(const vgh_graph* h, vgmi_ctx* ctx, const char* const* fas
         reg.list = bam_regions ? bam_regions : "";
         reg.bed = bam_regions_bed ? bam_regions_bed : "";
         reg.unplaced = bam_unplaced != 0;
-        vgh::FastqKmerHipR fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed,
-                              vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value), reg);
-        fk.build_fastq_index_regions();
+        vgh::FastqKmerHipL fk(ctx, files, h->g.k, threads, min_base_quality, fraction, seed,
+                              vgh::bam_filter_params(bam_exclude, bam_require, bam_min_mapq, bam_tag, bam_min_value), reg, rf);
+        fk.build_fastq_index_read_filter();
+        if (read_filter_stats) {
+            read_filter_stats[0] = fk.mReadNum;
+            for (int c = 0; c < 4; ++c) read_filter_stats[0] += fk.mReadsDropped[c], read_filter_stats[c + 1] = fk.mReadsDropped[c];
+        }
         if (masked_bases) *masked_bases = fk.mMaskedBases;
         if (reads_seen) *reads_seen = fk.mReadsSeen;
         if (reads_kept) *reads_kept = fk.mReadNum;

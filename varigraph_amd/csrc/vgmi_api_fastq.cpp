@@ -3,6 +3,7 @@
 #include "vgmi_ctx.h"
 
 #include "vgmi_bam_filter.h"
+#include "vgmi_read_filter.h"
 #include "vgmi_subsample.h"
 
 extern "C" {
@@ -71,6 +72,8 @@ struct vgmi_fastq {
     // once bytes have been committed.  The allocation (cap_regions intervals) stays with the stream's buffers
     vgh::BamInterval* d_regions = nullptr;
     uint32_t cap_regions = 0, n_regions = 0, regions_unplaced = 0;
+    // the read filter (vgmi_fastq_set_read_filter; the rule of vgmi_read_filter.h): on == 0 = off; fixed once bytes have been committed
+    vgh::ReadFilterParams rf = vgh::read_filter_params();
 };
 
 namespace {
@@ -141,6 +144,7 @@ int vgmi_fastq_open(vgmi_ctx* c, vgmi_fastq** out)
             r->sub_fraction = 1.0;
             r->filt = vgh::BamFilterParams{};
             r->n_regions = r->regions_unplaced = 0;
+            r->rf = vgh::read_filter_params();
             if (r->d_verdict) (void)hipMemsetAsync(r->d_verdict, 0xFF, 12, r->stream), (void)hipMemsetAsync(&r->d_verdict->good_bytes, 0, 8, r->stream);
             hipError_t e = launch_fastq_init(r->d_state, r->tail_max, r->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(r->stream, c->reset_done, 0);
@@ -254,6 +258,7 @@ hipError_t parse_chunk(vgmi_fastq* f, int i, uint32_t n_new, const uint32_t* n_n
     b.tail_max = f->tail_max;
     b.min_qual = f->min_quality ? 33u + f->min_quality : 0u;      // Phred+33
     b.sub = f->sub;
+    b.rf = f->fasta ? vgh::read_filter_params() : f->rf;      // (a FASTA stream has refused length bounds and has no qualities)
     if (!f->fasta) return launch_fastq_chunk(b, n_new, f->stream, n_new_dev);
     FaBuffers a{};
     a.q = b;
@@ -525,6 +530,7 @@ int vgmi_fastq_commit_bgzf(vgmi_fastq* f, size_t n_bytes, size_t* taken, size_t*
         bb.regions = f->d_regions;
         bb.n_regions = f->n_regions;
         bb.regions_unplaced = f->regions_unplaced;
+        bb.rf = f->rf;
         HIPCHK(c, launch_bam_chunk(bb, text, f->stream, &f->d_verdict->good_bytes));
         int rc = count_chunk(f, f->tail_max + (size_t)text);
         if (rc) return rc;
@@ -1001,6 +1007,42 @@ int vgmi_fastq_subsample_stats(vgmi_fastq* f, uint64_t* seen, uint64_t* kept)
     HIPCHK(c, hipMemcpy(&st, f->d_state, sizeof st, hipMemcpyDeviceToHost));
     *kept = st.n_records;
     *seen = f->sub.on ? st.n_seen : st.n_records;      // off: every read the device accepted is kept, and nothing numbers them
+    if (f->rf.on && !f->fasta) {      // with a read filter the kernels number the reads either way, and `kept` is subsampling's: the reads the filter evaluated
+        *kept = st.n_records + st.n_short + st.n_long + st.n_low_fraction + st.n_low_mean;
+        *seen = st.n_seen;
+    }
+    return VGMI_OK;
+}
+
+int vgmi_fastq_set_read_filter(vgmi_fastq* f, const vgmi_read_filter* r)
+{
+    if (!f || !r) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    if (const int bad = vgh::read_filter_invalid(r->min_len, r->max_len, r->min_mean_q, r->lowq_below, r->lowq_max_pct))
+        return fail(c, VGMI_E_INVALID, vgh::read_filter_invalid_text(bad));
+    if (f->committed) return fail(c, VGMI_E_STATE, "the read filter is set before the stream's first commit");
+    if (f->fasta && (r->min_len || r->max_len))
+        return fail(c, VGMI_E_INVALID, "a device FASTA stream takes no read-length bounds: a record's length is known only behind the scan (the host reader applies them)");
+    // all defaults: off, the stream that never called this; FASTA text has no qualities: quality-only parameters have no effect there
+    f->rf = f->fasta ? vgh::read_filter_params() : vgh::read_filter_params(r->min_len, r->max_len, r->min_mean_q, r->lowq_below, r->lowq_max_pct);
+    return VGMI_OK;
+}
+
+int vgmi_fastq_read_filter_stats(vgmi_fastq* f, uint64_t* evaluated, uint64_t* n_short, uint64_t* n_long, uint64_t* n_low_fraction, uint64_t* n_low_mean)
+{
+    if (!f || !evaluated || !n_short || !n_long || !n_low_fraction || !n_low_mean) return VGMI_E_INVALID;
+    vgmi_ctx* c = f->c;
+    *evaluated = *n_short = *n_long = *n_low_fraction = *n_low_mean = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(f->stream));
+    FqState st{};
+    HIPCHK(c, hipMemcpy(&st, f->d_state, sizeof st, hipMemcpyDeviceToHost));
+    *n_short = st.n_short;
+    *n_long = st.n_long;
+    *n_low_fraction = st.n_low_fraction;
+    *n_low_mean = st.n_low_mean;
+    // the reads subsampling kept among those the device accepted: the kept ones and the four classes (off: every accepted read, none dropped)
+    *evaluated = st.n_records + st.n_short + st.n_long + st.n_low_fraction + st.n_low_mean;
     return VGMI_OK;
 }
 

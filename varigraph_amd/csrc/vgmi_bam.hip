@@ -30,10 +30,13 @@
 // and B9 is bam_finish_filter_kernel / bam_finish_filter_sub_kernel; the kernels between run on the rec_bytes these leave.
 // With a region list (BamBuffers::regions; vgmi_fastq_set_bam_regions) B6 is bam_keep_region_kernel, the filter's B6 with the region test
 // in front of the tag walk; bam_cut_kernel and B9 as with a filter.
+// With a read filter (BamBuffers::rf; vgmi_fastq_set_read_filter, the rule in vgmi_read_filter.h) bam_read_filter_kernel runs in front of
+// B7 on the rec_bytes all of the above leave, and B9 is bam_finish_rf_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vgmi_bam_filter.h"
+#include "vgmi_read_filter.h"
 #include "vgmi_subsample.h"
 #include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
@@ -626,6 +629,119 @@ __global__ void bam_finish_filter_sub_kernel(const uint8_t* raw, FqState* st, Ba
     bam_finish_filter<true>(raw, st, bs, cand, rec_bytes, out_off, n_new, n_new_dev, cap, tail_max, n_ref);
 }
 
+// ---- the read filter (vgmi_read_filter.h), off the default path -----------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long bam_wave_sum64(unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Behind B6 in whichever form, bam_cut_kernel and bam_rank_kernel, in front of B7: one wavefront per candidate with rec_bytes != 0 -- a
+// read of the chain in front of any walk fault that subsampling kept, so an accepted one: the class counts go straight to the stream's.
+// The length tests first; with a quality test, B8's address arithmetic finds QUAL, a record whose QUAL[0] is 0xff passes (uniform over
+// the wavefront), lane i loads QUAL[i], and the sums are those of fq_read_quality_kernel with a table whose clamp is min(byte, 93).
+// A failing read's rec_bytes becomes 0, which B7 and B8 pass over; how many, for B9, in FqState::rf_dropped.
+__global__ __launch_bounds__(256) void bam_read_filter_kernel(const uint8_t* raw, FqState* st, const BamState* bs, const uint32_t* cand,
+                                                              uint32_t* rec_bytes, uint32_t cap, vgh::ReadFilterParams p)
+{
+    __shared__ uint32_t e_of[256];
+    __shared__ uint32_t sh[4];
+    const uint32_t n = bs->n_cand;
+    if (n > cap) return;   // (uniform)
+    e_of[threadIdx.x] = vgh::read_filter_e(vgh::read_filter_q_bam(threadIdx.x));      // (256 threads)
+    __syncthreads();
+    const bool quality = p.quality();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    uint32_t n_short = 0, n_long = 0, n_lf = 0, n_lm = 0;
+    for (uint32_t i = wave; i < n; i += n_waves) {
+        const uint32_t nb = rec_bytes[i];
+        if (!nb) continue;
+        const uint32_t l_seq = nb - 1;
+        int cls = vgh::read_filter_length_class(p, l_seq);
+        if (!cls && quality) {
+            const uint32_t o = cand[i];
+            const uint32_t s = o + 36u + raw[o + 12] + 4u * (bam_ld32(raw, o + 16) & 0xFFFFu);
+            const uint32_t q = s + (l_seq + 1u) / 2u;
+            if (raw[q] != 0xFFu) {      // (uniform over the wavefront)
+                unsigned long long sum = 0;
+                uint32_t low = 0;
+                for (uint32_t k = lane; k < l_seq; k += 64) {
+                    const uint32_t b = raw[q + k];
+                    sum += e_of[b];
+                    low += b < p.lowq_below;
+                }
+                sum = bam_wave_sum64(sum);
+                cls = vgh::read_filter_quality_class(p, l_seq, bam_wave_sum64(low), sum);
+            }
+        }
+        if (lane == 0 && cls) {
+            rec_bytes[i] = 0;
+            n_short += cls == vgh::READ_SHORT;
+            n_long += cls == vgh::READ_LONG;
+            n_lf += cls == vgh::READ_LOW_FRACTION;
+            n_lm += cls == vgh::READ_LOW_MEAN;
+        }
+    }
+    const uint32_t ts = block_reduce_add(n_short, sh), tl = block_reduce_add(n_long, sh);
+    const uint32_t tf = block_reduce_add(n_lf, sh), tm = block_reduce_add(n_lm, sh);
+    if (threadIdx.x) return;
+    if (ts) atomicAdd(&st->n_short, (unsigned long long)ts);
+    if (tl) atomicAdd(&st->n_long, (unsigned long long)tl);
+    if (tf) atomicAdd(&st->n_low_fraction, (unsigned long long)tf);
+    if (tm) atomicAdd(&st->n_low_mean, (unsigned long long)tm);
+    if (ts + tl + tf + tm) atomicAdd(&st->rf_dropped, ts + tl + tf + tm);
+}
+
+// B9 with a read filter, whatever else is set: bam_finish_filter's bookkeeping (without a record filter its sums stay 0 and nothing
+// faults), n_seen moves on by the chain's reads, and the reads the rule dropped leave n_records while n_seen and tot_reads stay the
+// passing records'
+__global__ void bam_finish_rf_kernel(const uint8_t* raw, FqState* st, BamState* bs, const uint32_t* cand, const uint32_t* rec_bytes,
+                                     const uint32_t* out_off, uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap, uint32_t tail_max, int32_t n_ref)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    const uint32_t end = bam_end(tail_max, n_new, n_new_dev);
+    uint32_t reads = 0, kept = 0, chain = 0, packed = 0, chain_end = st->start, tail = 0;
+    if (!st->stopped) {
+        const uint32_t n = bs->n_cand;
+        if (n > cap) {
+            st->stopped = 1;     // more candidates than the arrays hold: nothing of this chunk is taken, the host resumes at its first byte
+        } else {
+            if (bs->last != BAM_NONE) {
+                const uint32_t o = cand[bs->last];
+                chain_end = o + 4u + bam_ld32(raw, o);
+                reads = bs->n_kept;
+                chain = bs->n_chain;
+                kept = reads - bs->n_dropped - st->rf_dropped;
+                packed = out_off[n - 1] + rec_bytes[n - 1];
+            }
+            if (bs->first_fault != BAM_NONE) {
+                st->stopped = 1;     // the record at chain_end has auxiliary fields the walk cannot pass: the host names it
+            } else if (chain_end < end) {
+                // what follows the chain: the front of a record the next chunk completes, or something the host must judge
+                uint32_t block_size = 0;
+                const int r = bam_check(raw, chain_end, end, n_ref, &block_size);
+                if (r == 1 && (end - chain_end < 4u || block_size <= tail_max - 4u)) tail = end - chain_end;
+                else st->stopped = 1;     // not a valid record, or one longer than the carry (whole or not: never a candidate)
+            }
+        }
+    }
+    bs->n_dropped = 0;
+    bs->n_chain = 0;
+    bs->first_fault = BAM_NONE;
+    bs->tot_records += chain;
+    bs->tot_reads += reads;
+    st->rf_dropped = 0;
+    st->n_good = kept;
+    st->packed_bytes = packed;
+    st->n_seen += reads;
+    st->n_records += kept;
+    st->n_bases += packed - kept;
+    st->consumed += chain_end - st->start;
+    st->consumed_end = chain_end;
+    st->tail_len = tail;
+}
+
 // B10: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(256) void bam_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, BamState* bs, uint32_t tail_max)
 {
@@ -698,6 +814,8 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_rank_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.bam, b.block_sum, 1, b.cap_cand, b.sub.seed,
                            b.sub.threshold);
     }
+    if (b.rf.on)
+        hipLaunchKernelGGL(bam_read_filter_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.cap_cand, b.rf);
     hipLaunchKernelGGL(bam_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.bam, b.block_sum, b.out_off, 0, b.cap_cand);
     e = launch_scan_small(b.block_sum, n_rblk, nullptr, s);
     if (e != hipSuccess) return e;
@@ -706,7 +824,10 @@ hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, 
         hipLaunchKernelGGL(bam_decode_mask_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed,
                            b.cap_cand, b.min_qual);
     else hipLaunchKernelGGL(bam_decode_kernel, dim3(BAM_GRID), dim3(256), 0, s, b.raw, b.bam, b.cand, b.rec_bytes, b.out_off, b.packed, b.cap_cand);
-    if (filtered && b.sub.on)
+    if (b.rf.on)
+        hipLaunchKernelGGL(bam_finish_rf_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_cand,
+                           b.tail_max, b.n_ref);
+    else if (filtered && b.sub.on)
         hipLaunchKernelGGL(bam_finish_filter_sub_kernel, dim3(1), dim3(1), 0, s, b.raw, b.state, b.bam, b.cand, b.rec_bytes, b.out_off, n_new, n_new_dev,
                            b.cap_cand, b.tail_max, b.n_ref);
     else if (filtered)

@@ -31,9 +31,13 @@
 // With subsampling (FqBuffers::sub; vgmi_fastq_set_subsample) K4, K7 and K6 are their *_sub forms: record r of the chunk is read
 // FqState::n_seen + r of the file, a read the rule drops gets packed length 0, so the scan closes the block up over it, the copy skips
 // it, and the bookkeeping counts the kept records among the accepted ones.  Without it the chunk launches the kernels above.
+// With a read filter (FqBuffers::rf; vgmi_fastq_set_read_filter, the rule in vgmi_read_filter.h) K4 is fq_records_rf_kernel -- subsampling
+// where it is on, then the two length tests -- with a quality test fq_read_quality_kernel runs between K4 and K5 and turns the packed
+// length of a failing read to 0, K7 is fq_finish_rf_kernel and K6 the subsampling form.  Without it nothing of this is launched.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vgmi_read_filter.h"
 #include "vgmi_subsample.h"
 #include "vgmi_block_scan.h"
 #include "vgmi_kernels.h"
@@ -370,6 +374,137 @@ __global__ __launch_bounds__(256) void fq_pack_sub_kernel(const uint8_t* raw, Fq
     if (threadIdx.x == 0 && t) atomicAdd(&st->n_masked, (unsigned long long)t);
 }
 
+// ---- the read filter (vgmi_read_filter.h): K4 and K7 again and a kernel between K4 and K5, off the default path --------------------------
+// K4: the same checks; a record that subsampling (where it is on) or a length test drops has packed length 0.  No quality byte is
+// loaded here: with length bounds alone this is the whole filter.
+__global__ __launch_bounds__(256) void fq_records_rf_kernel(const uint8_t* raw, FqState* st, const uint32_t* nlpos, uint32_t* rec_bytes,
+                                                            uint32_t cap_lines, SubParams sub, vgh::ReadFilterParams p)
+{
+    if (st->stopped || st->dirty || st->n_lines > cap_lines) return;
+    const uint32_t R = st->n_lines >> 2;
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const uint32_t s0 = r ? nlpos[4 * r - 1] + 1 : st->start;
+    const uint32_t e0 = nlpos[4 * r], e1 = nlpos[4 * r + 1], e2 = nlpos[4 * r + 2], e3 = nlpos[4 * r + 3];
+    const uint32_t len = e1 - e0 - 1;
+    const uint32_t c1 = raw[e0 + 1];
+    const bool ok = raw[s0] == '@' && len >= 1 && c1 != '@' && c1 != '+' && c1 != '>' && raw[e1 + 1] == '+' && e3 - e2 - 1 == len;
+    const bool keep = (!sub.on || vgh::subsample_keep(st->n_seen + r, sub.seed, sub.threshold)) && vgh::read_filter_length_class(p, len) == vgh::READ_PASS;
+    rec_bytes[r] = keep ? len + 1 : 0u;
+    if (!ok) atomicMin(&st->first_bad, r);
+}
+
+// the sum of a 64-bit value over the wavefront, in every lane
+__device__ __forceinline__ unsigned long long fq_wave_sum64(unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Between K4 and K5, with a quality test set: shaped like K6, one wavefront per record, lane i loads quality byte q + i; every lane
+// keeps a 64-bit sum of E and a 32-bit count of the low bases, the wavefront adds them up by shuffles and lane 0 decides: a failing
+// read's packed length becomes 0.  E of a quality BYTE comes from a 256-entry LDS table, the clamp folded in (base: 33 for FASTQ
+// text); q < lowq_below is byte < 33 + lowq_below for every byte (a byte below 33 is quality 0, one above 126 is 93 >= the bound).
+// Only records below first_bad are touched -- first_bad is final once K4 has finished, and from there on nobody has checked that
+// line 4 has the sequence's length -- and of those only the ones K4 kept.  They are the chunk's accepted records (K7: good =
+// min(first_bad, R) on a chunk that is not stopped, dirty or over capacity), so the class counts go straight to the stream's.
+__global__ __launch_bounds__(256) void fq_read_quality_kernel(const uint8_t* raw, FqState* st, const uint32_t* nlpos, uint32_t* rec_bytes,
+                                                              uint32_t cap_lines, vgh::ReadFilterParams p)
+{
+    __shared__ uint32_t e_of[256];
+    __shared__ uint32_t sh[4];
+    if (st->stopped || st->dirty || st->n_lines > cap_lines) return;      // (uniform)
+    e_of[threadIdx.x] = vgh::read_filter_e(vgh::read_filter_q_fastq(threadIdx.x));      // (256 threads)
+    __syncthreads();
+    const uint32_t R = st->n_lines >> 2, first_bad = st->first_bad;
+    const uint32_t good = first_bad < R ? first_bad : R;
+    const uint32_t low_byte = p.lowq_below ? 33u + p.lowq_below : 0u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    uint32_t n_lf = 0, n_lm = 0;
+    for (uint32_t r = wave; r < good; r += n_waves) {
+        const uint32_t nb = rec_bytes[r];
+        if (!nb) continue;                                           // (uniform over the wavefront)
+        const uint32_t len = nb - 1, q = nlpos[4 * r + 2] + 1;        // [q, q + len) = its qualities (K4's check)
+        unsigned long long sum = 0;
+        uint32_t low = 0;
+        for (uint32_t i = lane; i < len; i += 64) {
+            const uint32_t b = raw[q + i];
+            sum += e_of[b];
+            low += b < low_byte;
+        }
+        sum = fq_wave_sum64(sum);
+        const unsigned long long n_low = fq_wave_sum64(low);
+        const int cls = vgh::read_filter_quality_class(p, len, n_low, sum);
+        if (lane == 0 && cls) {
+            rec_bytes[r] = 0;
+            n_lf += cls == vgh::READ_LOW_FRACTION;
+            n_lm += cls == vgh::READ_LOW_MEAN;
+        }
+    }
+    const uint32_t tf = block_reduce_add(n_lf, sh);
+    const uint32_t tm = block_reduce_add(n_lm, sh);
+    if (threadIdx.x == 0 && tf) atomicAdd(&st->n_low_fraction, (unsigned long long)tf);
+    if (threadIdx.x == 0 && tm) atomicAdd(&st->n_low_mean, (unsigned long long)tm);
+}
+
+// K7: fq_finish_sub_kernel's bookkeeping, and the accepted records a length test dropped are counted by class: such a record has packed
+// length 0, was kept by subsampling (evaluated again where it is on) and fails a length test (the quality kernel has counted its own)
+__global__ __launch_bounds__(1024) void fq_finish_rf_kernel(FqState* st, const uint32_t* nlpos, const uint32_t* rec_bytes, const uint32_t* out_off,
+                                                           uint32_t n_new, const uint32_t* n_new_dev, uint32_t cap_lines, uint32_t tail_max,
+                                                           SubParams sub, vgh::ReadFilterParams p)
+{
+    __shared__ uint32_t sh[16];
+    const uint32_t end = fq_end(tail_max, n_new, n_new_dev);
+    const bool stopped = st->stopped, unfit = st->dirty || st->n_lines > cap_lines;
+    const uint32_t R = st->n_lines >> 2, first_bad = st->first_bad;
+    const unsigned long long n_seen = st->n_seen;
+    uint32_t good = 0;
+    if (!stopped && !unfit) good = first_bad < R ? first_bad : R;
+    uint32_t mine = 0, n_short = 0, n_long = 0;
+    for (uint32_t r = threadIdx.x; r < good; r += blockDim.x) {
+        if (rec_bytes[r]) {
+            ++mine;
+            continue;
+        }
+        if (sub.on && !vgh::subsample_keep(n_seen + r, sub.seed, sub.threshold)) continue;
+        const int cls = vgh::read_filter_length_class(p, nlpos[4 * r + 1] - nlpos[4 * r] - 1);
+        n_short += cls == vgh::READ_SHORT;
+        n_long += cls == vgh::READ_LONG;
+    }
+    const uint32_t kept = block_reduce_add(mine, sh);      // (its barriers: every thread has read the state before thread 0 writes it)
+    const uint32_t t_short = block_reduce_add(n_short, sh);
+    const uint32_t t_long = block_reduce_add(n_long, sh);
+    if (threadIdx.x) return;
+    uint32_t consumed_end = st->start, packed = 0;
+    if (!stopped) {
+        if (unfit) {
+            st->stopped = 1;     // nothing of this chunk is taken: the host reader resumes at its first byte
+        } else {
+            if (first_bad < R) st->stopped = 1;
+            if (good) {
+                consumed_end = nlpos[4 * good - 1] + 1;
+                packed = out_off[good - 1] + rec_bytes[good - 1];
+            }
+        }
+    }
+    st->n_good = good;
+    st->packed_bytes = packed;
+    st->n_seen = n_seen + good;
+    st->n_records += kept;
+    st->n_short += t_short;
+    st->n_long += t_long;
+    st->n_bases += packed - kept;
+    st->consumed += consumed_end - st->start;
+    st->consumed_end = consumed_end;
+    uint32_t tail = st->stopped ? 0u : end - consumed_end;
+    if (tail > tail_max) {      // a "record" longer than the carry buffer: not a short-read FASTQ
+        st->stopped = 1;
+        tail = 0;
+    }
+    st->tail_len = tail;
+}
+
 // K8: the unconsumed tail goes in front of the next chunk's landing area, and the per-chunk state is re-armed
 __global__ __launch_bounds__(256) void fq_carry_kernel(const uint8_t* raw, uint8_t* raw_next, FqState* st, uint32_t tail_max)
 {
@@ -425,13 +560,25 @@ hipError_t launch_fastq_chunk(const FqBuffers& b, uint32_t n_new, hipStream_t s,
     hipLaunchKernelGGL(fq_count_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.tile);
     hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, b.tile, n_tiles, &b.state->n_lines);
     hipLaunchKernelGGL(fq_nlpos_kernel, dim3(n_tiles), dim3(256), 0, s, b.raw, b.state, b.tail_max, n_new, n_new_dev, b.tile, b.nlpos, b.cap_lines);
-    if (b.sub.on)
+    if (b.rf.on) {
+        hipLaunchKernelGGL(fq_records_rf_kernel, dim3((cap_rec + 255u) / 256u), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines, b.sub,
+                           b.rf);
+        if (b.rf.quality())
+            hipLaunchKernelGGL(fq_read_quality_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines, b.rf);
+    } else if (b.sub.on)
         hipLaunchKernelGGL(fq_records_sub_kernel, dim3((cap_rec + 255u) / 256u), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines,
                            b.sub.seed, b.sub.threshold);
     else hipLaunchKernelGGL(fq_records_kernel, dim3((cap_rec + 255u) / 256u), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.cap_lines);
     hipLaunchKernelGGL(fq_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.block_sum, b.out_off, 0, b.cap_lines);
     hipLaunchKernelGGL(fq_scan_small_kernel, dim3(1), dim3(1024), 0, s, b.block_sum, n_rblk, (uint32_t*)nullptr);
     hipLaunchKernelGGL(fq_scan_blocks_kernel, dim3(n_rblk), dim3(1024), 0, s, b.rec_bytes, b.state, b.block_sum, b.out_off, 1, b.cap_lines);
+    if (b.rf.on) {      // the kept records are those with rec_bytes != 0: the copy is the subsampling form's
+        hipLaunchKernelGGL(fq_finish_rf_kernel, dim3(1), dim3(1024), 0, s, b.state, b.nlpos, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_lines,
+                           b.tail_max, b.sub, b.rf);
+        hipLaunchKernelGGL(fq_pack_sub_kernel, dim3(2048), dim3(256), 0, s, b.raw, b.state, b.nlpos, b.rec_bytes, b.out_off, b.packed, b.min_qual);
+        hipLaunchKernelGGL(fq_carry_kernel, dim3(1), dim3(256), 0, s, b.raw, b.raw_next, b.state, b.tail_max);
+        return hipGetLastError();
+    }
     if (b.sub.on) {
         hipLaunchKernelGGL(fq_finish_sub_kernel, dim3(1), dim3(1024), 0, s, b.state, b.nlpos, b.rec_bytes, b.out_off, n_new, n_new_dev, b.cap_lines,
                            b.tail_max);

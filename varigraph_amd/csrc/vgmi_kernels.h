@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "vgmi_bam_filter.h"
+#include "vgmi_read_filter.h"
 #include "vgmi_count_plan.h"
 #include "vgmi_ctable.h"
 #include "vgmi_device.h"
@@ -143,6 +144,11 @@ struct FqState {                       // device-resident, one per open stream
                                        // those subsampling drops; BAM: the reads counted into n_records.  Nothing reads it after the chunk)
     unsigned long long n_seen;         // subsampling only (SubParams; 0 without it): reads numbered so far since the stream was opened, kept or
                                        // not -- the file number of this chunk's first read.  Last, so that every other field stays where it was
+    // with a read filter only (vgh::ReadFilterParams; vgmi_fastq_set_read_filter; 0 without it), last for the same reason: the reads among the
+    // accepted ones that subsampling kept and the rule dropped, by class, since the stream was opened
+    unsigned long long n_short, n_long, n_low_fraction, n_low_mean;
+    uint32_t rf_dropped;               // per chunk, BAM only: reads the rule's kernel dropped (B9 takes them out of n_records and re-arms it)
+    uint32_t rf_pad;
 };
 // Subsampling (vgmi_fastq_set_subsample): read i of the file is kept iff subsample_keep(i, seed, threshold) (vgmi_subsample.h).  A
 // dropped read is not a read: it adds nothing to the read block, n_records or n_bases.  on == 0: the chunk launches the kernels it
@@ -164,6 +170,7 @@ struct FqBuffers {
     uint32_t cap_lines, tail_max;
     uint32_t min_qual;                 // 0: off; else a base whose quality byte is below it (Phred+33: 33 + Q) is packed as 'N'
     SubParams sub;                     // rec_bytes of a dropped record is 0
+    vgh::ReadFilterParams rf;          // on == 0: off; else rec_bytes of a read that fails the rule of vgmi_read_filter.h is 0
 };
 hipError_t launch_fastq_init(FqState* st, uint32_t tail_max, hipStream_t s);
 // n_new_dev (may be null): the chunk is cut to min(n_new, *n_new_dev) bytes on the device (text in front of a block-gzip
@@ -227,6 +234,7 @@ struct BamBuffers {
     const vgh::BamInterval* regions;
     uint32_t n_regions;
     uint32_t regions_unplaced;         // refID == -1 passes the region test
+    vgh::ReadFilterParams rf;          // on == 0: off; else bam_read_filter_kernel turns rec_bytes of a read that fails the rule to 0 before the scan
 };
 hipError_t launch_bam_init(BamState* bs, unsigned long long header_bytes, hipStream_t s);
 hipError_t launch_bam_chunk(const BamBuffers& b, uint32_t n_new, hipStream_t s, const uint32_t* n_new_dev = nullptr);

@@ -80,6 +80,16 @@ def lib():
     l.vgh_reads_read_all_r.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_char_p, C.c_double, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp),
                                        C.POINTER(C.c_size_t)] + [C.POINTER(C.c_uint64)] * 5
+    l.vgh_sample_count_l.restype = C.c_int
+    l.vgh_sample_count_l.argtypes = l.vgh_sample_count.argtypes + [C.c_uint32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                   C.c_char_p, C.c_double, C.c_char_p, C.c_char_p, C.c_int,
+                                                                   C.POINTER(vgmi.ReadFilter)] + [C.POINTER(C.c_uint64)] * 6
+    l.vgh_reads_read_all_l.restype = C.c_int64
+    l.vgh_reads_read_all_l.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_char_p, C.c_double, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vgmi.ReadFilter),
+                                       C.POINTER(vp), C.POINTER(C.c_size_t)] + [C.POINTER(C.c_uint64)] * 6
+    l.vgh_parse_quality_tenths.restype = C.c_int
+    l.vgh_parse_quality_tenths.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
     l.vgh_reads_read_all_f.restype = C.c_int64
     l.vgh_reads_read_all_f.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_char_p, C.c_double, C.POINTER(vp), C.POINTER(C.c_size_t)] + [C.POINTER(C.c_uint64)] * 5
@@ -175,7 +185,7 @@ class Graph:
         return cov, rb.value
 
     def sample_count(self, ctx, fastq_paths, threads=4, sample_ploidy=2, use_depth=False, require_depth=True, min_base_quality=0,
-                     subsample=None, bam_filter=None, bam_regions=None, bam_regions_bed=None, bam_unplaced=False):
+                     subsample=None, bam_filter=None, bam_regions=None, bam_regions_bed=None, bam_unplaced=False, read_filter=None):
         """FastqKmerHip::build_fastq_index + coverage statistics for one sample.  require_depth=False: a sample too thin
         for the coverage peak (the reference exits with "Failed to retrieve depth information") still returns its
         counters.  min_base_quality: bases of FASTQ / BAM reads whose quality is below it are counted as N (vgh_sample_count_q);
@@ -184,7 +194,9 @@ class Graph:
         bam_filter=dict(exclude=0x900, require=0, min_mapq=0, tag=None, min_value=0.0), any key optional: the read filter of BAM files
         (vgh_sample_count_f); stats then has bam_records and bam_reads.  bam_regions="NAME,NAME:BEG-END,...", bam_regions_bed=a BED
         file's path, bam_unplaced: the regions of BAM files (vgh_sample_count_r), alone or with bam_filter; stats has bam_records and
-        bam_reads then too."""
+        bam_reads then too.  read_filter=dict(min_len, max_len, min_mean_q (tenths), lowq_below, lowq_max_pct), any key optional: the
+        read filter by length and read quality (vgh_sample_count_l), with any of the above; stats then has read_filter_stats =
+        (evaluated, short, long, low fraction, low mean).  Without it the calls are those of before."""
         i = self.info
         cov = np.empty(i["n_keys"], dtype=np.uint8)
         cov_node = np.empty(i["n_node_entries"], dtype=np.uint8)
@@ -194,7 +206,15 @@ class Graph:
         masked, seen, kept = C.c_uint64(), C.c_uint64(), C.c_uint64()
         recs, rds = C.c_uint64(), C.c_uint64()
         regions = bam_regions is not None or bam_regions_bed is not None or bam_unplaced
-        if regions:
+        rfs = (C.c_uint64 * 5)()
+        if read_filter is not None:
+            f, fs = bam_filter_args(bam_filter or {}), subsample if subsample is not None else (1.0, 0)
+            rf = vgmi.read_filter_struct(read_filter)
+            rc = self._l.vgh_sample_count_l(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
+                                            vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
+                                            float(fs[0]), int(fs[1]), *f, *_region_args(bam_regions, bam_regions_bed), int(bool(bam_unplaced)),
+                                            C.byref(rf), C.byref(seen), C.byref(kept), C.byref(masked), C.byref(recs), C.byref(rds), rfs)
+        elif regions:
             f, fs = bam_filter_args(bam_filter or {}), subsample if subsample is not None else (1.0, 0)
             rc = self._l.vgh_sample_count_r(self._h, ctx._h, arr, len(fastq_paths), threads, sample_ploidy, int(use_depth),
                                             vgmi._ptr(cov), vgmi._ptr(cov_node), vgmi._ptr(hist), C.byref(st), min_base_quality,
@@ -225,6 +245,8 @@ class Graph:
             stats["reads_seen"], stats["reads_kept"] = seen.value, kept.value
         if bam_filter is not None or regions:
             stats["bam_records"], stats["bam_reads"] = recs.value, rds.value
+        if read_filter is not None:
+            stats["read_filter_stats"] = tuple(int(v) for v in rfs)
         return cov, cov_node, hist, stats
 
 
@@ -397,6 +419,36 @@ def reads_read_all_r(path, bam_regions=None, bam_regions_bed=None, bam_unplaced=
     finally:
         l.vgh_free(p)
     return block, int(cnt), rb.value, mb.value, nx.value, rc.value, rd.value
+
+
+def reads_read_all_l(path, read_filter, bam_regions=None, bam_regions_bed=None, bam_unplaced=False, bam_filter=None, fraction=1.0, seed=11,
+                     first_number=0, min_base_quality=0, decode_threads=1):
+    """A file through the host reader with the read filter by length and read quality (vgh_reads_read_all_l; read_filter: the dict of
+    Graph.sample_count, or None), with or without the others: the tuple of reads_read_all_f + (read_filter_stats,), the 5 values
+    (evaluated, short, long, low fraction, low mean)."""
+    l = lib()
+    p, n, rb, mb, nx, rc, rd = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rfs = (C.c_uint64 * 5)()
+    rf = None if read_filter is None else C.byref(vgmi.read_filter_struct(read_filter))
+    cnt = l.vgh_reads_read_all_l(os.fsencode(path), decode_threads, min_base_quality, fraction, seed, first_number,
+                                 *bam_filter_args(bam_filter or {}), *_region_args(bam_regions, bam_regions_bed), int(bool(bam_unplaced)), rf,
+                                 C.byref(p), C.byref(n), C.byref(rb), C.byref(mb), C.byref(nx), C.byref(rc), C.byref(rd), rfs)
+    if cnt < 0:
+        raise RuntimeError(l.vgh_last_error().decode())
+    try:
+        block = _arr(p.value, n.value, np.uint8)
+    finally:
+        l.vgh_free(p)
+    return block, int(cnt), rb.value, mb.value, nx.value, rc.value, rd.value, tuple(int(v) for v in rfs)
+
+
+def parse_quality_tenths(text):
+    """--min-read-quality's text as tenths (vgh_parse_quality_tenths); ValueError for what the CLI refuses"""
+    l = lib()
+    t = C.c_uint32()
+    if l.vgh_parse_quality_tenths(os.fsencode(text), C.byref(t)):
+        raise ValueError(l.vgh_last_error().decode())
+    return t.value
 
 
 def sniff_input(path):

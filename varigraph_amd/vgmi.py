@@ -11,6 +11,17 @@ OK = 0
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_DUPLICATE_KEY, E_BAD_KEY, E_EMPTY_READ, E_NOMEM = range(-1, -9, -1)
 
 
+class ReadFilter(C.Structure):
+    """vgmi_read_filter (include/vgmi.h): the read filter by length and read quality; min_mean_q in tenths of a Phred unit"""
+    _fields_ = [("min_len", C.c_uint32), ("max_len", C.c_uint32), ("min_mean_q", C.c_uint32), ("lowq_below", C.c_uint32),
+                ("lowq_max_pct", C.c_uint32)]
+
+
+def read_filter_struct(read_filter):
+    """dict(min_len, max_len, min_mean_q, lowq_below, lowq_max_pct; any key optional, 0 = off) -> ReadFilter"""
+    return ReadFilter(*[int(read_filter.get(f[0], 0)) for f in ReadFilter._fields_])
+
+
 class VgmiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"vgmi error {code}: {msg}")
@@ -83,6 +94,8 @@ def load_library():
         "vgmi_fastq_masked_bases": (i32, [vp, C.POINTER(u64)]),
         "vgmi_fastq_set_subsample": (i32, [vp, C.c_double, u64]),
         "vgmi_fastq_subsample_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "vgmi_fastq_set_read_filter": (i32, [vp, C.POINTER(ReadFilter)]),
+        "vgmi_fastq_read_filter_stats": (i32, [vp] + [C.POINTER(u64)] * 5),
         "vgmi_fastq_set_bam_filter": (i32, [vp, u32, u32, u32, C.c_char_p, C.c_double]),
         "vgmi_fastq_bam_filter_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "vgmi_fastq_set_bam_regions": (i32, [vp, u32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
@@ -216,6 +229,7 @@ class Context:
         self._quality_streams = set()      # open streams on which vgmi_fastq_set_min_quality was called
         self._subsample_streams = set()    # open streams on which vgmi_fastq_set_subsample was called
         self._filter_streams = set()       # open streams on which vgmi_fastq_set_bam_filter was called
+        self._read_filter_streams = set()  # open streams on which vgmi_fastq_set_read_filter was called
 
     def close(self):
         if getattr(self, "_h", None):
@@ -360,15 +374,23 @@ class Context:
         self._chk(self._l.vgmi_pt_live_check(self._h, out))
         return tuple(int(v) for v in out)
 
-    def fastq_text(self, text, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None):
+    def fastq_text(self, text, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None, read_filter=None,
+                   read_filter_first=False):
         """Device-side FASTQ parser over one stream of file text (bytes), committed in pieces of `piece` bytes (default:
         whole staging buffers; a list or tuple gives a size per commit, the last one from there on).  min_quality: bases whose quality is below it are counted as N (vgmi_fastq_set_min_quality; 0 = off).
         subsample=(F, S): a seeded fraction of the reads is kept (vgmi_fastq_set_subsample); the dict then has n_seen, the reads the
-        device numbered, and n_records counts the kept ones.  Returns dict(n_records, n_bases, consumed, stopped, tail, masked_bases)."""
+        device numbered, and n_records counts the kept ones.  read_filter=dict(min_len, max_len, min_mean_q (tenths), lowq_below,
+        lowq_max_pct) or a list of such dicts, set in order: the read filter (vgmi_fastq_set_read_filter), behind the other setters or
+        with read_filter_first in front of them; the dict then has read_filter_stats = (evaluated, short, long, low fraction, low
+        mean).  Returns dict(n_records, n_bases, consumed, stopped, tail, masked_bases)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
+        if read_filter_first:
+            self._set_read_filter(fq, read_filter)
         self._set_options(fq, min_quality, subsample, subsample_first)
         self._set_bam_filter(fq, bam_filter)      # (accepted without effect: the text has no BAM records)
+        if not read_filter_first:
+            self._set_read_filter(fq, read_filter)
         return self._text_stream(fq, text, piece)
 
     def _set_min_quality(self, fq, min_quality):
@@ -424,6 +446,21 @@ class Context:
                 raise VgmiError(rc, msg)
         self._filter_streams.add(fq.value)
 
+    def _set_read_filter(self, fq, read_filter):
+        """vgmi_fastq_set_read_filter on a stream just opened; a refusal closes the stream and raises.  None (the default) does not
+        call the C entry at all.  A dict calls it once, a list of dicts once per dict, in order: the last value set holds -- [{...}, {}]
+        is how the tests show that the all-default struct is the stream of no call."""
+        if read_filter is None:
+            return
+        for f in [read_filter] if isinstance(read_filter, dict) else read_filter:
+            r = read_filter_struct(f)
+            rc = self._l.vgmi_fastq_set_read_filter(fq, C.byref(r))
+            if rc:
+                msg = self._l.vgmi_last_error(self._h).decode()
+                self._l.vgmi_fastq_close(fq, None, None, None, None, None, 0, None)
+                raise VgmiError(rc, msg)
+        self._read_filter_streams.add(fq.value)
+
     def _set_bam_regions(self, fq, bam_regions, bam_unplaced):
         """vgmi_fastq_set_bam_regions on a stream just opened; a refusal closes the stream and raises.  None (the default) does not call
         the C entry at all; a list of (ref, beg, end), 0-based half-open, in any order, calls it once -- the empty list too."""
@@ -458,6 +495,11 @@ class Context:
             res["filter_stats_rc"] = rc      # VGMI_E_STATE: the stream has no filter (every parameter at its default, or not a BAM stream)
             res["bam_records"] = recs.value if rc == 0 else None
             res["bam_reads"] = reads.value if rc == 0 else None
+        if fq.value in self._read_filter_streams:
+            self._read_filter_streams.discard(fq.value)
+            v = [C.c_uint64() for _ in range(5)]
+            rc = self._l.vgmi_fastq_read_filter_stats(fq, *[C.byref(x) for x in v])
+            res["read_filter_stats"] = tuple(x.value for x in v) if rc == 0 else None
         return res
 
     def _masked_bases(self, fq):
@@ -468,13 +510,14 @@ class Context:
         n = C.c_uint64()
         return n.value if self._l.vgmi_fastq_masked_bases(fq, C.byref(n)) == 0 else None
 
-    def fasta_text(self, text, piece=None, subsample=None, bam_filter=None):
+    def fasta_text(self, text, piece=None, subsample=None, bam_filter=None, read_filter=None):
         """Device-side FASTA parser (vgmi_fastq_open_fasta) over one stream of file text, as fastq_text.  The last record of the text
         is never taken by the device: it comes back as `tail`, from its header line on."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open_fasta(self._h, C.byref(fq)))
         self._set_subsample(fq, subsample)
         self._set_bam_filter(fq, bam_filter)
+        self._set_read_filter(fq, read_filter)      # (quality-only fields: accepted without effect; length bounds: refused)
         return self._text_stream(fq, text, piece)
 
     def _text_stream(self, fq, text, piece):
@@ -505,12 +548,13 @@ class Context:
         return {"n_records": nr.value, "n_bases": nb.value, "consumed": cons.value, "stopped": bool(st.value),
                 "tail": tail.raw[:tl.value], "masked_bases": masked, **sub}
 
-    def fastq_bgzf(self, comp, piece=None, min_quality=0, subsample=None):
+    def fastq_bgzf(self, comp, piece=None, min_quality=0, subsample=None, read_filter=None):
         """Block-gzip bytes through the device inflate + parser.  Returns the dict of fastq_text plus inflate_failed,
         good_compressed_bytes, taken (compressed bytes handed over as whole members)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
         self._set_options(fq, min_quality, subsample)
+        self._set_read_filter(fq, read_filter)
         return self._bgzf_stream(fq, comp, piece)
 
     def fasta_bgzf(self, comp, piece=None, subsample=None):
@@ -521,7 +565,7 @@ class Context:
         return self._bgzf_stream(fq, comp, piece)
 
     def bam_bgzf(self, comp, header_bytes, n_ref, piece=None, min_quality=0, subsample=None, subsample_first=False, bam_filter=None,
-                 filter_order=0, bam_regions=None, bam_unplaced=False, regions_first=False):
+                 filter_order=0, bam_regions=None, bam_unplaced=False, regions_first=False, read_filter=None, read_filter_first=False):
         """A BAM file's block-gzip bytes through the device inflate + BAM record kernels (vgmi_fastq_open_bam): header_bytes = the
         header's length in the decompressed stream (magic to the last reference), n_ref its number of references.  Returns the dict of fastq_bgzf; consumed
         counts decompressed bytes, header included."""
@@ -531,6 +575,10 @@ class Context:
         # setter in front of, between or behind the other two
         # bam_regions=[(ref, beg, end), ...], bam_unplaced: the region list (vgmi_fastq_set_bam_regions), set behind the other setters or,
         # with regions_first, in front of them
+        # read_filter: the read filter by length and read quality (vgmi_fastq_set_read_filter), behind every other setter or, with
+        # read_filter_first, in front of them
+        if read_filter_first:
+            self._set_read_filter(fq, read_filter)
         if regions_first:
             self._set_bam_regions(fq, bam_regions, bam_unplaced)
         if filter_order == 0:
@@ -545,6 +593,8 @@ class Context:
             self._set_bam_filter(fq, bam_filter)
         if not regions_first:
             self._set_bam_regions(fq, bam_regions, bam_unplaced)
+        if not read_filter_first:
+            self._set_read_filter(fq, read_filter)
         return self._bgzf_stream(fq, comp, piece)
 
     def _bgzf_stream(self, fq, comp, piece):
@@ -583,12 +633,13 @@ class Context:
                 "tail": tail.raw[:tl.value], "masked_bases": masked, "inflate_failed": bool(failed.value), "good_compressed_bytes": good.value,
                 "reason": reason.value, "taken": total_taken, **sub}
 
-    def fastq_gzip(self, comp, piece=None, min_quality=0, subsample=None):
+    def fastq_gzip(self, comp, piece=None, min_quality=0, subsample=None, read_filter=None):
         """Ordinary gzip bytes through the device inflate + parser (vgmi_fastq_commit_gzip).  Returns the dict of fastq_text plus stop
         (1 data over, 2 the device gave up), device_text_bytes, reason, taken (compressed bytes used up)."""
         fq = C.c_void_p()
         self._chk(self._l.vgmi_fastq_open(self._h, C.byref(fq)))
         self._set_options(fq, min_quality, subsample)
+        self._set_read_filter(fq, read_filter)
         return self._gzip_stream(fq, comp, piece)
 
     def fasta_gzip(self, comp, piece=None, subsample=None):
